@@ -10,7 +10,11 @@ bk1*tk*U(0,1) seed 4; options as the Class 1 driver (smoth 5, theta 1/4, bigph 1
 isnsp 1), cycle 'v'.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--rho R] [--cycle v|w]
-                  [--mask bernoulli|tree] [--n1 1024] [--no-cpu-baseline]
+                  [--mask bernoulli|tree] [--n1 1024] [--no-cpu-baseline] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the timed path hands back after its last step -- the iterate x of
+ipd_amg_bench_cycles(_sharded) -- as DIR/x.npy (float64).  The inputs depend on the arguments
+only (fixed seeds), so two builds run with the same arguments can be compared output for output.
 
 N>1 is launched by `python -m torch.distributed.run --nproc-per-node N ...`
 (one rank per GPU): `--mode sharded` (default) runs ONE system row-block sharded
@@ -33,6 +37,21 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec); ~6.3 TB/s achievable
 HANDOFF_FLOOR_US = 1.0  # MI355X_MICROARCH.md, table row `handoff-1to1`: an idle tagged-granule hand-off, 0.8-1.0 us
 BK1, TK = 0.0038, 0.0255
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(d, arrays, limit=DUMP_BYTES_MAX):
+    """Writes every array as d/<name>.npy in float64.  An array larger than its share of `limit` is
+    replaced by a fixed sample: its entries at sorted indices drawn with seed 0, the same entries on
+    every run of the same arguments."""
+    os.makedirs(d, exist_ok=True)
+    share = limit // max(len(arrays), 1) - 4096      # room for the .npy header
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        k = max(share // a.itemsize, 1)
+        if a.size > k:
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def build_mask(m, n, kind, rho, seed=2):
@@ -247,7 +266,11 @@ def main():
     ap.add_argument("--no-poly2", action="store_true",
                     help="level 2 of the resident kernel as sweeps (33 hand-offs per V cycle) instead of the "
                          "composed polynomial form (24)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the iterate they computed as DIR/x.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # invoked plainly (`python bench.py --gpus N`): start the ranks ourselves, as a CHILD
@@ -387,6 +410,8 @@ def main():
     replicas_result = None
     if sharded:
         wall, ev_ms, bytes_per_cycle = timed(_lib.lib.ipd_amg_bench_cycles_sharded)
+        # the replicas timing below goes on from this iterate: keep what the sharded path computed
+        x_timed = dx.to_array(np.float64, M) if args.dump_outputs else None
         ag, agv = c_int64(), c_int64()
         from ctypes import c_int32 as _ci32
         _lib.check(_lib.lib.ipd_comm_stats(ctx.handle, None, None, byref(ag), byref(agv), _ci32(0)))
@@ -400,6 +425,7 @@ def main():
                            "parallelism": "replicas x%d (independent systems, no collective)" % world}
     else:
         wall, ev_ms, bytes_per_cycle = timed(_lib.lib.ipd_amg_bench_cycles)
+        x_timed = None
 
     batched = None
     if args.batch > 1 and world == 1:
@@ -442,6 +468,8 @@ def main():
     # (warm-up + timed loop bodies, Class_AMG.m:103-104); a run that does not contract is an error
     from ctypes import c_int32 as _ci32
     x_end = dx.to_array(np.float64, M)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x": x_end if x_timed is None else x_timed})
     r0 = float(np.linalg.norm(Ae @ guess - f))
     rel_res_after = float(np.linalg.norm(Ae @ x_end - f)) / r0
     mode_, grid_, tmo_ = _ci32(), _ci32(), _ci32()

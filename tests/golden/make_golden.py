@@ -153,9 +153,29 @@ def bundled_driver_runs(ref_root):
     print("class2 driver: k=%d f=%.6f steps=%d" % (run["k"], run["fval"], len(run["log"])))
 
 
+def bundled_input_file(ref_root):
+    """data1-500.mat as MATLAB wrote it, less its first element (c, 250000 doubles: 1.9 MB that
+    data1_500.npz already holds): header and the other elements byte for byte.
+    tests/test_host_logic.py puts c back from data1_500.npz; the constants printed here are the
+    first 56 bytes of c's uncompressed element (tag, flags, dims, name, data tag) and the SHA-256
+    of that whole element, which the rebuilt one must match."""
+    import struct
+    import zlib
+    b = open(os.path.join(ref_root, "Class1", "InputData", "data1-500.mat"), "rb").read()
+    tag, nbytes = struct.unpack("<II", b[128:136])
+    assert tag == 15                                      # miCOMPRESSED, no padding after it
+    elem = zlib.decompress(b[136:136 + nbytes])
+    c = np.load(os.path.join(HERE, "data1_500.npz"))["c"]
+    assert elem[56:] == c.astype("<f8").tobytes()
+    open(os.path.join(HERE, "data1-500_without_c.mat"), "wb").write(b[:128] + b[136 + nbytes:])
+    print("data1-500.mat: C_ELEMENT_HEAD = %s, C_ELEMENT_SHA256 = %s" % (
+        elem[:56].hex(), hashlib.sha256(elem).hexdigest()))
+
+
 if __name__ == "__main__":
     root = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
     if "--drivers-only" not in sys.argv:
         synthetic()
         realistic(root)
     bundled_driver_runs(root)
+    bundled_input_file(root)

@@ -445,6 +445,34 @@ def test_n2048_variant(ipd):
     assert abs(relk2[-1] - r3 / r0) <= 1e-10
 
 
+def test_bench_command_steps_and_dumped_iterate(metric_system, tmp_path):
+    """`bench.py --steps 3 --warmup 2 --dump-outputs DIR` as a command: the result line reports 3 timed steps
+    and their ms_per_step, the resident kernel's timed launch ran exactly 3 loop bodies, and DIR/x.npy is
+    the iterate those steps left (the one whose residual the line reports)."""
+    import json
+    import subprocess
+    import sys
+    m, n, s, Ae, f, guess = metric_system
+    root = os.path.dirname(os.path.abspath(bench.__file__))
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [
+        os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
+        "--dump-outputs", str(tmp_path / "out")]
+    res = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-4000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["warmup"] == 2 and r["ms_per_step"] > 0
+    if "handoffs_per_cycle" in r["execution"]:      # resident: the library counted the launch's loop bodies
+        assert r["execution"]["handoffs_per_cycle"] is not None
+    assert sorted(os.listdir(tmp_path / "out")) == ["x.npy"]
+    x = np.load(tmp_path / "out" / "x.npy")
+    assert x.dtype == np.float64 and x.shape == (2 * m,)
+    A = sp.csr_matrix(Ae)
+    rel = np.linalg.norm(A @ x - f) / np.linalg.norm(A @ guess - f)
+    assert rel <= 1e-9 and np.isclose(rel, r["rel_res_after_steps"], rtol=1e-9, atol=0.0), (rel, r)
+
+
 def test_amg4pot_dense_two_resident_solves(ipd):
     """Class 2 in the dense regime: AMG4POT's two right-hand sides (Class2/AMG4POT.m:46-47) run as
     TWO level-resident kernels side by side (64 workgroups each at m=n=512) on two

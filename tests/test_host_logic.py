@@ -38,12 +38,31 @@ def test_load_input_casts_and_shapes(tmp_path):
     assert np.array_equal(d["c"], C.reshape(-1, order="F"))
 
 
-def test_load_input_reads_the_bundled_files_when_present():
+# c's element of the bundled data1-500.mat, uncompressed: its first 56 bytes (miMATRIX tag, array
+# flags, dims 250000 x 1, name 'c', data tag) and the SHA-256 of the whole element
+# (tests/golden/make_golden.py bundled_input_file)
+C_ELEMENT_HEAD = ("0e000000b0841e0006000000080000000600000000000000050000000800000090d00300"
+                  "0100000001000100630000000900000080841e00")
+C_ELEMENT_SHA256 = "ad6d50f771cd2f86490e0edb021d9cc4df219f28f37ae487747c655b757796eb"
+
+
+def test_load_input_reads_the_bundled_files_when_present(tmp_path):
+    """The bundled Class 1 input as MATLAB wrote it.  The repository keeps the file less its first
+    element (tests/golden/data1-500_without_c.mat: header and the other elements byte for byte);
+    c's element is rebuilt from data1_500.npz, checked against MATLAB's by its hash, compressed and
+    put back in its place."""
+    import hashlib
+    import struct
+    import zlib
     ipd = pkg()
-    f = "/root/reference/Class1/InputData/data1-500.mat"
-    if not os.path.exists(f):
-        pytest.skip("reference not mounted (GPU box)")
-    d = ipd.load_input(f)
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "data1_500.npz"))
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    g = np.load(os.path.join(gold, "data1_500.npz"))
+    elem = bytes.fromhex(C_ELEMENT_HEAD) + g["c"].astype("<f8").tobytes()
+    assert hashlib.sha256(elem).hexdigest() == C_ELEMENT_SHA256
+    z = zlib.compress(elem)
+    rest = open(os.path.join(gold, "data1-500_without_c.mat"), "rb").read()
+    f = tmp_path / "data1-500.mat"
+    f.write_bytes(rest[:128] + struct.pack("<II", 15, len(z)) + z + rest[128:])   # miCOMPRESSED
+    d = ipd.load_input(str(f))
     assert d["cls"] == 1 and d["m"] == d["n"] == 500 and np.isinf(d["gama"])
     assert np.array_equal(d["c"], g["c"]) and np.array_equal(d["r"], g["r"]) and np.array_equal(d["l"], g["l"])
