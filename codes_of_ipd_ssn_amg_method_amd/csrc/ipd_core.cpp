@@ -190,7 +190,7 @@ static double g_prof_t[PROF_SLOTS];
 static long long g_prof_n[PROF_SLOTS];
 bool ipd_prof_enabled() {
     static const bool on = [] {
-        const char* e = getenv("IPD_PROFILE");
+        const char* e = switch_value("IPD_PROFILE");
         return e && *e && *e != '0';
     }();
     return on;

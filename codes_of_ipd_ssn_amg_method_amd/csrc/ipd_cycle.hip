@@ -887,7 +887,6 @@ __global__ __launch_bounds__(BT) void k_smooth_mask(const SmoothArgs a, const Ma
 // W cycle at M = 1000).  Here one workgroup interprets the V/W recursion itself
 // (MG_Vcycle.m:12-45, MG_Wcycle.m:13-46), the stationary iteration and its stopping
 // rules (Class_AMG.m:86-109): one launch and one read-back per solve.
-static constexpr int SOLVE_ML = 24;
 struct SolveLevel {
     LevelDev lv;
     double* e;
@@ -1837,22 +1836,11 @@ __device__ __forceinline__ double lds_rowdot_mapped(AS3 const int* ci, AS3 const
 // dense thread-per-row level: the lane's part of row i (columns sub + Lr q) from the row-major dense copy
 // (leading dimension bdense_ld: whole groups of four q, and rows of a wave on different banks), and its
 // dot product with an LDS vector.  No index tests: the copy's and the vectors' padding are zeros
-// (bdense_pad entries, see build_image), so a group of four q is four loads at constant offsets.
-// 24 values per lane: the register budget of the tail (the resident kernels' worker paths set the
-// kernels' allocation; the tail must stay below it) -- the same storage serves the lane-map entries.
-constexpr int BDENSE_Q = 24;
+// (bdense_pad entries, see pack_image), so a group of four q is four loads at constant offsets.
+// (BDENSE_Q values per lane, ipd_limits.h)
 struct DenseRow {
     double v[BDENSE_Q];
 };
-__host__ __device__ __forceinline__ int bdense_lanes(int N) { return N > 64 ? 4 : 8; }   // == lanes_per_row(N), 33..96 rows
-__host__ __device__ __forceinline__ int bdense_pad(int N) {
-    const int g = 4 * bdense_lanes(N);
-    return (N + g - 1) / g * g;
-}
-__host__ __device__ __forceinline__ int bdense_ld(int N) {
-    const int Lr = bdense_lanes(N), p = bdense_pad(N);
-    return p % (2 * Lr) == Lr ? p : p + Lr;   // p is a multiple of 4 Lr
-}
 template <int LR>
 __device__ __forceinline__ void dense_row_load_t(AS3 const double* dA, int N, int i, int sub, DenseRow& R) {
     const int Q = bdense_pad(N) / LR;   // a multiple of 4

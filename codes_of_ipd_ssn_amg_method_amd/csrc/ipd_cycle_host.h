@@ -5,6 +5,8 @@
 
 #include <cstdlib>
 
+#include "ipd_level_plan.h"
+
 struct LevelRun {  // per-level run state kept next to Level
     LevelDev dev;
     bool e_zero = true;      // the iterate is identically zero and is not materialised
@@ -216,8 +218,7 @@ static void build_padded(ipd_ctx* ctx, Arena& ar, const Csr& A, int rows_per_lau
     dev->pci = nullptr;
     dev->pva = nullptr;
     dev->diag = nullptr;
-    const char* env = std::getenv("IPD_NO_PAD");
-    if (env && env[0] == '1') return;
+    if (switch_on("IPD_NO_PAD")) return;
     if (A.nr > 65535 || A.nr == 0) return;
     const double avg_off = (double)(A.nnz - A.nr) / (double)A.nr;
     // small levels too: one dependent round trip less per launch (measured -6 % solve time on
@@ -351,9 +352,9 @@ static BPolyDev pack_bpoly(ipd_ctx* ctx, ipd_amg* h, CycleState* st, int k, int 
 // rows of at most 1024 entries, at most 2048 rows each, and a tail level of at most 64 rows --
 // i.e. the dense regimes (regime D), where each launch of the multi-launch path is
 // latency-bound.  IPD_NO_RESIDENT=1 switches it off, IPD_RESIDENT_G overrides the grid.
-static void plan_resident(ipd_amg* h, CycleState* st) {
+static void plan_resident(ipd_amg* h, CycleState* st, const PlanSwitches& sw) {
     st->res_ok = false;
-    if (const char* e = std::getenv("IPD_NO_RESIDENT"); e && e[0] == '1') {
+    if (sw.no_resident) {
         st->res_off = true;   // (remembered: the mask-form kernel is set up later, by amg_attach_maskop)
         return;
     }
@@ -377,7 +378,7 @@ static void plan_resident(ipd_amg* h, CycleState* st) {
         priv2 = true;
     }
     const int N1 = l1.A.nr, N2 = l2.A.nr, Nt = l3.A.nr, nf = l1.nf, nc = N1 - nf;
-    if (const char* dbg = std::getenv("IPD_DEBUG_LEVELS"); dbg && dbg[0] == '1')
+    if (switch_on("IPD_DEBUG_LEVELS"))
         std::fprintf(stderr, "[ipd] resident plan: J=%d nf=%d nc=%d S1=%d S2=%d S3=%d N4=%d Nt=%d k_sub=%d sub_lds=%zu\n", h->J,
                      nf, nc, d1.S, d2.S, st->run[3].dev.S, h->J >= 4 ? h->L[4].A.nr : 0, Nt, st->k_sub, st->sub_lds);
     if (nf <= 0 || nc <= 0 || d1.S <= 0 || d2.S <= 0) return;
@@ -391,26 +392,26 @@ static void plan_resident(ipd_amg* h, CycleState* st) {
     const SolveDesc* tail_img = nullptr;   // the remote tail's LDS image and its dynamic LDS size
     size_t tail_lds = 0, tail_bm = 0;   // tail_bm: room for the image's operator copy (SolveDesc::bm_src)
     if (!local_tail) {
-        const char* nr = std::getenv("IPD_NO_RESIDENT_REMOTE");
         const bool cyc = h->opts.cycle == 'w' || h->opts.cycle == 'v';
-        remote = !(nr && nr[0] == '1') && h->J >= 4 && Nt <= BT && cyc &&
+        remote = !sw.no_resident_remote && h->J >= 4 && Nt <= BT && cyc &&
                  ((st->k_sub == 3 && st->d_sub) || (st->k_sub == 0 && st->d_sub3));
         // Level 3 in the registers of the resident workgroups as well, the tail rooted at level 4: for
         // a level 3 too big for the tail's LDS (a few hundred rows of 15-100 entries), and preferred to
         // the tail rooted at level 3 whenever an image rooted at level 4 exists (the tail's legs are the
         // serial part of a cycle: ~22 us each from level 4, ~100 us from level 3).
-        const char* n3 = std::getenv("IPD_NO_RESIDENT_THREE");
         tail_img = st->k_sub == 0 ? st->d_sub3 : st->d_sub;
         tail_lds = st->k_sub == 0 ? st->sub3_lds : st->sub_lds;
         tail_bm = st->k_sub == 0 ? st->sub3_bm : st->sub_bm;
         const bool img4 = (st->k_sub == 4 && st->d_sub) || (st->k_sub == 3 && st->d_sub4);
-        if (!(nr && nr[0] == '1') && !(n3 && n3[0] == '1') && h->J >= 5 && img4 && cyc) {
-            // (its rows are usually too uneven for the launches' padded copy -- hubs -- but in registers
-            // the stride is only a layout: a private copy with the longest row as stride, below)
-            const int S3 = st->run[3].dev.S > 0 ? st->run[3].dev.S : (st->run[3].maxoff + 3) / 4 * 4;
-            const int N4 = h->L[4].A.nr;
-            if (S3 > 0 && S3 <= 512 && Nt <= BT && N4 <= BT && N2 <= RES_NMAX / 2 &&
-                std::max(d1.S, d2.S) <= 512 && Nt + std::max(cdiv(std::max(nf, nc), RES_WAVES), cdiv(N2, RES_WAVES)) <= 2 * BT) {
+        // level 3 fits the resident workgroups' registers: its rows (usually too uneven for the launches'
+        // padded copy -- hubs -- but in registers the stride is only a layout: a private copy with the
+        // longest row as stride, below), the row slots and a root level 4 of at most BT rows
+        const int S3 = st->run[3].dev.S > 0 ? st->run[3].dev.S : (st->run[3].maxoff + 3) / 4 * 4;
+        const bool three_fits = h->J >= 4 && S3 > 0 && S3 <= 512 && Nt <= BT && h->L[4].A.nr <= BT &&
+                                N2 <= RES_NMAX / 2 && std::max(d1.S, d2.S) <= 512 &&
+                                Nt + std::max(cdiv(std::max(nf, nc), RES_WAVES), cdiv(N2, RES_WAVES)) <= 2 * BT;
+        if (!sw.no_resident_remote && !sw.no_resident_three && h->J >= 5 && img4 && cyc) {
+            if (three_fits) {
                 three = remote = true;
                 ke3 = S3 <= 256 ? 4 : 8;
                 if (st->k_sub == 3) {
@@ -426,21 +427,13 @@ static void plan_resident(ipd_amg* h, CycleState* st) {
         // (a V cycle visits the tail once: there the local tail stays ahead of a tail workgroup rooted at a
         // level 3 in block-wide polynomial form -- tree mask 0.096 against 0.102 ms; a W cycle is the other
         // way round, 0.198 against 0.191)
-        if (remote && !three && h->J == 4 && h->opts.cycle == 'v' && !(n3 && n3[0] == '1') &&
-            h->L[4].A.nr <= RES_TAIL_MAX) {
-            const int S3 = st->run[3].dev.S > 0 ? st->run[3].dev.S : (st->run[3].maxoff + 3) / 4 * 4;
-            if (S3 > 0 && S3 <= 512 && Nt <= BT && N2 <= RES_NMAX / 2 && std::max(d1.S, d2.S) <= 512 &&
-                Nt + std::max(cdiv(std::max(nf, nc), RES_WAVES), cdiv(N2, RES_WAVES)) <= 2 * BT)
-                remote = false;
-        }
-        if (!remote && !(nr && nr[0] == '1') && !(n3 && n3[0] == '1') && h->J == 4 && cyc &&
-            h->L[4].A.nr <= RES_TAIL_MAX) {
-            const int S3 = st->run[3].dev.S > 0 ? st->run[3].dev.S : (st->run[3].maxoff + 3) / 4 * 4;
-            if (S3 > 0 && S3 <= 512 && Nt <= BT && N2 <= RES_NMAX / 2 && std::max(d1.S, d2.S) <= 512 &&
-                Nt + std::max(cdiv(std::max(nf, nc), RES_WAVES), cdiv(N2, RES_WAVES)) <= 2 * BT) {
-                three = true;
-                ke3 = S3 <= 256 ? 4 : 8;
-            }
+        if (remote && !three && h->J == 4 && h->opts.cycle == 'v' && !sw.no_resident_three &&
+            h->L[4].A.nr <= RES_TAIL_MAX && three_fits)
+            remote = false;
+        if (!remote && !sw.no_resident_remote && !sw.no_resident_three && h->J == 4 && cyc &&
+            h->L[4].A.nr <= RES_TAIL_MAX && three_fits) {
+            three = true;
+            ke3 = S3 <= 256 ? 4 : 8;
         }
         if (!remote && !three) return;
     }
@@ -450,7 +443,7 @@ static void plan_resident(ipd_amg* h, CycleState* st) {
     if (ke > 16) return;
     if (three && ke > 8) return;   // (the third row slice does not fit beside two 16-entry ones)
     int G = std::max(cdiv(std::max(nf, nc), RES_WAVES), cdiv(N2, RES_WAVES));
-    if (const char* e = std::getenv("IPD_RESIDENT_G")) G = std::max(G, std::atoi(e));
+    if (const char* e = switch_value("IPD_RESIDENT_G")) G = std::max(G, std::atoi(e));
     // every workgroup owns at least one row of every block (the hand-off protocol needs it)
     if (G + (remote ? 1 : 0) > st->num_cu || G > std::min(std::min(nf, nc), N2)) return;
     const int Nin = three ? h->L[4].A.nr : Nt;   // rows of the remote tail's root level / of the local tail
@@ -459,7 +452,7 @@ static void plan_resident(ipd_amg* h, CycleState* st) {
     // level 3 in polynomial form (ResDesc::p3rows): remote tail, one restriction row per workgroup at most,
     // at most four rows of level 3 per workgroup
     const bool poly3 = three && remote && h->opts.smoth >= 1 && h->L[4].A.nr <= G && h->L[4].A.nr <= 128 && Nt <= 4 * G && Nt <= BT &&
-                       !(std::getenv("IPD_NO_POLY") && std::getenv("IPD_NO_POLY")[0] == '1');
+                       !sw.no_poly;
     if (poly3) ke3 = 1;
     // level 4 resident as well (ResDesc::p4rows), the tail workgroup rooted at level 5
     const int N5r = h->J >= 6 ? h->L[5].A.nr : 0;
@@ -583,7 +576,7 @@ static void plan_resident(ipd_amg* h, CycleState* st) {
     D.tctl = remote ? reinterpret_cast<unsigned*>(st->res_block + 6 * gbytes + 16) : D.tmo;
     D.dbg = nullptr;
     D.dbg_skip_seq = 0;
-    if (const char* e = std::getenv("IPD_RES_DEBUG_SKIP_PUBLISH")) D.dbg_skip_seq = (unsigned)std::max(0, std::atoi(e));
+    if (const char* e = switch_value("IPD_RES_DEBUG_SKIP_PUBLISH")) D.dbg_skip_seq = (unsigned)std::max(0, std::atoi(e));
     st->res_desc = D;
     st->res_remote = remote;
     st->resb_poly4 = poly4;
@@ -657,7 +650,7 @@ static bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double
     if (!lease.ok) return false;
     ResDesc D = st->res_desc;
     D.dbg = dbg_dev;
-    if (const char* dl = std::getenv("IPD_DEBUG_LEVELS"); dl && dl[0] == '1')
+    if (switch_on("IPD_DEBUG_LEVELS"))
         std::fprintf(stderr, "[ipd] resident launch: grid %d ke %d ke3 %d xm %d wident %d three %d remote %d\n", grid,
                      st->res_ke, st->res_ke3, D.xm, D.wident, D.three, D.remote);
     st->res_desc.dbg_skip_seq = 0;   // the test hook fires on ONE launch
@@ -788,11 +781,11 @@ static bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double
     return true;
 }
 
-void amg_prepare_levels(ipd_amg* h) {
+// Per-level vectors and constants (k_level_prepare), the padded copies and the launch geometry of every
+// level: st->run[k].dev
+static void prepare_level_runs(ipd_amg* h, CycleState* st) {
     ipd_ctx* ctx = h->ctx;
     Arena& ar = *h->arena;
-    std::unique_ptr<CycleState> st(new CycleState());
-    st->run.resize((size_t)h->J + 1);
     const int cu = ctx->num_cu;
     // first pass: per-level vectors and the longest off-diagonal row of every level (one
     // readback for all levels), second pass: padded copies and launch geometry
@@ -881,11 +874,7 @@ void amg_prepare_levels(ipd_amg* h) {
         rn.dev.xx = lv.xx;
         rn.dev.r = lv.r;
         rn.dev.rr = lv.rr;
-        rn.staged = N <= STAGE_MAX ? 1 : 0;
-        {
-            const char* ns = std::getenv("IPD_NO_STAGE");
-            if (ns && ns[0] == '1') rn.staged = 0;
-        }
+        rn.staged = N <= STAGE_MAX && !switch_on("IPD_NO_STAGE") ? 1 : 0;
         if (shared_level(k)) {   // the donor's padded copy and the geometry that goes with it
             const LevelDev& dd = dst_->run[(size_t)k].dev;
             rn.dev.S = dd.S;
@@ -897,10 +886,16 @@ void amg_prepare_levels(ipd_amg* h) {
             lv.lanes = donor->L[k].lanes;
         } else {
             build_padded(ctx, ar, lv.A, rows_per_launch, cu, hmax[(size_t)k], &rn.dev, &pads);
-        rn.maxoff = hmax[(size_t)k];
+            rn.maxoff = hmax[(size_t)k];
         }
     }
     pad_flush(ctx, &pads);
+}
+
+// Restriction / prolongation arguments of the launches, the coarsest level's PCG, the solve's vectors
+static void prepare_transfers(ipd_amg* h, CycleState* st) {
+    Arena& ar = *h->arena;
+    const int cu = h->ctx->num_cu;
     for (int k = 1; k < h->J; ++k) {
         Level& fine = h->L[k];
         Level& coarse = h->L[k + 1];
@@ -961,701 +956,474 @@ void amg_prepare_levels(ipd_amg* h) {
     st->x2 = ar.alloc<double>((size_t)h->L[1].A.nr);
     h->x = ar.alloc<double>((size_t)h->L[1].A.nr);
     h->b = ar.alloc<double>((size_t)h->L[1].A.nr);
-    // ---- single-workgroup kernels -------------------------------------------------------
-    // (a) whole solve in one workgroup when every level is small; (b) otherwise the sub-cycle
-    // below the first level from which everything fits in LDS runs as one launch per visit.
-    auto small_level = [&](int k) {
+}
+
+// Descriptor of image `spec` before its layout: every level's global arrays and its lanes per row in one workgroup
+static void fill_desc(ipd_amg* h, const CycleState* st, const ImageSpec& spec, SolveDesc* sd) {
+    std::memset(sd, 0, sizeof(SolveDesc));
+    sd->J = h->J;
+    sd->nu = h->opts.smoth;
+    sd->isnsp = h->opts.isnsp;
+    sd->wcycle = h->opts.cycle == 'w';
+    sd->anycycle = (h->opts.cycle == 'w' || h->opts.cycle == 'v');
+    sd->maxit = h->opts.maxit;
+    sd->retol = h->opts.retol;
+    sd->pcg = st->run[(size_t)h->J].pcg;
+    for (int k = 1; k <= h->J; ++k) {
+        SolveLevel& sl = sd->L[k];
+        sl.lv = st->run[(size_t)k].dev;
+        sl.lv.S = 0;  // the single-workgroup kernels walk the CSR arrays only
+        // in one workgroup a row is walked by few lanes: re-pick without widening
         const Level& lv = h->L[k];
-        // one workgroup is one CU: beyond ~1000 short rows per level the multi-launch
-        // path (many CUs per phase) wins again (measured: M = 1000 W-cycle solve 9.5 ms
-        // here vs 17 ms multi-launch; M = 2048: 8.0 ms here vs 5.6 ms multi-launch)
-        return lv.A.nr <= 1024 && lv.A.nnz <= 40000 && (k < 2 || lv.P.nnz <= 40000);
-    };
-    auto r16 = [](size_t b) { return (b + 15) / 16 * 16; };
-    auto fill_desc = [&](SolveDesc* sd) {
-        std::memset(sd, 0, sizeof(SolveDesc));
-        sd->J = h->J;
-        sd->nu = h->opts.smoth;
-        sd->isnsp = h->opts.isnsp;
-        sd->wcycle = h->opts.cycle == 'w';
-        sd->anycycle = (h->opts.cycle == 'w' || h->opts.cycle == 'v');
-        sd->maxit = h->opts.maxit;
-        sd->retol = h->opts.retol;
-        sd->pcg = st->run[(size_t)h->J].pcg;
-        for (int k = 1; k <= h->J; ++k) {
-            SolveLevel& sl = sd->L[k];
-            sl.lv = st->run[(size_t)k].dev;
-            sl.lv.S = 0;  // the single-workgroup kernels walk the CSR arrays only
-            // in one workgroup a row is walked by few lanes: re-pick without widening
-            const Level& lv = h->L[k];
-            {
-                const double avg = (double)lv.A.nnz / std::max(lv.A.nr, 1);
+        {
+            const double avg = (double)lv.A.nnz / std::max(lv.A.nr, 1);
+            int L = 1;
+            while (L < 64 && (double)L * 6.0 < avg) L <<= 1;
+            sl.lv.L = L;
+        }
+        sl.lv.G = 1;
+        sl.e = lv.e;
+        sl.e2 = lv.e2;
+        sl.w = lv.w;
+        sl.nnzA = lv.A.nnz;
+        sl.nnzP = k < h->J ? h->L[k + 1].P.nnz : 0;
+        if (k < h->J) {
+            sl.rest = st->run[(size_t)k].restrict_args;
+            sl.prol = st->run[(size_t)k].prolong_args;
+            for (XferArgs* xa : {&sl.rest, &sl.prol}) {
+                const double avg = (double)(xa == &sl.rest ? h->L[k + 1].Pt.nnz : h->L[k + 1].P.nnz) /
+                                   std::max(xa->nrows, 1);
                 int L = 1;
                 while (L < 64 && (double)L * 6.0 < avg) L <<= 1;
-                sl.lv.L = L;
-            }
-            sl.lv.G = 1;
-            sl.e = lv.e;
-            sl.e2 = lv.e2;
-            sl.w = lv.w;
-            sl.nnzA = lv.A.nnz;
-            sl.nnzP = k < h->J ? h->L[k + 1].P.nnz : 0;
-            if (k < h->J) {
-                sl.rest = st->run[(size_t)k].restrict_args;
-                sl.prol = st->run[(size_t)k].prolong_args;
-                for (XferArgs* xa : {&sl.rest, &sl.prol}) {
-                    const double avg = (double)(xa == &sl.rest ? h->L[k + 1].Pt.nnz : h->L[k + 1].P.nnz) /
-                                       std::max(xa->nrows, 1);
-                    int L = 1;
-                    while (L < 64 && (double)L * 6.0 < avg) L <<= 1;
-                    xa->L = L;
-                    xa->G = 1;
-                    xa->staged = 1;
-                    xa->row0 = 0;
-                    xa->row1 = xa->nrows;
-                }
+                xa->L = L;
+                xa->G = 1;
+                xa->staged = 1;
+                xa->row0 = 0;
+                xa->row1 = xa->nrows;
             }
         }
-    };
-    // bottom run of levels with <= 32 rows (k >= 2): candidates for the wave-level sub-cycle
-    // (33..64 rows run faster block-wide with 16 lanes per row than in one wave) -- <= 48 rows when
-    // the one-wave levels take the polynomial form (tiny_cycle: a visit is two dense passes whatever
-    // the row count; IPD_NO_POLY=1: sweeps)
-    int tiny_lo = h->J + 1;
-    bool use_poly = h->opts.smoth >= 1 && (h->opts.cycle == 'w' || h->opts.cycle == 'v') &&
-                    !(std::getenv("IPD_NO_POLY") && std::getenv("IPD_NO_POLY")[0] == '1') &&
-                    !(std::getenv("IPD_NO_BLK") && std::getenv("IPD_NO_BLK")[0] == '1');
-    // (polynomial form: a level whose stacked operator [e'; r_c] has more than 32 rows -- one lane per row in
-    // a single wave -- runs block-wide instead, out of LDS all the same: is_lpoly below)
-    bool use_lpoly = !(std::getenv("IPD_NO_BLK") && std::getenv("IPD_NO_BLK")[0] == '1');
-    auto find_tiny_lo = [&](int rows_max) {
-        int lo = h->J + 1;
-        for (int k = h->J; k >= 2; --k) {
-            if (h->L[k].A.nr > rows_max) break;
-            if (rows_max > 32 && use_lpoly && k < h->J && h->L[k].A.nr + h->L[k + 1].A.nr > 32) break;
-            lo = k;
-        }
-        return lo;
-    };
-    tiny_lo = find_tiny_lo(use_poly ? 48 : 32);
-    auto r8 = [](size_t n) { return (n + 7) / 8 * 8; };
-    auto poly_ld = [](size_t rows) -> size_t { return rows <= 32 ? 32 : (rows <= 48 ? 48 : 64); };
-    auto is_poly = [&](int k) {
-        return use_poly && k >= tiny_lo && k < h->J && h->L[k].A.nr + h->L[k + 1].A.nr <= 64;
-    };
-    // the thread-per-row / wave sub-cycles keep the residual in the free iterate buffer and never
-    // use the Gauss-Seidel scratch vector: 5 vectors per cached level instead of 7
-    bool lean_vectors = true;
-    {
-        const char* nb = std::getenv("IPD_NO_BLK");
-        if (nb && nb[0] == '1') lean_vectors = false;
     }
-    const bool use_lmap = lean_vectors;
-    // small, nearly full thread-per-row levels: dense copy instead of the CSR arrays (see SolveLevel::blk_dense)
-    const bool use_bdense = lean_vectors && !(std::getenv("IPD_NO_BLKDENSE") && std::getenv("IPD_NO_BLKDENSE")[0] == '1');
-    auto is_lpoly = [&](int k) {
-        return use_poly && use_lpoly && lean_vectors && k >= 2 && k < tiny_lo && k < h->J && h->L[k].A.nr <= 48 &&
-               h->L[k].A.nr + h->L[k + 1].A.nr <= 64;
+    sd->k_lds = spec.k_lds;
+    sd->k_semi = spec.k_semi;
+    sd->k_tiny = spec.k_tiny;
+    sd->k_blk = spec.k_blk;
+    sd->stage_bytes = (int)spec.stage_bytes;
+    if (spec.role != IMG_SOLVE) {
+        sd->root_r = h->L[spec.k_lds].r;
+        sd->root_e = h->L[spec.k_lds].e;
+    }
+}
+
+// An image's pieces: the constant arrays copied into it, the dense / lane-map / polynomial blocks computed
+// into it, and the relocations of the descriptor's LDS offsets
+struct ImageLayout {
+    std::vector<PackEntry> packs;
+    std::vector<unsigned> relocs;
+    std::vector<DenseEntry> dense;
+    std::vector<LmapEntry> lmaps;
+    std::vector<PolyEntry> polys;
+    size_t poly_lds = 0;   // dynamic LDS of k_pack_poly
+};
+
+// Packs the laid-out image on the device and records the levels' forms; with bm_extra, one block-wide
+// polynomial operator's LDS copy goes behind the image's `off` bytes (*bm_extra: its size, 0 = none).
+static SolveDesc* upload_image(ipd_ctx* ctx, ipd_amg* h, CycleState* st, SolveDesc* sd, int k_from, size_t off,
+                               size_t image_bytes, ImageLayout& lay, size_t* bm_extra) {
+    Arena& ar = *h->arena;
+    // One block-wide polynomial level's operator as an LDS copy (SolveDesc::bm_src), for the launches that can
+    // afford bm_bytes more dynamic LDS (the resident kernels' tail workgroup): the deepest such level whose
+    // stacked operator has at most 128 rows and fits behind the work vectors.
+    sd->bm_src = nullptr;
+    sd->bm_level = sd->bm_ld = sd->bm_off = sd->bm_bytes = 0;
+    if (bm_extra) {
+        *bm_extra = 0;
+        for (int k = h->J - 1; k >= std::max(2, k_from); --k) {
+            const SolveLevel& T = sd->L[k];
+            if (!T.gM || T.gLD != 128) continue;
+            const size_t N = (size_t)T.lv.N, Nc = (size_t)h->L[k + 1].A.nr, rows = N + Nc;
+            if (rows > 128) continue;
+            const size_t ld = (rows + 1) & ~size_t(1), ncols = 8 * (2 * ((N + 7) / 8) + (Nc + 7) / 8);
+            const size_t need = 8 * ld * (ncols + 1);   // (ld even: a multiple of 16; the vector W behind the columns)
+            if (off + need > (size_t)156 * 1024) continue;
+            double* cp = ar.alloc<double>(ld * (ncols + 1));
+            hipLaunchKernelGGL(k_bm_compact, dim3((unsigned)ncols + 1), dim3(128), 0, ctx->stream, T.gM, 128, cp,
+                               (int)ld, T.gW, (int)rows);
+            IPD_KERNEL_CHECK();
+            sd->bm_src = cp;
+            sd->bm_level = k;
+            sd->bm_ld = (int)ld;
+            sd->bm_off = (int)off;
+            sd->bm_bytes = (int)need;
+            *bm_extra = need;
+            break;
+        }
+    }
+    char* img = reinterpret_cast<char*>(ar.alloc_bytes(image_bytes));
+    // the image head and the pack descriptors go up in ONE copy: [head | packs | dense | lmaps | polys] in
+    // a scratch block, the head then moves into the image as one more entry of k_pack_image
+    auto r16b = [](size_t v) { return (v + 15) & ~size_t(15); };
+    const size_t o_packs = r16b(SOL_HEAD), o_dense = o_packs + r16b((lay.packs.size() + 1) * sizeof(PackEntry)),
+                 o_lmaps = o_dense + r16b(lay.dense.size() * sizeof(DenseEntry)),
+                 o_polys = o_lmaps + r16b(lay.lmaps.size() * sizeof(LmapEntry)),
+                 o_end = o_polys + r16b(lay.polys.size() * sizeof(PolyEntry));
+    char* stg = reinterpret_cast<char*>(ctx->scratch->alloc_bytes(o_end));
+    std::vector<char> hb(o_end, 0);
+    std::memcpy(hb.data(), sd, sizeof(SolveDesc));
+    std::memcpy(hb.data() + plan_r16(sizeof(SolveDesc)), lay.relocs.data(), lay.relocs.size() * sizeof(unsigned));
+    {
+        PackEntry he{};
+        he.src = stg;
+        he.dst_off = 0;
+        he.bytes = (unsigned)SOL_HEAD;
+        lay.packs.push_back(he);
+    }
+    std::memcpy(hb.data() + o_packs, lay.packs.data(), lay.packs.size() * sizeof(PackEntry));
+    if (!lay.dense.empty()) std::memcpy(hb.data() + o_dense, lay.dense.data(), lay.dense.size() * sizeof(DenseEntry));
+    if (!lay.lmaps.empty()) std::memcpy(hb.data() + o_lmaps, lay.lmaps.data(), lay.lmaps.size() * sizeof(LmapEntry));
+    if (!lay.polys.empty()) std::memcpy(hb.data() + o_polys, lay.polys.data(), lay.polys.size() * sizeof(PolyEntry));
+    ctx->upload_bytes(stg, hb.data(), o_end);
+    hipLaunchKernelGGL(k_pack_image, dim3((unsigned)lay.packs.size()), dim3(256), 0, ctx->stream,
+                       reinterpret_cast<const PackEntry*>(stg + o_packs), img);
+    IPD_KERNEL_CHECK();
+    if (!lay.dense.empty()) {
+        hipLaunchKernelGGL(k_pack_dense, dim3((unsigned)lay.dense.size()), dim3(256), 0, ctx->stream,
+                           reinterpret_cast<const DenseEntry*>(stg + o_dense), img);
+        IPD_KERNEL_CHECK();
+    }
+    if (!lay.lmaps.empty()) {
+        hipLaunchKernelGGL(k_pack_lmap, dim3((unsigned)lay.lmaps.size()), dim3(BT), 0, ctx->stream,
+                           reinterpret_cast<const LmapEntry*>(stg + o_lmaps), img);
+        IPD_KERNEL_CHECK();
+    }
+    if (!lay.polys.empty()) {
+        IPD_OPTIN_LDS(ctx, k_pack_poly, 156 * 1024);
+        hipLaunchKernelGGL(k_pack_poly, dim3((unsigned)lay.polys.size()), dim3(BT), lay.poly_lds, ctx->stream,
+                           reinterpret_cast<const PolyEntry*>(stg + o_polys), img);
+        IPD_KERNEL_CHECK();
+    }
+    st->level_forms.resize((size_t)h->J + 1, 0);
+    for (int k = std::max(k_from, sd->k_blk); k <= h->J; ++k) {
+        const SolveLevel& T = sd->L[k];
+        if (k == sd->k_semi) continue;
+        st->level_forms[(size_t)k] |= T.gM ? 16 : T.pMr ? (k >= sd->k_tiny ? 8 : 32) : k >= sd->k_tiny ? 4 : T.blk_dense ? 2 : 1;
+    }
+    return reinterpret_cast<SolveDesc*>(img);
+}
+
+// Lays image `spec` out (levels k_lds..J behind the staging area), packs it on the device and stores it
+// in st by its role
+static void pack_image(ipd_ctx* ctx, ipd_amg* h, CycleState* st, const LevelPlan& plan, const ImageSpec& spec) {
+    std::unique_ptr<SolveDesc> sdp(new SolveDesc());
+    SolveDesc* sd = sdp.get();
+    fill_desc(h, st, spec, sd);
+    if (spec.role == IMG_SOLVE) {
+        st->solve_cached = spec.k_lds <= h->J;
+        st->solve_lds = spec.lds;
+        if (!st->solve_cached) {   // nothing in LDS: the descriptor as it is
+            st->d_solve = reinterpret_cast<SolveDesc*>(h->arena->alloc_bytes(sizeof(SolveDesc)));
+            ctx->upload_bytes(st->d_solve, sd, sizeof(SolveDesc));
+            return;
+        }
+    }
+    const int k_from = spec.k_lds;
+    const size_t stage = spec.stage_bytes;
+    const bool lean = plan.lean_vectors && sd->k_blk <= std::max(2, k_from);
+    ImageLayout lay;
+    size_t off = stage + SOL_HEAD;   // LDS offset (from dyn_raw) of the next carve
+    auto carve = [&](size_t bytes) {
+        const size_t o = off;
+        off += plan_r16(bytes);
+        return o;
     };
-    // thread-per-row levels of 33..144 rows in block-wide polynomial form (SolveLevel::gM); use_poly may
-    // still be withdrawn below, hence the reference
-    const bool use_bpoly = lean_vectors && !(std::getenv("IPD_NO_BPOLY") && std::getenv("IPD_NO_BPOLY")[0] == '1');
-    auto bpoly_ld = [&](int k) { return h->L[k].A.nr + h->L[k + 1].A.nr <= 128 ? 128 : 256; };
-    auto is_bpoly = [&](int k) {
-        if (!use_poly || !use_bpoly || k < 2 || k >= h->J || k >= tiny_lo) return false;
-        const long long N = h->L[k].A.nr, Nc = h->L[k + 1].A.nr;
-        // (up to 224 rows below a level 1 of more than 2048 rows: there level 4 has 150-200 rows, often dense --
-        // 23 k entries do not fit an LDS image, the operators of this form stay in L2 -- and the mask-form
-        // resident kernel needs its tail rooted at level 4, ipd_resident_big.h DEEP)
-        const long long nmax = h->L[1].A.nr > RES_NMAX ? 224 : 144;
-        return N > 32 && N <= nmax && N + Nc <= 256 && 2 * ((N + 7) / 8 * 8) + (Nc + 7) / 8 * 8 <= 512 && !is_lpoly(k);
+    auto set_off = [&](auto& field, size_t o) {
+        using T = std::remove_reference_t<decltype(field)>;
+        field = reinterpret_cast<T>(o);
+        lay.relocs.push_back((unsigned)(reinterpret_cast<char*>(&field) - reinterpret_cast<char*>(sd)));
     };
-    std::vector<BPolyDev> bpoly_dev((size_t)h->J + 2);
-    auto ensure_bpoly = [&](int k, int nu, int isnsp) -> const BPolyDev& {
-        (void)nu;
-        BPolyDev& b = bpoly_dev[(size_t)k];
-        if (!b.M) {
-            b = pack_bpoly(ctx, h, st.get(), k, isnsp, bpoly_ld(k), false);
+    auto put = [&](auto& field, size_t n) {   // constant array: copied into the image
+        using T = std::remove_reference_t<decltype(field)>;
+        using E = std::remove_cv_t<std::remove_pointer_t<T>>;
+        const size_t o = carve(n * sizeof(E));
+        lay.packs.push_back(PackEntry{(const void*)field, (unsigned)(o - stage), (unsigned)(n * sizeof(E))});
+        set_off(field, o);
+    };
+    int bp_ld_max = 0;
+    for (int k = k_from; k <= h->J; ++k) {     // constants first: they form the image
+        SolveLevel& T = sd->L[k];
+        const size_t N = (size_t)T.lv.N;
+        if (k == sd->k_semi) continue;         // matrix, transfers, dinv, Axi stay in global memory
+        if (((plan.poly[(size_t)k] && k >= sd->k_tiny) || (plan.lpoly[(size_t)k] && k < sd->k_tiny)) && sd->k_blk <= k) {   // polynomial form: no CSR arrays (see plan_lds)
+            put(T.lv.xx, 1);
+            T.lv.rp = T.lv.ci = nullptr;
+            T.lv.va = T.lv.dinv = T.lv.Axi = nullptr;
+            T.rest.rp = T.rest.ci = T.prol.rp = T.prol.ci = nullptr;
+            T.rest.va = T.prol.va = nullptr;
+            continue;
+        }
+        if (plan.bpoly[(size_t)k] && sd->k_blk <= k && k < sd->k_tiny) {   // block-wide polynomial form (see plan_lds)
+            put(T.lv.xx, 1);
+            T.lv.rp = T.lv.ci = nullptr;
+            T.lv.va = T.lv.dinv = T.lv.Axi = nullptr;
+            T.rest.rp = T.rest.ci = T.prol.rp = T.prol.ci = nullptr;
+            T.rest.va = T.prol.va = nullptr;
             st->poly_ops.resize((size_t)h->J + 1);
             CycleState::PolyOp& po = st->poly_ops[(size_t)k];
-            po.M = b.M;
-            po.W = b.W;
-            po.LD = b.LD;
-            po.N = h->L[k].A.nr;
-            po.Nc = h->L[k + 1].A.nr;
-        }
-        return b;
-    };
-    auto is_bdense = [&](int k) {
-        if (!use_bdense || k < 2 || k >= h->J || k >= tiny_lo || is_bpoly(k)) return false;
-        const long long N = h->L[k].A.nr;
-        return N > 32 && N <= 96 && bdense_pad((int)N) / bdense_lanes((int)N) <= BDENSE_Q &&
-               3LL * h->L[k].A.nnz >= N * N;
-    };
-    // LDS cache plan: deepest levels first, while they fit; returns the first cached level
-    auto plan_lds = [&](size_t stage, size_t* used_out) {
-        size_t used = stage + SOL_HEAD + 256;
-        const size_t budget = 150 * 1024;
-        int k_lds = h->J + 1;
-        for (int k = h->J; k >= 1; --k) {
-            const Level& lv = h->L[k];
-            const size_t N = (size_t)lv.A.nr;
-            size_t bytes;
-            if (is_poly(k)) {
-                // polynomial form: [M2a; ..] and [M1; ..] stacked with the restriction, M1 P, w; three
-                // vectors; none of the level's CSR arrays (its parent applies the transfers to and from it)
-                const size_t Nc = (size_t)h->L[k + 1].A.nr, LD = poly_ld(N + Nc);
-                bytes = 2 * (8 * LD * r8(N)) + 8 * LD * r8(Nc) + 8 * LD + 3 * r16(8 * r8(N)) + 32;
-            } else if (is_lpoly(k)) {
-                const size_t Nc = (size_t)h->L[k + 1].A.nr, LD = 64;
-                bytes = 2 * (8 * LD * r8(N)) + 8 * LD * r8(Nc) + 8 * LD + 3 * r16(8 * r8(N)) + 32 + 8 * (8 * LD + 8);
-            } else if (is_bpoly(k)) {
-                // block-wide polynomial form: the operators stay in global memory; three vectors and the
-                // partial sums of a pass
-                bytes = 3 * r16(8 * r8(N)) + 48 + 8 * (8 * (size_t)bpoly_ld(k) + 8);
-            } else {
-                // (the thread-per-row sub-cycle deals BT threads to the rows: a level of more than BT rows cannot
-                // be held that way -- it fits the budget once its child's operators stay in L2, block-wide
-                // polynomial form of a 150-224-row level 4 below a 576-row level 3)
-                if (k >= 2 && N > (size_t)BT) break;
-                bytes = r16(4 * (N + 1)) +
-                        (is_bdense(k) ? r16(8 * N * (size_t)bdense_ld((int)N))
-                                      : r16(4 * (size_t)lv.A.nnz) + r16(8 * (size_t)lv.A.nnz)) +
-                        ((lean_vectors && k >= 2) ? 5 : 7) *
-                            r16(8 * (k >= tiny_lo ? r8(N) : is_bdense(k) ? (size_t)bdense_pad((int)N) : N)) +
-                        16;
-                if (k < h->J) {
-                    const size_t Nc = (size_t)h->L[k + 1].A.nr, np = (size_t)h->L[k + 1].P.nnz;
-                    bytes += r16(4 * (Nc + 1)) + r16(4 * (N + 1)) + 2 * (r16(4 * np) + r16(8 * np));
-                }
-                if (k == h->J) bytes += r16(4 * 8 * N);
-                if (use_lmap && !is_bdense(k) && k >= 2 && k < tiny_lo && N <= (size_t)BT) bytes += r16(4 * (BT + 1));   // lane map
-                if (k >= 3 && (is_bpoly(k - 1) || is_lpoly(k - 1))) bytes += 5 * 64;   // its vectors are padded to whole 8-entry blocks
-                if (k >= tiny_lo) {   // dense copies of the tiny levels
-                    bytes += r16(8 * N * N);
-                    if (k < h->J) bytes += 2 * r16(8 * N * (size_t)h->L[k + 1].A.nr);
-                }
+            if (!po.M) {   // packed once for all images
+                const BPolyDev b = pack_bpoly(ctx, h, st, k, sd->isnsp, bpoly_ld(h->L[k].A.nr, h->L[k + 1].A.nr), false);
+                po.M = b.M;
+                po.W = b.W;
+                po.LD = b.LD;
+                po.N = h->L[k].A.nr;
+                po.Nc = h->L[k + 1].A.nr;
             }
-            if (used + bytes > budget) break;
-            used += bytes;
-            k_lds = k;
+            T.gM = po.M;
+            T.gW = po.W;
+            T.gLD = po.LD;
+            bp_ld_max = std::max(bp_ld_max, po.LD);
+            continue;
         }
-        *used_out = used;
-        return k_lds;
-    };
-    if (use_poly) {   // not at the price of a level that would otherwise be cached
-        size_t u = 0;
-        const int with_poly = plan_lds(16, &u);
-        const int lo_poly = tiny_lo;
-        use_poly = false;
-        tiny_lo = find_tiny_lo(32);
-        const int without = plan_lds(16, &u);
-        if (with_poly <= without) {
-            use_poly = true;
-            tiny_lo = lo_poly;
-        } else if (use_lpoly) {
-            // the block-wide form out of LDS pads its operators to 64 rows: where that is what does not
-            // fit, the one-wave form (48 rows) may still
-            use_lpoly = false;
-            use_poly = true;
-            tiny_lo = find_tiny_lo(48);
-            if (plan_lds(16, &u) > without) {
-                use_poly = false;
-                tiny_lo = find_tiny_lo(32);
-            }
+        put(T.lv.rp, N + 1);
+        if (plan.bdense[(size_t)k] && sd->k_blk <= k && k < sd->k_tiny) {   // dense copy (carved below) instead of ci / va
+            T.blk_dense = 1;
+            T.lv.ci = nullptr;
+            T.lv.va = nullptr;
+        } else {
+            put(T.lv.ci, (size_t)T.nnzA);
+            put(T.lv.va, (size_t)T.nnzA);
+        }
+        put(T.lv.dinv, N);
+        put(T.lv.Axi, N);
+        put(T.lv.xx, 1);
+        if (k < h->J) {
+            const size_t Nc = (size_t)T.rest.nrows;
+            put(T.rest.rp, Nc + 1);
+            put(T.rest.ci, (size_t)T.nnzP);
+            put(T.rest.va, (size_t)T.nnzP);
+            put(T.prol.rp, N + 1);
+            put(T.prol.ci, (size_t)T.nnzP);
+            put(T.prol.va, (size_t)T.nnzP);
         }
     }
-    auto tiny_from = [&](int k_lds) {   // tiny levels: <= 32 rows, cached, Jacobi (k >= 2)
-        return std::max(tiny_lo, std::max(2, k_lds));
+    for (int k = std::max(k_from, sd->k_blk); k < std::min(sd->k_tiny, h->J + 1); ++k) {
+        if (!plan.lean_vectors || k == sd->k_semi || k < 2 || h->L[k].A.nr > BT || k == h->J || sd->L[k].blk_dense || sd->L[k].gM || plan.lpoly[(size_t)k]) continue;
+        SolveLevel& T = sd->L[k];
+        const size_t o = carve(4 * (BT + 1));
+        lay.lmaps.push_back(LmapEntry{h->L[k].A.rp, h->L[k].A.nr, (unsigned)(o - stage)});
+        set_off(T.lmap, o);
+    }
+    for (int k = k_from; k <= h->J; ++k) {
+        if (!sd->L[k].blk_dense) continue;
+        const Csr& m = h->L[k].A;
+        const int ld = bdense_ld(m.nr);
+        const size_t o = carve(8 * (size_t)m.nr * ld);
+        lay.dense.push_back(DenseEntry{m.rp, m.ci, m.va, m.nr, m.nc, (unsigned)(o - stage), ld});
+        set_off(sd->L[k].dA, o);
+    }
+    auto add_poly = [&](int k, size_t LD) {
+        SolveLevel& T = sd->L[k];
+        const Level& lv = h->L[k];
+        const size_t N = (size_t)lv.A.nr;
+        const Csr& P = h->L[k + 1].P;
+        const size_t Nc = (size_t)P.nc;
+        const LevelDev& gd = st->run[(size_t)k].dev;   // global pointers (T's are LDS offsets by now)
+        PolyEntry pe;
+        pe.Arp = lv.A.rp;
+        pe.Aci = lv.A.ci;
+        pe.Ava = lv.A.va;
+        pe.Prp = P.rp;
+        pe.Pci = P.ci;
+        pe.Pva = P.va;
+        pe.dinv = gd.dinv;
+        pe.Axi = gd.Axi;
+        pe.xx = gd.xx;
+        pe.N = (int)N;
+        pe.Nc = (int)Nc;
+        pe.nu = sd->nu;
+        pe.isnsp = sd->isnsp;
+        pe.LD = (int)LD;
+        T.pLD = (int)LD;
+        size_t o = carve(8 * LD * plan_r8(N));
+        pe.offMr = (unsigned)(o - stage);
+        set_off(T.pMr, o);
+        o = carve(8 * LD * plan_r8(N));
+        pe.offMe = (unsigned)(o - stage);
+        set_off(T.pMe, o);
+        o = carve(8 * LD * plan_r8(Nc));
+        pe.offMc = (unsigned)(o - stage);
+        set_off(T.pMc, o);
+        o = carve(8 * LD);
+        pe.offW = (unsigned)(o - stage);
+        set_off(T.pW, o);
+        lay.polys.push_back(pe);
+        lay.poly_lds = std::max(lay.poly_lds, 8 * (5 * N * N + 2 * N * Nc + 4 * N) + 64);
     };
-    auto blk_from = [&](int k_lds) {    // cached Jacobi levels: thread-per-row sub-cycle
-        const char* nb = std::getenv("IPD_NO_BLK");
-        if ((nb && nb[0] == '1') || k_lds > h->J) return h->J + 1;
-        return std::max(2, k_lds);
-    };
-    // Lays levels k_from..J out behind the staging area, packs the image on the device and
-    // returns it (the descriptor the kernels take); *lds_total = dynamic LDS bytes to request.
-    auto build_image = [&](SolveDesc* sd, int k_from, size_t stage, size_t* lds_total, size_t* bm_extra = nullptr) {
-        const bool lean = lean_vectors && sd->k_blk <= std::max(2, k_from);
-        std::vector<PackEntry> packs;
-        std::vector<unsigned> relocs;
-        size_t off = stage + SOL_HEAD;   // LDS offset (from dyn_raw) of the next carve
-        auto carve = [&](size_t bytes) {
-            const size_t o = off;
-            off += r16(bytes);
-            return o;
-        };
-        auto set_off = [&](auto& field, size_t o) {
-            using T = std::remove_reference_t<decltype(field)>;
-            field = reinterpret_cast<T>(o);
-            relocs.push_back((unsigned)(reinterpret_cast<char*>(&field) - reinterpret_cast<char*>(sd)));
-        };
-        auto put = [&](auto& field, size_t n) {   // constant array: copied into the image
-            using T = std::remove_reference_t<decltype(field)>;
-            using E = std::remove_cv_t<std::remove_pointer_t<T>>;
-            const size_t o = carve(n * sizeof(E));
-            packs.push_back(PackEntry{(const void*)field, (unsigned)(o - stage), (unsigned)(n * sizeof(E))});
+    for (int k = std::max(k_from, sd->k_blk); k < std::min(sd->k_tiny, h->J); ++k)
+        if (plan.lpoly[(size_t)k] && k != sd->k_semi) {   // block-wide out of LDS: leading dimension 64, one row per lane
+            add_poly(k, 64);
+            bp_ld_max = std::max(bp_ld_max, 64);
+        }
+    for (int k = std::max(k_from, sd->k_tiny); k <= h->J; ++k) {
+        SolveLevel& T = sd->L[k];
+        const Level& lv = h->L[k];
+        const size_t N = (size_t)lv.A.nr;
+        if (plan.poly[(size_t)k] && sd->k_blk <= k && k != sd->k_semi) {
+            add_poly(k, poly_ld(N + (size_t)h->L[k + 1].P.nc));
+            continue;
+        }
+        auto add = [&](const double*& field, const Csr& m) {
+            const size_t o = carve(8 * (size_t)m.nr * m.nc);
+            lay.dense.push_back(DenseEntry{m.rp, m.ci, m.va, m.nr, m.nc, (unsigned)(o - stage), 0});
             set_off(field, o);
         };
-        int bp_ld_max = 0;
-        for (int k = k_from; k <= h->J; ++k) {     // constants first: they form the image
-            SolveLevel& T = sd->L[k];
-            const size_t N = (size_t)T.lv.N;
-            if (k == sd->k_semi) continue;         // matrix, transfers, dinv, Axi stay in global memory
-            if (((is_poly(k) && k >= sd->k_tiny) || (is_lpoly(k) && k < sd->k_tiny)) && sd->k_blk <= k) {   // polynomial form: no CSR arrays (see plan_lds)
-                put(T.lv.xx, 1);
-                T.lv.rp = T.lv.ci = nullptr;
-                T.lv.va = T.lv.dinv = T.lv.Axi = nullptr;
-                T.rest.rp = T.rest.ci = T.prol.rp = T.prol.ci = nullptr;
-                T.rest.va = T.prol.va = nullptr;
-                continue;
-            }
-            if (is_bpoly(k) && sd->k_blk <= k && k < sd->k_tiny) {   // block-wide polynomial form (see plan_lds)
-                put(T.lv.xx, 1);
-                T.lv.rp = T.lv.ci = nullptr;
-                T.lv.va = T.lv.dinv = T.lv.Axi = nullptr;
-                T.rest.rp = T.rest.ci = T.prol.rp = T.prol.ci = nullptr;
-                T.rest.va = T.prol.va = nullptr;
-                const BPolyDev& b = ensure_bpoly(k, sd->nu, sd->isnsp);
-                T.gM = b.M;
-                T.gW = b.W;
-                T.gLD = b.LD;
-                bp_ld_max = std::max(bp_ld_max, b.LD);
-                continue;
-            }
-            put(T.lv.rp, N + 1);
-            if (is_bdense(k) && sd->k_blk <= k && k < sd->k_tiny) {   // dense copy (carved below) instead of ci / va
-                T.blk_dense = 1;
-                T.lv.ci = nullptr;
-                T.lv.va = nullptr;
-            } else {
-                put(T.lv.ci, (size_t)T.nnzA);
-                put(T.lv.va, (size_t)T.nnzA);
-            }
-            put(T.lv.dinv, N);
-            put(T.lv.Axi, N);
-            put(T.lv.xx, 1);
-            if (k < h->J) {
-                const size_t Nc = (size_t)T.rest.nrows;
-                put(T.rest.rp, Nc + 1);
-                put(T.rest.ci, (size_t)T.nnzP);
-                put(T.rest.va, (size_t)T.nnzP);
-                put(T.prol.rp, N + 1);
-                put(T.prol.ci, (size_t)T.nnzP);
-                put(T.prol.va, (size_t)T.nnzP);
-            }
+        add(T.dA, lv.A);
+        if (k < h->J) {
+            add(T.dP, h->L[k + 1].P);
+            add(T.dPt, h->L[k + 1].Pt);
         }
-        std::vector<LmapEntry> lmaps;
-        for (int k = std::max(k_from, sd->k_blk); k < std::min(sd->k_tiny, h->J + 1); ++k) {
-            if (!use_lmap || k == sd->k_semi || k < 2 || h->L[k].A.nr > BT || k == h->J || sd->L[k].blk_dense || sd->L[k].gM || is_lpoly(k)) continue;
-            SolveLevel& T = sd->L[k];
-            const size_t o = carve(4 * (BT + 1));
-            lmaps.push_back(LmapEntry{h->L[k].A.rp, h->L[k].A.nr, (unsigned)(o - stage)});
-            set_off(T.lmap, o);
+        (void)N;
+    }
+    const size_t image_bytes = off - stage;
+    for (int k = k_from; k <= h->J; ++k) {     // work vectors: carved, not copied
+        SolveLevel& T = sd->L[k];
+        // (one-wave levels: zero-padded to whole 8-entry blocks, see sol_load_image)
+        // (dense thread-per-row levels: zero-padded to whole groups of four entries per lane, dense_row_dot)
+        // (block-wide polynomial levels and their children: whole 8-entry blocks as well, bpoly_pass)
+        const bool pad8 = k >= sd->k_tiny || T.gM || T.pMr || (k > k_from && (sd->L[k - 1].gM || sd->L[k - 1].pMr));
+        const size_t N = T.blk_dense ? (size_t)bdense_pad(T.lv.N) : pad8 ? plan_r8((size_t)T.lv.N) : (size_t)T.lv.N;
+        set_off(T.lv.r, carve(N * 8));
+        set_off(T.e, carve(N * 8));
+        set_off(T.e2, carve(N * 8));
+        if (lean && k >= 2) {   // never dereferenced on these levels (see LevelPlan::lean_vectors)
+            T.lv.rr = T.e2;
+            lay.relocs.push_back((unsigned)(reinterpret_cast<char*>(&T.lv.rr) - reinterpret_cast<char*>(sd)));
+            T.w = T.e2;
+            lay.relocs.push_back((unsigned)(reinterpret_cast<char*>(&T.w) - reinterpret_cast<char*>(sd)));
+        } else {
+            set_off(T.lv.rr, carve(N * 8));
+            set_off(T.w, carve(N * 8));
         }
-        std::vector<DenseEntry> dense;
-        std::vector<PolyEntry> polys;
-        size_t poly_lds = 0;
-        for (int k = k_from; k <= h->J; ++k) {
-            if (!sd->L[k].blk_dense) continue;
-            const Csr& m = h->L[k].A;
-            const int ld = bdense_ld(m.nr);
-            const size_t o = carve(8 * (size_t)m.nr * ld);
-            dense.push_back(DenseEntry{m.rp, m.ci, m.va, m.nr, m.nc, (unsigned)(o - stage), ld});
-            set_off(sd->L[k].dA, o);
+    }
+    if (bp_ld_max) set_off(sd->bp_part, carve(8 * (8 * (size_t)bp_ld_max + 8)));
+    for (int k = std::max(1, k_from - 1); k < h->J; ++k) {   // vectors that cross levels
+        SolveLevel& T = sd->L[k];
+        if (k >= k_from) {
+            T.rest.x = T.lv.rr;
+            lay.relocs.push_back((unsigned)(reinterpret_cast<char*>(&T.rest.x) - reinterpret_cast<char*>(sd)));
         }
-        auto add_poly = [&](int k, size_t LD) {
-            SolveLevel& T = sd->L[k];
-            const Level& lv = h->L[k];
-            const size_t N = (size_t)lv.A.nr;
-            const Csr& P = h->L[k + 1].P;
-            const size_t Nc = (size_t)P.nc;
-            const LevelDev& gd = st->run[(size_t)k].dev;   // global pointers (T's are LDS offsets by now)
-            PolyEntry pe;
-            pe.Arp = lv.A.rp;
-            pe.Aci = lv.A.ci;
-            pe.Ava = lv.A.va;
-            pe.Prp = P.rp;
-            pe.Pci = P.ci;
-            pe.Pva = P.va;
-            pe.dinv = gd.dinv;
-            pe.Axi = gd.Axi;
-            pe.xx = gd.xx;
-            pe.N = (int)N;
-            pe.Nc = (int)Nc;
-            pe.nu = sd->nu;
-            pe.isnsp = sd->isnsp;
-            pe.LD = (int)LD;
-            T.pLD = (int)LD;
-            size_t o = carve(8 * LD * r8(N));
-            pe.offMr = (unsigned)(o - stage);
-            set_off(T.pMr, o);
-            o = carve(8 * LD * r8(N));
-            pe.offMe = (unsigned)(o - stage);
-            set_off(T.pMe, o);
-            o = carve(8 * LD * r8(Nc));
-            pe.offMc = (unsigned)(o - stage);
-            set_off(T.pMc, o);
-            o = carve(8 * LD);
-            pe.offW = (unsigned)(o - stage);
-            set_off(T.pW, o);
-            polys.push_back(pe);
-            poly_lds = std::max(poly_lds, 8 * (5 * N * N + 2 * N * Nc + 4 * N) + 64);
-        };
-        for (int k = std::max(k_from, sd->k_blk); k < std::min(sd->k_tiny, h->J); ++k)
-            if (is_lpoly(k) && k != sd->k_semi) {   // block-wide out of LDS: leading dimension 64, one row per lane
-                add_poly(k, 64);
-                bp_ld_max = std::max(bp_ld_max, 64);
-            }
-        for (int k = std::max(k_from, sd->k_tiny); k <= h->J; ++k) {
-            SolveLevel& T = sd->L[k];
-            const Level& lv = h->L[k];
-            const size_t N = (size_t)lv.A.nr;
-            if (is_poly(k) && sd->k_blk <= k && k != sd->k_semi) {
-                add_poly(k, poly_ld(N + (size_t)h->L[k + 1].P.nc));
-                continue;
-            }
-            auto add = [&](const double*& field, const Csr& m) {
-                const size_t o = carve(8 * (size_t)m.nr * m.nc);
-                dense.push_back(DenseEntry{m.rp, m.ci, m.va, m.nr, m.nc, (unsigned)(o - stage), 0});
-                set_off(field, o);
-            };
-            add(T.dA, lv.A);
-            if (k < h->J) {
-                add(T.dP, h->L[k + 1].P);
-                add(T.dPt, h->L[k + 1].Pt);
-            }
-            (void)N;
-        }
-        const size_t image_bytes = off - stage;
-        for (int k = k_from; k <= h->J; ++k) {     // work vectors: carved, not copied
-            SolveLevel& T = sd->L[k];
-            // (one-wave levels: zero-padded to whole 8-entry blocks, see sol_load_image)
-            // (dense thread-per-row levels: zero-padded to whole groups of four entries per lane, dense_row_dot)
-            // (block-wide polynomial levels and their children: whole 8-entry blocks as well, bpoly_pass)
-            const bool pad8 = k >= sd->k_tiny || T.gM || T.pMr || (k > k_from && (sd->L[k - 1].gM || sd->L[k - 1].pMr));
-            const size_t N = T.blk_dense ? (size_t)bdense_pad(T.lv.N) : pad8 ? r8((size_t)T.lv.N) : (size_t)T.lv.N;
-            set_off(T.lv.r, carve(N * 8));
-            set_off(T.e, carve(N * 8));
-            set_off(T.e2, carve(N * 8));
-            if (lean && k >= 2) {   // never dereferenced on these levels (see lean_vectors)
-                T.lv.rr = T.e2;
-                relocs.push_back((unsigned)(reinterpret_cast<char*>(&T.lv.rr) - reinterpret_cast<char*>(sd)));
-                T.w = T.e2;
-                relocs.push_back((unsigned)(reinterpret_cast<char*>(&T.w) - reinterpret_cast<char*>(sd)));
-            } else {
-                set_off(T.lv.rr, carve(N * 8));
-                set_off(T.w, carve(N * 8));
-            }
-        }
-        if (bp_ld_max) set_off(sd->bp_part, carve(8 * (8 * (size_t)bp_ld_max + 8)));
-        for (int k = std::max(1, k_from - 1); k < h->J; ++k) {   // vectors that cross levels
-            SolveLevel& T = sd->L[k];
-            if (k >= k_from) {
-                T.rest.x = T.lv.rr;
-                relocs.push_back((unsigned)(reinterpret_cast<char*>(&T.rest.x) - reinterpret_cast<char*>(sd)));
-            }
-            T.rest.y = sd->L[k + 1].lv.r;
-            relocs.push_back((unsigned)(reinterpret_cast<char*>(&T.rest.y) - reinterpret_cast<char*>(sd)));
-        }
-        {
-            sd->pcg.rp = sd->L[h->J].lv.rp;
-            sd->pcg.ci = sd->L[h->J].lv.ci;
-            sd->pcg.va = sd->L[h->J].lv.va;
-            for (auto* f : {(const void**)&sd->pcg.rp, (const void**)&sd->pcg.ci, (const void**)&sd->pcg.va})
-                relocs.push_back((unsigned)(reinterpret_cast<char*>(f) - reinterpret_cast<char*>(sd)));
-            set_off(sd->pcg.work, carve(4 * (size_t)sd->L[h->J].lv.N * 8));
-        }
-        IPD_REQUIRE(relocs.size() <= (size_t)RELOC_MAX, IPD_E_LIMIT, "LDS image: too many relocations");
-        sd->image_bytes = (int)image_bytes;
-        sd->dbg_skip = std::getenv("IPD_DEBUG_SKIP") ? std::atoi(std::getenv("IPD_DEBUG_SKIP")) : 0;
-        sd->lds_total = (int)r16(off);
-        off = r16(off);
-        sd->nreloc = (int)relocs.size();
-        *lds_total = off;
-        // One block-wide polynomial level's operator as an LDS copy (SolveDesc::bm_src), for the launches that can
-        // afford bm_bytes more dynamic LDS (the resident kernels' tail workgroup): the deepest such level whose
-        // stacked operator has at most 128 rows and fits behind the work vectors.
-        sd->bm_src = nullptr;
-        sd->bm_level = sd->bm_ld = sd->bm_off = sd->bm_bytes = 0;
-        if (bm_extra) {
-            *bm_extra = 0;
-            for (int k = h->J - 1; k >= std::max(2, k_from); --k) {
-                const SolveLevel& T = sd->L[k];
-                if (!T.gM || T.gLD != 128) continue;
-                const size_t N = (size_t)T.lv.N, Nc = (size_t)h->L[k + 1].A.nr, rows = N + Nc;
-                if (rows > 128) continue;
-                const size_t ld = (rows + 1) & ~size_t(1), ncols = 8 * (2 * ((N + 7) / 8) + (Nc + 7) / 8);
-                const size_t need = 8 * ld * (ncols + 1);   // (ld even: a multiple of 16; the vector W behind the columns)
-                if (off + need > (size_t)156 * 1024) continue;
-                double* cp = ar.alloc<double>(ld * (ncols + 1));
-                hipLaunchKernelGGL(k_bm_compact, dim3((unsigned)ncols + 1), dim3(128), 0, ctx->stream, T.gM, 128, cp,
-                                   (int)ld, T.gW, (int)rows);
-                IPD_KERNEL_CHECK();
-                sd->bm_src = cp;
-                sd->bm_level = k;
-                sd->bm_ld = (int)ld;
-                sd->bm_off = (int)off;
-                sd->bm_bytes = (int)need;
-                *bm_extra = need;
-                break;
-            }
-        }
-        char* img = reinterpret_cast<char*>(ar.alloc_bytes(image_bytes));
-        // the image head and the pack descriptors go up in ONE copy: [head | packs | dense | lmaps | polys] in
-        // a scratch block, the head then moves into the image as one more entry of k_pack_image
-        auto r16b = [](size_t v) { return (v + 15) & ~size_t(15); };
-        const size_t o_packs = r16b(SOL_HEAD), o_dense = o_packs + r16b((packs.size() + 1) * sizeof(PackEntry)),
-                     o_lmaps = o_dense + r16b(dense.size() * sizeof(DenseEntry)),
-                     o_polys = o_lmaps + r16b(lmaps.size() * sizeof(LmapEntry)),
-                     o_end = o_polys + r16b(polys.size() * sizeof(PolyEntry));
-        char* stg = reinterpret_cast<char*>(ctx->scratch->alloc_bytes(o_end));
-        std::vector<char> hb(o_end, 0);
-        std::memcpy(hb.data(), sd, sizeof(SolveDesc));
-        std::memcpy(hb.data() + r16(sizeof(SolveDesc)), relocs.data(), relocs.size() * sizeof(unsigned));
-        {
-            PackEntry he{};
-            he.src = stg;
-            he.dst_off = 0;
-            he.bytes = (unsigned)SOL_HEAD;
-            packs.push_back(he);
-        }
-        std::memcpy(hb.data() + o_packs, packs.data(), packs.size() * sizeof(PackEntry));
-        if (!dense.empty()) std::memcpy(hb.data() + o_dense, dense.data(), dense.size() * sizeof(DenseEntry));
-        if (!lmaps.empty()) std::memcpy(hb.data() + o_lmaps, lmaps.data(), lmaps.size() * sizeof(LmapEntry));
-        if (!polys.empty()) std::memcpy(hb.data() + o_polys, polys.data(), polys.size() * sizeof(PolyEntry));
-        ctx->upload_bytes(stg, hb.data(), o_end);
-        hipLaunchKernelGGL(k_pack_image, dim3((unsigned)packs.size()), dim3(256), 0, ctx->stream,
-                           reinterpret_cast<const PackEntry*>(stg + o_packs), img);
-        IPD_KERNEL_CHECK();
-        if (!dense.empty()) {
-            hipLaunchKernelGGL(k_pack_dense, dim3((unsigned)dense.size()), dim3(256), 0, ctx->stream,
-                               reinterpret_cast<const DenseEntry*>(stg + o_dense), img);
-            IPD_KERNEL_CHECK();
-        }
-        if (!lmaps.empty()) {
-            hipLaunchKernelGGL(k_pack_lmap, dim3((unsigned)lmaps.size()), dim3(BT), 0, ctx->stream,
-                               reinterpret_cast<const LmapEntry*>(stg + o_lmaps), img);
-            IPD_KERNEL_CHECK();
-        }
-        if (!polys.empty()) {
-            IPD_OPTIN_LDS(ctx, k_pack_poly, 156 * 1024);
-            hipLaunchKernelGGL(k_pack_poly, dim3((unsigned)polys.size()), dim3(BT), poly_lds, ctx->stream,
-                               reinterpret_cast<const PolyEntry*>(stg + o_polys), img);
-            IPD_KERNEL_CHECK();
-        }
-        st->level_forms.resize((size_t)h->J + 1, 0);
-        for (int k = std::max(k_from, sd->k_blk); k <= h->J; ++k) {
-            const SolveLevel& T = sd->L[k];
-            if (k == sd->k_semi) continue;
-            st->level_forms[(size_t)k] |= T.gM ? 16 : T.pMr ? (k >= sd->k_tiny ? 8 : 32) : k >= sd->k_tiny ? 4 : T.blk_dense ? 2 : 1;
-        }
-        return reinterpret_cast<SolveDesc*>(img);
-    };
+        T.rest.y = sd->L[k + 1].lv.r;
+        lay.relocs.push_back((unsigned)(reinterpret_cast<char*>(&T.rest.y) - reinterpret_cast<char*>(sd)));
+    }
+    {
+        sd->pcg.rp = sd->L[h->J].lv.rp;
+        sd->pcg.ci = sd->L[h->J].lv.ci;
+        sd->pcg.va = sd->L[h->J].lv.va;
+        for (auto* f : {(const void**)&sd->pcg.rp, (const void**)&sd->pcg.ci, (const void**)&sd->pcg.va})
+            lay.relocs.push_back((unsigned)(reinterpret_cast<char*>(f) - reinterpret_cast<char*>(sd)));
+        set_off(sd->pcg.work, carve(4 * (size_t)sd->L[h->J].lv.N * 8));
+    }
+    IPD_REQUIRE(lay.relocs.size() <= (size_t)RELOC_MAX, IPD_E_LIMIT, "LDS image: too many relocations");
+    sd->image_bytes = (int)image_bytes;
+    const char* skip = switch_value("IPD_DEBUG_SKIP");
+    sd->dbg_skip = skip ? std::atoi(skip) : 0;
+    sd->lds_total = (int)plan_r16(off);
+    off = plan_r16(off);
+    sd->nreloc = (int)lay.relocs.size();
+    size_t bm = 0;
+    SolveDesc* img = upload_image(ctx, h, st, sd, k_from, off, image_bytes, lay, spec.role == IMG_SOLVE ? nullptr : &bm);
+    switch (spec.role) {
+    case IMG_SOLVE:
+        st->d_solve = img;
+        st->solve_lds = off;
+        break;
+    case IMG_SUB:
+        st->d_sub = img;
+        st->sub_lds = off;
+        st->sub_bm = bm;
+        st->k_sub = plan.k_sub;
+        st->sub_semi_root = plan.sub_semi_root;
+        break;
+    case IMG_SUB3:
+        st->d_sub3 = img;
+        st->sub3_lds = off;
+        st->sub3_bm = bm;
+        break;
+    case IMG_SUB4:
+        st->d_sub4 = img;
+        st->sub4_lds = off;
+        st->sub4_bm = bm;
+        break;
+    case IMG_NONE:
+        break;
+    }
+}
+
+static PlanSwitches read_plan_switches() {
+    PlanSwitches s;
+    s.no_poly = switch_on("IPD_NO_POLY");
+    s.no_blk = switch_on("IPD_NO_BLK");
+    s.no_bpoly = switch_on("IPD_NO_BPOLY");
+    s.no_blkdense = switch_on("IPD_NO_BLKDENSE");
+    s.no_small = switch_on("IPD_NO_SMALL");
+    s.no_subcycle = switch_on("IPD_NO_SUBCYCLE");
+    s.no_resident = switch_on("IPD_NO_RESIDENT");
+    s.no_resident_remote = switch_on("IPD_NO_RESIDENT_REMOTE");
+    s.no_resident_three = switch_on("IPD_NO_RESIDENT_THREE");
+    s.no_resident_deep = switch_on("IPD_NO_RESIDENT_DEEP");
+    s.no_resident_big = switch_on("IPD_NO_RESIDENT_BIG");
+    s.no_res_poly4 = switch_on("IPD_NO_RES_POLY4");
+    return s;
+}
+
+static const char* const IMAGE_ROLE_NAMES[] = {"solve", "sub", "sub3", "sub4", "none"};
+
+void amg_prepare_levels(ipd_amg* h) {
+    std::unique_ptr<CycleState> st(new CycleState());
+    st->run.resize((size_t)h->J + 1);
+    prepare_level_runs(h, st.get());
+    prepare_transfers(h, st.get());
+    // single-workgroup kernels: which levels, in which form, in which LDS images (ipd_level_plan.h)
+    std::vector<LevelShape> shapes((size_t)h->J + 1);
+    for (int k = 1; k <= h->J; ++k) {
+        const Level& lv = h->L[k];
+        LevelShape& s = shapes[(size_t)k];
+        s.nr = lv.A.nr;
+        s.nnz = lv.A.nnz;
+        s.nf = lv.nf;
+        s.maxoff = st->run[(size_t)k].maxoff;
+        s.p_nnz = k >= 2 ? lv.P.nnz : 0;
+    }
+    PlanOptions po;
+    po.cycle = h->opts.cycle;
+    po.smoth = h->opts.smoth;
+    po.twogrid = h->opts.twogrid;
+    po.concurrent_pair = h->opts.concurrent_pair;
+    po.sol_head = SOL_HEAD;
+    const PlanSwitches sw = read_plan_switches();
+    const LevelPlan plan = plan_levels(shapes.data(), h->J, po, sw);
+    const bool debug = switch_on("IPD_DEBUG_LEVELS");
+    if (debug)
+        for (const ImageSpec& s : plan.images)
+            std::fprintf(stderr, "[ipd] image %s: k_lds=%d k_semi=%d k_tiny=%d k_blk=%d stage=%zu lds=%zu%s\n",
+                         IMAGE_ROLE_NAMES[s.role], s.k_lds, s.k_semi, s.k_tiny, s.k_blk, s.stage_bytes, s.lds,
+                         plan.sub5 == s.role ? " (level-5 tail)" : "");
+    ipd_ctx* ctx = h->ctx;
     IPD_OPTIN_LDS(ctx, k_solve_small<true>, 156 * 1024);
     IPD_OPTIN_LDS(ctx, k_solve_small<false>, 156 * 1024);
     IPD_OPTIN_LDS(ctx, k_subcycle, 156 * 1024);
-    // Level 2 as a semi-cached level (r, e, e2 in LDS; matrix rows from L2) with levels 3..J fully
-    // cached: returns the dynamic LDS needed behind a staging area of `stage` bytes, 0 = no
-    auto semi_plan = [&](size_t stage) -> size_t {
-        if (!lean_vectors || h->J < 3 || h->J > SOLVE_ML) return 0;
-        const Level& l2 = h->L[2];
-        if (l2.A.nr > BT || l2.A.nr <= 64 || (double)l2.A.nnz > 12.0 * l2.A.nr ||
-            (double)h->L[3].P.nnz > 12.0 * l2.A.nr)
-            return 0;
-        for (int k = 3; k <= h->J; ++k)
-            if (!small_level(k)) return 0;
-        size_t used = 0;
-        const int k_lds = plan_lds(stage, &used);
-        if (k_lds != 3) return 0;   // <= 2: level 2 fits entirely; > 3: a deeper level does not
-        const size_t need = used + 3 * r16(8 * (size_t)l2.A.nr);
-        return need <= 150 * 1024 ? need : 0;
-    };
-    if (!st->small_ok) {
-        const char* ns = std::getenv("IPD_NO_SMALL");
-        bool ok = !(ns && ns[0] == '1') && h->J <= SOLVE_ML;
-        size_t maxlen = 1;
-        for (int k = 1; k <= h->J && ok; ++k) {
-            ok = ok && small_level(k);
-            maxlen = std::max(maxlen, (size_t)h->L[k].A.nr);
-        }
-        if (ok) {
-            std::unique_ptr<SolveDesc> sd(new SolveDesc());
-            fill_desc(sd.get());
-            const size_t stage = r16(sizeof(double) * maxlen);
-            size_t used = 0;
-            int k_lds = plan_lds(stage, &used);
-            sd->k_lds = k_lds;
-            st->solve_cached = k_lds <= h->J;
-            sd->k_tiny = tiny_from(k_lds);
-            sd->k_blk = blk_from(k_lds);
-            sd->stage_bytes = (int)stage;
-            st->solve_lds = used;
-            if (st->solve_cached) {
-                st->d_solve = build_image(sd.get(), k_lds, stage, &st->solve_lds);
-            } else {
-                st->d_solve = reinterpret_cast<SolveDesc*>(ar.alloc_bytes(sizeof(SolveDesc)));
-                ctx->upload_bytes(st->d_solve, sd.get(), sizeof(SolveDesc));
-            }
-            st->solve_out = ar.alloc<double>(4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2));
-            st->small_ok = true;
-        }
+    for (const ImageSpec& s : plan.images) pack_image(ctx, h, st.get(), plan, s);
+    if (plan.small_ok) {
+        st->solve_out = h->arena->alloc<double>(4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2));
+        st->small_ok = true;
     }
-    {
-        const char* ns = std::getenv("IPD_NO_SUBCYCLE");
-        const bool want = !(ns && ns[0] == '1') && !st->small_ok && h->J <= SOLVE_ML && h->J >= 3 &&
-                          (h->opts.cycle == 'w' || h->opts.cycle == 'v');
-        bool semi_done = false;
-        if (want && semi_plan(16) != 0) {   // (b1) the sub-cycle is rooted at the semi-cached level 2
-            const size_t stage = 16;
-            std::unique_ptr<SolveDesc> sd(new SolveDesc());
-            fill_desc(sd.get());
-            sd->k_lds = 2;
-            sd->k_semi = 2;
-            sd->k_tiny = tiny_from(3);
-            sd->k_blk = blk_from(2);
-            sd->stage_bytes = (int)stage;
-            sd->root_r = h->L[2].r;
-            sd->root_e = h->L[2].e;
-            st->k_sub = 2;
-            st->d_sub = build_image(sd.get(), 2, stage, &st->sub_lds, &st->sub_bm);
-            semi_done = true;
-        }
-        if (want && !semi_done) {
-            // first level from which every level is small ...
-            int k_small = h->J + 1;
-            for (int k = h->J; k >= 2 && small_level(k); --k) k_small = k;
-            // Level 1 of 2049..4096 rows, six levels or more: the mask-form resident kernel's deep mode keeps
-            // levels 3 AND 4 in polynomial form in its workgroups and roots its tail workgroup at level 5
-            // (ipd_resident_big.h, POLY4) -- ONE image, rooted at level 5, serves it and the launches (which
-            // then run level 4 as launches: the fall-back).  (An image rooted at level 4 for the launches
-            // beside one rooted at level 5 for the resident kernel packed levels 5..J twice: 0.2 ms per hierarchy.)
-            const int nf1 = h->L[1].nf, nc1 = h->L[1].A.nr - nf1;
-            const bool root5 = h->J >= 6 && h->L[1].A.nr > RES_NMAX && nf1 > 0 && nf1 <= RB_HALF && nc1 <= RB_HALF &&
-                               h->L[2].A.nr == nc1 && h->L[3].A.nr <= RB_N3MAX && h->L[4].A.nr <= RB_N4MAX &&
-                               h->L[5].A.nr <= RB_N5MAX && h->opts.smoth >= 1 && !h->opts.twogrid && !h->opts.concurrent_pair &&
-                               !(std::getenv("IPD_NO_RES_POLY4") && std::getenv("IPD_NO_RES_POLY4")[0] == '1') &&
-                               !(std::getenv("IPD_NO_RESIDENT_DEEP") && std::getenv("IPD_NO_RESIDENT_DEEP")[0] == '1') &&
-                               !(std::getenv("IPD_NO_RESIDENT_BIG") && std::getenv("IPD_NO_RESIDENT_BIG")[0] == '1') &&
-                               !(std::getenv("IPD_NO_RESIDENT") && std::getenv("IPD_NO_RESIDENT")[0] == '1');
-            if (root5) k_small = std::max(k_small, 5);
-            if (k_small < h->J) {
-                // ... and everything below it fits in LDS (the stage area holds N_root doubles)
-                for (int kroot = k_small; kroot < h->J; ++kroot) {
-                    // the generic phases (and their staging vector) only run when IPD_NO_BLK is set
-                    const size_t stage = lean_vectors ? 16 : r16(sizeof(double) * (size_t)h->L[kroot].A.nr);
-                    size_t used = 0;
-                    const int k_lds = plan_lds(stage, &used);
-                    // the root itself does not fit beside the deeper levels but has at most BT rows (a
-                    // level 3 of 170-310 rows with 40-100 entries each in the m=n=1024 runs): it becomes a
-                    // semi-cached root -- vectors in LDS, rows walked from L2 by several lanes each
-                    // (glb_rowdot_range), 2-3 us per sweep against 5 us for the launch it replaces
-                    bool semi_root = false;
-                    // (only with short rows, <= 12 entries on average like the semi-cached level 2: measured on
-                    // the Newton systems of the m=n=1024 Class 1 run, a level 3 of 2-3 k entries gains 5-9 % per W
-                    // cycle as launches and opens the hierarchy to the resident kernel's remote tail, -15...-23 %;
-                    // with 4 k entries it loses 12 %, with 9-17 k entries a sweep from L2 through one CU costs
-                    // more than the launch: 0.72 -> 1.09 ms, 0.54 -> 1.21 ms per W cycle)
-                    if (k_lds == kroot + 1 && kroot >= 3 && lean_vectors && h->L[kroot].A.nr <= BT &&
-                        (double)h->L[kroot].A.nnz <= 12.0 * h->L[kroot].A.nr &&
-                        (double)h->L[kroot + 1].P.nnz <= 12.0 * h->L[kroot].A.nr &&
-                        used + 3 * r16(8 * (size_t)h->L[kroot].A.nr) <= 150 * 1024) {
-                        semi_root = true;
-                    }
-                    if (k_lds > kroot && !semi_root) continue;
-                    std::unique_ptr<SolveDesc> sd(new SolveDesc());
-                    fill_desc(sd.get());
-                    sd->k_lds = kroot;
-                    if (semi_root) sd->k_semi = kroot;
-                    sd->k_tiny = tiny_from(kroot + (semi_root ? 1 : 0));
-                    sd->k_blk = blk_from(kroot);
-                    sd->stage_bytes = (int)stage;
-                    sd->root_r = h->L[kroot].r;
-                    sd->root_e = h->L[kroot].e;
-                    st->k_sub = kroot;
-                    st->sub_semi_root = semi_root;
-                    st->d_sub = build_image(sd.get(), kroot, stage, &st->sub_lds, &st->sub_bm);
-                    break;
-                }
-            }
-        }
-    }
-    // (b2) Where level 3 is only a semi-cached root (its rows come from L2), the level-resident kernel
-    // does better with level 3 in registers and its tail rooted at level 4 (plan_resident, `three`:
-    // 0.50-0.51 against 0.57-0.61 ms per W cycle on the Newton systems of the m=n=1024 Class 1 run), so a
-    // second image rooted at level 4 is packed for it.  (Where levels 3..J fit the image as they are,
-    // the tail rooted at level 3 stays 3-6 % ahead: 0.49-0.51 against 0.51-0.54 ms.)
-    // With level 3 in polynomial form (plan_resident, poly3: a visit of it is three hand-offs instead of
-    // thirteen) the same holds wherever that form applies, semi-cached root or not: 0.33-0.36 -> see DESIGN.
-    const bool poly3_likely =
-        h->J >= 5 && h->opts.smoth >= 1 && h->L[1].nf > 0 &&
-        h->L[4].A.nr <= 128 &&
-        h->L[4].A.nr <= std::max(cdiv(std::max(h->L[1].nf, h->L[1].A.nr - h->L[1].nf), RES_WAVES), cdiv(h->L[2].A.nr, RES_WAVES)) &&
-        !(std::getenv("IPD_NO_POLY") && std::getenv("IPD_NO_POLY")[0] == '1');
-    if (st->k_sub == 3 && (st->sub_semi_root || poly3_likely) && st->d_sub && h->J >= 5 && h->J <= SOLVE_ML && h->L[3].A.nr <= BT &&
-        h->L[4].A.nr <= BT && st->run[3].maxoff <= 512 && h->L[1].nf > 0 &&
-        !(std::getenv("IPD_NO_RESIDENT_THREE") && std::getenv("IPD_NO_RESIDENT_THREE")[0] == '1') &&
-        !(std::getenv("IPD_NO_RESIDENT") && std::getenv("IPD_NO_RESIDENT")[0] == '1')) {
-        const size_t stage = 16;
-        size_t used = 0;
-        bool ok = lean_vectors;
-        for (int k = 4; k <= h->J && ok; ++k) ok = small_level(k);
-        if (ok && plan_lds(stage, &used) <= 4) {
-            std::unique_ptr<SolveDesc> sd(new SolveDesc());
-            fill_desc(sd.get());
-            sd->k_lds = 4;
-            sd->k_tiny = tiny_from(4);
-            sd->k_blk = blk_from(4);
-            sd->stage_bytes = (int)stage;
-            sd->root_r = h->L[4].r;
-            sd->root_e = h->L[4].e;
-            st->d_sub4 = build_image(sd.get(), 4, stage, &st->sub4_lds, &st->sub4_bm);
-        }
-    }
-    // (b3) No sub-cycle at all because level 3's interpolation is big (P_3 with more than 40 k entries:
-    // a dense 1024 x 50 block early in a run), although levels 3..J themselves are small: the launch
-    // path would gain nothing from an image whose restriction and prolongation stay launches, but the
-    // resident kernel's remote tail does not use P_3 from the image -- its workgroups apply it -- so an
-    // image rooted at level 3 is packed for it alone.
-    if (st->k_sub == 0 && !st->small_ok && h->J >= 4 && h->J <= SOLVE_ML && lean_vectors && h->L[3].A.nr <= BT &&
-        h->L[1].nf > 0 && (h->opts.cycle == 'w' || h->opts.cycle == 'v') &&
-        !(std::getenv("IPD_NO_RESIDENT") && std::getenv("IPD_NO_RESIDENT")[0] == '1') &&
-        !(std::getenv("IPD_NO_SUBCYCLE") && std::getenv("IPD_NO_SUBCYCLE")[0] == '1')) {
-        bool ok = true;
-        for (int k = 3; k <= h->J && ok; ++k)
-            ok = h->L[k].A.nr <= 1024 && h->L[k].A.nnz <= 40000 && (k == 3 || h->L[k].P.nnz <= 40000);
-        const size_t stage = 16;
-        size_t used = 0;
-        if (ok && plan_lds(stage, &used) <= 3) {
-            std::unique_ptr<SolveDesc> sd(new SolveDesc());
-            fill_desc(sd.get());
-            sd->k_lds = 3;
-            sd->k_tiny = tiny_from(3);
-            sd->k_blk = blk_from(3);
-            sd->stage_bytes = (int)stage;
-            sd->root_r = h->L[3].r;
-            sd->root_e = h->L[3].e;
-            st->d_sub3 = build_image(sd.get(), 3, stage, &st->sub3_lds, &st->sub3_bm);
-        }
-    }
-    // (b4) the image rooted at level 5 (see root5 above) is the one the deep mode's tail workgroup takes
-    if (st->k_sub == 5 && st->d_sub && !st->sub_semi_root && h->J >= 6 && h->L[1].A.nr > RES_NMAX) {
+    if (plan.sub5 == IMG_SUB) {
         st->d_sub5 = st->d_sub;
         st->sub5_lds = st->sub_lds;
+    } else if (plan.sub5 == IMG_SUB4) {
+        st->d_sub5 = st->d_sub4;
+        st->sub5_lds = st->sub4_lds;
     }
-    // (b5) ... and k_resident's POLY3 mode (level 1 of at most 2048 rows) keeps level 4 in polynomial form in its
-    // workgroups as well when there are six levels or more (ResDesc::p4rows).  Its tail workgroup takes the
-    // image rooted at level 4 that the POLY3 mode uses anyway and enters it at level 5 (an image of its own,
-    // rooted at level 5, packed levels 5..J a second time: +85 us per hierarchy, more than the cycles gained).
-    if (!st->d_sub5 && poly3_likely && h->J >= 6 && h->L[1].A.nr <= RES_NMAX &&
-        ((st->k_sub == 3 && st->d_sub4) || (st->k_sub == 4 && st->d_sub && !st->sub_semi_root)) &&
-        h->L[4].A.nr <= RES_P4_SEG && h->L[5].A.nr <= 64 &&
-        !(std::getenv("IPD_NO_RES_POLY4") && std::getenv("IPD_NO_RES_POLY4")[0] == '1')) {
-        st->d_sub5 = st->k_sub == 3 ? st->d_sub4 : st->d_sub;
-        st->sub5_lds = st->k_sub == 3 ? st->sub4_lds : st->sub_lds;
-    }
-    plan_resident(h, st.get());
-    if (const char* dbg = std::getenv("IPD_DEBUG_LEVELS"); dbg && dbg[0] == '1') {
+    plan_resident(h, st.get(), sw);
+    if (debug) {
         std::fprintf(stderr, "[ipd] J=%d small=%d k_sub=%d resident=%d(G=%d,KE=%d) levels:", h->J,
                      (int)st->small_ok, st->k_sub, (int)st->res_ok, st->res_G, st->res_ke);
         for (int k = 1; k <= h->J; ++k) std::fprintf(stderr, " %d/%d", h->L[k].A.nr, h->L[k].A.nnz);
@@ -1875,7 +1643,7 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
     const bool for_resident = st->res_ok && !st->res_desc.three && st->res_desc.wident && h->J == 3 &&
                               true;
     bool sweeps_too = !transfers_only;
-    const bool big_forced = std::getenv("IPD_RESIDENT_BIG") && std::getenv("IPD_RESIDENT_BIG")[0] == '1';
+    const bool big_forced = switch_on("IPD_RESIDENT_BIG");
     // Realistic hierarchy with a level 1 beyond k_resident's 2048 rows (the Newton systems of the m = n = 2048
     // runs): candidate for the mask-form kernel's DEEP mode (ipd_resident_big.h) -- it needs the bit mask
     // whatever the population of the rows
@@ -1883,9 +1651,6 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
     size_t deep_img_lds = 0;
     bool deep_cand = false;
     {
-        const char* nrs = std::getenv("IPD_NO_RESIDENT");
-        const char* nbg = std::getenv("IPD_NO_RESIDENT_BIG");
-        const char* ndp = std::getenv("IPD_NO_RESIDENT_DEEP");
         const bool cyc = h->opts.cycle == 'w' || h->opts.cycle == 'v';
         if ((st->k_sub == 4 && st->d_sub) || (st->k_sub == 5 && st->d_sub5)) {   // (rooted at 5: POLY4 only, below)
             deep_img = st->d_sub;
@@ -1894,7 +1659,7 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
             deep_img = st->d_sub4;
             deep_img_lds = st->sub4_lds;
         }
-        deep_cand = !(nrs && nrs[0] == '1') && !(nbg && nbg[0] == '1') && !(ndp && ndp[0] == '1') && !st->res_off &&
+        deep_cand = !switch_on("IPD_NO_RESIDENT") && !switch_on("IPD_NO_RESIDENT_BIG") && !switch_on("IPD_NO_RESIDENT_DEEP") && !st->res_off &&
                     !st->res_ok && !st->resb && !st->small_ok && !h->opts.twogrid && cyc && h->opts.smoth >= 1 &&
                     h->J >= 5 && (n + m > RES_NMAX || big_forced) && n <= RB_HALF && m <= RB_HALF && lv.nf == n &&
                     lv.N == m + n && h->L[2].A.nr == m && h->L[3].A.nr <= RB_N3MAX && h->L[4].A.nr <= RB_N4MAX &&
@@ -1902,8 +1667,7 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
     }
     if (transfers_only && !for_resident && !big_forced && !deep_cand) return false;
     if (policy) {
-        const char* on = std::getenv("IPD_MASKOP");
-        if (!(on && on[0] == '1') && (double)lv.A.nnz < 4.0e6) {
+        if (!switch_on("IPD_MASKOP") && (double)lv.A.nnz < 4.0e6) {
             if (!for_resident && !deep_cand) return false;
             sweeps_too = false;   // below the size where the mask SWEEPS of the launch path pay
         }
@@ -1967,13 +1731,10 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
     // one-row tail: the mask-form resident kernel (ipd_resident_big.h).  IPD_RESIDENT_BIG=1 prefers it
     // wherever it applies (tests), IPD_NO_RESIDENT_BIG=1 switches it off.
     {
-        const char* nrs = std::getenv("IPD_NO_RESIDENT");
-        const char* nbg = std::getenv("IPD_NO_RESIDENT_BIG");
-        const char* fbg = std::getenv("IPD_RESIDENT_BIG");
-        const bool forced = fbg && fbg[0] == '1';
+        const bool forced = switch_on("IPD_RESIDENT_BIG");
         const bool cyc = h->opts.cycle == 'w' || h->opts.cycle == 'v';
         const int G = cdiv(std::max(n, m), RES_WAVES);
-        if (!(nrs && nrs[0] == '1') && !st->res_off && !(nbg && nbg[0] == '1') &&
+        if (!switch_on("IPD_NO_RESIDENT") && !st->res_off && !switch_on("IPD_NO_RESIDENT_BIG") &&
             (forced || (!st->res_ok && n + m > RES_NMAX)) && !st->small_ok &&
             !st->resb && h->J == 3 && h->L[3].A.nr == 1 && n <= RB_HALF && m <= RB_HALF && h->L[2].A.nr == m && cyc &&
             !h->opts.twogrid && G <= st->num_cu && G <= std::min(n, m) && h->opts.smoth >= 1) {
@@ -2042,7 +1803,7 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
                 B.presleep = 13;
                 const size_t gbytes = (size_t)RB_GRAN * 16;
                 B.ranks = 1;   // rank groups with a granule buffer each (test hook, see ResBigDesc::ranks)
-                if (const char* e = std::getenv("IPD_RESIDENT_RANKS")) B.ranks = std::max(1, std::min(8, std::atoi(e)));
+                if (const char* e = switch_value("IPD_RESIDENT_RANKS")) B.ranks = std::max(1, std::min(8, std::atoi(e)));
                 if (B.ranks > G) B.ranks = 1;
                 st->res_block_bytes = (size_t)B.ranks * 2 * gbytes + 16;
                 st->res_block = reinterpret_cast<unsigned char*>(ar.alloc_bytes(st->res_block_bytes));
@@ -2058,7 +1819,7 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
                 st->res_lds = RB_LDS_BYTES;
                 st->res_capacity = -1;
                 st->res_desc.dbg_skip_seq = 0;
-                if (const char* e = std::getenv("IPD_RES_DEBUG_SKIP_PUBLISH")) st->res_desc.dbg_skip_seq = (unsigned)std::max(0, std::atoi(e));
+                if (const char* e = switch_value("IPD_RES_DEBUG_SKIP_PUBLISH")) st->res_desc.dbg_skip_seq = (unsigned)std::max(0, std::atoi(e));
                 if (!st->res_out) st->res_out = ar.alloc<double>(4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2));
                 st->res_ok = true;
             }
@@ -2071,7 +1832,7 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
     if (deep_cand && !st->resb) {
         const int N3 = h->L[3].A.nr, N4 = h->L[4].A.nr;
         int G = std::max(std::max(cdiv(std::max(n, m), 2 * RES_WAVES), cdiv(N3, 4)), std::max(N4, 128));
-        if (const char* e = std::getenv("IPD_RESIDENT_G")) G = std::max(G, std::atoi(e));
+        if (const char* e = switch_value("IPD_RESIDENT_G")) G = std::max(G, std::atoi(e));
         LevelDev d2 = st->run[2].dev;
         if (d2.S <= 0 && st->run[2].maxoff > 0) d2.S = -((st->run[2].maxoff + 3) / 4 * 4);   // private copy wanted
         const int S2 = std::abs(d2.S);
@@ -2180,7 +1941,7 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
                 st->res_lds = std::max(RB_LDS_BYTES, deep_img_lds);
                 st->res_capacity = -1;
                 st->res_desc.dbg_skip_seq = 0;
-                if (const char* e = std::getenv("IPD_RES_DEBUG_SKIP_PUBLISH")) st->res_desc.dbg_skip_seq = (unsigned)std::max(0, std::atoi(e));
+                if (const char* e = switch_value("IPD_RES_DEBUG_SKIP_PUBLISH")) st->res_desc.dbg_skip_seq = (unsigned)std::max(0, std::atoi(e));
                 if (!st->res_out) st->res_out = ar.alloc<double>(4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2));
                 st->res_ok = true;
             }
@@ -2306,8 +2067,7 @@ void amg_cycle(ipd_amg* h, int k, int isnsp, bool wcycle, bool keep_e) {
     XferArgs ra = rn.restrict_args;
     const bool rest_small =
         ra.staged && phase_is_small(st, ra.nrows, ra.L, (double)h->L[k + 1].Pt.nnz, ra.ncols);
-    const char* nrrc = std::getenv("IPD_NO_RRC");
-    const bool no_rrc = nrrc && nrrc[0] == '1';
+    const bool no_rrc = switch_on("IPD_NO_RRC");
     const Csr& T1 = h->L[k + 1].T1;
     // Fused where the two launches are latency-bound (measured: tree-mask W cycle 0.432 -> 0.413 ms,
     // realistic Newton systems -2...-3.5 %); once T1 is megabytes the pair is bandwidth-bound and the
@@ -2866,8 +2626,7 @@ extern "C" int ipd_amg_bench_cycles(ipd_amg* h, const double* b_dev, double* x_d
                 return;
             }
         }
-        const char* ng = std::getenv("IPD_NO_GRAPH");
-        const bool use_graph = !(ng && ng[0] == '1');
+        const bool use_graph = !switch_on("IPD_NO_GRAPH");
         IPD_HIP(hipMemcpyAsync(h->x, x_dev, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
                                ctx->stream));
         // initial residual (Class_AMG.m:89); x stays in h->x
@@ -3004,7 +2763,7 @@ extern "C" int ipd_amg_bench_cycles_sharded(ipd_amg* h, const double* b_dev, dou
         CallScope scope(ctx);
         CycleState* st = state_of(h);
         IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
-        const char* emu = std::getenv("IPD_SHARD_EMULATE");
+        const char* emu = switch_value("IPD_SHARD_EMULATE");
         const int emu_ranks = emu ? std::atoi(emu) : 0;
         struct Restore {
             CycleState* st;

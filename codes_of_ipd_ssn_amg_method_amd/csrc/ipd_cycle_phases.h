@@ -28,7 +28,6 @@
 // 8 was slower on every workload (m=n=1024 Class 1 run 1.58 -> 1.55 s, tree-mask W cycle
 // 0.532 -> 0.503 ms): short rows fill 3-6 of the slots and the rest are clamped dummy loads.
 static constexpr int ROW_U = 4;
-static constexpr int STAGE_MAX = 7680;   // vector entries staged in LDS (60 KiB)
 
 // LDS scratch of a phase
 struct PhaseLds {

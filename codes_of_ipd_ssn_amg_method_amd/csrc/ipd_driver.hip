@@ -1677,10 +1677,7 @@ extern "C" int ipd_apd_create(ipd_ctx* ctx, const ipd_apd_data* d, ipd_apd** out
         h->s_prev = A.alloc<unsigned long long>(h->s_words);
         if (d->cls == 2) h->t_prev = A.alloc<unsigned long long>((size_t)h->M);
         h->step_changed = A.alloc<int>(1);
-        {
-            const char* e = getenv("IPD_NO_STEP_DONOR");
-            h->step_reuse = !(e && e[0] == '1');
-        }
+        h->step_reuse = !switch_on("IPD_NO_STEP_DONOR");
         const Geo& g = h->geo;
         h->lpart = A.alloc<double>((size_t)g.njg * m);
         h->rpart = A.alloc<double>((size_t)g.nib * 4 * n);

@@ -522,10 +522,10 @@ static std::function<void(int*, double*)> class_amg_prepare(
 static void dump_system(ipd_ctx* ctx, const Csr& Ae, const double* f, int nf) {
     static std::atomic<int> calls{0};
     const int call = calls++;
-    const char* prefix = getenv("IPD_DUMP_SYSTEM");
+    const char* prefix = switch_value("IPD_DUMP_SYSTEM");
     if (!prefix) return;
     int lo = 0, hi = 0;
-    if (const char* e = getenv("IPD_DUMP_CALLS")) {
+    if (const char* e = switch_value("IPD_DUMP_CALLS")) {
         if (sscanf(e, "%d-%d", &lo, &hi) < 2) hi = lo;
     }
     if (call < lo || call > hi) return;
@@ -842,8 +842,7 @@ void amg4pot_dev(ipd_ctx* ctx, const Csr& H0, const double* tdiag, const double*
                  const double* q, int m, int n, double bk1, double tk, const double* z,
                  const uint8_t* s, const double* phi, const AmgOpts& opts, ipd_rng* rng,
                  double* zeta, HybridOut* out, StepDonors* step) {
-    const char* nc = getenv("IPD_NO_POT_CONCURRENT");
-    const bool concurrent = !(nc && nc[0] == '1');
+    const bool concurrent = !switch_on("IPD_NO_POT_CONCURRENT");
     HybridCache cache;
     if (!concurrent) {
         if (step) step->prev.clear();
@@ -863,8 +862,7 @@ void amg4pot_dev(ipd_ctx* ctx, const Csr& H0, const double* tdiag, const double*
     popts.concurrent_pair = true;
     Deferred first, second;
     bool have_first = false;
-    const char* nd = getenv("IPD_NO_DONOR");
-    const bool donors = !(nd && nd[0] == '1');
+    const bool donors = !switch_on("IPD_NO_DONOR");
     if (step && !donors) step->prev.clear();
     auto solve = [&](const double* rhs, double* x, HybridOut* o) {
         if (!have_first) {

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "ipd_amg.h"
+#include "ipd_switches.h"
 
 // ---------------------------------------------------------------------------
 // errors

@@ -1,0 +1,383 @@
+// Level planner of the single-workgroup kernels: from the level sizes and the options alone it decides
+// each level's form (polynomial, block-wide polynomial, dense thread-per-row, thread-per-row, tiny
+// dense) and which LDS images are packed -- the whole solve, the sub-cycle and the images rooted at
+// levels 3 and 4 the resident kernels take -- with their LDS budget.  amg_prepare_levels packs what it
+// returns (pack_image, ipd_cycle_host.h).  Host-clean, no HIP: tests/level_plan_driver.cpp runs it on
+// the CPU.
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+#include <vector>
+
+#include "ipd_limits.h"
+
+struct LevelShape {   // level k of the hierarchy, as far as the planner looks at it
+    int nr = 0;       // rows
+    int nnz = 0;      // entries of A_k
+    int nf = 0;       // F-block size (level 1 of a bigraph hierarchy; 0 = Jacobi)
+    int maxoff = 0;   // longest off-diagonal row (0 where the level's data come from a donor)
+    int p_nnz = 0;    // entries of P_k (level k-1 <- k), k >= 2
+};
+
+struct PlanOptions {
+    char cycle = 'v';
+    int smoth = 1;
+    bool twogrid = false, concurrent_pair = false;
+    size_t sol_head = 0;   // SOL_HEAD: the image head (SolveDesc and its relocation table)
+};
+
+struct PlanSwitches {   // the IPD_NO_* switches of the planner and plan_resident (ipd_switches.h), read once per hierarchy
+    bool no_poly = false, no_blk = false, no_bpoly = false, no_blkdense = false, no_small = false,
+         no_subcycle = false, no_resident = false, no_resident_remote = false, no_resident_three = false,
+         no_resident_deep = false, no_resident_big = false, no_res_poly4 = false;
+};
+
+enum ImageRole { IMG_SOLVE, IMG_SUB, IMG_SUB3, IMG_SUB4, IMG_NONE };
+
+struct ImageSpec {
+    ImageRole role;
+    int k_lds;            // first level of the image (its root; > J: the whole solve with nothing cached)
+    int k_semi;           // semi-cached root level (vectors in LDS, rows from L2), 0 = none
+    int k_tiny;           // first tiny (dense) level
+    int k_blk;            // first thread-per-row level (J + 1: none, the generic phases)
+    size_t stage_bytes;   // staging area in front of the image
+    size_t lds;           // predicted dynamic LDS (plan_lds)
+};
+
+struct LevelPlan {
+    int J = 0;
+    bool use_poly = false, use_lpoly = false, lean_vectors = false;
+    int tiny_lo = 0;
+    // per level (index 1..J): polynomial forms of the one-wave (poly) and block-wide (lpoly: out of LDS,
+    // bpoly: operators in global memory) kinds, dense thread-per-row copy
+    std::vector<char> poly, lpoly, bpoly, bdense;
+    std::vector<ImageSpec> images;   // in packing order
+    bool small_ok = false;           // an IMG_SOLVE image is planned
+    int k_sub = 0;                   // root of the IMG_SUB image, 0 = none
+    bool sub_semi_root = false;
+    ImageRole sub5 = IMG_NONE;       // the image that serves the tail rooted at level 5 (d_sub5)
+
+    const ImageSpec* image(ImageRole r) const {
+        for (const ImageSpec& s : images)
+            if (s.role == r) return &s;
+        return nullptr;
+    }
+    // level k of image s is a thread-per-row level (BT threads dealt to its rows)
+    bool thread_per_row(const ImageSpec& s, int k) const {
+        return k >= std::max(s.k_lds, s.k_blk) && k < s.k_tiny && k <= J && k != s.k_semi && !poly[(size_t)k] &&
+               !lpoly[(size_t)k] && !bpoly[(size_t)k];
+    }
+};
+
+static inline size_t plan_r8(size_t n) { return (n + 7) / 8 * 8; }
+static inline size_t plan_r16(size_t b) { return (b + 15) / 16 * 16; }
+static inline size_t poly_ld(size_t rows) { return rows <= 32 ? 32 : (rows <= 48 ? 48 : 64); }
+static inline int bpoly_ld(int N, int Nc) { return N + Nc <= 128 ? 128 : 256; }
+
+struct LevelPlanner {
+    const LevelShape* L;   // 1..J
+    int J;
+    PlanOptions o;
+    PlanSwitches sw;
+    bool cyc;
+    // decided on the way (see plan_levels)
+    bool use_poly, use_lpoly, lean_vectors, use_lmap, use_bdense, use_bpoly;
+    int tiny_lo;
+
+    static int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+    // one workgroup is one CU: beyond ~1000 short rows per level the multi-launch path (many CUs per
+    // phase) wins again (measured: M = 1000 W-cycle solve 9.5 ms here vs 17 ms multi-launch; M = 2048:
+    // 8.0 ms here vs 5.6 ms multi-launch).  The transfer to a level at or above k_root is not looked at.
+    bool small_level(int k, int k_root = 1) const {
+        return L[k].nr <= 1024 && L[k].nnz <= 40000 && (k <= k_root || L[k].p_nnz <= 40000);
+    }
+    // bottom run of levels with <= 32 rows (k >= 2): candidates for the wave-level sub-cycle
+    // (33..64 rows run faster block-wide with 16 lanes per row than in one wave) -- <= 48 rows when
+    // the one-wave levels take the polynomial form (tiny_cycle: a visit is two dense passes whatever
+    // the row count; IPD_NO_POLY=1: sweeps)
+    int find_tiny_lo(int rows_max) const {
+        int lo = J + 1;
+        for (int k = J; k >= 2; --k) {
+            if (L[k].nr > rows_max) break;
+            if (rows_max > 32 && use_lpoly && k < J && L[k].nr + L[k + 1].nr > 32) break;
+            lo = k;
+        }
+        return lo;
+    }
+    bool is_poly(int k) const { return use_poly && k >= tiny_lo && k < J && L[k].nr + L[k + 1].nr <= 64; }
+    // (polynomial form: a level whose stacked operator [e'; r_c] has more than 32 rows -- one lane per row in
+    // a single wave -- runs block-wide instead, out of LDS all the same)
+    bool is_lpoly(int k) const {
+        return use_poly && use_lpoly && lean_vectors && k >= 2 && k < tiny_lo && k < J && L[k].nr <= 48 &&
+               L[k].nr + L[k + 1].nr <= 64;
+    }
+    // thread-per-row levels of 33..144 rows in block-wide polynomial form (SolveLevel::gM)
+    bool is_bpoly(int k) const {
+        if (!use_poly || !use_bpoly || k < 2 || k >= J || k >= tiny_lo) return false;
+        const long long N = L[k].nr, Nc = L[k + 1].nr;
+        // (up to 224 rows below a level 1 of more than 2048 rows: there level 4 has 150-200 rows, often dense --
+        // 23 k entries do not fit an LDS image, the operators of this form stay in L2 -- and the mask-form
+        // resident kernel needs its tail rooted at level 4, ipd_resident_big.h DEEP)
+        const long long nmax = L[1].nr > RES_NMAX ? 224 : 144;
+        return N > 32 && N <= nmax && N + Nc <= 256 && 2 * ((N + 7) / 8 * 8) + (Nc + 7) / 8 * 8 <= 512 && !is_lpoly(k);
+    }
+    // small, nearly full thread-per-row levels: dense copy instead of the CSR arrays (see SolveLevel::blk_dense)
+    bool is_bdense(int k) const {
+        if (!use_bdense || k < 2 || k >= J || k >= tiny_lo || is_bpoly(k)) return false;
+        const long long N = L[k].nr;
+        return N > 32 && N <= 96 && bdense_pad((int)N) / bdense_lanes((int)N) <= BDENSE_Q && 3LL * L[k].nnz >= N * N;
+    }
+    // LDS cache plan: deepest levels first, while they fit; returns the first cached level
+    int plan_lds(size_t stage, size_t* used_out) const {
+        size_t used = stage + o.sol_head + 256;
+        const size_t budget = 150 * 1024;
+        int k_lds = J + 1;
+        for (int k = J; k >= 1; --k) {
+            const size_t N = (size_t)L[k].nr;
+            size_t bytes;
+            if (is_poly(k)) {
+                // polynomial form: [M2a; ..] and [M1; ..] stacked with the restriction, M1 P, w; three
+                // vectors; none of the level's CSR arrays (its parent applies the transfers to and from it)
+                const size_t Nc = (size_t)L[k + 1].nr, LD = poly_ld(N + Nc);
+                bytes = 2 * (8 * LD * plan_r8(N)) + 8 * LD * plan_r8(Nc) + 8 * LD + 3 * plan_r16(8 * plan_r8(N)) + 32;
+            } else if (is_lpoly(k)) {
+                const size_t Nc = (size_t)L[k + 1].nr, LD = 64;
+                bytes = 2 * (8 * LD * plan_r8(N)) + 8 * LD * plan_r8(Nc) + 8 * LD + 3 * plan_r16(8 * plan_r8(N)) + 32 +
+                        8 * (8 * LD + 8);
+            } else if (is_bpoly(k)) {
+                // block-wide polynomial form: the operators stay in global memory; three vectors and the
+                // partial sums of a pass
+                bytes = 3 * plan_r16(8 * plan_r8(N)) + 48 + 8 * (8 * (size_t)bpoly_ld(L[k].nr, L[k + 1].nr) + 8);
+            } else {
+                // (the thread-per-row sub-cycle deals BT threads to the rows: a level of more than BT rows cannot
+                // be held that way -- it fits the budget once its child's operators stay in L2, block-wide
+                // polynomial form of a 150-224-row level 4 below a 576-row level 3)
+                if (k >= 2 && N > (size_t)BT) break;
+                bytes = plan_r16(4 * (N + 1)) +
+                        (is_bdense(k) ? plan_r16(8 * N * (size_t)bdense_ld((int)N))
+                                      : plan_r16(4 * (size_t)L[k].nnz) + plan_r16(8 * (size_t)L[k].nnz)) +
+                        ((lean_vectors && k >= 2) ? 5 : 7) *
+                            plan_r16(8 * (k >= tiny_lo ? plan_r8(N) : is_bdense(k) ? (size_t)bdense_pad((int)N) : N)) +
+                        16;
+                if (k < J) {
+                    const size_t Nc = (size_t)L[k + 1].nr, np = (size_t)L[k + 1].p_nnz;
+                    bytes += plan_r16(4 * (Nc + 1)) + plan_r16(4 * (N + 1)) + 2 * (plan_r16(4 * np) + plan_r16(8 * np));
+                }
+                if (k == J) bytes += plan_r16(4 * 8 * N);
+                if (use_lmap && !is_bdense(k) && k >= 2 && k < tiny_lo && N <= (size_t)BT) bytes += plan_r16(4 * (BT + 1));   // lane map
+                if (k >= 3 && (is_bpoly(k - 1) || is_lpoly(k - 1))) bytes += 5 * 64;   // its vectors are padded to whole 8-entry blocks
+                if (k >= tiny_lo) {   // dense copies of the tiny levels
+                    bytes += plan_r16(8 * N * N);
+                    if (k < J) bytes += 2 * plan_r16(8 * N * (size_t)L[k + 1].nr);
+                }
+            }
+            if (used + bytes > budget) break;
+            used += bytes;
+            k_lds = k;
+        }
+        *used_out = used;
+        return k_lds;
+    }
+    int tiny_from(int k_lds) const { return std::max(tiny_lo, std::max(2, k_lds)); }   // tiny levels: cached, Jacobi (k >= 2)
+    int blk_from(int k_lds) const { return (sw.no_blk || k_lds > J) ? J + 1 : std::max(2, k_lds); }   // thread-per-row levels
+    // Level 2 as a semi-cached level (r, e, e2 in LDS; matrix rows from L2) with levels 3..J fully
+    // cached: returns the dynamic LDS needed behind a staging area of `stage` bytes, 0 = no
+    size_t semi_plan(size_t stage) const {
+        if (!lean_vectors || J < 3 || J > SOLVE_ML) return 0;
+        if (L[2].nr > BT || L[2].nr <= 64 || (double)L[2].nnz > 12.0 * L[2].nr || (double)L[3].p_nnz > 12.0 * L[2].nr)
+            return 0;
+        for (int k = 3; k <= J; ++k)
+            if (!small_level(k)) return 0;
+        size_t used = 0;
+        const int k_lds = plan_lds(stage, &used);
+        if (k_lds != 3) return 0;   // <= 2: level 2 fits entirely; > 3: a deeper level does not
+        const size_t need = used + 3 * plan_r16(8 * (size_t)L[2].nr);
+        return need <= 150 * 1024 ? need : 0;
+    }
+    // an image rooted at level k (the sub-cycle and the resident kernels' tails)
+    ImageSpec rooted(ImageRole role, int k, bool semi, size_t stage, size_t lds) const {
+        return ImageSpec{role, k, semi ? k : 0, tiny_from(k + (semi ? 1 : 0)), blk_from(k), stage, lds};
+    }
+
+    void choose_forms();
+    void plan_solve(LevelPlan& p) const;
+    void plan_sub(LevelPlan& p) const;
+    void plan_tails(LevelPlan& p) const;
+};
+
+// The levels' forms: the polynomial forms are taken, but not at the price of a level that would
+// otherwise be cached.
+inline void LevelPlanner::choose_forms() {
+    use_poly = o.smoth >= 1 && cyc && !sw.no_poly && !sw.no_blk;
+    use_lpoly = !sw.no_blk;
+    tiny_lo = find_tiny_lo(use_poly ? 48 : 32);
+    // the thread-per-row / wave sub-cycles keep the residual in the free iterate buffer and never
+    // use the Gauss-Seidel scratch vector: 5 vectors per cached level instead of 7
+    lean_vectors = !sw.no_blk;
+    use_lmap = lean_vectors;
+    use_bdense = lean_vectors && !sw.no_blkdense;
+    use_bpoly = lean_vectors && !sw.no_bpoly;
+    if (!use_poly) return;
+    size_t u = 0;
+    const int with_poly = plan_lds(16, &u);
+    const int lo_poly = tiny_lo;
+    use_poly = false;
+    tiny_lo = find_tiny_lo(32);
+    const int without = plan_lds(16, &u);
+    if (with_poly <= without) {
+        use_poly = true;
+        tiny_lo = lo_poly;
+    } else if (use_lpoly) {
+        // the block-wide form out of LDS pads its operators to 64 rows: where that is what does not
+        // fit, the one-wave form (48 rows) may still
+        use_lpoly = false;
+        use_poly = true;
+        tiny_lo = find_tiny_lo(48);
+        if (plan_lds(16, &u) > without) {
+            use_poly = false;
+            tiny_lo = find_tiny_lo(32);
+        }
+    }
+}
+
+// (a) the whole solve in one workgroup when every level is small
+inline void LevelPlanner::plan_solve(LevelPlan& p) const {
+    bool ok = !sw.no_small && J <= SOLVE_ML;
+    size_t maxlen = 1;
+    for (int k = 1; k <= J && ok; ++k) {
+        ok = ok && small_level(k);
+        maxlen = std::max(maxlen, (size_t)L[k].nr);
+    }
+    if (!ok) return;
+    const size_t stage = plan_r16(sizeof(double) * maxlen);
+    size_t used = 0;
+    const int k_lds = plan_lds(stage, &used);
+    p.images.push_back(ImageSpec{IMG_SOLVE, k_lds, 0, tiny_from(k_lds), blk_from(k_lds), stage, used});
+    p.small_ok = true;
+}
+
+// (b) otherwise the sub-cycle below the first level from which everything fits in LDS runs as one
+// launch per visit
+inline void LevelPlanner::plan_sub(LevelPlan& p) const {
+    if (sw.no_subcycle || p.small_ok || J > SOLVE_ML || J < 3 || !cyc) return;
+    if (const size_t need = semi_plan(16)) {   // (b1) the sub-cycle is rooted at the semi-cached level 2
+        p.images.push_back(rooted(IMG_SUB, 2, true, 16, need));
+        p.k_sub = 2;
+        return;
+    }
+    // first level from which every level is small ...
+    int k_small = J + 1;
+    for (int k = J; k >= 2 && small_level(k); --k) k_small = k;
+    // Level 1 of 2049..4096 rows, six levels or more: the mask-form resident kernel's deep mode keeps
+    // levels 3 AND 4 in polynomial form in its workgroups and roots its tail workgroup at level 5
+    // (ipd_resident_big.h, POLY4) -- ONE image, rooted at level 5, serves it and the launches (which
+    // then run level 4 as launches: the fall-back).  (An image rooted at level 4 for the launches
+    // beside one rooted at level 5 for the resident kernel packed levels 5..J twice: 0.2 ms per hierarchy.)
+    const int nf1 = L[1].nf, nc1 = L[1].nr - nf1;
+    const bool root5 = J >= 6 && L[1].nr > RES_NMAX && nf1 > 0 && nf1 <= RB_HALF && nc1 <= RB_HALF && L[2].nr == nc1 &&
+                       L[3].nr <= RB_N3MAX && L[4].nr <= RB_N4MAX && L[5].nr <= RB_N5MAX && o.smoth >= 1 && !o.twogrid &&
+                       !o.concurrent_pair && !sw.no_res_poly4 && !sw.no_resident_deep && !sw.no_resident_big &&
+                       !sw.no_resident;
+    if (root5) k_small = std::max(k_small, 5);
+    // ... and everything below it fits in LDS
+    for (int kroot = k_small; kroot < J; ++kroot) {
+        // the generic phases (and their staging vector of N_root doubles) only run when IPD_NO_BLK is set
+        const size_t stage = lean_vectors ? 16 : plan_r16(sizeof(double) * (size_t)L[kroot].nr);
+        size_t used = 0;
+        const int k_lds = plan_lds(stage, &used);
+        // the root itself does not fit beside the deeper levels but has at most BT rows (a
+        // level 3 of 170-310 rows with 40-100 entries each in the m=n=1024 runs): it becomes a
+        // semi-cached root -- vectors in LDS, rows walked from L2 by several lanes each
+        // (glb_rowdot_range), 2-3 us per sweep against 5 us for the launch it replaces
+        // (only with short rows, <= 12 entries on average like the semi-cached level 2: measured on
+        // the Newton systems of the m=n=1024 Class 1 run, a level 3 of 2-3 k entries gains 5-9 % per W
+        // cycle as launches and opens the hierarchy to the resident kernel's remote tail, -15...-23 %;
+        // with 4 k entries it loses 12 %, with 9-17 k entries a sweep from L2 through one CU costs
+        // more than the launch: 0.72 -> 1.09 ms, 0.54 -> 1.21 ms per W cycle)
+        const size_t semi_need = used + 3 * plan_r16(8 * (size_t)L[kroot].nr);
+        const bool semi_root = k_lds == kroot + 1 && kroot >= 3 && lean_vectors && L[kroot].nr <= BT &&
+                               (double)L[kroot].nnz <= 12.0 * L[kroot].nr &&
+                               (double)L[kroot + 1].p_nnz <= 12.0 * L[kroot].nr && semi_need <= 150 * 1024;
+        if (k_lds > kroot && !semi_root) continue;
+        p.images.push_back(rooted(IMG_SUB, kroot, semi_root, stage, semi_root ? semi_need : used));
+        p.k_sub = kroot;
+        p.sub_semi_root = semi_root;
+        return;
+    }
+}
+
+// Images for the resident kernels' tail workgroups alone, and the image that serves a tail rooted at level 5
+inline void LevelPlanner::plan_tails(LevelPlan& p) const {
+    size_t used = 0;
+    // (b2) Where level 3 is only a semi-cached root (its rows come from L2), the level-resident kernel
+    // does better with level 3 in registers and its tail rooted at level 4 (plan_resident, `three`:
+    // 0.50-0.51 against 0.57-0.61 ms per W cycle on the Newton systems of the m=n=1024 Class 1 run), so a
+    // second image rooted at level 4 is packed for it.  (Where levels 3..J fit the image as they are,
+    // the tail rooted at level 3 stays 3-6 % ahead: 0.49-0.51 against 0.51-0.54 ms.)
+    // With level 3 in polynomial form (plan_resident, poly3: a visit of it is three hand-offs instead of
+    // thirteen) the same holds wherever that form applies, semi-cached root or not: 0.33-0.36 -> see DESIGN.
+    const bool poly3_likely =
+        J >= 5 && o.smoth >= 1 && L[1].nf > 0 && L[4].nr <= 128 &&
+        L[4].nr <= std::max(cdiv(std::max(L[1].nf, L[1].nr - L[1].nf), RES_WAVES), cdiv(L[2].nr, RES_WAVES)) &&
+        !sw.no_poly;
+    if (p.k_sub == 3 && (p.sub_semi_root || poly3_likely) && J >= 5 && J <= SOLVE_ML && L[3].nr <= BT &&
+        L[4].nr <= BT && L[3].maxoff <= 512 && L[1].nf > 0 && !sw.no_resident_three && !sw.no_resident) {
+        bool ok = lean_vectors;
+        for (int k = 4; k <= J && ok; ++k) ok = small_level(k);
+        if (ok && plan_lds(16, &used) <= 4) p.images.push_back(rooted(IMG_SUB4, 4, false, 16, used));
+    }
+    // (b3) No sub-cycle at all because level 3's interpolation is big (P_3 with more than 40 k entries:
+    // a dense 1024 x 50 block early in a run), although levels 3..J themselves are small: the launch
+    // path would gain nothing from an image whose restriction and prolongation stay launches, but the
+    // resident kernel's remote tail does not use P_3 from the image -- its workgroups apply it -- so an
+    // image rooted at level 3 is packed for it alone.
+    if (p.k_sub == 0 && !p.small_ok && J >= 4 && J <= SOLVE_ML && lean_vectors && L[3].nr <= BT && L[1].nf > 0 &&
+        cyc && !sw.no_resident && !sw.no_subcycle) {
+        bool ok = true;
+        for (int k = 3; k <= J && ok; ++k) ok = small_level(k, 3);
+        if (ok && plan_lds(16, &used) <= 3) p.images.push_back(rooted(IMG_SUB3, 3, false, 16, used));
+    }
+    // (b4) the image rooted at level 5 (see root5, plan_sub) is the one the deep mode's tail workgroup takes
+    if (p.k_sub == 5 && !p.sub_semi_root && J >= 6 && L[1].nr > RES_NMAX) p.sub5 = IMG_SUB;
+    // (b5) ... and k_resident's POLY3 mode (level 1 of at most 2048 rows) keeps level 4 in polynomial form in its
+    // workgroups as well when there are six levels or more (ResDesc::p4rows).  Its tail workgroup takes the
+    // image rooted at level 4 that the POLY3 mode uses anyway and enters it at level 5 (an image of its own,
+    // rooted at level 5, packed levels 5..J a second time: +85 us per hierarchy, more than the cycles gained).
+    if (p.sub5 == IMG_NONE && poly3_likely && J >= 6 && L[1].nr <= RES_NMAX &&
+        ((p.k_sub == 3 && p.image(IMG_SUB4)) || (p.k_sub == 4 && !p.sub_semi_root)) && L[4].nr <= RES_P4_SEG &&
+        L[5].nr <= 64 && !sw.no_res_poly4)
+        p.sub5 = p.k_sub == 3 ? IMG_SUB4 : IMG_SUB;
+}
+
+// L[1..J]: the levels' shapes
+inline LevelPlan plan_levels(const LevelShape* L, int J, const PlanOptions& o, const PlanSwitches& sw) {
+    LevelPlanner pl{};
+    pl.L = L;
+    pl.J = J;
+    pl.o = o;
+    pl.sw = sw;
+    pl.cyc = o.cycle == 'w' || o.cycle == 'v';
+    pl.choose_forms();
+    LevelPlan p;
+    p.J = J;
+    p.use_poly = pl.use_poly;
+    p.use_lpoly = pl.use_lpoly;
+    p.lean_vectors = pl.lean_vectors;
+    p.tiny_lo = pl.tiny_lo;
+    p.poly.assign((size_t)J + 2, 0);
+    p.lpoly.assign((size_t)J + 2, 0);
+    p.bpoly.assign((size_t)J + 2, 0);
+    p.bdense.assign((size_t)J + 2, 0);
+    for (int k = 1; k <= J; ++k) {
+        p.poly[(size_t)k] = pl.is_poly(k);
+        p.lpoly[(size_t)k] = pl.is_lpoly(k);
+        p.bpoly[(size_t)k] = pl.is_bpoly(k);
+        p.bdense[(size_t)k] = pl.is_bdense(k);
+    }
+    pl.plan_solve(p);
+    pl.plan_sub(p);
+    pl.plan_tails(p);
+    return p;
+}

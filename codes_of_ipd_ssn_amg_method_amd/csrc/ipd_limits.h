@@ -1,0 +1,48 @@
+// Sizes and limits shared by the device code and the level planner (ipd_level_plan.h).  Host-clean:
+// the planner's CPU test compiles it with a plain C++ compiler.
+#pragma once
+
+#if defined(__HIPCC__)
+#define IPD_HD_INLINE __host__ __device__ __forceinline__
+#else
+#define IPD_HD_INLINE inline
+#endif
+
+// threads per block of every phase kernel and of the single-workgroup kernels (their helpers
+// share the block reductions, so it is one constant).  Measured, 1024 -> 512: regime-D V cycle
+// 0.194 -> 0.190 ms, tree-mask W cycle 0.503 -> 0.431 ms, m=n=1024 Class 1 / Class 2 driver runs
+// 1.53 / 0.74 -> 1.47 / 0.70 s, m=n=4096 Class 1 5.33 -> 4.97 s (only the bandwidth-bound
+// m=n=2048 regime-D cycle loses: 0.328 -> 0.342 ms); 256: 0.234 ms and the sub-cycle kernel no
+// longer takes 300-1000-row roots (Class 1 run 20 s).
+static constexpr int BT = 512;
+
+static constexpr int STAGE_MAX = 7680;   // vector entries staged in LDS (60 KiB)
+
+// levels a single-workgroup image (SolveDesc) holds
+static constexpr int SOLVE_ML = 24;
+
+// dense thread-per-row levels (SolveLevel::blk_dense, ipd_cycle.hip): 24 values per lane: the register
+// budget of the tail (the resident kernels' worker paths set the kernels' allocation; the tail must stay
+// below it) -- the same storage serves the lane-map entries.
+static constexpr int BDENSE_Q = 24;
+IPD_HD_INLINE int bdense_lanes(int N) { return N > 64 ? 4 : 8; }   // == lanes_per_row(N), 33..96 rows
+IPD_HD_INLINE int bdense_pad(int N) {
+    const int g = 4 * bdense_lanes(N);
+    return (N + g - 1) / g * g;
+}
+IPD_HD_INLINE int bdense_ld(int N) {
+    const int Lr = bdense_lanes(N), p = bdense_pad(N);
+    return p % (2 * Lr) == Lr ? p : p + Lr;   // p is a multiple of 4 Lr
+}
+
+// level-resident kernel (ipd_resident.h)
+static constexpr int RES_WAVES = BT / 64;     // row slots per block and workgroup (one wave per row)
+static constexpr int RES_NMAX = 4 * BT;        // rows per level (fixed LDS slots)
+static constexpr int RES_P4_SEG = 128;         // ... of ResDesc::p4rows: 128 + 128 + 64
+
+// mask-form resident kernel (ipd_resident_big.h)
+static constexpr int RB_NMAX = 8 * BT;                 // rows of level 1
+static constexpr int RB_HALF = 4 * BT;                 // rows of a block of level 1 / of level 2
+static constexpr int RB_N3MAX = 2 * BT;                // rows of the polynomial level 3 (DEEP)
+static constexpr int RB_N4MAX = BT / 2;                // rows of the remote tail's root level (DEEP)
+static constexpr int RB_N5MAX = BT / 4;                // rows of the tail's root level when level 4 is resident too (POLY4)

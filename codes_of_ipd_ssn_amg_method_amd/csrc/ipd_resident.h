@@ -37,14 +37,11 @@
 
 typedef unsigned int res_v4u __attribute__((ext_vector_type(4)));
 
-static constexpr int RES_WAVES = BT / 64;     // row slots per block and workgroup (one wave per row)
 static constexpr int RES_TAIL_MAX = 64;       // rows of the redundantly solved tail level
-static constexpr int RES_NMAX = 4 * BT;        // rows per level (fixed LDS slots)
 static constexpr int RES_GRAN_MAX = RES_NMAX;  // granules per hand-off buffer
 static constexpr size_t RES_LDS_BYTES = sizeof(double) * ((size_t)9 * RES_NMAX + RES_NMAX / 2 + 3 * RES_TAIL_MAX + 16 * RES_WAVES + 12);
 static constexpr unsigned RES_SPIN_MAX = 1u << 18;
 static constexpr int RES_P3_LD = 1152;         // row stride of ResDesc::p3rows: 512 + 512 + 128
-static constexpr int RES_P4_SEG = 128;         // ... of ResDesc::p4rows: 128 + 128 + 64
 static constexpr int RES_P4_LD = 2 * RES_P4_SEG + 64;
 
 struct ResLevelDesc {
@@ -105,7 +102,7 @@ struct ResDesc {
     // serves the visits of everything below level 2: the other workgroups hand it r_3 = P3' rr_2
     // (tin, Nt granules) and receive the prolongated correction P3 e_3 (tout, N2 granules).
     int remote;
-    const SolveDesc* sub;     // image of levels 3..J (build_image), NULL without remote tail
+    const SolveDesc* sub;     // image of levels 3..J (pack_image), NULL without remote tail
     unsigned char* tin;       // 2 x RES_GRAN_MAX granules by visit parity
     unsigned char* tout;
     unsigned* tctl;           // [0] != 0: the solve is over, the tail workgroup leaves

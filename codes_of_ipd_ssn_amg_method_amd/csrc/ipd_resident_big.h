@@ -30,15 +30,10 @@
 // Reference: AMG/Class_AMG.m:86-109, AMG/MG_Vcycle.m:12-45, AMG/MG_Wcycle.m:13-46, PCG.m:68-87.
 #pragma once
 
-static constexpr int RB_NMAX = 8 * BT;                 // rows of level 1
-static constexpr int RB_HALF = 4 * BT;                 // rows of a block of level 1 / of level 2
 static constexpr int RB_GRAN = RB_NMAX;                // granules per hand-off buffer
 static constexpr int RB_RPW_MAX = 2;                   // rows of a block per wave
-static constexpr int RB_N3MAX = 2 * BT;                // rows of the polynomial level 3 (DEEP)
-static constexpr int RB_N4MAX = BT / 2;                // rows of the remote tail's root level (DEEP)
 static constexpr int RB_P3_SEG = RB_N3MAX;             // p3rows layout: [Mr (RB_P3_SEG) | Me (RB_P3_SEG) | Mc (RB_N4MAX)]
 static constexpr int RB_P3_LD = 2 * RB_P3_SEG + RB_N4MAX;
-static constexpr int RB_N5MAX = BT / 4;                // rows of the tail's root level when level 4 is resident too (POLY4)
 static constexpr int RB_P4_SEG = RB_N4MAX;             // p4rows layout: [Mr (RB_P4_SEG) | Me (RB_P4_SEG) | Mc (RB_N5MAX)]
 static constexpr int RB_P4_LD = 2 * RB_P4_SEG + RB_N5MAX;
 // LDS (doubles): E2, TU, P3C / RR2, E1S, XS, reductions, publish slots, own-row constants, fail word;

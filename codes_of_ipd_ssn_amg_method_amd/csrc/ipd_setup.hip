@@ -518,7 +518,7 @@ static bool mis_set_small(ipd_ctx* ctx, const Csr& A, double theta, ipd_rng* rng
                           uint8_t* strong, double* maxrow, double* diag, int* cidx, int* Nc, int* bad) {
     const int N = A.nr;
     if (N > MIS_SMALL_ROWS || A.nnz > MIS_SMALL_NNZ || N < 1) return false;
-    if (const char* e = getenv("IPD_NO_MIS_SMALL"); e && e[0] == '1') return false;
+    if (switch_on("IPD_NO_MIS_SMALL")) return false;
     unsigned ticket = 0;
     if (!ctx->mailbox_begin(&ticket)) return false;
     Arena& tmp = *ctx->scratch;
@@ -1341,7 +1341,7 @@ void amg_transfer(ipd_ctx* ctx, Arena& dst, const Csr& A, const AmgOpts& o, int 
         // very long rows (filled-in level 2 under dense masks): the product form (see k_w_split_count), whose
         // product can run on register tiles; otherwise one kernel (k_build_W_w)
         bool split = (double)A.nnz / std::max(N, 1) >= 256.0;
-        if (const char* e = getenv("IPD_INTERP")) split = !strcmp(e, "split");
+        if (const char* e = switch_value("IPD_INTERP")) split = !strcmp(e, "split");
         // (the product form adds into rows that start out as zeros)
         double* dense = (split && o.inter < 2) ? zeroed<double>(ctx, dense_elems) : tmp.alloc<double>(dense_elems);
         // P's row pointers.  With a lazy count the compaction scans the plain counts on its way in (scan_head).
@@ -1447,7 +1447,7 @@ void amg_transfer(ipd_ctx* ctx, Arena& dst, const Csr& A, const AmgOpts& o, int 
             IPD_KERNEL_CHECK();
             dense_rowcount(ctx, N, Nc, Nc, dense, rowcnt, pt);
         } else {
-            const char* bwe = getenv("IPD_INTERP");
+            const char* bwe = switch_value("IPD_INTERP");
             if (bwe && !strcmp(bwe, "block")) {   // (the barrier-per-neighbour form, kept for the bit-for-bit tests)
                 const bool wide = (double)A.nnz / std::max(N, 1) >= 96.0;
                 IPD_OPTIN_LDS(ctx, k_build_W, 128 * 1024);

@@ -751,7 +751,7 @@ static bool spgemm_prefers_tiles(const Csr& X, const Csr& Y, size_t* bytes, int 
     *bytes = 8 * (nrp * nkp + nkp * ncp + nrp * ncp);
     if (X.nr == 0 || X.nc == 0 || Y.nc == 0 || X.nnz == 0) return false;
     if (*bytes > (size_t(12) << 30)) return false;   // 12 GiB of dense scratch at most
-    if (const char* e = getenv("IPD_PRODUCT")) {
+    if (const char* e = switch_value("IPD_PRODUCT")) {
         if (!strcmp(e, "tiles")) return true;
         if (!strcmp(e, "rows")) return false;
     }
@@ -766,7 +766,7 @@ static bool spgemm_prefers_tiles(const Csr& X, const Csr& Y, size_t* bytes, int 
     const double t_walk = tiles >= 256.0 ? 20.0 + std::ceil(tiles / 256.0) * steps * 0.9
                                          : std::ceil(4.0 * tiles / 1024.0) * steps * 0.23;
     const double t_tiles = 20.0 + t_walk + (double)*bytes / 3.0e6;   // (operand block zeroed and written at ~3 TB/s)
-    if (const char* dbg = getenv("IPD_DEBUG_LEVELS"); dbg && dbg[0] == '1')
+    if (switch_on("IPD_DEBUG_LEVELS"))
         std::fprintf(stderr, "[ipd] product %d x %d x %d: x row %.1f, y row %.1f entries; model rows %.1f us, tiles %.1f us\n",
                      X.nr, X.nc, Y.nc, xlen, ylen, t_rows, t_tiles);
     return t_tiles < t_rows;
