@@ -29,7 +29,7 @@ __all__ = [
     "Class_AMG", "AMGHierarchy", "MG_Vcycle", "MG_Wcycle", "PCG", "components", "Hybrid_AMG",
     "AMG4POT", "MatlabRand", "IpdError", "amg_options", "APDWorkspace", "warmup_class1",
     "warmup_class2", "APD_SsN_Class1", "APD_SsN_Class2", "twogrid_bigph", "twogrid", "Hybrid_twogrid",
-    "aug_PCG", "PCG4POT", "load_input", "sparse_multiply", "spd_solve",
+    "aug_PCG", "PCG4POT", "load_input", "sparse_multiply", "spd_solve", "AMG_PCG",
 ]
 
 
@@ -313,6 +313,24 @@ class AMGHierarchy:
         n = it.value + 1
         return x, int(it.value), float(rel.value), rel_resk[:n].copy(), rhok[:n].copy()
 
+    def pcg(self, e, pcg_options: dict | None = None):
+        """``[d,it,res,resk] = AMG_PCG(h,e,pcg_options)`` (``ipd_amg_pcg``): PCG.m's loop on level 1
+        preconditioned by one cycle of this hierarchy, flexible beta.  ``pcg_options``: ``retol``,
+        ``maxit``, ``guess``; ``precd`` must stay unset.  ``resk`` has ``maxit`` slots like ``PCG``."""
+        e = f64(e)
+        o = _pcg_opts_struct(pcg_options)
+        g = None
+        if pcg_options is not None and pcg_options.get("guess") is not None:
+            g = f64(pcg_options["guess"])
+        maxit = int(o.maxit) if o.maxit >= 0 else 10000
+        d = np.empty(self.N)
+        it = c_int64()
+        res = c_double()
+        resk = np.zeros(maxit)
+        check(lib.ipd_amg_pcg(self.handle, dptr(e), dptr(g) if g is not None else None, byref(o), dptr(d),
+                              byref(it), byref(res), dptr(resk)))
+        return d, int(it.value), float(res.value), resk
+
     def cycle_bytes(self) -> float:
         v = c_double()
         check(lib.ipd_amg_cycle_bytes(self.handle, byref(v)))
@@ -355,6 +373,16 @@ def Class_AMG(A, b, amg_options: dict | None = None, rng: MatlabRand | None = No
     try:
         guess = None if amg_options is None else amg_options.get("guess")
         return h.solve(b, guess)
+    finally:
+        h.close()
+
+
+def AMG_PCG(A, b, amg_options: dict, pcg_options: dict | None = None, rng: MatlabRand | None = None):
+    """``[d,it,res,resk] = AMG_PCG(A,b,amg_options,pcg_options)``: Class_AMG's setup, then
+    conjugate gradients preconditioned by one cycle of the hierarchy (``AMGHierarchy.pcg``)."""
+    h = AMGHierarchy(A, amg_options, rng)
+    try:
+        return h.pcg(b, pcg_options)
     finally:
         h.close()
 

@@ -51,7 +51,9 @@ struct Level {
     int lanes = 64;         // lanes per row used by the row kernels of this level
 };
 
-struct CycleState;  // ipd_cycle.hip
+struct CycleState;   // ipd_cycle.hip
+struct KrylovState;  // ipd_krylov.hip
+struct LevelDev;     // ipd_cycle_dev.h
 
 struct ipd_amg {
     ipd_ctx* ctx = nullptr;
@@ -72,6 +74,9 @@ struct ipd_amg {
     double* hist = nullptr;  // device copy of [res0, res, rnorm]
     // PCG work vectors for the coarsest level
     double* pcg_work = nullptr;
+    // AMG-preconditioned CG (ipd_krylov.hip): its level-1 sized vectors, scalars and tickets out of
+    // `arena`, made on the first ipd_amg_pcg call
+    std::shared_ptr<KrylovState> kry;
 };
 
 // ipd_setup.hip
@@ -95,6 +100,11 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
 static constexpr int RES_MASK_MIN_ROWS = 2048;
 void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, double* x_dev,
                    int32_t* it, double* rel_res, double* rel_resk, double* rhok);
+// Level 1's launch-path row walk (descriptor, LDS staging, grid of a whole-level pass); false when
+// the level is sharded over ranks.  amg_apply_cycle: L[1].e = one cycle from zero on L[1].r with
+// the hierarchy's own cycle and isnsp (IPD_E_ARG for a cycle other than 'v'/'w'), queue flushed.
+bool amg_level1_walk(ipd_amg* h, LevelDev* lv, int* staged, int* grid);
+void amg_apply_cycle(ipd_amg* h);
 void pcg_dev(ipd_ctx* ctx, const Csr& H, const double* e, const double* guess, double tol,
              long long maxit, int precd, double* d, long long* it, double* res, double* resk_host,
              long long nf = 0);

@@ -2349,6 +2349,25 @@ static void run_cycle_api(ipd_amg* h, const double* r, int isnsp, int k, const d
     ctx->fetch(h->L[k].e, e_out, N);
 }
 
+// ---- the cycle as a preconditioner (ipd_krylov.hip) -------------------------------------
+bool amg_level1_walk(ipd_amg* h, LevelDev* lv, int* staged, int* grid) {
+    CycleState* st = state_of(h);
+    IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
+    if (st->shard_ranks > 1 && !st->shard_emulate) return false;
+    const LevelRun& rn = st->run[1];
+    *lv = rn.dev;
+    *staged = rn.staged;
+    *grid = pick_blocks(rn.dev.N, rn.dev.L, st->num_cu);
+    return true;
+}
+
+void amg_apply_cycle(ipd_amg* h) {
+    const int cyc = h->opts.cycle;
+    IPD_REQUIRE(cyc == 'v' || cyc == 'w', IPD_E_ARG, "AMG-PCG: the hierarchy's cycle must be 'v' or 'w'");
+    amg_cycle(h, 1, h->opts.isnsp, cyc == 'w', false);   // what run_cycle_api(h, r, isnsp, 1, NULL, ..) runs
+    flush_fused(h->ctx, state_of(h));
+}
+
 extern "C" int ipd_amg_vcycle(ipd_amg* h, const double* r, int isnsp, int k, double* e) {
     return ipd_guard([&] { run_cycle_api(h, r, isnsp, k, nullptr, e, false); });
 }

@@ -1,0 +1,388 @@
+// AMG-preconditioned conjugate gradients on a device hierarchy: the loop of PCG.m:68-87 with the
+// preconditioner M(r) = one cycle of the hierarchy from a zero guess (MG_Vcycle(r,isnsp,1) or
+// MG_Wcycle(r,isnsp,1) with the hierarchy's own cycle, smoth, isnsp, bigph and fnode) and the
+// flexible (Polak-Ribiere) beta = (r'w - r'w_old) / delta_old.
+//
+// Why not PCG.m's Fletcher-Reeves beta = delta_new / delta_old: with isnsp = 1 the cycle is not a
+// symmetric operator (the kernel-augmented pre-smoother P0 + R(I - A P0) is not the transpose of the
+// post-smoother P0 + R'(I - A P0)), and the coarsest solve is a PCG to 1e-11, which is not linear at
+// all.  For a symmetric linear M both forms agree in exact arithmetic.
+//
+// One iteration = K1 + K2 + the cycle + K3, and one host read (the scalar block, for the loop test):
+//   K1 k_kry_dir_spmv  p_new = w + beta p_old formed inside the level-1 row walk's gather (p_old is
+//                      only read, so no workgroup sees a neighbour's half-written p), p_new and
+//                      w_old = w stored for the owned rows, q = A_1 p_new, partials of p_new'q; the
+//                      last workgroup forms alpha.  With START it forms r = e - A_1 d0 instead.
+//   K2 k_kry_update    d += alpha p ; r -= alpha q, the new r also written into the cycle's input
+//                      L[1].r (the PCG keeps its own r: no cycle path is then trusted to leave
+//                      L[1].r alone).
+//   cycle              amg_apply_cycle: w = L[1].e.
+//   K3 k_kry_dots      r'w and r'w_old in one pass; the last workgroup forms delta_new, beta,
+//                      resk and the stop flag.
+// Reductions are per-workgroup partials summed in fixed workgroup order by the workgroup that
+// arrives last (agent-scope release / acquire around a ticket it resets itself): no float
+// atomics, the same bits run to run.  Separate multiplies and adds (-ffp-contract=off).
+//
+// Always the launch-path cycle: the resident kernels (k_resident*, k_solve_small) run whole
+// Class_AMG loops and are not used here.
+#include "ipd_amg_internal.h"
+
+#include <cmath>
+
+#include "ipd_cycle_dev.h"
+#include "ipd_cycle_phases.h"
+
+// scalar block (doubles)
+enum { SC_DNEW, SC_DOLD, SC_ALPHA, SC_BETA, SC_D0, SC_IT, SC_RES, SC_STOP, SC_N };
+
+struct KrylovState {
+    int N = 0;
+    int G1 = 0, G3 = 0;          // workgroups of K1 / of K2 and K3
+    double* p[2] = {nullptr, nullptr};
+    double* q = nullptr;
+    double* w_old = nullptr;
+    double* d = nullptr;
+    double* r = nullptr;
+    double* sc = nullptr;        // SC_N scalars
+    double* part1 = nullptr;     // G1 partials of p'q
+    double* part3 = nullptr;     // 2 x G3 partials of r'w, r'w_old
+    unsigned* cnt = nullptr;     // tickets of K1 and K3
+};
+
+// Wave 0 of every workgroup calls this after thread 0 stored the workgroup's partials; true (in wave
+// 0 only) in the workgroup that arrives last, which then sees every partial and has reset the ticket.
+__device__ __forceinline__ bool kry_last_arrival(unsigned* cnt) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // keep: the fence's own wait can be dropped
+    unsigned t = 0;
+    if (threadIdx.x == 0) t = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    t = __builtin_amdgcn_readfirstlane(t);
+    if (t != gridDim.x - 1) return false;
+    if (threadIdx.x == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    return true;
+}
+
+// sum of part[0], part[stride], ... (n terms) in a fixed order, result in every lane of wave 0
+__device__ __forceinline__ double kry_sum_parts(const double* part, int n, int stride) {
+    double s = 0.0;
+    for (int i = (int)threadIdx.x; i < n; i += 64) s += part[(size_t)i * stride];
+    return wave_sum(s);
+}
+
+struct KryDirArgs {
+    LevelDev lv;
+    const double* w;       // preconditioned residual; START: the initial guess (NULL: zero)
+    const double* p_old;   // NULL: first direction (beta = 0, p_old not read)
+    double* p_new;
+    double* w_old;
+    double* q;
+    const double* e;       // START: right-hand side
+    double* r;             // START: residual (the PCG's copy) ...
+    double* r1;            // ... and the cycle's input L[1].r
+    double* d;             // START: d = d0
+    double* sc;
+    double* part;
+    unsigned* cnt;
+};
+
+// Level-1 row walk of phase_top (ipd_cycle_phases.h), gathering p_new = w + beta p_old.
+template <bool STAGED, bool PAD, bool START>
+__global__ __launch_bounds__(BT) void k_kry_dir_spmv(KryDirArgs a) {
+    __shared__ PhaseLds lds;
+    extern __shared__ __attribute__((aligned(16))) double xs[];
+    const LevelDev& lv = a.lv;
+    const int b = blockIdx.x, G = gridDim.x;
+    const int tid = threadIdx.x;
+    const int N = lv.N, L = lv.L, gpb = BT / L;
+    const int g = tid / L, gl = tid - g * L;
+    const bool uni = L >= 64;
+    const int niter = (N + G * gpb - 1) / (G * gpb);
+    const double* __restrict__ w = a.w;
+    const double* __restrict__ po = a.p_old;
+    const double beta = (!START && po) ? a.sc[SC_BETA] : 0.0;
+    auto xglobal = [&](int j) -> double {
+        if (START) return w ? w[j] : 0.0;
+        return po ? w[j] + beta * po[j] : w[j];
+    };
+    auto xlds = [&](int j) { return xs[j]; };
+    int row = uniform_if(b * gpb + g, uni);
+    bool valid = row < N;
+    bool owner = valid && gl == 0;
+    RowCursor rc;
+    RowBatch bt;
+    row_open<PAD>(lv, row, valid, owner, gl, L, rc, bt);
+    if (STAGED) {
+        vec_pass(N, [&](int j) { return xglobal(j); }, [&](int j, double v) { xs[j] = v; });
+        __syncthreads();
+    }
+    double acc = 0.0;
+    for (int it = 0; it < niter; ++it) {
+        if (it > 0) {
+            row = uniform_if((it * G + b) * gpb + g, uni);
+            valid = row < N;
+            owner = valid && gl == 0;
+            row_open<PAD>(lv, row, valid, owner, gl, L, rc, bt);
+        }
+        double s = STAGED ? row_finish<PAD>(lv, rc, bt, gl, L, xlds)
+                          : row_finish<PAD>(lv, rc, bt, gl, L, xglobal);
+        double dummy;
+        s = reduce_rows(s, L, false, 0.0, &dummy, &lds);
+        if (owner) {
+            const double xo = STAGED ? xs[row] : xglobal(row);
+            if (PAD) s += rc.dg * xo;
+            if (START) {                                                          // PCG.m:68
+                const double ri = a.e[row] - s;
+                a.r[row] = ri;
+                a.r1[row] = ri;
+                a.d[row] = xo;
+            } else {
+                a.p_new[row] = xo;
+                a.w_old[row] = w[row];
+                a.q[row] = s;                                                     // :77
+                acc += xo * s;
+            }
+        }
+    }
+    if (START) return;
+    block_totals_to(acc, a.part + b, 0.0, nullptr, &lds);
+    if (tid >= 64 || !kry_last_arrival(a.cnt)) return;
+    const double pq = kry_sum_parts(a.part, G, 1);
+    if (tid == 0) {
+        const double dn = a.sc[SC_DNEW];
+        a.sc[SC_DOLD] = dn;                                                       // :77
+        a.sc[SC_ALPHA] = dn / pq;                                                 // :78
+    }
+}
+
+// d += alpha p ; r -= alpha q (both copies of r)                                 PCG.m:79
+__global__ __launch_bounds__(BT) void k_kry_update(int N, const double* __restrict__ sc,
+                                                   const double* __restrict__ p,
+                                                   const double* __restrict__ q, double* __restrict__ d,
+                                                   double* __restrict__ r, double* __restrict__ r1) {
+    const double alpha = sc[SC_ALPHA];
+    for (int i = blockIdx.x * BT + threadIdx.x; i < N; i += gridDim.x * BT) {
+        d[i] = d[i] + alpha * p[i];
+        const double ri = r[i] - alpha * q[i];
+        r[i] = ri;
+        r1[i] = ri;
+    }
+}
+
+struct KryDotArgs {
+    int N;
+    const double* r;
+    const double* w;
+    const double* w_old;   // FIRST: not read
+    double tol2;           // retol^2
+    double maxit;
+    double* sc;
+    double* part;          // [r'w | r'w_old] x G
+    unsigned* cnt;
+};
+
+template <bool FIRST>
+__global__ __launch_bounds__(BT) void k_kry_dots(KryDotArgs a) {
+    __shared__ PhaseLds lds;
+    const int G = gridDim.x, b = blockIdx.x, tid = threadIdx.x;
+    double rw = 0.0, rwo = 0.0;
+    for (int i = b * BT + tid; i < a.N; i += G * BT) {
+        const double ri = a.r[i];
+        rw += ri * a.w[i];
+        if (!FIRST) rwo += ri * a.w_old[i];
+    }
+    block_totals_to(rw, a.part + 2 * b, rwo, FIRST ? nullptr : a.part + 2 * b + 1, &lds);
+    if (tid >= 64 || !kry_last_arrival(a.cnt)) return;
+    const double dn = kry_sum_parts(a.part, G, 2);
+    const double s_wo = FIRST ? 0.0 : kry_sum_parts(a.part + 1, G, 2);
+    if (tid == 0) {
+        double d0, itv;
+        if (FIRST) {                                                              // PCG.m:70-72
+            d0 = dn;
+            itv = 0.0;
+            a.sc[SC_D0] = d0;
+            a.sc[SC_BETA] = 0.0;
+        } else {
+            d0 = a.sc[SC_D0];
+            a.sc[SC_BETA] = (dn - s_wo) / a.sc[SC_DOLD];                          // flexible :82
+            itv = a.sc[SC_IT] + 1.0;                                              // :84
+        }
+        a.sc[SC_DNEW] = dn;                                                       // :81
+        a.sc[SC_IT] = itv;
+        a.sc[SC_RES] = sqrt(fabs(dn / d0));                                       // :85 / :88
+        a.sc[SC_STOP] = (itv < a.maxit && dn > a.tol2 * d0) ? 0.0 : 1.0;          // :76
+    }
+}
+
+static KrylovState* krylov_state(ipd_amg* h, int N, int G1, int G3) {
+    if (!h->kry) {
+        auto ks = std::make_shared<KrylovState>();
+        Arena& ar = *h->arena;   // the hierarchy's own storage (not the per-call zero pool)
+        ks->N = N;
+        ks->G1 = G1;
+        ks->G3 = G3;
+        for (auto& v : ks->p) v = ar.alloc<double>((size_t)N);
+        ks->q = ar.alloc<double>((size_t)N);
+        ks->w_old = ar.alloc<double>((size_t)N);
+        ks->d = ar.alloc<double>((size_t)N);
+        ks->r = ar.alloc<double>((size_t)N);
+        ks->sc = ar.alloc<double>(SC_N);
+        ks->part1 = ar.alloc<double>((size_t)G1);
+        ks->part3 = ar.alloc<double>(2 * (size_t)G3);
+        ks->cnt = ar.alloc<unsigned>(2);
+        h->kry = ks;
+    }
+    IPD_REQUIRE(h->kry->N == N && h->kry->G1 == G1 && h->kry->G3 == G3, IPD_E_ARG,
+                "AMG-PCG: level-1 geometry changed");
+    return h->kry.get();
+}
+
+#define KRY_LAUNCH_K1(START, grid, dyn, args)                                                          \
+    do {                                                                                               \
+        if (staged) {                                                                                  \
+            if (pad)                                                                                   \
+                hipLaunchKernelGGL((k_kry_dir_spmv<true, true, START>), dim3(grid), dim3(BT), dyn,     \
+                                   ctx->stream, args);                                                 \
+            else                                                                                       \
+                hipLaunchKernelGGL((k_kry_dir_spmv<true, false, START>), dim3(grid), dim3(BT), dyn,    \
+                                   ctx->stream, args);                                                 \
+        } else {                                                                                       \
+            if (pad)                                                                                   \
+                hipLaunchKernelGGL((k_kry_dir_spmv<false, true, START>), dim3(grid), dim3(BT), 0,      \
+                                   ctx->stream, args);                                                 \
+            else                                                                                       \
+                hipLaunchKernelGGL((k_kry_dir_spmv<false, false, START>), dim3(grid), dim3(BT), 0,     \
+                                   ctx->stream, args);                                                 \
+        }                                                                                              \
+        IPD_KERNEL_CHECK();                                                                            \
+    } while (0)
+
+// [d,it,res,resk] = AMG_PCG(h,e,pcg_options) on device vectors; resk: host, maxit slots or NULL
+static void amg_pcg_dev(ipd_amg* h, const double* e, const double* guess, double tol, long long maxit,
+                        double* d_out, long long* it_out, double* res_out, double* resk) {
+    ipd_ctx* ctx = h->ctx;
+    const int cyc = h->opts.cycle;
+    IPD_REQUIRE(cyc == 'v' || cyc == 'w', IPD_E_ARG,
+                "AMG-PCG: the hierarchy's cycle must be 'v' or 'w' (any other value applies no correction)");
+    LevelDev lv;
+    int staged = 0, G1 = 1;
+    IPD_REQUIRE(amg_level1_walk(h, &lv, &staged, &G1), IPD_E_UNSUPPORTED,
+                "AMG-PCG: level 1 is sharded over ranks");
+    const bool pad = lv.S > 0;
+    const int N = lv.N;
+    const int G3 = std::max(1, std::min(ctx->num_cu, cdiv(N, BT)));
+    KrylovState* ks = krylov_state(h, N, G1, G3);
+    const size_t dyn = staged ? sizeof(double) * (size_t)N : 0;
+    double* r1 = h->L[1].r;
+    // tickets start at zero on every call (the last arriver resets its own, this covers a launch
+    // that never completed)
+    IPD_HIP(hipMemsetAsync(ks->cnt, 0, 2 * sizeof(unsigned), ctx->stream));
+
+    KryDirArgs ka{};
+    ka.lv = lv;
+    ka.w = guess;                                                                 // PCG.m:68
+    ka.e = e;
+    ka.r = ks->r;
+    ka.r1 = r1;
+    ka.d = ks->d;
+    KRY_LAUNCH_K1(true, G1, dyn, ka);
+    KryDotArgs kd{};
+    kd.N = N;
+    kd.r = ks->r;
+    kd.w_old = ks->w_old;
+    kd.tol2 = tol * tol;
+    kd.maxit = (double)maxit;
+    kd.sc = ks->sc;
+    kd.part = ks->part3;
+    kd.cnt = ks->cnt + 1;
+    amg_apply_cycle(h);                                                           // :69
+    kd.w = h->L[1].e;
+    hipLaunchKernelGGL(k_kry_dots<true>, dim3(G3), dim3(BT), 0, ctx->stream, kd);
+    IPD_KERNEL_CHECK();
+    double sc[SC_N];
+    ctx->fetch(ks->sc, sc, SC_N);
+
+    ka = KryDirArgs{};
+    ka.lv = lv;
+    ka.w_old = ks->w_old;
+    ka.q = ks->q;
+    ka.sc = ks->sc;
+    ka.part = ks->part1;
+    ka.cnt = ks->cnt;
+    int cur = 0;   // p[cur]: the current direction
+    bool have_p = false;
+    long long it = 0;
+    while (sc[SC_STOP] == 0.0) {                                                  // :76
+        ka.w = h->L[1].e;
+        ka.p_old = have_p ? ks->p[cur] : nullptr;
+        ka.p_new = ks->p[cur ^ 1];
+        KRY_LAUNCH_K1(false, G1, dyn, ka);                                        // :77-78, :83
+        cur ^= 1;
+        have_p = true;
+        hipLaunchKernelGGL(k_kry_update, dim3(G3), dim3(BT), 0, ctx->stream, N, (const double*)ks->sc,
+                           (const double*)ks->p[cur], (const double*)ks->q, ks->d, ks->r, r1);
+        IPD_KERNEL_CHECK();                                                       // :79
+        amg_apply_cycle(h);                                                       // :80
+        kd.w = h->L[1].e;
+        hipLaunchKernelGGL(k_kry_dots<false>, dim3(G3), dim3(BT), 0, ctx->stream, kd);
+        IPD_KERNEL_CHECK();                                                       // :81-82, :84-85
+        ctx->fetch(ks->sc, sc, SC_N);
+        it = (long long)sc[SC_IT];
+        if (resk) resk[it - 1] = sc[SC_RES];
+    }
+    IPD_HIP(hipMemcpyAsync(d_out, ks->d, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, ctx->stream));
+    if (it_out) *it_out = it;
+    if (res_out) *res_out = sc[SC_RES];                                           // :88
+    ctx->sync();
+}
+
+static void pcg_opts_of(const ipd_pcg_opts* o, double* tol, long long* maxit) {
+    *tol = 1e-11;   // PCG.m:24-27 defaults
+    *maxit = 10000;
+    if (!o) return;
+    IPD_REQUIRE(o->precd == -1, IPD_E_ARG, "AMG-PCG: pcg_options.precd must be unset (the hierarchy preconditions)");
+    if (o->retol >= 0) *tol = o->retol;
+    if (o->maxit >= 0) *maxit = o->maxit;
+}
+
+extern "C" int ipd_amg_pcg_dev(ipd_amg* h, const double* e_dev, const double* guess_dev,
+                               const ipd_pcg_opts* o, double* d_dev, int64_t* it, double* res,
+                               double* resk) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && e_dev && d_dev, IPD_E_ARG, "NULL argument");
+        double tol;
+        long long maxit;
+        pcg_opts_of(o, &tol, &maxit);
+        CallScope scope(h->ctx);
+        long long its = 0;
+        amg_pcg_dev(h, e_dev, guess_dev, tol, maxit, d_dev, &its, res, resk);
+        if (it) *it = its;
+    });
+}
+
+extern "C" int ipd_amg_pcg(ipd_amg* h, const double* e, const double* guess, const ipd_pcg_opts* o,
+                           double* d, int64_t* it, double* res, double* resk) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && e && d, IPD_E_ARG, "NULL argument");
+        double tol;
+        long long maxit;
+        pcg_opts_of(o, &tol, &maxit);
+        ipd_ctx* ctx = h->ctx;
+        CallScope scope(ctx);
+        const size_t N = (size_t)h->L[1].A.nr;
+        double* de = ctx->scratch->alloc<double>(N);
+        double* dd = ctx->scratch->alloc<double>(N);
+        double* dg = nullptr;
+        ctx->upload(de, e, N);
+        if (guess) {
+            dg = ctx->scratch->alloc<double>(N);
+            ctx->upload(dg, guess, N);
+        }
+        long long its = 0;
+        amg_pcg_dev(h, de, dg, tol, maxit, dd, &its, res, resk);
+        if (it) *it = its;
+        ctx->fetch(dd, d, N);
+    });
+}

@@ -165,6 +165,18 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)it);
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(res);
         if (nlhs > 3) { plhs[3] = col((size_t)maxit); std::memcpy(mxGetDoubles(plhs[3]), rk.data(), sizeof(double) * (size_t)maxit); }
+    } else if (fn == "AMG_PCG") {                // [d,it,res,resk] = AMG_PCG(A,b,amg_options,pcg_options)
+        ipd_csc A = csc_of(a[0]); ipd_amg_opts ao = opts_of(nrhs > 3 ? a[2] : nullptr);
+        ipd_pcg_opts o; ipd_pcg_opts_init(&o); const mxArray* so = nrhs > 4 ? a[3] : nullptr;
+        if (so) { o.retol = field(so, "retol", -1); o.maxit = (int64_t)field(so, "maxit", -1); o.precd = (int32_t)field(so, "precd", -1); }
+        if (g_h) { ipd_amg_destroy(g_h); g_h = nullptr; }
+        chk(ipd_amg_setup(g_ctx, &A, &ao, g_rng, &g_h));   // the gateway's hierarchy, as Class_AMG leaves it
+        const int64_t maxit = o.maxit >= 0 ? o.maxit : 10000;
+        plhs[0] = col((size_t)A.nrows); int64_t it = 0; double res = 0; std::vector<double> rk((size_t)maxit + 1);
+        chk(ipd_amg_pcg(g_h, mxGetDoubles(a[1]), opt_vec(so, "guess"), &o, mxGetDoubles(plhs[0]), &it, &res, rk.data()));
+        if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)it);
+        if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(res);
+        if (nlhs > 3) { plhs[3] = col((size_t)it); std::memcpy(mxGetDoubles(plhs[3]), rk.data(), sizeof(double) * (size_t)it); }
     } else if (fn == "components") {             // 1-based outputs for MATLAB
         ipd_csc A = csc_of(a[0]); const size_t N = (size_t)A.nrows; int64_t nc = 0;
         std::vector<int64_t> b(N), sz(N), p(N), r(N + 1);

@@ -174,6 +174,19 @@ int ipd_amg_get_cmask(const ipd_amg* h, int k, uint8_t* isC /* rows of level k-1
  * maxit+1 entries (may be NULL); *it = number of cycles.                     */
 int ipd_amg_solve(ipd_amg* h, const double* b, const double* guess, double* x,
                   int32_t* it, double* rel_res, double* rel_resk, double* rhok);
+/* [d,it,res,resk] = AMG_PCG(h,e,pcg_options): conjugate gradients on level 1 of the hierarchy,
+ * preconditioned by one cycle of it from a zero guess -- MG_Vcycle(r,isnsp,1) / MG_Wcycle(r,isnsp,1)
+ * with the hierarchy's own cycle, smoth, isnsp, bigph and fnode, the operator ipd_amg_vcycle /
+ * ipd_amg_wcycle(h,r,isnsp,1,NULL,e) apply.  The loop is PCG.m:68-87 with one departure: the
+ * flexible (Polak-Ribiere) beta = (r'w - r'w_old)/delta_old instead of delta_new/delta_old, since
+ * the cycle is not symmetric for isnsp = 1 and its coarsest solve is not linear (both agree for a
+ * symmetric linear preconditioner).  pcg_options: retol (default 1e-11) and maxit (default 1e4);
+ * precd must stay unset (-1), else IPD_E_ARG; a hierarchy whose cycle is neither 'v' nor 'w' is
+ * IPD_E_ARG.  guess may be NULL (zeros); resk needs maxit slots or NULL; e = 0 (with a zero guess)
+ * gives it = 0, res = NaN.  Always the launch-path cycle: the resident whole-solve kernels are not
+ * used.                                                                                          */
+int ipd_amg_pcg(ipd_amg* h, const double* e, const double* guess, const ipd_pcg_opts* o,
+                double* d, int64_t* it, double* res, double* resk /* maxit slots or NULL */);
 /* e = MG_Vcycle(r,isnsp,k)   AMG/MG_Vcycle.m:2 ; k is 1-based               */
 int ipd_amg_vcycle(ipd_amg* h, const double* r, int isnsp, int k, double* e);
 /* e = MG_Wcycle(r,isnsp,k,e) AMG/MG_Wcycle.m:2 ; e_inout NULL-able input    */
@@ -260,6 +273,9 @@ int ipd_amg_setup_dev(ipd_ctx*, const ipd_dmat* A, const ipd_amg_opts* o, ipd_rn
 int ipd_amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev,
                       double* x_dev, int32_t* it, double* rel_res, double* rel_resk,
                       double* rhok);
+/* ipd_amg_pcg on device vectors (guess_dev may be NULL); resk stays a host array               */
+int ipd_amg_pcg_dev(ipd_amg* h, const double* e_dev, const double* guess_dev,
+                    const ipd_pcg_opts* o, double* d_dev, int64_t* it, double* res, double* resk);
 /* Hybrid_AMG with H0 already on the device (output of ipd_asat_dev)          */
 int ipd_hybrid_amg_dev(ipd_ctx*, const ipd_dmat* H0, const double* t_dev, const double* p_dev,
                        const double* q_dev, int64_t m, int64_t n, double bk1, double tk,
