@@ -30,6 +30,7 @@ __all__ = [
     "AMG4POT", "MatlabRand", "IpdError", "amg_options", "APDWorkspace", "warmup_class1",
     "warmup_class2", "APD_SsN_Class1", "APD_SsN_Class2", "twogrid_bigph", "twogrid", "Hybrid_twogrid",
     "aug_PCG", "PCG4POT", "load_input", "sparse_multiply", "spd_solve", "AMG_PCG",
+    "Class_AMG_multi",
 ]
 
 
@@ -313,6 +314,25 @@ class AMGHierarchy:
         n = it.value + 1
         return x, int(it.value), float(rel.value), rel_resk[:n].copy(), rhok[:n].copy()
 
+    def solve_multi(self, B, guess=None):
+        """Several right-hand sides (``ipd_amg_solve_multi``): column j of ``B`` (N x k) through the
+        solve phase of Class_AMG as if solved alone.  Returns ``X`` (N x k), ``it`` (k,), ``rel_res``
+        (k,) and the lists of the k ``rel_resk`` and ``rhok`` histories (``it[j] + 1`` entries each).
+        For one right-hand side ``solve`` stays the faster call."""
+        Bf, gf, k = multi_args(self.N, B, guess)
+        X = np.empty((self.N, k), order="F")
+        it = np.zeros(k, np.int32)
+        rel = np.zeros(k)
+        hs = self.maxit + 1
+        rel_resk = np.full((hs, k), np.nan, order="F")
+        rhok = np.full((hs, k), np.nan, order="F")
+        check(lib.ipd_amg_solve_multi(self.handle, dptr(Bf), self.N, k, dptr(gf) if gf is not None else None,
+                                      dptr(X), it.ctypes.data_as(POINTER(c_int32)), dptr(rel),
+                                      dptr(rel_resk), dptr(rhok)))
+        n = [int(v) + 1 for v in it]
+        return (X, it.astype(np.int64), rel, [rel_resk[:n[j], j].copy() for j in range(k)],
+                [rhok[:n[j], j].copy() for j in range(k)])
+
     def pcg(self, e, pcg_options: dict | None = None):
         """``[d,it,res,resk] = AMG_PCG(h,e,pcg_options)`` (``ipd_amg_pcg``): PCG.m's loop on level 1
         preconditioned by one cycle of this hierarchy, flexible beta.  ``pcg_options``: ``retol``,
@@ -373,6 +393,39 @@ def Class_AMG(A, b, amg_options: dict | None = None, rng: MatlabRand | None = No
     try:
         guess = None if amg_options is None else amg_options.get("guess")
         return h.solve(b, guess)
+    finally:
+        h.close()
+
+
+def multi_args(N: int, B, guess=None):
+    """``B`` (N x k, or a vector: k = 1) and ``guess`` (same shape or None) as column-major float64
+    blocks with leading dimension N; ValueError on a shape that does not fit."""
+    Bf = np.asarray(B, dtype=np.float64)
+    if Bf.ndim == 1:
+        Bf = Bf.reshape(-1, 1)
+    if Bf.ndim != 2 or Bf.shape[0] != N or Bf.shape[1] < 1:
+        raise ValueError(f"solve_multi: B must be {N} x k with k >= 1, got shape {np.shape(B)}")
+    k = int(Bf.shape[1])
+    Bf = np.asfortranarray(Bf)
+    gf = None
+    if guess is not None:
+        gf = np.asarray(guess, dtype=np.float64)
+        if gf.ndim == 1:
+            gf = gf.reshape(-1, 1)
+        if gf.shape != (N, k):
+            raise ValueError(f"solve_multi: guess must be {N} x {k}, got shape {np.shape(guess)}")
+        gf = np.asfortranarray(gf)
+    return Bf, gf, k
+
+
+def Class_AMG_multi(A, B, amg_options: dict | None = None, rng: MatlabRand | None = None):
+    """``[X,it,rel_res,rel_resk,rhok] = Class_AMG_multi(A,B,amg_options)``: one Class_AMG setup, then
+    every column of ``B`` through its solve phase (``AMGHierarchy.solve_multi``).  A guess in
+    ``amg_options`` is N x k."""
+    h = AMGHierarchy(A, amg_options, rng)
+    try:
+        guess = None if amg_options is None else amg_options.get("guess")
+        return h.solve_multi(B, guess)
     finally:
         h.close()
 

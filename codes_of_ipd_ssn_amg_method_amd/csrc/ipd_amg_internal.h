@@ -53,6 +53,7 @@ struct Level {
 
 struct CycleState;   // ipd_cycle.hip
 struct KrylovState;  // ipd_krylov.hip
+struct BlockState;   // ipd_block.hip
 struct LevelDev;     // ipd_cycle_dev.h
 
 struct ipd_amg {
@@ -77,6 +78,9 @@ struct ipd_amg {
     // AMG-preconditioned CG (ipd_krylov.hip): its level-1 sized vectors, scalars and tickets out of
     // `arena`, made on the first ipd_amg_pcg call
     std::shared_ptr<KrylovState> kry;
+    // block solve of several right-hand sides (ipd_block.hip): its N x W work blocks out of `arena`,
+    // made on the first ipd_amg_solve_multi call and made again for a wider W
+    std::shared_ptr<BlockState> blk;
 };
 
 // ipd_setup.hip
@@ -105,6 +109,30 @@ void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, dou
 // the hierarchy's own cycle and isnsp (IPD_E_ARG for a cycle other than 'v'/'w'), queue flushed.
 bool amg_level1_walk(ipd_amg* h, LevelDev* lv, int* staged, int* grid);
 void amg_apply_cycle(ipd_amg* h);
+// What the block solve (ipd_block.hip) needs of a level's launch-path cycle: the CSR matrices with
+// their lanes per row and whole-level grids, the smoother data and the coarsest PCG's settings.
+struct BlockCsr {
+    int nr = 0, nc = 0;
+    int L = 1, grid = 1;       // lanes per row, workgroups of a whole-matrix row walk
+    const int* rp = nullptr;   // NULL: absent
+    const int* ci = nullptr;
+    const double* va = nullptr;
+};
+struct BlockLevel {
+    int N = 0, nf = 0;                  // rows, F-block size (0: Jacobi)
+    BlockCsr A;
+    const double* dinv = nullptr;
+    const double* Axi = nullptr;
+    const double* xx = nullptr;
+    BlockCsr Pt, P, T1;                 // k < J: restriction, prolongation; T1 = P'A when the fused
+                                        // residual + restriction applies (else T1.rp == NULL)
+    int pcg_L = 1, pcg_precd = 2;       // k == J: PCG(A,r) of the cycle
+    double pcg_tol = 0.0;
+    long long pcg_maxit = 0;
+};
+// 1-based levels (out[0] unused; out == NULL: the check alone); false when the hierarchy runs sharded
+// over ranks
+bool amg_block_levels(ipd_amg* h, std::vector<BlockLevel>* out);
 void pcg_dev(ipd_ctx* ctx, const Csr& H, const double* e, const double* guess, double tol,
              long long maxit, int precd, double* d, long long* it, double* res, double* resk_host,
              long long nf = 0);

@@ -2361,6 +2361,54 @@ bool amg_level1_walk(ipd_amg* h, LevelDev* lv, int* staged, int* grid) {
     return true;
 }
 
+// ---- the launch-path cycle's CSR forms, for the block solve (ipd_block.hip) ----------------
+bool amg_block_levels(ipd_amg* h, std::vector<BlockLevel>* out) {
+    CycleState* st = state_of(h);
+    IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
+    if (st->shard_ranks > 1) return false;
+    if (!out) return true;
+    const int cu = st->num_cu;
+    auto csr_of = [&](const Csr& m, int L) {
+        BlockCsr c;
+        c.nr = m.nr;
+        c.nc = m.nc;
+        c.L = L;
+        c.grid = pick_blocks(m.nr, L, cu);
+        c.rp = m.rp;
+        c.ci = m.ci;
+        c.va = m.va;
+        return c;
+    };
+    out->assign((size_t)h->J + 1, BlockLevel{});
+    for (int k = 1; k <= h->J; ++k) {
+        const Level& lv = h->L[k];
+        const LevelRun& rn = st->run[(size_t)k];
+        BlockLevel& bl = (*out)[(size_t)k];
+        bl.N = lv.N;
+        bl.nf = lv.nf;
+        bl.A = csr_of(lv.A, rn.dev.L);
+        bl.dinv = lv.dinv;
+        bl.Axi = lv.Axi;
+        bl.xx = lv.xx;
+        if (k < h->J) {
+            const Level& cl = h->L[k + 1];
+            bl.Pt = csr_of(cl.Pt, rn.restrict_args.L);
+            bl.P = csr_of(cl.P, rn.prolong_args.L);
+            const Csr& T1 = cl.T1;
+            // amg_cycle's rule for the fused residual + restriction (the fused-program case aside)
+            if (!switch_on("IPD_NO_RRC") && T1.rp && T1.nr == cl.Pt.nr && T1.nnz <= (1 << 18))
+                bl.T1 = csr_of(T1, pick_lanes(T1.nnz + cl.Pt.nnz, cl.Pt.nr, cu));
+        } else {
+            const PcgArgs& a = rn.pcg;
+            bl.pcg_L = a.L;
+            bl.pcg_precd = a.precd;
+            bl.pcg_tol = a.tol;
+            bl.pcg_maxit = a.maxit;
+        }
+    }
+    return true;
+}
+
 void amg_apply_cycle(ipd_amg* h) {
     const int cyc = h->opts.cycle;
     IPD_REQUIRE(cyc == 'v' || cyc == 'w', IPD_E_ARG, "AMG-PCG: the hierarchy's cycle must be 'v' or 'w'");

@@ -10,6 +10,8 @@
 // logical arrays are mxLogical bytes; MATLAB owns the inputs; errors are raised through
 // mexErrMsgIdAndTxt with ipd_last_error(); one process-wide context and one process-wide
 // "current hierarchy" emulate the reference's `global Ack Prok J smoth_it Rk`.
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -150,6 +152,36 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(rel);
         if (nlhs > 3) { plhs[3] = col((size_t)it + 1); std::memcpy(mxGetDoubles(plhs[3]), rk.data(), sizeof(double) * ((size_t)it + 1)); }
         if (nlhs > 4) { plhs[4] = col((size_t)it + 1); std::memcpy(mxGetDoubles(plhs[4]), rho.data(), sizeof(double) * ((size_t)it + 1)); }
+    } else if (fn == "Class_AMG_multi") {        // [X,it,rel_res,rel_resk,rhok] = Class_AMG_multi(A,B,opts)
+        // one setup, every column of B through its solve phase; rel_resk / rhok: (max(it)+1) x k, NaN
+        // past a column's own it+1 entries
+        ipd_csc A = csc_of(a[0]); const mxArray* so = nrhs > 3 ? a[2] : nullptr;
+        ipd_amg_opts o = opts_of(so);
+        const int maxit = o.maxit >= 0 ? o.maxit : 50;
+        const size_t N = (size_t)A.nrows, k = mxGetN(a[1]), hs = (size_t)maxit + 1;
+        // B must be N x k and a guess N x k: the library reads and writes ldb*k doubles (ldb = N here)
+        if (mxGetM(a[1]) != N || k < 1)
+            mexErrMsgIdAndTxt("ipdamg:arg", "Class_AMG_multi: B must have size(A,1) rows and at least one column");
+        const mxArray* gv = (so && mxIsStruct(so)) ? mxGetField(so, 0, "guess") : nullptr;
+        if (gv && !mxIsEmpty(gv) && mxGetNumberOfElements(gv) != N * k)
+            mexErrMsgIdAndTxt("ipdamg:arg", "Class_AMG_multi: amg_options.guess must be size(B) (or empty)");
+        if (g_h) { ipd_amg_destroy(g_h); g_h = nullptr; }
+        chk(ipd_amg_setup(g_ctx, &A, &o, g_rng, &g_h));   // the gateway's hierarchy, as Class_AMG leaves it
+        plhs[0] = mxCreateDoubleMatrix((mwSize)N, (mwSize)k, mxREAL);
+        std::vector<int32_t> it(k); std::vector<double> rel(k), rk(hs * k, NAN), rho(hs * k, NAN);
+        chk(ipd_amg_solve_multi(g_h, mxGetDoubles(a[1]), (int64_t)N, (int64_t)k, opt_vec(so, "guess"),
+                                mxGetDoubles(plhs[0]), it.data(), rel.data(), rk.data(), rho.data()));
+        size_t rows = 1;
+        for (size_t j = 0; j < k; ++j) rows = std::max(rows, (size_t)it[j] + 1);
+        if (nlhs > 1) { plhs[1] = col(k); for (size_t j = 0; j < k; ++j) mxGetDoubles(plhs[1])[j] = it[j]; }
+        if (nlhs > 2) { plhs[2] = col(k); std::memcpy(mxGetDoubles(plhs[2]), rel.data(), sizeof(double) * k); }
+        for (int q = 3; q <= 4 && q < nlhs; ++q) {
+            const std::vector<double>& h = q == 3 ? rk : rho;
+            plhs[q] = mxCreateDoubleMatrix((mwSize)rows, (mwSize)k, mxREAL);
+            for (size_t j = 0; j < k; ++j)
+                for (size_t i = 0; i < rows; ++i)
+                    mxGetDoubles(plhs[q])[j * rows + i] = i <= (size_t)it[j] ? h[j * hs + i] : NAN;
+        }
     } else if (fn == "MG_Vcycle" || fn == "MG_Wcycle") {   // e = MG_?cycle(r,isnsp,k[,e]) on the current hierarchy
         if (!g_h) mexErrMsgIdAndTxt("ipdamg:state", "no hierarchy: call Class_AMG first (global Ack Prok J Rk)");
         const int isnsp = nrhs > 2 ? (int)mxGetScalar(a[1]) : 0, k = nrhs > 3 ? (int)mxGetScalar(a[2]) : 1;

@@ -174,6 +174,23 @@ int ipd_amg_get_cmask(const ipd_amg* h, int k, uint8_t* isC /* rows of level k-1
  * maxit+1 entries (may be NULL); *it = number of cycles.                     */
 int ipd_amg_solve(ipd_amg* h, const double* b, const double* guess, double* x,
                   int32_t* it, double* rel_res, double* rel_resk, double* rhok);
+/* Several right-hand sides: column j of B (N x nrhs, column-major, leading dimension ldb >= N) goes
+ * through the solve phase of Class_AMG (AMG/Class_AMG.m:86-109) on this hierarchy as if it were solved
+ * alone -- guess column j (guess may be NULL: zeros), its own count it[j], rel_res[j] and histories
+ * (column j of rel_resk / rhok, (maxit+1) x nrhs column-major, each may be NULL; the first it[j]+1
+ * entries follow ipd_amg_solve's convention, later slots are left untouched).  A column whose loop
+ * has stopped stays frozen while the others go on.  Results agree with ipd_amg_solve to rounding (the
+ * summation order differs); they do not depend on the other columns of the call and repeat bit for
+ * bit.  Columns run in blocks of up to 8 (the next power of two), chunk by chunk, through block
+ * forms of the launch-path cycle: the CSR matrices of every level; an attached mask operator or
+ * level-2 polynomial form is ignored.  X (ld = ldb) may not alias B.  IPD_E_ARG for NULL h, B, X or
+ * it, nrhs < 1, ldb < N, and a hierarchy set up for a sharded run.
+ * For ONE right-hand side ipd_amg_solve stays the call to use: its hierarchies may run the whole
+ * solve as one single-workgroup or resident launch.                                              */
+int ipd_amg_solve_multi(ipd_amg* h, const double* B, int64_t ldb, int64_t nrhs,
+                        const double* guess /* N x nrhs, ld = ldb, or NULL */, double* X /* ld = ldb */,
+                        int32_t* it /* nrhs */, double* rel_res /* nrhs or NULL */,
+                        double* rel_resk /* (maxit+1) x nrhs or NULL */, double* rhok /* same or NULL */);
 /* [d,it,res,resk] = AMG_PCG(h,e,pcg_options): conjugate gradients on level 1 of the hierarchy,
  * preconditioned by one cycle of it from a zero guess -- MG_Vcycle(r,isnsp,1) / MG_Wcycle(r,isnsp,1)
  * with the hierarchy's own cycle, smoth, isnsp, bigph and fnode, the operator ipd_amg_vcycle /
@@ -273,6 +290,11 @@ int ipd_amg_setup_dev(ipd_ctx*, const ipd_dmat* A, const ipd_amg_opts* o, ipd_rn
 int ipd_amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev,
                       double* x_dev, int32_t* it, double* rel_res, double* rel_resk,
                       double* rhok);
+/* ipd_amg_solve_multi on device blocks B, guess (or NULL) and X; it, rel_res and the histories stay
+ * host arrays                                                                                    */
+int ipd_amg_solve_multi_dev(ipd_amg* h, const double* B_dev, int64_t ldb, int64_t nrhs,
+                            const double* guess_dev, double* X_dev, int32_t* it, double* rel_res,
+                            double* rel_resk, double* rhok);
 /* ipd_amg_pcg on device vectors (guess_dev may be NULL); resk stays a host array               */
 int ipd_amg_pcg_dev(ipd_amg* h, const double* e_dev, const double* guess_dev,
                     const ipd_pcg_opts* o, double* d_dev, int64_t* it, double* res, double* resk);
