@@ -561,7 +561,12 @@ static void plan_resident(ipd_amg* h, CycleState* st, const PlanSwitches& sw) {
     }
     D.localfirst = 1;
     D.pollsleep = 1;   // (0..2 sleeps between polls made no difference, from 3 on it was worse)
-    D.presleep = 13;   // measured: 0 -> 0.0869, 8 -> 0.0796, 12..14 -> 0.0770, 16 -> 0.0784 ms per V cycle (a failing poll delays the publishes it waits for)
+    // s_sleep(1) count between a publish and the first poll (a failing poll delays the publishes it waits for).
+    // Round 2: 0 -> 0.0869, 8 -> 0.0796, 12..14 -> 0.0770, 16 -> 0.0784 ms per V cycle.  With the shorter
+    // hand-off of round 5 the best value moved down: metric workload 8 -> 0.0446, 13 -> 0.0456 ms
+    // (6 / 7 / 9: 0.0450 / 0.0460 / 0.0447), W cycle 0.0852 against 0.0876, the sweep form of level 2 even.
+    D.presleep = 8;
+    if (const char* e = switch_value("IPD_RES_PRESLEEP")) D.presleep = std::max(0, std::atoi(e));
     const size_t gbytes = (size_t)RES_GRAN_MAX * 16;
     st->res_block_bytes = 2 * gbytes + 16 + (remote ? 4 * gbytes + 16 : 0);
     st->res_block = reinterpret_cast<unsigned char*>(ar.alloc_bytes(st->res_block_bytes));

@@ -269,6 +269,33 @@ __device__ __forceinline__ double res_rowdot(unsigned (&c)[KE / 2], const double
     return (s0 + s1) + (s2 + s3);
 }
 
+// The same dot product with fused multiply-adds, each partial sum seeded with its first product
+// (k_resident's half sweeps): 4 v_mul_f64 + 12 v_fmac_f64 per lane instead of 16 multiplies and 16 adds,
+// four of them adds to 0.0 -- half the fp64 instructions the two waves of a SIMD issue per row dot, and a
+// dependent chain per partial sum half as long.
+template <int KE, int OFFB>
+__device__ __forceinline__ double res_rowdot_fma(unsigned (&c)[KE / 2], const double (&a)[KE],
+                                                 const char* smb) {
+    static_assert(KE % 4 == 0, "four partial sums");
+    double y[KE];
+#pragma unroll
+    for (int q = 0; q < KE / 2; ++q) {
+        asm volatile("" : "+v"(c[q]));   // (see res_rowdot)
+        const unsigned lo = c[q] & 0xffffu, hi = c[q] >> 16;
+        y[2 * q] = *reinterpret_cast<const double*>(smb + OFFB + lo);
+        y[2 * q + 1] = *reinterpret_cast<const double*>(smb + OFFB + hi);
+    }
+    double s0 = a[0] * y[0], s1 = a[1] * y[1], s2 = a[2] * y[2], s3 = a[3] * y[3];
+#pragma unroll
+    for (int q = 4; q < KE; q += 4) {
+        s0 = __builtin_fma(a[q], y[q], s0);
+        s1 = __builtin_fma(a[q + 1], y[q + 1], s1);
+        s2 = __builtin_fma(a[q + 2], y[q + 2], s2);
+        s3 = __builtin_fma(a[q + 3], y[q + 3], s3);
+    }
+    return (s0 + s1) + (s2 + s3);
+}
+
 // CSR row of a transfer operator (global, L2-resident) against an LDS vector, one wave per row
 __device__ __forceinline__ double res_csr_rowdot(const ResCsr& M, int e0, int e1, int lane,
                                                  const double* sm, int off) {
@@ -343,6 +370,18 @@ __device__ __forceinline__ double res_red8(const double* red) {
 #pragma unroll
     for (int k = 0; k < RES_WAVES; ++k) t += red[k];
     return t;
+}
+
+// The same sum as a fixed pairwise tree (k_resident's hand-offs): the eight reads are issued together and
+// three dependent adds follow, where the sequential form became four LDS round trips and eight dependent
+// adds, the first of them to 0.0, between the closing barrier and the next row dot.  Every workgroup adds
+// in the same order, so every workgroup gets the same bits.
+__device__ __forceinline__ double res_red8_tree(const double* red) {
+    static_assert(RES_WAVES == 8, "eight waves");
+    double v[RES_WAVES];
+#pragma unroll
+    for (int k = 0; k < RES_WAVES; ++k) v[k] = red[k];
+    return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
 }
 
 // The tail workgroup of a remote-tail launch: k_subcycle's body as a server.  It loads the LDS
@@ -568,6 +607,9 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     const bool nsp = D.isnsp != 0;
     const double xx1 = nsp ? D.L1.xx[0] : 1.0, xx2 = nsp ? D.L2.xx[0] : 1.0;
     const double xx3 = (THREE && nsp) ? D.L3.xx[0] : 1.0;
+    // the kernel-space scalars of the hand-offs are formed as sum * (1 / xx): a multiply where a division
+    // (thirteen dependent instructions) stood between the closing barrier and the next row dot
+    const double rxx1 = 1.0 / xx1, rxx2 = 1.0 / xx2, rxx3 = 1.0 / xx3;
     for (int j = tid; j < N1; j += BT) {
         sm[oX + j] = xg[j];
         sm[oE1 + j] = 0.0;
@@ -653,17 +695,26 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     }
 
     // ---- hand-off wrapper: sweep + barrier + store + (optional) block sums + barrier ------------
-    // STORE(j, v) is called for every granule of the thread; EXTRA() runs once per thread in the
-    // store phase (fix-ups on rows the thread does not sweep); both may add to p0 / p1, whose block
-    // totals are returned in t0 / t1.
+    // STORE(j, v) is called for every granule of the thread; EXTRA() runs once per thread (fix-ups on
+    // rows the thread does not sweep); both may add to p0 / p1, whose block totals are returned in
+    // t0 / t1.  Nothing reads the vectors between the publish barrier and the closing barrier, so
+    // whatever does not need the received values runs BEFORE the wait, where it hides under the
+    // hand-off latency: EXTRA, and PRE(j), which RES_HANDOFF_P calls for every granule to read the
+    // LDS operands of STORE into pa_[u_] / pb_[u_].  The store phase after the wait is then register
+    // arithmetic and LDS writes only (a read there was a dependent LDS round trip per granule on the
+    // critical path).
     // The waves have left their values in sm[oPUB + w] (first block) / sm[oPUB + RES_WAVES + w]
     // (second block); after the barrier -- which also ends the step's reads of the vectors that
     // are about to change -- wave 0 publishes them: one store instruction, one 128-byte segment per
     // block (a store per wave would be eight 16-byte partial-line writes: measured 2.6 us of waiting
     // per hand-off against 1.4).  gA/cA, gB/cB: first granule and row count of the two blocks.
 #define RES_HANDOFF(NJ, n, gA, cA, gB, cB, STORE, EXTRA, want_sums, t0, t1)                        \
+    RES_HANDOFF_P(NJ, n, gA, cA, gB, cB, {}, STORE, EXTRA, want_sums, t0, t1)
+#define RES_HANDOFF_P(NJ, n, gA, cA, gB, cB, PRE, STORE, EXTRA, want_sums, t0, t1)                 \
     do {                                                                                           \
-        double hv_[NJ];                                                                            \
+        double hv_[NJ], pa_[NJ], pb_[NJ];                                                          \
+        (void)pa_;                                                                                 \
+        (void)pb_;                                                                                 \
         ++seq;                                                                                     \
         /* a give-up of the previous hand-off (its closing barrier has ordered the flag): read here, where the */ \
         /* LDS round trip hides under the barrier, not behind the closing barrier on the critical path          */ \
@@ -678,6 +729,12 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 !(seq == D.dbg_skip_seq && b == G - 1))                                            \
                 res_publish(rs, seq, (second_ ? (gB) : (gA)) + l8_, sm[oPUB + lane]);              \
         }                                                                                          \
+        double p0 = 0.0, p1 = 0.0;                                                                 \
+        _Pragma("unroll") for (int u_ = 0; u_ < NJ; ++u_) {                                        \
+            const int j = tid + u_ * BT;                                                           \
+            if (j < (n)) { PRE; }                                                                  \
+        }                                                                                          \
+        EXTRA;                                                                                     \
         if (dbg) dbg_acc[0] -= __builtin_amdgcn_s_memtime();                                       \
         for (int ps_ = 0; ps_ < D.presleep; ++ps_) __builtin_amdgcn_s_sleep(1);                    \
         if (res_sweep<NJ>(rs, seq, (n), dead, D.tmo, hv_, D.pollsleep)) {                             \
@@ -689,7 +746,6 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             dbg_acc[0] += t_;                                                                      \
             dbg_acc[4] -= t_;                                                                      \
         }                                                                                          \
-        double p0 = 0.0, p1 = 0.0;                                                                 \
         _Pragma("unroll") for (int u_ = 0; u_ < NJ; ++u_) {                                        \
             const int j = tid + u_ * BT;                                                           \
             if (j < (n)) {                                                                         \
@@ -697,7 +753,6 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 STORE;                                                                             \
             }                                                                                      \
         }                                                                                          \
-        EXTRA;                                                                                     \
         if (want_sums) {                                                                           \
             p0 = wave_sum(p0);                                                                     \
             if ((want_sums) > 1) p1 = wave_sum(p1);                                                \
@@ -714,8 +769,8 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         __syncthreads();                                                                           \
         if (dbg) dbg_acc[5] += __builtin_amdgcn_s_memtime();                                       \
         if (want_sums) {                                                                           \
-            t0 = res_red8(red);                                                                    \
-            if ((want_sums) > 1) t1 = res_red8(red + RES_WAVES);                                   \
+            t0 = res_red8_tree(red);                                                               \
+            if ((want_sums) > 1) t1 = res_red8_tree(red + RES_WAVES);                              \
         }                                                                                          \
     } while (0)
 
@@ -749,8 +804,8 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
 
     // r = b - A x (rows of this wave), ||r||, c1 for a zero start; E1 := 0        Class_AMG.m:89,96,103
     auto top = [&]() __attribute__((always_inline)) {
-        const double sF = wave_sum(res_rowdot<KE1, 8 * oX>(cF, aF, smb));
-        const double sC = wave_sum(res_rowdot<KE1, 8 * oX>(cC, aC, smb));
+        const double sF = wave_sum(res_rowdot_fma<KE1, 8 * oX>(cF, aF, smb));
+        const double sC = wave_sum(res_rowdot_fma<KE1, 8 * oX>(cC, aC, smb));
         if (lane == 0) {
             sm[oPUB + w] = bF - (sF + dgF * sm[oX + rF]);
             sm[oPUB + RES_WAVES + w] = bC - (sC + dgC * sm[oX + rC]);
@@ -758,7 +813,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         double nrm2 = 0.0, sumr = 0.0;
         RES_HANDOFF(4, N1, loF, hiF - loF, loC, hiC - loC,
                     { sm[oR1 + j] = v; sm[oE1 + j] = 0.0; p0 += v * v; p1 += v; }, {}, 2, nrm2, sumr);
-        c1 = nsp ? sumr / xx1 : 0.0;
+        c1 = nsp ? sumr * rxx1 : 0.0;
         if (lfirst) {   // first half (F rows) of the first pre-smoothing sweep: half1(true, true, true)
             for (int j = tid; j < nf; j += BT) {
                 const double g_i = sm[oR1 + j] - sm[oAX1 + j] * c1;
@@ -782,7 +837,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         if (!ezero) eo = sm[oE1 + rr_];
         const double dg_ = frows ? dgF : dgC, dv_ = frows ? dvF : dvC;
         const double r_own = sm[oR1 + rr_], ax_own = sm[oAX1 + rr_];
-        if (!(ezero && first)) s = wave_sum(frows ? res_rowdot<KE1, 8 * oE1>(cF, aF, smb) : res_rowdot<KE1, 8 * oE1>(cC, aC, smb));
+        if (!(ezero && first)) s = wave_sum(frows ? res_rowdot_fma<KE1, 8 * oE1>(cF, aF, smb) : res_rowdot_fma<KE1, 8 * oE1>(cC, aC, smb));
         s += dg_ * eo;
         const double g_i = r_own - s - ax_own * c1;
         const double wv = eo + dv_ * g_i;
@@ -796,21 +851,22 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             const int oth0 = frows ? nf : 0, noth = frows ? nc : nf;
             const double cc = c1;
             double xig = 0.0;
-            RES_HANDOFF(2, nblk, g0, cnt, 0, 0,
-                        {
-                            const double en = v + cc;
-                            sm[oE1 + blk0 + j] = en;
-                            p0 += sm[oR1 + blk0 + j] - sm[oAX1 + blk0 + j] * en;
-                        },
-                        {
-                            for (int jo = tid; jo < noth; jo += BT) {
-                                const double en = sm[oE1 + oth0 + jo] + cc;
-                                sm[oE1 + oth0 + jo] = en;
-                                p0 += sm[oR1 + oth0 + jo] - sm[oAX1 + oth0 + jo] * en;
-                            }
-                        },
-                        (nsp ? 1 : 0), xig, dum1);
-            c1 = nsp ? xig / xx1 : 0.0;
+            RES_HANDOFF_P(2, nblk, g0, cnt, 0, 0,
+                          { pa_[u_] = sm[oR1 + blk0 + j]; pb_[u_] = sm[oAX1 + blk0 + j]; },
+                          {
+                              const double en = v + cc;
+                              sm[oE1 + blk0 + j] = en;
+                              p0 += pa_[u_] - pb_[u_] * en;
+                          },
+                          {
+                              for (int jo = tid; jo < noth; jo += BT) {
+                                  const double en = sm[oE1 + oth0 + jo] + cc;
+                                  sm[oE1 + oth0 + jo] = en;
+                                  p0 += sm[oR1 + oth0 + jo] - sm[oAX1 + oth0 + jo] * en;
+                              }
+                          },
+                          (nsp ? 1 : 0), xig, dum1);
+            c1 = nsp ? xig * rxx1 : 0.0;
         }
     };
     auto sweep1 = [&](bool post, bool ezero) __attribute__((always_inline)) {
@@ -822,7 +878,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     auto sweep2 = [&](bool ezero) __attribute__((always_inline)) {
         double s = 0.0, eo = 0.0;
         if (!ezero) {
-            s = wave_sum(res_rowdot<KE2, 8 * oE2>(c2, a2, smb));
+            s = wave_sum(res_rowdot_fma<KE2, 8 * oE2>(c2, a2, smb));
             eo = sm[oE2 + r2];
             s += dg2 * eo;
         }
@@ -831,14 +887,14 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         if (lane == 0) sm[oPUB + w] = wv;
         const double cc = c2s;
         double xig = 0.0;
-        RES_HANDOFF(4, N2, lo2, hi2 - lo2, 0, 0,
-                    {
-                        const double en = v + cc;
-                        sm[oE2 + j] = en;
-                        p0 += sm[oR2 + j] - sm[oAX2 + j] * en;
-                    },
-                    {}, (nsp ? 1 : 0), xig, dum1);
-        c2s = nsp ? xig / xx2 : 0.0;
+        RES_HANDOFF_P(4, N2, lo2, hi2 - lo2, 0, 0, { pa_[u_] = sm[oR2 + j]; pb_[u_] = sm[oAX2 + j]; },
+                      {
+                          const double en = v + cc;
+                          sm[oE2 + j] = en;
+                          p0 += pa_[u_] - pb_[u_] * en;
+                      },
+                      {}, (nsp ? 1 : 0), xig, dum1);
+        c2s = nsp ? xig * rxx2 : 0.0;
     };
 
     // tail level: restriction, Jacobi-PCG (PCG.m:68-87, zero guess), prolongation -- all of it by
@@ -1049,7 +1105,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                              p0 += sm[oR3L + j] - sm[oAX3L + j] * en;
                          },
                          (nsp ? 1 : 0), xig);
-            c3s = nsp ? xig / xx3 : 0.0;
+            c3s = nsp ? xig * rxx3 : 0.0;
         }
     };
     // one visit of level 3 and, through the remote tail rooted at level 4, of everything below it
@@ -1236,7 +1292,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         for (int s = (lfirst2 && !keep) ? 1 : 0; s < nu; ++s) sweep2(!keep && s == 0);
         // rr = r - A e                                                           MG_Vcycle.m:27
         {
-            const double s = wave_sum(res_rowdot<KE2, 8 * oE2>(c2, a2, smb)) + dg2 * sm[oE2 + r2];
+            const double s = wave_sum(res_rowdot_fma<KE2, 8 * oE2>(c2, a2, smb)) + dg2 * sm[oE2 + r2];
             if (lane == 0) sm[oPUB + w] = sm[oR2 + r2] - s;
             RES_HANDOFF(4, N2, lo2, hi2 - lo2, 0, 0, { sm[oRR2 + j] = v; }, {}, 0, dum0, dum1);
         }
@@ -1247,7 +1303,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 if (lane == 0) sm[oPUB + w] = s;
                 double sumr = 0.0;
                 RES_HANDOFF3({ sm[oR3L + j] = v; sm[oE3L + j] = 0.0; p0 += v; }, (nsp ? 1 : 0), sumr);
-                c3s = nsp ? sumr / xx3 : 0.0;
+                c3s = nsp ? sumr * rxx3 : 0.0;
                 sumr3 = sumr;
             }
             for (int leg = 0; leg < (D.wcycle ? 2 : 1); ++leg) visit3(leg == 1);   // MG_Wcycle.m:28-30
@@ -1255,9 +1311,9 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 const double sP = res_csr_rowdot(D.P3, rowp[12 * w + 10], rowp[12 * w + 11], lane, sm, oE3L);
                 if (lane == 0) sm[oPUB + w] = sm[oE2 + r2] + sP;
                 double xig = 0.0;
-                RES_HANDOFF(4, N2, lo2, hi2 - lo2, 0, 0,
-                            { sm[oE2 + j] = v; p0 += sm[oR2 + j] - sm[oAX2 + j] * v; }, {}, (nsp ? 1 : 0), xig, dum1);
-                c2s = nsp ? xig / xx2 : 0.0;
+                RES_HANDOFF_P(4, N2, lo2, hi2 - lo2, 0, 0, { pa_[u_] = sm[oR2 + j]; pb_[u_] = sm[oAX2 + j]; },
+                              { sm[oE2 + j] = v; p0 += pa_[u_] - pb_[u_] * v; }, {}, (nsp ? 1 : 0), xig, dum1);
+                c2s = nsp ? xig * rxx2 : 0.0;
             }
         } else {
             tail();
@@ -1271,15 +1327,15 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         const int nu = D.nu;
         for (int s = 0; s < nu; ++s) sweep1(false, s == 0);
         {   // rr = r - A e on both blocks
-            const double sF = wave_sum(res_rowdot<KE1, 8 * oE1>(cF, aF, smb)) + dgF * sm[oE1 + rF];
-            const double sC = wave_sum(res_rowdot<KE1, 8 * oE1>(cC, aC, smb)) + dgC * sm[oE1 + rC];
+            const double sF = wave_sum(res_rowdot_fma<KE1, 8 * oE1>(cF, aF, smb)) + dgF * sm[oE1 + rF];
+            const double sC = wave_sum(res_rowdot_fma<KE1, 8 * oE1>(cC, aC, smb)) + dgC * sm[oE1 + rC];
             if (lane == 0) {
                 sm[oPUB + w] = sm[oR1 + rF] - sF;
                 sm[oPUB + RES_WAVES + w] = sm[oR1 + rC] - sC;
             }
             if (xm) {   // the F part arrives pre-scaled by rho for the mask-form restriction below
-                RES_HANDOFF(4, N1, loF, hiF - loF, loC, hiC - loC,
-                            { sm[oRR1 + j] = j < nf ? v * sm[oRHO + j] : v; }, {}, 0, dum0, dum1);
+                RES_HANDOFF_P(4, N1, loF, hiF - loF, loC, hiC - loC, { pa_[u_] = j < nf ? sm[oRHO + j] : 1.0; },
+                              { sm[oRR1 + j] = j < nf ? v * pa_[u_] : v; }, {}, 0, dum0, dum1);
             } else {
                 RES_HANDOFF(4, N1, loF, hiF - loF, loC, hiC - loC, { sm[oRR1 + j] = v; }, {}, 0, dum0, dum1);
             }
@@ -1295,7 +1351,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             double sumr = 0.0;
             RES_HANDOFF(4, N2, lo2, hi2 - lo2, 0, 0, { sm[oR2 + j] = v; sm[oE2 + j] = 0.0; p0 += v; }, {},
                         (nsp ? 1 : 0), sumr, dum1);
-            c2s = nsp ? sumr / xx2 : 0.0;
+            c2s = nsp ? sumr * rxx2 : 0.0;
             sumr2p = sumr;
             if (lfirst2 && !POLY2) {   // sweep2(true) of the first visit, same thread-to-entry map and sums
                 const double cc = c2s;
@@ -1333,9 +1389,9 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 sm[oPUB + RES_WAVES + w] = sm[oE1 + rC] + sC;
             }
             double xig = 0.0;
-            RES_HANDOFF(4, N1, loF, hiF - loF, loC, hiC - loC,
-                        { sm[oE1 + j] = v; p0 += sm[oR1 + j] - sm[oAX1 + j] * v; }, {}, (nsp ? 1 : 0), xig, dum1);
-            c1 = nsp ? xig / xx1 : 0.0;
+            RES_HANDOFF_P(4, N1, loF, hiF - loF, loC, hiC - loC, { pa_[u_] = sm[oR1 + j]; pb_[u_] = sm[oAX1 + j]; },
+                          { sm[oE1 + j] = v; p0 += pa_[u_] - pb_[u_] * v; }, {}, (nsp ? 1 : 0), xig, dum1);
+            c1 = nsp ? xig * rxx1 : 0.0;
         }
         for (int s = 0; s < nu; ++s) sweep1(true, false);
     };
@@ -1433,6 +1489,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
 #undef RES_HANDOFF3R
 #undef RES_HANDOFF4
 #undef RES_HANDOFF
+#undef RES_HANDOFF_P
 #undef dgF
 #undef dvF
 #undef bF

@@ -25,6 +25,7 @@ static constexpr SwitchInfo IPD_SWITCHES[] = {
     {"IPD_NO_RES_POLY4", SW_FLAG, "deep mode / POLY3 mode with the tail rooted at level 4 (A/B of POLY4)"},
     {"IPD_RESIDENT_G", SW_VALUE, "<grid>: more resident workgroups than the rows need (measurement)"},
     {"IPD_RESIDENT_RANKS", SW_VALUE, "<R>: rank groups with a granule buffer each (the sharded resident kernel in emulation, tests)"},
+    {"IPD_RES_PRESLEEP", SW_VALUE, "<n>: k_resident's s_sleep(1) count between a publish and the first poll (measurement)"},
     {"IPD_RES_DEBUG_SKIP_PUBLISH", SW_VALUE, "<step>: one omitted publish exercises the give-up and recovery path (tests)"},
     {"IPD_NO_SUBCYCLE", SW_FLAG, "the single-workgroup sub-cycle off: the generic phases stay tested"},
     {"IPD_NO_SMALL", SW_FLAG, "the single-workgroup whole solve off: the generic phases stay tested"},
