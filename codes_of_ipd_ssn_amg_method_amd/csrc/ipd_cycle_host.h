@@ -52,6 +52,12 @@ struct CycleState {
         int LD = 0, N = 0, Nc = 0;
     };
     std::vector<PolyOp> poly_ops;
+    struct RowsOp {                // row-layout polynomial operators of the resident kernels (ipd_amg_packed_operator)
+        const double* M = nullptr; // [N + Nc][ld], W (N + Nc entries) right behind
+        int ld = 0, seg = 0, N = 0, Nc = 0;
+    };
+    std::vector<RowsOp> rows_ops;  // per level: form 64 (level 3 / 4 of k_resident's `three` mode or of DEEP mode)
+    RowsOp poly2_op;               // form 128: level 2 composed over a visit
     SolveDesc* d_sub4 = nullptr;   // image rooted at level 4 for the resident kernel's `three` mode
     size_t sub4_lds = 0;           // (packed beside d_sub when that one is rooted at level 3)
     SolveDesc* d_sub3 = nullptr;   // image rooted at level 3 for the resident kernel alone (k_sub == 0)
@@ -347,6 +353,24 @@ static BPolyDev pack_bpoly(ipd_ctx* ctx, ipd_amg* h, CycleState* st, int k, int 
     return b;
 }
 
+// what a row-layout pack holds (its own layout), for ipd_amg_packed_operator
+static CycleState::RowsOp rows_op(const BPolyDev& b) {
+    CycleState::RowsOp r;
+    r.M = b.M;
+    r.ld = b.e.rows_ld;
+    r.seg = b.e.rows_seg;
+    r.N = b.e.N;
+    r.Nc = b.e.Nc;
+    return r;
+}
+// one kernel's set of row-layout levels: level 3 is packed first and starts the set afresh, so that a
+// hierarchy planned for one resident kernel and then for another never reports a mix of the two
+static void record_rows_op(CycleState* st, const ipd_amg* h, int k, const BPolyDev& b) {
+    if (k == 3) st->rows_ops.assign((size_t)h->J + 1, CycleState::RowsOp{});
+    st->rows_ops.resize((size_t)h->J + 1);
+    st->rows_ops[(size_t)k] = rows_op(b);
+}
+
 // ---- level-resident solve kernel: eligibility and launch ---------------------------------
 // Eligible: three levels -- a bigraph Gauss-Seidel level 1 and a Jacobi level 2 with padded
 // rows of at most 1024 entries, at most 2048 rows each, and a tail level of at most 64 rows --
@@ -518,12 +542,14 @@ static void plan_resident(ipd_amg* h, CycleState* st, const PlanSwitches& sw) {
             const BPolyDev pb = pack_bpoly(h->ctx, h, st, 3, h->opts.isnsp, 0, true);
             D.p3rows = pb.M;
             D.p3w = pb.W;
+            record_rows_op(st, h, 3, pb);
             st->level_forms.resize((size_t)h->J + 1, 0);
             st->level_forms[3] |= 64;
             if (poly4) {
                 const BPolyDev pb4 = pack_bpoly(h->ctx, h, st, 4, h->opts.isnsp, 0, true, RES_P4_SEG, RES_P4_LD);
                 D.p4rows = pb4.M;
                 D.p4w = pb4.W;
+                record_rows_op(st, h, 4, pb4);
                 D.N5 = N5r;
                 st->level_forms[4] |= 64;
             }
@@ -1867,11 +1893,13 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
             IPD_KERNEL_CHECK();
             if (ctx->fetch1(bad) == 0) {
                 const BPolyDev pb = pack_bpoly(ctx, h, st, 3, h->opts.isnsp, 0, true, RB_P3_SEG, RB_P3_LD);
+                record_rows_op(st, h, 3, pb);
                 st->level_forms.resize((size_t)h->J + 1, 0);
                 st->level_forms[3] |= 64;
                 BPolyDev pb4;
                 if (poly4) {
                     pb4 = pack_bpoly(ctx, h, st, 4, h->opts.isnsp, 0, true, RB_P4_SEG, RB_P4_LD);
+                    record_rows_op(st, h, 4, pb4);
                     st->level_forms[4] |= 64;
                 }
                 ResBigDesc B{};
@@ -1988,6 +2016,7 @@ static bool amg_attach_poly2(ipd_amg* h) {
     st->res_desc.p2w = pb.W;
     st->res_desc.p2seg = seg;
     st->res_desc.p2ld = ld;
+    st->poly2_op = rows_op(pb);
     st->res_poly2 = true;
     st->res_capacity = -1;
     st->level_forms.resize((size_t)h->J + 1, 0);
@@ -2580,6 +2609,50 @@ extern "C" int ipd_amg_poly_operator(const ipd_amg* h, int32_t k, double* out, i
         *ld = po.LD;
         *n = po.N;
         *nc = po.Nc;
+    });
+}
+
+// Test hook: the polynomial operator of level k exactly as packed for `form` (see include/ipd_amg.h).
+extern "C" int ipd_amg_packed_operator(const ipd_amg* h, int32_t k, int32_t form, double* out, int64_t cap,
+                                       int32_t* ld, int32_t* seg, int32_t* n, int32_t* nc) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && ld && seg && n && nc && (out || cap == 0), IPD_E_ARG, "NULL argument");
+        const CycleState* st = h->cyc.get();
+        IPD_REQUIRE(st && (form == 16 || form == 64 || form == 128), IPD_E_ARG, "no such form");
+        const double* M = nullptr;
+        int LD = 0, S = 0, N = 0, Nc = 0;
+        int64_t need = 0;
+        if (form == 16) {
+            if (k >= 1 && (size_t)k < st->poly_ops.size()) {
+                const CycleState::PolyOp& po = st->poly_ops[(size_t)k];
+                M = po.M;
+                LD = po.LD;
+                N = po.N;
+                Nc = po.Nc;
+                S = (N + 7) / 8 * 8;
+                need = (int64_t)LD * (2 * S + (Nc + 7) / 8 * 8 + 1);   // W lies right behind M (pack_bpoly)
+            }
+        } else {
+            const CycleState::RowsOp* op = nullptr;
+            if (form == 64 && k >= 1 && (size_t)k < st->rows_ops.size()) op = &st->rows_ops[(size_t)k];
+            if (form == 128 && k == 2) op = &st->poly2_op;
+            if (op) {
+                M = op->M;
+                LD = op->ld;
+                S = op->seg;
+                N = op->N;
+                Nc = op->Nc;
+                need = (int64_t)(N + Nc) * (LD + 1);                   // W lies right behind the rows
+            }
+        }
+        IPD_REQUIRE(M, IPD_E_ARG, "level has no operator packed in that form");
+        *ld = LD;
+        *seg = S;
+        *n = N;
+        *nc = Nc;
+        if (!out) return;   // size query
+        IPD_REQUIRE(cap >= need, IPD_E_ARG, "buffer too small");
+        h->ctx->fetch(M, out, (size_t)need);
     });
 }
 

@@ -485,6 +485,17 @@ int ipd_amg_level_forms(const ipd_amg* h, int32_t* forms, int32_t count);
  * (AMG/MG_Vcycle.m:14-41 as two dense maps).  IPD_E_ARG without such an operator. */
 int ipd_amg_poly_operator(const ipd_amg* h, int32_t k, double* out, int64_t cap, int32_t* ld, int32_t* n,
                           int32_t* nc);
+/* Test hook: the polynomial operator of level k exactly as packed for `form` (ipd_amg_level_forms' bits):
+ * 16: the images' column-major layout of ipd_amg_poly_operator (*seg = *n rounded up to 8);
+ * 64: level 3 or 4 of a resident kernel (k_resident's `three` mode or the mask-form kernel's deep mode);
+ * 128: level 2 composed over a visit (ipd_amg_attach_level2_poly).
+ * 64 / 128: row-major, *n + *nc rows of *ld doubles, then the *n + *nc factors of 1'r; `out` needs
+ * (*n + *nc) (*ld + 1) doubles.  Row i < n: [M2a | M1 | M1 P] at columns 0, *seg, 2 *seg, factor w_i;
+ * row n + c: [P' - T1 M2a | -T1 M1] and factor -T1 w (T1 = P'A).  Form 128 replaces M1 in rows i < n by
+ * B = (I + M1) M2a and w_i by (I + M1) w.  out = NULL with cap = 0: only the layout (*ld, *seg, *n, *nc).
+ * IPD_E_ARG when level k has no operator in that form, or cap is below what the layout needs.       */
+int ipd_amg_packed_operator(const ipd_amg* h, int32_t k, int32_t form, double* out, int64_t cap, int32_t* ld,
+                            int32_t* seg, int32_t* n, int32_t* nc);
 /* Mode 2 only: `cycles` loop bodies in one launch with in-kernel stamps of workgroup 0:
  * stamps[0] shader clocks spent waiting in hand-off sweeps, [1] shader clocks of the launch,
  * [2] hand-offs, [3] 100 MHz ticks of the launch, [4] clocks in the barrier ahead of the

@@ -50,25 +50,32 @@ def capture(ipd, N, kcap):
 
 @pytest.fixture(scope="module", params=[12, 24], ids=["k13", "k25"])
 def newton2048(ipd, request):
+    """(n, Ae, f, tk): the captured system, or -- when it has several components -- its largest component as
+    Hybrid_AMG.m:55-70 takes it (Ae(pk, pk) with pk ascending, so the F side comes first and n = sum(pk <= N)),
+    the system ipd_hybrid's gathered mask form serves."""
     N = 2048
     Ae, f, tk = capture(ipd, N, request.param)
-    if sp.csgraph.connected_components(Ae)[0] != 1:
-        pytest.skip("the captured system has several components (the mask form needs the whole Ae)")
+    ncomp, lab = sp.csgraph.connected_components(Ae)
+    if ncomp > 1:
+        pk = np.flatnonzero(lab == np.argmax(np.bincount(lab)))
+        return int((pk < N).sum()), sp.csr_matrix(Ae[pk, :][:, pk]), f[pk], tk
     return N, Ae, f, tk
 
 
-def _deep_hierarchy(ipd, Ae, N, tk, cycle):
-    h = ipd.AMGHierarchy(Ae, options(cycle, N), ipd.MatlabRand(5489))
-    one = np.ones(N)
-    h.attach_mask_operator(one, one, tk)
+def _deep_hierarchy(ipd, Ae, n, tk, cycle):
+    """The hierarchy with the mask form attached for the gathered p (C rows) and q (F rows): all ones in these
+    captures (Hybrid_AMG.m:17-24 with p = q = 1)."""
+    h = ipd.AMGHierarchy(Ae, options(cycle, n), ipd.MatlabRand(5489))
+    h.attach_mask_operator(np.ones(Ae.shape[0] - n), np.ones(n), tk)
     return h
 
 
 @pytest.mark.parametrize("cycle", ["w", "v"])
 def test_deep_mode_against_the_oracle_and_the_launches(ipd, newton2048, cycle):
     N, Ae, f, tk = newton2048
+    M = Ae.shape[0]
     # Hybrid_AMG.m:40 starts from bk1 * tk * rand(M, 1): a non-zero guess for the W case, zeros for the V case
-    x0 = 1e-4 * np.random.RandomState(4).random_sample(2 * N) if cycle == "w" else np.zeros(2 * N)
+    x0 = 1e-4 * np.random.RandomState(4).random_sample(M) if cycle == "w" else np.zeros(M)
     h = _deep_hierarchy(ipd, Ae, N, tk, cycle)
     mode, grid, _ = solve_mode(h)
     if mode != 2:
@@ -110,7 +117,30 @@ def test_deep_mode_against_the_oracle_and_the_launches(ipd, newton2048, cycle):
     assert np.linalg.norm(Ae @ (a - b)) <= 5e-9 * nf_
     assert np.array_equal(a, bench_cycles(h, f, x0, 3)[0])
     # zero right-hand side (Class_AMG.m:91-92)
-    xz, itz, relz, relkz, rhokz = h.solve(np.zeros(2 * N), None)
+    xz, itz, relz, relkz, rhokz = h.solve(np.zeros(M), None)
     assert itz == 0 and relkz[0] == 0.0 and not xz.any()
     h.close()
     hc.close()
+
+
+def test_deep_mode_polynomial_operators_against_numpy(ipd, newton2048):
+    """Levels 3 and 4 of the deep mode in polynomial form (ResBigDesc::p3rows / p4rows in the RB_P3_SEG /
+    RB_P4_SEG row layouts, forms bit 64) as packed, against the numpy restatement of the algebra
+    (tests/test_gpu_poly_operators.py: bars, padding -- the deep passes read whole segments -- and the power
+    of the check against nu -+ 1, isnsp flipped and D^-1 scaled by 1 + 1e-6)."""
+    from tests.test_gpu_poly_operators import check_rows_operator
+    N, Ae, f, tk = newton2048
+    h = _deep_hierarchy(ipd, Ae, N, tk, "w")
+    if solve_mode(h)[0] != 2:
+        pytest.skip("hierarchy %s not taken by the mask-form kernel's deep mode" % h.level_sizes())
+    assert resident_kernel_name(h) in ("k_resident_big<4,2,true>", "k_resident_big<8,2,true>")
+    forms = h.level_forms()
+    assert forms[2] & 64, forms
+    levels = [k for k in (3, 4) if k < h.J and forms[k - 1] & 64]
+    from codes_of_ipd_ssn_amg_method_amd import _lib
+    lev, root = c_int32(), c_int32()
+    _lib.check(_lib.lib.ipd_amg_resident_levels(h.handle, byref(lev), byref(root)))
+    assert levels == ([3, 4] if (lev.value, root.value) == (4, 5) else [3]), (levels, lev.value, root.value)
+    for k in levels:
+        check_rows_operator(h, k, 1, 5)
+    h.close()

@@ -21,7 +21,7 @@ import scipy.sparse as sp
 import bench
 from oracle import ipd_oracle as O
 from tests import problems as PR
-from tests.test_gpu_bench_workload import bench_cycles, env, options, same_history, solve_mode
+from tests.test_gpu_bench_workload import bench_cycles, env, options, resident_kernel_name, same_history, solve_mode
 
 pytestmark = pytest.mark.gpu
 
@@ -289,4 +289,32 @@ def test_block_wide_polynomial_operators_against_numpy(ipd, newton_system):
             assert np.abs(got - want).max() <= tol * (1.0 + np.abs(want).max()), (k, name)
         # the padding the passes rely on is zero
         assert not M[N + Nc:, :].any() and not M[:, N:N8].any() and not M[:, N8 + N:2 * N8].any()
+    h.close()
+
+
+def test_row_layout_polynomial_operators_against_numpy(ipd, newton_system):
+    """Level 3 (and level 4 where POLY4 is packed) of k_resident's `three` mode in polynomial form
+    (ResDesc::p3rows / p4rows, forms bit 64) as packed, against the numpy restatement of the algebra
+    (tests/test_gpu_poly_operators.py: bars, padding, and the power of the check against nu -+ 1, isnsp
+    flipped and D^-1 scaled by 1 + 1e-6)."""
+    from codes_of_ipd_ssn_amg_method_amd import _lib
+    from tests.test_gpu_poly_operators import check_image_form_hook, check_rows_operator
+    Ae, f, n, _ = newton_system
+    opts = options("w", n)
+    h = ipd.AMGHierarchy(Ae, opts, ipd.MatlabRand(5489))
+    forms = h.level_forms()
+    for k in range(1, h.J):                                  # (form 16 through the same hook)
+        if forms[k - 1] & 16:
+            check_image_form_hook(h, k)
+    levels = [k for k in (3, 4) if k < h.J and forms[k - 1] & 64]
+    if not levels:
+        pytest.skip("no level of %s in the resident kernels' polynomial form (forms %s, kernel %s)" % (
+            h.level_sizes(), forms, resident_kernel_name(h)))
+    assert resident_kernel_name(h).startswith("k_resident<"), resident_kernel_name(h)
+    # level 4 is in polynomial form exactly where the kernel holds it (POLY4: resident levels 4, tail root 5)
+    lev, root = c_int32(), c_int32()
+    _lib.check(_lib.lib.ipd_amg_resident_levels(h.handle, byref(lev), byref(root)))
+    assert levels == ([3, 4] if (lev.value, root.value) == (4, 5) else [3]), (levels, lev.value, root.value)
+    for k in levels:
+        check_rows_operator(h, k, opts["isnsp"], opts["smoth"])
     h.close()

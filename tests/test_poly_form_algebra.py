@@ -64,3 +64,39 @@ def test_a_visit_is_two_dense_maps(N, Nc, isnsp):
         assert np.abs(pre - pre_poly).max() <= 1e-11 * scale
         assert np.abs(rc - rc_poly).max() <= 1e-11 * (scale + np.abs(rc).max())
         assert np.abs(post - post_poly).max() <= 1e-11 * scale
+
+
+def composed_operators(A, P, dinv, isnsp, nu):
+    """What amg_attach_poly2 / k_bpoly_compose produce for a level whose coarse level has ONE row (the
+    metric's level 2): the whole visit of MG_Vcycle.m:14-41 as e = B r + wB (1'r) + mp ec, where the coarse
+    correction is ec = (s r + ws (1'r)) / Ac (PCG.m on one row) -- pre-smoothing from zero, the restriction
+    and post-smoothing folded into one dense map."""
+    M = stacked_operators(A, P, dinv, isnsp, nu)
+    I1 = np.eye(A.shape[0]) + M["M1"]
+    return dict(B=I1 @ M["M2a"], wB=I1 @ M["w"], mp=M["Mc"][:, 0], s=M["Mr_low"][0], ws=float(M["W_low"][0]))
+
+
+@pytest.mark.parametrize("nu", [1, 2, 5])
+@pytest.mark.parametrize("isnsp", [0, 1])
+@pytest.mark.parametrize("N", [14, 40, 100])
+def test_composed_visit_is_one_dense_map(N, isnsp, nu):
+    """Level 2 of a three-level hierarchy whose coarsest level has one row: the composed operator of the
+    resident kernel's POLY2 form (ResDesc::p2rows) against the oracle's visit -- pre-smoothing from zero
+    (O._smooth, MG_Vcycle.m:14-25), restriction (:27), the one-row coarse solve (:43, PCG.m), prolongation
+    and post-smoothing (:31-41)."""
+    A, P, dinv, rs = level(N, 1, 11 * N + 3 * nu + isnsp)
+    As = sp.csr_matrix(A)
+    R = sp.diags(dinv).tocsr()
+    Ac = sp.csr_matrix(P.T @ A @ P)
+    C = composed_operators(A, P, dinv, isnsp, nu)
+    for _ in range(3):
+        r = rs.standard_normal(N)
+        pre = O._smooth(As, R, r, np.zeros(N), isnsp, nu)
+        rc = P.T @ (r - A @ pre)
+        ec = O.PCG(Ac, rc)[0]
+        e = O._smooth(As, R, r, pre + P @ ec, isnsp, nu)
+        sumr = float(np.ones(N) @ r)
+        rc_poly = float(C["s"] @ r) + C["ws"] * sumr
+        e_poly = C["B"] @ r + C["wB"] * sumr + C["mp"] * (rc_poly / Ac[0, 0])
+        assert abs(rc[0] - rc_poly) <= 1e-11 * (1.0 + abs(rc[0]) + np.abs(r).max())
+        assert np.abs(e - e_poly).max() <= 1e-11 * (1.0 + np.abs(e).max())
