@@ -259,9 +259,14 @@ static inline T* zeroed(ipd_ctx* ctx, size_t n) {
 // end of the producer: the counts array starts out as zeros (zero pool), every producer stores count + 1 with
 // an agent-scope store (scan_put: written through, visible across the XCDs' L2s without a fence), and the
 // scanning workgroup polls the entries until none is zero.  It is the last workgroup to be dispatched, so every
-// entry it waits for belongs to a workgroup that is running or done; a bounded spin turns a missing entry into
-// a negative total (the host raises) instead of a hang.  Bit 30 of an entry is a flag the producer may set
-// (scan_put's third argument); the OR of the flags travels beside the total.
+// entry it waits for belongs to a workgroup that is running or done.  That rests on an ASSUMPTION about the
+// hardware, not on anything HIP guarantees: workgroups are dispatched in blockIdx order (x fastest, then y), also
+// for grids larger than the chip holds at once (k_spgemm_rows: up to 16384 workgroups).  Were a workgroup with a
+// lower index dispatched only after the scanning one, it could wait for a slot the spinning workgroup holds.  A
+// bounded spin turns a missing entry into a negative total instead of a hang, and the host raises on it: a waited
+// total in TailTotal::wait, a lazily fetched one where the fetch lands (spgemm_check_lazy_count, amg_transfer).
+// Bit 30 of an entry is a flag the producer may set (scan_put's third argument); the OR of the flags travels
+// beside the total.
 struct ScanTail {
     const int* in = nullptr;     // n biased counts (zeros before the launch)
     int* out = nullptr;          // n+1 row pointers (nullptr: no tail)
@@ -542,6 +547,9 @@ constexpr size_t SPGEMM_LAZY_MAX = size_t(1) << 21;
 // maxrow_dev (lazy only): the longest row of C is stored there; x_maxrow: the longest row of X if known (estimate)
 void csr_spgemm(ipd_ctx* ctx, Arena& dst, const Csr& X, const Csr& Y, Csr* C, int* total_dev = nullptr,
                 LazyPost* post = nullptr, int* maxrow_dev = nullptr, int x_maxrow = 0);
+// the caller's check of a fetched lazy count against the bound C's arrays were sized by (C.nnz before the fetch):
+// a count outside [0, C.nnz] (a ScanTail total of -1) raises IPD_E_HIP naming the product and the level
+void spgemm_check_lazy_count(const Csr& C, int fetched, const char* product, int level);
 void csr_expand_dense(ipd_ctx* ctx, const Csr& A, double* dense, int ld);  // dense pre-zeroed
 // st.out != NULL: rowcnt is zeroed<int> and the launch's tail scans the (biased) counts into st.out (nr > 0);
 // an empty st leaves plain counts

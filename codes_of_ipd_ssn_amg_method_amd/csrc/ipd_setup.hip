@@ -1512,6 +1512,14 @@ void amg_transfer(ipd_ctx* ctx, Arena& dst, const Csr& A, const AmgOpts& o, int 
         else
             ctx->fetch(c3, h3, 5);
         hint[3] = h3[4];
+        // P, P'A and Ac were sized by bounds (P.nnz, T1.nnz, C.nnz until here); a count outside [0, bound] is a
+        // scan that never completed (a ScanTail total of -1, ipd_internal.h) and must size nothing that follows
+        if (lazy && (h3[0] < 0 || h3[0] > P.nnz))
+            throw IpdError(IPD_E_HIP, "transfer: lazily fetched entry count of P on level " + std::to_string(level) +
+                                          " is " + std::to_string(h3[0]) + ", outside [0, " +
+                                          std::to_string(P.nnz) + "]");
+        spgemm_check_lazy_count(T1, h3[1], "P'*A", level);
+        spgemm_check_lazy_count(C, h3[2], "P'*A*P", level);
         if (lazy) {
             P.nnz = Pt.nnz = h3[0];
             IPD_REQUIRE(h3[3] == 0, IPD_E_UNSUPPORTED,

@@ -891,6 +891,13 @@ void csr_spgemm(ipd_ctx* ctx, Arena& dst, const Csr& X, const Csr& Y, Csr* C, in
     *C = out;
 }
 
+void spgemm_check_lazy_count(const Csr& C, int fetched, const char* product, int level) {
+    if (fetched < 0 || fetched > C.nnz)
+        throw IpdError(IPD_E_HIP, std::string("spgemm: lazily fetched entry count of ") + product + " on level " +
+                                      std::to_string(level) + " is " + std::to_string(fetched) + ", outside [0, " +
+                                      std::to_string(C.nnz) + "]");
+}
+
 // dense-row helpers shared with the interpolation build (ipd_setup.hip)
 void csr_expand_dense(ipd_ctx* ctx, const Csr& A, double* dense, int ld) {
     if (A.nr == 0 || A.nnz == 0) return;

@@ -1,5 +1,7 @@
 """The BASELINE.json configurations at FULL size, checked through size-independent
-properties (the oracle would take minutes at these sizes):
+properties (the oracle itself takes well under a second per setup or Hybrid_AMG call at these sizes for
+tree, hub and Bernoulli(0.04) masks -- tests/test_gpu_setup_at_scale.py compares with it bit for bit there --
+but tens of seconds for the rho = 1 masks):
   [1] Class 1, m=n=256, V-cycle AMG       [2] Class 1, m=n=1024, W-cycle + Hybrid_AMG
   [3] Class 2, m=n=512, AMG4POT           [4] Class 1, m=n=2048 (the sharded config; the
       row-block logic is exercised in emulation on one GPU, see test_gpu_sharded.py)
