@@ -57,15 +57,15 @@ def test_deep_mode_against_the_oracle_and_the_launches(ipd, newton2048, cycle):
     x0 = 1e-4 * np.random.RandomState(4).random_sample(M) if cycle == "w" else np.zeros(M)
     h = _deep_hierarchy(ipd, Ae, N, tk, cycle)
     mode, grid, _ = solve_mode(h)
-    if mode != 2:
-        pytest.skip("hierarchy %s / %s not taken by the mask-form kernel's deep mode" % (
-            h.level_sizes(), [h.level_dims(k)[1] for k in range(1, h.J + 1)]))
-    assert resident_kernel_name(h) in ("k_resident_big<4,2,true>", "k_resident_big<8,2,true>")
-    assert h.J >= 5 and 129 <= grid <= 256
+    assert mode == 2, (h.level_sizes(), [h.level_dims(k)[1] for k in range(1, h.J + 1)])
+    # both captures: level-2 rows of at most 16 entries (KE2 = 4), six levels, level 4 resident as well
+    # (tests/test_gpu_resident_instantiations.py reaches <8,2,true> and the tail rooted at 4)
+    assert resident_kernel_name(h) == "k_resident_big<4,2,true>"
+    assert h.J >= 6 and 129 <= grid <= 256
     from codes_of_ipd_ssn_amg_method_amd import _lib
     lev, root = c_int32(), c_int32()
     _lib.check(_lib.lib.ipd_amg_resident_levels(h.handle, byref(lev), byref(root)))
-    assert (lev.value, root.value) in ((3, 4), (4, 5))      # (4, 5): level 4 resident as well (six levels and more)
+    assert (lev.value, root.value) == (4, 5)
     with env(IPD_NO_RESIDENT_DEEP=1):
         hc = _deep_hierarchy(ipd, Ae, N, tk, cycle)
     assert solve_mode(hc)[0] == 0 and hc.level_sizes() == h.level_sizes()
@@ -110,9 +110,8 @@ def test_deep_mode_polynomial_operators_against_numpy(ipd, newton2048):
     from tests.test_gpu_poly_operators import check_rows_operator
     N, Ae, f, tk = newton2048
     h = _deep_hierarchy(ipd, Ae, N, tk, "w")
-    if solve_mode(h)[0] != 2:
-        pytest.skip("hierarchy %s not taken by the mask-form kernel's deep mode" % h.level_sizes())
-    assert resident_kernel_name(h) in ("k_resident_big<4,2,true>", "k_resident_big<8,2,true>")
+    assert solve_mode(h)[0] == 2, h.level_sizes()
+    assert resident_kernel_name(h) == "k_resident_big<4,2,true>"
     forms = h.level_forms()
     assert forms[2] & 64, forms
     levels = [k for k in (3, 4) if k < h.J and forms[k - 1] & 64]

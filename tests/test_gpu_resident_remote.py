@@ -109,17 +109,24 @@ def test_remote_tail_matches_the_multi_launch_path(ipd, newton_system, cycle):
     hc.close()
 
 
-def _against_oracle(ipd, Ae, f, n, cycle, x0, expect_mode=None, kv=None):
+def _against_oracle(ipd, Ae, f, n, cycle, x0, expect_mode=None, kv=None, smoth=5, isnsp=1, attach=None,
+                    inspect=None):
     """One Class_AMG solve on the device against the SciPy oracle's (AMG/Class_AMG.m:86-109): the same
     hierarchy sizes, the same cycle count, residual histories to 1e-10 and A(x - x_oracle) at the
-    rounding floor of A*x."""
-    opts = options(cycle, n)
+    rounding floor of A*x.  `attach(h)` (a mask operator, the composed level 2) must succeed before the
+    solve, and `inspect(h)` sees the hierarchy the solve runs on (both under `kv`)."""
+    opts = options(cycle, n, isnsp=isnsp)
+    opts["smoth"] = smoth
     with env(**(kv or {})):
         h = ipd.AMGHierarchy(Ae, opts, ipd.MatlabRand(5489))
+        if attach is not None:
+            assert attach(h)
         mode = solve_mode(h)[0]
         if expect_mode is not None and mode != expect_mode:
             h.close()
             return None
+        if inspect is not None:
+            inspect(h)
         x, it, rr, relk, rhok = h.solve(f, x0)
     assert solve_mode(h)[2] == 0
     o = dict(opts)
