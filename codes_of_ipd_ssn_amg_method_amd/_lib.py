@@ -109,6 +109,11 @@ _multi_args = [c_void_p, POINTER(c_double), c_int64, c_int64, POINTER(c_double),
                POINTER(c_int32), POINTER(c_double), POINTER(c_double), POINTER(c_double)]
 lib.ipd_amg_solve_multi.argtypes = _multi_args
 lib.ipd_amg_solve_multi_dev.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p] + _multi_args[6:]
+_pcg_multi_args = [c_void_p, POINTER(c_double), c_int64, c_int64, POINTER(c_double), POINTER(ipd_pcg_opts),
+                   POINTER(c_double), POINTER(c_int64), POINTER(c_double), POINTER(c_double)]
+lib.ipd_amg_pcg_multi.argtypes = _pcg_multi_args
+lib.ipd_amg_pcg_multi_dev.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_void_p, POINTER(ipd_pcg_opts),
+                                      c_void_p] + _pcg_multi_args[7:]
 
 # every symbol the header declares (tests check that they all resolve)
 EXPORTS = [
@@ -118,6 +123,7 @@ EXPORTS = [
     "ipd_aty", "ipd_asat", "ipd_inv_aat", "ipd_inv_hht", "ipd_strength", "ipd_cf_split",
     "ipd_mis_set", "ipd_transfer", "ipd_amg_setup", "ipd_amg_destroy", "ipd_amg_num_levels",
     "ipd_amg_level_dims", "ipd_amg_get_A", "ipd_amg_get_P", "ipd_amg_get_cmask", "ipd_amg_solve", "ipd_amg_solve_multi", "ipd_amg_solve_multi_dev", "ipd_amg_pcg", "ipd_amg_pcg_dev",
+    "ipd_amg_pcg_multi", "ipd_amg_pcg_multi_dev",
     "ipd_amg_vcycle", "ipd_amg_wcycle", "ipd_class_amg", "ipd_pcg", "ipd_components",
     "ipd_hybrid_amg", "ipd_amg4pot", "ipd_dmalloc", "ipd_dfree", "ipd_h2d", "ipd_d2h",
     "ipd_dmat_upload", "ipd_dmat_download", "ipd_dmat_dims", "ipd_dmat_destroy",

@@ -30,7 +30,7 @@ __all__ = [
     "AMG4POT", "MatlabRand", "IpdError", "amg_options", "APDWorkspace", "warmup_class1",
     "warmup_class2", "APD_SsN_Class1", "APD_SsN_Class2", "twogrid_bigph", "twogrid", "Hybrid_twogrid",
     "aug_PCG", "PCG4POT", "load_input", "sparse_multiply", "spd_solve", "AMG_PCG",
-    "Class_AMG_multi",
+    "Class_AMG_multi", "AMG_PCG_multi",
 ]
 
 
@@ -351,6 +351,24 @@ class AMGHierarchy:
                               byref(it), byref(res), dptr(resk)))
         return d, int(it.value), float(res.value), resk
 
+    def pcg_multi(self, E, pcg_options: dict | None = None):
+        """Several right-hand sides (``ipd_amg_pcg_multi``): column j of ``E`` (N x k) through ``pcg``'s
+        loop as if solved alone.  Returns ``D`` (N x k), ``it`` (k,), ``res`` (k,) and ``resk``
+        (maxit x k, zeros past ``it[j]`` in column j).  ``pcg_options``: ``retol``, ``maxit``, ``guess``
+        (N x k); ``precd`` must stay unset."""
+        g = None if pcg_options is None else pcg_options.get("guess")
+        Ef, gf, k = multi_args(self.N, E, g)
+        o = _pcg_opts_struct(pcg_options)
+        maxit = int(o.maxit) if o.maxit >= 0 else 10000
+        D = np.empty((self.N, k), order="F")
+        it = np.zeros(k, np.int64)
+        res = np.zeros(k)
+        resk = np.zeros((maxit, k), order="F")
+        check(lib.ipd_amg_pcg_multi(self.handle, dptr(Ef), self.N, k, dptr(gf) if gf is not None else None,
+                                    byref(o), dptr(D), it.ctypes.data_as(POINTER(c_int64)), dptr(res),
+                                    dptr(resk)))
+        return D, it, res, resk
+
     def cycle_bytes(self) -> float:
         v = c_double()
         check(lib.ipd_amg_cycle_bytes(self.handle, byref(v)))
@@ -436,6 +454,17 @@ def AMG_PCG(A, b, amg_options: dict, pcg_options: dict | None = None, rng: Matla
     h = AMGHierarchy(A, amg_options, rng)
     try:
         return h.pcg(b, pcg_options)
+    finally:
+        h.close()
+
+
+def AMG_PCG_multi(A, E, amg_options: dict, pcg_options: dict | None = None, rng: MatlabRand | None = None):
+    """``[D,it,res,resk] = AMG_PCG_multi(A,E,amg_options,pcg_options)``: Class_AMG's setup, then every
+    column of ``E`` through AMG-preconditioned CG as if solved alone (``AMGHierarchy.pcg_multi``).  A
+    guess in ``pcg_options`` is N x k."""
+    h = AMGHierarchy(A, amg_options, rng)
+    try:
+        return h.pcg_multi(E, pcg_options)
     finally:
         h.close()
 

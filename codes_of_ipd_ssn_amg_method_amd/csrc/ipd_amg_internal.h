@@ -53,7 +53,8 @@ struct Level {
 
 struct CycleState;   // ipd_cycle.hip
 struct KrylovState;  // ipd_krylov.hip
-struct BlockState;   // ipd_block.hip
+struct BlockState;   // ipd_block.h
+struct BlockKrylovState;   // ipd_block_krylov.hip
 struct LevelDev;     // ipd_cycle_dev.h
 
 struct ipd_amg {
@@ -81,6 +82,9 @@ struct ipd_amg {
     // block solve of several right-hand sides (ipd_block.hip): its N x W work blocks out of `arena`,
     // made on the first ipd_amg_solve_multi call and made again for a wider W
     std::shared_ptr<BlockState> blk;
+    // AMG-PCG of several right-hand sides (ipd_block_krylov.hip): its N x W vectors, scalars and tickets
+    // out of `arena`, made on the first ipd_amg_pcg_multi call and made again for a wider W
+    std::shared_ptr<BlockKrylovState> bkry;
 };
 
 // ipd_setup.hip

@@ -31,9 +31,7 @@
 
 #include "ipd_cycle_dev.h"
 #include "ipd_cycle_phases.h"
-
-// scalar block (doubles)
-enum { SC_DNEW, SC_DOLD, SC_ALPHA, SC_BETA, SC_D0, SC_IT, SC_RES, SC_STOP, SC_N };
+#include "ipd_krylov.h"
 
 struct KrylovState {
     int N = 0;
@@ -48,29 +46,6 @@ struct KrylovState {
     double* part3 = nullptr;     // 2 x G3 partials of r'w, r'w_old
     unsigned* cnt = nullptr;     // tickets of K1 and K3
 };
-
-// Wave 0 of every workgroup calls this after thread 0 stored the workgroup's partials; true (in wave
-// 0 only) in the workgroup that arrives last, which then sees every partial and has reset the ticket.
-__device__ __forceinline__ bool kry_last_arrival(unsigned* cnt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // keep: the fence's own wait can be dropped
-    unsigned t = 0;
-    if (threadIdx.x == 0) t = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    t = __builtin_amdgcn_readfirstlane(t);
-    if (t != gridDim.x - 1) return false;
-    if (threadIdx.x == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    return true;
-}
-
-// sum of part[0], part[stride], ... (n terms) in a fixed order, result in every lane of wave 0
-__device__ __forceinline__ double kry_sum_parts(const double* part, int n, int stride) {
-    double s = 0.0;
-    for (int i = (int)threadIdx.x; i < n; i += 64) s += part[(size_t)i * stride];
-    return wave_sum(s);
-}
 
 struct KryDirArgs {
     LevelDev lv;
@@ -336,15 +311,6 @@ static void amg_pcg_dev(ipd_amg* h, const double* e, const double* guess, double
     if (it_out) *it_out = it;
     if (res_out) *res_out = sc[SC_RES];                                           // :88
     ctx->sync();
-}
-
-static void pcg_opts_of(const ipd_pcg_opts* o, double* tol, long long* maxit) {
-    *tol = 1e-11;   // PCG.m:24-27 defaults
-    *maxit = 10000;
-    if (!o) return;
-    IPD_REQUIRE(o->precd == -1, IPD_E_ARG, "AMG-PCG: pcg_options.precd must be unset (the hierarchy preconditions)");
-    if (o->retol >= 0) *tol = o->retol;
-    if (o->maxit >= 0) *maxit = o->maxit;
 }
 
 extern "C" int ipd_amg_pcg_dev(ipd_amg* h, const double* e_dev, const double* guess_dev,

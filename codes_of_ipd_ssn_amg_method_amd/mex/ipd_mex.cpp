@@ -209,6 +209,35 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)it);
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(res);
         if (nlhs > 3) { plhs[3] = col((size_t)it); std::memcpy(mxGetDoubles(plhs[3]), rk.data(), sizeof(double) * (size_t)it); }
+    } else if (fn == "AMG_PCG_multi") {          // [D,it,res,resk] = AMG_PCG_multi(A,B,amg_options,pcg_options)
+        // one setup, every column of B through AMG_PCG's loop; resk: max(it) x k, NaN past a column's own it
+        ipd_csc A = csc_of(a[0]); ipd_amg_opts ao = opts_of(nrhs > 3 ? a[2] : nullptr);
+        ipd_pcg_opts o; ipd_pcg_opts_init(&o); const mxArray* so = nrhs > 4 ? a[3] : nullptr;
+        if (so) { o.retol = field(so, "retol", -1); o.maxit = (int64_t)field(so, "maxit", -1); o.precd = (int32_t)field(so, "precd", -1); }
+        const int64_t maxit = o.maxit >= 0 ? o.maxit : 10000;
+        const size_t N = (size_t)A.nrows, k = mxGetN(a[1]);
+        // B must be N x k and a guess N x k: the library reads and writes lde*k doubles (lde = N here)
+        if (mxGetM(a[1]) != N || k < 1)
+            mexErrMsgIdAndTxt("ipdamg:arg", "AMG_PCG_multi: B must have size(A,1) rows and at least one column");
+        const mxArray* gv = (so && mxIsStruct(so)) ? mxGetField(so, 0, "guess") : nullptr;
+        if (gv && !mxIsEmpty(gv) && mxGetNumberOfElements(gv) != N * k)
+            mexErrMsgIdAndTxt("ipdamg:arg", "AMG_PCG_multi: pcg_options.guess must be size(B) (or empty)");
+        if (g_h) { ipd_amg_destroy(g_h); g_h = nullptr; }
+        chk(ipd_amg_setup(g_ctx, &A, &ao, g_rng, &g_h));   // the gateway's hierarchy, as Class_AMG leaves it
+        plhs[0] = mxCreateDoubleMatrix((mwSize)N, (mwSize)k, mxREAL);
+        std::vector<int64_t> it(k); std::vector<double> res(k), rk((size_t)maxit * k);
+        chk(ipd_amg_pcg_multi(g_h, mxGetDoubles(a[1]), (int64_t)N, (int64_t)k, opt_vec(so, "guess"), &o,
+                              mxGetDoubles(plhs[0]), it.data(), res.data(), rk.data()));
+        size_t rows = 0;
+        for (size_t j = 0; j < k; ++j) rows = std::max(rows, (size_t)it[j]);
+        if (nlhs > 1) { plhs[1] = col(k); for (size_t j = 0; j < k; ++j) mxGetDoubles(plhs[1])[j] = (double)it[j]; }
+        if (nlhs > 2) { plhs[2] = col(k); std::memcpy(mxGetDoubles(plhs[2]), res.data(), sizeof(double) * k); }
+        if (nlhs > 3) {
+            plhs[3] = mxCreateDoubleMatrix((mwSize)rows, (mwSize)k, mxREAL);
+            for (size_t j = 0; j < k; ++j)
+                for (size_t i = 0; i < rows; ++i)
+                    mxGetDoubles(plhs[3])[j * rows + i] = i < (size_t)it[j] ? rk[j * (size_t)maxit + i] : NAN;
+        }
     } else if (fn == "components") {             // 1-based outputs for MATLAB
         ipd_csc A = csc_of(a[0]); const size_t N = (size_t)A.nrows; int64_t nc = 0;
         std::vector<int64_t> b(N), sz(N), p(N), r(N + 1);

@@ -204,6 +204,23 @@ int ipd_amg_solve_multi(ipd_amg* h, const double* B, int64_t ldb, int64_t nrhs,
  * used.                                                                                          */
 int ipd_amg_pcg(ipd_amg* h, const double* e, const double* guess, const ipd_pcg_opts* o,
                 double* d, int64_t* it, double* res, double* resk /* maxit slots or NULL */);
+/* Several right-hand sides: column j of E (N x nrhs, column-major, leading dimension lde >= N) runs
+ * ipd_amg_pcg's loop on this hierarchy as if it were solved alone -- guess column j (guess may be NULL:
+ * zeros), its own it[j], res[j] and resk(1:it[j], j) (resk: maxit x nrhs column-major or NULL; later
+ * slots are left untouched).  A column that has stopped stays frozen (its D and residual are left
+ * alone, its cycle input is zero) while the others go on.  pcg_options, the stop test and the edge
+ * conventions are ipd_amg_pcg's (a zero column with a zero guess: it = 0, res = NaN).  Results do not
+ * depend on the other columns of the call and repeat bit for bit; they agree with ipd_amg_pcg to
+ * rounding (the block cycle sums over the CSR arrays in another order).  Columns run in blocks of up
+ * to 8 (the next power of two), chunk by chunk, through block forms of the launch-path cycle, as in
+ * ipd_amg_solve_multi: an attached mask operator or level-2 polynomial form is ignored.  D (ld = lde)
+ * may not alias E; rows N..lde-1 of D are the caller's and are carried through.  IPD_E_ARG for NULL
+ * h, E, D or it, nrhs < 1, lde < N, precd set, a cycle other than 'v' / 'w', and a hierarchy set up
+ * for a sharded run.                                                                             */
+int ipd_amg_pcg_multi(ipd_amg* h, const double* E, int64_t lde, int64_t nrhs,
+                      const double* guess /* N x nrhs, ld = lde, or NULL */, const ipd_pcg_opts* o,
+                      double* D /* ld = lde */, int64_t* it /* nrhs */, double* res /* nrhs or NULL */,
+                      double* resk /* maxit x nrhs or NULL */);
 /* e = MG_Vcycle(r,isnsp,k)   AMG/MG_Vcycle.m:2 ; k is 1-based               */
 int ipd_amg_vcycle(ipd_amg* h, const double* r, int isnsp, int k, double* e);
 /* e = MG_Wcycle(r,isnsp,k,e) AMG/MG_Wcycle.m:2 ; e_inout NULL-able input    */
@@ -298,6 +315,10 @@ int ipd_amg_solve_multi_dev(ipd_amg* h, const double* B_dev, int64_t ldb, int64_
 /* ipd_amg_pcg on device vectors (guess_dev may be NULL); resk stays a host array               */
 int ipd_amg_pcg_dev(ipd_amg* h, const double* e_dev, const double* guess_dev,
                     const ipd_pcg_opts* o, double* d_dev, int64_t* it, double* res, double* resk);
+/* ipd_amg_pcg_multi on device blocks E, guess (or NULL) and D; it, res and resk stay host arrays */
+int ipd_amg_pcg_multi_dev(ipd_amg* h, const double* E_dev, int64_t lde, int64_t nrhs,
+                          const double* guess_dev, const ipd_pcg_opts* o, double* D_dev, int64_t* it,
+                          double* res, double* resk);
 /* Hybrid_AMG with H0 already on the device (output of ipd_asat_dev)          */
 int ipd_hybrid_amg_dev(ipd_ctx*, const ipd_dmat* H0, const double* t_dev, const double* p_dev,
                        const double* q_dev, int64_t m, int64_t n, double bk1, double tk,
