@@ -5,7 +5,7 @@
 
 #include <cstdlib>
 
-#include "ipd_level_plan.h"
+#include "ipd_resident_plan.h"
 
 struct LevelRun {  // per-level run state kept next to Level
     LevelDev dev;
@@ -15,6 +15,27 @@ struct LevelRun {  // per-level run state kept next to Level
     XferArgs restrict_args;  // r_{k+1} = P' rr_k   (stored on level k)
     XferArgs prolong_args;   // e_k += P e_{k+1}
     PcgArgs pcg;             // coarsest only
+};
+
+// The resident solve kernels (ipd_resident.h, ipd_resident_big.h): the whole Class_AMG loop in one launch of
+// co-resident workgroups.  The plan (ipd_resident_plan.h) and what running it needs; ipd_resident_host.h is the
+// only code that looks inside -- the rest of the host asks whether a plan is active (`ok`) and for its grid.
+struct ResidentState {
+    bool ok = false;             // a plan is active
+    bool off = false;            // IPD_NO_RESIDENT=1 when the hierarchy was set up
+    ResidentPlan plan;
+    ResDesc desc{};              // k_resident's descriptor (kept under a mask-form plan that replaced it: its rho)
+    ResBigDesc big{};            // the mask-form kernel's
+    unsigned skip_publish = 0;   // test hook (IPD_RES_DEBUG_SKIP_PUBLISH): fires on ONE launch
+    unsigned char* block = nullptr;   // granule block, zeroed before every launch
+    size_t block_bytes = 0;
+    double* out = nullptr;
+    int timeouts = 0;            // launches whose bounded spins gave up (then: multi-launch path)
+    long long last_handoffs = 0;   // hand-offs and cycles of the last launch (ipd_amg_resident_kernel)
+    int last_cycles = 0;
+    int capacity = -1;   // workgroups of the chosen instantiation the device holds at once (-1: not asked yet)
+    int line_ke = 0, line_ke3 = 0;   // what the "[ipd] resident launch:" line shows as ke / ke3
+    bool mask_form() const { return plan.kind == RESIDENT_BIG || plan.kind == RESIDENT_DEEP; }
 };
 
 struct CycleState {
@@ -62,38 +83,13 @@ struct CycleState {
     size_t sub4_lds = 0;           // (packed beside d_sub when that one is rooted at level 3)
     SolveDesc* d_sub3 = nullptr;   // image rooted at level 3 for the resident kernel alone (k_sub == 0)
     size_t sub3_lds = 0;
-    SolveDesc* d_sub5 = nullptr;   // image rooted at level 5 for the mask-form kernel's deep mode with level 4 resident
-    size_t sub5_lds = 0;
+    ImageRole sub5 = IMG_NONE;     // the image whose levels 5..J serve a resident kernel's tail rooted at level 5 (POLY4)
     int k_sub = 0;
     size_t sub_lds = 0;
     // dynamic LDS an image's operator copy needs on top of its *_lds (SolveDesc::bm_src; 0: none)
     size_t sub_bm = 0, sub3_bm = 0, sub4_bm = 0;
     double* x2 = nullptr;
-    // level-resident solve kernel (ipd_resident.h): the whole Class_AMG loop in one launch of
-    // res_G co-resident workgroups that keep the matrices of levels 1-2 in registers
-    bool res_ok = false;
-    bool res_remote = false;   // levels >= 3 served by a tail workgroup (see ResDesc::remote)
-    int res_ke3 = 0;           // > 0: level 3 resident as well (entries per lane of its rows), tail rooted at 4
-    size_t res_block_bytes = 0;
-    ResDesc res_desc{};
-    int res_G = 0;
-    int res_ke = 0;          // entries per lane of a padded row (template argument)
-    size_t res_lds = 0;
-    double* res_out = nullptr;
-    unsigned char* res_block = nullptr;   // [gran0 | gran1 | tmo]: zeroed before every launch
-    int res_timeouts = 0;    // launches whose bounded spins gave up (then: multi-launch path)
-    long long res_last_handoffs = 0;   // hand-offs and cycles of the last launch (ipd_amg_resident_kernel)
-    int res_last_cycles = 0;
-    int res_capacity = -1;   // workgroups of the chosen instantiation the device holds at once (-1: not asked yet)
-    // level 1 of up to 4096 rows: the mask-form resident kernel (ipd_resident_big.h), set up by
-    // amg_attach_maskop once the bit mask of level 1 is there
-    bool resb = false;
-    bool res_off = false;    // IPD_NO_RESIDENT=1 when the hierarchy was set up
-    ResBigDesc resb_desc;
-    int resb_ke2 = 16;
-    bool res_poly2 = false;  // k_resident<16,16,0,true>: level 2 composed over a visit (ipd_amg_attach_level2_poly)
-    bool resb_deep = false;  // realistic hierarchy: level 3 in polynomial form, remote tail at level 4 (RPW = 2)
-    bool resb_poly4 = false; // ... level 4 in polynomial form as well, remote tail at level 5
+    ResidentState res;   // the resident solve kernels: plan and run state (ipd_resident_host.h)
     hipGraphExec_t gexec[2] = {nullptr, nullptr};  // captured Class_AMG loop bodies (x->x2, x2->x)
     const double* gb = nullptr;                    // right-hand side the graphs were captured for
     ~CycleState() {
@@ -371,446 +367,49 @@ static void record_rows_op(CycleState* st, const ipd_amg* h, int k, const BPolyD
     st->rows_ops[(size_t)k] = rows_op(b);
 }
 
-// ---- level-resident solve kernel: eligibility and launch ---------------------------------
-// Eligible: three levels -- a bigraph Gauss-Seidel level 1 and a Jacobi level 2 with padded
-// rows of at most 1024 entries, at most 2048 rows each, and a tail level of at most 64 rows --
-// i.e. the dense regimes (regime D), where each launch of the multi-launch path is
-// latency-bound.  IPD_NO_RESIDENT=1 switches it off, IPD_RESIDENT_G overrides the grid.
-static void plan_resident(ipd_amg* h, CycleState* st, const PlanSwitches& sw) {
-    st->res_ok = false;
-    if (sw.no_resident) {
-        st->res_off = true;   // (remembered: the mask-form kernel is set up later, by amg_attach_maskop)
-        return;
-    }
-    if (st->small_ok || h->J < 3 || h->opts.twogrid) return;
-    const Level& l1 = h->L[1];
-    const Level& l2 = h->L[2];
-    const Level& l3 = h->L[3];
-    // Rows live in registers: the padded stride is only a layout here, so a level whose rows are too
-    // uneven for the launches' padded copy (hubs) gets a private copy with its longest row as stride
-    // (built below, once the hierarchy is known to be taken).  d1 / d2 carry the stride either way.
-    LevelDev d1 = st->run[1].dev;
-    LevelDev d2 = st->run[2].dev;
-    const bool nopriv = false;
-    bool priv1 = false, priv2 = false;
-    if (d1.S <= 0 && st->run[1].maxoff > 0 && !nopriv) {
-        d1.S = (st->run[1].maxoff + 3) / 4 * 4;
-        priv1 = true;
-    }
-    if (d2.S <= 0 && st->run[2].maxoff > 0 && !nopriv) {
-        d2.S = (st->run[2].maxoff + 3) / 4 * 4;
-        priv2 = true;
-    }
-    const int N1 = l1.A.nr, N2 = l2.A.nr, Nt = l3.A.nr, nf = l1.nf, nc = N1 - nf;
-    if (switch_on("IPD_DEBUG_LEVELS"))
-        std::fprintf(stderr, "[ipd] resident plan: J=%d nf=%d nc=%d S1=%d S2=%d S3=%d N4=%d Nt=%d k_sub=%d sub_lds=%zu\n", h->J,
-                     nf, nc, d1.S, d2.S, st->run[3].dev.S, h->J >= 4 ? h->L[4].A.nr : 0, Nt, st->k_sub, st->sub_lds);
-    if (nf <= 0 || nc <= 0 || d1.S <= 0 || d2.S <= 0) return;
-    if (N1 > 4 * BT || N2 > 4 * BT || nf > 2 * BT || nc > 2 * BT || Nt < 1) return;
-    // everything below level 2: a tail of <= 64 rows solved redundantly by every workgroup (three
-    // levels), or -- deeper hierarchies -- the single-workgroup sub-cycle rooted at level 3 run by ONE
-    // extra workgroup out of its LDS image (the image the multi-launch path launches k_subcycle with)
-    const bool local_tail = h->J == 3 && Nt <= RES_TAIL_MAX;
-    bool remote = false, three = false;
-    int ke3 = 0;
-    const SolveDesc* tail_img = nullptr;   // the remote tail's LDS image and its dynamic LDS size
-    size_t tail_lds = 0, tail_bm = 0;   // tail_bm: room for the image's operator copy (SolveDesc::bm_src)
-    if (!local_tail) {
-        const bool cyc = h->opts.cycle == 'w' || h->opts.cycle == 'v';
-        remote = !sw.no_resident_remote && h->J >= 4 && Nt <= BT && cyc &&
-                 ((st->k_sub == 3 && st->d_sub) || (st->k_sub == 0 && st->d_sub3));
-        // Level 3 in the registers of the resident workgroups as well, the tail rooted at level 4: for
-        // a level 3 too big for the tail's LDS (a few hundred rows of 15-100 entries), and preferred to
-        // the tail rooted at level 3 whenever an image rooted at level 4 exists (the tail's legs are the
-        // serial part of a cycle: ~22 us each from level 4, ~100 us from level 3).
-        tail_img = st->k_sub == 0 ? st->d_sub3 : st->d_sub;
-        tail_lds = st->k_sub == 0 ? st->sub3_lds : st->sub_lds;
-        tail_bm = st->k_sub == 0 ? st->sub3_bm : st->sub_bm;
-        const bool img4 = (st->k_sub == 4 && st->d_sub) || (st->k_sub == 3 && st->d_sub4);
-        // level 3 fits the resident workgroups' registers: its rows (usually too uneven for the launches'
-        // padded copy -- hubs -- but in registers the stride is only a layout: a private copy with the
-        // longest row as stride, below), the row slots and a root level 4 of at most BT rows
-        const int S3 = st->run[3].dev.S > 0 ? st->run[3].dev.S : (st->run[3].maxoff + 3) / 4 * 4;
-        const bool three_fits = h->J >= 4 && S3 > 0 && S3 <= 512 && Nt <= BT && h->L[4].A.nr <= BT &&
-                                N2 <= RES_NMAX / 2 && std::max(d1.S, d2.S) <= 512 &&
-                                Nt + std::max(cdiv(std::max(nf, nc), RES_WAVES), cdiv(N2, RES_WAVES)) <= 2 * BT;
-        if (!sw.no_resident_remote && !sw.no_resident_three && h->J >= 5 && img4 && cyc) {
-            if (three_fits) {
-                three = remote = true;
-                ke3 = S3 <= 256 ? 4 : 8;
-                if (st->k_sub == 3) {
-                    tail_img = st->d_sub4;
-                    tail_lds = st->sub4_lds;
-                    tail_bm = st->sub4_bm;
-                }
-            }
-        }
-        // Four levels with a level 3 too big for any LDS image and a coarsest level of at most 64 rows
-        // (dense masks early in a run, the bench's tree / hub masks): level 3 resident, level 4 solved
-        // by every workgroup as the local tail -- no tail workgroup.
-        // (a V cycle visits the tail once: there the local tail stays ahead of a tail workgroup rooted at a
-        // level 3 in block-wide polynomial form -- tree mask 0.096 against 0.102 ms; a W cycle is the other
-        // way round, 0.198 against 0.191)
-        if (remote && !three && h->J == 4 && h->opts.cycle == 'v' && !sw.no_resident_three &&
-            h->L[4].A.nr <= RES_TAIL_MAX && three_fits)
-            remote = false;
-        if (!remote && !sw.no_resident_remote && !sw.no_resident_three && h->J == 4 && cyc &&
-            h->L[4].A.nr <= RES_TAIL_MAX && three_fits) {
-            three = true;
-            ke3 = S3 <= 256 ? 4 : 8;
-        }
-        if (!remote && !three) return;
-    }
-    const int smax = std::max(d1.S, d2.S);
-    int ke = 4;
-    while (64 * ke < smax) ke <<= 1;
-    if (ke > 16) return;
-    if (three && ke > 8) return;   // (the third row slice does not fit beside two 16-entry ones)
-    int G = std::max(cdiv(std::max(nf, nc), RES_WAVES), cdiv(N2, RES_WAVES));
-    if (const char* e = switch_value("IPD_RESIDENT_G")) G = std::max(G, std::atoi(e));
-    // every workgroup owns at least one row of every block (the hand-off protocol needs it)
-    if (G + (remote ? 1 : 0) > st->num_cu || G > std::min(std::min(nf, nc), N2)) return;
-    const int Nin = three ? h->L[4].A.nr : Nt;   // rows of the remote tail's root level / of the local tail
-    if (remote && Nin > RES_WAVES * G) return;   // one row of the restriction to it per wave
-    if (three && Nt + G > 2 * BT) return;        // level-3 hand-offs: N3 + G granules, two per thread
-    // level 3 in polynomial form (ResDesc::p3rows): remote tail, one restriction row per workgroup at most,
-    // at most four rows of level 3 per workgroup
-    const bool poly3 = three && remote && h->opts.smoth >= 1 && h->L[4].A.nr <= G && h->L[4].A.nr <= 128 && Nt <= 4 * G && Nt <= BT &&
-                       !sw.no_poly;
-    if (poly3) ke3 = 1;
-    // level 4 resident as well (ResDesc::p4rows), the tail workgroup rooted at level 5
-    const int N5r = h->J >= 6 ? h->L[5].A.nr : 0;
-    const bool poly4 = poly3 && st->d_sub5 && h->L[1].A.nr <= RES_NMAX && N5r >= 1 && N5r <= 64 && N5r <= G &&
-                       h->L[4].A.nr <= RES_P4_SEG && h->L[4].A.nr + G <= BT;
-    if (poly4) {
-        tail_img = st->d_sub5;
-        tail_lds = st->sub5_lds;
-        tail_bm = 0;   // (entered at level 5: the copied level is one the resident workgroups hold)
-    }
-    if (!remote || tail_lds + tail_bm > (size_t)156 * 1024) tail_bm = 0;
-    const size_t lds = remote ? std::max<size_t>(RES_LDS_BYTES, tail_lds + tail_bm) : RES_LDS_BYTES;
-    if (lds > 156 * 1024) return;
-    Arena& ar = *h->arena;
-    ResDesc D{};
-    auto lev = [](const LevelDev& d) {
-        ResLevelDesc L;
-        L.N = d.N;
-        L.nf = d.nf;
-        L.S = d.S;
-        L.pci = d.pci;
-        L.pva = d.pva;
-        L.diag = d.diag;
-        L.dinv = d.dinv;
-        L.Axi = d.Axi;
-        L.xx = d.xx;
-        return L;
-    };
-    auto csr = [](const Csr& m) {
-        ResCsr c;
-        c.rp = m.rp;
-        c.ci = m.ci;
-        c.va = m.va;
-        return c;
-    };
-    auto private_pad = [&](const Csr& A, LevelDev& d) {   // k_pad_build with stride d.S
-        unsigned short* pci = ar.alloc<unsigned short>((size_t)A.nr * d.S);
-        double* pva = ar.alloc<double>((size_t)A.nr * d.S);
-        double* dg = ar.alloc<double>((size_t)A.nr);
-        hipLaunchKernelGGL(k_pad_build, dim3(std::max(1, std::min(cdiv(A.nr, 4), 4096))), dim3(256), 0,
-                           h->ctx->stream, A.nr, d.S, A.rp, A.ci, A.va, pci, pva, dg);
-        IPD_KERNEL_CHECK();
-        d.pci = pci;
-        d.pva = pva;
-        d.diag = dg;
-    };
-    if (priv1) private_pad(l1.A, d1);
-    if (priv2) private_pad(l2.A, d2);
-    D.L1 = lev(d1);
-    D.L2 = lev(d2);
-    D.Pt2 = csr(l2.Pt);
-    D.P2 = csr(l2.P);
-    D.Pt3 = csr(l3.Pt);
-    D.P3 = csr(l3.P);
-    D.A3 = csr(l3.A);
-    D.Nt = Nin;
-    D.three = three ? 1 : 0;
-    D.tail_root = poly4 ? 5 : three ? 4 : 3;
-    D.A4 = csr(three ? h->L[4].A : l3.A);
-    if (three) {
-        LevelDev d3 = st->run[3].dev;
-        if (poly3) {
-            const BPolyDev pb = pack_bpoly(h->ctx, h, st, 3, h->opts.isnsp, 0, true);
-            D.p3rows = pb.M;
-            D.p3w = pb.W;
-            record_rows_op(st, h, 3, pb);
-            st->level_forms.resize((size_t)h->J + 1, 0);
-            st->level_forms[3] |= 64;
-            if (poly4) {
-                const BPolyDev pb4 = pack_bpoly(h->ctx, h, st, 4, h->opts.isnsp, 0, true, RES_P4_SEG, RES_P4_LD);
-                D.p4rows = pb4.M;
-                D.p4w = pb4.W;
-                record_rows_op(st, h, 4, pb4);
-                D.N5 = N5r;
-                st->level_forms[4] |= 64;
-            }
-        } else if (d3.S <= 0) {   // private padded copy of level 3, stride = its longest row
-            d3.S = (st->run[3].maxoff + 3) / 4 * 4;
-            private_pad(l3.A, d3);
-        }
-        D.L3 = lev(d3);
-        D.Pt4 = csr(h->L[4].Pt);
-        D.P4 = csr(h->L[4].P);
-    } else {
-        D.L3 = lev(d2);   // unused
-        D.Pt4 = csr(l3.Pt);
-        D.P4 = csr(l3.P);
-    }
-    D.nu = h->opts.smoth;
-    D.isnsp = h->opts.isnsp;
-    D.wcycle = h->opts.cycle == 'w';
-    D.anycycle = (h->opts.cycle == 'w' || h->opts.cycle == 'v');
-    D.maxit = h->opts.maxit;
-    D.retol = h->opts.retol;
-    D.pcg_maxit = h->opts.pcg_maxit;
-    // bigraph transfers P = [W; I]: the kernel adds the identity entries instead of walking them
-    // (a bigraph level 1 built by amg_transfer has them by construction -- k_bigph_fill writes the rows of I --
-    // which saves the check and its round trip on every hierarchy of a run)
-    D.wident = 0;
-    if (N2 == nc && h->opts.bigph) {
-        D.wident = 1;
-    } else if (N2 == nc) {
-        int* bad = zeroed<int>(h->ctx, 1);
-        hipLaunchKernelGGL(k_res_check_ident, dim3(cdiv(N2, 256)), dim3(256), 0, h->ctx->stream, nf, N2,
-                           csr(l2.P), csr(l2.Pt), bad);
-        IPD_KERNEL_CHECK();
-        D.wident = h->ctx->fetch1(bad) == 0 ? 1 : 0;
-    }
-    D.localfirst = 1;
-    D.pollsleep = 1;   // (0..2 sleeps between polls made no difference, from 3 on it was worse)
-    // s_sleep(1) count between a publish and the first poll (a failing poll delays the publishes it waits for).
-    // Round 2: 0 -> 0.0869, 8 -> 0.0796, 12..14 -> 0.0770, 16 -> 0.0784 ms per V cycle.  With the shorter
-    // hand-off of round 5 the best value moved down: metric workload 8 -> 0.0446, 13 -> 0.0456 ms
-    // (6 / 7 / 9: 0.0450 / 0.0460 / 0.0447), W cycle 0.0852 against 0.0876, the sweep form of level 2 even.
-    D.presleep = 8;
-    if (const char* e = switch_value("IPD_RES_PRESLEEP")) D.presleep = std::max(0, std::atoi(e));
-    const size_t gbytes = (size_t)RES_GRAN_MAX * 16;
-    st->res_block_bytes = 2 * gbytes + 16 + (remote ? 4 * gbytes + 16 : 0);
-    st->res_block = reinterpret_cast<unsigned char*>(ar.alloc_bytes(st->res_block_bytes));
-    D.gran0 = st->res_block;
-    D.gran1 = st->res_block + gbytes;
-    D.tmo = reinterpret_cast<unsigned*>(st->res_block + 2 * gbytes);
-    D.remote = remote ? 1 : 0;
-    D.sub = remote ? tail_img : nullptr;
-    D.tail_bm = (remote && tail_bm > 0) ? 1 : 0;
-    D.tin = remote ? st->res_block + 2 * gbytes + 16 : st->res_block;        // never touched without
-    D.tout = remote ? st->res_block + 4 * gbytes + 16 : st->res_block;       // a remote tail
-    D.tctl = remote ? reinterpret_cast<unsigned*>(st->res_block + 6 * gbytes + 16) : D.tmo;
-    D.dbg = nullptr;
-    D.dbg_skip_seq = 0;
-    if (const char* e = switch_value("IPD_RES_DEBUG_SKIP_PUBLISH")) D.dbg_skip_seq = (unsigned)std::max(0, std::atoi(e));
-    st->res_desc = D;
-    st->res_remote = remote;
-    st->resb_poly4 = poly4;
-    st->res_ke3 = ke3;
-    st->res_G = G;
-    st->res_ke = ke;
-    st->res_lds = lds;
-    st->res_out = ar.alloc<double>(4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2));
-    st->res_ok = true;
-}
-
-// Resident kernels need all their workgroups on the chip at once (one per CU): as many of them may
-// run side by side as their grids fit into the device's CUs -- two of 128 workgroups on an MI355X
-// (AMG4POT's two concurrent solves, bench.py --batch 2) -- and a further one waits for a free slot
-// (a solve lasts a millisecond or two; running it as launches beside two resident kernels slows all
-// three: --batch 4 fell from 2 x 20 M to 17.6 M DoF*cycles/s) and takes the multi-launch path only
-// if none frees up within 50 ms.  (The spins are bounded, so an over-commitment could only cost the
-// launch, never hang.)
-struct ResidentSlots {
-    std::mutex mu;
-    std::condition_variable cv;
-    int used[64] = {0};
-    bool acquire(int device, int workgroups, int cus, int wait_ms) {
-        std::unique_lock<std::mutex> lock(mu);
-        if (workgroups > cus) return false;
-        const bool got = cv.wait_for(lock, std::chrono::milliseconds(wait_ms),
-                                     [&] { return used[device & 63] + workgroups <= cus; });
-        if (!got) return false;
-        used[device & 63] += workgroups;
-        return true;
-    }
-    void release(int device, int workgroups) {
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            used[device & 63] -= workgroups;
-        }
-        cv.notify_all();
-    }
-};
-static ResidentSlots& resident_slots() {
-    static ResidentSlots s;
+// The planners' switches, read at the call in which they take effect (amg_prepare_levels, amg_attach_maskop): the
+// one place that reads them
+static PlanSwitches read_plan_switches() {
+    PlanSwitches s;
+    s.no_poly = switch_on("IPD_NO_POLY");
+    s.no_blk = switch_on("IPD_NO_BLK");
+    s.no_bpoly = switch_on("IPD_NO_BPOLY");
+    s.no_blkdense = switch_on("IPD_NO_BLKDENSE");
+    s.no_small = switch_on("IPD_NO_SMALL");
+    s.no_subcycle = switch_on("IPD_NO_SUBCYCLE");
+    s.no_resident = switch_on("IPD_NO_RESIDENT");
+    s.no_resident_remote = switch_on("IPD_NO_RESIDENT_REMOTE");
+    s.no_resident_three = switch_on("IPD_NO_RESIDENT_THREE");
+    s.no_resident_deep = switch_on("IPD_NO_RESIDENT_DEEP");
+    s.no_resident_big = switch_on("IPD_NO_RESIDENT_BIG");
+    s.no_res_poly4 = switch_on("IPD_NO_RES_POLY4");
+    s.resident_big = switch_on("IPD_RESIDENT_BIG");
+    s.maskop = switch_on("IPD_MASKOP");
+    if (const char* e = switch_value("IPD_RESIDENT_G")) s.resident_g = std::atoi(e);
+    if (const char* e = switch_value("IPD_RESIDENT_RANKS")) s.resident_ranks = std::atoi(e);
+    if (const char* e = switch_value("IPD_RES_PRESLEEP")) s.res_presleep = std::max(0, std::atoi(e));
+    if (const char* e = switch_value("IPD_RES_DEBUG_SKIP_PUBLISH")) s.res_skip_publish = (unsigned)std::max(0, std::atoi(e));
     return s;
 }
-struct ResidentLease {
-    int device, wgs;
-    bool ok;
-    ResidentLease(int d, int w, int cus, int wait_ms)
-        : device(d), wgs(w), ok(resident_slots().acquire(d, w, cus, wait_ms)) {}
-    ~ResidentLease() {
-        if (ok) resident_slots().release(device, wgs);
-    }
-};
 
-// Runs the whole solve (fixed_cycles == 0) or exactly fixed_cycles loop bodies on the
-// iterate in x (in: guess, out: result).  Returns false when the kernel could not be used
-// (another resident kernel is running, or a spin gave up): x is then unspecified and the
-// caller takes the multi-launch path.  `ms`: device time of the launch (HIP events), optional.
-static bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double* x, int fixed_cycles,
-                         std::vector<double>* out_host, float* ms, long long* dbg_dev = nullptr) {
-    ipd_ctx* ctx = h->ctx;
-    const int grid = st->res_G + (st->res_remote ? 1 : 0);
-    if (ctx->res_penalty > 0) {   // an earlier launch of this context gave up: stay on the launches for a while
-        --ctx->res_penalty;
-        return false;
+// the levels as the planners look at them
+static std::vector<LevelShape> level_shapes(const ipd_amg* h, const CycleState* st) {
+    std::vector<LevelShape> shapes((size_t)h->J + 1);
+    for (int k = 1; k <= h->J; ++k) {
+        const Level& lv = h->L[k];
+        LevelShape& s = shapes[(size_t)k];
+        s.nr = lv.A.nr;
+        s.nnz = lv.A.nnz;
+        s.nf = lv.nf;
+        s.maxoff = st->run[(size_t)k].maxoff;
+        s.p_nnz = k >= 2 ? lv.P.nnz : 0;
     }
-    // A remote-tail launch is 129 workgroups at M = 2048: two of them do not fit side by side, and a
-    // realistic solve is a few milliseconds of mostly serial sub-cycle work -- waiting for the other
-    // solve (AMG4POT's two right-hand sides) would serialise them, so the loser runs as launches
-    // beside it at once.  The dense three-level launches (128 workgroups, two fit) keep waiting.
-    ResidentLease lease(ctx->device, grid, st->num_cu, st->res_remote ? 0 : 50);
-    if (!lease.ok) return false;
-    ResDesc D = st->res_desc;
-    D.dbg = dbg_dev;
-    if (switch_on("IPD_DEBUG_LEVELS"))
-        std::fprintf(stderr, "[ipd] resident launch: grid %d ke %d ke3 %d xm %d wident %d three %d remote %d\n", grid,
-                     st->res_ke, st->res_ke3, D.xm, D.wident, D.three, D.remote);
-    st->res_desc.dbg_skip_seq = 0;   // the test hook fires on ONE launch
-    IPD_HIP(hipMemsetAsync(st->res_block, 0, st->res_block_bytes, ctx->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ms) {
-        for (hipEvent_t& ev : ctx->tev)
-            if (!ev) IPD_HIP(hipEventCreate(&ev));
-        e0 = ctx->tev[0];
-        e1 = ctx->tev[1];
-        IPD_HIP(hipEventRecord(e0, ctx->stream));
-    }
-    // The workgroups spin on one another, so ALL of them must be on the chip at once: the grid is
-    // checked against what the device can hold of this instantiation (registers, LDS: one workgroup
-    // per CU) before the first launch; an oversized grid takes the multi-launch path for good.
-    bool fits = true;
-    if (st->resb) {
-        ResBigDesc B = st->resb_desc;
-        B.dbg_skip_seq = D.dbg_skip_seq;
-#define IPD_RESB_LAUNCH(KE2, RPW, DEEP)                                                             \
-    do {                                                                                            \
-        IPD_OPTIN_LDS(ctx, (k_resident_big<KE2, RPW, DEEP>), 156 * 1024);                           \
-        if (st->res_capacity < 0) {                                                                 \
-            int nb_ = 0;                                                                            \
-            IPD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, (k_resident_big<KE2, RPW, DEEP>), BT, st->res_lds)); \
-            st->res_capacity = nb_ * st->num_cu;                                                    \
-        }                                                                                           \
-        if (grid > st->res_capacity) {                                                              \
-            fits = false;                                                                           \
-            break;                                                                                  \
-        }                                                                                           \
-        hipLaunchKernelGGL((k_resident_big<KE2, RPW, DEEP>), dim3(grid), dim3(BT), st->res_lds, ctx->stream, B, \
-                           b_dev, x, st->res_out, fixed_cycles);                                    \
-    } while (0)
-#ifdef IPD_DEV_ONLY_RES16
-        (void)B;
-        fits = false;
-#else
-        if (st->resb_deep) {
-            if (st->resb_ke2 == 4)
-                IPD_RESB_LAUNCH(4, 2, true);
-            else
-                IPD_RESB_LAUNCH(8, 2, true);
-        } else if (st->resb_ke2 == 16)
-            IPD_RESB_LAUNCH(16, 1, false);
-        else
-            IPD_RESB_LAUNCH(32, 1, false);
-#endif
-#undef IPD_RESB_LAUNCH
-    } else
-#define IPD_RES_LAUNCH4(KE, KE3, P2)                                                                   \
-    do {                                                                                            \
-        IPD_OPTIN_LDS(ctx, (k_resident<KE, KE, KE3, P2>), 156 * 1024);                                  \
-        if (st->res_capacity < 0) {                                                                 \
-            int nb_ = 0;                                                                            \
-            IPD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, (k_resident<KE, KE, KE3, P2>), BT, st->res_lds)); \
-            st->res_capacity = nb_ * st->num_cu;                                                    \
-        }                                                                                           \
-        if (grid > st->res_capacity) {                                                              \
-            fits = false;                                                                           \
-            break;                                                                                  \
-        }                                                                                           \
-        hipLaunchKernelGGL((k_resident<KE, KE, KE3, P2>), dim3(grid), dim3(BT), st->res_lds, ctx->stream, \
-                           D, b_dev, x, st->res_out, fixed_cycles);                                 \
-    } while (0)
-#define IPD_RES_LAUNCH(KE, KE3) IPD_RES_LAUNCH4(KE, KE3, false)
-#if defined(IPD_DEV_ONLY_BIG)   // (development: compile the mask-form kernels alone, see tools/kernel_regs.py)
-    (void)D;
-    fits = false;
-#elif defined(IPD_DEV_ONLY_RES16)   // (... or the metric's instantiations alone)
-    if (st->res_poly2)
-        IPD_RES_LAUNCH4(16, 0, true);
-    else
-        IPD_RES_LAUNCH(16, 0);
-#else
-    if (st->res_poly2) {
-        IPD_RES_LAUNCH4(16, 0, true);
-    } else if (st->res_ke3 == 0) {
-        if (st->res_ke == 4)
-            IPD_RES_LAUNCH(4, 0);
-        else if (st->res_ke == 8)
-            IPD_RES_LAUNCH(8, 0);
-        else
-            IPD_RES_LAUNCH(16, 0);
-    } else if (st->res_ke3 == 1) {
-        if (st->res_ke == 4)
-            IPD_RES_LAUNCH(4, 1);
-        else
-            IPD_RES_LAUNCH(8, 1);
-    } else if (st->res_ke == 4) {
-        if (st->res_ke3 == 4)
-            IPD_RES_LAUNCH(4, 4);
-        else
-            IPD_RES_LAUNCH(4, 8);
-    } else {
-        if (st->res_ke3 == 4)
-            IPD_RES_LAUNCH(8, 4);
-        else
-            IPD_RES_LAUNCH(8, 8);
-    }
-#endif
-#undef IPD_RES_LAUNCH
-#undef IPD_RES_LAUNCH4
-    if (!fits) {
-        st->res_ok = false;
-        return false;
-    }
-    IPD_KERNEL_CHECK();
-    if (ms) IPD_HIP(hipEventRecord(e1, ctx->stream));
-    const size_t nout = 4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2);
-    std::vector<double> out(nout);
-    ctx->fetch(st->res_out, out.data(), nout);   // waits for the kernel (through the host mailbox: no stream synchronisation)
-    if (ms) {
-        IPD_HIP(hipEventSynchronize(e1));
-        IPD_HIP(hipEventElapsedTime(ms, e0, e1));
-    }
-    if (out[3] != 0.0) {   // a bounded spin gave up somewhere (any workgroup: the kernel reports the
-        // time-out word, not only workgroup 0's own view): not every workgroup was resident
-        ++st->res_timeouts;
-        ++ctx->res_giveups;
-        ctx->res_penalty = 32 << std::min(ctx->res_giveups - 1, 6);
-        if (st->res_timeouts >= 2) st->res_ok = false;
-        return false;
-    }
-    st->res_last_handoffs = (long long)out[nout - 1];
-    st->res_last_cycles = fixed_cycles > 0 ? fixed_cycles : (int)out[0];
-    if (out_host) *out_host = std::move(out);
-    return true;
+    return shapes;
 }
+
+// the resident kernels: their table, the execution of a plan, the launch, the attach functions.  (Included
+// here, ahead of the first launch of any other kernel template: the object lists its kernels in this order.)
+#include "ipd_resident_host.h"
 
 // Per-level vectors and constants (k_level_prepare), the padded copies and the launch geometry of every
 // level: st->run[k].dev
@@ -1388,23 +987,6 @@ static void pack_image(ipd_ctx* ctx, ipd_amg* h, CycleState* st, const LevelPlan
     }
 }
 
-static PlanSwitches read_plan_switches() {
-    PlanSwitches s;
-    s.no_poly = switch_on("IPD_NO_POLY");
-    s.no_blk = switch_on("IPD_NO_BLK");
-    s.no_bpoly = switch_on("IPD_NO_BPOLY");
-    s.no_blkdense = switch_on("IPD_NO_BLKDENSE");
-    s.no_small = switch_on("IPD_NO_SMALL");
-    s.no_subcycle = switch_on("IPD_NO_SUBCYCLE");
-    s.no_resident = switch_on("IPD_NO_RESIDENT");
-    s.no_resident_remote = switch_on("IPD_NO_RESIDENT_REMOTE");
-    s.no_resident_three = switch_on("IPD_NO_RESIDENT_THREE");
-    s.no_resident_deep = switch_on("IPD_NO_RESIDENT_DEEP");
-    s.no_resident_big = switch_on("IPD_NO_RESIDENT_BIG");
-    s.no_res_poly4 = switch_on("IPD_NO_RES_POLY4");
-    return s;
-}
-
 static const char* const IMAGE_ROLE_NAMES[] = {"solve", "sub", "sub3", "sub4", "none"};
 
 void amg_prepare_levels(ipd_amg* h) {
@@ -1413,16 +995,7 @@ void amg_prepare_levels(ipd_amg* h) {
     prepare_level_runs(h, st.get());
     prepare_transfers(h, st.get());
     // single-workgroup kernels: which levels, in which form, in which LDS images (ipd_level_plan.h)
-    std::vector<LevelShape> shapes((size_t)h->J + 1);
-    for (int k = 1; k <= h->J; ++k) {
-        const Level& lv = h->L[k];
-        LevelShape& s = shapes[(size_t)k];
-        s.nr = lv.A.nr;
-        s.nnz = lv.A.nnz;
-        s.nf = lv.nf;
-        s.maxoff = st->run[(size_t)k].maxoff;
-        s.p_nnz = k >= 2 ? lv.P.nnz : 0;
-    }
+    const std::vector<LevelShape> shapes = level_shapes(h, st.get());
     PlanOptions po;
     po.cycle = h->opts.cycle;
     po.smoth = h->opts.smoth;
@@ -1446,17 +1019,12 @@ void amg_prepare_levels(ipd_amg* h) {
         st->solve_out = h->arena->alloc<double>(4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2));
         st->small_ok = true;
     }
-    if (plan.sub5 == IMG_SUB) {
-        st->d_sub5 = st->d_sub;
-        st->sub5_lds = st->sub_lds;
-    } else if (plan.sub5 == IMG_SUB4) {
-        st->d_sub5 = st->d_sub4;
-        st->sub5_lds = st->sub4_lds;
-    }
-    plan_resident(h, st.get(), sw);
+    st->sub5 = plan.sub5;
+    prepare_resident(h, st.get(), shapes, sw);
     if (debug) {
-        std::fprintf(stderr, "[ipd] J=%d small=%d k_sub=%d resident=%d(G=%d,KE=%d) levels:", h->J,
-                     (int)st->small_ok, st->k_sub, (int)st->res_ok, st->res_G, st->res_ke);
+        std::fprintf(stderr, "[ipd] J=%d small=%d k_sub=%d ", h->J, (int)st->small_ok, st->k_sub);
+        print_resident_summary(stderr, st.get());
+        std::fprintf(stderr, " levels:");
         for (int k = 1; k <= h->J; ++k) std::fprintf(stderr, " %d/%d", h->L[k].A.nr, h->L[k].A.nnz);
         std::fprintf(stderr, "\n");
     }
@@ -1653,408 +1221,6 @@ __global__ void k_maskop_scales(int nf, int nc, const double* __restrict__ p,
         else
             beta[t - nf] = p[t - nf] * p[t - nf];
     }
-}
-
-// Derives the bit-mask form of level 1 from its CSR arrays; keeps the CSR kernels (returns
-// false) unless A_1 is exactly Hybrid_AMG's rescaled operator for these p, q, tk.
-//
-// When it pays (`policy` true: the solvers' own call): the mask sweep moves 13x fewer bytes but is
-// the slower launch while the level is latency-bound -- regime D at m = n = 1024 (2.1 M entries):
-// 5.7 us against 5.2 us for the padded CSR sweep -- and the faster one once the CSR sweep is
-// bandwidth-bound -- m = n = 2048 (8.4 M entries): 8.3 us against 13.4 us.  The solvers therefore
-// attach it from 4 M entries on; IPD_MASKOP=1 lowers that to 16 entries per row, IPD_NO_MASKOP=1
-// switches it off.  An explicit ipd_amg_attach_mask_operator call is not subject to the policy.
-bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int m, int n, double tk,
-                       bool policy, bool transfers_only) {
-    ipd_ctx* ctx = h->ctx;
-    CycleState* st = state_of(h);
-    if (!st) return false;
-    const Level& lv = h->L[1];
-    // the level-resident kernel takes its level 1 <-> 2 transfers from the mask whatever the size
-    const bool for_resident = st->res_ok && !st->res_desc.three && st->res_desc.wident && h->J == 3 &&
-                              true;
-    bool sweeps_too = !transfers_only;
-    const bool big_forced = switch_on("IPD_RESIDENT_BIG");
-    // Realistic hierarchy with a level 1 beyond k_resident's 2048 rows (the Newton systems of the m = n = 2048
-    // runs): candidate for the mask-form kernel's DEEP mode (ipd_resident_big.h) -- it needs the bit mask
-    // whatever the population of the rows
-    const SolveDesc* deep_img = nullptr;
-    size_t deep_img_lds = 0;
-    bool deep_cand = false;
-    {
-        const bool cyc = h->opts.cycle == 'w' || h->opts.cycle == 'v';
-        if ((st->k_sub == 4 && st->d_sub) || (st->k_sub == 5 && st->d_sub5)) {   // (rooted at 5: POLY4 only, below)
-            deep_img = st->d_sub;
-            deep_img_lds = st->sub_lds;
-        } else if (st->k_sub == 3 && st->d_sub4) {
-            deep_img = st->d_sub4;
-            deep_img_lds = st->sub4_lds;
-        }
-        deep_cand = !switch_on("IPD_NO_RESIDENT") && !switch_on("IPD_NO_RESIDENT_BIG") && !switch_on("IPD_NO_RESIDENT_DEEP") && !st->res_off &&
-                    !st->res_ok && !st->resb && !st->small_ok && !h->opts.twogrid && cyc && h->opts.smoth >= 1 &&
-                    h->J >= 5 && (n + m > RES_NMAX || big_forced) && n <= RB_HALF && m <= RB_HALF && lv.nf == n &&
-                    lv.N == m + n && h->L[2].A.nr == m && h->L[3].A.nr <= RB_N3MAX && h->L[4].A.nr <= RB_N4MAX &&
-                    deep_img != nullptr && std::max(RB_LDS_BYTES, deep_img_lds) <= (size_t)156 * 1024;
-    }
-    if (transfers_only && !for_resident && !big_forced && !deep_cand) return false;
-    if (policy) {
-        if (!switch_on("IPD_MASKOP") && (double)lv.A.nnz < 4.0e6) {
-            if (!for_resident && !deep_cand) return false;
-            sweeps_too = false;   // below the size where the mask SWEEPS of the launch path pay
-        }
-    }
-    if (h->J < 2 || lv.nf != n || lv.N != m + n || tk == 0.0) return false;
-    // a row of the mask costs nw word walks whatever its population: with fewer than ~16 entries
-    // per row the padded CSR sweep always beats it
-    if ((double)lv.A.nnz < 16.0 * lv.N) {
-        if (!deep_cand) return false;
-        sweeps_too = false;
-    }
-    if (std::max(m, n) > 4096) return false;   // a row's mask words must fit one wave (64 words)
-    Arena& ar = *h->arena;
-    MaskOp mo;
-    mo.nf = n;
-    mo.nc = m;
-    mo.nwf = cdiv(m, 64);
-    mo.nwc = cdiv(n, 64);
-    unsigned long long* fb = ar.alloc<unsigned long long>((size_t)n * mo.nwf);
-    unsigned long long* cb = ar.alloc<unsigned long long>((size_t)m * mo.nwc);
-    double* alpha = ar.alloc<double>((size_t)n);
-    double* beta = ar.alloc<double>((size_t)m);
-    double* diag = ar.alloc<double>((size_t)lv.N);
-    int* bad = ctx->scratch->alloc<int>(1);
-    IPD_HIP(hipMemsetAsync(fb, 0, sizeof(unsigned long long) * (size_t)n * mo.nwf, ctx->stream));
-    IPD_HIP(hipMemsetAsync(cb, 0, sizeof(unsigned long long) * (size_t)m * mo.nwc, ctx->stream));
-    IPD_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(k_maskop_scales, dim3(cdiv(lv.N, 256)), dim3(256), 0, ctx->stream, n, m, p_dev,
-                       q_dev, 1.0 / tk, alpha, beta);
-    hipLaunchKernelGGL(k_maskop_build, dim3(std::max(1, std::min(cdiv(lv.N, 4), 2048))), dim3(256), 0,
-                       ctx->stream, lv.N, n, lv.A.rp, lv.A.ci, lv.A.va, (const double*)alpha,
-                       (const double*)beta, mo.nwf, mo.nwc, fb, cb, diag, bad);
-    IPD_KERNEL_CHECK();
-    if (ctx->fetch1(bad) != 0) return false;
-    mo.fbits = fb;
-    mo.cbits = cb;
-    mo.alpha = alpha;
-    mo.beta = beta;
-    mo.diag = diag;
-    if (for_resident && lv.nf <= RES_NMAX / 2 && h->L[2].A.nr == m) {
-        // W(j,i) = s_ij beta_i rho_j: rho from the row sums (isnsp: rows normalised to sum 1, transfer.m:22-24)
-        // or alpha_j / A_jj, then every entry of P checked against the form
-        double* rho = ar.alloc<double>((size_t)n);
-        IPD_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
-        hipLaunchKernelGGL(k_res_xmask_rho, dim3(cdiv(n, 4)), dim3(256), 0, ctx->stream, n, m, h->opts.isnsp,
-                           (const unsigned long long*)fb, mo.nwf, (const double*)alpha, (const double*)beta,
-                           (const double*)diag, h->L[2].P.rp, h->L[2].P.ci, h->L[2].P.va, rho, bad);
-        IPD_KERNEL_CHECK();
-        if (ctx->fetch1(bad) == 0) {
-            ResDesc& D = st->res_desc;
-            D.xm = 1;
-            D.xm_nwf = mo.nwf;
-            D.xm_nwc = mo.nwc;
-            D.xm_fbits = fb;
-            D.xm_cbits = cb;
-            D.xm_beta = beta;
-            D.xm_rho = rho;
-        }
-    }
-    // Level 1 beyond k_resident's 2048 rows (m = n = 2048: BASELINE config 4's size), three levels with a
-    // one-row tail: the mask-form resident kernel (ipd_resident_big.h).  IPD_RESIDENT_BIG=1 prefers it
-    // wherever it applies (tests), IPD_NO_RESIDENT_BIG=1 switches it off.
-    {
-        const bool forced = switch_on("IPD_RESIDENT_BIG");
-        const bool cyc = h->opts.cycle == 'w' || h->opts.cycle == 'v';
-        const int G = cdiv(std::max(n, m), RES_WAVES);
-        if (!switch_on("IPD_NO_RESIDENT") && !st->res_off && !switch_on("IPD_NO_RESIDENT_BIG") &&
-            (forced || (!st->res_ok && n + m > RES_NMAX)) && !st->small_ok &&
-            !st->resb && h->J == 3 && h->L[3].A.nr == 1 && n <= RB_HALF && m <= RB_HALF && h->L[2].A.nr == m && cyc &&
-            !h->opts.twogrid && G <= st->num_cu && G <= std::min(n, m) && h->opts.smoth >= 1) {
-            LevelDev d2 = st->run[2].dev;
-            if (d2.S <= 0 && st->run[2].maxoff > 0) {   // private padded copy, stride = the longest row
-                d2.S = (st->run[2].maxoff + 3) / 4 * 4;
-                const Csr& A2 = h->L[2].A;
-                unsigned short* pci = ar.alloc<unsigned short>((size_t)A2.nr * d2.S);
-                double* pva = ar.alloc<double>((size_t)A2.nr * d2.S);
-                double* dg = ar.alloc<double>((size_t)A2.nr);
-                hipLaunchKernelGGL(k_pad_build, dim3(std::max(1, std::min(cdiv(A2.nr, 4), 4096))), dim3(256), 0,
-                                   ctx->stream, A2.nr, d2.S, A2.rp, A2.ci, A2.va, pci, pva, dg);
-                IPD_KERNEL_CHECK();
-                d2.pci = pci;
-                d2.pva = pva;
-                d2.diag = dg;
-            }
-            double* rho = const_cast<double*>(st->res_desc.xm_rho);
-            bool rho_ok = st->res_desc.xm != 0;
-            if (!rho_ok) {
-                rho = ar.alloc<double>((size_t)n);
-                IPD_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
-                hipLaunchKernelGGL(k_res_xmask_rho, dim3(cdiv(n, 4)), dim3(256), 0, ctx->stream, n, m, h->opts.isnsp,
-                                   (const unsigned long long*)fb, mo.nwf, (const double*)alpha, (const double*)beta,
-                                   (const double*)diag, h->L[2].P.rp, h->L[2].P.ci, h->L[2].P.va, rho, bad);
-                IPD_KERNEL_CHECK();
-                rho_ok = ctx->fetch1(bad) == 0;
-            }
-            if (rho_ok && d2.S > 0 && d2.S <= 64 * 32) {
-                ResBigDesc B{};
-                B.nf = n;
-                B.nc = m;
-                B.N2 = m;
-                B.S2 = d2.S;
-                B.pci2 = d2.pci;
-                B.pva2 = d2.pva;
-                B.diag2 = d2.diag;
-                B.dinv2 = d2.dinv;
-                B.Axi2 = d2.Axi;
-                B.xx2 = d2.xx;
-                B.diag1 = diag;
-                B.dinv1 = st->run[1].dev.dinv;
-                B.Axi1 = st->run[1].dev.Axi;
-                B.xx1 = st->run[1].dev.xx;
-                B.fbits = fb;
-                B.cbits = cb;
-                B.nwf = mo.nwf;
-                B.nwc = mo.nwc;
-                B.alpha = alpha;
-                B.beta = beta;
-                B.rho = rho;
-                B.P3.rp = h->L[3].P.rp;
-                B.P3.ci = h->L[3].P.ci;
-                B.P3.va = h->L[3].P.va;
-                B.A3.rp = h->L[3].A.rp;
-                B.A3.ci = h->L[3].A.ci;
-                B.A3.va = h->L[3].A.va;
-                B.nu = h->opts.smoth;
-                B.isnsp = h->opts.isnsp;
-                B.wcycle = h->opts.cycle == 'w';
-                B.anycycle = 1;
-                B.maxit = h->opts.maxit;
-                B.retol = h->opts.retol;
-                B.pcg_maxit = h->opts.pcg_maxit;
-                B.pollsleep = 1;
-                B.presleep = 13;
-                const size_t gbytes = (size_t)RB_GRAN * 16;
-                B.ranks = 1;   // rank groups with a granule buffer each (test hook, see ResBigDesc::ranks)
-                if (const char* e = switch_value("IPD_RESIDENT_RANKS")) B.ranks = std::max(1, std::min(8, std::atoi(e)));
-                if (B.ranks > G) B.ranks = 1;
-                st->res_block_bytes = (size_t)B.ranks * 2 * gbytes + 16;
-                st->res_block = reinterpret_cast<unsigned char*>(ar.alloc_bytes(st->res_block_bytes));
-                B.gran = st->res_block;
-                B.tmo = reinterpret_cast<unsigned*>(st->res_block + (size_t)B.ranks * 2 * gbytes);
-                B.dbg_skip_seq = 0;
-                st->resb_desc = B;
-                st->resb_ke2 = d2.S <= 64 * 16 ? 16 : 32;
-                st->resb = true;
-                st->res_remote = false;
-                st->res_ke3 = 0;
-                st->res_G = G;
-                st->res_lds = RB_LDS_BYTES;
-                st->res_capacity = -1;
-                st->res_desc.dbg_skip_seq = 0;
-                if (const char* e = switch_value("IPD_RES_DEBUG_SKIP_PUBLISH")) st->res_desc.dbg_skip_seq = (unsigned)std::max(0, std::atoi(e));
-                if (!st->res_out) st->res_out = ar.alloc<double>(4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2));
-                st->res_ok = true;
-            }
-        }
-    }
-    // DEEP mode of the mask-form kernel: realistic hierarchies (five levels and more) whose level 1 exceeds
-    // k_resident's 2048 rows.  Level 2 as short register slices, level 3 in polynomial form (pack_bpoly in the
-    // RB_P3_SEG row layout), the LDS image rooted at level 4 for the tail workgroup; G <= 255 workgroups
-    // (the tail needs a compute unit of its own), two rows of each block per wave.
-    if (deep_cand && !st->resb) {
-        const int N3 = h->L[3].A.nr, N4 = h->L[4].A.nr;
-        int G = std::max(std::max(cdiv(std::max(n, m), 2 * RES_WAVES), cdiv(N3, 4)), std::max(N4, 128));
-        if (const char* e = switch_value("IPD_RESIDENT_G")) G = std::max(G, std::atoi(e));
-        LevelDev d2 = st->run[2].dev;
-        if (d2.S <= 0 && st->run[2].maxoff > 0) d2.S = -((st->run[2].maxoff + 3) / 4 * 4);   // private copy wanted
-        const int S2 = std::abs(d2.S);
-        // level 4 resident as well (POLY4), the tail rooted at level 5: the only form an image rooted at level 5 serves
-        const int N5 = h->J >= 6 ? h->L[5].A.nr : 0;
-        const bool poly4 = st->d_sub5 && st->k_sub == 5 && N4 <= 2 * G && N5 >= 1 && N5 <= G && N5 <= RB_N5MAX &&
-                           N4 + G <= BT && std::max(RB_LDS_BYTES, st->sub5_lds) <= (size_t)156 * 1024;
-        if (G + 1 <= st->num_cu && G <= std::min(n, m) && S2 > 0 && S2 <= 64 * 8 && (poly4 || st->k_sub != 5)) {
-            if (d2.S < 0) {
-                d2.S = S2;
-                const Csr& A2 = h->L[2].A;
-                unsigned short* pci = ar.alloc<unsigned short>((size_t)A2.nr * d2.S);
-                double* pva = ar.alloc<double>((size_t)A2.nr * d2.S);
-                double* dg = ar.alloc<double>((size_t)A2.nr);
-                hipLaunchKernelGGL(k_pad_build, dim3(std::max(1, std::min(cdiv(A2.nr, 4), 4096))), dim3(256), 0,
-                                   ctx->stream, A2.nr, d2.S, A2.rp, A2.ci, A2.va, pci, pva, dg);
-                IPD_KERNEL_CHECK();
-                d2.pci = pci;
-                d2.pva = pva;
-                d2.diag = dg;
-            }
-            double* rho = ar.alloc<double>((size_t)n);
-            IPD_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
-            hipLaunchKernelGGL(k_res_xmask_rho, dim3(cdiv(n, 4)), dim3(256), 0, ctx->stream, n, m, h->opts.isnsp,
-                               (const unsigned long long*)fb, mo.nwf, (const double*)alpha, (const double*)beta,
-                               (const double*)diag, h->L[2].P.rp, h->L[2].P.ci, h->L[2].P.va, rho, bad);
-            IPD_KERNEL_CHECK();
-            if (ctx->fetch1(bad) == 0) {
-                const BPolyDev pb = pack_bpoly(ctx, h, st, 3, h->opts.isnsp, 0, true, RB_P3_SEG, RB_P3_LD);
-                record_rows_op(st, h, 3, pb);
-                st->level_forms.resize((size_t)h->J + 1, 0);
-                st->level_forms[3] |= 64;
-                BPolyDev pb4;
-                if (poly4) {
-                    pb4 = pack_bpoly(ctx, h, st, 4, h->opts.isnsp, 0, true, RB_P4_SEG, RB_P4_LD);
-                    record_rows_op(st, h, 4, pb4);
-                    st->level_forms[4] |= 64;
-                }
-                ResBigDesc B{};
-                B.nf = n;
-                B.nc = m;
-                B.N2 = m;
-                B.S2 = d2.S;
-                B.pci2 = d2.pci;
-                B.pva2 = d2.pva;
-                B.diag2 = d2.diag;
-                B.dinv2 = d2.dinv;
-                B.Axi2 = d2.Axi;
-                B.xx2 = d2.xx;
-                B.diag1 = diag;
-                B.dinv1 = st->run[1].dev.dinv;
-                B.Axi1 = st->run[1].dev.Axi;
-                B.xx1 = st->run[1].dev.xx;
-                B.fbits = fb;
-                B.cbits = cb;
-                B.nwf = mo.nwf;
-                B.nwc = mo.nwc;
-                B.alpha = alpha;
-                B.beta = beta;
-                B.rho = rho;
-                B.P3.rp = h->L[3].P.rp;   // (unused in DEEP mode)
-                B.P3.ci = h->L[3].P.ci;
-                B.P3.va = h->L[3].P.va;
-                B.A3.rp = h->L[3].A.rp;
-                B.A3.ci = h->L[3].A.ci;
-                B.A3.va = h->L[3].A.va;
-                B.N3 = N3;
-                B.N4 = N4;
-                B.Pt3.rp = h->L[3].Pt.rp;
-                B.Pt3.ci = h->L[3].Pt.ci;
-                B.Pt3.va = h->L[3].Pt.va;
-                B.P3d.rp = h->L[3].P.rp;
-                B.P3d.ci = h->L[3].P.ci;
-                B.P3d.va = h->L[3].P.va;
-                B.p3rows = pb.M;
-                B.p3w = pb.W;
-                B.N5 = poly4 ? N5 : 0;
-                B.p4rows = pb4.M;
-                B.p4w = pb4.W;
-                B.nu = h->opts.smoth;
-                B.isnsp = h->opts.isnsp;
-                B.wcycle = h->opts.cycle == 'w';
-                B.anycycle = 1;
-                B.maxit = h->opts.maxit;
-                B.retol = h->opts.retol;
-                B.pcg_maxit = h->opts.pcg_maxit;
-                B.pollsleep = 1;
-                B.presleep = 13;
-                const size_t gbytes = (size_t)RB_GRAN * 16, tbytes = (size_t)RES_GRAN_MAX * 16;
-                st->res_block_bytes = 2 * gbytes + 16 + 4 * tbytes + 16;
-                st->res_block = reinterpret_cast<unsigned char*>(ar.alloc_bytes(st->res_block_bytes));
-                B.gran = st->res_block;
-                B.tmo = reinterpret_cast<unsigned*>(st->res_block + 2 * gbytes);
-                B.dbg_skip_seq = 0;
-                B.sub = poly4 ? st->d_sub5 : deep_img;
-                if (poly4) deep_img_lds = st->sub5_lds;
-                B.tin = st->res_block + 2 * gbytes + 16;
-                B.tout = st->res_block + 2 * gbytes + 16 + 2 * tbytes;
-                B.tctl = reinterpret_cast<unsigned*>(st->res_block + 2 * gbytes + 16 + 4 * tbytes);
-                st->resb_desc = B;
-                st->resb_ke2 = d2.S <= 64 * 4 ? 4 : 8;
-                st->resb = true;
-                st->resb_deep = true;
-                st->resb_poly4 = poly4;
-                st->res_remote = true;
-                st->res_ke3 = 1;
-                st->res_G = G;
-                st->res_lds = std::max(RB_LDS_BYTES, deep_img_lds);
-                st->res_capacity = -1;
-                st->res_desc.dbg_skip_seq = 0;
-                if (const char* e = switch_value("IPD_RES_DEBUG_SKIP_PUBLISH")) st->res_desc.dbg_skip_seq = (unsigned)std::max(0, std::atoi(e));
-                if (!st->res_out) st->res_out = ar.alloc<double>(4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2));
-                st->res_ok = true;
-            }
-        }
-    }
-    if (!sweeps_too) return st->res_desc.xm != 0 || st->resb;
-    st->maskop = mo;
-    st->mask_ok = true;
-    // captured graphs (if any) were recorded with the CSR sweeps
-    for (auto& g : st->gexec)
-        if (g) {
-            (void)hipGraphExecDestroy(g);
-            g = nullptr;
-        }
-    return true;
-}
-
-// Level 2 of the level-resident kernel in polynomial form, composed over a whole visit (ResDesc::p2rows):
-// three levels with a one-row tail, V cycle, 16-entry slices -- the metric's workload.  Packing costs five
-// dense products of N2^3 (0.5 ms at N2 = 1024) against 18 us saved per cycle: it pays where many cycles run
-// on one hierarchy (bench.py's fixed-hierarchy throughput), never in a solve of such a system, which takes one
-// or two cycles -- so the solvers do not attach it themselves.
-static bool amg_attach_poly2(ipd_amg* h) {
-    ipd_ctx* ctx = h->ctx;
-    CycleState* st = state_of(h);
-    if (!st || !st->res_ok || st->resb || st->res_poly2 || st->res_remote || st->res_ke3 != 0 || st->res_ke != 16) return false;
-    const ResDesc& R = st->res_desc;
-    const int N2 = R.L2.N, nf = R.L1.nf;
-    if (h->J != 3 || R.Nt != 1 || R.three || h->opts.cycle != 'v' || h->opts.smoth < 1 || N2 > RES_NMAX / 2 ||
-        nf > RES_NMAX / 2 || N2 > 64 * 16)
-        return false;
-    const int seg = RES_NMAX / 2, ld = 2 * seg + 128;
-    const BPolyDev pb = pack_bpoly(ctx, h, st, 2, h->opts.isnsp, 0, true, seg, ld);
-    const int Np = pb.e.Np, nT = (Np / 16) * (Np / 16);
-    // (IPD_OPTIN_LDS is not needed: the tiles use static LDS only)
-    hipLaunchKernelGGL(k_bpoly_compose, dim3((unsigned)(nT + (N2 + 3) / 4)), dim3(256), 0, ctx->stream, pb.e, nT);
-    IPD_KERNEL_CHECK();
-    st->res_desc.p2rows = pb.M;
-    st->res_desc.p2w = pb.W;
-    st->res_desc.p2seg = seg;
-    st->res_desc.p2ld = ld;
-    st->poly2_op = rows_op(pb);
-    st->res_poly2 = true;
-    st->res_capacity = -1;
-    st->level_forms.resize((size_t)h->J + 1, 0);
-    st->level_forms[2] |= 128;
-    ctx->sync();   // the pack's scratch operands die with the call scope
-    return true;
-}
-
-extern "C" int ipd_amg_attach_level2_poly(ipd_amg* h, int32_t* attached) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h, IPD_E_ARG, "NULL handle");
-        h->ctx->set_device();
-        CallScope scope(h->ctx);
-        const bool ok = amg_attach_poly2(h);
-        if (attached) *attached = ok ? 1 : 0;
-    });
-}
-
-extern "C" int ipd_amg_attach_mask_operator(ipd_amg* h, const double* p_dev, const double* q_dev,
-                                            int64_t m, int64_t n, double tk, int32_t* attached) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h && p_dev && q_dev && m > 0 && n > 0, IPD_E_ARG, "bad argument");
-        h->ctx->set_device();
-        CallScope scope(h->ctx);
-        const bool ok = amg_attach_maskop(h, p_dev, q_dev, (int)m, (int)n, tk, false, false);
-        if (attached) *attached = ok ? 1 : 0;
-    });
-}
-
-extern "C" int ipd_amg_attach_mask_transfers(ipd_amg* h, const double* p_dev, const double* q_dev,
-                                             int64_t m, int64_t n, double tk, int32_t* attached) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h && p_dev && q_dev && m > 0 && n > 0, IPD_E_ARG, "bad argument");
-        h->ctx->set_device();
-        CallScope scope(h->ctx);
-        const bool ok = amg_attach_maskop(h, p_dev, q_dev, (int)m, (int)n, tk, false, true);
-        if (attached) *attached = ok ? 1 : 0;
-    });
 }
 
 // Solves A_k e = r_k approximately; r in L[k].r, result in L[k].e.
@@ -2269,7 +1435,7 @@ void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, dou
         ctx->sync();
         return;
     }
-    if (st->res_ok && st->shard_ranks == 1) {
+    if (st->res.ok && st->shard_ranks == 1) {
         // dense regime: the whole solve phase is one launch of co-resident workgroups
         std::vector<double> out;
         if (run_resident(h, st, b_dev, xa, 0, &out, nullptr)) {
@@ -2540,45 +1706,6 @@ extern "C" int ipd_amg_cycle_bytes(const ipd_amg* h, double* bytes_per_cycle) {
     return IPD_OK;
 }
 
-// Mode 2 only: how many levels the resident workgroups keep in registers (2 or 3) and the level
-// the tail is rooted at (3: the local tail of a three-level hierarchy or the remote tail workgroup's
-// sub-cycle root; 4: remote tail below a resident level 3); zeros otherwise.
-extern "C" int ipd_amg_resident_levels(const ipd_amg* h, int32_t* levels, int32_t* tail_root) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h, IPD_E_ARG, "NULL handle");
-        const CycleState* st = h->cyc.get();
-        const bool on = st && st->res_ok;
-        if (levels) *levels = on ? (st->resb_poly4 ? 4 : st->res_ke3 > 0 ? 3 : 2) : 0;
-        if (tail_root) *tail_root = on ? (st->resb_poly4 ? 5 : st->res_ke3 > 0 ? 4 : 3) : 0;
-    });
-}
-
-// Which resident kernel this hierarchy's solve phase launches (mode 2 of ipd_amg_solve_mode) -- the
-// instantiation's name as it appears in a rocprofv3 kernel trace, "" otherwise -- and what its last
-// launch did: chip-wide hand-offs (tagged-granule exchanges, plus visits of the remote tail) and loop
-// bodies.  bench.py derives hand-offs per cycle from these instead of re-deriving the kernel from sizes.
-extern "C" int ipd_amg_resident_kernel(const ipd_amg* h, char* name, int32_t cap, int64_t* handoffs,
-                                       int32_t* cycles, int32_t* mask_transfers) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h && name && cap > 0, IPD_E_ARG, "bad argument");
-        const CycleState* st = h->cyc.get();
-        char buf[64] = "";
-        if (st && st->res_ok) {
-            if (st->resb)
-                std::snprintf(buf, sizeof buf, "k_resident_big<%d,%d,%s>", st->resb_ke2, st->resb_deep ? 2 : 1,
-                              st->resb_deep ? "true" : "false");
-            else
-                std::snprintf(buf, sizeof buf, st->res_poly2 ? "k_resident<%d,%d,%d,true>" : "k_resident<%d,%d,%d>",
-                              st->res_ke, st->res_ke, st->res_ke3);
-        }
-        std::snprintf(name, (size_t)cap, "%s", buf);
-        if (handoffs) *handoffs = st ? st->res_last_handoffs : 0;
-        if (cycles) *cycles = st ? st->res_last_cycles : 0;
-        // level 1 <-> 2 transfers from the bit mask: always in the mask-form kernel, ResDesc::xm otherwise
-        if (mask_transfers) *mask_transfers = (st && st->res_ok && (st->resb || st->res_desc.xm)) ? 1 : 0;
-    });
-}
-
 // How the levels held in the LDS images of this hierarchy run (bit mask over all images packed):
 // 1 thread-per-row sweeps, 2 the same with dense rows in registers, 4 one-wave sweeps, 8 one-wave
 // polynomial form, 16 block-wide polynomial form; 0: the level is in no image.
@@ -2656,41 +1783,6 @@ extern "C" int ipd_amg_packed_operator(const ipd_amg* h, int32_t k, int32_t form
     });
 }
 
-extern "C" int ipd_amg_solve_mode(const ipd_amg* h, int32_t* mode, int32_t* grid, int32_t* timeouts) {
-    if (!h || !mode) return IPD_E_ARG;
-    const CycleState* st = h->cyc.get();
-    if (!st) return IPD_E_ARG;
-    *mode = st->small_ok ? 1 : (st->res_ok ? 2 : 0);
-    if (grid) *grid = st->res_ok ? st->res_G + (st->res_remote ? 1 : 0) : (st->small_ok ? 1 : 0);
-    if (timeouts) *timeouts = st->res_timeouts;
-    return IPD_OK;
-}
-
-extern "C" int ipd_amg_bench_resident(ipd_amg* h, const double* b_dev, double* x_dev, int cycles,
-                                      double* total_ms, int64_t stamps[10]) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h && b_dev && x_dev && cycles > 0 && total_ms && stamps, IPD_E_ARG, "bad argument");
-        ipd_ctx* ctx = h->ctx;
-        CallScope scope(ctx);
-        CycleState* st = state_of(h);
-        IPD_REQUIRE(st && st->res_ok, IPD_E_ARG, "hierarchy does not run in resident mode");
-        const int N = h->L[1].A.nr;
-        long long* dbg = ctx->scratch->alloc<long long>(16);
-        IPD_HIP(hipMemsetAsync(dbg, 0, 128, ctx->stream));
-        IPD_HIP(hipMemcpyAsync(h->x, x_dev, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-        float msf = 0.f;
-        IPD_REQUIRE(run_resident(h, st, b_dev, h->x, cycles, nullptr, &msf, dbg), IPD_E_HIP,
-                    "resident kernel gave up (not every workgroup was resident)");
-        IPD_HIP(hipMemcpyAsync(x_dev, h->x, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-        long long hs[10];
-        ctx->fetch(dbg, hs, 10);
-        for (int i = 0; i < 10; ++i) stamps[i] = hs[i];
-        *total_ms = msf;
-    });
-}
-
 // Captures the two loop bodies (x -> x2 and x2 -> x) as HIP graphs: one graph launch
 // per cycle instead of ~40 kernel launches, so the host never paces the device.
 static void ensure_graphs(ipd_amg* h, CycleState* st, const double* b_dev) {
@@ -2758,7 +1850,7 @@ extern "C" int ipd_amg_bench_cycles(ipd_amg* h, const double* b_dev, double* x_d
             if (bytes_per_cycle) *bytes_per_cycle = cycle_bytes(h);
             return;
         }
-        if (st->res_ok) {  // one launch of co-resident workgroups runs all the cycles
+        if (st->res.ok) {  // one launch of co-resident workgroups runs all the cycles
             IPD_HIP(hipMemcpyAsync(h->x, x_dev, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
                                    ctx->stream));
             float msf = 0.f;

@@ -27,10 +27,16 @@ struct PlanOptions {
     size_t sol_head = 0;   // SOL_HEAD: the image head (SolveDesc and its relocation table)
 };
 
-struct PlanSwitches {   // the IPD_NO_* switches of the planner and plan_resident (ipd_switches.h), read once per hierarchy
+// The switches of the level planner and of the resident planner (ipd_switches.h), read by read_plan_switches
+// at the call in which they take effect: amg_prepare_levels and again amg_attach_maskop
+struct PlanSwitches {
     bool no_poly = false, no_blk = false, no_bpoly = false, no_blkdense = false, no_small = false,
          no_subcycle = false, no_resident = false, no_resident_remote = false, no_resident_three = false,
          no_resident_deep = false, no_resident_big = false, no_res_poly4 = false;
+    bool resident_big = false, maskop = false;   // IPD_RESIDENT_BIG, IPD_MASKOP
+    int resident_g = 0, resident_ranks = 0;      // IPD_RESIDENT_G, IPD_RESIDENT_RANKS (0: unset)
+    int res_presleep = -1;                       // IPD_RES_PRESLEEP (-1: unset)
+    unsigned res_skip_publish = 0;               // IPD_RES_DEBUG_SKIP_PUBLISH
 };
 
 enum ImageRole { IMG_SOLVE, IMG_SUB, IMG_SUB3, IMG_SUB4, IMG_NONE };
@@ -70,6 +76,18 @@ struct LevelPlan {
     }
 };
 
+// Conditions of the resident planner (ipd_resident_plan.h) that this one anticipates when it packs images for it
+// workgroups of k_resident: one wave per row of the larger block of level 1 and of level 2
+static inline int resident_rows_G(int nf, int nc, int N2) {
+    return std::max((std::max(nf, nc) + RES_WAVES - 1) / RES_WAVES, (N2 + RES_WAVES - 1) / RES_WAVES);
+}
+// k_resident's POLY3: the tail's root level 4 has one restriction row per workgroup at most
+static inline bool resident_poly3_root_fits(int N4, int G) { return N4 <= G && N4 <= 128; }
+// the mask-form kernel's deep mode: blocks of level 1 (nf, nc), level 2 = the C block, levels 3 and 4
+static inline bool resident_deep_sizes_fit(int nf, int nc, int N2, int N3, int N4) {
+    return nf <= RB_HALF && nc <= RB_HALF && N2 == nc && N3 <= RB_N3MAX && N4 <= RB_N4MAX;
+}
+
 static inline size_t plan_r8(size_t n) { return (n + 7) / 8 * 8; }
 static inline size_t plan_r16(size_t b) { return (b + 15) / 16 * 16; }
 static inline size_t poly_ld(size_t rows) { return rows <= 32 ? 32 : (rows <= 48 ? 48 : 64); }
@@ -84,8 +102,6 @@ struct LevelPlanner {
     // decided on the way (see plan_levels)
     bool use_poly, use_lpoly, lean_vectors, use_lmap, use_bdense, use_bpoly;
     int tiny_lo;
-
-    static int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
     // one workgroup is one CU: beyond ~1000 short rows per level the multi-launch path (many CUs per
     // phase) wins again (measured: M = 1000 W-cycle solve 9.5 ms here vs 17 ms multi-launch; M = 2048:
@@ -276,8 +292,8 @@ inline void LevelPlanner::plan_sub(LevelPlan& p) const {
     // then run level 4 as launches: the fall-back).  (An image rooted at level 4 for the launches
     // beside one rooted at level 5 for the resident kernel packed levels 5..J twice: 0.2 ms per hierarchy.)
     const int nf1 = L[1].nf, nc1 = L[1].nr - nf1;
-    const bool root5 = J >= 6 && L[1].nr > RES_NMAX && nf1 > 0 && nf1 <= RB_HALF && nc1 <= RB_HALF && L[2].nr == nc1 &&
-                       L[3].nr <= RB_N3MAX && L[4].nr <= RB_N4MAX && L[5].nr <= RB_N5MAX && o.smoth >= 1 && !o.twogrid &&
+    const bool root5 = J >= 6 && L[1].nr > RES_NMAX && nf1 > 0 &&
+                       resident_deep_sizes_fit(nf1, nc1, L[2].nr, L[3].nr, L[4].nr) && L[5].nr <= RB_N5MAX && o.smoth >= 1 && !o.twogrid &&
                        !o.concurrent_pair && !sw.no_res_poly4 && !sw.no_resident_deep && !sw.no_resident_big &&
                        !sw.no_resident;
     if (root5) k_small = std::max(k_small, 5);
@@ -319,9 +335,8 @@ inline void LevelPlanner::plan_tails(LevelPlan& p) const {
     // With level 3 in polynomial form (plan_resident, poly3: a visit of it is three hand-offs instead of
     // thirteen) the same holds wherever that form applies, semi-cached root or not: 0.33-0.36 -> see DESIGN.
     const bool poly3_likely =
-        J >= 5 && o.smoth >= 1 && L[1].nf > 0 && L[4].nr <= 128 &&
-        L[4].nr <= std::max(cdiv(std::max(L[1].nf, L[1].nr - L[1].nf), RES_WAVES), cdiv(L[2].nr, RES_WAVES)) &&
-        !sw.no_poly;
+        J >= 5 && o.smoth >= 1 && L[1].nf > 0 &&
+        resident_poly3_root_fits(L[4].nr, resident_rows_G(L[1].nf, L[1].nr - L[1].nf, L[2].nr)) && !sw.no_poly;
     if (p.k_sub == 3 && (p.sub_semi_root || poly3_likely) && J >= 5 && J <= SOLVE_ML && L[3].nr <= BT &&
         L[4].nr <= BT && L[3].maxoff <= 512 && L[1].nf > 0 && !sw.no_resident_three && !sw.no_resident) {
         bool ok = lean_vectors;

@@ -2,6 +2,8 @@
 // the planner's CPU test compiles it with a plain C++ compiler.
 #pragma once
 
+#include <cstddef>
+
 #if defined(__HIPCC__)
 #define IPD_HD_INLINE __host__ __device__ __forceinline__
 #else
@@ -39,6 +41,9 @@ IPD_HD_INLINE int bdense_ld(int N) {
 static constexpr int RES_WAVES = BT / 64;     // row slots per block and workgroup (one wave per row)
 static constexpr int RES_NMAX = 4 * BT;        // rows per level (fixed LDS slots)
 static constexpr int RES_P4_SEG = 128;         // ... of ResDesc::p4rows: 128 + 128 + 64
+static constexpr int RES_TAIL_MAX = 64;        // rows of the redundantly solved tail level
+static constexpr size_t RES_LDS_BYTES = sizeof(double) * ((size_t)9 * RES_NMAX + RES_NMAX / 2 + 3 * RES_TAIL_MAX + 16 * RES_WAVES + 12);
+static constexpr size_t RES_LDS_MAX = (size_t)156 * 1024;   // dynamic LDS a resident launch may ask for (its own or its tail image's)
 
 // mask-form resident kernel (ipd_resident_big.h)
 static constexpr int RB_NMAX = 8 * BT;                 // rows of level 1
@@ -46,3 +51,10 @@ static constexpr int RB_HALF = 4 * BT;                 // rows of a block of lev
 static constexpr int RB_N3MAX = 2 * BT;                // rows of the polynomial level 3 (DEEP)
 static constexpr int RB_N4MAX = BT / 2;                // rows of the remote tail's root level (DEEP)
 static constexpr int RB_N5MAX = BT / 4;                // rows of the tail's root level when level 4 is resident too (POLY4)
+static constexpr int RB_RPW_MAX = 2;                   // rows of a block per wave
+// LDS (doubles): E2, TU, P3C / RR2, E1S, XS, reductions, publish slots, own-row constants, fail word;
+// DEEP: R3, E3 (RB_N3MAX each), E4, R4 (RB_N4MAX each), E5 (RB_N5MAX), 128 partial sums of the polynomial passes
+static constexpr size_t RB_LDS_DOUBLES = (size_t)2 * RB_NMAX + 3 * RB_HALF + 2 * RES_WAVES +
+                                         2 * 8 * RB_RPW_MAX + 20 * 8 * RB_RPW_MAX + 8 +
+                                         2 * RB_N3MAX + 2 * RB_N4MAX + RB_N5MAX + 128;
+static constexpr size_t RB_LDS_BYTES = sizeof(double) * RB_LDS_DOUBLES;

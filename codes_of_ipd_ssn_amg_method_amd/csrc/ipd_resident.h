@@ -37,9 +37,7 @@
 
 typedef unsigned int res_v4u __attribute__((ext_vector_type(4)));
 
-static constexpr int RES_TAIL_MAX = 64;       // rows of the redundantly solved tail level
 static constexpr int RES_GRAN_MAX = RES_NMAX;  // granules per hand-off buffer
-static constexpr size_t RES_LDS_BYTES = sizeof(double) * ((size_t)9 * RES_NMAX + RES_NMAX / 2 + 3 * RES_TAIL_MAX + 16 * RES_WAVES + 12);
 static constexpr unsigned RES_SPIN_MAX = 1u << 18;
 static constexpr int RES_P3_LD = 1152;         // row stride of ResDesc::p3rows: 512 + 512 + 128
 static constexpr int RES_P4_LD = 2 * RES_P4_SEG + 64;

@@ -31,18 +31,10 @@
 #pragma once
 
 static constexpr int RB_GRAN = RB_NMAX;                // granules per hand-off buffer
-static constexpr int RB_RPW_MAX = 2;                   // rows of a block per wave
 static constexpr int RB_P3_SEG = RB_N3MAX;             // p3rows layout: [Mr (RB_P3_SEG) | Me (RB_P3_SEG) | Mc (RB_N4MAX)]
 static constexpr int RB_P3_LD = 2 * RB_P3_SEG + RB_N4MAX;
 static constexpr int RB_P4_SEG = RB_N4MAX;             // p4rows layout: [Mr (RB_P4_SEG) | Me (RB_P4_SEG) | Mc (RB_N5MAX)]
 static constexpr int RB_P4_LD = 2 * RB_P4_SEG + RB_N5MAX;
-// LDS (doubles): E2, TU, P3C / RR2, E1S, XS, reductions, publish slots, own-row constants, fail word;
-// DEEP: R3, E3 (RB_N3MAX each), E4, R4 (RB_N4MAX each), E5 (RB_N5MAX), 128 partial sums of the polynomial passes
-static constexpr size_t RB_LDS_DOUBLES = (size_t)2 * RB_NMAX + 3 * RB_HALF + 2 * RES_WAVES +
-                                         2 * 8 * RB_RPW_MAX + 20 * 8 * RB_RPW_MAX + 8 +
-                                         2 * RB_N3MAX + 2 * RB_N4MAX + RB_N5MAX + 128;
-static constexpr size_t RB_LDS_BYTES = sizeof(double) * RB_LDS_DOUBLES;
-
 struct ResBigDesc {
     int nf, nc, N2, S2;
     const unsigned short* pci2;   // level 2: padded rows (stride S2), 16-bit columns

@@ -1,0 +1,654 @@
+// Host side of the resident kernels (included by ipd_cycle_host.h, which defines CycleState and its
+// ResidentState member, at the place of the first kernel-template launch of the translation unit): the table of
+// their instantiations, the execution of a plan (ipd_resident_plan.h decides, this file does the device work
+// the plan calls for, verifies what only the device can verify and commits it to CycleState::res), the slots
+// and the launch, the attach functions and the introspection entry points.
+#pragma once
+
+// ---- the instantiations ---------------------------------------------------------------------
+// One row per instantiation: its name as a rocprofv3 kernel trace (and ipd_amg_resident_kernel) spells it, the
+// plan's key, the kernel.  A key without a row is never launched -- the hierarchy takes the launches -- so the
+// development builds (tools/kernel_regs.py) compile a subset by leaving rows out.  (The rows' order is the order
+// of the kernels in the object.)
+struct ResidentKernel {
+    const char* name;
+    ResidentKey key;
+    const void* fn;
+};
+#define IPD_KFN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+static const ResidentKernel RESIDENT_KERNELS[] = {
+#ifndef IPD_DEV_ONLY_RES16   // (development: the metric's instantiations alone)
+    {"k_resident_big<4,2,true>", ResidentKey::mask(4, 2, true), IPD_KFN(k_resident_big<4, 2, true>)},
+    {"k_resident_big<8,2,true>", ResidentKey::mask(8, 2, true), IPD_KFN(k_resident_big<8, 2, true>)},
+    {"k_resident_big<16,1,false>", ResidentKey::mask(16, 1, false), IPD_KFN(k_resident_big<16, 1, false>)},
+    {"k_resident_big<32,1,false>", ResidentKey::mask(32, 1, false), IPD_KFN(k_resident_big<32, 1, false>)},
+#endif
+#ifndef IPD_DEV_ONLY_BIG   // (... or the mask-form kernels alone)
+    {"k_resident<16,16,0,true>", ResidentKey::k(16, 0, true), IPD_KFN(k_resident<16, 16, 0, true>)},
+#ifndef IPD_DEV_ONLY_RES16
+    {"k_resident<4,4,0>", ResidentKey::k(4, 0, false), IPD_KFN(k_resident<4, 4, 0, false>)},
+    {"k_resident<8,8,0>", ResidentKey::k(8, 0, false), IPD_KFN(k_resident<8, 8, 0, false>)},
+#endif
+    {"k_resident<16,16,0>", ResidentKey::k(16, 0, false), IPD_KFN(k_resident<16, 16, 0, false>)},
+#ifndef IPD_DEV_ONLY_RES16
+    {"k_resident<4,4,1>", ResidentKey::k(4, 1, false), IPD_KFN(k_resident<4, 4, 1, false>)},
+    {"k_resident<8,8,1>", ResidentKey::k(8, 1, false), IPD_KFN(k_resident<8, 8, 1, false>)},
+    {"k_resident<4,4,4>", ResidentKey::k(4, 4, false), IPD_KFN(k_resident<4, 4, 4, false>)},
+    {"k_resident<4,4,8>", ResidentKey::k(4, 8, false), IPD_KFN(k_resident<4, 4, 8, false>)},
+    {"k_resident<8,8,4>", ResidentKey::k(8, 4, false), IPD_KFN(k_resident<8, 8, 4, false>)},
+    {"k_resident<8,8,8>", ResidentKey::k(8, 8, false), IPD_KFN(k_resident<8, 8, 8, false>)},
+#endif
+#endif
+};
+#undef IPD_KFN
+static const ResidentKernel* resident_kernel(const ResidentKey& key) {
+    for (const ResidentKernel& k : RESIDENT_KERNELS)
+        if (k.key == key) return &k;
+    return nullptr;
+}
+
+// ---- the pieces a plan's execution is made of -------------------------------------------------
+static ResidentInputs resident_inputs(const ipd_amg* h, const CycleState* st, const std::vector<LevelShape>& shapes) {
+    ResidentInputs in;
+    in.L = shapes.data();
+    in.J = h->J;
+    for (int k = 1; k <= std::min(3, h->J); ++k) in.S[k] = st->run[(size_t)k].dev.S;
+    in.cycle = h->opts.cycle;
+    in.smoth = h->opts.smoth;
+    in.twogrid = h->opts.twogrid;
+    in.bigph = h->opts.bigph;
+    in.num_cu = st->num_cu;
+    in.small_ok = st->small_ok;
+    in.k_sub = st->k_sub;
+    in.img[IMG_SUB] = ResidentImage{st->d_sub != nullptr, st->sub_lds, st->sub_bm};
+    in.img[IMG_SUB3] = ResidentImage{st->d_sub3 != nullptr, st->sub3_lds, st->sub3_bm};
+    in.img[IMG_SUB4] = ResidentImage{st->d_sub4 != nullptr, st->sub4_lds, st->sub4_bm};
+    in.sub5 = st->sub5;
+    return in;
+}
+static const SolveDesc* resident_image(const CycleState* st, ImageRole r) {
+    return r == IMG_SUB ? st->d_sub : r == IMG_SUB3 ? st->d_sub3 : r == IMG_SUB4 ? st->d_sub4 : nullptr;
+}
+
+// level k's rows as the plan wants them: the launches' padded copy or a private one with stride p.S[k] (k_pad_build)
+static LevelDev resident_rows(ipd_amg* h, const CycleState* st, const ResidentPlan& p, int k) {
+    LevelDev d = st->run[(size_t)k].dev;
+    if (!p.priv[k]) return d;
+    const Csr& A = h->L[k].A;
+    Arena& ar = *h->arena;
+    d.S = p.S[k];
+    unsigned short* pci = ar.alloc<unsigned short>((size_t)A.nr * d.S);
+    double* pva = ar.alloc<double>((size_t)A.nr * d.S);
+    double* dg = ar.alloc<double>((size_t)A.nr);
+    hipLaunchKernelGGL(k_pad_build, dim3(std::max(1, std::min(cdiv(A.nr, 4), 4096))), dim3(256), 0, h->ctx->stream,
+                       A.nr, d.S, A.rp, A.ci, A.va, pci, pva, dg);
+    IPD_KERNEL_CHECK();
+    d.pci = pci;
+    d.pva = pva;
+    d.diag = dg;
+    return d;
+}
+
+// W(j,i) = s_ij beta_i rho_j: rho from the row sums (isnsp: rows normalised to sum 1, transfer.m:22-24)
+// or alpha_j / A_jj, then every entry of P checked against the form; nullptr where P is not of it
+static double* mask_transfer_rho(ipd_amg* h, const MaskOp& mo, int* bad) {
+    ipd_ctx* ctx = h->ctx;
+    double* rho = h->arena->alloc<double>((size_t)mo.nf);
+    IPD_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(k_res_xmask_rho, dim3(cdiv(mo.nf, 4)), dim3(256), 0, ctx->stream, mo.nf, mo.nc, h->opts.isnsp,
+                       (const unsigned long long*)mo.fbits, mo.nwf, mo.alpha, mo.beta, mo.diag, h->L[2].P.rp,
+                       h->L[2].P.ci, h->L[2].P.va, rho, bad);
+    IPD_KERNEL_CHECK();
+    return ctx->fetch1(bad) == 0 ? rho : nullptr;
+}
+
+static ResCsr res_csr(const Csr& m) { return ResCsr{m.rp, m.ci, m.va}; }
+static ResLevelDesc res_level(const LevelDev& d) {
+    return ResLevelDesc{d.N, d.nf, d.S, d.pci, d.pva, d.diag, d.dinv, d.Axi, d.xx};
+}
+
+template <class Desc>
+static void set_cycle_options(Desc& D, const ipd_amg* h, int presleep) {
+    D.nu = h->opts.smoth;
+    D.isnsp = h->opts.isnsp;
+    D.wcycle = h->opts.cycle == 'w';
+    D.anycycle = (h->opts.cycle == 'w' || h->opts.cycle == 'v');
+    D.maxit = h->opts.maxit;
+    D.retol = h->opts.retol;
+    D.pcg_maxit = h->opts.pcg_maxit;
+    D.pollsleep = 1;   // (0..2 sleeps between polls made no difference, from 3 on it was worse)
+    D.presleep = presleep;
+    D.dbg_skip_seq = 0;
+}
+
+// The granule block, zeroed before every launch: [hand-off granules | time-out word] and, with a tail
+// workgroup, [tin | tout: 2 x RES_GRAN_MAX granules each, by visit parity | tctl].  Returns the granules.
+template <class Desc>
+static unsigned char* alloc_resident_block(ipd_amg* h, ResidentState& R, Desc& D, size_t gran_bytes, bool tail) {
+    const size_t tbytes = (size_t)RES_GRAN_MAX * 16;
+    R.block_bytes = gran_bytes + 16 + (tail ? 4 * tbytes + 16 : 0);
+    R.block = reinterpret_cast<unsigned char*>(h->arena->alloc_bytes(R.block_bytes));
+    D.tmo = reinterpret_cast<unsigned*>(R.block + gran_bytes);
+    D.tin = tail ? R.block + gran_bytes + 16 : R.block;                // never touched without
+    D.tout = tail ? R.block + gran_bytes + 16 + 2 * tbytes : R.block;  // a tail workgroup
+    D.tctl = tail ? reinterpret_cast<unsigned*>(R.block + gran_bytes + 16 + 4 * tbytes) : D.tmo;
+    return R.block;
+}
+
+// level k in polynomial form, row layout (pack_bpoly), for the resident workgroups: form 64
+static BPolyDev pack_resident_poly(ipd_amg* h, CycleState* st, int k, int seg, int ld) {
+    const BPolyDev pb = pack_bpoly(h->ctx, h, st, k, h->opts.isnsp, 0, true, seg, ld);
+    record_rows_op(st, h, k, pb);
+    st->level_forms.resize((size_t)h->J + 1, 0);
+    st->level_forms[(size_t)k] |= 64;
+    return pb;
+}
+
+// the plan is taken: from here on the solve phase is one launch of p.key's instantiation
+static void commit_resident(ipd_amg* h, ResidentState& R, const ResidentPlan& p, const PlanSwitches& sw) {
+    R.plan = p;
+    R.capacity = -1;
+    R.skip_publish = sw.res_skip_publish;
+    if (!R.out) R.out = h->arena->alloc<double>(4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2));
+    R.ok = true;
+}
+
+// ---- k_resident: planned at amg_prepare_levels -------------------------------------------------
+static void prepare_resident(ipd_amg* h, CycleState* st, const std::vector<LevelShape>& shapes, const PlanSwitches& sw) {
+    ResidentState& R = st->res;
+    R.ok = false;
+    R.off = sw.no_resident;   // (remembered: the mask-form kernel is set up later, by amg_attach_maskop)
+    const ResidentPlan p = plan_resident(resident_inputs(h, st, shapes), sw);
+    if (p.considered && switch_on("IPD_DEBUG_LEVELS"))
+        std::fprintf(stderr, "[ipd] resident plan: J=%d nf=%d nc=%d S1=%d S2=%d S3=%d N4=%d Nt=%d k_sub=%d sub_lds=%zu\n", h->J,
+                     h->L[1].nf, h->L[1].A.nr - h->L[1].nf, p.S[1], p.S[2], st->run[3].dev.S,
+                     h->J >= 4 ? h->L[4].A.nr : 0, h->L[3].A.nr, st->k_sub, st->sub_lds);
+    if (p.kind == RESIDENT_NONE) return;
+    const Level& l1 = h->L[1];
+    const Level& l2 = h->L[2];
+    const Level& l3 = h->L[3];
+    const int N2 = l2.A.nr, nf = l1.nf;
+    ResDesc D{};
+    D.L1 = res_level(resident_rows(h, st, p, 1));
+    D.L2 = res_level(resident_rows(h, st, p, 2));
+    D.Pt2 = res_csr(l2.Pt);
+    D.P2 = res_csr(l2.P);
+    D.Pt3 = res_csr(l3.Pt);
+    D.P3 = res_csr(l3.P);
+    D.A3 = res_csr(l3.A);
+    D.Nt = p.Nin;
+    D.three = p.three ? 1 : 0;
+    D.tail_root = p.tail_root;
+    D.A4 = res_csr(p.three ? h->L[4].A : l3.A);
+    if (p.three) {
+        if (p.poly3) {
+            const BPolyDev pb = pack_resident_poly(h, st, 3, 512, RES_P3_LD);
+            D.p3rows = pb.M;
+            D.p3w = pb.W;
+            if (p.poly4) {
+                const BPolyDev pb4 = pack_resident_poly(h, st, 4, RES_P4_SEG, RES_P4_LD);
+                D.p4rows = pb4.M;
+                D.p4w = pb4.W;
+                D.N5 = h->L[5].A.nr;
+            }
+        }
+        D.L3 = res_level(resident_rows(h, st, p, 3));
+        D.Pt4 = res_csr(h->L[4].Pt);
+        D.P4 = res_csr(h->L[4].P);
+    } else {
+        D.L3 = D.L2;   // unused
+        D.Pt4 = res_csr(l3.Pt);
+        D.P4 = res_csr(l3.P);
+    }
+    // s_sleep(1) count between a publish and the first poll (a failing poll delays the publishes it waits for).
+    // Round 2: 0 -> 0.0869, 8 -> 0.0796, 12..14 -> 0.0770, 16 -> 0.0784 ms per V cycle.  With the shorter
+    // hand-off of round 5 the best value moved down: metric workload 8 -> 0.0446, 13 -> 0.0456 ms
+    // (6 / 7 / 9: 0.0450 / 0.0460 / 0.0447), W cycle 0.0852 against 0.0876, the sweep form of level 2 even.
+    set_cycle_options(D, h, sw.res_presleep >= 0 ? sw.res_presleep : 8);
+    D.wident = p.wident > 0 ? 1 : 0;
+    if (p.wident < 0) {   // P = [W; I] to be verified
+        int* bad = zeroed<int>(h->ctx, 1);
+        hipLaunchKernelGGL(k_res_check_ident, dim3(cdiv(N2, 256)), dim3(256), 0, h->ctx->stream, nf, N2,
+                           res_csr(l2.P), res_csr(l2.Pt), bad);
+        IPD_KERNEL_CHECK();
+        D.wident = h->ctx->fetch1(bad) == 0 ? 1 : 0;
+    }
+    D.localfirst = 1;
+    const size_t gbytes = (size_t)RES_GRAN_MAX * 16;
+    D.gran0 = alloc_resident_block(h, R, D, 2 * gbytes, p.remote);
+    D.gran1 = D.gran0 + gbytes;
+    D.remote = p.remote ? 1 : 0;
+    D.sub = resident_image(st, p.tail_image);
+    D.tail_bm = p.tail_bm ? 1 : 0;
+    D.dbg = nullptr;
+    R.desc = D;
+    R.line_ke = p.key.ke;
+    R.line_ke3 = p.key.ke3;
+    commit_resident(h, R, p, sw);
+}
+
+// Resident kernels need all their workgroups on the chip at once (one per CU): as many of them may
+// run side by side as their grids fit into the device's CUs -- two of 128 workgroups on an MI355X
+// (AMG4POT's two concurrent solves, bench.py --batch 2) -- and a further one waits for a free slot
+// (a solve lasts a millisecond or two; running it as launches beside two resident kernels slows all
+// three: --batch 4 fell from 2 x 20 M to 17.6 M DoF*cycles/s) and takes the multi-launch path only
+// if none frees up within 50 ms.  (The spins are bounded, so an over-commitment could only cost the
+// launch, never hang.)
+struct ResidentSlots {
+    std::mutex mu;
+    std::condition_variable cv;
+    int used[64] = {0};
+    bool acquire(int device, int workgroups, int cus, int wait_ms) {
+        std::unique_lock<std::mutex> lock(mu);
+        if (workgroups > cus) return false;
+        const bool got = cv.wait_for(lock, std::chrono::milliseconds(wait_ms),
+                                     [&] { return used[device & 63] + workgroups <= cus; });
+        if (!got) return false;
+        used[device & 63] += workgroups;
+        return true;
+    }
+    void release(int device, int workgroups) {
+        {
+            std::lock_guard<std::mutex> lock(mu);
+            used[device & 63] -= workgroups;
+        }
+        cv.notify_all();
+    }
+};
+static ResidentSlots& resident_slots() {
+    static ResidentSlots s;
+    return s;
+}
+struct ResidentLease {
+    int device, wgs;
+    bool ok;
+    ResidentLease(int d, int w, int cus, int wait_ms)
+        : device(d), wgs(w), ok(resident_slots().acquire(d, w, cus, wait_ms)) {}
+    ~ResidentLease() {
+        if (ok) resident_slots().release(device, wgs);
+    }
+};
+
+// Runs the whole solve (fixed_cycles == 0) or exactly fixed_cycles loop bodies on the
+// iterate in x (in: guess, out: result).  Returns false when the kernel could not be used
+// (another resident kernel is running, or a spin gave up): x is then unspecified and the
+// caller takes the multi-launch path.  `ms`: device time of the launch (HIP events), optional.
+static bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double* x, int fixed_cycles,
+                         std::vector<double>* out_host, float* ms, long long* dbg_dev = nullptr) {
+    ipd_ctx* ctx = h->ctx;
+    ResidentState& R = st->res;
+    const ResidentPlan& p = R.plan;
+    const int grid = p.grid();
+    if (ctx->res_penalty > 0) {   // an earlier launch of this context gave up: stay on the launches for a while
+        --ctx->res_penalty;
+        return false;
+    }
+    // A remote-tail launch is 129 workgroups at M = 2048: two of them do not fit side by side, and a
+    // realistic solve is a few milliseconds of mostly serial sub-cycle work -- waiting for the other
+    // solve (AMG4POT's two right-hand sides) would serialise them, so the loser runs as launches
+    // beside it at once.  The dense three-level launches (128 workgroups, two fit) keep waiting.
+    ResidentLease lease(ctx->device, grid, st->num_cu, p.remote ? 0 : 50);
+    if (!lease.ok) return false;
+    ResDesc D = R.desc;
+    D.dbg = dbg_dev;
+    D.dbg_skip_seq = R.skip_publish;
+    ResBigDesc B = R.big;
+    B.dbg_skip_seq = R.skip_publish;
+    if (switch_on("IPD_DEBUG_LEVELS"))
+        std::fprintf(stderr, "[ipd] resident launch: grid %d ke %d ke3 %d xm %d wident %d three %d remote %d\n", grid,
+                     R.line_ke, R.line_ke3, D.xm, D.wident, D.three, D.remote);
+    R.skip_publish = 0;   // the test hook fires on ONE launch
+    IPD_HIP(hipMemsetAsync(R.block, 0, R.block_bytes, ctx->stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (ms) {
+        for (hipEvent_t& ev : ctx->tev)
+            if (!ev) IPD_HIP(hipEventCreate(&ev));
+        e0 = ctx->tev[0];
+        e1 = ctx->tev[1];
+        IPD_HIP(hipEventRecord(e0, ctx->stream));
+    }
+    // The workgroups spin on one another, so ALL of them must be on the chip at once: the grid is
+    // checked against what the device can hold of this instantiation (registers, LDS: one workgroup
+    // per CU) before the first launch; an oversized grid takes the multi-launch path for good -- and so
+    // does a key the table has no row for.
+    const ResidentKernel* kern = resident_kernel(p.key);
+    if (kern) {
+        IPD_OPTIN_LDS(ctx, kern->fn, RES_LDS_MAX);
+        if (R.capacity < 0) {
+            int nb = 0;
+            IPD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern->fn, BT, p.lds));
+            R.capacity = nb * st->num_cu;
+        }
+    }
+    if (!kern || grid > R.capacity) {
+        R.ok = false;
+        return false;
+    }
+    void* args[] = {p.key.big ? (void*)&B : (void*)&D, (void*)&b_dev, (void*)&x, (void*)&R.out, (void*)&fixed_cycles};
+    IPD_HIP(hipLaunchKernel(kern->fn, dim3(grid), dim3(BT), args, p.lds, ctx->stream));
+    IPD_KERNEL_CHECK();
+    if (ms) IPD_HIP(hipEventRecord(e1, ctx->stream));
+    const size_t nout = 4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2);
+    std::vector<double> out(nout);
+    ctx->fetch(R.out, out.data(), nout);   // waits for the kernel (through the host mailbox: no stream synchronisation)
+    if (ms) {
+        IPD_HIP(hipEventSynchronize(e1));
+        IPD_HIP(hipEventElapsedTime(ms, e0, e1));
+    }
+    if (out[3] != 0.0) {   // a bounded spin gave up somewhere (any workgroup: the kernel reports the
+        // time-out word, not only workgroup 0's own view): not every workgroup was resident
+        ++R.timeouts;
+        ++ctx->res_giveups;
+        ctx->res_penalty = 32 << std::min(ctx->res_giveups - 1, 6);
+        if (R.timeouts >= 2) R.ok = false;
+        return false;
+    }
+    R.last_handoffs = (long long)out[nout - 1];
+    R.last_cycles = fixed_cycles > 0 ? fixed_cycles : (int)out[0];
+    if (out_host) *out_host = std::move(out);
+    return true;
+}
+
+// the "resident=..." field of amg_prepare_levels' debug line
+static void print_resident_summary(std::FILE* f, const CycleState* st) {
+    std::fprintf(f, "resident=%d(G=%d,KE=%d)", (int)st->res.ok, st->res.plan.G, st->res.plan.key.ke);
+}
+
+// ---- the mask-form kernel: planned by amg_attach_maskop -----------------------------------------
+// what both of its modes put into ResBigDesc
+static ResBigDesc big_desc(ipd_amg* h, const CycleState* st, const MaskOp& mo, const LevelDev& d2, const double* rho) {
+    ResBigDesc B{};
+    B.nf = mo.nf;
+    B.nc = mo.nc;
+    B.N2 = mo.nc;
+    B.S2 = d2.S;
+    B.pci2 = d2.pci;
+    B.pva2 = d2.pva;
+    B.diag2 = d2.diag;
+    B.dinv2 = d2.dinv;
+    B.Axi2 = d2.Axi;
+    B.xx2 = d2.xx;
+    B.diag1 = mo.diag;
+    B.dinv1 = st->run[1].dev.dinv;
+    B.Axi1 = st->run[1].dev.Axi;
+    B.xx1 = st->run[1].dev.xx;
+    B.fbits = mo.fbits;
+    B.cbits = mo.cbits;
+    B.nwf = mo.nwf;
+    B.nwc = mo.nwc;
+    B.alpha = mo.alpha;
+    B.beta = mo.beta;
+    B.rho = rho;
+    B.P3 = res_csr(h->L[3].P);   // (unused in DEEP mode)
+    B.A3 = res_csr(h->L[3].A);
+    set_cycle_options(B, h, 13);
+    return B;
+}
+static void commit_mask_form(ipd_amg* h, ResidentState& R, const ResidentPlan& p, const ResBigDesc& B,
+                             const PlanSwitches& sw) {
+    R.big = B;
+    R.line_ke3 = p.kind == RESIDENT_DEEP ? 1 : 0;   // (the launch line's ke stays a replaced plan's)
+    commit_resident(h, R, p, sw);
+}
+
+__global__ void k_maskop_scales(int nf, int nc, const double* __restrict__ p, const double* __restrict__ q, double itk,
+                                double* __restrict__ alpha, double* __restrict__ beta);   // (ipd_cycle_host.h)
+
+// Derives the bit-mask form of level 1 from its CSR arrays; keeps the CSR kernels (returns
+// false) unless A_1 is exactly Hybrid_AMG's rescaled operator for these p, q, tk.
+//
+// When it pays (`policy` true: the solvers' own call): the mask sweep moves 13x fewer bytes but is
+// the slower launch while the level is latency-bound -- regime D at m = n = 1024 (2.1 M entries):
+// 5.7 us against 5.2 us for the padded CSR sweep -- and the faster one once the CSR sweep is
+// bandwidth-bound -- m = n = 2048 (8.4 M entries): 8.3 us against 13.4 us.  The solvers therefore
+// attach it from 4 M entries on; IPD_MASKOP=1 lowers that to 16 entries per row, IPD_NO_MASKOP=1
+// switches it off.  An explicit ipd_amg_attach_mask_operator call is not subject to the policy.
+//
+// The resident kernels' share (ipd_resident_plan.h): k_resident takes its level 1 <-> 2 transfers from the
+// mask, and the mask-form kernel is planned here, its three-level mode (which IPD_RESIDENT_BIG=1 lets
+// replace a k_resident plan, reusing its rho) or, when no plan exists, its deep mode.
+bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int m, int n, double tk,
+                       bool policy, bool transfers_only) {
+    ipd_ctx* ctx = h->ctx;
+    CycleState* st = state_of(h);
+    if (!st) return false;
+    ResidentState& R = st->res;
+    const Level& lv = h->L[1];
+    const PlanSwitches sw = read_plan_switches();
+    const std::vector<LevelShape> shapes = level_shapes(h, st);
+    const ResidentInputs in = resident_inputs(h, st, shapes);
+    const ResidentFacts facts{m, n, R.off, R.ok, R.mask_form(), R.desc.wident != 0};   // (as the call finds them)
+    const bool for_resident = resident_wants_mask_transfers(in, facts);
+    bool sweeps_too = !transfers_only;
+    const bool deep_cand = resident_deep_candidate(in, sw, facts);
+    if (transfers_only && !for_resident && !sw.resident_big && !deep_cand) return false;
+    if (policy) {
+        if (!sw.maskop && (double)lv.A.nnz < 4.0e6) {
+            if (!for_resident && !deep_cand) return false;
+            sweeps_too = false;   // below the size where the mask SWEEPS of the launch path pay
+        }
+    }
+    if (h->J < 2 || lv.nf != n || lv.N != m + n || tk == 0.0) return false;
+    // a row of the mask costs nw word walks whatever its population: with fewer than ~16 entries
+    // per row the padded CSR sweep always beats it
+    if ((double)lv.A.nnz < 16.0 * lv.N) {
+        if (!deep_cand) return false;
+        sweeps_too = false;
+    }
+    if (std::max(m, n) > 4096) return false;   // a row's mask words must fit one wave (64 words)
+    Arena& ar = *h->arena;
+    MaskOp mo;
+    mo.nf = n;
+    mo.nc = m;
+    mo.nwf = cdiv(m, 64);
+    mo.nwc = cdiv(n, 64);
+    unsigned long long* fb = ar.alloc<unsigned long long>((size_t)n * mo.nwf);
+    unsigned long long* cb = ar.alloc<unsigned long long>((size_t)m * mo.nwc);
+    double* alpha = ar.alloc<double>((size_t)n);
+    double* beta = ar.alloc<double>((size_t)m);
+    double* diag = ar.alloc<double>((size_t)lv.N);
+    int* bad = ctx->scratch->alloc<int>(1);
+    IPD_HIP(hipMemsetAsync(fb, 0, sizeof(unsigned long long) * (size_t)n * mo.nwf, ctx->stream));
+    IPD_HIP(hipMemsetAsync(cb, 0, sizeof(unsigned long long) * (size_t)m * mo.nwc, ctx->stream));
+    IPD_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(k_maskop_scales, dim3(cdiv(lv.N, 256)), dim3(256), 0, ctx->stream, n, m, p_dev,
+                       q_dev, 1.0 / tk, alpha, beta);
+    hipLaunchKernelGGL(k_maskop_build, dim3(std::max(1, std::min(cdiv(lv.N, 4), 2048))), dim3(256), 0,
+                       ctx->stream, lv.N, n, lv.A.rp, lv.A.ci, lv.A.va, (const double*)alpha,
+                       (const double*)beta, mo.nwf, mo.nwc, fb, cb, diag, bad);
+    IPD_KERNEL_CHECK();
+    if (ctx->fetch1(bad) != 0) return false;
+    mo.fbits = fb;
+    mo.cbits = cb;
+    mo.alpha = alpha;
+    mo.beta = beta;
+    mo.diag = diag;
+    if (for_resident && resident_mask_transfers_fit(in, facts)) {
+        if (double* rho = mask_transfer_rho(h, mo, bad)) {
+            ResDesc& D = R.desc;
+            D.xm = 1;
+            D.xm_nwf = mo.nwf;
+            D.xm_nwc = mo.nwc;
+            D.xm_fbits = fb;
+            D.xm_cbits = cb;
+            D.xm_beta = beta;
+            D.xm_rho = rho;
+        }
+    }
+    {
+        const ResidentPlan p = plan_resident_big(in, sw, facts);
+        if (p.kind == RESIDENT_BIG) {
+            const LevelDev d2 = resident_rows(h, st, p, 2);
+            const double* rho = R.desc.xm ? R.desc.xm_rho : mask_transfer_rho(h, mo, bad);
+            if (rho) {
+                ResBigDesc B = big_desc(h, st, mo, d2, rho);
+                B.ranks = p.ranks;
+                B.gran = alloc_resident_block(h, R, B, (size_t)p.ranks * 2 * RB_GRAN * 16, false);
+                B.tin = B.tout = nullptr;   // (no tail workgroup)
+                B.tctl = nullptr;
+                commit_mask_form(h, R, p, B, sw);
+            }
+        }
+    }
+    if (deep_cand && !R.mask_form()) {
+        const ResidentPlan p = plan_resident_deep(in, sw, facts);
+        if (p.kind == RESIDENT_DEEP) {
+            const LevelDev d2 = resident_rows(h, st, p, 2);
+            if (const double* rho = mask_transfer_rho(h, mo, bad)) {
+                const BPolyDev pb = pack_resident_poly(h, st, 3, RB_P3_SEG, RB_P3_LD);
+                BPolyDev pb4;
+                if (p.poly4) pb4 = pack_resident_poly(h, st, 4, RB_P4_SEG, RB_P4_LD);
+                ResBigDesc B = big_desc(h, st, mo, d2, rho);
+                B.N3 = h->L[3].A.nr;
+                B.N4 = h->L[4].A.nr;
+                B.Pt3 = res_csr(h->L[3].Pt);
+                B.P3d = res_csr(h->L[3].P);
+                B.p3rows = pb.M;
+                B.p3w = pb.W;
+                B.N5 = p.poly4 ? h->L[5].A.nr : 0;
+                B.p4rows = pb4.M;
+                B.p4w = pb4.W;
+                B.gran = alloc_resident_block(h, R, B, (size_t)2 * RB_GRAN * 16, true);
+                B.sub = resident_image(st, p.tail_image);
+                commit_mask_form(h, R, p, B, sw);
+            }
+        }
+    }
+    if (!sweeps_too) return R.desc.xm != 0 || R.mask_form();
+    st->maskop = mo;
+    st->mask_ok = true;
+    // captured graphs (if any) were recorded with the CSR sweeps
+    for (auto& g : st->gexec)
+        if (g) {
+            (void)hipGraphExecDestroy(g);
+            g = nullptr;
+        }
+    return true;
+}
+
+// Level 2 of the level-resident kernel in polynomial form, composed over a whole visit (ResDesc::p2rows):
+// three levels with a one-row tail, V cycle, 16-entry slices -- the metric's workload.  Packing costs five
+// dense products of N2^3 (0.5 ms at N2 = 1024) against 18 us saved per cycle: it pays where many cycles run
+// on one hierarchy (bench.py's fixed-hierarchy throughput), never in a solve of such a system, which takes one
+// or two cycles -- so the solvers do not attach it themselves.
+static bool amg_attach_poly2(ipd_amg* h) {
+    ipd_ctx* ctx = h->ctx;
+    CycleState* st = state_of(h);
+    if (!st || !st->res.ok) return false;
+    ResidentState& R = st->res;
+    if (!resident_takes_poly2(R.plan, resident_inputs(h, st, level_shapes(h, st)))) return false;
+    const int N2 = h->L[2].A.nr;
+    const int seg = RES_NMAX / 2, ld = 2 * seg + 128;
+    const BPolyDev pb = pack_bpoly(ctx, h, st, 2, h->opts.isnsp, 0, true, seg, ld);
+    const int Np = pb.e.Np, nT = (Np / 16) * (Np / 16);
+    // (IPD_OPTIN_LDS is not needed: the tiles use static LDS only)
+    hipLaunchKernelGGL(k_bpoly_compose, dim3((unsigned)(nT + (N2 + 3) / 4)), dim3(256), 0, ctx->stream, pb.e, nT);
+    IPD_KERNEL_CHECK();
+    R.desc.p2rows = pb.M;
+    R.desc.p2w = pb.W;
+    R.desc.p2seg = seg;
+    R.desc.p2ld = ld;
+    st->poly2_op = rows_op(pb);
+    R.plan.key.poly2 = true;
+    R.capacity = -1;   // (another instantiation: asked again before its first launch)
+    st->level_forms.resize((size_t)h->J + 1, 0);
+    st->level_forms[2] |= 128;
+    ctx->sync();   // the pack's scratch operands die with the call scope
+    return true;
+}
+
+extern "C" int ipd_amg_attach_level2_poly(ipd_amg* h, int32_t* attached) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h, IPD_E_ARG, "NULL handle");
+        h->ctx->set_device();
+        CallScope scope(h->ctx);
+        const bool ok = amg_attach_poly2(h);
+        if (attached) *attached = ok ? 1 : 0;
+    });
+}
+
+static int attach_mask(ipd_amg* h, const double* p_dev, const double* q_dev, int64_t m, int64_t n, double tk,
+                       int32_t* attached, bool transfers_only) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && p_dev && q_dev && m > 0 && n > 0, IPD_E_ARG, "bad argument");
+        h->ctx->set_device();
+        CallScope scope(h->ctx);
+        const bool ok = amg_attach_maskop(h, p_dev, q_dev, (int)m, (int)n, tk, false, transfers_only);
+        if (attached) *attached = ok ? 1 : 0;
+    });
+}
+extern "C" int ipd_amg_attach_mask_operator(ipd_amg* h, const double* p_dev, const double* q_dev,
+                                            int64_t m, int64_t n, double tk, int32_t* attached) {
+    return attach_mask(h, p_dev, q_dev, m, n, tk, attached, false);
+}
+extern "C" int ipd_amg_attach_mask_transfers(ipd_amg* h, const double* p_dev, const double* q_dev,
+                                             int64_t m, int64_t n, double tk, int32_t* attached) {
+    return attach_mask(h, p_dev, q_dev, m, n, tk, attached, true);
+}
+
+// ---- introspection -----------------------------------------------------------------------------
+// Mode 2 only: how many levels the resident workgroups keep in registers (2 or 3) and the level
+// the tail is rooted at (3: the local tail of a three-level hierarchy or the remote tail workgroup's
+// sub-cycle root; 4: remote tail below a resident level 3); zeros otherwise.
+extern "C" int ipd_amg_resident_levels(const ipd_amg* h, int32_t* levels, int32_t* tail_root) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h, IPD_E_ARG, "NULL handle");
+        const CycleState* st = h->cyc.get();
+        const bool on = st && st->res.ok;
+        if (levels) *levels = on ? st->res.plan.levels : 0;
+        if (tail_root) *tail_root = on ? st->res.plan.tail_root : 0;
+    });
+}
+
+// Which resident kernel this hierarchy's solve phase launches (mode 2 of ipd_amg_solve_mode) -- the
+// instantiation's name as it appears in a rocprofv3 kernel trace, "" otherwise -- and what its last
+// launch did: chip-wide hand-offs (tagged-granule exchanges, plus visits of the remote tail) and loop
+// bodies.  bench.py derives hand-offs per cycle from these instead of re-deriving the kernel from sizes.
+extern "C" int ipd_amg_resident_kernel(const ipd_amg* h, char* name, int32_t cap, int64_t* handoffs,
+                                       int32_t* cycles, int32_t* mask_transfers) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && name && cap > 0, IPD_E_ARG, "bad argument");
+        const CycleState* st = h->cyc.get();
+        const ResidentKernel* kern = st && st->res.ok ? resident_kernel(st->res.plan.key) : nullptr;
+        std::snprintf(name, (size_t)cap, "%s", kern ? kern->name : "");
+        if (handoffs) *handoffs = st ? st->res.last_handoffs : 0;
+        if (cycles) *cycles = st ? st->res.last_cycles : 0;
+        // level 1 <-> 2 transfers from the bit mask: always in the mask-form kernel, ResDesc::xm otherwise
+        if (mask_transfers) *mask_transfers = (st && st->res.ok && (st->res.mask_form() || st->res.desc.xm)) ? 1 : 0;
+    });
+}
+
+extern "C" int ipd_amg_solve_mode(const ipd_amg* h, int32_t* mode, int32_t* grid, int32_t* timeouts) {
+    if (!h || !mode) return IPD_E_ARG;
+    const CycleState* st = h->cyc.get();
+    if (!st) return IPD_E_ARG;
+    *mode = st->small_ok ? 1 : (st->res.ok ? 2 : 0);
+    if (grid) *grid = st->res.ok ? st->res.plan.grid() : (st->small_ok ? 1 : 0);
+    if (timeouts) *timeouts = st->res.timeouts;
+    return IPD_OK;
+}
+
+extern "C" int ipd_amg_bench_resident(ipd_amg* h, const double* b_dev, double* x_dev, int cycles,
+                                      double* total_ms, int64_t stamps[10]) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && b_dev && x_dev && cycles > 0 && total_ms && stamps, IPD_E_ARG, "bad argument");
+        ipd_ctx* ctx = h->ctx;
+        CallScope scope(ctx);
+        CycleState* st = state_of(h);
+        IPD_REQUIRE(st && st->res.ok, IPD_E_ARG, "hierarchy does not run in resident mode");
+        const int N = h->L[1].A.nr;
+        long long* dbg = ctx->scratch->alloc<long long>(16);
+        IPD_HIP(hipMemsetAsync(dbg, 0, 128, ctx->stream));
+        IPD_HIP(hipMemcpyAsync(h->x, x_dev, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
+                               ctx->stream));
+        float msf = 0.f;
+        IPD_REQUIRE(run_resident(h, st, b_dev, h->x, cycles, nullptr, &msf, dbg), IPD_E_HIP,
+                    "resident kernel gave up (not every workgroup was resident)");
+        IPD_HIP(hipMemcpyAsync(x_dev, h->x, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
+                               ctx->stream));
+        long long hs[10];
+        ctx->fetch(dbg, hs, 10);
+        for (int i = 0; i < 10; ++i) stamps[i] = hs[i];
+        *total_ms = msf;
+    });
+}

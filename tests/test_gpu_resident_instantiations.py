@@ -1,5 +1,5 @@
-"""Every instantiation of the level-resident kernels that run_resident can launch, each reached on purpose and
-checked against the oracle.
+"""Every instantiation of the level-resident kernels that run_resident (csrc/ipd_resident_host.h) can launch, each
+reached on purpose and checked against the oracle.
 
 The row width is a template parameter, so each width is separate machine code: k_resident<KE1,KE2,KE3,POLY2>
 (csrc/ipd_resident.h) in ten forms and k_resident_big<KE2,RPW,DEEP> (csrc/ipd_resident_big.h) in four.  A lane
@@ -90,55 +90,18 @@ def _src(name):
 # ---------------------------------------------------------------------------------------------------------------
 # inventory (CPU): the instantiations run_resident launches in the normal build
 # ---------------------------------------------------------------------------------------------------------------
-def run_resident_source():
-    text = _src("ipd_cycle_host.h")
-    start = text.index("static bool run_resident(")
-    return text[start:text.index("\n}\n", start)]
-
-
-def normal_build_lines(body):
-    """The lines of `body` a build without any IPD_DEV_ONLY_* macro compiles (the development-only branches of
-    run_resident are dropped; any other conditional there is an error)."""
-    out, stack = [], []                     # stack entries: [parent active, this branch active, a branch taken]
-    active = True
-    for line in body.splitlines():
-        t = line.strip()
-        m = re.match(r"#\s*(ifdef|if|elif|else|endif)\b(.*)", t)
-        if not m:
-            if active and not t.startswith("#"):
-                out.append(line)
-            continue
-        kw, cond = m.group(1), m.group(2).split("//")[0].strip()
-        if kw in ("ifdef", "if", "elif"):
-            assert re.fullmatch(r"(defined\()?IPD_DEV_ONLY_\w+\)?", cond), ("unexpected conditional", t)
-        if kw in ("ifdef", "if"):
-            stack.append([active, False, False])
-        elif kw == "elif":
-            stack[-1][1] = False
-        elif kw == "else":
-            stack[-1][1] = not stack[-1][2]
-            stack[-1][2] = True
-        else:
-            stack.pop()
-        active = (stack[-1][0] and stack[-1][1]) if stack else True
-    assert not stack
-    return out
-
-
 def launched_instantiations():
-    """Kernel names, as ipd_amg_resident_kernel spells them, of every launch in run_resident's normal build."""
-    names = []
-    for line in normal_build_lines(run_resident_source()):
-        for ke, ke3, p2 in re.findall(r"IPD_RES_LAUNCH4\((\d+),\s*(\d+),\s*(true|false)\)", line):
-            names.append("k_resident<%s,%s,%s%s>" % (ke, ke, ke3, ",true" if p2 == "true" else ""))
-        for ke, ke3 in re.findall(r"IPD_RES_LAUNCH\((\d+),\s*(\d+)\)", line):
-            names.append("k_resident<%s,%s,%s>" % (ke, ke, ke3))
-        for ke2, rpw, deep in re.findall(r"IPD_RESB_LAUNCH\((\d+),\s*(\d+),\s*(true|false)\)", line):
-            names.append("k_resident_big<%s,%s,%s>" % (ke2, rpw, deep))
-    return names
+    """Kernel names, as ipd_amg_resident_kernel spells them, of every row of the table run_resident launches from
+    (RESIDENT_KERNELS, csrc/ipd_resident_host.h) in the normal build."""
+    from tests.test_resident_plan import resident_table
+    rows = resident_table()
+    for name, from_key, from_kernel in rows:           # a row's name, key and kernel say the same
+        assert name == from_key == from_kernel, (name, from_key, from_kernel)
+    return [r[0] for r in rows]
 
 
-# the width rules, mirrored from the sources (test_width_rules_match_the_sources pins them)
+# the width rules, mirrored from the planner (csrc/ipd_resident_plan.h): tests/test_resident_plan.py runs the planner
+# against them for every stride and checks its cut-offs
 def ke_of(smax):
     """plan_resident: ke = 4; while (64 * ke < smax) ke <<= 1;"""
     ke = 4
@@ -302,26 +265,10 @@ def test_inventory_matches_the_case_table():
     launched = launched_instantiations()
     assert len(launched) == len(set(launched)) == 14, launched
     assert set(launched) == set(CASES), sorted(set(launched) ^ set(CASES))
-    host = _src("ipd_cycle_host.h")
-    # the spelling of ipd_amg_resident_kernel, which the GPU cases compare with
-    assert 'std::snprintf(buf, sizeof buf, "k_resident_big<%d,%d,%s>", st->resb_ke2, st->resb_deep ? 2 : 1,' in host
-    assert ('st->res_poly2 ? "k_resident<%d,%d,%d,true>" : "k_resident<%d,%d,%d>",\n'
-            '                              st->res_ke, st->res_ke, st->res_ke3);') in host
 
 
 def test_width_rules_match_the_sources():
-    host = _src("ipd_cycle_host.h")
-    plan = host[host.index("static void plan_resident("):host.index("static bool run_resident(")]
-    assert "    int ke = 4;\n    while (64 * ke < smax) ke <<= 1;\n    if (ke > 16) return;" in plan
-    assert "if (three && ke > 8) return;" in plan
-    assert plan.count("ke3 = S3 <= 256 ? 4 : 8;") == 2 and "if (poly3) ke3 = 1;" in plan
-    assert "const int smax = std::max(d1.S, d2.S);" in plan
-    assert "d1.S = (st->run[1].maxoff + 3) / 4 * 4;" in plan and "d2.S = (st->run[2].maxoff + 3) / 4 * 4;" in plan
-    assert "S3 > 0 && S3 <= 512 && Nt <= BT" in plan and "std::max(d1.S, d2.S) <= 512" in plan
-    assert "st->resb_ke2 = d2.S <= 64 * 16 ? 16 : 32;" in host
-    assert "st->resb_ke2 = d2.S <= 64 * 4 ? 4 : 8;" in host
-    assert "if (rho_ok && d2.S > 0 && d2.S <= 64 * 32) {" in host
-    assert "S2 > 0 && S2 <= 64 * 8" in host
+    # (the host's rules: test_resident_plan.py, test_widths_match_the_mirrors_for_every_stride)
     res = _src("ipd_resident.h")
     assert "const int e = lane + 64 * q;\n        const bool ok = valid && e < L.S;" in res
     assert [ke_of(s) for s in (1, 256, 257, 512, 513, 1024, 1025)] == [4, 4, 8, 8, 16, 16, 32]
