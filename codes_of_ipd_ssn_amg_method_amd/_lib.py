@@ -123,6 +123,8 @@ EXPORTS = [
     "ipd_aty", "ipd_asat", "ipd_inv_aat", "ipd_inv_hht", "ipd_strength", "ipd_cf_split",
     "ipd_mis_set", "ipd_transfer", "ipd_amg_setup", "ipd_amg_destroy", "ipd_amg_num_levels",
     "ipd_amg_level_dims", "ipd_amg_get_A", "ipd_amg_get_P", "ipd_amg_get_cmask", "ipd_amg_solve", "ipd_amg_solve_multi", "ipd_amg_solve_multi_dev", "ipd_amg_pcg", "ipd_amg_pcg_dev",
+    "ipd_amg_pcg_planned", "ipd_amg_pcg_planned_dev", "ipd_amg_pcg_mode",
+    "ipd_hybrid_amg_pcg", "ipd_hybrid_amg_pcg_dev", "ipd_amg4pot_pcg", "ipd_apd_set_krylov",
     "ipd_amg_pcg_multi", "ipd_amg_pcg_multi_dev",
     "ipd_amg_vcycle", "ipd_amg_wcycle", "ipd_class_amg", "ipd_pcg", "ipd_components",
     "ipd_hybrid_amg", "ipd_amg4pot", "ipd_dmalloc", "ipd_dfree", "ipd_h2d", "ipd_d2h",

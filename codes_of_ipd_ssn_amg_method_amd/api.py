@@ -30,7 +30,7 @@ __all__ = [
     "AMG4POT", "MatlabRand", "IpdError", "amg_options", "APDWorkspace", "warmup_class1",
     "warmup_class2", "APD_SsN_Class1", "APD_SsN_Class2", "twogrid_bigph", "twogrid", "Hybrid_twogrid",
     "aug_PCG", "PCG4POT", "load_input", "sparse_multiply", "spd_solve", "AMG_PCG",
-    "Class_AMG_multi", "AMG_PCG_multi",
+    "Class_AMG_multi", "AMG_PCG_multi", "Hybrid_AMG_PCG",
 ]
 
 
@@ -333,10 +333,13 @@ class AMGHierarchy:
         return (X, it.astype(np.int64), rel, [rel_resk[:n[j], j].copy() for j in range(k)],
                 [rhok[:n[j], j].copy() for j in range(k)])
 
-    def pcg(self, e, pcg_options: dict | None = None):
+    def pcg(self, e, pcg_options: dict | None = None, planned: bool = False):
         """``[d,it,res,resk] = AMG_PCG(h,e,pcg_options)`` (``ipd_amg_pcg``): PCG.m's loop on level 1
         preconditioned by one cycle of this hierarchy, flexible beta.  ``pcg_options``: ``retol``,
-        ``maxit``, ``guess``; ``precd`` must stay unset.  ``resk`` has ``maxit`` slots like ``PCG``."""
+        ``maxit``, ``guess``; ``precd`` must stay unset.  ``resk`` has ``maxit`` slots like ``PCG``.
+        ``planned=True`` (``ipd_amg_pcg_planned``): the whole loop as ONE single-workgroup launch where
+        the hierarchy is planned for the single-workgroup solve and ``maxit`` <= 1000 (the default
+        1e4 is beyond it), the same launches elsewhere; ``pcg_mode`` tells which it was."""
         e = f64(e)
         o = _pcg_opts_struct(pcg_options)
         g = None
@@ -347,9 +350,18 @@ class AMGHierarchy:
         it = c_int64()
         res = c_double()
         resk = np.zeros(maxit)
-        check(lib.ipd_amg_pcg(self.handle, dptr(e), dptr(g) if g is not None else None, byref(o), dptr(d),
-                              byref(it), byref(res), dptr(resk)))
+        fn = lib.ipd_amg_pcg_planned if planned else lib.ipd_amg_pcg
+        check(fn(self.handle, dptr(e), dptr(g) if g is not None else None, byref(o), dptr(d),
+                 byref(it), byref(res), dptr(resk)))
         return d, int(it.value), float(res.value), resk
+
+    @property
+    def pcg_mode(self) -> int:
+        """How the most recent ``pcg`` call on this hierarchy ran (``ipd_amg_pcg_mode``): -1 none yet,
+        0 as launches, 1 as one single-workgroup launch."""
+        mode = c_int32(-1)
+        check(lib.ipd_amg_pcg_mode(self.handle, byref(mode)))
+        return int(mode.value)
 
     def pcg_multi(self, E, pcg_options: dict | None = None):
         """Several right-hand sides (``ipd_amg_pcg_multi``): column j of ``E`` (N x k) through ``pcg``'s
@@ -448,12 +460,14 @@ def Class_AMG_multi(A, B, amg_options: dict | None = None, rng: MatlabRand | Non
         h.close()
 
 
-def AMG_PCG(A, b, amg_options: dict, pcg_options: dict | None = None, rng: MatlabRand | None = None):
+def AMG_PCG(A, b, amg_options: dict, pcg_options: dict | None = None, rng: MatlabRand | None = None,
+            planned: bool = False):
     """``[d,it,res,resk] = AMG_PCG(A,b,amg_options,pcg_options)``: Class_AMG's setup, then
-    conjugate gradients preconditioned by one cycle of the hierarchy (``AMGHierarchy.pcg``)."""
+    conjugate gradients preconditioned by one cycle of the hierarchy (``AMGHierarchy.pcg``;
+    ``planned``: as one launch where the hierarchy allows it)."""
     h = AMGHierarchy(A, amg_options, rng)
     try:
-        return h.pcg(b, pcg_options)
+        return h.pcg(b, pcg_options, planned)
     finally:
         h.close()
 
@@ -558,6 +572,25 @@ def Hybrid_AMG(prob_data: dict, amg_options: dict, rng: MatlabRand | None = None
     return zeta, int(it.value), float(res.value), info
 
 
+def Hybrid_AMG_PCG(prob_data: dict, amg_options: dict, rng: MatlabRand | None = None):
+    """``[zeta,itamg,resamg,info] = Hybrid_AMG_PCG(prob_data,amg_options)`` (``ipd_hybrid_amg_pcg``):
+    ``Hybrid_AMG`` with AMG-preconditioned CG (``AMGHierarchy.pcg(planned=True)``) in place of every
+    ``Class_AMG`` solve phase -- same rescaling, components, random guesses (the ``rand`` stream
+    advances as in ``Hybrid_AMG``) and small-block direct solves; ``retol`` / ``maxit`` are
+    ``amg_options``'; ``itamg`` / ``resamg`` are the largest PCG count / ``res`` over the large
+    components."""
+    rng = rng or MatlabRand()
+    s, keep, m, n = _prob_struct(prob_data, False)
+    o = _opts_struct(amg_options)
+    zeta = np.empty(m + n)
+    it = c_int32()
+    res = c_double()
+    info = np.zeros(2, np.int64)
+    check(lib.ipd_hybrid_amg_pcg(_h(), byref(s), byref(o), rng.handle, dptr(zeta), byref(it),
+                                 byref(res), iptr(info)))
+    return zeta, int(it.value), float(res.value), info
+
+
 def Hybrid_twogrid(prob_data: dict, amg_options: dict, rng: MatlabRand | None = None):
     """``[zeta,itamg,resamg,info] = Hybrid_twogrid(prob_data,amg_options)``
     (``Hybrid_twogrid.m:1``)."""
@@ -659,9 +692,10 @@ def PCG4POT(prob_data: dict, pcg_options: dict | None = None):
 
 def AMG4POT(prob_data: dict, amg_options: dict, str_: str = "amg", rng: MatlabRand | None = None):
     """``[zeta,itamg,resamg,info] = AMG4POT(prob_data,amg_options,str)``
-    (``Class2/AMG4POT.m:1``); ``str`` = ``'amg'`` or ``'twogrid'`` (``:44-51``)."""
-    if str_ not in ("amg", "twogrid"):
-        raise ValueError("AMG4POT: str must be 'amg' or 'twogrid'")
+    (``Class2/AMG4POT.m:1``); ``str`` = ``'amg'`` or ``'twogrid'`` (``:44-51``), or ``'amg_pcg'``: both
+    ``Hybrid_AMG`` calls as ``Hybrid_AMG_PCG``."""
+    if str_ not in ("amg", "twogrid", "amg_pcg"):
+        raise ValueError("AMG4POT: str must be 'amg', 'twogrid' or 'amg_pcg'")
     rng = rng or MatlabRand()
     s, keep, m, n = _prob_struct(prob_data, True)
     o = _opts_struct(amg_options)
@@ -669,7 +703,7 @@ def AMG4POT(prob_data: dict, amg_options: dict, str_: str = "amg", rng: MatlabRa
     it = c_int32()
     res = c_double()
     info = np.zeros(2, np.int64)
-    fn = lib.ipd_amg4pot if str_ == "amg" else lib.ipd_amg4pot_twogrid
+    fn = {"amg": lib.ipd_amg4pot, "twogrid": lib.ipd_amg4pot_twogrid, "amg_pcg": lib.ipd_amg4pot_pcg}[str_]
     check(fn(_h(), byref(s), byref(o), rng.handle, dptr(zeta), byref(it), byref(res), iptr(info)))
     return zeta, int(it.value), float(res.value), info
 
@@ -777,11 +811,14 @@ class APDWorkspace:
         return o
 
     def run(self, amg_options: dict, rng: MatlabRand | None = None, iters: int | None = None,
-            **opts) -> dict:
+            krylov: bool = False, **opts) -> dict:
+        """``krylov=True``: ``inner_solver = 4`` runs AMG-preconditioned CG behind ``Hybrid_AMG`` /
+        ``AMG4POT`` (``ipd_apd_set_krylov``); the AMG counters then count PCG iterations."""
         o = self.options(**opts)
         ao = _opts_struct(amg_options)
         rng = rng or MatlabRand()
         res = L.ipd_apd_result()
+        check(lib.ipd_apd_set_krylov(self.handle, c_int32(1 if krylov else 0)))
         check(lib.ipd_apd_run(self.handle, byref(o), byref(ao), rng.handle,
                               c_int32(o.maxit if iters is None else int(iters)), byref(res)))
         return dict(converged=bool(res.converged), k=res.k, fval=res.fval, kkt=list(res.kkt),
@@ -864,11 +901,11 @@ def warmup_class2(c, r, l, p, q, mu, phi, res=None, maxit=None):
         ws.close()
 
 
-def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts) -> dict:
+def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool = False) -> dict:
     try:
         if warm is not None:
             ws.warmup(*warm)
-        out = ws.run(amg_opts, rng, **opts)
+        out = ws.run(amg_opts, rng, krylov=krylov, **opts)
         u, v, lam, bk = ws.state()
         out.update(ws.history())
         out.update(uk=u, vk=v, lk=lam, bk=bk, records=ws.records(), reuse_stats=ws.reuse_stats())
@@ -879,23 +916,25 @@ def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts) -> dict:
 
 
 def APD_SsN_Class1(c, r, l, p, q, gama=np.inf, prob=2, rng: MatlabRand | None = None,
-                   amg_opts: dict | None = None, **opts) -> dict:
+                   amg_opts: dict | None = None, krylov: bool = False, **opts) -> dict:
     """The script ``Class1/APD_SsN_Class1.m`` with ``inner_solver = 4`` on the workspace it
-    loads (``:27``); returns the variables it leaves behind.  Warm start as ``:53-59``."""
+    loads (``:27``); returns the variables it leaves behind.  Warm start as ``:53-59``.
+    ``krylov``: see ``APDWorkspace.run``."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=30, theta=1 / 4, smoth=5, cycle="w",
                                 isnsp=1, inter=1, guess=None)                          # :87-88
     warm = (0.0, 100) if prob > 0 else (5e-2, np.inf)                                  # :53-58
     ws = APDWorkspace(1, c, r, l, p, q, gama=gama)
-    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts))
+    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov)
 
 
 def APD_SsN_Class2(c, r, l, p, q, mu, phi, rng: MatlabRand | None = None,
-                   amg_opts: dict | None = None, **opts) -> dict:
-    """The script ``Class2/APD_SsN_Class2.m`` with ``inner_solver = 4`` (AMG4POT 'amg')."""
+                   amg_opts: dict | None = None, krylov: bool = False, **opts) -> dict:
+    """The script ``Class2/APD_SsN_Class2.m`` with ``inner_solver = 4`` (AMG4POT 'amg', or
+    'amg_pcg' with ``krylov``)."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=40, theta=1 / 4, smoth=10, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     ws = APDWorkspace(2, c, r, l, p, q, mu=mu, phi=phi)
-    return _run_script(ws, amg_opts, rng, (0.0, 100), opts)
+    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov)
 
 
 def load_input(path: str) -> dict:

@@ -23,6 +23,11 @@ struct AmgOpts {
     // for a resident kernel of 200+ workgroups, the other runs as launches -- the planner then keeps the LDS
     // image the launches do best with (rooted at level 4) instead of the one the resident kernel does best with
     bool concurrent_pair = false;
+    // Hybrid_AMG / AMG4POT / the drivers with AMG-PCG as the inner solver (ipd_hybrid_amg_pcg,
+    // ipd_amg4pot_pcg, ipd_apd_set_krylov): every Class_AMG solve phase (Hybrid_AMG.m:41, :70) is
+    // amg_pcg_planned_dev from the same random guess with this retol and maxit; setup, components,
+    // small blocks and the rand stream are untouched.  Not an amg_options field.
+    bool krylov = false;
 };
 AmgOpts amg_fill_twogrid_defaults(const ipd_amg_opts* o);
 AmgOpts amg_fill_defaults(const ipd_amg_opts* o);
@@ -113,6 +118,25 @@ void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, dou
 // the hierarchy's own cycle and isnsp (IPD_E_ARG for a cycle other than 'v'/'w'), queue flushed.
 bool amg_level1_walk(ipd_amg* h, LevelDev* lv, int* staged, int* grid);
 void amg_apply_cycle(ipd_amg* h);
+// The whole AMG-PCG solve as ONE single-workgroup launch (k_pcg_small) on a hierarchy planned for the
+// single-workgroup solve (amg_pcg_small_ok: an IMG_SOLVE image, not sharded).  The launch is queued on
+// h->ctx's stream; the caller reads `out` back: out[0] = it, out[1] = res, out[2] = delta_0, resk at
+// out[4 .. 4 + maxit).  d holds the initial guess going in and the solution coming out.
+struct PcgSmallVecs {
+    const double* e = nullptr;
+    double* d = nullptr;
+    double* r = nullptr;
+    double* p = nullptr;
+    double* q = nullptr;
+    double* w_old = nullptr;
+    double* out = nullptr;     // 4 + maxit doubles
+};
+bool amg_pcg_small_ok(ipd_amg* h);
+void amg_pcg_small_launch(ipd_amg* h, const PcgSmallVecs& v, double tol, int maxit);
+// ipd_krylov.hip: [d,it,res,resk] = AMG_PCG(h,e,pcg_options) on device vectors, as one launch where the
+// hierarchy is planned for it and as launches elsewhere (resk: host, maxit slots or NULL)
+void amg_pcg_planned_dev(ipd_amg* h, const double* e, const double* guess, double tol, long long maxit,
+                         double* d_out, long long* it_out, double* res_out, double* resk);
 // What the block solve (ipd_block.hip) needs of a level's launch-path cycle: the CSR matrices with
 // their lanes per row and whole-level grids, the smoother data and the coarsest PCG's settings.
 struct BlockCsr {

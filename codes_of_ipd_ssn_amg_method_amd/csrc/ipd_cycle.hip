@@ -3166,6 +3166,156 @@ __global__ __launch_bounds__(BT) void k_solve_small(const SolveDesc* __restrict_
     }
 }
 
+// ---------------------------------------------------------------------------
+// whole AMG-PCG solve in ONE workgroup (ipd_amg_pcg_planned)
+// ---------------------------------------------------------------------------
+// The loop of ipd_krylov.hip (PCG.m:68-87, flexible beta) run by the workgroup that k_solve_small is, on
+// the same SolveDesc / LDS image, with M(r) = sol_cycle(c) from a zero guess: one launch and one
+// read-back per solve.  The PCG's own vectors (d, r, p, q, w_old) are the hierarchy's krylov_state
+// vectors in global memory (<= 8 KB each, L2-resident): the image's LDS budget is planned to the byte
+// for the stationary solve, and five more level-1 vectors would push level 1 of the larger mode-1
+// hierarchies out of it.  The PCG keeps its own r apart from the cycle's input L[1].lv.r.
+// Reductions are block_sum's (per-thread strided partials, wave sums, the waves summed in fixed
+// order, every thread reading the same total), so the loop test is uniform and the bits repeat.
+struct PcgSmallArgs {
+    const double* e;   // right-hand side
+    double* d;         // in: initial guess, out: solution
+    double* r;         // the PCG's residual
+    double* p;
+    double* q;
+    double* w_old;
+    double tol2;       // retol^2
+    int maxit;
+    double* out;       // out[0] = it, out[1] = res, out[2] = delta_0; resk at out[4 .. 4 + maxit)
+};
+
+// p = w + beta p (p not read for the first direction), w_old = w, q = A_1 p by the level-1 row walk
+// with the gather staged in c.xs; returns the thread's share of p'q.  k_kry_dir_spmv for one workgroup.
+__device__ __forceinline__ double pcgs_dir_spmv(SolveCtx& c, const PcgSmallArgs& a,
+                                                const double* __restrict__ w, double beta,
+                                                bool have_p) {
+    const LevelDev& lv = c.D->L[1].lv;
+    double* xs = c.xs;
+    const int tid = threadIdx.x;
+    const int N = lv.N, L = lv.L, gpb = BT / L;
+    const int g = tid / L, gl = tid - g * L;
+    const bool uni = L >= 64;
+    const int niter = (N + gpb - 1) / gpb;
+    const double* po = a.p;
+    auto xlds = [&](int j) { return xs[j]; };
+    int row = uniform_if(g, uni);
+    bool valid = row < N;
+    bool owner = valid && gl == 0;
+    RowCursor rc;
+    RowBatch bt;
+    row_open<false>(lv, row, valid, owner, gl, L, rc, bt);
+    if (have_p)
+        vec_pass(N, [&](int j) { return w[j] + beta * po[j]; }, [&](int j, double v) { xs[j] = v; });
+    else
+        vec_pass(N, [&](int j) { return w[j]; }, [&](int j, double v) { xs[j] = v; });
+    __syncthreads();   // every p_old is read before an owner stores its p_new
+    double acc = 0.0;
+    for (int it = 0; it < niter; ++it) {
+        if (it > 0) {
+            row = uniform_if(it * gpb + g, uni);
+            valid = row < N;
+            owner = valid && gl == 0;
+            row_open<false>(lv, row, valid, owner, gl, L, rc, bt);
+        }
+        double s = row_finish<false>(lv, rc, bt, gl, L, xlds);
+        double dummy;
+        s = reduce_rows(s, L, false, 0.0, &dummy, c.lds);
+        if (owner) {
+            const double xo = xs[row];
+            a.p[row] = xo;
+            a.w_old[row] = w[row];
+            a.q[row] = s;                                                     // PCG.m:77
+            acc += xo * s;
+        }
+    }
+    return acc;
+}
+
+template <bool CACHED>
+__global__ __launch_bounds__(BT) void k_pcg_small(const SolveDesc* __restrict__ D_global,
+                                                  const PcgSmallArgs a) {
+    __shared__ PhaseLds lds;
+    __shared__ double red[16];
+    __shared__ double blkpart[48 + SOLVE_ML + 1];
+    extern __shared__ __attribute__((aligned(16))) char dyn_raw[];
+    SolveDesc* LD = nullptr;
+    if (CACHED) LD = sol_load_image(D_global, dyn_raw);
+    SolveCtx c;
+    c.D = CACHED ? LD : D_global;
+    c.lds = &lds;
+    c.red = red;
+    c.xs = reinterpret_cast<double*>(dyn_raw);
+    c.swapmask = 0;
+    c.zeromask = 0;
+    c.part = blkpart;
+    c.sumr = blkpart + 48;
+    c.dbg = nullptr;
+    c.bm_lds = 0;
+    const SolveDesc* D = c.D;
+    const int N = D->L[1].lv.N;
+    double* const r1 = D->L[1].lv.r;   // the cycle's input
+    {   // r = e - A_1 d0 (PCG.m:68); the walk's copy of d0 goes to p, which the first direction overwrites
+        TopArgs ta;
+        ta.lv = D->L[1].lv;
+        ta.b = a.e;
+        ta.x = a.d;
+        ta.e = nullptr;
+        ta.xnew = a.p;
+        ta.row0 = 0;
+        ta.row1 = N;
+        ta.staged = 1;
+        phase_top<true, false>(ta, 0, 1, c.lds, c.xs);
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < N; i += BT) a.r[i] = r1[i];
+    __syncthreads();
+    sol_cycle(c);                                                             // :69
+    const double* w = sol_e(c, 1);
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < N; i += BT) acc += a.r[i] * w[i];
+    double delta = block_sum(acc, red);                                       // :70
+    const double delta0 = delta;
+    double beta = 0.0;
+    double res = sqrt(fabs(delta / delta0));
+    int it = 0;
+    while (it < a.maxit && delta > a.tol2 * delta0) {                         // :76
+        const double pq = block_sum(pcgs_dir_spmv(c, a, w, beta, it > 0), red);   // :77, :83
+        const double alpha = delta / pq;                                      // :78
+        for (int i = threadIdx.x; i < N; i += BT) {                           // :79
+            a.d[i] = a.d[i] + alpha * a.p[i];
+            const double ri = a.r[i] - alpha * a.q[i];
+            a.r[i] = ri;
+            r1[i] = ri;
+        }
+        __syncthreads();
+        sol_cycle(c);                                                         // :80
+        w = sol_e(c, 1);
+        double rw = 0.0, rwo = 0.0;
+        for (int i = threadIdx.x; i < N; i += BT) {
+            const double ri = a.r[i];
+            rw += ri * w[i];
+            rwo += ri * a.w_old[i];
+        }
+        const double dn = block_sum(rw, red);                                 // :81
+        const double s_wo = block_sum(rwo, red);
+        beta = (dn - s_wo) / delta;                                           // flexible :82
+        delta = dn;
+        ++it;                                                                 // :84
+        res = sqrt(fabs(dn / delta0));                                        // :85
+        if (threadIdx.x == 0) a.out[4 + it - 1] = res;
+    }
+    if (threadIdx.x == 0) {
+        a.out[0] = (double)it;
+        a.out[1] = res;                                                       // :88
+        a.out[2] = delta0;
+    }
+}
+
 // Sub-cycle rooted at level k_lds >= 2 of a hierarchy whose upper levels run as multi-workgroup
 // launches: ONE workgroup, every level from the root down cached in LDS.  r_{root} is read from
 // and the correction written to the global vectors the surrounding launches use.

@@ -1013,6 +1013,8 @@ void amg_prepare_levels(ipd_amg* h) {
     ipd_ctx* ctx = h->ctx;
     IPD_OPTIN_LDS(ctx, k_solve_small<true>, 156 * 1024);
     IPD_OPTIN_LDS(ctx, k_solve_small<false>, 156 * 1024);
+    IPD_OPTIN_LDS(ctx, k_pcg_small<true>, 156 * 1024);
+    IPD_OPTIN_LDS(ctx, k_pcg_small<false>, 156 * 1024);
     IPD_OPTIN_LDS(ctx, k_subcycle, 156 * 1024);
     for (const ImageSpec& s : plan.images) pack_image(ctx, h, st.get(), plan, s);
     if (plan.small_ok) {
@@ -1614,6 +1616,38 @@ void amg_apply_cycle(ipd_amg* h) {
     IPD_REQUIRE(cyc == 'v' || cyc == 'w', IPD_E_ARG, "AMG-PCG: the hierarchy's cycle must be 'v' or 'w'");
     amg_cycle(h, 1, h->opts.isnsp, cyc == 'w', false);   // what run_cycle_api(h, r, isnsp, 1, NULL, ..) runs
     flush_fused(h->ctx, state_of(h));
+}
+
+// ---- the whole AMG-PCG solve as one single-workgroup launch (ipd_amg_pcg_planned) ---------
+bool amg_pcg_small_ok(ipd_amg* h) {
+    CycleState* st = state_of(h);
+    IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
+    return st->small_ok && st->shard_ranks == 1;
+}
+
+void amg_pcg_small_launch(ipd_amg* h, const PcgSmallVecs& v, double tol, int maxit) {
+    ipd_ctx* ctx = h->ctx;
+    CycleState* st = state_of(h);
+    IPD_REQUIRE(st && st->small_ok && st->shard_ranks == 1, IPD_E_ARG,
+                "AMG-PCG: the hierarchy is not planned for the single-workgroup solve");
+    IPD_REQUIRE(maxit >= 0 && maxit <= PCG_SMALL_MAXIT, IPD_E_ARG, "AMG-PCG: maxit beyond the one-launch cap");
+    PcgSmallArgs a;
+    a.e = v.e;
+    a.d = v.d;
+    a.r = v.r;
+    a.p = v.p;
+    a.q = v.q;
+    a.w_old = v.w_old;
+    a.tol2 = tol * tol;
+    a.maxit = maxit;
+    a.out = v.out;
+    if (st->solve_cached)
+        hipLaunchKernelGGL(k_pcg_small<true>, dim3(1), dim3(BT), st->solve_lds, ctx->stream,
+                           (const SolveDesc*)st->d_solve, a);
+    else
+        hipLaunchKernelGGL(k_pcg_small<false>, dim3(1), dim3(BT), st->solve_lds, ctx->stream,
+                           (const SolveDesc*)st->d_solve, a);
+    IPD_KERNEL_CHECK();
 }
 
 extern "C" int ipd_amg_vcycle(ipd_amg* h, const double* r, int isnsp, int k, double* e) {

@@ -1008,6 +1008,7 @@ struct ipd_apd {
     int restarts = 0;
     // row f3: hierarchies of the previous Newton step and what its system was built from
     StepDonors step;
+    bool krylov = false;   // ipd_apd_set_krylov: inner_solver 4 runs AMG-PCG behind Hybrid_AMG / AMG4POT
     bool step_reuse = true, have_prev = false;
     double prev_bk1 = 0.0, prev_tk = 0.0;
     size_t s_words = 0;
@@ -1754,6 +1755,13 @@ extern "C" int ipd_apd_set_state(ipd_apd* h, const double* u, const double* v, c
     });
 }
 
+extern "C" int ipd_apd_set_krylov(ipd_apd* h, int32_t on) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h, IPD_E_ARG, "NULL handle");
+        h->krylov = on != 0;
+    });
+}
+
 extern "C" int ipd_apd_get_state(ipd_apd* h, double* u, double* v, double* lam, double* bk) {
     return ipd_guard([&] {
         IPD_REQUIRE(h, IPD_E_ARG, "NULL handle");
@@ -1780,7 +1788,8 @@ extern "C" int ipd_apd_run(ipd_apd* h, const ipd_apd_opts* o, const ipd_amg_opts
                     IPD_E_ARG, "bad driver options");
         IPD_REQUIRE(oo.inner_solver >= 1 && oo.inner_solver <= 5, IPD_E_ARG,
                     "inner_solver must be 1 (direct), 2 (PCG), 3 (aug_PCG / PCG4POT), 4 (AMG) or 5 (two-grid)");
-        const AmgOpts ao = oo.inner_solver == 5 ? amg_fill_twogrid_defaults(amg) : amg_fill_defaults(amg);
+        AmgOpts ao = oo.inner_solver == 5 ? amg_fill_twogrid_defaults(amg) : amg_fill_defaults(amg);
+        ao.krylov = h->krylov && oo.inner_solver == 4;
         h->ctx->set_device();
         ensure_kkt(h);
         for (int it = 0; it < iters && h->k < oo.maxit && !h->converged; ++it)

@@ -491,23 +491,33 @@ static std::function<void(int*, double*)> class_amg_prepare(
             donor = cache->donors[cache->next_donor++];
         own = std::shared_ptr<ipd_amg>(amg_setup(ctx, A, o, rng, donor), ipd_amg_destroy);
         h = own.get();
-        if (mh.p && o.bigph) amg_attach_maskop(h, mh.p, mh.q, mh.m, mh.n, mh.tk, true);
+        if (mh.p && o.bigph && !o.krylov) amg_attach_maskop(h, mh.p, mh.q, mh.m, mh.n, mh.tk, true);
         if (cache->record_donors) cache->recorded.push_back(own);
         if (cache->shared_count && own->donor) ++*cache->shared_count;
     } else {
         ProfScope ps(ctx, PROF_AMG_SETUP);
         std::unique_ptr<ipd_amg, void (*)(ipd_amg*)> fresh(amg_setup(ctx, A, o, rng), ipd_amg_destroy);
         h = fresh.get();
-        // matrix-free level 1 where it pays (policy in amg_attach_maskop)
-        if (mh.p && o.bigph) amg_attach_maskop(h, mh.p, mh.q, mh.m, mh.n, mh.tk, true);
+        // matrix-free level 1 where it pays (policy in amg_attach_maskop); not under AMG-PCG, whose
+        // level-1 product walks A_1's rows and whose cycle is then the CSR one throughout
+        if (mh.p && o.bigph && !o.krylov) amg_attach_maskop(h, mh.p, mh.q, mh.m, mh.n, mh.tk, true);
         own = std::shared_ptr<ipd_amg>(fresh.release(), ipd_amg_destroy);
     }
-    return [ctx, h, own, f, dg, u_out](int* it, double* rel_res) {
+    const bool krylov = o.krylov;
+    const double pcg_tol = o.retol;
+    const long long pcg_maxit = o.maxit;
+    return [ctx, h, own, f, dg, u_out, krylov, pcg_tol, pcg_maxit](int* it, double* rel_res) {
         int32_t its = 0;
         double rr = 0.0;
         {
             ProfScope ps(ctx, PROF_AMG_SOLVE);
-            amg_solve_dev(h, f, dg, u_out, &its, &rr, nullptr, nullptr);
+            if (krylov) {   // every piece of PCG state belongs to h: right for either of AMG4POT's two threads
+                long long itp = 0;
+                amg_pcg_planned_dev(h, f, dg, pcg_tol, pcg_maxit, u_out, &itp, &rr, nullptr);
+                its = (int32_t)itp;
+            } else {
+                amg_solve_dev(h, f, dg, u_out, &its, &rr, nullptr, nullptr);
+            }
         }
         *it = its;
         *rel_res = rr;
@@ -1275,17 +1285,26 @@ extern "C" int ipd_hybrid_amg(ipd_ctx* ctx, const ipd_prob* pd, const ipd_amg_op
                               double* zeta, int32_t* itamg, double* resamg, int64_t info[2]) {
     return hybrid_host(ctx, pd, amg_fill_defaults(o), rng, zeta, itamg, resamg, info);
 }
+static AmgOpts amg_fill_krylov(const ipd_amg_opts* o) {
+    AmgOpts ao = amg_fill_defaults(o);
+    ao.krylov = true;
+    return ao;
+}
+// Hybrid_AMG.m with every Class_AMG call replaced by setup + AMG-PCG from the same random guess
+extern "C" int ipd_hybrid_amg_pcg(ipd_ctx* ctx, const ipd_prob* pd, const ipd_amg_opts* o, ipd_rng* rng,
+                                  double* zeta, int32_t* itamg, double* resamg, int64_t info[2]) {
+    return hybrid_host(ctx, pd, amg_fill_krylov(o), rng, zeta, itamg, resamg, info);
+}
 extern "C" int ipd_hybrid_twogrid(ipd_ctx* ctx, const ipd_prob* pd, const ipd_amg_opts* o,
                                   ipd_rng* rng, double* zeta, int32_t* itamg, double* resamg,
                                   int64_t info[2]) {
     return hybrid_host(ctx, pd, amg_fill_twogrid_defaults(o), rng, zeta, itamg, resamg, info);
 }
 
-extern "C" int ipd_hybrid_amg_dev(ipd_ctx* ctx, const ipd_dmat* H0, const double* t_dev,
-                                  const double* p_dev, const double* q_dev, int64_t m, int64_t n,
-                                  double bk1, double tk, const double* z_dev,
-                                  const ipd_amg_opts* o, ipd_rng* rng, double* zeta_dev,
-                                  int32_t* itamg, double* resamg, int64_t info[2]) {
+static int hybrid_dev_entry(ipd_ctx* ctx, const ipd_dmat* H0, const double* t_dev, const double* p_dev,
+                            const double* q_dev, int64_t m, int64_t n, double bk1, double tk,
+                            const double* z_dev, const ipd_amg_opts* o, bool krylov, ipd_rng* rng,
+                            double* zeta_dev, int32_t* itamg, double* resamg, int64_t info[2]) {
     return ipd_guard([&] {
         IPD_REQUIRE(ctx && H0 && p_dev && q_dev && z_dev && zeta_dev, IPD_E_ARG, "NULL argument");
         IPD_REQUIRE(m > 0 && n > 0, IPD_E_ARG, "bad m/n");
@@ -1293,7 +1312,7 @@ extern "C" int ipd_hybrid_amg_dev(ipd_ctx* ctx, const ipd_dmat* H0, const double
         CompOrderScope order_scope(ctx);
         HybridOut ho;
         hybrid_amg_dev(ctx, H0->m, t_dev, p_dev, q_dev, (int)m, (int)n, bk1, tk, z_dev,
-                       amg_fill_defaults(o), rng, zeta_dev, &ho);
+                       krylov ? amg_fill_krylov(o) : amg_fill_defaults(o), rng, zeta_dev, &ho);
         ctx->sync();
         if (itamg) *itamg = ho.itamg;
         if (resamg) *resamg = ho.resamg;
@@ -1302,6 +1321,22 @@ extern "C" int ipd_hybrid_amg_dev(ipd_ctx* ctx, const ipd_dmat* H0, const double
             info[1] = ho.it_num;
         }
     });
+}
+extern "C" int ipd_hybrid_amg_dev(ipd_ctx* ctx, const ipd_dmat* H0, const double* t_dev,
+                                  const double* p_dev, const double* q_dev, int64_t m, int64_t n,
+                                  double bk1, double tk, const double* z_dev,
+                                  const ipd_amg_opts* o, ipd_rng* rng, double* zeta_dev,
+                                  int32_t* itamg, double* resamg, int64_t info[2]) {
+    return hybrid_dev_entry(ctx, H0, t_dev, p_dev, q_dev, m, n, bk1, tk, z_dev, o, false, rng, zeta_dev, itamg,
+                            resamg, info);
+}
+extern "C" int ipd_hybrid_amg_pcg_dev(ipd_ctx* ctx, const ipd_dmat* H0, const double* t_dev,
+                                      const double* p_dev, const double* q_dev, int64_t m, int64_t n,
+                                      double bk1, double tk, const double* z_dev,
+                                      const ipd_amg_opts* o, ipd_rng* rng, double* zeta_dev,
+                                      int32_t* itamg, double* resamg, int64_t info[2]) {
+    return hybrid_dev_entry(ctx, H0, t_dev, p_dev, q_dev, m, n, bk1, tk, z_dev, o, true, rng, zeta_dev, itamg,
+                            resamg, info);
 }
 
 static int amg4pot_host(ipd_ctx* ctx, const ipd_prob* pd, const AmgOpts& ao, ipd_rng* rng,
@@ -1347,6 +1382,11 @@ static int amg4pot_host(ipd_ctx* ctx, const ipd_prob* pd, const AmgOpts& ao, ipd
 extern "C" int ipd_amg4pot(ipd_ctx* ctx, const ipd_prob* pd, const ipd_amg_opts* o, ipd_rng* rng,
                            double* zeta, int32_t* itamg, double* resamg, int64_t info[2]) {
     return amg4pot_host(ctx, pd, amg_fill_defaults(o), rng, zeta, itamg, resamg, info);
+}
+// AMG4POT(prob_data, amg_options, 'amg_pcg'): both Hybrid_AMG calls with AMG-PCG as the inner solver
+extern "C" int ipd_amg4pot_pcg(ipd_ctx* ctx, const ipd_prob* pd, const ipd_amg_opts* o, ipd_rng* rng,
+                               double* zeta, int32_t* itamg, double* resamg, int64_t info[2]) {
+    return amg4pot_host(ctx, pd, amg_fill_krylov(o), rng, zeta, itamg, resamg, info);
 }
 // AMG4POT(prob_data, amg_options, 'twogrid')                      Class2/AMG4POT.m:48-51
 extern "C" int ipd_amg4pot_twogrid(ipd_ctx* ctx, const ipd_prob* pd, const ipd_amg_opts* o,

@@ -24,10 +24,13 @@
 // atomics, the same bits run to run.  Separate multiplies and adds (-ffp-contract=off).
 //
 // Always the launch-path cycle: the resident kernels (k_resident*, k_solve_small) run whole
-// Class_AMG loops and are not used here.
+// Class_AMG loops and are not used here.  ipd_amg_pcg_planned (below) is the form that runs the same
+// loop as ONE single-workgroup launch (k_pcg_small, ipd_cycle.hip) on a hierarchy planned for the
+// single-workgroup solve, and is this file's amg_pcg_dev on every other hierarchy.
 #include "ipd_amg_internal.h"
 
 #include <cmath>
+#include <cstring>
 
 #include "ipd_cycle_dev.h"
 #include "ipd_cycle_phases.h"
@@ -45,6 +48,8 @@ struct KrylovState {
     double* part1 = nullptr;     // G1 partials of p'q
     double* part3 = nullptr;     // 2 x G3 partials of r'w, r'w_old
     unsigned* cnt = nullptr;     // tickets of K1 and K3
+    double* out = nullptr;       // k_pcg_small's read-back: it, res, delta_0, -, resk[PCG_SMALL_MAXIT]
+    int last_mode = -1;          // how the most recent AMG-PCG call ran (ipd_amg_pcg_mode)
 };
 
 struct KryDirArgs {
@@ -207,6 +212,7 @@ static KrylovState* krylov_state(ipd_amg* h, int N, int G1, int G3) {
         ks->part1 = ar.alloc<double>((size_t)G1);
         ks->part3 = ar.alloc<double>(2 * (size_t)G3);
         ks->cnt = ar.alloc<unsigned>(2);
+        ks->out = ar.alloc<double>(4 + (size_t)PCG_SMALL_MAXIT);
         h->kry = ks;
     }
     IPD_REQUIRE(h->kry->N == N && h->kry->G1 == G1 && h->kry->G3 == G3, IPD_E_ARG,
@@ -249,6 +255,7 @@ static void amg_pcg_dev(ipd_amg* h, const double* e, const double* guess, double
     const int N = lv.N;
     const int G3 = std::max(1, std::min(ctx->num_cu, cdiv(N, BT)));
     KrylovState* ks = krylov_state(h, N, G1, G3);
+    ks->last_mode = 0;
     const size_t dyn = staged ? sizeof(double) * (size_t)N : 0;
     double* r1 = h->L[1].r;
     // tickets start at zero on every call (the last arriver resets its own, this covers a launch
@@ -311,6 +318,97 @@ static void amg_pcg_dev(ipd_amg* h, const double* e, const double* guess, double
     if (it_out) *it_out = it;
     if (res_out) *res_out = sc[SC_RES];                                           // :88
     ctx->sync();
+}
+
+// amg_pcg_dev's contract; on a hierarchy planned for the single-workgroup solve the whole loop is one
+// launch of k_pcg_small and one read-back, on every other hierarchy (and for maxit beyond
+// PCG_SMALL_MAXIT) it IS amg_pcg_dev.
+void amg_pcg_planned_dev(ipd_amg* h, const double* e, const double* guess, double tol, long long maxit,
+                         double* d_out, long long* it_out, double* res_out, double* resk) {
+    if (!amg_pcg_small_ok(h) || maxit > PCG_SMALL_MAXIT || maxit < 0) {
+        amg_pcg_dev(h, e, guess, tol, maxit, d_out, it_out, res_out, resk);
+        return;
+    }
+    ipd_ctx* ctx = h->ctx;
+    const int cyc = h->opts.cycle;
+    IPD_REQUIRE(cyc == 'v' || cyc == 'w', IPD_E_ARG,
+                "AMG-PCG: the hierarchy's cycle must be 'v' or 'w' (any other value applies no correction)");
+    LevelDev lv;
+    int staged = 0, G1 = 1;
+    IPD_REQUIRE(amg_level1_walk(h, &lv, &staged, &G1), IPD_E_UNSUPPORTED,
+                "AMG-PCG: level 1 is sharded over ranks");
+    const int N = lv.N;
+    const int G3 = std::max(1, std::min(ctx->num_cu, cdiv(N, BT)));
+    KrylovState* ks = krylov_state(h, N, G1, G3);   // the launch path's vectors: one state per hierarchy
+    ks->last_mode = 1;
+    if (guess)
+        IPD_HIP(hipMemcpyAsync(ks->d, guess, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, ctx->stream));
+    else
+        IPD_HIP(hipMemsetAsync(ks->d, 0, sizeof(double) * (size_t)N, ctx->stream));
+    PcgSmallVecs v;
+    v.e = e;
+    v.d = ks->d;
+    v.r = ks->r;
+    v.p = ks->p[0];
+    v.q = ks->q;
+    v.w_old = ks->w_old;
+    v.out = ks->out;
+    amg_pcg_small_launch(h, v, tol, (int)maxit);
+    std::vector<double> out(4 + (size_t)maxit);
+    ctx->fetch(ks->out, out.data(), out.size());
+    const long long it = (long long)out[0];
+    if (resk && it > 0) std::memcpy(resk, out.data() + 4, sizeof(double) * (size_t)it);
+    IPD_HIP(hipMemcpyAsync(d_out, ks->d, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, ctx->stream));
+    if (it_out) *it_out = it;
+    if (res_out) *res_out = out[1];
+    ctx->sync();
+}
+
+extern "C" int ipd_amg_pcg_mode(const ipd_amg* h, int32_t* mode) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && mode, IPD_E_ARG, "NULL argument");
+        *mode = h->kry ? h->kry->last_mode : -1;
+    });
+}
+
+extern "C" int ipd_amg_pcg_planned_dev(ipd_amg* h, const double* e_dev, const double* guess_dev,
+                                       const ipd_pcg_opts* o, double* d_dev, int64_t* it, double* res,
+                                       double* resk) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && e_dev && d_dev, IPD_E_ARG, "NULL argument");
+        double tol;
+        long long maxit;
+        pcg_opts_of(o, &tol, &maxit);
+        CallScope scope(h->ctx);
+        long long its = 0;
+        amg_pcg_planned_dev(h, e_dev, guess_dev, tol, maxit, d_dev, &its, res, resk);
+        if (it) *it = its;
+    });
+}
+
+extern "C" int ipd_amg_pcg_planned(ipd_amg* h, const double* e, const double* guess, const ipd_pcg_opts* o,
+                                   double* d, int64_t* it, double* res, double* resk) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && e && d, IPD_E_ARG, "NULL argument");
+        double tol;
+        long long maxit;
+        pcg_opts_of(o, &tol, &maxit);
+        ipd_ctx* ctx = h->ctx;
+        CallScope scope(ctx);
+        const size_t N = (size_t)h->L[1].A.nr;
+        double* de = ctx->scratch->alloc<double>(N);
+        double* dd = ctx->scratch->alloc<double>(N);
+        double* dg = nullptr;
+        ctx->upload(de, e, N);
+        if (guess) {
+            dg = ctx->scratch->alloc<double>(N);
+            ctx->upload(dg, guess, N);
+        }
+        long long its = 0;
+        amg_pcg_planned_dev(h, de, dg, tol, maxit, dd, &its, res, resk);
+        if (it) *it = its;
+        ctx->fetch(dd, d, N);
+    });
 }
 
 extern "C" int ipd_amg_pcg_dev(ipd_amg* h, const double* e_dev, const double* guess_dev,

@@ -23,6 +23,10 @@ static constexpr int STAGE_MAX = 7680;   // vector entries staged in LDS (60 KiB
 // levels a single-workgroup image (SolveDesc) holds
 static constexpr int SOLVE_ML = 24;
 
+// most iterations the one-launch AMG-PCG (k_pcg_small) is asked for: at ~0.3 ms per iteration a launch
+// then cannot outlast ~0.3 s; a call with a larger maxit runs as launches
+static constexpr int PCG_SMALL_MAXIT = 1000;
+
 // dense thread-per-row levels (SolveLevel::blk_dense, ipd_cycle.hip): 24 values per lane: the register
 // budget of the tail (the resident kernels' worker paths set the kernels' allocation; the tail must stay
 // below it) -- the same storage serves the lane-map entries.

@@ -197,7 +197,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)it);
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(res);
         if (nlhs > 3) { plhs[3] = col((size_t)maxit); std::memcpy(mxGetDoubles(plhs[3]), rk.data(), sizeof(double) * (size_t)maxit); }
-    } else if (fn == "AMG_PCG") {                // [d,it,res,resk] = AMG_PCG(A,b,amg_options,pcg_options)
+    } else if (fn == "AMG_PCG") {                // [d,it,res,resk] = AMG_PCG(A,b,amg_options,pcg_options[,planned])
         ipd_csc A = csc_of(a[0]); ipd_amg_opts ao = opts_of(nrhs > 3 ? a[2] : nullptr);
         ipd_pcg_opts o; ipd_pcg_opts_init(&o); const mxArray* so = nrhs > 4 ? a[3] : nullptr;
         if (so) { o.retol = field(so, "retol", -1); o.maxit = (int64_t)field(so, "maxit", -1); o.precd = (int32_t)field(so, "precd", -1); }
@@ -205,7 +205,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         chk(ipd_amg_setup(g_ctx, &A, &ao, g_rng, &g_h));   // the gateway's hierarchy, as Class_AMG leaves it
         const int64_t maxit = o.maxit >= 0 ? o.maxit : 10000;
         plhs[0] = col((size_t)A.nrows); int64_t it = 0; double res = 0; std::vector<double> rk((size_t)maxit + 1);
-        chk(ipd_amg_pcg(g_h, mxGetDoubles(a[1]), opt_vec(so, "guess"), &o, mxGetDoubles(plhs[0]), &it, &res, rk.data()));
+        const bool planned = nrhs > 5 && !mxIsEmpty(a[4]) && mxGetScalar(a[4]) != 0;   // one launch where the hierarchy allows it
+        chk((planned ? ipd_amg_pcg_planned : ipd_amg_pcg)(g_h, mxGetDoubles(a[1]), opt_vec(so, "guess"), &o, mxGetDoubles(plhs[0]), &it, &res, rk.data()));
         if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)it);
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(res);
         if (nlhs > 3) { plhs[3] = col((size_t)it); std::memcpy(mxGetDoubles(plhs[3]), rk.data(), sizeof(double) * (size_t)it); }
@@ -248,8 +249,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nlhs > 2) { plhs[2] = mxCreateDoubleMatrix(1, (mwSize)N, mxREAL); for (size_t i = 0; i < N; ++i) mxGetDoubles(plhs[2])[i] = (double)(p[i] + 1); }
         if (nlhs > 3) { plhs[3] = mxCreateDoubleMatrix(1, (mwSize)nc + 1, mxREAL); for (int64_t c = 0; c <= nc; ++c) mxGetDoubles(plhs[3])[c] = (double)(r[(size_t)c] + 1); }
     } else if (fn == "Hybrid_AMG" || fn == "AMG4POT" || fn == "Hybrid_twogrid" || fn == "AMG4POT_twogrid" ||
+               fn == "Hybrid_AMG_PCG" || fn == "AMG4POT_pcg" ||
                fn == "aug_PCG" || fn == "PCG4POT") {   // [zeta,it,res,info] = f(prob_data,options)
-        const mxArray* pd = a[0]; const bool pot = fn == "AMG4POT" || fn == "AMG4POT_twogrid" || fn == "PCG4POT";
+        const mxArray* pd = a[0];
+        const bool pot = fn == "AMG4POT" || fn == "AMG4POT_twogrid" || fn == "AMG4POT_pcg" || fn == "PCG4POT";
         const mxArray *p = mxGetField(pd, 0, "p"), *q = mxGetField(pd, 0, "q");
         ipd_prob P; std::memset(&P, 0, sizeof(P));
         P.m = (int64_t)mxGetNumberOfElements(p); P.n = (int64_t)mxGetNumberOfElements(q);
@@ -271,6 +274,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             ipd_amg_opts o = opts_of(a[1]);
             if (fn == "Hybrid_AMG") chk(ipd_hybrid_amg(g_ctx, &P, &o, g_rng, mxGetDoubles(plhs[0]), &it, &res, info));
             else if (fn == "AMG4POT") chk(ipd_amg4pot(g_ctx, &P, &o, g_rng, mxGetDoubles(plhs[0]), &it, &res, info));
+            else if (fn == "Hybrid_AMG_PCG") chk(ipd_hybrid_amg_pcg(g_ctx, &P, &o, g_rng, mxGetDoubles(plhs[0]), &it, &res, info));
+            else if (fn == "AMG4POT_pcg") chk(ipd_amg4pot_pcg(g_ctx, &P, &o, g_rng, mxGetDoubles(plhs[0]), &it, &res, info));
             else if (fn == "Hybrid_twogrid") chk(ipd_hybrid_twogrid(g_ctx, &P, &o, g_rng, mxGetDoubles(plhs[0]), &it, &res, info));
             else chk(ipd_amg4pot_twogrid(g_ctx, &P, &o, g_rng, mxGetDoubles(plhs[0]), &it, &res, info));
         }
@@ -302,6 +307,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         chk(ipd_apd_get_state(g_apd, mxGetDoubles(plhs[0]), nullptr, mxGetDoubles(lk), &bk));
         if (nlhs > 1) plhs[1] = lk; else mxDestroyArray(lk);
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(bk);
+    } else if (fn == "apd_krylov") {   // ipd_mex('apd_krylov', on): AMG-PCG as the inner solver of the following apd_run calls
+        if (!g_apd) mexErrMsgIdAndTxt("ipdamg:state", "no workspace: call apd_create first");
+        chk(ipd_apd_set_krylov(g_apd, mxGetScalar(a[0]) != 0 ? 1 : 0));
     } else if (fn == "apd_run") {      // out = ipd_mex('apd_run', amg_options[, iters]): the main loop, inner_solver = 4
         if (!g_apd) mexErrMsgIdAndTxt("ipdamg:state", "no workspace: call apd_create first");
         ipd_amg_opts o = opts_of(a[0]); ipd_apd_result r;

@@ -204,6 +204,19 @@ int ipd_amg_solve_multi(ipd_amg* h, const double* B, int64_t ldb, int64_t nrhs,
  * used.                                                                                          */
 int ipd_amg_pcg(ipd_amg* h, const double* e, const double* guess, const ipd_pcg_opts* o,
                 double* d, int64_t* it, double* res, double* resk /* maxit slots or NULL */);
+/* ipd_amg_pcg's signature and conventions (precd unset, cycle 'v' / 'w', guess may be NULL, resk of
+ * maxit slots or NULL, e = 0 with a zero guess: it = 0, res = NaN), planned like ipd_amg_solve: on a
+ * hierarchy planned for the single-workgroup whole solve (every level small, not sharded -- mode 1
+ * of ipd_amg_resident_levels) the whole loop, its cycles included, is ONE single-workgroup launch and one
+ * read-back.  The cycle is then the single-workgroup kernel's (the same operator as the launch-path
+ * cycle, summed in another order), so results agree with ipd_amg_pcg to rounding and repeat bit for
+ * bit.  On every other hierarchy, and for maxit above 1000 (a launch stays bounded), it IS
+ * ipd_amg_pcg, bit for bit.                                                                      */
+int ipd_amg_pcg_planned(ipd_amg* h, const double* e, const double* guess, const ipd_pcg_opts* o,
+                        double* d, int64_t* it, double* res, double* resk /* maxit slots or NULL */);
+/* How the most recent ipd_amg_pcg / ipd_amg_pcg_planned call (host or _dev) on this hierarchy ran:
+ * -1 none yet, 0 as launches, 1 as one single-workgroup launch.                                  */
+int ipd_amg_pcg_mode(const ipd_amg* h, int32_t* mode);
 /* Several right-hand sides: column j of E (N x nrhs, column-major, leading dimension lde >= N) runs
  * ipd_amg_pcg's loop on this hierarchy as if it were solved alone -- guess column j (guess may be NULL:
  * zeros), its own it[j], res[j] and resk(1:it[j], j) (resk: maxit x nrhs column-major or NULL; later
@@ -278,6 +291,17 @@ int ipd_amg4pot_twogrid(ipd_ctx*, const ipd_prob* pd, const ipd_amg_opts* o, ipd
                         double* zeta, int32_t* itamg, double* resamg, int64_t info[2]);
 int ipd_amg4pot(ipd_ctx*, const ipd_prob* pd, const ipd_amg_opts* o, ipd_rng* rng,
                 double* zeta, int32_t* itamg, double* resamg, int64_t info[2]);
+/* Hybrid_AMG.m / AMG4POT.m with AMG-preconditioned CG as the inner solver: every Class_AMG call
+ * (Hybrid_AMG.m:41, :70) is its setup followed by ipd_amg_pcg_planned from the SAME random guess
+ * bk1*tk*rand(size(f)) -- same Ae, f, components, isnsp / fnode rule and small-block direct solves,
+ * and the rand stream advances exactly as in Hybrid_AMG.  retol and maxit are amg_options' (Class_AMG's
+ * defaults when unset); itamg = the most PCG iterations over the large components, resamg = their
+ * largest PCG res, info as in Hybrid_AMG.  The mask form of level 1 is not attached: the PCG's level-1
+ * product and its cycle walk A_1's rows.                                                          */
+int ipd_hybrid_amg_pcg(ipd_ctx*, const ipd_prob* pd, const ipd_amg_opts* o, ipd_rng* rng,
+                       double* zeta, int32_t* itamg, double* resamg, int64_t info[2]);
+int ipd_amg4pot_pcg(ipd_ctx*, const ipd_prob* pd, const ipd_amg_opts* o, ipd_rng* rng,
+                    double* zeta, int32_t* itamg, double* resamg, int64_t info[2]);
 
 /* ---- device-resident path (inputs already in HBM) ------------------------ */
 /* raw device memory on the context's GPU */
@@ -315,6 +339,9 @@ int ipd_amg_solve_multi_dev(ipd_amg* h, const double* B_dev, int64_t ldb, int64_
 /* ipd_amg_pcg on device vectors (guess_dev may be NULL); resk stays a host array               */
 int ipd_amg_pcg_dev(ipd_amg* h, const double* e_dev, const double* guess_dev,
                     const ipd_pcg_opts* o, double* d_dev, int64_t* it, double* res, double* resk);
+/* ipd_amg_pcg_planned on device vectors (guess_dev may be NULL); resk stays a host array       */
+int ipd_amg_pcg_planned_dev(ipd_amg* h, const double* e_dev, const double* guess_dev,
+                            const ipd_pcg_opts* o, double* d_dev, int64_t* it, double* res, double* resk);
 /* ipd_amg_pcg_multi on device blocks E, guess (or NULL) and D; it, res and resk stay host arrays */
 int ipd_amg_pcg_multi_dev(ipd_amg* h, const double* E_dev, int64_t lde, int64_t nrhs,
                           const double* guess_dev, const ipd_pcg_opts* o, double* D_dev, int64_t* it,
@@ -324,6 +351,11 @@ int ipd_hybrid_amg_dev(ipd_ctx*, const ipd_dmat* H0, const double* t_dev, const 
                        const double* q_dev, int64_t m, int64_t n, double bk1, double tk,
                        const double* z_dev, const ipd_amg_opts* o, ipd_rng* rng,
                        double* zeta_dev, int32_t* itamg, double* resamg, int64_t info[2]);
+/* ipd_hybrid_amg_pcg with H0 already on the device                          */
+int ipd_hybrid_amg_pcg_dev(ipd_ctx*, const ipd_dmat* H0, const double* t_dev, const double* p_dev,
+                           const double* q_dev, int64_t m, int64_t n, double bk1, double tk,
+                           const double* z_dev, const ipd_amg_opts* o, ipd_rng* rng,
+                           double* zeta_dev, int32_t* itamg, double* resamg, int64_t info[2]);
 
 /* X = A \ B, MATLAB's mldivide for a sparse symmetric positive definite A (CSC, both triangles)
  * and a dense column-major B (n x nrhs): the reference's cold-path direct solves
@@ -403,6 +435,11 @@ int ipd_apd_warmup(ipd_apd* h, double res, int64_t maxit);
  * lam = lk (n+m resp. n+m+1).  NULL pointers are skipped.                        */
 int ipd_apd_set_state(ipd_apd* h, const double* u, const double* v, const double* lam, double bk);
 int ipd_apd_get_state(ipd_apd* h, double* u, double* v, double* lam, double* bk);
+/* on != 0: inner_solver = 4 runs ipd_hybrid_amg_pcg resp. ipd_amg4pot_pcg instead of Hybrid_AMG /
+ * AMG4POT 'amg'; FailAMG / MaxAMG / TotalAMG / SumAMG and the per-step records then count PCG
+ * iterations by the same rules (itamg == amg_options.maxit is a failure).  Off (the default) is
+ * the stationary iteration; other inner solvers ignore it.  Holds until changed.                 */
+int ipd_apd_set_krylov(ipd_apd* h, int32_t on);
 /* Runs up to `iters` further APD iterations (`for k = 1:maxit`, Class1 :101-275,
  * Class2 :95-285) with inner_solver = 4 (Hybrid_AMG resp. AMG4POT 'amg'); stops
  * early at `CONV` or at opts->maxit.                                              */

@@ -10,10 +10,13 @@ One JSON line per case and repetition:
   launched        the same solve on a hierarchy set up with IPD_NO_RESIDENT=1 IPD_NO_SMALL=1:
                   ms per cycle of the launch path (what AMG-PCG runs)
   pcg             it, res, true relative residual |A d - e| / |e|, wall ms
+  planned         the same for AMGHierarchy.pcg(planned=True) and pcg_mode (1: the whole loop was ONE
+                  single-workgroup launch; 0: it ran as `pcg` does)
   overhead_us     (pcg_ms - it * launched_cycle_ms) / it: K1-K3 plus the per-iteration read
-Every case is warmed up first; --reps repetitions alternate the two solvers.
+Every case is warmed up first; --reps repetitions alternate the order of the solvers.
+--variant v1 runs the cases with a V cycle and one smoothing sweep instead of the drivers' options.
 
-  python tools/bench_amg_pcg.py [--reps 2] [--cases golden,newton,regimeD] [--out FILE]"""
+  python tools/bench_amg_pcg.py [--reps 2] [--cases golden,newton,regimeD] [--variant driver|v1] [--out FILE]"""
 import argparse
 import json
 import os
@@ -79,6 +82,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--cases", default="golden,newton,regimeD")
+    ap.add_argument("--variant", default="driver", choices=["driver", "v1"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import codes_of_ipd_ssn_amg_method_amd as ipd
@@ -88,8 +92,10 @@ def main():
     built = []
     for name, mk in cases(ipd, args.cases.split(",")):
         Ae, f, n = mk()
-        o = O.amg_options_class1("w")
+        o = O.amg_options_class1("w" if args.variant == "driver" else "v")
         o.update(fnode=n)
+        if args.variant == "v1":
+            o.update(smoth=1)
         h = ipd.AMGHierarchy(Ae, o, ipd.MatlabRand())
         os.environ["IPD_NO_RESIDENT"] = "1"
         os.environ["IPD_NO_SMALL"] = "1"
@@ -98,12 +104,12 @@ def main():
         finally:
             del os.environ["IPD_NO_RESIDENT"]
             del os.environ["IPD_NO_SMALL"]
-        h.solve(f), hl.solve(f), h.pcg(f, po)          # warm-up
+        h.solve(f), hl.solve(f), h.pcg(f, po), h.pcg(f, po, planned=True)          # warm-up
         built.append((name, Ae, f, h, hl))
     for rep in range(args.reps):
         for name, Ae, f, h, hl in built:
-            order = ("stationary", "pcg") if rep % 2 == 0 else ("pcg", "stationary")
-            rec = {"case": name, "rep": rep, "rows": int(Ae.shape[0]), "nnz": int(Ae.nnz), "levels": h.level_sizes()}
+            order = ("stationary", "pcg", "planned") if rep % 2 == 0 else ("planned", "pcg", "stationary")
+            rec = {"case": name, "variant": args.variant, "rep": rep, "rows": int(Ae.shape[0]), "nnz": int(Ae.nnz), "levels": h.level_sizes()}
             for which in order:
                 if which == "stationary":
                     (x, it, rr, _, _), ms = timed(lambda: h.solve(f))
@@ -111,12 +117,17 @@ def main():
                     (x, itl, rrl, _, _), msl = timed(lambda: hl.solve(f))
                     rec["launched"] = {"it": itl, "ms": msl, "mode": solve_mode(hl),
                                        "ms_per_cycle": msl / max(itl, 1)}
-                else:
+                elif which == "pcg":
                     (d, it, res, _), ms = timed(lambda: h.pcg(f, po))
                     tr = float(np.linalg.norm(Ae @ d - f) / np.linalg.norm(f))
                     rec["pcg"] = {"it": it, "res": res, "true_rel_res": tr, "ms": ms}
+                else:
+                    (d, it, res, _), ms = timed(lambda: h.pcg(f, po, planned=True))
+                    tr = float(np.linalg.norm(Ae @ d - f) / np.linalg.norm(f))
+                    rec["planned"] = {"it": it, "res": res, "true_rel_res": tr, "ms": ms, "mode": h.pcg_mode}
             it = max(rec["pcg"]["it"], 1)
             rec["overhead_us"] = 1e3 * (rec["pcg"]["ms"] - it * rec["launched"]["ms_per_cycle"]) / it
+            rec["planned_speedup"] = rec["pcg"]["ms"] / rec["planned"]["ms"]
             line = json.dumps(rec)
             print(line, flush=True)
             if sink:

@@ -3,7 +3,11 @@
 evaluation pass.  (The CPU restatement is timed by tests/time_oracle_drivers.py: only tests/ may
 import oracle/.)
 
-  python tools/bench_driver.py [--sizes 500,1024] [--classes 1,2]
+  python tools/bench_driver.py [--sizes 500,1024] [--classes 1,2] [--krylov off,on] [--bundled]
+
+--krylov on: the inner solver is AMG-preconditioned CG behind Hybrid_AMG / AMG4POT (APDWorkspace.run's
+krylov keyword); --bundled: Class 1 on the bundled 500 x 500 input (tests/golden/data1_500.npz) instead
+of the synthetic problems.
 """
 import argparse
 import json
@@ -27,7 +31,12 @@ def problem(cls, N, seed=1):
     return dict(c=c, r=r, l=l, mu=0.65 * min(r.sum(), l.sum()))
 
 
-def run(cls, N, pr, cycle="w"):
+def bundled():
+    d = np.load(os.path.join(ROOT, "tests", "golden", "data1_500.npz"))
+    return dict(c=d["c"], r=d["r"], l=d["l"])
+
+
+def run(cls, N, pr, cycle="w", krylov=False):
     one = np.ones(N)
     t0 = time.perf_counter()
     if cls == 1:
@@ -40,7 +49,7 @@ def run(cls, N, pr, cycle="w"):
     t1 = time.perf_counter()
     ws.warmup(0.0, 100)
     t2 = time.perf_counter()
-    out = ws.run(amg, ipd.MatlabRand(5489))
+    out = ws.run(amg, ipd.MatlabRand(5489), krylov=krylov)
     t3 = time.perf_counter()
     lls = np.array([r["ll"] for r in ws.records()] or [0])
     ll_stats = dict(mean=float(lls.mean()), p50=float(np.median(lls)), max=int(lls.max()),
@@ -58,7 +67,7 @@ def run(cls, N, pr, cycle="w"):
     ms, by = ws.bench_eval(200)
     rec = dict(cls=cls, N=N, upload_s=t1 - t0, warmup_s=t2 - t1, apd_s=t3 - t2, k=out["k"],
                converged=out["converged"], fval=out["fval"], newton_steps=out["nrec"],
-               SumAMG=out["SumAMG"], eval_us=1e3 * ms / 200, eval_GBps=by * 200 / (ms * 1e-3) / 1e9,
+               SumAMG=out["SumAMG"], FailAMG=out["FailAMG"], MaxAMG=out["MaxAMG"], krylov=bool(krylov), eval_us=1e3 * ms / 200, eval_GBps=by * 200 / (ms * 1e-3) / 1e9,
                eval_bytes=by, ll=ll_stats)
     if prof:
         rec["profile_s_calls"] = prof
@@ -72,13 +81,19 @@ def main():
     ap.add_argument("--classes", default="1,2")
     ap.add_argument("--cycle", default="w", choices=["v", "w"],
                     help="AMG cycle of the inner solver (the reference scripts use w)")
+    ap.add_argument("--krylov", default="off", help="off, on or off,on: AMG-PCG as the inner solver")
+    ap.add_argument("--bundled", action="store_true", help="Class 1 on the bundled 500 x 500 input")
     a = ap.parse_args()
-    for N in [int(x) for x in a.sizes.split(",")]:
-        for cls in [int(x) for x in a.classes.split(",")]:
-            pr = problem(cls, N)
-            rec = run(cls, N, pr, a.cycle)
-            rec["cycle"] = a.cycle
-            print(json.dumps(rec), flush=True)
+    sizes = [500] if a.bundled else [int(x) for x in a.sizes.split(",")]
+    classes = [1] if a.bundled else [int(x) for x in a.classes.split(",")]
+    for N in sizes:
+        for cls in classes:
+            pr = bundled() if a.bundled else problem(cls, N)
+            for kry in a.krylov.split(","):
+                rec = run(cls, N, pr, a.cycle, kry == "on")
+                rec["cycle"] = a.cycle
+                rec["input"] = "data1_500" if a.bundled else "synthetic"
+                print(json.dumps(rec), flush=True)
 
 
 if __name__ == "__main__":
