@@ -3034,9 +3034,8 @@ __global__ __launch_bounds__(256) void k_bpoly_compose(const BPolyEntry e, int n
     }
 }
 
-static constexpr int RELOC_MAX = 640;
 __host__ __device__ constexpr size_t sol_r16(size_t b) { return (b + 15) / 16 * 16; }
-static constexpr size_t SOL_HEAD = sol_r16(sizeof(SolveDesc)) + sol_r16(4 * RELOC_MAX);
+static_assert(sol_r16(sizeof(SolveDesc)) + sol_r16(4 * RELOC_MAX) == SOL_HEAD, "ipd_limits.h: SOL_HEAD is the image head");
 
 // One flat copy of the image (many 16-byte loads in flight per lane) instead of one dependent
 // global round trip per array (measured: ~60 arrays x ~1.5 us dominated the sub-cycle kernel).

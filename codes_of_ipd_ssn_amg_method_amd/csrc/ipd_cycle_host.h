@@ -54,18 +54,24 @@ struct CycleState {
     size_t pending_lds = 0;
     bool fuse_enabled = true;
     CycleState() { pending.n = 0; }
-    // single-workgroup whole-solve kernel (small hierarchies): device descriptor + outputs
-    SolveDesc* d_solve = nullptr;
-    double* solve_out = nullptr;
-    size_t solve_lds = 0;
+    // The LDS images of the single-workgroup kernels (ipd_level_plan.h) by role: the whole solve (k_solve_small,
+    // k_pcg_small), the sub-cycle rooted at level k_sub (k_subcycle), and the images rooted at level 3 (no sub-cycle:
+    // k_sub == 0) and at level 4 (beside a sub-cycle rooted at level 3: `three` mode) that the resident kernels' tail
+    // workgroup takes alone
+    struct Image {
+        SolveDesc* desc = nullptr;
+        size_t lds = 0;   // dynamic LDS of a launch
+        size_t bm = 0;    // ... and what the image's operator copy needs on top of it (SolveDesc::bm_src; 0: none)
+    };
+    Image img[IMG_NONE];
+    double* solve_out = nullptr;   // the whole-solve kernel's outputs
     bool small_ok = false;
     bool solve_cached = false;
     // matrix-free level-1 operator (bit mask + scale vectors), see k_smooth_mask
     bool mask_ok = false;
     MaskOp maskop{};
-    // single-workgroup sub-cycle rooted at level k_sub (0 = none), see k_subcycle
-    SolveDesc* d_sub = nullptr;
-    bool sub_semi_root = false;    // d_sub's root level is semi-cached (rows from L2)
+    int k_sub = 0;                 // root of the IMG_SUB image (0 = none)
+    bool sub_semi_root = false;    // ... which is semi-cached (rows from L2)
     std::vector<int> level_forms;  // per level, over all images packed: see ipd_amg_level_forms
     struct PolyOp {                // block-wide polynomial operators packed for the images (ipd_amg_poly_operator)
         const double* M = nullptr;
@@ -79,15 +85,7 @@ struct CycleState {
     };
     std::vector<RowsOp> rows_ops;  // per level: form 64 (level 3 / 4 of k_resident's `three` mode or of DEEP mode)
     RowsOp poly2_op;               // form 128: level 2 composed over a visit
-    SolveDesc* d_sub4 = nullptr;   // image rooted at level 4 for the resident kernel's `three` mode
-    size_t sub4_lds = 0;           // (packed beside d_sub when that one is rooted at level 3)
-    SolveDesc* d_sub3 = nullptr;   // image rooted at level 3 for the resident kernel alone (k_sub == 0)
-    size_t sub3_lds = 0;
     ImageRole sub5 = IMG_NONE;     // the image whose levels 5..J serve a resident kernel's tail rooted at level 5 (POLY4)
-    int k_sub = 0;
-    size_t sub_lds = 0;
-    // dynamic LDS an image's operator copy needs on top of its *_lds (SolveDesc::bm_src; 0: none)
-    size_t sub_bm = 0, sub3_bm = 0, sub4_bm = 0;
     double* x2 = nullptr;
     ResidentState res;   // the resident solve kernels: plan and run state (ipd_resident_host.h)
     hipGraphExec_t gexec[2] = {nullptr, nullptr};  // captured Class_AMG loop bodies (x->x2, x2->x)
@@ -588,6 +586,14 @@ static void prepare_transfers(ipd_amg* h, CycleState* st) {
     h->b = ar.alloc<double>((size_t)h->L[1].A.nr);
 }
 
+// in one workgroup a row is walked by few lanes: re-picked without widening
+static int lanes_in_one_workgroup(int nnz, int rows) {
+    const double avg = (double)nnz / std::max(rows, 1);
+    int L = 1;
+    while (L < 64 && (double)L * 6.0 < avg) L <<= 1;
+    return L;
+}
+
 // Descriptor of image `spec` before its layout: every level's global arrays and its lanes per row in one workgroup
 static void fill_desc(ipd_amg* h, const CycleState* st, const ImageSpec& spec, SolveDesc* sd) {
     std::memset(sd, 0, sizeof(SolveDesc));
@@ -603,14 +609,8 @@ static void fill_desc(ipd_amg* h, const CycleState* st, const ImageSpec& spec, S
         SolveLevel& sl = sd->L[k];
         sl.lv = st->run[(size_t)k].dev;
         sl.lv.S = 0;  // the single-workgroup kernels walk the CSR arrays only
-        // in one workgroup a row is walked by few lanes: re-pick without widening
         const Level& lv = h->L[k];
-        {
-            const double avg = (double)lv.A.nnz / std::max(lv.A.nr, 1);
-            int L = 1;
-            while (L < 64 && (double)L * 6.0 < avg) L <<= 1;
-            sl.lv.L = L;
-        }
+        sl.lv.L = lanes_in_one_workgroup(lv.A.nnz, lv.A.nr);
         sl.lv.G = 1;
         sl.e = lv.e;
         sl.e2 = lv.e2;
@@ -621,11 +621,7 @@ static void fill_desc(ipd_amg* h, const CycleState* st, const ImageSpec& spec, S
             sl.rest = st->run[(size_t)k].restrict_args;
             sl.prol = st->run[(size_t)k].prolong_args;
             for (XferArgs* xa : {&sl.rest, &sl.prol}) {
-                const double avg = (double)(xa == &sl.rest ? h->L[k + 1].Pt.nnz : h->L[k + 1].P.nnz) /
-                                   std::max(xa->nrows, 1);
-                int L = 1;
-                while (L < 64 && (double)L * 6.0 < avg) L <<= 1;
-                xa->L = L;
+                xa->L = lanes_in_one_workgroup(xa == &sl.rest ? h->L[k + 1].Pt.nnz : h->L[k + 1].P.nnz, xa->nrows);
                 xa->G = 1;
                 xa->staged = 1;
                 xa->row0 = 0;
@@ -644,9 +640,9 @@ static void fill_desc(ipd_amg* h, const CycleState* st, const ImageSpec& spec, S
     }
 }
 
-// An image's pieces: the constant arrays copied into it, the dense / lane-map / polynomial blocks computed
-// into it, and the relocations of the descriptor's LDS offsets
-struct ImageLayout {
+// What packs an image on the device: the constant arrays copied into it, the dense / lane-map / polynomial
+// blocks computed into it, and the relocations of the descriptor's LDS offsets
+struct ImagePack {
     std::vector<PackEntry> packs;
     std::vector<unsigned> relocs;
     std::vector<DenseEntry> dense;
@@ -655,10 +651,10 @@ struct ImageLayout {
     size_t poly_lds = 0;   // dynamic LDS of k_pack_poly
 };
 
-// Packs the laid-out image on the device and records the levels' forms; with bm_extra, one block-wide
+// Packs the bound image on the device and records the levels' forms; with bm_extra, one block-wide
 // polynomial operator's LDS copy goes behind the image's `off` bytes (*bm_extra: its size, 0 = none).
 static SolveDesc* upload_image(ipd_ctx* ctx, ipd_amg* h, CycleState* st, SolveDesc* sd, int k_from, size_t off,
-                               size_t image_bytes, ImageLayout& lay, size_t* bm_extra) {
+                               size_t image_bytes, ImagePack& lay, size_t* bm_extra) {
     Arena& ar = *h->arena;
     // One block-wide polynomial level's operator as an LDS copy (SolveDesc::bm_src), for the launches that can
     // afford bm_bytes more dynamic LDS (the resident kernels' tail workgroup): the deepest such level whose
@@ -674,7 +670,7 @@ static SolveDesc* upload_image(ipd_ctx* ctx, ipd_amg* h, CycleState* st, SolveDe
             if (rows > 128) continue;
             const size_t ld = (rows + 1) & ~size_t(1), ncols = 8 * (2 * ((N + 7) / 8) + (Nc + 7) / 8);
             const size_t need = 8 * ld * (ncols + 1);   // (ld even: a multiple of 16; the vector W behind the columns)
-            if (off + need > (size_t)156 * 1024) continue;
+            if (off + need > IMAGE_LDS_OPTIN) continue;
             double* cp = ar.alloc<double>(ld * (ncols + 1));
             hipLaunchKernelGGL(k_bm_compact, dim3((unsigned)ncols + 1), dim3(128), 0, ctx->stream, T.gM, 128, cp,
                                (int)ld, T.gW, (int)rows);
@@ -691,11 +687,10 @@ static SolveDesc* upload_image(ipd_ctx* ctx, ipd_amg* h, CycleState* st, SolveDe
     char* img = reinterpret_cast<char*>(ar.alloc_bytes(image_bytes));
     // the image head and the pack descriptors go up in ONE copy: [head | packs | dense | lmaps | polys] in
     // a scratch block, the head then moves into the image as one more entry of k_pack_image
-    auto r16b = [](size_t v) { return (v + 15) & ~size_t(15); };
-    const size_t o_packs = r16b(SOL_HEAD), o_dense = o_packs + r16b((lay.packs.size() + 1) * sizeof(PackEntry)),
-                 o_lmaps = o_dense + r16b(lay.dense.size() * sizeof(DenseEntry)),
-                 o_polys = o_lmaps + r16b(lay.lmaps.size() * sizeof(LmapEntry)),
-                 o_end = o_polys + r16b(lay.polys.size() * sizeof(PolyEntry));
+    const size_t o_packs = plan_r16(SOL_HEAD), o_dense = o_packs + plan_r16((lay.packs.size() + 1) * sizeof(PackEntry)),
+                 o_lmaps = o_dense + plan_r16(lay.dense.size() * sizeof(DenseEntry)),
+                 o_polys = o_lmaps + plan_r16(lay.lmaps.size() * sizeof(LmapEntry)),
+                 o_end = o_polys + plan_r16(lay.polys.size() * sizeof(PolyEntry));
     char* stg = reinterpret_cast<char*>(ctx->scratch->alloc_bytes(o_end));
     std::vector<char> hb(o_end, 0);
     std::memcpy(hb.data(), sd, sizeof(SolveDesc));
@@ -726,7 +721,7 @@ static SolveDesc* upload_image(ipd_ctx* ctx, ipd_amg* h, CycleState* st, SolveDe
         IPD_KERNEL_CHECK();
     }
     if (!lay.polys.empty()) {
-        IPD_OPTIN_LDS(ctx, k_pack_poly, 156 * 1024);
+        IPD_OPTIN_LDS(ctx, k_pack_poly, IMAGE_LDS_OPTIN);
         hipLaunchKernelGGL(k_pack_poly, dim3((unsigned)lay.polys.size()), dim3(BT), lay.poly_lds, ctx->stream,
                            reinterpret_cast<const PolyEntry*>(stg + o_polys), img);
         IPD_KERNEL_CHECK();
@@ -740,254 +735,105 @@ static SolveDesc* upload_image(ipd_ctx* ctx, ipd_amg* h, CycleState* st, SolveDe
     return reinterpret_cast<SolveDesc*>(img);
 }
 
-// Lays image `spec` out (levels k_lds..J behind the staging area), packs it on the device and stores it
-// in st by its role
-static void pack_image(ipd_ctx* ctx, ipd_amg* h, CycleState* st, const LevelPlan& plan, const ImageSpec& spec) {
+static const char* const IMAGE_ROLE_NAMES[] = {"solve", "sub", "sub3", "sub4", "none"};
+
+// the descriptor's pointer that piece (level, slot) of a layout stands for: its place in SolveLevel, or in the
+// SolveDesc itself for the image-wide slots
+#define IPD_LV(m) offsetof(SolveLevel, m)
+static const size_t SLOT_FIELD[SLOT_COUNT] = {
+    IPD_LV(lv.rp), IPD_LV(lv.ci), IPD_LV(lv.va), IPD_LV(lv.dinv), IPD_LV(lv.Axi), IPD_LV(lv.xx),
+    IPD_LV(rest.rp), IPD_LV(rest.ci), IPD_LV(rest.va), IPD_LV(prol.rp), IPD_LV(prol.ci), IPD_LV(prol.va),
+    IPD_LV(lmap), IPD_LV(dA), IPD_LV(dP), IPD_LV(dPt), IPD_LV(pMr), IPD_LV(pMe), IPD_LV(pMc), IPD_LV(pW),
+    IPD_LV(lv.r), IPD_LV(e), IPD_LV(e2), IPD_LV(lv.rr), IPD_LV(w),
+    offsetof(SolveDesc, bp_part), offsetof(SolveDesc, pcg.work), IPD_LV(rest.x), IPD_LV(rest.y),
+    offsetof(SolveDesc, pcg.rp), offsetof(SolveDesc, pcg.ci), offsetof(SolveDesc, pcg.va)};
+#undef IPD_LV
+static size_t* slot_field(SolveDesc* sd, int level, ImageSlot slot) {   // (every one is a pointer: read and written as its bits)
+    const bool wide = slot == SLOT_BP_PART || slot == SLOT_PCG_WORK || slot >= SLOT_PCG_RP;
+    return reinterpret_cast<size_t*>(reinterpret_cast<char*>(wide ? (void*)sd : (void*)&sd->L[level]) + SLOT_FIELD[slot]);
+}
+
+// Binds the layout to the descriptor: every piece's pointer becomes its LDS offset and one relocation, every
+// copied or computed piece one pack entry
+static ImagePack bind_layout(ipd_ctx* ctx, ipd_amg* h, CycleState* st, const std::vector<LevelShape>& shapes, const LevelPlan& plan,
+                             const ImageSpec& spec, const ImageLayout& lay, SolveDesc* sd) {
+    ImagePack pk;
+    for (int k = spec.k_lds; k <= h->J; ++k) {
+        const LevelPieces own = plan.pieces(shapes.data(), spec, k);
+        if (own.form == FORM_SEMI) continue;   // matrix, transfers, dinv, Axi stay in global memory
+        // a form that has no piece for one of the level's arrays does not read it
+        for (int q = SLOT_RP; q <= SLOT_PROL_VA; ++q)
+            if (!own.has((ImageSlot)q)) *slot_field(sd, k, (ImageSlot)q) = 0;
+        sd->L[k].blk_dense = own.form == FORM_BDENSE;
+        if (own.form != FORM_BPOLY) continue;
+        st->poly_ops.resize((size_t)h->J + 1);   // the operators stay in global memory
+        CycleState::PolyOp& po = st->poly_ops[(size_t)k];
+        if (!po.M) {   // packed once for all images
+            const BPolyDev b = pack_bpoly(ctx, h, st, k, sd->isnsp, (int)own.ld(), false);
+            po = CycleState::PolyOp{b.M, b.W, b.LD, h->L[k].A.nr, h->L[k + 1].A.nr};
+        }
+        sd->L[k].gM = po.M;
+        sd->L[k].gW = po.W;
+        sd->L[k].gLD = po.LD;
+    }
+    for (const ImagePiece& p : lay.pieces) {
+        size_t* field = slot_field(sd, p.level, p.slot);
+        const void* src = reinterpret_cast<const void*>(*field);   // the global array, where the piece is a copy of one
+        *field = p.off;
+        pk.relocs.push_back((unsigned)(reinterpret_cast<char*>(field) - reinterpret_cast<char*>(sd)));
+        const int k = p.level;
+        const unsigned dst = (unsigned)(p.off - spec.stage_bytes);
+        if (p.kind == PIECE_COPY) pk.packs.push_back(PackEntry{src, dst, (unsigned)p.bytes});
+        if (p.kind == PIECE_LMAP) pk.lmaps.push_back(LmapEntry{h->L[k].A.rp, h->L[k].A.nr, dst});
+        if (p.kind == PIECE_DENSE) {
+            const Csr& m = p.slot == SLOT_DA ? h->L[k].A : p.slot == SLOT_DP ? h->L[k + 1].P : h->L[k + 1].Pt;
+            pk.dense.push_back(DenseEntry{m.rp, m.ci, m.va, m.nr, m.nc, dst, sd->L[k].blk_dense ? bdense_ld(m.nr) : 0});
+        }
+        if (p.kind != PIECE_POLY) continue;
+        if (p.slot == SLOT_PMR) {   // pMr, pMe, pMc, pW follow one another: one entry of k_pack_poly
+            const Level& lv = h->L[k];
+            const Csr& P = h->L[k + 1].P;
+            const LevelDev& gd = st->run[(size_t)k].dev;   // global pointers (the descriptor's are LDS offsets by now)
+            const size_t N = (size_t)lv.A.nr, Nc = (size_t)P.nc;
+            sd->L[k].pLD = (int)plan.pieces(shapes.data(), spec, k).ld();
+            pk.polys.push_back(PolyEntry{lv.A.rp, lv.A.ci, lv.A.va, P.rp, P.ci, P.va, gd.dinv, gd.Axi, gd.xx, (int)N, (int)Nc,
+                                         sd->nu, sd->isnsp, sd->L[k].pLD, 0, 0, 0, 0});
+            pk.poly_lds = std::max(pk.poly_lds, 8 * (5 * N * N + 2 * N * Nc + 4 * N) + 64);
+        }
+        PolyEntry& pe = pk.polys.back();
+        (p.slot == SLOT_PMR ? pe.offMr : p.slot == SLOT_PME ? pe.offMe : p.slot == SLOT_PMC ? pe.offMc : pe.offW) = dst;
+    }
+    return pk;
+}
+
+// Packs image `spec` as image_layout lays it out (levels k_lds..J behind the staging area) and stores it in st
+// by its role
+static void pack_image(ipd_ctx* ctx, ipd_amg* h, CycleState* st, const std::vector<LevelShape>& shapes, const LevelPlan& plan,
+                       const ImageSpec& spec) {
     std::unique_ptr<SolveDesc> sdp(new SolveDesc());
     SolveDesc* sd = sdp.get();
     fill_desc(h, st, spec, sd);
-    if (spec.role == IMG_SOLVE) {
-        st->solve_cached = spec.k_lds <= h->J;
-        st->solve_lds = spec.lds;
-        if (!st->solve_cached) {   // nothing in LDS: the descriptor as it is
-            st->d_solve = reinterpret_cast<SolveDesc*>(h->arena->alloc_bytes(sizeof(SolveDesc)));
-            ctx->upload_bytes(st->d_solve, sd, sizeof(SolveDesc));
-            return;
-        }
+    CycleState::Image& out = st->img[spec.role];
+    st->solve_cached = st->solve_cached || (spec.role == IMG_SOLVE && spec.k_lds <= h->J);
+    if (spec.k_lds > h->J) {   // a solve with nothing in LDS: the descriptor as it is
+        out.desc = reinterpret_cast<SolveDesc*>(h->arena->alloc_bytes(sizeof(SolveDesc)));
+        out.lds = spec.lds;
+        ctx->upload_bytes(out.desc, sd, sizeof(SolveDesc));
+        return;
     }
-    const int k_from = spec.k_lds;
-    const size_t stage = spec.stage_bytes;
-    const bool lean = plan.lean_vectors && sd->k_blk <= std::max(2, k_from);
-    ImageLayout lay;
-    size_t off = stage + SOL_HEAD;   // LDS offset (from dyn_raw) of the next carve
-    auto carve = [&](size_t bytes) {
-        const size_t o = off;
-        off += plan_r16(bytes);
-        return o;
-    };
-    auto set_off = [&](auto& field, size_t o) {
-        using T = std::remove_reference_t<decltype(field)>;
-        field = reinterpret_cast<T>(o);
-        lay.relocs.push_back((unsigned)(reinterpret_cast<char*>(&field) - reinterpret_cast<char*>(sd)));
-    };
-    auto put = [&](auto& field, size_t n) {   // constant array: copied into the image
-        using T = std::remove_reference_t<decltype(field)>;
-        using E = std::remove_cv_t<std::remove_pointer_t<T>>;
-        const size_t o = carve(n * sizeof(E));
-        lay.packs.push_back(PackEntry{(const void*)field, (unsigned)(o - stage), (unsigned)(n * sizeof(E))});
-        set_off(field, o);
-    };
-    int bp_ld_max = 0;
-    for (int k = k_from; k <= h->J; ++k) {     // constants first: they form the image
-        SolveLevel& T = sd->L[k];
-        const size_t N = (size_t)T.lv.N;
-        if (k == sd->k_semi) continue;         // matrix, transfers, dinv, Axi stay in global memory
-        if (((plan.poly[(size_t)k] && k >= sd->k_tiny) || (plan.lpoly[(size_t)k] && k < sd->k_tiny)) && sd->k_blk <= k) {   // polynomial form: no CSR arrays (see plan_lds)
-            put(T.lv.xx, 1);
-            T.lv.rp = T.lv.ci = nullptr;
-            T.lv.va = T.lv.dinv = T.lv.Axi = nullptr;
-            T.rest.rp = T.rest.ci = T.prol.rp = T.prol.ci = nullptr;
-            T.rest.va = T.prol.va = nullptr;
-            continue;
-        }
-        if (plan.bpoly[(size_t)k] && sd->k_blk <= k && k < sd->k_tiny) {   // block-wide polynomial form (see plan_lds)
-            put(T.lv.xx, 1);
-            T.lv.rp = T.lv.ci = nullptr;
-            T.lv.va = T.lv.dinv = T.lv.Axi = nullptr;
-            T.rest.rp = T.rest.ci = T.prol.rp = T.prol.ci = nullptr;
-            T.rest.va = T.prol.va = nullptr;
-            st->poly_ops.resize((size_t)h->J + 1);
-            CycleState::PolyOp& po = st->poly_ops[(size_t)k];
-            if (!po.M) {   // packed once for all images
-                const BPolyDev b = pack_bpoly(ctx, h, st, k, sd->isnsp, bpoly_ld(h->L[k].A.nr, h->L[k + 1].A.nr), false);
-                po.M = b.M;
-                po.W = b.W;
-                po.LD = b.LD;
-                po.N = h->L[k].A.nr;
-                po.Nc = h->L[k + 1].A.nr;
-            }
-            T.gM = po.M;
-            T.gW = po.W;
-            T.gLD = po.LD;
-            bp_ld_max = std::max(bp_ld_max, po.LD);
-            continue;
-        }
-        put(T.lv.rp, N + 1);
-        if (plan.bdense[(size_t)k] && sd->k_blk <= k && k < sd->k_tiny) {   // dense copy (carved below) instead of ci / va
-            T.blk_dense = 1;
-            T.lv.ci = nullptr;
-            T.lv.va = nullptr;
-        } else {
-            put(T.lv.ci, (size_t)T.nnzA);
-            put(T.lv.va, (size_t)T.nnzA);
-        }
-        put(T.lv.dinv, N);
-        put(T.lv.Axi, N);
-        put(T.lv.xx, 1);
-        if (k < h->J) {
-            const size_t Nc = (size_t)T.rest.nrows;
-            put(T.rest.rp, Nc + 1);
-            put(T.rest.ci, (size_t)T.nnzP);
-            put(T.rest.va, (size_t)T.nnzP);
-            put(T.prol.rp, N + 1);
-            put(T.prol.ci, (size_t)T.nnzP);
-            put(T.prol.va, (size_t)T.nnzP);
-        }
-    }
-    for (int k = std::max(k_from, sd->k_blk); k < std::min(sd->k_tiny, h->J + 1); ++k) {
-        if (!plan.lean_vectors || k == sd->k_semi || k < 2 || h->L[k].A.nr > BT || k == h->J || sd->L[k].blk_dense || sd->L[k].gM || plan.lpoly[(size_t)k]) continue;
-        SolveLevel& T = sd->L[k];
-        const size_t o = carve(4 * (BT + 1));
-        lay.lmaps.push_back(LmapEntry{h->L[k].A.rp, h->L[k].A.nr, (unsigned)(o - stage)});
-        set_off(T.lmap, o);
-    }
-    for (int k = k_from; k <= h->J; ++k) {
-        if (!sd->L[k].blk_dense) continue;
-        const Csr& m = h->L[k].A;
-        const int ld = bdense_ld(m.nr);
-        const size_t o = carve(8 * (size_t)m.nr * ld);
-        lay.dense.push_back(DenseEntry{m.rp, m.ci, m.va, m.nr, m.nc, (unsigned)(o - stage), ld});
-        set_off(sd->L[k].dA, o);
-    }
-    auto add_poly = [&](int k, size_t LD) {
-        SolveLevel& T = sd->L[k];
-        const Level& lv = h->L[k];
-        const size_t N = (size_t)lv.A.nr;
-        const Csr& P = h->L[k + 1].P;
-        const size_t Nc = (size_t)P.nc;
-        const LevelDev& gd = st->run[(size_t)k].dev;   // global pointers (T's are LDS offsets by now)
-        PolyEntry pe;
-        pe.Arp = lv.A.rp;
-        pe.Aci = lv.A.ci;
-        pe.Ava = lv.A.va;
-        pe.Prp = P.rp;
-        pe.Pci = P.ci;
-        pe.Pva = P.va;
-        pe.dinv = gd.dinv;
-        pe.Axi = gd.Axi;
-        pe.xx = gd.xx;
-        pe.N = (int)N;
-        pe.Nc = (int)Nc;
-        pe.nu = sd->nu;
-        pe.isnsp = sd->isnsp;
-        pe.LD = (int)LD;
-        T.pLD = (int)LD;
-        size_t o = carve(8 * LD * plan_r8(N));
-        pe.offMr = (unsigned)(o - stage);
-        set_off(T.pMr, o);
-        o = carve(8 * LD * plan_r8(N));
-        pe.offMe = (unsigned)(o - stage);
-        set_off(T.pMe, o);
-        o = carve(8 * LD * plan_r8(Nc));
-        pe.offMc = (unsigned)(o - stage);
-        set_off(T.pMc, o);
-        o = carve(8 * LD);
-        pe.offW = (unsigned)(o - stage);
-        set_off(T.pW, o);
-        lay.polys.push_back(pe);
-        lay.poly_lds = std::max(lay.poly_lds, 8 * (5 * N * N + 2 * N * Nc + 4 * N) + 64);
-    };
-    for (int k = std::max(k_from, sd->k_blk); k < std::min(sd->k_tiny, h->J); ++k)
-        if (plan.lpoly[(size_t)k] && k != sd->k_semi) {   // block-wide out of LDS: leading dimension 64, one row per lane
-            add_poly(k, 64);
-            bp_ld_max = std::max(bp_ld_max, 64);
-        }
-    for (int k = std::max(k_from, sd->k_tiny); k <= h->J; ++k) {
-        SolveLevel& T = sd->L[k];
-        const Level& lv = h->L[k];
-        const size_t N = (size_t)lv.A.nr;
-        if (plan.poly[(size_t)k] && sd->k_blk <= k && k != sd->k_semi) {
-            add_poly(k, poly_ld(N + (size_t)h->L[k + 1].P.nc));
-            continue;
-        }
-        auto add = [&](const double*& field, const Csr& m) {
-            const size_t o = carve(8 * (size_t)m.nr * m.nc);
-            lay.dense.push_back(DenseEntry{m.rp, m.ci, m.va, m.nr, m.nc, (unsigned)(o - stage), 0});
-            set_off(field, o);
-        };
-        add(T.dA, lv.A);
-        if (k < h->J) {
-            add(T.dP, h->L[k + 1].P);
-            add(T.dPt, h->L[k + 1].Pt);
-        }
-        (void)N;
-    }
-    const size_t image_bytes = off - stage;
-    for (int k = k_from; k <= h->J; ++k) {     // work vectors: carved, not copied
-        SolveLevel& T = sd->L[k];
-        // (one-wave levels: zero-padded to whole 8-entry blocks, see sol_load_image)
-        // (dense thread-per-row levels: zero-padded to whole groups of four entries per lane, dense_row_dot)
-        // (block-wide polynomial levels and their children: whole 8-entry blocks as well, bpoly_pass)
-        const bool pad8 = k >= sd->k_tiny || T.gM || T.pMr || (k > k_from && (sd->L[k - 1].gM || sd->L[k - 1].pMr));
-        const size_t N = T.blk_dense ? (size_t)bdense_pad(T.lv.N) : pad8 ? plan_r8((size_t)T.lv.N) : (size_t)T.lv.N;
-        set_off(T.lv.r, carve(N * 8));
-        set_off(T.e, carve(N * 8));
-        set_off(T.e2, carve(N * 8));
-        if (lean && k >= 2) {   // never dereferenced on these levels (see LevelPlan::lean_vectors)
-            T.lv.rr = T.e2;
-            lay.relocs.push_back((unsigned)(reinterpret_cast<char*>(&T.lv.rr) - reinterpret_cast<char*>(sd)));
-            T.w = T.e2;
-            lay.relocs.push_back((unsigned)(reinterpret_cast<char*>(&T.w) - reinterpret_cast<char*>(sd)));
-        } else {
-            set_off(T.lv.rr, carve(N * 8));
-            set_off(T.w, carve(N * 8));
-        }
-    }
-    if (bp_ld_max) set_off(sd->bp_part, carve(8 * (8 * (size_t)bp_ld_max + 8)));
-    for (int k = std::max(1, k_from - 1); k < h->J; ++k) {   // vectors that cross levels
-        SolveLevel& T = sd->L[k];
-        if (k >= k_from) {
-            T.rest.x = T.lv.rr;
-            lay.relocs.push_back((unsigned)(reinterpret_cast<char*>(&T.rest.x) - reinterpret_cast<char*>(sd)));
-        }
-        T.rest.y = sd->L[k + 1].lv.r;
-        lay.relocs.push_back((unsigned)(reinterpret_cast<char*>(&T.rest.y) - reinterpret_cast<char*>(sd)));
-    }
-    {
-        sd->pcg.rp = sd->L[h->J].lv.rp;
-        sd->pcg.ci = sd->L[h->J].lv.ci;
-        sd->pcg.va = sd->L[h->J].lv.va;
-        for (auto* f : {(const void**)&sd->pcg.rp, (const void**)&sd->pcg.ci, (const void**)&sd->pcg.va})
-            lay.relocs.push_back((unsigned)(reinterpret_cast<char*>(f) - reinterpret_cast<char*>(sd)));
-        set_off(sd->pcg.work, carve(4 * (size_t)sd->L[h->J].lv.N * 8));
-    }
-    IPD_REQUIRE(lay.relocs.size() <= (size_t)RELOC_MAX, IPD_E_LIMIT, "LDS image: too many relocations");
-    sd->image_bytes = (int)image_bytes;
+    const ImageLayout lay = image_layout(shapes.data(), plan, spec);
+    // what is packed is what the planner admitted (a rooted image's prediction may count levels above the root)
+    IPD_REQUIRE(lay.total <= spec.lds && lay.total <= IMAGE_LDS_OPTIN, IPD_E_LIMIT, "LDS image: larger than planned");
+    IPD_REQUIRE(lay.pieces.size() <= (size_t)RELOC_MAX, IPD_E_LIMIT, "LDS image: too many relocations");
+    ImagePack pk = bind_layout(ctx, h, st, shapes, plan, spec, lay, sd);
+    sd->image_bytes = (int)lay.image_bytes;
     const char* skip = switch_value("IPD_DEBUG_SKIP");
     sd->dbg_skip = skip ? std::atoi(skip) : 0;
-    sd->lds_total = (int)plan_r16(off);
-    off = plan_r16(off);
-    sd->nreloc = (int)lay.relocs.size();
-    size_t bm = 0;
-    SolveDesc* img = upload_image(ctx, h, st, sd, k_from, off, image_bytes, lay, spec.role == IMG_SOLVE ? nullptr : &bm);
-    switch (spec.role) {
-    case IMG_SOLVE:
-        st->d_solve = img;
-        st->solve_lds = off;
-        break;
-    case IMG_SUB:
-        st->d_sub = img;
-        st->sub_lds = off;
-        st->sub_bm = bm;
-        st->k_sub = plan.k_sub;
-        st->sub_semi_root = plan.sub_semi_root;
-        break;
-    case IMG_SUB3:
-        st->d_sub3 = img;
-        st->sub3_lds = off;
-        st->sub3_bm = bm;
-        break;
-    case IMG_SUB4:
-        st->d_sub4 = img;
-        st->sub4_lds = off;
-        st->sub4_bm = bm;
-        break;
-    case IMG_NONE:
-        break;
-    }
+    sd->lds_total = (int)lay.total;
+    sd->nreloc = (int)pk.relocs.size();
+    out.desc = upload_image(ctx, h, st, sd, spec.k_lds, lay.total, lay.image_bytes, pk, spec.role == IMG_SOLVE ? nullptr : &out.bm);
+    out.lds = lay.total;
 }
-
-static const char* const IMAGE_ROLE_NAMES[] = {"solve", "sub", "sub3", "sub4", "none"};
 
 void amg_prepare_levels(ipd_amg* h) {
     std::unique_ptr<CycleState> st(new CycleState());
@@ -1001,7 +847,6 @@ void amg_prepare_levels(ipd_amg* h) {
     po.smoth = h->opts.smoth;
     po.twogrid = h->opts.twogrid;
     po.concurrent_pair = h->opts.concurrent_pair;
-    po.sol_head = SOL_HEAD;
     const PlanSwitches sw = read_plan_switches();
     const LevelPlan plan = plan_levels(shapes.data(), h->J, po, sw);
     const bool debug = switch_on("IPD_DEBUG_LEVELS");
@@ -1011,12 +856,14 @@ void amg_prepare_levels(ipd_amg* h) {
                          IMAGE_ROLE_NAMES[s.role], s.k_lds, s.k_semi, s.k_tiny, s.k_blk, s.stage_bytes, s.lds,
                          plan.sub5 == s.role ? " (level-5 tail)" : "");
     ipd_ctx* ctx = h->ctx;
-    IPD_OPTIN_LDS(ctx, k_solve_small<true>, 156 * 1024);
-    IPD_OPTIN_LDS(ctx, k_solve_small<false>, 156 * 1024);
-    IPD_OPTIN_LDS(ctx, k_pcg_small<true>, 156 * 1024);
-    IPD_OPTIN_LDS(ctx, k_pcg_small<false>, 156 * 1024);
-    IPD_OPTIN_LDS(ctx, k_subcycle, 156 * 1024);
-    for (const ImageSpec& s : plan.images) pack_image(ctx, h, st.get(), plan, s);
+    IPD_OPTIN_LDS(ctx, k_solve_small<true>, IMAGE_LDS_OPTIN);
+    IPD_OPTIN_LDS(ctx, k_solve_small<false>, IMAGE_LDS_OPTIN);
+    IPD_OPTIN_LDS(ctx, k_pcg_small<true>, IMAGE_LDS_OPTIN);
+    IPD_OPTIN_LDS(ctx, k_pcg_small<false>, IMAGE_LDS_OPTIN);
+    IPD_OPTIN_LDS(ctx, k_subcycle, IMAGE_LDS_OPTIN);
+    st->k_sub = plan.k_sub;
+    st->sub_semi_root = plan.sub_semi_root;
+    for (const ImageSpec& s : plan.images) pack_image(ctx, h, st.get(), shapes, plan, s);
     if (plan.small_ok) {
         st->solve_out = h->arena->alloc<double>(4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2));
         st->small_ok = true;
@@ -1237,8 +1084,8 @@ void amg_cycle(ipd_amg* h, int k, int isnsp, bool wcycle, bool keep_e) {
     const int cu = st->num_cu;
     if (st->k_sub == k) {  // everything from here down: one workgroup, LDS-resident (replicated)
         flush_fused(ctx, st);
-        hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->sub_lds, ctx->stream,
-                           (const SolveDesc*)st->d_sub, keep_e ? 1 : 0);
+        hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->img[IMG_SUB].lds, ctx->stream,
+                           (const SolveDesc*)st->img[IMG_SUB].desc, keep_e ? 1 : 0);
         IPD_KERNEL_CHECK();
         rn.e_zero = false;
         return;
@@ -1412,20 +1259,8 @@ void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, dou
                                ctx->stream));
     else
         IPD_HIP(hipMemsetAsync(xa, 0, sizeof(double) * (size_t)N, ctx->stream));
-    if (st->small_ok && st->shard_ranks == 1) {
-        // small hierarchy: the whole solve phase is one single-workgroup launch
-        if (st->solve_cached)
-            hipLaunchKernelGGL(k_solve_small<true>, dim3(1), dim3(BT), st->solve_lds, ctx->stream,
-                               (const SolveDesc*)st->d_solve, b_dev, xa, xb, st->hist,
-                               st->solve_out, 0);
-        else
-            hipLaunchKernelGGL(k_solve_small<false>, dim3(1), dim3(BT), st->solve_lds, ctx->stream,
-                               (const SolveDesc*)st->d_solve, b_dev, xa, xb, st->hist,
-                               st->solve_out, 0);
-        IPD_KERNEL_CHECK();
-        const size_t nout = 4 + 2 * ((size_t)o.maxit + 2);
-        std::vector<double> out(nout);
-        ctx->fetch(st->solve_out, out.data(), nout);
+    // what a one-launch solve read back: iterations, last relative residual, then the two histories
+    auto deliver = [&](const std::vector<double>& out) {
         const int its = (int)out[0];
         if (rel_resk) std::memcpy(rel_resk, out.data() + 4, sizeof(double) * ((size_t)its + 1));
         if (rhok) std::memcpy(rhok, out.data() + 4 + (o.maxit + 2), sizeof(double) * ((size_t)its + 1));
@@ -1435,21 +1270,29 @@ void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, dou
         if (it_out) *it_out = its;
         if (rel_res_out) *rel_res_out = out[1];
         ctx->sync();
+    };
+    if (st->small_ok && st->shard_ranks == 1) {
+        // small hierarchy: the whole solve phase is one single-workgroup launch
+        if (st->solve_cached)
+            hipLaunchKernelGGL(k_solve_small<true>, dim3(1), dim3(BT), st->img[IMG_SOLVE].lds, ctx->stream,
+                               (const SolveDesc*)st->img[IMG_SOLVE].desc, b_dev, xa, xb, st->hist,
+                               st->solve_out, 0);
+        else
+            hipLaunchKernelGGL(k_solve_small<false>, dim3(1), dim3(BT), st->img[IMG_SOLVE].lds, ctx->stream,
+                               (const SolveDesc*)st->img[IMG_SOLVE].desc, b_dev, xa, xb, st->hist,
+                               st->solve_out, 0);
+        IPD_KERNEL_CHECK();
+        const size_t nout = 4 + 2 * ((size_t)o.maxit + 2);
+        std::vector<double> out(nout);
+        ctx->fetch(st->solve_out, out.data(), nout);
+        deliver(out);
         return;
     }
     if (st->res.ok && st->shard_ranks == 1) {
         // dense regime: the whole solve phase is one launch of co-resident workgroups
         std::vector<double> out;
         if (run_resident(h, st, b_dev, xa, 0, &out, nullptr)) {
-            const int its = (int)out[0];
-            if (rel_resk) std::memcpy(rel_resk, out.data() + 4, sizeof(double) * ((size_t)its + 1));
-            if (rhok) std::memcpy(rhok, out.data() + 4 + (o.maxit + 2), sizeof(double) * ((size_t)its + 1));
-            if (x_dev)
-                IPD_HIP(hipMemcpyAsync(x_dev, xa, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                                       ctx->stream));
-            if (it_out) *it_out = its;
-            if (rel_res_out) *rel_res_out = out[1];
-            ctx->sync();
+            deliver(out);
             return;
         }
         // not usable right now: restore the initial guess and take the multi-launch path
@@ -1642,11 +1485,11 @@ void amg_pcg_small_launch(ipd_amg* h, const PcgSmallVecs& v, double tol, int max
     a.maxit = maxit;
     a.out = v.out;
     if (st->solve_cached)
-        hipLaunchKernelGGL(k_pcg_small<true>, dim3(1), dim3(BT), st->solve_lds, ctx->stream,
-                           (const SolveDesc*)st->d_solve, a);
+        hipLaunchKernelGGL(k_pcg_small<true>, dim3(1), dim3(BT), st->img[IMG_SOLVE].lds, ctx->stream,
+                           (const SolveDesc*)st->img[IMG_SOLVE].desc, a);
     else
-        hipLaunchKernelGGL(k_pcg_small<false>, dim3(1), dim3(BT), st->solve_lds, ctx->stream,
-                           (const SolveDesc*)st->d_solve, a);
+        hipLaunchKernelGGL(k_pcg_small<false>, dim3(1), dim3(BT), st->img[IMG_SOLVE].lds, ctx->stream,
+                           (const SolveDesc*)st->img[IMG_SOLVE].desc, a);
     IPD_KERNEL_CHECK();
 }
 
@@ -1863,12 +1706,12 @@ extern "C" int ipd_amg_bench_cycles(ipd_amg* h, const double* b_dev, double* x_d
             IPD_HIP(hipEventCreate(&e1));
             IPD_HIP(hipEventRecord(e0, ctx->stream));
             if (st->solve_cached)
-                hipLaunchKernelGGL(k_solve_small<true>, dim3(1), dim3(BT), st->solve_lds,
-                                   ctx->stream, (const SolveDesc*)st->d_solve, b_dev, h->x, st->x2,
+                hipLaunchKernelGGL(k_solve_small<true>, dim3(1), dim3(BT), st->img[IMG_SOLVE].lds,
+                                   ctx->stream, (const SolveDesc*)st->img[IMG_SOLVE].desc, b_dev, h->x, st->x2,
                                    st->hist, st->solve_out, cycles);
             else
-                hipLaunchKernelGGL(k_solve_small<false>, dim3(1), dim3(BT), st->solve_lds,
-                                   ctx->stream, (const SolveDesc*)st->d_solve, b_dev, h->x, st->x2,
+                hipLaunchKernelGGL(k_solve_small<false>, dim3(1), dim3(BT), st->img[IMG_SOLVE].lds,
+                                   ctx->stream, (const SolveDesc*)st->img[IMG_SOLVE].desc, b_dev, h->x, st->x2,
                                    st->hist, st->solve_out, cycles);
             IPD_KERNEL_CHECK();
             IPD_HIP(hipEventRecord(e1, ctx->stream));
@@ -1954,7 +1797,7 @@ extern "C" int ipd_amg_bench_subcycle(ipd_amg* h, int reps, double* total_ms, in
         const size_t off = offsetof(SolveDesc, dbg);
         // (a stamp is two s_memrealtime reads and a read-modify-write of global memory, ~0.5 us each: the
         // per-stage figures are for proportions)
-        ctx->upload_bytes(reinterpret_cast<char*>(st->d_sub) + off, &dbg, sizeof(dbg));
+        ctx->upload_bytes(reinterpret_cast<char*>(st->img[IMG_SUB].desc) + off, &dbg, sizeof(dbg));
         {   // a right-hand side that is not zero (a zero one ends every coarse PCG at once)
             std::vector<double> rr((size_t)h->L[st->k_sub].N);
             unsigned lcg = 12345u;
@@ -1967,12 +1810,12 @@ extern "C" int ipd_amg_bench_subcycle(ipd_amg* h, int reps, double* total_ms, in
         hipEvent_t e0, e1;
         IPD_HIP(hipEventCreate(&e0));
         IPD_HIP(hipEventCreate(&e1));
-        hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->sub_lds, ctx->stream,
-                           (const SolveDesc*)st->d_sub, 0);
+        hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->img[IMG_SUB].lds, ctx->stream,
+                           (const SolveDesc*)st->img[IMG_SUB].desc, 0);
         IPD_HIP(hipEventRecord(e0, ctx->stream));
         for (int r = 0; r < reps; ++r)
-            hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->sub_lds, ctx->stream,
-                               (const SolveDesc*)st->d_sub, 0);
+            hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->img[IMG_SUB].lds, ctx->stream,
+                               (const SolveDesc*)st->img[IMG_SUB].desc, 0);
         IPD_HIP(hipEventRecord(e1, ctx->stream));
         IPD_HIP(hipEventSynchronize(e1));
         IPD_KERNEL_CHECK();
@@ -1988,7 +1831,7 @@ extern "C" int ipd_amg_bench_subcycle(ipd_amg* h, int reps, double* total_ms, in
         if (stamps)
             for (int i = 0; i < 8; ++i) stamps[i] = hs[i];
         long long* none = nullptr;
-        ctx->upload_bytes(reinterpret_cast<char*>(st->d_sub) + off, &none, sizeof(none));
+        ctx->upload_bytes(reinterpret_cast<char*>(st->img[IMG_SUB].desc) + off, &none, sizeof(none));
     });
 }
 

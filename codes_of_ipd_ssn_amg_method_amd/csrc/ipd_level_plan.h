@@ -2,12 +2,14 @@
 // each level's form (polynomial, block-wide polynomial, dense thread-per-row, thread-per-row, tiny
 // dense) and which LDS images are packed -- the whole solve, the sub-cycle and the images rooted at
 // levels 3 and 4 the resident kernels take -- with their LDS budget.  amg_prepare_levels packs what it
-// returns (pack_image, ipd_cycle_host.h).  Host-clean, no HIP: tests/level_plan_driver.cpp runs it on
-// the CPU.
+// returns (pack_image, ipd_cycle_host.h).  What an image holds -- its pieces, their sizes and LDS offsets
+// -- is written down here once (image_layout): plan_lds sums the pieces to decide what fits, pack_image
+// binds them to the descriptor.  Host-clean, no HIP: tests/level_plan_driver.cpp runs it on the CPU.
 #pragma once
 
 #include <algorithm>
 #include <cstddef>
+#include <numeric>
 #include <vector>
 
 #include "ipd_limits.h"
@@ -24,7 +26,7 @@ struct PlanOptions {
     char cycle = 'v';
     int smoth = 1;
     bool twogrid = false, concurrent_pair = false;
-    size_t sol_head = 0;   // SOL_HEAD: the image head (SolveDesc and its relocation table)
+    size_t sol_head = SOL_HEAD;   // the image head (SolveDesc and its relocation table)
 };
 
 // The switches of the level planner and of the resident planner (ipd_switches.h), read by read_plan_switches
@@ -49,6 +51,169 @@ struct ImageSpec {
     int k_blk;            // first thread-per-row level (J + 1: none, the generic phases)
     size_t stage_bytes;   // staging area in front of the image
     size_t lds;           // predicted dynamic LDS (plan_lds)
+    int k_cached;         // the first level that plan_lds run cached (<= k_lds; k_semi + 1 under a semi-cached root)
+};
+
+static inline size_t plan_r8(size_t n) { return (n + 7) / 8 * 8; }
+static inline size_t plan_r16(size_t b) { return (b + 15) / 16 * 16; }
+static inline size_t poly_ld(size_t rows) { return rows <= 32 ? 32 : (rows <= 48 ? 48 : 64); }
+static inline int bpoly_ld(int N, int Nc) { return N + Nc <= 128 ? 128 : 256; }
+static inline size_t bp_part_bytes(size_t LD) { return 8 * (8 * LD + 8); }   // partial sums of a block-wide polynomial pass
+
+// ---- What an image is made of ---------------------------------------------------------------------------
+// The form of a level in an image: semi-cached root (vectors only), CSR arrays (thread-per-row, or the
+// generic phases), dense thread-per-row copy, tiny dense, one-wave polynomial, block-wide polynomial out
+// of LDS, block-wide polynomial with the operators in L2
+enum LevelForm { FORM_SEMI, FORM_CSR, FORM_BDENSE, FORM_TINY, FORM_POLY, FORM_LPOLY, FORM_BPOLY };
+static inline bool block_wide(LevelForm f) { return f == FORM_LPOLY || f == FORM_BPOLY; }
+static inline bool polynomial(LevelForm f) { return f == FORM_POLY || block_wide(f); }
+static inline LevelForm level_form(const ImageSpec& s, int k, bool poly, bool lpoly, bool bpoly, bool bdense) {
+    if (k == s.k_semi) return FORM_SEMI;
+    const bool tiny = k >= s.k_tiny;
+    if (s.k_blk <= k) {
+        if (tiny ? poly : lpoly) return tiny ? FORM_POLY : FORM_LPOLY;
+        if (!tiny && bpoly) return FORM_BPOLY;
+        if (!tiny && bdense) return FORM_BDENSE;
+    }
+    return tiny ? FORM_TINY : FORM_CSR;
+}
+
+// The pointers of the descriptor (SolveDesc) that point into LDS, in the order of the image
+enum ImageSlot {
+    SLOT_RP, SLOT_CI, SLOT_VA, SLOT_DINV, SLOT_AXI, SLOT_XX,                              // the level's constants
+    SLOT_REST_RP, SLOT_REST_CI, SLOT_REST_VA, SLOT_PROL_RP, SLOT_PROL_CI, SLOT_PROL_VA,   // transfers to level k + 1
+    SLOT_LMAP, SLOT_DA, SLOT_DP, SLOT_DPT, SLOT_PMR, SLOT_PME, SLOT_PMC, SLOT_PW,         // blocks computed into the image
+    SLOT_R, SLOT_E, SLOT_E2, SLOT_RR, SLOT_W,                                             // work vectors
+    SLOT_BP_PART, SLOT_PCG_WORK,                                                          // work areas: image-wide, coarsest level
+    SLOT_REST_X, SLOT_REST_Y, SLOT_PCG_RP, SLOT_PCG_CI, SLOT_PCG_VA,                      // always aliases
+    SLOT_COUNT
+};
+// how a piece gets its content: copied from global memory, computed by k_pack_dense / k_pack_lmap /
+// k_pack_poly, a work vector (zeroed on arrival), or the address of another piece
+enum PieceKind { PIECE_COPY, PIECE_DENSE, PIECE_LMAP, PIECE_POLY, PIECE_WORK, PIECE_ALIAS };
+static inline PieceKind slot_kind(ImageSlot s) {
+    return s <= SLOT_PROL_VA ? PIECE_COPY : s == SLOT_LMAP ? PIECE_LMAP : s <= SLOT_DPT ? PIECE_DENSE : s <= SLOT_PW ? PIECE_POLY : PIECE_WORK;
+}
+
+// which slots a level of a given form owns (transfers: above the coarsest level only; lane map: see has)
+static constexpr unsigned slot_bits(int first, int last) { return ((2u << last) - 1u) & ~((1u << first) - 1u); }
+static constexpr unsigned SLOTS_VECTORS = slot_bits(SLOT_R, SLOT_W), SLOTS_XFER = slot_bits(SLOT_REST_RP, SLOT_PROL_VA),
+                          SLOTS_ROWS = slot_bits(SLOT_RP, SLOT_RP) | slot_bits(SLOT_DINV, SLOT_XX) | SLOTS_XFER | SLOTS_VECTORS;
+static constexpr unsigned FORM_SLOTS[] = {
+    /* FORM_SEMI   */ SLOTS_VECTORS,
+    /* FORM_CSR    */ SLOTS_ROWS | slot_bits(SLOT_CI, SLOT_VA) | slot_bits(SLOT_LMAP, SLOT_LMAP),
+    /* FORM_BDENSE */ SLOTS_ROWS | slot_bits(SLOT_DA, SLOT_DA),
+    /* FORM_TINY   */ SLOTS_ROWS | slot_bits(SLOT_CI, SLOT_VA) | slot_bits(SLOT_DA, SLOT_DPT),
+    /* FORM_POLY   */ slot_bits(SLOT_XX, SLOT_XX) | slot_bits(SLOT_PMR, SLOT_PW) | SLOTS_VECTORS,
+    /* FORM_LPOLY  */ slot_bits(SLOT_XX, SLOT_XX) | slot_bits(SLOT_PMR, SLOT_PW) | SLOTS_VECTORS,
+    /* FORM_BPOLY  */ slot_bits(SLOT_XX, SLOT_XX) | SLOTS_VECTORS};
+
+// Level k of an image in a given form: which pieces it owns and how large they are
+struct LevelPieces {
+    const LevelShape* L;
+    int J, k;
+    LevelForm form;
+    bool lean;      // rr and w are never dereferenced: aliases of e2 (see choose_forms)
+    bool lmap_ok;   // a thread-per-row level that takes a lane map (unless it is the coarsest)
+    bool pad8;      // vectors zero-padded to whole 8-entry blocks (one-wave levels: sol_load_image; polynomial
+                    // levels and the children of block-wide ones: bpoly_pass)
+
+    size_t ld() const {   // leading dimension of the level's polynomial operators
+        return form == FORM_POLY    ? poly_ld((size_t)L[k].nr + (size_t)L[k + 1].nr)
+               : form == FORM_LPOLY ? 64
+                                    : (size_t)bpoly_ld(L[k].nr, L[k + 1].nr);
+    }
+    // (dense thread-per-row levels: whole groups of four entries per lane, dense_row_dot)
+    size_t vec_len() const {
+        return form == FORM_BDENSE ? (size_t)bdense_pad(L[k].nr) : pad8 ? plan_r8((size_t)L[k].nr) : (size_t)L[k].nr;
+    }
+    bool has(ImageSlot s) const {
+        if (s == SLOT_PCG_WORK) return k == J;
+        if (s > SLOT_W || !(FORM_SLOTS[form] >> s & 1u)) return false;
+        if (s == SLOT_LMAP) return lmap_ok && k < J;
+        return k < J || !((SLOTS_XFER | slot_bits(SLOT_DP, SLOT_DPT)) >> s & 1u);
+    }
+    bool alias(ImageSlot s) const { return lean && (s == SLOT_RR || s == SLOT_W); }
+    size_t bytes(ImageSlot s) const {
+        const size_t N = (size_t)L[k].nr, nnz = (size_t)L[k].nnz, Nc = k < J ? (size_t)L[k + 1].nr : 0,
+                     np = k < J ? (size_t)L[k + 1].p_nnz : 0, LD = polynomial(form) ? ld() : 0, v = 8 * vec_len();
+        const size_t in_slot_order[] = {
+            4 * (N + 1), 4 * nnz, 8 * nnz, 8 * N, 8 * N, 8,                                         // rp ci va dinv Axi xx
+            4 * (Nc + 1), 4 * np, 8 * np, 4 * (N + 1), 4 * np, 8 * np,                              // rest, prol: rp ci va
+            4 * ((size_t)BT + 1), form == FORM_BDENSE ? 8 * N * (size_t)bdense_ld((int)N) : 8 * N * N, 8 * N * Nc, 8 * N * Nc,   // lmap dA dP dPt
+            8 * LD * plan_r8(N), 8 * LD * plan_r8(N), 8 * LD * plan_r8(Nc), 8 * LD,                 // pMr pMe pMc pW
+            v, v, v, v, v, 0, 4 * N * 8};                                                           // r e e2 rr w, -, pcg.work
+        return s <= SLOT_PCG_WORK ? in_slot_order[s] : 0;
+    }
+    size_t sum() const {   // LDS the level's own pieces take
+        size_t b = 0;
+        for (int s = SLOT_RP; s <= SLOT_PCG_WORK; ++s)
+            if (has((ImageSlot)s) && !alias((ImageSlot)s)) b += plan_r16(bytes((ImageSlot)s));
+        return b;
+    }
+};
+static inline LevelPieces level_pieces(const LevelShape* L, int J, const ImageSpec& s, bool lean_vectors, int k,
+                                       LevelForm form, bool below_block_wide) {
+    LevelPieces p{L, J, k, form, false, false, false};
+    p.lean = lean_vectors && s.k_blk <= std::max(2, s.k_lds) && k >= 2;
+    p.lmap_ok = lean_vectors && form == FORM_CSR && s.k_blk <= k && k >= 2 && L[k].nr <= BT;
+    p.pad8 = k >= s.k_tiny || polynomial(form) || below_block_wide;
+    return p;
+}
+
+// What plan_lds counts on top of the pieces.  Every term is an over-count, kept because it decides which
+// levels are admitted near the budget: dropping one changes plans.
+static constexpr size_t RESERVE_HEAD = 256;           // once per image; nothing is carved for it
+static constexpr size_t RESERVE_XX_POLY = 16;         // a polynomial level's 16-byte xx slot is counted as 32 B ...
+static constexpr size_t RESERVE_XX_BPOLY = 32;        // ... and as 48 B where the operators stay in L2
+static constexpr size_t RESERVE_CHILD_PAD = 5 * 64;   // bounds the padding of the vectors of a level below a block-wide polynomial
+                                                      // one (carved: at most 3 x 48 B, none under a parent outside the image)
+enum Reserve {
+    RSV_HEAD, RSV_XX,
+    RSV_BP_PART,         // bp_part is counted for every block-wide polynomial level, carved once at the largest LD
+    RSV_CHILD_PAD,
+    RSV_COARSEST_LMAP,   // the lane map is counted for a thread-per-row coarsest level, which gets none
+    RSV_CONST_PAD,       // dinv and Axi are counted at the padded length of the level's work vectors
+    RSV_ABOVE_ROOT,      // levels the plan_lds run cached above the root of the image (ImageSpec::k_cached)
+    RSV_COUNT
+};
+struct ImageReserves {
+    size_t of[RSV_COUNT] = {};
+    size_t sum() const { return std::accumulate(of, of + RSV_COUNT, (size_t)0); }
+};
+// level k as plan_lds counts it -- deepest first, before the image it ends up in is known: as the root of an
+// image of its own
+static inline ImageSpec level_alone(int k, int tiny_lo) {
+    return ImageSpec{IMG_NONE, k, 0, std::max(tiny_lo, std::max(2, k)), std::max(2, k), 0, 0, k};
+}
+static inline ImageReserves level_reserves(const LevelPieces& p, bool below_block_wide) {
+    ImageReserves r;
+    if (polynomial(p.form)) r.of[RSV_XX] = p.form == FORM_BPOLY ? RESERVE_XX_BPOLY : RESERVE_XX_POLY;
+    if (block_wide(p.form)) r.of[RSV_BP_PART] = plan_r16(bp_part_bytes(p.ld()));
+    if (!polynomial(p.form)) {
+        r.of[RSV_CONST_PAD] = 2 * (plan_r16(8 * p.vec_len()) - plan_r16(8 * (size_t)p.L[p.k].nr));
+        if (below_block_wide) r.of[RSV_CHILD_PAD] = RESERVE_CHILD_PAD;
+        if (p.lmap_ok && p.k == p.J) r.of[RSV_COARSEST_LMAP] = plan_r16(p.bytes(SLOT_LMAP));
+    }
+    return r;
+}
+
+struct ImagePiece {
+    int level;   // 0: image-wide
+    ImageSlot slot;
+    PieceKind kind;
+    size_t bytes;   // as copied or computed; the next piece starts plan_r16(bytes) further on
+    size_t off;     // LDS offset from the start of dynamic LDS (the staging area included); PIECE_ALIAS: of the other piece
+};
+struct ImageLayout {
+    std::vector<ImagePiece> pieces;   // in the order of the image; each is one relocation of the descriptor
+    size_t image_bytes = 0;           // head, constants and computed blocks: what is copied to LDS behind the staging area
+    size_t total = 0;                 // dynamic LDS of a launch: staging area, image, work vectors
+    const ImagePiece* find(int level, ImageSlot slot) const {
+        for (const ImagePiece& p : pieces)
+            if (p.level == level && p.slot == slot) return &p;
+        return nullptr;
+    }
 };
 
 struct LevelPlan {
@@ -69,12 +234,64 @@ struct LevelPlan {
             if (s.role == r) return &s;
         return nullptr;
     }
+    LevelForm form(const ImageSpec& s, int k) const {
+        return level_form(s, k, poly[(size_t)k], lpoly[(size_t)k], bpoly[(size_t)k], bdense[(size_t)k]);
+    }
+    LevelPieces pieces(const LevelShape* L, const ImageSpec& s, int k) const {
+        return level_pieces(L, J, s, lean_vectors, k, form(s, k), k > s.k_lds && block_wide(form(s, k - 1)));
+    }
     // level k of image s is a thread-per-row level (BT threads dealt to its rows)
     bool thread_per_row(const ImageSpec& s, int k) const {
-        return k >= std::max(s.k_lds, s.k_blk) && k < s.k_tiny && k <= J && k != s.k_semi && !poly[(size_t)k] &&
-               !lpoly[(size_t)k] && !bpoly[(size_t)k];
+        return k >= std::max(s.k_lds, s.k_blk) && k <= J && (form(s, k) == FORM_CSR || form(s, k) == FORM_BDENSE);
     }
 };
+
+// The image of spec s, piece by piece: the constants of levels k_lds..J, lane maps, dense thread-per-row
+// copies, block-wide polynomial operators, one-wave polynomial or tiny dense blocks; behind the image the
+// work vectors, bp_part and the coarsest PCG's work area.  (s.k_lds <= J: a solve with nothing cached has none.)
+inline ImageLayout image_layout(const LevelShape* L, const LevelPlan& plan, const ImageSpec& s) {
+    constexpr unsigned ANY_FORM = ~0u;
+    ImageLayout lay;
+    const int J = plan.J;
+    size_t off = s.stage_bytes + SOL_HEAD;
+    auto place = [&](int k, ImageSlot slot, PieceKind kind, size_t bytes) {
+        lay.pieces.push_back(ImagePiece{k, slot, kind, bytes, off});
+        off += plan_r16(bytes);
+    };
+    auto alias = [&](int k, ImageSlot slot, int of_level, ImageSlot of_slot) {
+        lay.pieces.push_back(ImagePiece{k, slot, PIECE_ALIAS, 0, lay.find(of_level, of_slot)->off});
+    };
+    auto pass = [&](ImageSlot first, ImageSlot last, unsigned forms) {
+        for (int k = s.k_lds; k <= J; ++k) {
+            const LevelPieces p = plan.pieces(L, s, k);
+            if (!(forms >> p.form & 1u)) continue;
+            for (int q = first; q <= last; ++q) {
+                const ImageSlot slot = (ImageSlot)q;
+                if (!p.has(slot)) continue;
+                p.alias(slot) ? alias(k, slot, k, SLOT_E2) : place(k, slot, slot_kind(slot), p.bytes(slot));
+            }
+        }
+    };
+    pass(SLOT_RP, SLOT_PROL_VA, ANY_FORM);
+    pass(SLOT_LMAP, SLOT_LMAP, ANY_FORM);
+    pass(SLOT_DA, SLOT_DA, 1u << FORM_BDENSE);
+    pass(SLOT_PMR, SLOT_PW, 1u << FORM_LPOLY);
+    pass(SLOT_DA, SLOT_PW, 1u << FORM_TINY | 1u << FORM_POLY);
+    lay.image_bytes = off - s.stage_bytes;
+    pass(SLOT_R, SLOT_W, ANY_FORM);
+    size_t bp_ld = 0;
+    for (int k = s.k_lds; k < J; ++k)
+        if (block_wide(plan.form(s, k))) bp_ld = std::max(bp_ld, plan.pieces(L, s, k).ld());
+    if (bp_ld) place(0, SLOT_BP_PART, PIECE_WORK, bp_part_bytes(bp_ld));
+    for (int k = std::max(1, s.k_lds - 1); k < J; ++k) {   // vectors that cross levels
+        if (k >= s.k_lds) alias(k, SLOT_REST_X, k, SLOT_RR);
+        alias(k, SLOT_REST_Y, k + 1, SLOT_R);
+    }
+    for (int q = 0; q < 3; ++q) alias(0, (ImageSlot)(SLOT_PCG_RP + q), J, (ImageSlot)(SLOT_RP + q));   // the coarsest PCG's CSR arrays
+    pass(SLOT_PCG_WORK, SLOT_PCG_WORK, ANY_FORM);
+    lay.total = off;
+    return lay;
+}
 
 // Conditions of the resident planner (ipd_resident_plan.h) that this one anticipates when it packs images for it
 // workgroups of k_resident: one wave per row of the larger block of level 1 and of level 2
@@ -87,11 +304,6 @@ static inline bool resident_poly3_root_fits(int N4, int G) { return N4 <= G && N
 static inline bool resident_deep_sizes_fit(int nf, int nc, int N2, int N3, int N4) {
     return nf <= RB_HALF && nc <= RB_HALF && N2 == nc && N3 <= RB_N3MAX && N4 <= RB_N4MAX;
 }
-
-static inline size_t plan_r8(size_t n) { return (n + 7) / 8 * 8; }
-static inline size_t plan_r16(size_t b) { return (b + 15) / 16 * 16; }
-static inline size_t poly_ld(size_t rows) { return rows <= 32 ? 32 : (rows <= 48 ? 48 : 64); }
-static inline int bpoly_ld(int N, int Nc) { return N + Nc <= 128 ? 128 : 256; }
 
 struct LevelPlanner {
     const LevelShape* L;   // 1..J
@@ -145,51 +357,23 @@ struct LevelPlanner {
         const long long N = L[k].nr;
         return N > 32 && N <= 96 && bdense_pad((int)N) / bdense_lanes((int)N) <= BDENSE_Q && 3LL * L[k].nnz >= N * N;
     }
-    // LDS cache plan: deepest levels first, while they fit; returns the first cached level
+    // level k as plan_lds counts it (level_alone): its form there
+    LevelForm form_alone(int k) const {
+        return level_form(level_alone(k, tiny_lo), k, is_poly(k), is_lpoly(k), is_bpoly(k), is_bdense(k));
+    }
+    // LDS cache plan: deepest levels first, while they fit; returns the first cached level.  A level counts
+    // with its pieces in its form (LevelPieces) and the reserves named above.
     int plan_lds(size_t stage, size_t* used_out) const {
-        size_t used = stage + o.sol_head + 256;
-        const size_t budget = 150 * 1024;
+        size_t used = stage + o.sol_head + RESERVE_HEAD;
         int k_lds = J + 1;
         for (int k = J; k >= 1; --k) {
-            const size_t N = (size_t)L[k].nr;
-            size_t bytes;
-            if (is_poly(k)) {
-                // polynomial form: [M2a; ..] and [M1; ..] stacked with the restriction, M1 P, w; three
-                // vectors; none of the level's CSR arrays (its parent applies the transfers to and from it)
-                const size_t Nc = (size_t)L[k + 1].nr, LD = poly_ld(N + Nc);
-                bytes = 2 * (8 * LD * plan_r8(N)) + 8 * LD * plan_r8(Nc) + 8 * LD + 3 * plan_r16(8 * plan_r8(N)) + 32;
-            } else if (is_lpoly(k)) {
-                const size_t Nc = (size_t)L[k + 1].nr, LD = 64;
-                bytes = 2 * (8 * LD * plan_r8(N)) + 8 * LD * plan_r8(Nc) + 8 * LD + 3 * plan_r16(8 * plan_r8(N)) + 32 +
-                        8 * (8 * LD + 8);
-            } else if (is_bpoly(k)) {
-                // block-wide polynomial form: the operators stay in global memory; three vectors and the
-                // partial sums of a pass
-                bytes = 3 * plan_r16(8 * plan_r8(N)) + 48 + 8 * (8 * (size_t)bpoly_ld(L[k].nr, L[k + 1].nr) + 8);
-            } else {
-                // (the thread-per-row sub-cycle deals BT threads to the rows: a level of more than BT rows cannot
-                // be held that way -- it fits the budget once its child's operators stay in L2, block-wide
-                // polynomial form of a 150-224-row level 4 below a 576-row level 3)
-                if (k >= 2 && N > (size_t)BT) break;
-                bytes = plan_r16(4 * (N + 1)) +
-                        (is_bdense(k) ? plan_r16(8 * N * (size_t)bdense_ld((int)N))
-                                      : plan_r16(4 * (size_t)L[k].nnz) + plan_r16(8 * (size_t)L[k].nnz)) +
-                        ((lean_vectors && k >= 2) ? 5 : 7) *
-                            plan_r16(8 * (k >= tiny_lo ? plan_r8(N) : is_bdense(k) ? (size_t)bdense_pad((int)N) : N)) +
-                        16;
-                if (k < J) {
-                    const size_t Nc = (size_t)L[k + 1].nr, np = (size_t)L[k + 1].p_nnz;
-                    bytes += plan_r16(4 * (Nc + 1)) + plan_r16(4 * (N + 1)) + 2 * (plan_r16(4 * np) + plan_r16(8 * np));
-                }
-                if (k == J) bytes += plan_r16(4 * 8 * N);
-                if (use_lmap && !is_bdense(k) && k >= 2 && k < tiny_lo && N <= (size_t)BT) bytes += plan_r16(4 * (BT + 1));   // lane map
-                if (k >= 3 && (is_bpoly(k - 1) || is_lpoly(k - 1))) bytes += 5 * 64;   // its vectors are padded to whole 8-entry blocks
-                if (k >= tiny_lo) {   // dense copies of the tiny levels
-                    bytes += plan_r16(8 * N * N);
-                    if (k < J) bytes += 2 * plan_r16(8 * N * (size_t)L[k + 1].nr);
-                }
-            }
-            if (used + bytes > budget) break;
+            const LevelPieces p = level_pieces(L, J, level_alone(k, tiny_lo), lean_vectors, k, form_alone(k), false);
+            // (the thread-per-row sub-cycle deals BT threads to the rows: a level of more than BT rows cannot
+            // be held that way -- it fits the budget once its child's operators stay in L2, block-wide
+            // polynomial form of a 150-224-row level 4 below a 576-row level 3)
+            if (!polynomial(p.form) && k >= 2 && L[k].nr > BT) break;
+            const size_t bytes = p.sum() + level_reserves(p, k >= 2 && block_wide(form_alone(k - 1))).sum();
+            if (used + bytes > IMAGE_LDS_BUDGET) break;
             used += bytes;
             k_lds = k;
         }
@@ -210,11 +394,11 @@ struct LevelPlanner {
         const int k_lds = plan_lds(stage, &used);
         if (k_lds != 3) return 0;   // <= 2: level 2 fits entirely; > 3: a deeper level does not
         const size_t need = used + 3 * plan_r16(8 * (size_t)L[2].nr);
-        return need <= 150 * 1024 ? need : 0;
+        return need <= IMAGE_LDS_BUDGET ? need : 0;
     }
     // an image rooted at level k (the sub-cycle and the resident kernels' tails)
-    ImageSpec rooted(ImageRole role, int k, bool semi, size_t stage, size_t lds) const {
-        return ImageSpec{role, k, semi ? k : 0, tiny_from(k + (semi ? 1 : 0)), blk_from(k), stage, lds};
+    ImageSpec rooted(ImageRole role, int k, bool semi, size_t stage, size_t lds, int k_cached) const {
+        return ImageSpec{role, k, semi ? k : 0, tiny_from(k + (semi ? 1 : 0)), blk_from(k), stage, lds, k_cached};
     }
 
     void choose_forms();
@@ -270,7 +454,7 @@ inline void LevelPlanner::plan_solve(LevelPlan& p) const {
     const size_t stage = plan_r16(sizeof(double) * maxlen);
     size_t used = 0;
     const int k_lds = plan_lds(stage, &used);
-    p.images.push_back(ImageSpec{IMG_SOLVE, k_lds, 0, tiny_from(k_lds), blk_from(k_lds), stage, used});
+    p.images.push_back(ImageSpec{IMG_SOLVE, k_lds, 0, tiny_from(k_lds), blk_from(k_lds), stage, used, k_lds});
     p.small_ok = true;
 }
 
@@ -279,7 +463,7 @@ inline void LevelPlanner::plan_solve(LevelPlan& p) const {
 inline void LevelPlanner::plan_sub(LevelPlan& p) const {
     if (sw.no_subcycle || p.small_ok || J > SOLVE_ML || J < 3 || !cyc) return;
     if (const size_t need = semi_plan(16)) {   // (b1) the sub-cycle is rooted at the semi-cached level 2
-        p.images.push_back(rooted(IMG_SUB, 2, true, 16, need));
+        p.images.push_back(rooted(IMG_SUB, 2, true, 16, need, 3));
         p.k_sub = 2;
         return;
     }
@@ -315,9 +499,9 @@ inline void LevelPlanner::plan_sub(LevelPlan& p) const {
         const size_t semi_need = used + 3 * plan_r16(8 * (size_t)L[kroot].nr);
         const bool semi_root = k_lds == kroot + 1 && kroot >= 3 && lean_vectors && L[kroot].nr <= BT &&
                                (double)L[kroot].nnz <= 12.0 * L[kroot].nr &&
-                               (double)L[kroot + 1].p_nnz <= 12.0 * L[kroot].nr && semi_need <= 150 * 1024;
+                               (double)L[kroot + 1].p_nnz <= 12.0 * L[kroot].nr && semi_need <= IMAGE_LDS_BUDGET;
         if (k_lds > kroot && !semi_root) continue;
-        p.images.push_back(rooted(IMG_SUB, kroot, semi_root, stage, semi_root ? semi_need : used));
+        p.images.push_back(rooted(IMG_SUB, kroot, semi_root, stage, semi_root ? semi_need : used, k_lds));
         p.k_sub = kroot;
         p.sub_semi_root = semi_root;
         return;
@@ -341,7 +525,8 @@ inline void LevelPlanner::plan_tails(LevelPlan& p) const {
         L[4].nr <= BT && L[3].maxoff <= 512 && L[1].nf > 0 && !sw.no_resident_three && !sw.no_resident) {
         bool ok = lean_vectors;
         for (int k = 4; k <= J && ok; ++k) ok = small_level(k);
-        if (ok && plan_lds(16, &used) <= 4) p.images.push_back(rooted(IMG_SUB4, 4, false, 16, used));
+        const int k_lds = ok ? plan_lds(16, &used) : J + 1;
+        if (k_lds <= 4) p.images.push_back(rooted(IMG_SUB4, 4, false, 16, used, k_lds));
     }
     // (b3) No sub-cycle at all because level 3's interpolation is big (P_3 with more than 40 k entries:
     // a dense 1024 x 50 block early in a run), although levels 3..J themselves are small: the launch
@@ -352,7 +537,8 @@ inline void LevelPlanner::plan_tails(LevelPlan& p) const {
         cyc && !sw.no_resident && !sw.no_subcycle) {
         bool ok = true;
         for (int k = 3; k <= J && ok; ++k) ok = small_level(k, 3);
-        if (ok && plan_lds(16, &used) <= 3) p.images.push_back(rooted(IMG_SUB3, 3, false, 16, used));
+        const int k_lds = ok ? plan_lds(16, &used) : J + 1;
+        if (k_lds <= 3) p.images.push_back(rooted(IMG_SUB3, 3, false, 16, used, k_lds));
     }
     // (b4) the image rooted at level 5 (see root5, plan_sub) is the one the deep mode's tail workgroup takes
     if (p.k_sub == 5 && !p.sub_semi_root && J >= 6 && L[1].nr > RES_NMAX) p.sub5 = IMG_SUB;

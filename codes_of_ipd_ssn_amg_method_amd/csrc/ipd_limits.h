@@ -22,6 +22,14 @@ static constexpr int STAGE_MAX = 7680;   // vector entries staged in LDS (60 KiB
 
 // levels a single-workgroup image (SolveDesc) holds
 static constexpr int SOLVE_ML = 24;
+// An LDS image (ipd_level_plan.h): the planner admits levels while the predicted dynamic LDS stays within the
+// budget; the kernels that run out of an image opt in to a little more (an image's operator copy, SolveDesc::bm_src,
+// goes behind it).  The head of an image is the descriptor and its relocation table of RELOC_MAX words:
+// SOL_HEAD == sol_r16(sizeof(SolveDesc)) + sol_r16(4 * RELOC_MAX), asserted where SolveDesc is defined.
+static constexpr size_t IMAGE_LDS_BUDGET = (size_t)150 * 1024;
+static constexpr size_t IMAGE_LDS_OPTIN = (size_t)156 * 1024;
+static constexpr int RELOC_MAX = 640;
+static constexpr size_t SOL_HEAD = 12592;
 
 // most iterations the one-launch AMG-PCG (k_pcg_small) is asked for: at ~0.3 ms per iteration a launch
 // then cannot outlast ~0.3 s; a call with a larger maxit runs as launches
@@ -47,7 +55,7 @@ static constexpr int RES_NMAX = 4 * BT;        // rows per level (fixed LDS slot
 static constexpr int RES_P4_SEG = 128;         // ... of ResDesc::p4rows: 128 + 128 + 64
 static constexpr int RES_TAIL_MAX = 64;        // rows of the redundantly solved tail level
 static constexpr size_t RES_LDS_BYTES = sizeof(double) * ((size_t)9 * RES_NMAX + RES_NMAX / 2 + 3 * RES_TAIL_MAX + 16 * RES_WAVES + 12);
-static constexpr size_t RES_LDS_MAX = (size_t)156 * 1024;   // dynamic LDS a resident launch may ask for (its own or its tail image's)
+static constexpr size_t RES_LDS_MAX = IMAGE_LDS_OPTIN;   // dynamic LDS a resident launch may ask for (its own or its tail image's)
 
 // mask-form resident kernel (ipd_resident_big.h)
 static constexpr int RB_NMAX = 8 * BT;                 // rows of level 1

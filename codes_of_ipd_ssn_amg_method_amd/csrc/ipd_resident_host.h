@@ -60,14 +60,13 @@ static ResidentInputs resident_inputs(const ipd_amg* h, const CycleState* st, co
     in.num_cu = st->num_cu;
     in.small_ok = st->small_ok;
     in.k_sub = st->k_sub;
-    in.img[IMG_SUB] = ResidentImage{st->d_sub != nullptr, st->sub_lds, st->sub_bm};
-    in.img[IMG_SUB3] = ResidentImage{st->d_sub3 != nullptr, st->sub3_lds, st->sub3_bm};
-    in.img[IMG_SUB4] = ResidentImage{st->d_sub4 != nullptr, st->sub4_lds, st->sub4_bm};
+    for (ImageRole r : {IMG_SUB, IMG_SUB3, IMG_SUB4})
+        in.img[r] = ResidentImage{st->img[r].desc != nullptr, st->img[r].lds, st->img[r].bm};
     in.sub5 = st->sub5;
     return in;
 }
 static const SolveDesc* resident_image(const CycleState* st, ImageRole r) {
-    return r == IMG_SUB ? st->d_sub : r == IMG_SUB3 ? st->d_sub3 : r == IMG_SUB4 ? st->d_sub4 : nullptr;
+    return r == IMG_SUB || r == IMG_SUB3 || r == IMG_SUB4 ? st->img[r].desc : nullptr;
 }
 
 // level k's rows as the plan wants them: the launches' padded copy or a private one with stride p.S[k] (k_pad_build)
@@ -162,7 +161,7 @@ static void prepare_resident(ipd_amg* h, CycleState* st, const std::vector<Level
     if (p.considered && switch_on("IPD_DEBUG_LEVELS"))
         std::fprintf(stderr, "[ipd] resident plan: J=%d nf=%d nc=%d S1=%d S2=%d S3=%d N4=%d Nt=%d k_sub=%d sub_lds=%zu\n", h->J,
                      h->L[1].nf, h->L[1].A.nr - h->L[1].nf, p.S[1], p.S[2], st->run[3].dev.S,
-                     h->J >= 4 ? h->L[4].A.nr : 0, h->L[3].A.nr, st->k_sub, st->sub_lds);
+                     h->J >= 4 ? h->L[4].A.nr : 0, h->L[3].A.nr, st->k_sub, st->img[IMG_SUB].lds);
     if (p.kind == RESIDENT_NONE) return;
     const Level& l1 = h->L[1];
     const Level& l2 = h->L[2];

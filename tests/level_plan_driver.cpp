@@ -5,6 +5,14 @@
 //   plan <small_ok> <k_sub> <sub_semi_root> <sub5 role> <use_poly> <tiny_lo>
 //   image <role> <k_lds> <k_semi> <k_tiny> <k_blk> <stage> <lds> <rows of its largest thread-per-row level k >= 2>
 //   end
+// and, between an image line and the next, the image as image_layout lays it out (none for a solve with
+// nothing cached):
+//   level <k> <form> <rows>                       one per level of the image
+//   piece <level> <slot> <kind> <bytes> <offset>  in the order of the image
+//   layout <image_bytes> <total> <relocations> <k_cached> then the named reserves of the prediction:
+//          <head> <xx> <bp_part> <child_pad> <coarsest_lmap> <const_pad> <above_root>
+// The first line of the output is
+//   limits <IMAGE_LDS_BUDGET> <IMAGE_LDS_OPTIN> <RELOC_MAX> <SOL_HEAD> <BT>
 #include <cstdio>
 #include <cstring>
 #include <iostream>
@@ -13,11 +21,36 @@
 
 #include "ipd_level_plan.h"
 
-// SOL_HEAD of the gfx950 build: sol_r16(sizeof(SolveDesc)) + sol_r16(4 * RELOC_MAX)
-static constexpr size_t SOL_HEAD_GFX950 = 12592;
+static const char* const SLOT_NAMES[SLOT_COUNT] = {
+    "rp", "ci", "va", "dinv", "Axi", "xx", "rest.rp", "rest.ci", "rest.va", "prol.rp", "prol.ci", "prol.va",
+    "lmap", "dA", "dP", "dPt", "pMr", "pMe", "pMc", "pW", "r", "e", "e2", "rr", "w",
+    "bp_part", "pcg.work", "rest.x", "rest.y", "pcg.rp", "pcg.ci", "pcg.va"};
+static const char* const KIND_NAMES[] = {"copy", "dense", "lmap", "poly", "work", "alias"};
+
+// What the prediction s.lds holds beyond the layout's total, term by term, from the header's names: the reserves
+// plan_lds counted for the levels it cached (level_reserves), less what the layout does carve of them
+static ImageReserves image_reserves(const LevelShape* L, const LevelPlan& plan, const ImageSpec& s, const ImageLayout& lay) {
+    ImageReserves r;
+    r.of[RSV_HEAD] = RESERVE_HEAD;
+    for (int k = s.k_cached; k <= plan.J; ++k) {
+        const ImageSpec a = level_alone(k, plan.tiny_lo);
+        const bool below = k >= 2 && block_wide(plan.form(level_alone(k - 1, plan.tiny_lo), k - 1));
+        const LevelPieces counted = level_pieces(L, plan.J, a, plan.lean_vectors, k, plan.form(a, k), false);
+        const ImageReserves lr = level_reserves(counted, below);
+        for (int q = 0; q < RSV_COUNT; ++q) r.of[q] += lr.of[q];
+        if (k < s.k_lds)
+            r.of[RSV_ABOVE_ROOT] += counted.sum();
+        else
+            r.of[RSV_CHILD_PAD] -= plan.pieces(L, s, k).sum() - counted.sum();   // the padding that is carved
+    }
+    if (const ImagePiece* bp = lay.find(0, SLOT_BP_PART)) r.of[RSV_BP_PART] -= plan_r16(bp->bytes);
+    return r;
+}
 
 int main() {
     static const char* const roles[] = {"solve", "sub", "sub3", "sub4", "none"};
+    static const char* const forms[] = {"semi", "csr", "bdense", "tiny", "poly", "lpoly", "bpoly"};
+    std::printf("limits %zu %zu %d %zu %d\n", IMAGE_LDS_BUDGET, IMAGE_LDS_OPTIN, RELOC_MAX, SOL_HEAD, BT);
     std::string line;
     while (std::getline(std::cin, line)) {
         std::istringstream in(line);
@@ -29,7 +62,6 @@ int main() {
         o.smoth = smoth;
         o.twogrid = twogrid != 0;
         o.concurrent_pair = pair != 0;
-        o.sol_head = SOL_HEAD_GFX950;
         PlanSwitches sw;
         const struct {
             const char* name;
@@ -71,6 +103,16 @@ int main() {
                 if (p.thread_per_row(s, k)) tpr = std::max(tpr, L[k].nr);
             std::printf("image %s %d %d %d %d %zu %zu %d\n", roles[s.role], s.k_lds, s.k_semi, s.k_tiny, s.k_blk,
                         s.stage_bytes, s.lds, tpr);
+            if (s.k_lds > J) continue;
+            const ImageLayout lay = image_layout(L.data(), p, s);
+            for (int k = s.k_lds; k <= J; ++k) std::printf("level %d %s %d\n", k, forms[p.form(s, k)], L[k].nr);
+            for (const ImagePiece& q : lay.pieces)
+                std::printf("piece %d %s %s %zu %zu\n", q.level, SLOT_NAMES[q.slot], KIND_NAMES[q.kind], q.bytes,
+                            q.off);
+            const ImageReserves r = image_reserves(L.data(), p, s, lay);
+            std::printf("layout %zu %zu %zu %d", lay.image_bytes, lay.total, lay.pieces.size(), s.k_cached);
+            for (size_t v : r.of) std::printf(" %zu", v);
+            std::printf("\n");
         }
         std::printf("end\n");
     }

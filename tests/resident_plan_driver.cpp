@@ -20,8 +20,6 @@
 
 #include "ipd_resident_plan.h"
 
-// SOL_HEAD of the gfx950 build: sol_r16(sizeof(SolveDesc)) + sol_r16(4 * RELOC_MAX)
-static constexpr size_t SOL_HEAD_GFX950 = 12592;
 static const char* const ROLES[] = {"solve", "sub", "sub3", "sub4", "none"};
 
 static void print_plan(const char* stage, const ResidentPlan& p) {
@@ -96,7 +94,6 @@ int main() {
             o.cycle = ri.cycle;
             o.smoth = smoth;
             o.twogrid = ri.twogrid;
-            o.sol_head = SOL_HEAD_GFX950;
             const LevelPlan lp = plan_levels(L.data(), J, o, sw);
             ri.small_ok = lp.small_ok;
             ri.k_sub = lp.k_sub;
