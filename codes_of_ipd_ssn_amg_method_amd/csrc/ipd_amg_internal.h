@@ -3,6 +3,7 @@
 #pragma once
 
 #include "ipd_internal.h"
+#include "ipd_launch_plan.h"   // HalfRanges
 
 // Filled-in amg_options (Class_AMG.m:26-34 defaults applied).
 struct AmgOpts {
@@ -53,7 +54,6 @@ struct Level {
     double* w = nullptr;    // first-half result of a Gauss-Seidel sweep (without the +c shift)
     double* rr = nullptr;   // residual r - A e
     double* scal = nullptr; // small device scalars (sum r, partial dots ...)
-    int lanes = 64;         // lanes per row used by the row kernels of this level
 };
 
 struct CycleState;   // ipd_cycle.hip
@@ -149,6 +149,7 @@ struct BlockCsr {
 struct BlockLevel {
     int N = 0, nf = 0;                  // rows, F-block size (0: Jacobi)
     BlockCsr A;
+    HalfRanges sweep[2];                // pre, post: the row ranges of a smoother sweep and their grids
     const double* dinv = nullptr;
     const double* Axi = nullptr;
     const double* xx = nullptr;

@@ -599,10 +599,6 @@ struct BlockRun {
     ipd_ctx* ctx;
     BlockState* bs;
 
-    static int grid_of(int nrows, int L, int cu) {
-        return (int)std::max<long long>(1, std::min<long long>(cu, ((long long)nrows * L + BT - 1) / BT));
-    }
-
     void sweep(int k, bool post) {   // launch_sweep (ipd_cycle_host.h), CSR form
         const BlockLevel& bl = bs->lv[(size_t)k];
         BlockVecs& v = bs->v[(size_t)k];
@@ -624,25 +620,15 @@ struct BlockRun {
         a.eold_zero = v.e_zero ? 1 : 0;
         const bool staged = blk_staged((long long)bl.N * W);
         const size_t dyn = staged ? sizeof(double) * (size_t)bl.N * W : 0;
-        const int cu = ctx->num_cu;
-        auto go = [&](int r0, int r1) {
-            a.row0 = r0;
-            a.row1 = r1;
-            BLK_GO(k_blk_smooth, W, staged, grid_of(r1 - r0, a.L, cu), dyn, a);
-        };
-        if (bl.nf == 0) {
-            a.u0 = a.u1 = 0;
-            a.wout = nullptr;
-            go(0, bl.N);
-        } else {   // pre: F rows then C rows ; post: C rows then F rows
-            const int f0 = post ? bl.nf : 0, f1 = post ? bl.N : bl.nf;
-            const int s0 = post ? 0 : bl.nf, s1 = post ? bl.nf : bl.N;
-            a.u0 = a.u1 = 0;
-            go(f0, f1);
-            a.u0 = f0;
-            a.u1 = f1;
-            a.wout = nullptr;
-            go(s0, s1);
+        const HalfRanges& hr = bl.sweep[post ? 1 : 0];   // the ranges and the protocol of launch_sweep
+        a.u0 = a.u1 = 0;
+        for (int i = 0; i < hr.n; ++i) {
+            if (i == hr.n - 1) a.wout = nullptr;
+            a.row0 = hr.r[i].r0;
+            a.row1 = hr.r[i].r1;
+            BLK_GO(k_blk_smooth, W, staged, hr.r[i].G, dyn, a);
+            a.u0 = a.row0;
+            a.u1 = a.row1;
         }
         v.e_zero = false;
         std::swap(v.e, v.e2);
@@ -717,7 +703,7 @@ struct BlockRun {
             a.y = cv.r;
             const bool staged = blk_staged(2LL * bl.Pt.nc * W);
             const size_t dyn = staged ? 2 * sizeof(double) * (size_t)bl.Pt.nc * W : 0;
-            BLK_GO(k_blk_rrc, W, staged, grid_of(a.nrows, a.L, ctx->num_cu), dyn, a);
+            BLK_GO(k_blk_rrc, W, staged, bl.T1.grid, dyn, a);
         } else {
             walk(bl.A, v.e, v.r, v.rr, 0);                                    // rr = r - A e
             walk(bl.Pt, v.rr, nullptr, cv.r, 0);                              // r_{k+1} = P' rr

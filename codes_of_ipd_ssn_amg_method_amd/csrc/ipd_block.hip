@@ -12,7 +12,7 @@
 //                 scalar c per column, evaluated by every workgroup (1'r - (A1)'e) / xx
 //   k_blk_resid   rr = r - A e (k_resid)          k_blk_rrc  r_c = P'r - T1 e (k_rrc)
 //   k_blk_xfer    y = P'x, y += P x (k_xfer)      k_blk_top  x_new = x + e, r = b - A x_new (k_top)
-//   k_blk_conv    per-column norms, Class_AMG's loop test and the active mask (k_conv)
+//   k_blk_conv    per-column norms, Class_AMG's loop test and the active mask (conv_block)
 //   k_blk_pcg     the coarsest Jacobi-PCG, one workgroup per column (k_pcg)
 //   k_blk_in / k_blk_out   column-major <-> row-interleaved at entry and exit
 // A gathered block of N*W <= STAGE_MAX doubles is staged in LDS; larger ones are gathered from L2.

@@ -158,11 +158,6 @@ __device__ __forceinline__ void conv_block(const ConvArgs& a, double* red) {
     }
 }
 
-__global__ __launch_bounds__(BT) void k_conv(ConvArgs a) {
-    __shared__ double red[16];
-    conv_block(a, red);
-}
-
 // sum of a vector into one slot (entry point of ipd_amg_vcycle / wcycle)
 __global__ __launch_bounds__(BT) void k_vec_sum(const double* v, int n, double* out) {
     __shared__ double red[16];
@@ -659,33 +654,6 @@ __global__ __launch_bounds__(BT) void k_fused(FusedProg prog) {
     }
 }
 
-// lanes per row: about 2 entries per lane (half a ROW_U batch), widened while the launch
-// would leave most of the chip idle
-static int pick_lanes(long long nnz, int nrows, int blocks_target) {
-    if (nrows <= 0) return 1;
-    const double avg = (double)nnz / (double)nrows;
-    int L = 1;  // short rows: one lane walks the whole row in a single ROW_U batch
-    // mean entries per lane aimed at.  Short rows (the realistic levels): 2 -- m=n=1024 driver
-    // runs, Class 1 / Class 2: 1.5: 1.54 / 0.75 s, 2: 1.52 / 0.73, 3: 1.55 / 0.75, 4: 1.61 / 0.80,
-    // 6: 1.62 / 0.81.  Long rows (dense masks): 12 -- with 2 the 512..1024-entry rows of the
-    // regime-D transfers spread over 512-1024 lanes and the cross-wave reduction costs more than
-    // the shorter walk saves (k_xfer 6.6 -> 10.0 us, V cycle 0.200 -> 0.206 ms).
-    const double forced = 0.0, forced_long = 0.0;
-    // regime D, m=n=1024 / 2048, ms per V cycle: 3: 0.2007 / 0.387, 4.5: 0.1968 / 0.378,
-    // 6: 0.1960 / 0.376, 9: 0.1975 / 0.374, 17: 0.1969 / 0.370
-    // (with 512-thread blocks: 6: 0.1903 / 0.337, 12: 0.1866 / 0.324, 24: 0.1891 / 0.320)
-    const double long_rows = forced_long > 0.0 ? forced_long : 3.0 * ROW_U;
-    const double per_lane = forced > 0.0 ? forced : (avg >= 64.0 ? long_rows : 0.5 * ROW_U);
-    while (L < BT && (double)L * per_lane < avg) L <<= 1;
-    // widen while most of the chip would idle (tools/ubench_small.hip: a 1024-row launch of
-    // short rows costs the same 6.5 us on 1, 4 or 16 workgroups, so spreading is free and
-    // keeps one CU's load-issue rate from becoming the limit)
-    while (L < BT && (long long)nrows * L < (long long)blocks_target * BT / 2 &&
-           (double)L * 2.0 <= avg)
-        L <<= 1;
-    return L;
-}
-
 void pcg_dev(ipd_ctx* ctx, const Csr& H, const double* e, const double* guess, double tol,
              long long maxit, int precd, double* d, long long* it, double* res,
              double* resk_host, long long nf) {
@@ -698,7 +666,7 @@ void pcg_dev(ipd_ctx* ctx, const Csr& H, const double* e, const double* guess, d
     const long long nresk = resk_host ? std::min<long long>(maxit, 1 << 20) : 0;
     PcgArgs a;
     a.N = H.nr;
-    a.L = std::min(pick_lanes(H.nnz, H.nr, 1), 64);
+    a.L = std::min(pick_lanes(H.nnz, H.nr, 1), PCG_LANES_MAX);
     a.rp = H.rp;
     a.ci = H.ci;
     a.va = H.va;

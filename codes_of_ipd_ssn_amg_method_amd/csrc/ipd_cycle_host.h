@@ -10,7 +10,7 @@
 struct LevelRun {  // per-level run state kept next to Level
     LevelDev dev;
     bool e_zero = true;      // the iterate is identically zero and is not materialised
-    int staged = 0;          // N <= STAGE_MAX: gather vectors go through LDS
+    LaunchLevel plan;        // how the level's phases run on the multi-launch path (ipd_launch_plan.h)
     int maxoff = 0;          // longest off-diagonal row (k_level_prepare)
     XferArgs restrict_args;  // r_{k+1} = P' rr_k   (stored on level k)
     XferArgs prolong_args;   // e_k += P e_{k+1}
@@ -52,7 +52,6 @@ struct CycleState {
     // fused single-workgroup program under construction (flushed before any big launch)
     FusedProg pending;
     size_t pending_lds = 0;
-    bool fuse_enabled = true;
     CycleState() { pending.n = 0; }
     // The LDS images of the single-workgroup kernels (ipd_level_plan.h) by role: the whole solve (k_solve_small,
     // k_pcg_small), the sub-cycle rooted at level k_sub (k_subcycle), and the images rooted at level 3 (no sub-cycle:
@@ -198,10 +197,7 @@ __global__ __launch_bounds__(BT) void k_levels_sum(const PrepLevels P) {
     if (threadIdx.x == 0) P.xx[k][0] = tot;
 }
 
-static int pick_blocks(int nrows, int L, int cu);
-
-// Builds the padded off-diagonal copy when the level is big and regular enough
-// (see ipd_cycle_phases.h, item 2) and adapts the launch geometry to it.
+// Builds the padded off-diagonal copy of width S (pad_width, ipd_launch_plan.h; 0: none)
 static void pad_flush(ipd_ctx* ctx, PadBatch* b) {
     if (b->n == 0) return;
     int rows = 1;
@@ -211,21 +207,11 @@ static void pad_flush(ipd_ctx* ctx, PadBatch* b) {
     IPD_KERNEL_CHECK();
     b->n = 0;
 }
-static void build_padded(ipd_ctx* ctx, Arena& ar, const Csr& A, int rows_per_launch, int cu,
-                         int maxlen /* longest off-diagonal row, from k_level_prepare */,
-                         LevelDev* dev, PadBatch* batch) {
-    dev->S = 0;
+static void build_padded(ipd_ctx* ctx, Arena& ar, const Csr& A, int S, LevelDev* dev, PadBatch* batch) {
     dev->pci = nullptr;
     dev->pva = nullptr;
     dev->diag = nullptr;
-    if (switch_on("IPD_NO_PAD")) return;
-    if (A.nr > 65535 || A.nr == 0) return;
-    const double avg_off = (double)(A.nnz - A.nr) / (double)A.nr;
-    // small levels too: one dependent round trip less per launch (measured -6 % solve time on
-    // the m=n=1024 Class 1 run)
-    if (avg_off < 0.5) return;
-    const int S = (maxlen + 3) / 4 * 4;
-    if (S == 0 || (double)S > 1.3 * avg_off + 16.0) return;
+    if (S == 0) return;
     unsigned short* pci = ar.alloc<unsigned short>((size_t)A.nr * S);
     double* pva = ar.alloc<double>((size_t)A.nr * S);
     double* diag = ar.alloc<double>((size_t)A.nr);
@@ -241,29 +227,10 @@ static void build_padded(ipd_ctx* ctx, Arena& ar, const Csr& A, int rows_per_lau
         batch->pva[q] = pva;
         batch->diag[q] = diag;
     }
-    dev->S = S;
     dev->pci = pci;
     dev->pva = pva;
     dev->diag = diag;
-    // one batch (ROW_U entries = 2 vectors) per lane, widened until the chip is filled
-    const int nvec = S / 4;
-    int L = 4;
-    // batches per lane aimed at before the chip-filling rule below widens again.  Regime D at
-    // m=n=2048 (2048-entry rows, bandwidth-bound): 1: 0.376 ms per V cycle, 2: 0.342, 4: 0.332,
-    // 8/16: 0.332; m=n=1024 unchanged (0.197), m=n=4096 Class 1 run 5.37 -> 5.29 s
-    // (with 512-thread blocks: 4: 0.337, 8: 0.324-0.330, 16: 0.325)
-    const int batches = 8;
-    while (L < BT && L * (ROW_U / 4) * batches < nvec) L <<= 1;
-    const double fill = 1.0;   // one workgroup per CU (0.5 left half the chip idle on a 1024-row level: 6.16 -> 5.79 us)
-    while (L < BT && (double)rows_per_launch * L < fill * cu * BT && L < nvec) L <<= 1;
-    dev->L = L;
-    dev->G = pick_blocks(rows_per_launch, L, cu);
 }
-
-static int pick_blocks(int nrows, int L, int cu) {
-    return (int)std::max<long long>(1, std::min<long long>(cu, ((long long)nrows * L + BT - 1) / BT));
-}
-
 
 // Packs the polynomial form of level k (k_bpoly_*, ipd_cycle.hip) into the hierarchy's arena: LD-row
 // column-major [Mr | Me | Mc] for the single-workgroup images, or (rows) the row-major layout the
@@ -369,6 +336,9 @@ static void record_rows_op(CycleState* st, const ipd_amg* h, int k, const BPolyD
 // one place that reads them
 static PlanSwitches read_plan_switches() {
     PlanSwitches s;
+    s.no_pad = switch_on("IPD_NO_PAD");
+    s.no_stage = switch_on("IPD_NO_STAGE");
+    s.no_rrc = switch_on("IPD_NO_RRC");
     s.no_poly = switch_on("IPD_NO_POLY");
     s.no_blk = switch_on("IPD_NO_BLK");
     s.no_bpoly = switch_on("IPD_NO_BPOLY");
@@ -409,14 +379,13 @@ static std::vector<LevelShape> level_shapes(const ipd_amg* h, const CycleState* 
 // here, ahead of the first launch of any other kernel template: the object lists its kernels in this order.)
 #include "ipd_resident_host.h"
 
-// Per-level vectors and constants (k_level_prepare), the padded copies and the launch geometry of every
-// level: st->run[k].dev
-static void prepare_level_runs(ipd_amg* h, CycleState* st) {
+// Per-level vectors and constants (k_level_prepare), the launch plan of every level and the padded copies
+// it asks for: st->run[k].plan, st->run[k].dev
+static void prepare_level_runs(ipd_amg* h, CycleState* st, const LaunchSwitches& sw) {
     ipd_ctx* ctx = h->ctx;
     Arena& ar = *h->arena;
-    const int cu = ctx->num_cu;
     // first pass: per-level vectors and the longest off-diagonal row of every level (one
-    // readback for all levels), second pass: padded copies and launch geometry
+    // readback for all levels), then the launch plan, second pass: padded copies and launch geometry
     int* maxoff = zeroed<int>(ctx, (size_t)h->J + 1);
     // levels whose constant data come from the donor hierarchy (see ipd_amg::donor)
     const ipd_amg* donor = h->donor.get();
@@ -431,26 +400,16 @@ static void prepare_level_runs(ipd_amg* h, CycleState* st) {
         lv.N = N;
         lv.nf = (k == 1 && h->opts.bigph) ? (int)h->opts.fnode : 0;
         IPD_REQUIRE(lv.nf < N, IPD_E_ARG, "fnode must be smaller than the matrix size");
-        if (shared_level(k)) {
-            const Level& dl = donor->L[k];
-            lv.dinv = dl.dinv;
-            lv.Axi = dl.Axi;
-            lv.xx = dl.xx;
-            lv.r = ar.alloc<double>((size_t)N);
-            lv.e = ar.alloc<double>((size_t)N);
-            lv.e2 = ar.alloc<double>((size_t)N);
-            lv.w = ar.alloc<double>((size_t)N);
-            lv.rr = ar.alloc<double>((size_t)N);
-            continue;
-        }
-        lv.dinv = ar.alloc<double>((size_t)N);
-        lv.Axi = ar.alloc<double>((size_t)N);
-        lv.xx = ar.alloc<double>(1);
+        const Level* dl = shared_level(k) ? &donor->L[k] : nullptr;
+        lv.dinv = dl ? dl->dinv : ar.alloc<double>((size_t)N);
+        lv.Axi = dl ? dl->Axi : ar.alloc<double>((size_t)N);
+        lv.xx = dl ? dl->xx : ar.alloc<double>(1);
         lv.r = ar.alloc<double>((size_t)N);
         lv.e = ar.alloc<double>((size_t)N);
         lv.e2 = ar.alloc<double>((size_t)N);
         lv.w = ar.alloc<double>((size_t)N);
         lv.rr = ar.alloc<double>((size_t)N);
+        if (dl) continue;
         if (prep.n < PREP_ML) {
             const int q = prep.n++;
             prep.N[q] = N;
@@ -481,19 +440,31 @@ static void prepare_level_runs(ipd_amg* h, CycleState* st) {
     }
     std::vector<int> hmax((size_t)h->J + 1);
     ctx->fetch(maxoff, hmax.data(), (size_t)h->J + 1);
+    std::vector<LaunchShape> shapes((size_t)h->J + 1);
+    for (int k = 1; k <= h->J; ++k) {
+        const Level& lv = h->L[k];
+        LaunchShape& s = shapes[(size_t)k] = LaunchShape{lv.A.nr, lv.A.nnz, lv.nf, hmax[(size_t)k]};
+        if (k == h->J) break;
+        const Level& cl = h->L[k + 1];
+        s.Pt = MatShape{cl.Pt.nr, cl.Pt.nc, cl.Pt.nnz};
+        s.P = MatShape{cl.P.nr, cl.P.nc, cl.P.nnz};
+        s.t1 = cl.T1.rp != nullptr;
+        s.T1 = MatShape{cl.T1.nr, cl.T1.nc, cl.T1.nnz};
+    }
+    LaunchLevel dplan[3];   // the donor's records: its padded copy goes with its geometry
+    int dlevels = 0;
+    for (int k = 1; k <= 2 && shared_level(k); ++k) dplan[dlevels = k] = dst_->run[(size_t)k].plan;
+    const std::vector<LaunchLevel> plan = plan_launches(shapes.data(), h->J, ctx->num_cu, sw, dplan, dlevels);
     PadBatch pads;   // the levels' padded copies: one launch after the loop
     for (int k = 1; k <= h->J; ++k) {
         Level& lv = h->L[k];
-        const int N = lv.N;
-        // launch geometry: for a GS level the work per launch is half the matrix
-        const int rows_per_launch = lv.nf > 0 ? std::max(1, N / 2) : N;
-        const long long nnz_per_launch = lv.nf > 0 ? std::max(1, lv.A.nnz / 2) : lv.A.nnz;
-        lv.lanes = pick_lanes(nnz_per_launch, rows_per_launch, cu);
         LevelRun& rn = st->run[(size_t)k];
-        rn.dev.N = N;
+        rn.plan = plan[(size_t)k];
+        rn.dev.N = lv.N;
         rn.dev.nf = lv.nf;
-        rn.dev.L = lv.lanes;
-        rn.dev.G = pick_blocks(rows_per_launch, lv.lanes, cu);
+        rn.dev.S = rn.plan.S;
+        rn.dev.L = rn.plan.L;
+        rn.dev.G = rn.plan.G;
         rn.dev.rp = lv.A.rp;
         rn.dev.ci = lv.A.ci;
         rn.dev.va = lv.A.va;
@@ -502,18 +473,13 @@ static void prepare_level_runs(ipd_amg* h, CycleState* st) {
         rn.dev.xx = lv.xx;
         rn.dev.r = lv.r;
         rn.dev.rr = lv.rr;
-        rn.staged = N <= STAGE_MAX && !switch_on("IPD_NO_STAGE") ? 1 : 0;
-        if (shared_level(k)) {   // the donor's padded copy and the geometry that goes with it
+        if (shared_level(k)) {
             const LevelDev& dd = dst_->run[(size_t)k].dev;
-            rn.dev.S = dd.S;
             rn.dev.pci = dd.pci;
             rn.dev.pva = dd.pva;
             rn.dev.diag = dd.diag;
-            rn.dev.L = dd.L;
-            rn.dev.G = dd.G;
-            lv.lanes = donor->L[k].lanes;
         } else {
-            build_padded(ctx, ar, lv.A, rows_per_launch, cu, hmax[(size_t)k], &rn.dev, &pads);
+            build_padded(ctx, ar, lv.A, rn.plan.S, &rn.dev, &pads);
             rn.maxoff = hmax[(size_t)k];
         }
     }
@@ -523,47 +489,24 @@ static void prepare_level_runs(ipd_amg* h, CycleState* st) {
 // Restriction / prolongation arguments of the launches, the coarsest level's PCG, the solve's vectors
 static void prepare_transfers(ipd_amg* h, CycleState* st) {
     Arena& ar = *h->arena;
-    const int cu = h->ctx->num_cu;
+    auto xfer = [](const Csr& m, const XferPlan& xp, const double* x, double* y, int add) {
+        // nrows, ncols, L, G, row0, row1, rp, ci, va, x, y, add, staged
+        return XferArgs{m.nr, m.nc, xp.L, xp.G, 0, m.nr, m.rp, m.ci, m.va, x, y, add, xp.staged ? 1 : 0};
+    };
     for (int k = 1; k < h->J; ++k) {
         Level& fine = h->L[k];
         Level& coarse = h->L[k + 1];
         LevelRun& rn = st->run[(size_t)k];
-        XferArgs ra;  // restriction: rows of P' (coarse rows), gathers the fine residual
-        ra.nrows = coarse.Pt.nr;
-        ra.ncols = coarse.Pt.nc;
-        ra.L = pick_lanes(coarse.Pt.nnz, coarse.Pt.nr, cu);
-        ra.G = pick_blocks(ra.nrows, ra.L, cu);
-        ra.rp = coarse.Pt.rp;
-        ra.ci = coarse.Pt.ci;
-        ra.va = coarse.Pt.va;
-        ra.x = fine.rr;
-        ra.y = coarse.r;
-        ra.add = 0;
-        ra.row0 = 0;
-        ra.row1 = ra.nrows;
-        ra.staged = ra.ncols <= STAGE_MAX ? 1 : 0;
-        rn.restrict_args = ra;
-        XferArgs pa;  // prolongation: rows of P (fine rows), gathers the coarse correction
-        pa.nrows = coarse.P.nr;
-        pa.ncols = coarse.P.nc;
-        pa.L = pick_lanes(coarse.P.nnz, coarse.P.nr, cu);
-        pa.G = pick_blocks(pa.nrows, pa.L, cu);
-        pa.rp = coarse.P.rp;
-        pa.ci = coarse.P.ci;
-        pa.va = coarse.P.va;
-        pa.x = coarse.e;
-        pa.y = fine.e;
-        pa.add = 1;
-        pa.row0 = 0;
-        pa.row1 = pa.nrows;
-        pa.staged = pa.ncols <= STAGE_MAX ? 1 : 0;
-        rn.prolong_args = pa;
+        // restriction: rows of P' (coarse rows), gathers the fine residual
+        rn.restrict_args = xfer(coarse.Pt, rn.plan.rest, fine.rr, coarse.r, 0);
+        // prolongation: rows of P (fine rows), gathers the coarse correction
+        rn.prolong_args = xfer(coarse.P, rn.plan.prol, coarse.e, fine.e, 1);
     }
     {   // coarsest level: PCG(A,r) with the 2-argument defaults (PCG.m:18-23)
         Level& cl = h->L[h->J];
         PcgArgs a;
         a.N = cl.A.nr;
-        a.L = std::min(pick_lanes(cl.A.nnz, cl.A.nr, 1), 64);
+        a.L = st->run[(size_t)h->J].plan.pcg_L;
         a.rp = cl.A.rp;
         a.ci = cl.A.ci;
         a.va = cl.A.va;
@@ -578,8 +521,7 @@ static void prepare_transfers(ipd_amg* h, CycleState* st) {
         a.nresk = 0;
         st->run[(size_t)h->J].pcg = a;
     }
-    st->num_cu = cu;
-    st->fuse_enabled = true;
+    st->num_cu = h->ctx->num_cu;
     st->hist = ar.alloc<double>(8);
     st->x2 = ar.alloc<double>((size_t)h->L[1].A.nr);
     h->x = ar.alloc<double>((size_t)h->L[1].A.nr);
@@ -838,7 +780,8 @@ static void pack_image(ipd_ctx* ctx, ipd_amg* h, CycleState* st, const std::vect
 void amg_prepare_levels(ipd_amg* h) {
     std::unique_ptr<CycleState> st(new CycleState());
     st->run.resize((size_t)h->J + 1);
-    prepare_level_runs(h, st.get());
+    const PlanSwitches sw = read_plan_switches();
+    prepare_level_runs(h, st.get(), sw);
     prepare_transfers(h, st.get());
     // single-workgroup kernels: which levels, in which form, in which LDS images (ipd_level_plan.h)
     const std::vector<LevelShape> shapes = level_shapes(h, st.get());
@@ -847,9 +790,11 @@ void amg_prepare_levels(ipd_amg* h) {
     po.smoth = h->opts.smoth;
     po.twogrid = h->opts.twogrid;
     po.concurrent_pair = h->opts.concurrent_pair;
-    const PlanSwitches sw = read_plan_switches();
     const LevelPlan plan = plan_levels(shapes.data(), h->J, po, sw);
     const bool debug = switch_on("IPD_DEBUG_LEVELS");
+    if (debug)
+        for (int k = 1; k <= h->J; ++k)
+            std::fprintf(stderr, "[ipd] launch plan: %s\n", launch_plan_line(st->run[(size_t)k].plan, k, h->J).c_str());
     if (debug)
         for (const ImageSpec& s : plan.images)
             std::fprintf(stderr, "[ipd] image %s: k_lds=%d k_semi=%d k_tiny=%d k_blk=%d stage=%zu lds=%zu%s\n",
@@ -903,16 +848,7 @@ void amg_prepare_levels(ipd_amg* h) {
         IPD_KERNEL_CHECK();                                                                       \
     } while (0)
 
-// ---- fused-program emitter -----------------------------------------------------------
-// A phase is "small" when one workgroup covers its rows in ONE pass and its matrix slice
-// is a few thousand entries: then it costs 1-3 us inside a fused program against >= 5 us
-// as a launch of its own.  Larger phases lose inside a single workgroup (one CU issues
-// ~60 B/clk of loads: tools/ubench_small.hip) and stay separate launches.
-static bool phase_is_small(const CycleState* st, int rows, int L, double nnz_est, int stage_len) {
-    return st->fuse_enabled && stage_len <= STAGE_MAX && (long long)rows * L <= (long long)BT &&
-           nnz_est <= 6000.0;
-}
-
+// ---- fused-program emitter (which phases are queued: phase_is_small, ipd_launch_plan.h) -------
 static void flush_fused(ipd_ctx* ctx, CycleState* st) {
     if (st->pending.n == 0) return;
     hipLaunchKernelGGL(k_fused, dim3(1), dim3(BT), st->pending_lds, ctx->stream, st->pending);
@@ -930,25 +866,25 @@ static PhaseDesc& push_phase(ipd_ctx* ctx, CycleState* st, int type, int stage_l
     return d;
 }
 
-// Runs `launch(r0, r1)` over the row range [lo, hi) of a level.  Unsharded: one call.
-// Sharded: this rank's slice only, followed by one grouped RCCL all-gather of the
-// vectors the launch produced (each rank wrote its own slice of every one of them).
+// Runs `launch(r0, r1, grid)` over the row range `rg` of a matrix walked by L lanes per row.  Unsharded: one
+// call with the planned grid.  Sharded: this rank's slice only (its grid: the slice's own), followed by one
+// grouped RCCL all-gather of the vectors the launch produced (each rank wrote its own slice of every one of them).
 template <class F>
-static void run_rows(ipd_ctx* ctx, CycleState* st, int lo, int hi, F launch,
+static void run_rows(ipd_ctx* ctx, CycleState* st, const RowRange& rg, int L, F launch,
                      std::initializer_list<double*> produced) {
     flush_fused(ctx, st);  // big launch: everything queued before it must run first
     const int G = st->shard_ranks;
-    const int rows = hi - lo;
+    const int lo = rg.r0, rows = rg.r1 - rg.r0;
     if (G <= 1 || rows % G != 0 || rows < st->shard_min_rows) {  // replicated level
-        launch(lo, hi);
+        launch(rg.r0, rg.r1, rg.G);
         return;
     }
-    const int cnt = rows / G;
+    const int cnt = rows / G, grid = pick_blocks(cnt, L, st->num_cu);
     if (st->shard_emulate) {
-        for (int vr = 0; vr < G; ++vr) launch(lo + vr * cnt, lo + (vr + 1) * cnt);
+        for (int vr = 0; vr < G; ++vr) launch(lo + vr * cnt, lo + (vr + 1) * cnt, grid);
         return;
     }
-    launch(lo + st->shard_rank * cnt, lo + (st->shard_rank + 1) * cnt);
+    launch(lo + st->shard_rank * cnt, lo + (st->shard_rank + 1) * cnt, grid);
     double* bases[4];
     int nv = 0;
     for (double* v : produced)
@@ -956,27 +892,35 @@ static void run_rows(ipd_ctx* ctx, CycleState* st, int lo, int hi, F launch,
     comm_allgather_inplace(ctx, bases, nv, cnt);
 }
 
-static void launch_smooth(ipd_ctx* ctx, const SmoothArgs& a, int cu) {
+static void launch_smooth(ipd_ctx* ctx, const SmoothArgs& a, int grid) {
     const size_t dyn = a.staged ? sizeof(double) * (size_t)a.lv.N : 0;
-    const int grid = pick_blocks(a.row1 - a.row0, a.lv.L, cu);
     IPD_LAUNCH_SP(k_smooth, a.staged, a.lv.S > 0, grid, dyn, a);
 }
 
-static void launch_xfer(ipd_ctx* ctx, const XferArgs& a, int cu) {
+// a restriction or prolongation as planned: queued into the fused program or launched over its rows
+static void issue_xfer(ipd_ctx* ctx, CycleState* st, XferArgs a, const XferPlan& xp) {
+    if (xp.queued) {
+        push_phase(ctx, st, PH_XFER, a.ncols).u.x = a;
+        return;
+    }
     const size_t dyn = a.staged ? sizeof(double) * (size_t)a.ncols : 0;
-    const int grid = pick_blocks(a.row1 - a.row0, a.L, cu);
-    if (a.staged)
-        hipLaunchKernelGGL(k_xfer<true>, dim3(grid), dim3(BT), dyn, ctx->stream, a);
-    else
-        hipLaunchKernelGGL(k_xfer<false>, dim3(grid), dim3(BT), 0, ctx->stream, a);
-    IPD_KERNEL_CHECK();
+    run_rows(ctx, st, RowRange{0, a.nrows, xp.G}, a.L,
+             [&](int r0, int r1, int grid) {
+                 a.row0 = r0;
+                 a.row1 = r1;
+                 if (a.staged)
+                     hipLaunchKernelGGL(k_xfer<true>, dim3(grid), dim3(BT), dyn, ctx->stream, a);
+                 else
+                     hipLaunchKernelGGL(k_xfer<false>, dim3(grid), dim3(BT), 0, ctx->stream, a);
+                 IPD_KERNEL_CHECK();
+             },
+             {a.y});
 }
 
 static void launch_resid(ipd_ctx* ctx, const LevelRun& rn, const double* e, int r0, int r1,
-                         int cu) {
-    const size_t dyn = rn.staged ? sizeof(double) * (size_t)rn.dev.N : 0;
-    const int grid = pick_blocks(r1 - r0, rn.dev.L, cu);
-    IPD_LAUNCH_SP(k_resid, rn.staged, rn.dev.S > 0, grid, dyn, rn.dev, e, r0, r1);
+                         int grid) {
+    const size_t dyn = rn.plan.staged ? sizeof(double) * (size_t)rn.dev.N : 0;
+    IPD_LAUNCH_SP(k_resid, rn.plan.staged, rn.dev.S > 0, grid, dyn, rn.dev, e, r0, r1);
 }
 
 // one smoother sweep on level k: Jacobi = one launch, bigraph GS = two half launches
@@ -991,71 +935,41 @@ static void launch_sweep(ipd_amg* h, CycleState* st, int k, int isnsp, bool post
     a.win = lv.w;
     a.wout = lv.w;
     a.isnsp = isnsp;
-    a.staged = rn.staged;
+    a.staged = rn.plan.staged;
     a.eold_zero = rn.e_zero ? 1 : 0;
-    const int cu = st->num_cu;
-    const int rows_launch = lv.nf > 0 ? std::max(lv.nf, lv.N - lv.nf) : lv.N;
-    const bool small = a.staged && phase_is_small(st, rows_launch, a.lv.L,
-                                                  (double)lv.A.nnz * rows_launch / std::max(lv.N, 1),
-                                                  lv.N);
-    auto go = [&](int r0, int r1) {
+    const LaunchLevel& p = rn.plan;
+    // How a range is issued: queued into the fused program (replicated on every rank), or as launches of the
+    // bit-mask kernel (level 1 with a mask operator: same two half sweeps, 1 bit per matrix entry; sharded runs
+    // give each owner its block of the half's rows -- a row range inside one half is all the kernel needs) or
+    // of the rows kernel
+    const bool mask = k == 1 && lv.nf > 0 && st->mask_ok;
+    const MaskOp& mo = st->maskop;
+    auto rows = [&](int r0, int r1, int grid) {
         a.row0 = r0;
         a.row1 = r1;
-        if (small)
+        if (p.sweep_queued) {
             push_phase(ctx, st, PH_SMOOTH, lv.N).u.s = a;
-        else
-            launch_smooth(ctx, a, cu);
-    };
-    if (small) {  // replicated on every rank, queued into the fused program
-        if (lv.nf == 0) {
-            a.u0 = a.u1 = 0;
-            a.wout = nullptr;
-            go(0, lv.N);
+        } else if (!mask) {
+            launch_smooth(ctx, a, grid);
         } else {
-            const int f0 = post ? lv.nf : 0, f1 = post ? lv.N : lv.nf;
-            const int s0 = post ? 0 : lv.nf, s1 = post ? lv.nf : lv.N;
-            a.u0 = a.u1 = 0;
-            go(f0, f1);
-            a.u0 = f0;
-            a.u1 = f1;
-            a.wout = nullptr;
-            go(s0, s1);
-        }
-    } else if (lv.nf == 0) {
-        a.u0 = a.u1 = 0;
-        a.wout = nullptr;
-        run_rows(ctx, st, 0, lv.N, go, {a.enew});
-    } else if (k == 1 && st->mask_ok) {
-        // bit-mask operator: same two half sweeps, 1 bit per matrix entry; sharded runs give each
-        // owner its block of the half's rows (a row range inside one half is all the kernel needs)
-        const MaskOp& mo = st->maskop;
-        const size_t dyn = sizeof(double) * 64 * (size_t)std::max(mo.nwf, mo.nwc);
-        auto half = [&](int r0, int r1) {
-            a.row0 = r0;
-            a.row1 = r1;
+            const size_t dyn = sizeof(double) * 64 * (size_t)std::max(mo.nwf, mo.nwc);
             const int nwh = (r0 < mo.nf) ? mo.nwf : mo.nwc;
-            const int grid = std::max(1, cdiv(r1 - r0, std::min(MASK_RW, 64 / nwh) * (BT / 64)));
-            hipLaunchKernelGGL(k_smooth_mask, dim3(grid), dim3(BT), dyn, ctx->stream, a, mo);
+            const int mgrid = std::max(1, cdiv(r1 - r0, std::min(MASK_RW, 64 / nwh) * (BT / 64)));
+            hipLaunchKernelGGL(k_smooth_mask, dim3(mgrid), dim3(BT), dyn, ctx->stream, a, mo);
             IPD_KERNEL_CHECK();
-        };
-        const int f0 = post ? lv.nf : 0, f1 = post ? lv.N : lv.nf;
-        const int s0 = post ? 0 : lv.nf, s1 = post ? lv.nf : lv.N;
-        a.u0 = a.u1 = 0;
-        run_rows(ctx, st, f0, f1, half, {a.enew, a.wout});
-        a.u0 = f0;
-        a.u1 = f1;
-        a.wout = nullptr;
-        run_rows(ctx, st, s0, s1, half, {a.enew});
-    } else {
-        // pre: F rows then C rows (Rk{1});  post: C rows then F rows (Rk{1}')
-        const int f0 = post ? lv.nf : 0, f1 = post ? lv.N : lv.nf;  // first half rows
-        const int s0 = post ? 0 : lv.nf, s1 = post ? lv.nf : lv.N;  // second half rows
-        a.u0 = a.u1 = 0;
-        run_rows(ctx, st, f0, f1, go, {a.enew, a.wout});
-        a.u0 = f0;
-        a.u1 = f1;
-        a.wout = nullptr;
-        run_rows(ctx, st, s0, s1, go, {a.enew});
+        }
+    };
+    // Jacobi: one range.  Bigraph GS: the first half hands its result (wout) to the second, which updates with it
+    const HalfRanges& hr = p.sweep[post ? 1 : 0];
+    a.u0 = a.u1 = 0;
+    for (int i = 0; i < hr.n; ++i) {
+        if (i == hr.n - 1) a.wout = nullptr;
+        if (p.sweep_queued)
+            rows(hr.r[i].r0, hr.r[i].r1, 0);
+        else
+            run_rows(ctx, st, hr.r[i], a.lv.L, rows, {a.enew, a.wout});
+        a.u0 = hr.r[i].r0;
+        a.u1 = hr.r[i].r1;
     }
     rn.e_zero = false;
     std::swap(lv.e, lv.e2);
@@ -1081,7 +995,7 @@ void amg_cycle(ipd_amg* h, int k, int isnsp, bool wcycle, bool keep_e) {
     IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
     Level& lv = h->L[k];
     LevelRun& rn = st->run[(size_t)k];
-    const int cu = st->num_cu;
+    const LaunchLevel& p = rn.plan;
     if (st->k_sub == k) {  // everything from here down: one workgroup, LDS-resident (replicated)
         flush_fused(ctx, st);
         hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->img[IMG_SUB].lds, ctx->stream,
@@ -1094,12 +1008,7 @@ void amg_cycle(ipd_amg* h, int k, int isnsp, bool wcycle, bool keep_e) {
         PcgArgs a = rn.pcg;                            // replicated on every rank
         a.rhs = lv.r;
         a.d = lv.e;
-        if (st->fuse_enabled) {
-            push_phase(ctx, st, PH_PCG, 0).u.p = a;
-        } else {
-            hipLaunchKernelGGL(k_pcg, dim3(1), dim3(BT), 0, ctx->stream, a);
-            IPD_KERNEL_CHECK();
-        }
+        push_phase(ctx, st, PH_PCG, 0).u.p = a;
         return;
     }
     const int nu = h->opts.smoth;
@@ -1112,33 +1021,24 @@ void amg_cycle(ipd_amg* h, int k, int isnsp, bool wcycle, bool keep_e) {
         }
     }
     for (int s = 0; s < nu; ++s) launch_sweep(h, st, k, isnsp, false);          // :14-25
-    const bool resid_small = rn.staged && phase_is_small(st, lv.N, rn.dev.L, (double)lv.A.nnz, lv.N);
     XferArgs ra = rn.restrict_args;
-    const bool rest_small =
-        ra.staged && phase_is_small(st, ra.nrows, ra.L, (double)h->L[k + 1].Pt.nnz, ra.ncols);
-    const bool no_rrc = switch_on("IPD_NO_RRC");
-    const Csr& T1 = h->L[k + 1].T1;
-    // Fused where the two launches are latency-bound (measured: tree-mask W cycle 0.432 -> 0.413 ms,
-    // realistic Newton systems -2...-3.5 %); once T1 is megabytes the pair is bandwidth-bound and the
-    // fused walk (CSR T1, 12 B per entry, against the padded A, 10 B) is the slower one (regime D at
-    // m=n=2048: 0.321 -> 0.342 ms), so large T1 keep the two launches.
-    if (!no_rrc && !resid_small && !rest_small && T1.rp && T1.nr == ra.nrows && T1.nnz <= (1 << 18)) {
+    if (p.rrc) {
         // r_{k+1} = P'r - (P'A) e: one launch instead of residual + restriction           :27
+        const Csr& T1 = h->L[k + 1].T1;
         RrcArgs rc;
         rc.p = ra;
         rc.p.x = lv.r;
-        rc.p.L = pick_lanes(T1.nnz + h->L[k + 1].Pt.nnz, ra.nrows, cu);
+        rc.p.L = p.rrc_walk.L;
         rc.rp2 = T1.rp;
         rc.ci2 = T1.ci;
         rc.va2 = T1.va;
         rc.e = lv.e;
-        const bool staged = 2 * (size_t)ra.ncols <= (size_t)STAGE_MAX && rn.staged;
+        const bool staged = p.rrc_walk.staged;
         const size_t dyn = staged ? 2 * sizeof(double) * (size_t)ra.ncols : 0;
-        run_rows(ctx, st, 0, ra.nrows,
-                 [&](int r0, int r1) {
+        run_rows(ctx, st, RowRange{0, ra.nrows, p.rrc_walk.G}, rc.p.L,
+                 [&](int r0, int r1, int grid) {
                      rc.p.row0 = r0;
                      rc.p.row1 = r1;
-                     const int grid = pick_blocks(r1 - r0, rc.p.L, cu);
                      if (staged)
                          hipLaunchKernelGGL(k_rrc<true>, dim3(grid), dim3(BT), dyn, ctx->stream, rc);
                      else
@@ -1147,46 +1047,26 @@ void amg_cycle(ipd_amg* h, int k, int isnsp, bool wcycle, bool keep_e) {
                  },
                  {ra.y});
     } else {
-        if (resid_small) {                                                              // :27
+        if (p.resid_queued) {                                                           // :27
             ResidDesc& rd = push_phase(ctx, st, PH_RESID, lv.N).u.r;
             rd.lv = rn.dev;
             rd.e = lv.e;
             rd.row0 = 0;
             rd.row1 = lv.N;
         } else {
-            run_rows(ctx, st, 0, lv.N,
-                     [&](int r0, int r1) { launch_resid(ctx, rn, lv.e, r0, r1, cu); }, {lv.rr});
+            run_rows(ctx, st, RowRange{0, lv.N, p.G_all}, rn.dev.L,
+                     [&](int r0, int r1, int grid) { launch_resid(ctx, rn, lv.e, r0, r1, grid); }, {lv.rr});
         }
-        if (rest_small)
-            push_phase(ctx, st, PH_XFER, ra.ncols).u.x = ra;
-        else
-            run_rows(ctx, st, 0, ra.nrows,
-                     [&](int r0, int r1) {
-                         ra.row0 = r0;
-                         ra.row1 = r1;
-                         launch_xfer(ctx, ra, cu);
-                     },
-                     {ra.y});
+        issue_xfer(ctx, st, ra, p.rest);
     }
     amg_cycle(h, k + 1, isnsp, wcycle, false);                                   // :29
     // MG_Wcycle.m:30 -- the second correction; on the coarsest level it repeats the
     // identical zero-guess PCG solve, so it is skipped there (same bits).
     if (wcycle && k + 1 < h->J) amg_cycle(h, k + 1, isnsp, wcycle, true);
-    {
-        XferArgs pa = rn.prolong_args;                                           // :31
-        pa.x = h->L[k + 1].e;
-        pa.y = lv.e;
-        if (pa.staged && phase_is_small(st, pa.nrows, pa.L, (double)h->L[k + 1].P.nnz, pa.ncols))
-            push_phase(ctx, st, PH_XFER, pa.ncols).u.x = pa;
-        else
-        run_rows(ctx, st, 0, pa.nrows,
-                 [&](int r0, int r1) {
-                     pa.row0 = r0;
-                     pa.row1 = r1;
-                     launch_xfer(ctx, pa, cu);
-                 },
-                 {pa.y});
-    }
+    XferArgs pa = rn.prolong_args;                                               // :31
+    pa.x = h->L[k + 1].e;
+    pa.y = lv.e;
+    issue_xfer(ctx, st, pa, p.prol);
     for (int s = 0; s < nu; ++s) launch_sweep(h, st, k, isnsp, true);           // :33-41
 }
 
@@ -1200,18 +1080,17 @@ static void launch_top(ipd_amg* h, CycleState* st, const double* b, const double
     a.x = x;
     a.e = e;
     a.xnew = xnew;
-    a.staged = rn.staged;
+    a.staged = rn.plan.staged;
     const size_t dyn = a.staged ? sizeof(double) * (size_t)rn.dev.N : 0;
-    if (a.staged && phase_is_small(st, rn.dev.N, rn.dev.L, (double)h->L[1].A.nnz, rn.dev.N)) {
+    if (rn.plan.top_queued) {
         a.row0 = 0;
         a.row1 = rn.dev.N;
         push_phase(ctx, st, PH_TOP, rn.dev.N).u.t = a;
     } else {
-        run_rows(ctx, st, 0, rn.dev.N,
-                 [&](int r0, int r1) {
+        run_rows(ctx, st, RowRange{0, rn.dev.N, rn.plan.G_all}, rn.dev.L,
+                 [&](int r0, int r1, int grid) {
                      a.row0 = r0;
                      a.row1 = r1;
-                     const int grid = pick_blocks(r1 - r0, rn.dev.L, st->num_cu);
                      IPD_LAUNCH_SP(k_top, a.staged, rn.dev.S > 0, grid, dyn, a);
                  },
                  {rn.dev.r, xnew});
@@ -1221,12 +1100,7 @@ static void launch_top(ipd_amg* h, CycleState* st, const double* b, const double
     ca.n = rn.dev.N;
     ca.hist = st->hist;
     ca.first = first ? 1 : 0;
-    if (st->fuse_enabled) {
-        push_phase(ctx, st, PH_CONV, 0).u.c = ca;
-    } else {
-        hipLaunchKernelGGL(k_conv, dim3(1), dim3(BT), 0, ctx->stream, ca);
-        IPD_KERNEL_CHECK();
-    }
+    push_phase(ctx, st, PH_CONV, 0).u.c = ca;
     flush_fused(ctx, st);  // the loop body ends here: nothing stays queued across calls
 }
 
@@ -1244,6 +1118,52 @@ static void enqueue_loop_body(ipd_amg* h, CycleState* st, const double* b, const
 
 static void ensure_graphs(ipd_amg* h, CycleState* st, const double* b_dev);
 
+// the whole solve phase (cycles == 0) or `cycles` cycles without stopping rules as one single-workgroup launch
+static void launch_solve_small(ipd_ctx* ctx, CycleState* st, const double* b_dev, double* x, int cycles) {
+    const CycleState::Image& im = st->img[IMG_SOLVE];
+    if (st->solve_cached)
+        hipLaunchKernelGGL(k_solve_small<true>, dim3(1), dim3(BT), im.lds, ctx->stream, (const SolveDesc*)im.desc,
+                           b_dev, x, st->x2, st->hist, st->solve_out, cycles);
+    else
+        hipLaunchKernelGGL(k_solve_small<false>, dim3(1), dim3(BT), im.lds, ctx->stream, (const SolveDesc*)im.desc,
+                           b_dev, x, st->x2, st->hist, st->solve_out, cycles);
+    IPD_KERNEL_CHECK();
+}
+
+static void copy_vec(ipd_ctx* ctx, double* dst, const double* src, int N) {
+    IPD_HIP(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, ctx->stream));
+}
+
+// x = the initial guess (NULL: zeros)
+static void load_guess(ipd_ctx* ctx, double* x, const double* guess_dev, int N) {
+    if (guess_dev)
+        copy_vec(ctx, x, guess_dev, N);
+    else
+        IPD_HIP(hipMemsetAsync(x, 0, sizeof(double) * (size_t)N, ctx->stream));
+}
+
+// Times what the stream is given between construction and stop() with HIP events
+struct StreamTimer {
+    hipStream_t stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    explicit StreamTimer(hipStream_t s) : stream(s) {
+        IPD_HIP(hipEventCreate(&e0));
+        IPD_HIP(hipEventCreate(&e1));
+        IPD_HIP(hipEventRecord(e0, stream));
+    }
+    float stop() {   // milliseconds
+        IPD_HIP(hipEventRecord(e1, stream));
+        IPD_HIP(hipEventSynchronize(e1));
+        float ms = 0.f;
+        IPD_HIP(hipEventElapsedTime(&ms, e0, e1));
+        return ms;
+    }
+    ~StreamTimer() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
 // Class_AMG.m:86-109
 void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, double* x_dev,
                    int32_t* it_out, double* rel_res_out, double* rel_resk, double* rhok) {
@@ -1254,34 +1174,20 @@ void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, dou
     const int N = h->L[1].A.nr;
     double* xa = h->x;
     double* xb = st->x2;
-    if (guess_dev)
-        IPD_HIP(hipMemcpyAsync(xa, guess_dev, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-    else
-        IPD_HIP(hipMemsetAsync(xa, 0, sizeof(double) * (size_t)N, ctx->stream));
+    load_guess(ctx, xa, guess_dev, N);
     // what a one-launch solve read back: iterations, last relative residual, then the two histories
     auto deliver = [&](const std::vector<double>& out) {
         const int its = (int)out[0];
         if (rel_resk) std::memcpy(rel_resk, out.data() + 4, sizeof(double) * ((size_t)its + 1));
         if (rhok) std::memcpy(rhok, out.data() + 4 + (o.maxit + 2), sizeof(double) * ((size_t)its + 1));
-        if (x_dev)
-            IPD_HIP(hipMemcpyAsync(x_dev, xa, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                                   ctx->stream));
+        if (x_dev) copy_vec(ctx, x_dev, xa, N);
         if (it_out) *it_out = its;
         if (rel_res_out) *rel_res_out = out[1];
         ctx->sync();
     };
     if (st->small_ok && st->shard_ranks == 1) {
         // small hierarchy: the whole solve phase is one single-workgroup launch
-        if (st->solve_cached)
-            hipLaunchKernelGGL(k_solve_small<true>, dim3(1), dim3(BT), st->img[IMG_SOLVE].lds, ctx->stream,
-                               (const SolveDesc*)st->img[IMG_SOLVE].desc, b_dev, xa, xb, st->hist,
-                               st->solve_out, 0);
-        else
-            hipLaunchKernelGGL(k_solve_small<false>, dim3(1), dim3(BT), st->img[IMG_SOLVE].lds, ctx->stream,
-                               (const SolveDesc*)st->img[IMG_SOLVE].desc, b_dev, xa, xb, st->hist,
-                               st->solve_out, 0);
-        IPD_KERNEL_CHECK();
+        launch_solve_small(ctx, st, b_dev, xa, 0);
         const size_t nout = 4 + 2 * ((size_t)o.maxit + 2);
         std::vector<double> out(nout);
         ctx->fetch(st->solve_out, out.data(), nout);
@@ -1296,11 +1202,7 @@ void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, dou
             return;
         }
         // not usable right now: restore the initial guess and take the multi-launch path
-        if (guess_dev)
-            IPD_HIP(hipMemcpyAsync(xa, guess_dev, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                                   ctx->stream));
-        else
-            IPD_HIP(hipMemsetAsync(xa, 0, sizeof(double) * (size_t)N, ctx->stream));
+        load_guess(ctx, xa, guess_dev, N);
     }
     launch_top(h, st, b_dev, xa, nullptr, xb, true);                            // :89
     std::swap(xa, xb);
@@ -1329,9 +1231,7 @@ void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, dou
         }
         it -= 1;                                                                 // :108
     }
-    if (x_dev)
-        IPD_HIP(hipMemcpyAsync(x_dev, xa, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                               ctx->stream));
+    if (x_dev) copy_vec(ctx, x_dev, xa, N);
     if (xa != h->x) std::swap(h->x, st->x2);  // keep h->x pointing at the current iterate
     if (it_out) *it_out = it;
     if (rel_res_out) *rel_res_out = rel_res;
@@ -1401,8 +1301,8 @@ bool amg_level1_walk(ipd_amg* h, LevelDev* lv, int* staged, int* grid) {
     if (st->shard_ranks > 1 && !st->shard_emulate) return false;
     const LevelRun& rn = st->run[1];
     *lv = rn.dev;
-    *staged = rn.staged;
-    *grid = pick_blocks(rn.dev.N, rn.dev.L, st->num_cu);
+    *staged = rn.plan.staged ? 1 : 0;
+    *grid = rn.plan.G_all;
     return true;
 }
 
@@ -1412,18 +1312,7 @@ bool amg_block_levels(ipd_amg* h, std::vector<BlockLevel>* out) {
     IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
     if (st->shard_ranks > 1) return false;
     if (!out) return true;
-    const int cu = st->num_cu;
-    auto csr_of = [&](const Csr& m, int L) {
-        BlockCsr c;
-        c.nr = m.nr;
-        c.nc = m.nc;
-        c.L = L;
-        c.grid = pick_blocks(m.nr, L, cu);
-        c.rp = m.rp;
-        c.ci = m.ci;
-        c.va = m.va;
-        return c;
-    };
+    auto csr_of = [](const Csr& m, int L, int grid) { return BlockCsr{m.nr, m.nc, L, grid, m.rp, m.ci, m.va}; };
     out->assign((size_t)h->J + 1, BlockLevel{});
     for (int k = 1; k <= h->J; ++k) {
         const Level& lv = h->L[k];
@@ -1431,18 +1320,18 @@ bool amg_block_levels(ipd_amg* h, std::vector<BlockLevel>* out) {
         BlockLevel& bl = (*out)[(size_t)k];
         bl.N = lv.N;
         bl.nf = lv.nf;
-        bl.A = csr_of(lv.A, rn.dev.L);
+        const LaunchLevel& p = rn.plan;
+        bl.A = csr_of(lv.A, p.L, p.G_all);
+        bl.sweep[0] = p.sweep[0];
+        bl.sweep[1] = p.sweep[1];
         bl.dinv = lv.dinv;
         bl.Axi = lv.Axi;
         bl.xx = lv.xx;
         if (k < h->J) {
             const Level& cl = h->L[k + 1];
-            bl.Pt = csr_of(cl.Pt, rn.restrict_args.L);
-            bl.P = csr_of(cl.P, rn.prolong_args.L);
-            const Csr& T1 = cl.T1;
-            // amg_cycle's rule for the fused residual + restriction (the fused-program case aside)
-            if (!switch_on("IPD_NO_RRC") && T1.rp && T1.nr == cl.Pt.nr && T1.nnz <= (1 << 18))
-                bl.T1 = csr_of(T1, pick_lanes(T1.nnz + cl.Pt.nnz, cl.Pt.nr, cu));
+            bl.Pt = csr_of(cl.Pt, p.rest.L, p.rest.G);
+            bl.P = csr_of(cl.P, p.prol.L, p.prol.G);
+            if (p.rrc_rule) bl.T1 = csr_of(cl.T1, p.rrc_walk.L, p.rrc_walk.G);
         } else {
             const PcgArgs& a = rn.pcg;
             bl.pcg_L = a.L;
@@ -1689,6 +1578,31 @@ static void ensure_graphs(ipd_amg* h, CycleState* st, const double* b_dev) {
     st->gb = b_dev;
 }
 
+// Times `cycles` loop bodies on x_dev, eager or as the captured graphs, after the initial residual
+// (Class_AMG.m:89); milliseconds
+static float time_loop_bodies(ipd_amg* h, CycleState* st, const double* b_dev, double* x_dev, int cycles,
+                              bool use_graph) {
+    ipd_ctx* ctx = h->ctx;
+    const int N = h->L[1].A.nr;
+    copy_vec(ctx, h->x, x_dev, N);
+    launch_top(h, st, b_dev, h->x, nullptr, st->x2, true);   // x stays in h->x
+    copy_vec(ctx, h->x, st->x2, N);
+    if (use_graph) ensure_graphs(h, st, b_dev);
+    double* xs[2] = {h->x, st->x2};
+    StreamTimer timer(ctx->stream);
+    int v = 0;
+    for (int c = 0; c < cycles; ++c) {
+        if (use_graph)
+            IPD_HIP(hipGraphLaunch(st->gexec[v], ctx->stream));
+        else
+            enqueue_loop_body(h, st, b_dev, xs[v], xs[v ^ 1]);
+        v ^= 1;
+    }
+    const float ms = timer.stop();
+    copy_vec(ctx, x_dev, xs[v], N);
+    return ms;
+}
+
 extern "C" int ipd_amg_bench_cycles(ipd_amg* h, const double* b_dev, double* x_dev, int cycles,
                                     double* total_ms, double* bytes_per_cycle) {
     return ipd_guard([&] {
@@ -1698,77 +1612,21 @@ extern "C" int ipd_amg_bench_cycles(ipd_amg* h, const double* b_dev, double* x_d
         CycleState* st = state_of(h);
         IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
         const int N = h->L[1].A.nr;
-        if (st->small_ok) {  // one launch runs all the cycles (no stopping rules)
-            IPD_HIP(hipMemcpyAsync(h->x, x_dev, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                                   ctx->stream));
-            hipEvent_t e0, e1;
-            IPD_HIP(hipEventCreate(&e0));
-            IPD_HIP(hipEventCreate(&e1));
-            IPD_HIP(hipEventRecord(e0, ctx->stream));
-            if (st->solve_cached)
-                hipLaunchKernelGGL(k_solve_small<true>, dim3(1), dim3(BT), st->img[IMG_SOLVE].lds,
-                                   ctx->stream, (const SolveDesc*)st->img[IMG_SOLVE].desc, b_dev, h->x, st->x2,
-                                   st->hist, st->solve_out, cycles);
-            else
-                hipLaunchKernelGGL(k_solve_small<false>, dim3(1), dim3(BT), st->img[IMG_SOLVE].lds,
-                                   ctx->stream, (const SolveDesc*)st->img[IMG_SOLVE].desc, b_dev, h->x, st->x2,
-                                   st->hist, st->solve_out, cycles);
-            IPD_KERNEL_CHECK();
-            IPD_HIP(hipEventRecord(e1, ctx->stream));
-            IPD_HIP(hipEventSynchronize(e1));
-            float msf = 0.f;
-            IPD_HIP(hipEventElapsedTime(&msf, e0, e1));
-            IPD_HIP(hipEventDestroy(e0));
-            IPD_HIP(hipEventDestroy(e1));
-            IPD_HIP(hipMemcpyAsync(x_dev, h->x, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                                   ctx->stream));
-            ctx->sync();
-            *total_ms = msf;
-            if (bytes_per_cycle) *bytes_per_cycle = cycle_bytes(h);
-            return;
-        }
-        if (st->res.ok) {  // one launch of co-resident workgroups runs all the cycles
-            IPD_HIP(hipMemcpyAsync(h->x, x_dev, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                                   ctx->stream));
-            float msf = 0.f;
-            if (run_resident(h, st, b_dev, h->x, cycles, nullptr, &msf)) {
-                IPD_HIP(hipMemcpyAsync(x_dev, h->x, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                                       ctx->stream));
-                ctx->sync();
-                *total_ms = msf;
-                if (bytes_per_cycle) *bytes_per_cycle = cycle_bytes(h);
-                return;
-            }
-        }
-        const bool use_graph = !switch_on("IPD_NO_GRAPH");
-        IPD_HIP(hipMemcpyAsync(h->x, x_dev, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-        // initial residual (Class_AMG.m:89); x stays in h->x
-        launch_top(h, st, b_dev, h->x, nullptr, st->x2, true);
-        IPD_HIP(hipMemcpyAsync(h->x, st->x2, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-        if (use_graph) ensure_graphs(h, st, b_dev);
-        double* xs[2] = {h->x, st->x2};
-        hipEvent_t ev0, ev1;
-        IPD_HIP(hipEventCreate(&ev0));
-        IPD_HIP(hipEventCreate(&ev1));
-        IPD_HIP(hipEventRecord(ev0, ctx->stream));
-        int v = 0;
-        for (int c = 0; c < cycles; ++c) {
-            if (use_graph)
-                IPD_HIP(hipGraphLaunch(st->gexec[v], ctx->stream));
-            else
-                enqueue_loop_body(h, st, b_dev, xs[v], xs[v ^ 1]);
-            v ^= 1;
-        }
-        IPD_HIP(hipEventRecord(ev1, ctx->stream));
-        IPD_HIP(hipEventSynchronize(ev1));
         float ms = 0.f;
-        IPD_HIP(hipEventElapsedTime(&ms, ev0, ev1));
-        IPD_HIP(hipEventDestroy(ev0));
-        IPD_HIP(hipEventDestroy(ev1));
-        IPD_HIP(hipMemcpyAsync(x_dev, xs[v], sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                               ctx->stream));
+        bool done = false;
+        if (st->small_ok || st->res.ok) {  // one launch runs all the cycles (no stopping rules)
+            copy_vec(ctx, h->x, x_dev, N);
+            if (st->small_ok) {            // ... of one workgroup
+                StreamTimer timer(ctx->stream);
+                launch_solve_small(ctx, st, b_dev, h->x, cycles);
+                ms = timer.stop();
+                done = true;
+            } else {                       // ... of co-resident workgroups
+                done = run_resident(h, st, b_dev, h->x, cycles, nullptr, &ms);
+            }
+            if (done) copy_vec(ctx, x_dev, h->x, N);
+        }
+        if (!done) ms = time_loop_bodies(h, st, b_dev, x_dev, cycles, !switch_on("IPD_NO_GRAPH"));
         ctx->sync();
         *total_ms = ms;
         if (bytes_per_cycle) *bytes_per_cycle = cycle_bytes(h);
@@ -1807,22 +1665,14 @@ extern "C" int ipd_amg_bench_subcycle(ipd_amg* h, int reps, double* total_ms, in
             }
             ctx->upload(h->L[st->k_sub].r, rr.data(), rr.size());
         }
-        hipEvent_t e0, e1;
-        IPD_HIP(hipEventCreate(&e0));
-        IPD_HIP(hipEventCreate(&e1));
         hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->img[IMG_SUB].lds, ctx->stream,
                            (const SolveDesc*)st->img[IMG_SUB].desc, 0);
-        IPD_HIP(hipEventRecord(e0, ctx->stream));
+        StreamTimer timer(ctx->stream);
         for (int r = 0; r < reps; ++r)
             hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->img[IMG_SUB].lds, ctx->stream,
                                (const SolveDesc*)st->img[IMG_SUB].desc, 0);
-        IPD_HIP(hipEventRecord(e1, ctx->stream));
-        IPD_HIP(hipEventSynchronize(e1));
+        const float ms = timer.stop();
         IPD_KERNEL_CHECK();
-        float ms = 0.f;
-        IPD_HIP(hipEventElapsedTime(&ms, e0, e1));
-        IPD_HIP(hipEventDestroy(e0));
-        IPD_HIP(hipEventDestroy(e1));
         *total_ms = ms;
         long long hs[16];
         ctx->fetch(dbg, hs, 16);
@@ -1849,18 +1699,10 @@ extern "C" int ipd_amg_bench_sweeps(ipd_amg* h, int k, int reps, double* total_m
         rn.e_zero = true;
         for (int w = 0; w < 4; ++w) launch_sweep(h, st, k, h->opts.isnsp, false);
         flush_fused(ctx, st);
-        hipEvent_t ev0, ev1;
-        IPD_HIP(hipEventCreate(&ev0));
-        IPD_HIP(hipEventCreate(&ev1));
-        IPD_HIP(hipEventRecord(ev0, ctx->stream));
+        StreamTimer timer(ctx->stream);
         for (int s = 0; s < reps; ++s) launch_sweep(h, st, k, h->opts.isnsp, false);
         flush_fused(ctx, st);
-        IPD_HIP(hipEventRecord(ev1, ctx->stream));
-        IPD_HIP(hipEventSynchronize(ev1));
-        float ms = 0.f;
-        IPD_HIP(hipEventElapsedTime(&ms, ev0, ev1));
-        IPD_HIP(hipEventDestroy(ev0));
-        IPD_HIP(hipEventDestroy(ev1));
+        const float ms = timer.stop();
         *total_ms = ms;
         if (launches_per_sweep) *launches_per_sweep = lv.nf > 0 ? 2 : 1;
         if (bytes_per_sweep) *bytes_per_sweep = spmv_bytes(lv.A) + 6 * 8.0 * lv.A.nr;
@@ -1895,30 +1737,7 @@ extern "C" int ipd_amg_bench_cycles_sharded(ipd_amg* h, const double* b_dev, dou
             st->shard_rank = comm_rank(ctx);
             IPD_REQUIRE(st->shard_ranks == 1 || ctx->comm, IPD_E_COMM, "call ipd_comm_init first");
         }
-        const int N = h->L[1].A.nr;
-        IPD_HIP(hipMemcpyAsync(h->x, x_dev, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-        launch_top(h, st, b_dev, h->x, nullptr, st->x2, true);
-        IPD_HIP(hipMemcpyAsync(h->x, st->x2, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-        double* xs[2] = {h->x, st->x2};
-        hipEvent_t ev0, ev1;
-        IPD_HIP(hipEventCreate(&ev0));
-        IPD_HIP(hipEventCreate(&ev1));
-        IPD_HIP(hipEventRecord(ev0, ctx->stream));
-        int v = 0;
-        for (int c = 0; c < cycles; ++c) {
-            enqueue_loop_body(h, st, b_dev, xs[v], xs[v ^ 1]);
-            v ^= 1;
-        }
-        IPD_HIP(hipEventRecord(ev1, ctx->stream));
-        IPD_HIP(hipEventSynchronize(ev1));
-        float ms = 0.f;
-        IPD_HIP(hipEventElapsedTime(&ms, ev0, ev1));
-        IPD_HIP(hipEventDestroy(ev0));
-        IPD_HIP(hipEventDestroy(ev1));
-        IPD_HIP(hipMemcpyAsync(x_dev, xs[v], sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
-                               ctx->stream));
+        const float ms = time_loop_bodies(h, st, b_dev, x_dev, cycles, false);
         ctx->sync();
         *total_ms = ms;
         if (bytes_per_cycle) *bytes_per_cycle = cycle_bytes(h);

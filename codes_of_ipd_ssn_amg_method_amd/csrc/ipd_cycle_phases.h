@@ -24,10 +24,7 @@
 //      launches, deterministic, and reduced in the same LDS exchange as the rows.
 #pragma once
 
-// matrix entries in flight per lane and batch (one 4-entry vector of the padded format).
-// 8 was slower on every workload (m=n=1024 Class 1 run 1.58 -> 1.55 s, tree-mask W cycle
-// 0.532 -> 0.503 ms): short rows fill 3-6 of the slots and the rest are clamped dummy loads.
-static constexpr int ROW_U = 4;
+#include "ipd_limits.h"   // BT, ROW_U (matrix entries in flight per lane and batch)
 
 // LDS scratch of a phase
 struct PhaseLds {
@@ -549,7 +546,7 @@ __device__ __forceinline__ void phase_rrc(const RrcArgs& a, int b, int G, PhaseL
 }
 
 // ---------------------------------------------------------------------------
-// top of the Class_AMG loop: x_new = x + e ; r = b - A x_new  (k_conv then forms ||r||)
+// top of the Class_AMG loop: x_new = x + e ; r = b - A x_new  (the PH_CONV phase then forms ||r||)
 // ---------------------------------------------------------------------------
 struct TopArgs {
     LevelDev lv;

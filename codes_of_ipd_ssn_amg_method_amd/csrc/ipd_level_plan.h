@@ -12,6 +12,7 @@
 #include <numeric>
 #include <vector>
 
+#include "ipd_launch_plan.h"
 #include "ipd_limits.h"
 
 struct LevelShape {   // level k of the hierarchy, as far as the planner looks at it
@@ -29,9 +30,10 @@ struct PlanOptions {
     size_t sol_head = SOL_HEAD;   // the image head (SolveDesc and its relocation table)
 };
 
-// The switches of the level planner and of the resident planner (ipd_switches.h), read by read_plan_switches
-// at the call in which they take effect: amg_prepare_levels and again amg_attach_maskop
-struct PlanSwitches {
+// The switches of the launch planner (ipd_launch_plan.h), of the level planner and of the resident planner
+// (ipd_switches.h), read by read_plan_switches at the call in which they take effect: amg_prepare_levels and
+// again amg_attach_maskop
+struct PlanSwitches : LaunchSwitches {
     bool no_poly = false, no_blk = false, no_bpoly = false, no_blkdense = false, no_small = false,
          no_subcycle = false, no_resident = false, no_resident_remote = false, no_resident_three = false,
          no_resident_deep = false, no_resident_big = false, no_res_poly4 = false;

@@ -20,6 +20,20 @@ static constexpr int BT = 512;
 
 static constexpr int STAGE_MAX = 7680;   // vector entries staged in LDS (60 KiB)
 
+// matrix entries in flight per lane and batch (one 4-entry vector of the padded format).
+// 8 was slower on every workload (m=n=1024 Class 1 run 1.58 -> 1.55 s, tree-mask W cycle
+// 0.532 -> 0.503 ms): short rows fill 3-6 of the slots and the rest are clamped dummy loads.
+static constexpr int ROW_U = 4;
+
+// Thresholds of the launch path's rules (ipd_launch_plan.h, where the measurements behind them are recorded)
+static constexpr double QUEUED_NNZ_MAX = 6000.0;   // matrix entries of a phase queued into the fused program
+static constexpr int RRC_T1_NNZ_MAX = 1 << 18;     // entries of T1 = P'A up to which residual + restriction run fused
+static constexpr int PAD_ROWS_MAX = 65535;         // rows of a padded copy (16-bit columns)
+static constexpr double PAD_AVG_MIN = 0.5;         // mean off-diagonal row length from which a level is padded
+static constexpr double PAD_SLACK_FACTOR = 1.3, PAD_SLACK = 16.0;   // pad width S <= 1.3 * mean + 16
+static constexpr int PAD_BATCHES = 8;              // ROW_U batches per lane of a padded row before the chip-filling rule
+static constexpr int PCG_LANES_MAX = 64;           // lanes per row of the coarsest level's PCG
+
 // levels a single-workgroup image (SolveDesc) holds
 static constexpr int SOLVE_ML = 24;
 // An LDS image (ipd_level_plan.h): the planner admits levels while the predicted dynamic LDS stays within the

@@ -90,7 +90,7 @@ static inline int resident_cdiv(int a, int b) { return (a + b - 1) / b; }
 // copy with its longest row as stride (built once the hierarchy is known to be taken)
 static inline int resident_stride(const ResidentInputs& in, int k, bool* priv) {
     *priv = in.S[k] <= 0 && in.L[k].maxoff > 0;
-    return *priv ? (in.L[k].maxoff + 3) / 4 * 4 : in.S[k];
+    return *priv ? pad_stride(in.L[k].maxoff) : in.S[k];
 }
 
 // ---- level-resident kernel (k_resident) ----------------------------------------------------
