@@ -11,6 +11,14 @@
 //     lane l holds entries l, l+64, ... of the padded row (16-bit column, fp64 value) in VGPRs;
 //   * every workgroup keeps the full vectors of both levels (x, e, r, r - A e, A*1) in LDS, so a
 //     row dot product is LDS gathers + one DPP wave sum, no memory traffic at all;
+//   * 16-entry rows (the dense regime, the metric's workload): level 1 is held turned by 90 degrees, in
+//     COLUMN SLICES -- thread t, which polls granules t and t + 512 of a block, holds columns t and t + 512
+//     of the (at most 8) rows its workgroup owns in the other block, densely: 32 doubles, what the two row
+//     slices cost, and no column registers.  A received value is multiplied in the register it arrived in,
+//     a transposing butterfly (res_cs_rows) leaves the waves' row totals in LDS, and after ONE barrier
+//     lanes 0..7 of wave 0 add them, finish the rows and publish the next half sweep from registers
+//     (half1_cs): no gather phase, no store phase, no closing barrier and no trip of the published values
+//     through LDS remain on a half sweep's chain.  The other kernels keep a row per wave;
 //   * the only global traffic is the hand-off of each half sweep's result: a row's new value is
 //     published as ONE 16-byte write-through (sc1) store of two self-tagged 8-byte granules
 //     {lo, tag, hi, tag} (MI355X guide, Guideline 16 R2: the data is the flag) and every
@@ -382,6 +390,56 @@ __device__ __forceinline__ double res_red8_tree(const double* red) {
     return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
 }
 
+// ---- column slices (k_resident with 16-entry rows: level 1 turned by 90 degrees) ----------------------
+// Thread t holds columns t and t + BT of the (at most RES_WAVES) rows its workgroup owns in a block, so a
+// value that thread t has just received -- or read from LDS -- meets its matrix entries in the register it
+// arrived in.  res_cs_rows forms the workgroup's row totals from two such values per thread:
+//   1. part[r] = A[r][0] v0 + A[r][1] v1: one multiply and one fused multiply-add per row;
+//   2. a transposing butterfly over the wave: 8 -> 4 values (permlane32 swap: the lower half of the wave keeps
+//      rows 0..3, the upper half rows 4..7), 4 -> 2 (permlane16 swap), 2 -> 1 (DPP row_ror:8), then three more
+//      DPP steps on the single value: lanes 8 r .. 8 r + 7 end up with the wave's total of row r;
+//   3. lane 8 r writes it to part_out[8 r + w].
+// After the caller's barrier res_red8_tree(part_out + 8 r) is row r's sum over all columns.  Map, butterfly and
+// tree are the same in every workgroup, so every workgroup forms the same bits from the same values.
+__device__ __forceinline__ void res_swap_halves32(double& a, double& b) {
+    // lanes 32..63 of a <-> lanes 0..31 of b
+    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+    a = __hiloint2double((int)hi[0], (int)lo[0]);
+    b = __hiloint2double((int)hi[1], (int)lo[1]);
+}
+__device__ __forceinline__ void res_swap_rows16(double& a, double& b) {
+    // odd 16-lane rows of a <-> even 16-lane rows of b
+    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+    a = __hiloint2double((int)hi[0], (int)lo[0]);
+    b = __hiloint2double((int)hi[1], (int)lo[1]);
+}
+__device__ __forceinline__ void res_cs_rows(const double (&A)[RES_WAVES][2], double v0, double v1, double* part_out,
+                                            int w, int lane) {
+    static_assert(RES_WAVES == 8, "eight rows per block and workgroup");
+    double p[RES_WAVES];
+#pragma unroll
+    for (int r = 0; r < RES_WAVES; ++r) p[r] = __builtin_fma(A[r][1], v1, A[r][0] * v0);
+    double q[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {   // lanes 0..31: rows k, lanes 32..63: rows k + 4
+        res_swap_halves32(p[k], p[k + 4]);
+        q[k] = p[k] + p[k + 4];
+    }
+    double t[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {   // 16-lane rows 0..3 of the wave: rows k, k + 2, k + 4, k + 6
+        res_swap_rows16(q[k], q[k + 2]);
+        t[k] = q[k] + q[k + 2];
+    }
+    const bool f = (lane & 8) != 0;   // lanes 8..15 of a 16-lane row keep the odd row
+    const double keep = f ? t[1] : t[0], send = f ? t[0] : t[1];
+    double u = keep + dpp_get<0x128, 0xf>(send);   // row_ror:8 -- the value of lane ^ 8
+    u = subwave_sum(u, 8);
+    if ((lane & 7) == 0) part_out[8 * (lane >> 3) + w] = u;
+}
+
 // The tail workgroup of a remote-tail launch: k_subcycle's body as a server.  It loads the LDS
 // image of levels 3..J once, then for every visit waits for r_3 (D.Nt <= BT granules in tin), runs
 // the V or W sub-cycle rooted at level 3 out of LDS (both legs of MG_Wcycle.m:28-30 when level 3 is
@@ -456,7 +514,8 @@ __device__ __forceinline__ void res_tail_workgroup(const ResDesc& D, char* dyn_r
 // (the layout of k_solve_small; the last slot: hand-offs of the launch).  fixed_cycles > 0: exactly that many loop bodies, no stopping
 // rules (bench hook).  dbg (optional, 16 words): [0] shader clocks spent waiting in sweeps by
 // workgroup 0, [1] clocks of the whole loop, [2] number of hand-offs, [3] 100 MHz ticks of the loop,
-// [4] clocks in the barrier before the publish, [5] in the store phase, [6] in the closing barrier.
+// [4] clocks in the barrier before the publish, [5] in the store phase, [6] in the closing barrier, [9] in the
+// finishing lanes of the column-slice half sweeps (whose one barrier counts as [4], their receipt as [5]).
 template <int KE1, int KE2, int KE3 = 0, bool POLY2 = false>
 __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const double* __restrict__ bvec,
                                                     double* xg, double* out, int fixed_cycles) {
@@ -487,11 +546,16 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     constexpr int oBETA = oAX2 + RES_NMAX / 2;         // ... beta of the C nodes: upper half of the AX2 slot (!THREE)
     constexpr int oU = oRR2;                           // ... beta .* e_2: lower half of the RR2 slot (free after the visit)
     constexpr int oR3 = 9 * RES_NMAX + RES_NMAX / 2, oE3 = oR3 + RES_TAIL_MAX, oP3 = oE3 + RES_TAIL_MAX;
+    // column slices: the waves' row totals, two buffers of RES_WAVES rows x RES_WAVES waves, and the waves' parts of
+    // the kernel-space scalar (two buffers by hand-off parity).  They share the tail level's slots: the tail runs
+    // between level 2's hand-offs, where no level-1 total is in flight.
+    constexpr int oPART = oR3, oPART9 = oR3 + 2 * RES_WAVES * RES_WAVES;
+    static_assert(2 * RES_WAVES * RES_WAVES + 2 * RES_WAVES <= 3 * RES_TAIL_MAX, "the totals fit the tail's slots");
     constexpr int oRED = oP3 + RES_TAIL_MAX;          // 2*RES_WAVES doubles
     constexpr int oPUB = oRED + 2 * RES_WAVES;        // values the waves publish this step (2 blocks)
     constexpr int oOWN = oPUB + 2 * RES_WAVES;        // 10 scalars of each wave's rows
     int* fail = reinterpret_cast<int*>(sm + oOWN + 10 * RES_WAVES);
-    long long* dbg_acc = reinterpret_cast<long long*>(sm + oOWN + 10 * RES_WAVES + 1);   // 8 words
+    long long* dbg_acc = reinterpret_cast<long long*>(sm + oOWN + 10 * RES_WAVES + 1);   // 9 words (+1 .. +9; rowp starts at +12)
     // entry ranges of this wave's rows of the transfer operators: read once, a walk then starts
     // with its entries instead of a dependent trip for the row pointers
     int* rowp = reinterpret_cast<int*>(sm + oOWN + 10 * RES_WAVES + 12);                 // 12 ints per wave
@@ -517,10 +581,57 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     const int r3 = v3 ? row3 : 0;
 
     // ---- matrix slices -> registers (the only read of the matrices in the whole solve) --------
-    unsigned cF[KE1 / 2], cC[KE1 / 2], c2[KE2 / 2];
-    double aF[KE1], aC[KE1], a2[KE2];
-    res_load_slice<KE1>(D.L1, rF, vF, lane, cF, aF);
-    res_load_slice<KE1>(D.L1, rC, vC, lane, cC, aC);
+    // 16-entry rows: level 1 in column slices (see res_cs_rows) -- thread t holds columns nf + t, nf + t + BT of
+    // the workgroup's F rows (AF) and columns t, t + BT of its C rows (AC), 32 doubles, and no column registers.
+    // The layout has no slot for an entry of an F row in an F column or of a C row in a C column (the bigraph
+    // level 1 has none: transfer.m:20-21 needs a diagonal Aff, and the Newton systems' Acc is diagonal too); a
+    // hierarchy that has one is reported to the host (out[3] = 2), which drops its resident plan: it runs as launches.
+    constexpr bool CS1 = KE1 == 16;
+    constexpr int KR1 = CS1 ? 4 : KE1;   // the row-per-wave slices of level 1 (unused with column slices)
+    unsigned cF[KR1 / 2], cC[KR1 / 2], c2[KE2 / 2];
+    double aF[KR1], aC[KR1], a2[KE2];
+    double AF[RES_WAVES][2], AC[RES_WAVES][2];
+    (void)cF; (void)cC; (void)aF; (void)aC; (void)AF; (void)AC;
+    if constexpr (CS1) {
+        // dense slices from the padded rows through LDS (the vector slots are still unused: a block's stage is
+        // RES_WAVES rows of 2 BT doubles): zero the stage, wave w scatters row w, every thread reads its columns
+        constexpr int SW = 2 * BT;
+        bool lost = false;
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {
+            for (int i = tid; i < RES_WAVES * SW; i += BT) sm[i] = 0.0;
+            __syncthreads();
+            const int row = blk == 0 ? rF : rC, c0 = blk == 0 ? nf : 0, ncol = blk == 0 ? nc : nf;
+            if (blk == 0 ? vF : vC)
+                for (int e = lane; e < D.L1.S; e += 64) {
+                    const size_t off = (size_t)row * D.L1.S + e;
+                    const int k = (int)D.L1.pci[off] - c0;
+                    const double aa = D.L1.pva[off];
+                    if (aa != 0.0) {   // (padding entries have value 0)
+                        if (k >= 0 && k < ncol && k < SW)
+                            sm[w * SW + k] = aa;
+                        else
+                            lost = true;
+                    }
+                }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < RES_WAVES; ++r)
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const double aa = sm[r * SW + tid + u * BT];
+                    if (blk == 0) AF[r][u] = aa; else AC[r][u] = aa;
+                }
+            __syncthreads();
+        }
+        if (lost) {   // word 1: "the layout cannot hold this matrix" (not a time-out); word 0 ends everybody's waits
+            __hip_atomic_store(D.tmo + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(D.tmo, 0x7ffffffeu, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    } else {
+        res_load_slice<KR1>(D.L1, rF, vF, lane, cF, aF);
+        res_load_slice<KR1>(D.L1, rC, vC, lane, cC, aC);
+    }
     if (POLY2) {
 #pragma unroll
         for (int q = 0; q < KE2; ++q) {
@@ -687,7 +798,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     bool dead = false;      // a spin gave up somewhere: skip every further wait
     const bool dbg = D.dbg != nullptr && b == 0 && tid == 0;
     if (dbg) {
-        dbg_acc[0] = dbg_acc[3] = dbg_acc[4] = dbg_acc[5] = dbg_acc[6] = dbg_acc[7] = 0;
+        dbg_acc[0] = dbg_acc[3] = dbg_acc[4] = dbg_acc[5] = dbg_acc[6] = dbg_acc[7] = dbg_acc[8] = 0;
         dbg_acc[1] = __builtin_amdgcn_s_memtime();
         dbg_acc[2] = __builtin_amdgcn_s_memrealtime();
     }
@@ -709,6 +820,9 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
 #define RES_HANDOFF(NJ, n, gA, cA, gB, cB, STORE, EXTRA, want_sums, t0, t1)                        \
     RES_HANDOFF_P(NJ, n, gA, cA, gB, cB, {}, STORE, EXTRA, want_sums, t0, t1)
 #define RES_HANDOFF_P(NJ, n, gA, cA, gB, cB, PRE, STORE, EXTRA, want_sums, t0, t1)                 \
+    RES_HANDOFF_PV(NJ, n, gA, cA, gB, cB, sm[oPUB + lane], PRE, STORE, EXTRA, want_sums, t0, t1)
+    // PUBV: the value lane 8 * block + row of wave 0 publishes (column slices: formed in the lane from PART)
+#define RES_HANDOFF_PV(NJ, n, gA, cA, gB, cB, PUBV, PRE, STORE, EXTRA, want_sums, t0, t1)          \
     do {                                                                                           \
         double hv_[NJ], pa_[NJ], pb_[NJ];                                                          \
         (void)pa_;                                                                                 \
@@ -725,7 +839,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             const bool second_ = lane >= RES_WAVES;                                                \
             if (lane < 2 * RES_WAVES && l8_ < (second_ ? (cB) : (cA)) &&                           \
                 !(seq == D.dbg_skip_seq && b == G - 1))                                            \
-                res_publish(rs, seq, (second_ ? (gB) : (gA)) + l8_, sm[oPUB + lane]);              \
+                res_publish(rs, seq, (second_ ? (gB) : (gA)) + l8_, (PUBV));                       \
         }                                                                                          \
         double p0 = 0.0, p1 = 0.0;                                                                 \
         _Pragma("unroll") for (int u_ = 0; u_ < NJ; ++u_) {                                        \
@@ -801,14 +915,54 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     (void)dum1;
 
     // r = b - A x (rows of this wave), ||r||, c1 for a zero start; E1 := 0        Class_AMG.m:89,96,103
+    // column slices: state of the half sweeps' pipeline.  csFed: the block (0: F, 1: C) whose rows' totals buffer
+    // csBuf of PART holds, formed from the values of the last hand-off as they arrived (-1: none).  eFo / eCo: in
+    // the finishing lanes (wave 0, lane r < RES_WAVES) the iterate of the workgroup's rows loF + r / loC + r.
+    // Every change of an own row's e goes through a publish of that lane, so the lane tracks it in a register
+    // (wv + c has the bits of the received v + c that the other threads store) and never reads an entry of E1
+    // that another thread may be shifting.
+    int csFed = -1, csBuf = 0;
+    double eFo = 0.0, eCo = 0.0;
+    (void)csFed; (void)csBuf; (void)eFo; (void)eCo;
+    // A times the LDS vector at `off` on both blocks' own rows, one call each: thread t brings entries t, t + BT of
+    // the other block.  The caller's barrier follows; then finishing lane 8 sec + r holds row r's total of block sec.
+    auto cs_both_rows = [&](int off) __attribute__((always_inline)) {
+        const double f0 = tid < nc ? sm[off + nf + tid] : 0.0, f1 = tid + BT < nc ? sm[off + nf + tid + BT] : 0.0;
+        const double g0 = tid < nf ? sm[off + tid] : 0.0, g1 = tid + BT < nf ? sm[off + tid + BT] : 0.0;
+        res_cs_rows(AF, f0, f1, sm + oPART, w, lane);
+        res_cs_rows(AC, g0, g1, sm + oPART + RES_WAVES * RES_WAVES, w, lane);
+        csFed = -1;
+        eFo = eCo = 0.0;   // (dead outside a run of half sweeps: its first one reloads them)
+    };
+
+    // ... after the hand-off's publish barrier, in a publishing lane (wave 0, lane 8 sec + r): b - A v (top) or
+    // r - A v of its row, from the eight waves' parts -- published from the register, no trip through oPUB
+    auto cs_row_value = [&](int off, bool rhs_b) __attribute__((always_inline)) {
+        const bool sec = lane >= RES_WAVES;
+        const int r = lane & (RES_WAVES - 1);
+        const int row = sec ? (loC + r < hiC ? loC + r : hiC - 1) : (loF + r < hiF ? loF + r : hiF - 1);
+        const double T = res_red8_tree(sm + oPART + RES_WAVES * lane);
+        const double dg_ = sm[oOWN + (sec ? 3 : 0) * RES_WAVES + r];
+        const double base = rhs_b ? sm[oOWN + (sec ? 5 : 2) * RES_WAVES + r] : sm[oR1 + row];
+        return base - (T + dg_ * sm[off + row]);
+    };
+
     auto top = [&]() __attribute__((always_inline)) {
-        const double sF = wave_sum(res_rowdot_fma<KE1, 8 * oX>(cF, aF, smb));
-        const double sC = wave_sum(res_rowdot_fma<KE1, 8 * oX>(cC, aC, smb));
+        if constexpr (CS1) {
+            cs_both_rows(oX);
+        } else {
+        const double sF = wave_sum(res_rowdot_fma<KR1, 8 * oX>(cF, aF, smb));
+        const double sC = wave_sum(res_rowdot_fma<KR1, 8 * oX>(cC, aC, smb));
         if (lane == 0) {
             sm[oPUB + w] = bF - (sF + dgF * sm[oX + rF]);
             sm[oPUB + RES_WAVES + w] = bC - (sC + dgC * sm[oX + rC]);
         }
+        }
         double nrm2 = 0.0, sumr = 0.0;
+        if constexpr (CS1)
+            RES_HANDOFF_PV(4, N1, loF, hiF - loF, loC, hiC - loC, cs_row_value(oX, true), {},
+                           { sm[oR1 + j] = v; sm[oE1 + j] = 0.0; p0 += v * v; p1 += v; }, {}, 2, nrm2, sumr);
+        else
         RES_HANDOFF(4, N1, loF, hiF - loF, loC, hiC - loC,
                     { sm[oR1 + j] = v; sm[oE1 + j] = 0.0; p0 += v * v; p1 += v; }, {}, 2, nrm2, sumr);
         c1 = nsp ? sumr * rxx1 : 0.0;
@@ -825,7 +979,147 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     // one half of a bigraph Gauss-Seidel sweep on level 1.  `first`: rows of the first half (the
     // other half still holds the old iterate); second half: + the shift by c of both halves and
     // the scalar of the next sweep.                         MG_Vcycle.m:15-21,34-38; Class_AMG.m:56-59
+    //
+    // Column slices: ONE barrier per half sweep.  The values of block X that a thread has just received are
+    // multiplied, in the registers they arrived in, with the workgroup's rows of the other block (whose columns
+    // X are), reduced by res_cs_rows and left in PART before the barrier; after it the finishing lanes add the
+    // eight waves' parts, finish their rows and publish the NEXT half sweep from registers.  Whatever else the
+    // step needs (the other half's shift by c and its part of the next scalar, the reads of r and A*1) runs
+    // between that publish and the next wait.  `feed`: the next hand-off is the other block's half sweep.  A
+    // half sweep that does not follow the other block's (the first of a run) takes its totals from E1 in LDS
+    // first, with a barrier of its own.
+    // the finishing lanes (wave 0, lane r < RES_WAVES) of hand-off `sq`: row totals -> new values -> publish
+    auto cs_finish = [&](bool frows, bool first, bool zs, unsigned sq) __attribute__((always_inline)) {
+        if (dbg) dbg_acc[8] -= __builtin_amdgcn_s_memtime();
+        const double cc = c1;
+        if (w == 0 && lane < RES_WAVES) {
+            // (every workgroup owns a row of every block)
+            const int row = frows ? (loF + lane < hiF ? loF + lane : hiF - 1) : (loC + lane < hiC ? loC + lane : hiC - 1);
+            const int g0 = frows ? loF : loC - nf, cnt = frows ? hiF - loF : hiC - loC;
+            // (the row's own scalars first: their reads go out with the parts', one LDS latency for all)
+            const double dg_ = sm[oOWN + (frows ? 0 : 3) * RES_WAVES + lane];
+            const double dv_ = sm[oOWN + (frows ? 1 : 4) * RES_WAVES + lane];
+            const double r_own = sm[oR1 + row], ax_own = sm[oAX1 + row];
+            const double T = zs ? 0.0 : res_red8_tree(sm + oPART + RES_WAVES * RES_WAVES * csBuf + RES_WAVES * lane);
+            const double eo = frows ? eFo : eCo;
+            const double s = T + dg_ * eo;
+            const double g_i = r_own - s - ax_own * cc;
+            const double wv = eo + dv_ * g_i;
+            if (lane < cnt && !(sq == D.dbg_skip_seq && b == G - 1)) res_publish(rs, sq, g0 + lane, wv);
+            // this half: wv (+ c in a second half); the other half: + c in a second half
+            const double mine = first ? wv : wv + cc;
+            if (frows) {
+                eFo = mine;
+                if (!first) eCo = eCo + cc;
+            } else {
+                eCo = mine;
+                if (!first) eFo = eFo + cc;
+            }
+        }
+        if (dbg) dbg_acc[8] += __builtin_amdgcn_s_memtime();
+    };
+    auto half1_cs = [&](bool frows, bool first, bool ezero, bool feed) __attribute__((always_inline)) {
+        const int blk0 = frows ? 0 : nf, nblk = frows ? nf : nc;
+        const int oth0 = frows ? nf : 0, noth = frows ? nc : nf;
+        const int me = frows ? 0 : 1;
+        ++seq;
+        if (*fail) dead = true;           // (a give-up of the previous hand-off: its barrier has ordered the flag)
+        if (ezero && first) {             // zero start: the row's sum and its own entry are zero
+            eFo = eCo = 0.0;
+            cs_finish(frows, first, true, seq);
+        } else if (csFed != me) {         // the first of a run: the totals from E1 in LDS, the own entries too
+            const double v0 = tid < noth ? sm[oE1 + oth0 + tid] : 0.0;
+            const double v1 = tid + BT < noth ? sm[oE1 + oth0 + tid + BT] : 0.0;
+            csBuf ^= 1;
+            if (frows)
+                res_cs_rows(AF, v0, v1, sm + oPART + RES_WAVES * RES_WAVES * csBuf, w, lane);
+            else
+                res_cs_rows(AC, v0, v1, sm + oPART + RES_WAVES * RES_WAVES * csBuf, w, lane);
+            eFo = sm[oE1 + (loF + lane < hiF ? loF + lane : hiF - 1)];
+            eCo = sm[oE1 + (loC + lane < hiC ? loC + lane : hiC - 1)];
+            __syncthreads();
+            cs_finish(frows, first, false, seq);
+        }
+        // (else: published behind the barrier of the other block's half sweep, below)
+        // ---- between the publish and the wait ------------------------------------------------------------
+        const double cc = c1;
+        double pa[2] = {0.0, 0.0}, pb[2] = {0.0, 0.0}, p0 = 0.0;
+        if (!first) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int j = tid + u * BT;
+                if (j < nblk) {
+                    pa[u] = sm[oR1 + blk0 + j];
+                    pb[u] = sm[oAX1 + blk0 + j];
+                }
+            }
+            // other half: w -> w + c, and its part of the scalar of the next sweep (each entry of E1 is read and
+            // written by thread j % BT alone, here, in the receipt below and in the reads that feed res_cs_rows)
+            for (int jo = tid; jo < noth; jo += BT) {
+                const double en = sm[oE1 + oth0 + jo] + cc;
+                sm[oE1 + oth0 + jo] = en;
+                p0 += sm[oR1 + oth0 + jo] - sm[oAX1 + oth0 + jo] * en;
+            }
+        }
+        if (dbg) dbg_acc[0] -= __builtin_amdgcn_s_memtime();
+        for (int ps = 0; ps < D.presleep; ++ps) __builtin_amdgcn_s_sleep(1);
+        double hv[2] = {0.0, 0.0};
+        if (res_sweep<2>(rs, seq, nblk, dead, D.tmo, hv, D.pollsleep)) {
+            *fail = 1;
+            if (lane == 0) __hip_atomic_store(D.tmo, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (dbg) {
+            const long long t_ = __builtin_amdgcn_s_memtime();
+            dbg_acc[0] += t_;
+            dbg_acc[4] -= t_;
+        }
+        // ---- receipt: the values meet their matrix entries in the registers they arrived in ---------------
+        double en[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int j = tid + u * BT;
+            en[u] = j < nblk ? (first ? hv[u] : hv[u] + cc) : 0.0;
+        }
+        if (feed) {
+            csBuf ^= 1;
+            if (frows)
+                res_cs_rows(AC, en[0], en[1], sm + oPART + RES_WAVES * RES_WAVES * csBuf, w, lane);
+            else
+                res_cs_rows(AF, en[0], en[1], sm + oPART + RES_WAVES * RES_WAVES * csBuf, w, lane);
+            csFed = 1 - me;
+        } else {
+            csFed = -1;
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int j = tid + u * BT;
+            if (j < nblk) {
+                sm[oE1 + blk0 + j] = en[u];
+                if (!first) p0 += pa[u] - pb[u] * en[u];
+            }
+        }
+        double* part9 = sm + oPART9 + RES_WAVES * (int)(seq & 1);
+        if (!first && nsp) {
+            p0 = wave_sum(p0);
+            if (lane == 0) part9[w] = p0;
+        }
+        if (dbg) {
+            const long long t_ = __builtin_amdgcn_s_memtime();
+            dbg_acc[4] += t_;
+            dbg_acc[3] -= t_;
+        }
+        __syncthreads();
+        if (dbg) dbg_acc[3] += __builtin_amdgcn_s_memtime();
+        // the scalar of the next sweep and, where the other block's half sweep follows, its publish: the reads of
+        // the waves' parts, of the scalar's parts and of the rows' own scalars go out together
+        if (!first) c1 = nsp ? res_red8_tree(part9) * rxx1 : 0.0;
+        if (feed)
+            cs_finish(!frows, !first, false, seq + 1);
+        else
+            eFo = eCo = 0.0;   // (dead outside a run of half sweeps: its first one reloads them)
+    };
     auto half1 = [&](bool frows, bool first, bool ezero) __attribute__((always_inline)) {
+        if constexpr (!CS1) {   // (16-entry rows: half1_cs)
         double s = 0.0, eo = 0.0;
         const int row = frows ? rowF : rowC;
         const bool valid = frows ? vF : vC;
@@ -835,7 +1129,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         if (!ezero) eo = sm[oE1 + rr_];
         const double dg_ = frows ? dgF : dgC, dv_ = frows ? dvF : dvC;
         const double r_own = sm[oR1 + rr_], ax_own = sm[oAX1 + rr_];
-        if (!(ezero && first)) s = wave_sum(frows ? res_rowdot_fma<KE1, 8 * oE1>(cF, aF, smb) : res_rowdot_fma<KE1, 8 * oE1>(cC, aC, smb));
+        if (!(ezero && first)) s = wave_sum(frows ? res_rowdot_fma<KR1, 8 * oE1>(cF, aF, smb) : res_rowdot_fma<KR1, 8 * oE1>(cC, aC, smb));
         s += dg_ * eo;
         const double g_i = r_own - s - ax_own * c1;
         const double wv = eo + dv_ * g_i;
@@ -866,10 +1160,16 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                           (nsp ? 1 : 0), xig, dum1);
             c1 = nsp ? xig * rxx1 : 0.0;
         }
+        }
     };
-    auto sweep1 = [&](bool post, bool ezero) __attribute__((always_inline)) {
+    auto sweep1 = [&](bool post, bool ezero, bool last) __attribute__((always_inline)) {
+        if constexpr (CS1) {
+            if (!(lfirst && ezero && !post)) half1_cs(!post, true, ezero, true);
+            half1_cs(post, false, ezero, !last);   // (the run's next sweep starts with the other block)
+        } else {
         if (!(lfirst && ezero && !post)) half1(!post, true, ezero);   // else: done by top()    // pre: F rows first (Rk{1}); post: C rows first (Rk{1}')
         half1(post, false, ezero);
+        }
     };
 
     // weighted-Jacobi sweep on level 2                                   MG_Vcycle.m:15-21; Class_AMG.m:84
@@ -1323,14 +1623,28 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     // MG_Vcycle / MG_Wcycle from level 1 down; the correction ends in E1
     auto cycle = [&]() __attribute__((always_inline)) {
         const int nu = D.nu;
-        for (int s = 0; s < nu; ++s) sweep1(false, s == 0);
+        for (int s = 0; s < nu; ++s) sweep1(false, s == 0, s == nu - 1);
         {   // rr = r - A e on both blocks
-            const double sF = wave_sum(res_rowdot_fma<KE1, 8 * oE1>(cF, aF, smb)) + dgF * sm[oE1 + rF];
-            const double sC = wave_sum(res_rowdot_fma<KE1, 8 * oE1>(cC, aC, smb)) + dgC * sm[oE1 + rC];
+            if constexpr (CS1) {
+                cs_both_rows(oE1);
+            } else {
+            const double sF = wave_sum(res_rowdot_fma<KR1, 8 * oE1>(cF, aF, smb)) + dgF * sm[oE1 + rF];
+            const double sC = wave_sum(res_rowdot_fma<KR1, 8 * oE1>(cC, aC, smb)) + dgC * sm[oE1 + rC];
             if (lane == 0) {
                 sm[oPUB + w] = sm[oR1 + rF] - sF;
                 sm[oPUB + RES_WAVES + w] = sm[oR1 + rC] - sC;
             }
+            }
+            if constexpr (CS1) {
+                if (xm) {   // the F part arrives pre-scaled by rho for the mask-form restriction below
+                    RES_HANDOFF_PV(4, N1, loF, hiF - loF, loC, hiC - loC, cs_row_value(oE1, false),
+                                   { pa_[u_] = j < nf ? sm[oRHO + j] : 1.0; },
+                                   { sm[oRR1 + j] = j < nf ? v * pa_[u_] : v; }, {}, 0, dum0, dum1);
+                } else {
+                    RES_HANDOFF_PV(4, N1, loF, hiF - loF, loC, hiC - loC, cs_row_value(oE1, false), {},
+                                   { sm[oRR1 + j] = v; }, {}, 0, dum0, dum1);
+                }
+            } else
             if (xm) {   // the F part arrives pre-scaled by rho for the mask-form restriction below
                 RES_HANDOFF_P(4, N1, loF, hiF - loF, loC, hiC - loC, { pa_[u_] = j < nf ? sm[oRHO + j] : 1.0; },
                               { sm[oRR1 + j] = j < nf ? v * pa_[u_] : v; }, {}, 0, dum0, dum1);
@@ -1391,7 +1705,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                           { sm[oE1 + j] = v; p0 += pa_[u_] - pb_[u_] * v; }, {}, (nsp ? 1 : 0), xig, dum1);
             c1 = nsp ? xig * rxx1 : 0.0;
         }
-        for (int s = 0; s < nu; ++s) sweep1(true, false);
+        for (int s = 0; s < nu; ++s) sweep1(true, false, s == nu - 1);
     };
 
     auto add_correction = [&]() __attribute__((always_inline)) {   // x += e                                       Class_AMG.m:98,101
@@ -1468,6 +1782,9 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         // workgroup 0 itself saw every hand-off arrive
         const unsigned anytmo = __hip_atomic_load(D.tmo, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
         out[3] = (dead || anytmo != 0) ? 1.0 : 0.0;
+        // column slices: a workgroup met an entry the layout has no slot for (an F row in an F column, a C row in a C
+        // column) -- no time-out: the host drops the resident plan of this hierarchy and runs it as launches
+        if (CS1 && __hip_atomic_load(D.tmo + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) out[3] = 2.0;
         // the last slot of the rhok block is never written by the iteration (it <= maxit): hand-offs of this
         // launch, chip-wide ones and visits of the remote tail (ipd_amg_resident_kernel)
         out[4 + 2 * (maxit + 2) - 1] = (double)(seq + tseq);
@@ -1482,12 +1799,14 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         D.dbg[6] = dbg_acc[5];
         D.dbg[7] = dbg_acc[6];
         D.dbg[8] = dbg_acc[7];
+        if (CS1 && !D.remote) D.dbg[9] = dbg_acc[8];   // (a remote tail reports its busy time there)
     }
 #undef RES_HANDOFF3
 #undef RES_HANDOFF3R
 #undef RES_HANDOFF4
 #undef RES_HANDOFF
 #undef RES_HANDOFF_P
+#undef RES_HANDOFF_PV
 #undef dgF
 #undef dvF
 #undef bF

@@ -334,6 +334,10 @@ static bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double
         IPD_HIP(hipEventSynchronize(e1));
         IPD_HIP(hipEventElapsedTime(ms, e0, e1));
     }
+    if (out[3] == 2.0) {   // the column-slice layout cannot hold this level 1 (an entry of Aff or Acc off the diagonal):
+        R.ok = false;      // no time-out and no penalty for the context -- this hierarchy runs as launches from now on
+        return false;
+    }
     if (out[3] != 0.0) {   // a bounded spin gave up somewhere (any workgroup: the kernel reports the
         // time-out word, not only workgroup 0's own view): not every workgroup was resident
         ++R.timeouts;

@@ -559,7 +559,8 @@ int ipd_amg_packed_operator(const ipd_amg* h, int32_t k, int32_t form, double* o
  * [2] hand-offs, [3] 100 MHz ticks of the launch, [4] clocks in the barrier ahead of the
  * publish (the wave's wait for the workgroup's slowest row), [5] in the store phase,
  * [6] in the closing barrier, [7] in the CSR row walks of the two transfers, [8] in the tail
- * level's solve; the rest is the row dot products.  total_ms: HIP events.          */
+ * level's solve; [9] in the finishing lanes of the column-slice half sweeps (16-entry rows; with a
+ * remote tail: the tail workgroup's busy clocks); the rest is the row work.  total_ms: HIP events. */
 int ipd_amg_bench_resident(ipd_amg* h, const double* b_dev, double* x_dev, int cycles,
                            double* total_ms, int64_t stamps[10]);
 

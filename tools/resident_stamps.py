@@ -33,23 +33,34 @@ def main():
     print("level 1 <-> 2 transfers from the bit mask:", h.attach_mask_transfers(np.ones(m), np.ones(n), bench.TK))
     if a.cycle == "v" and not a.no_poly2:
         print("level 2 composed over a visit (ipd_amg_attach_level2_poly):", h.attach_level2_poly())
+    from ctypes import c_int32, create_string_buffer
+    name = create_string_buffer(64)
+    _lib.check(_lib.lib.ipd_amg_resident_kernel(h.handle, name, c_int32(64), None, None, None))
+    colslice = name.value.decode().startswith("k_resident<16,16,0")   # only these write stamps[9] (no remote tail here)
+    print("kernel:", name.value.decode())
     db = _lib.DeviceBuffer.from_array(f)
     dx = _lib.DeviceBuffer.from_array(guess)
     st = (c_int64 * 10)()
     ms = c_double()
     for rep in range(3):
         _lib.check(_lib.lib.ipd_amg_bench_resident(h.handle, db.ptr, dx.ptr, c_int(a.cycles), byref(ms), st))
-        wait, tot, nh, ticks, bar1, store, bar2, xfer, tail = [int(v) for v in st][:9]
+        wait, tot, nh, ticks, bar1, store, bar2, xfer, tail, fin = [int(v) for v in st][:10]
+        if not colslice:
+            fin = 0
+        # (stamps[9]: the finishing lanes of the column-slice half sweeps -- this system has no remote tail,
+        # whose busy time the slot carries otherwise.  A column-slice half sweep has ONE barrier, counted as the
+        # barrier before the publish, and no store phase of its own: "store+sums" is then receipt -> products ->
+        # butterfly -> PART, and the closing barrier is that of the other hand-offs alone.)
         clk_mhz = tot / (ticks / 100.0)
         print("cycles=%d  %.3f ms  -> %.2f us/cycle, %d hand-offs (%.1f per cycle, %.2f us each); "
               "workgroup 0: waiting in sweeps %.1f %% (%.2f us per hand-off), shader clock %.0f MHz"
               % (a.cycles, ms.value, 1e3 * ms.value / a.cycles, nh, nh / a.cycles,
                  1e3 * ms.value / nh, 100.0 * wait / tot, wait / clk_mhz / nh, clk_mhz))
-        rest = tot - wait - bar1 - store - bar2 - xfer - tail
+        rest = tot - wait - bar1 - store - bar2 - xfer - tail - fin
         print("   per cycle (us): transfers P'rr, P e_2 %.2f | tail level %.2f" % (
             xfer / clk_mhz / a.cycles, tail / clk_mhz / a.cycles))
-        print("   per hand-off (us): row work %.2f | barrier before publish %.2f | sweep wait %.2f | "
-              "store+sums %.2f | closing barrier %.2f" % tuple(v / clk_mhz / nh for v in (rest, bar1, wait, store, bar2)))
+        print("   per hand-off (us): row work %.2f | barrier before publish %.2f | finishing lanes %.2f | sweep wait %.2f | "
+              "store+sums %.2f | closing barrier %.2f" % tuple(v / clk_mhz / nh for v in (rest, bar1, fin, wait, store, bar2)))
 
 
 if __name__ == "__main__":
