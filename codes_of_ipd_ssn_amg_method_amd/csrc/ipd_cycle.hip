@@ -3336,6 +3336,7 @@ __global__ __launch_bounds__(BT) void k_subcycle(const SolveDesc* __restrict__ D
     for (int i = threadIdx.x; i < N0; i += BT) ge[i] = res[i];
 }
 
+#include "ipd_resident_proto.h"
 #include "ipd_resident.h"
 #include "ipd_resident_big.h"
 #include "ipd_cycle_host.h"

@@ -19,34 +19,20 @@
 //     lanes 0..7 of wave 0 add them, finish the rows and publish the next half sweep from registers
 //     (half1_cs): no gather phase, no store phase, no closing barrier and no trip of the published values
 //     through LDS remain on a half sweep's chain.  The other kernels keep a row per wave;
-//   * the only global traffic is the hand-off of each half sweep's result: a row's new value is
-//     published as ONE 16-byte write-through (sc1) store of two self-tagged 8-byte granules
-//     {lo, tag, hi, tag} (MI355X guide, Guideline 16 R2: the data is the flag) and every
-//     workgroup sweeps all granules of the step with sc1 loads until every tag carries the
-//     step number.  Two buffers by step parity: a workgroup writes step t+2 only after it has
-//     seen all of step t+1, which every workgroup publishes only after it has read all of t
-//     (every workgroup owns at least one row of every block, so "all of t+1" includes everyone).
-//     tools/ubench_exchange.hip prices the step at 1.9 us (G = 128) against 4.6-5.0 us for the
-//     launch it replaces (profiles/r2_ubench_exchange.txt);
+//   * the only global traffic is the hand-off of each half sweep's result: tagged 16-byte granules that every
+//     workgroup publishes and sweeps, two buffers by step parity (ipd_resident_proto.h describes the protocol,
+//     its bounded spins and the give-up word);
 //   * the kernel-space scalar c = 1'(r - A e)/xx of the next sweep is reduced in the same sweep
 //     phase that stores the new iterate (no extra barrier), the transfers to and from level 2 walk
 //     the CSR rows of P'/P from L2 (twice per cycle), and the tail level (<= 64 rows, 1 row in
 //     the dense regime) is solved redundantly by every workgroup, so it needs no hand-off;
-//   * the stationary iteration and its stopping rules (Class_AMG.m:86-109) run in the kernel:
-//     every workgroup forms the same norm from the same LDS copy in the same order and so takes
-//     the same decision; one launch and one read-back per solve.
-//
-// Every spin is bounded: a workgroup that gives up raises `tmo`, every later sweep of every
-// workgroup gives up at once, and the host falls back to the multi-launch path.
+//   * the stationary iteration and its stopping rules (Class_AMG.m:86-109) run in the kernel
+//     (res_stationary, ipd_resident_proto.h): one launch and one read-back per solve.
 //
 // Arithmetic per row is the multi-launch kernels' (phase_smooth / phase_resid / phase_xfer /
 // phase_top), only the order inside a row's dot product differs (lane-strided entries).
 #pragma once
 
-typedef unsigned int res_v4u __attribute__((ext_vector_type(4)));
-
-static constexpr int RES_GRAN_MAX = RES_NMAX;  // granules per hand-off buffer
-static constexpr unsigned RES_SPIN_MAX = 1u << 18;
 static constexpr int RES_P3_LD = 1152;         // row stride of ResDesc::p3rows: 512 + 512 + 128
 static constexpr int RES_P4_LD = 2 * RES_P4_SEG + 64;
 
@@ -59,11 +45,6 @@ struct ResLevelDesc {
     const double* Axi;
     const double* xx;
 };
-struct ResCsr {
-    const int* rp;
-    const int* ci;
-    const double* va;
-};
 struct ResDesc {
     ResLevelDesc L1, L2;
     ResLevelDesc L3;  // third resident level (Jacobi, <= BT rows), `three` != 0 only
@@ -73,7 +54,6 @@ struct ResDesc {
     ResCsr A3;        // tail operator (CSR), local tail only
     ResCsr A4;        // ... when level 3 is resident too and level 4 is the (local) tail
     int three;        // levels 1-3 resident (hierarchies whose level 3 does not fit the tail's LDS)
-    int tail_root;    // remote tail: 3 or 4
     // Level 3 in polynomial form (template argument KE3 == 1, remote tail only; pack_bpoly with rows):
     // row i < N3 of p3rows is [M2a | M1](i,:) and row N3 + c is the restriction row c stacked on it,
     // entries 0..N3-1 applied to r_3, 512..512+N3-1 to e_3 and (rows < N3) 1024..1024+N4-1 = (M1 P4)(i,:)
@@ -98,20 +78,16 @@ struct ResDesc {
     // and more; N5 > 0): row b < N4 of [M2a | M1] and the restriction row N4 + b (b < N5) per workgroup, fetched
     // from L2 at every pass (row stride RES_P4_LD: [Mr (128) | Me (128) | Mc (64)]); the restricted residual of
     // level 3 goes to EVERYBODY in the ack granules of level 3's hand-off, and the tail workgroup is rooted
-    // at level 5 (ResDesc::sub then holds levels 5..J, tail_root = 5).  With the tail at level 4 its two legs
+    // at level 5 (ResTail::sub then holds levels 5..J, root = 5).  With the tail at level 4 its two legs
     // per visit of level 3 were 50 us of serial work on the late Newton systems (4 per W cycle: 200 of 296 us).
     int N5;
     const double* p4rows;
     const double* p4w;
-    // Remote tail (hierarchies with more than three levels): workgroup gridDim.x - 1 holds the LDS
-    // image of the single-workgroup sub-cycle rooted at level 3 (k_subcycle's code and data) and
-    // serves the visits of everything below level 2: the other workgroups hand it r_3 = P3' rr_2
-    // (tin, Nt granules) and receive the prolongated correction P3 e_3 (tout, N2 granules).
+    // Remote tail (hierarchies with more than three levels): workgroup gridDim.x - 1 serves the visits of
+    // everything below the resident levels (ipd_resident_proto.h): rooted at level 3, the other workgroups hand
+    // it r_3 = P3' rr_2 (Nt granules) and receive the prolongated correction P3 e_3 (N2 granules).
     int remote;
-    const SolveDesc* sub;     // image of levels 3..J (pack_image), NULL without remote tail
-    unsigned char* tin;       // 2 x RES_GRAN_MAX granules by visit parity
-    unsigned char* tout;
-    unsigned* tctl;           // [0] != 0: the solve is over, the tail workgroup leaves
+    ResTail tail;     // what that workgroup reads and the wire to it
     // Level 1 <-> 2 transfers from the active-set bit mask (amg_attach_maskop, three-level hierarchies
     // with bigraph transfers only): W(j,i) = s_ij beta_i rho_j (AMG/transfer.m:19-25 on Hybrid_AMG's
     // rescaled operator), so a row of P' or P is 1 bit per entry -- 16 bits per lane, held in one
@@ -123,7 +99,6 @@ struct ResDesc {
     const double* xm_beta;   // nc: the C node's factor
     const double* xm_rho;    // nf: the F row's factor (1 / row sum with isnsp)
     int localfirst;   // zero-start first sweeps formed locally (see k_resident); 0: handed off like the rest
-    int tail_bm;      // the launch's dynamic LDS has room for the tail image's operator copy (SolveDesc::bm_src)
     int wident;       // P = [W; I] verified (k_res_check_ident): identity entries are added, not walked
     int Nt;           // rows of the tail level (local tail) or of the remote tail's root level
     int nu, isnsp, wcycle, anycycle, maxit;
@@ -138,95 +113,6 @@ struct ResDesc {
     unsigned dbg_skip_seq;   // test hook (IPD_RES_DEBUG_SKIP_PUBLISH=<step>): the last workgroup omits its
                              // publish of that step, so every sweep of the step gives up; 0 = off
 };
-
-// one fp64 value as two self-tagged 8-byte granules
-__device__ __forceinline__ res_v4u res_pack(double v, unsigned tag) {
-    res_v4u g;
-    g.x = (unsigned)__double2loint(v);
-    g.y = tag;
-    g.z = (unsigned)__double2hiint(v);
-    g.w = tag;
-    return g;
-}
-
-__device__ __forceinline__ void res_publish(__amdgpu_buffer_rsrc_t rs, unsigned seq, int gidx, double v) {
-    __builtin_amdgcn_raw_buffer_store_b128(res_pack(v, seq), rs,
-                                           (int)(seq & 1) * (RES_GRAN_MAX * 16) + gidx * 16, 0,
-                                           16 /* sc1: write-through */);
-}
-
-// Sweeps the n granules of hand-off `seq` (n <= NJ*BT); granule j goes to thread j % BT, pass
-// u = j / BT.  Returns the values in v[u] and true when the bounded spin gave up; the caller
-// stores the values after the barrier it places (all waves have then finished the step's
-// reads of the vectors that are about to change).
-template <int NJ>
-__device__ __forceinline__ bool res_sweep(__amdgpu_buffer_rsrc_t rs, unsigned seq, int n, bool dead,
-                                          unsigned* tmo, double (&v)[NJ], int pollsleep = 1) {
-    const int base = (int)(seq & 1) * (RES_GRAN_MAX * 16);
-    const int j0 = threadIdx.x;
-    unsigned spins = 0;
-    bool bad = false;
-    if (!dead) {
-        for (;;) {
-            res_v4u gq[NJ];
-#pragma unroll
-            for (int u = 0; u < NJ; ++u) {
-                const int j = j0 + u * BT;
-                gq[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, base + (j < n ? j : 0) * 16, 0, 16 /* sc1 */);
-            }
-            bool ok = true;
-#pragma unroll
-            for (int u = 0; u < NJ; ++u) {
-                const int j = j0 + u * BT;
-                ok &= (j >= n) | ((gq[u].y == seq) & (gq[u].w == seq));
-                v[u] = __hiloint2double((int)gq[u].z, (int)gq[u].x);
-            }
-            if (__all(ok)) break;
-            if (++spins > RES_SPIN_MAX ||
-                ((spins & 255) == 255 &&
-                 __hip_atomic_load(tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-                bad = true;
-                break;
-            }
-            for (int ps = 0; ps < pollsleep; ++ps) __builtin_amdgcn_s_sleep(1);
-            asm volatile("" ::: "memory");
-        }
-    }
-    return bad;
-}
-
-// The same sweep for the slow hand-offs of the remote tail (tens of microseconds): long sleeps
-// between polls, no give-up count -- it ends when every tag carries `seq` (returns 0), when the
-// time-out word is raised (1) or when the exit word is (2; tail workgroup only, ctl may be NULL).
-template <int NJ>
-__device__ __forceinline__ int res_wait_slow(__amdgpu_buffer_rsrc_t rs, unsigned seq, int n,
-                                             const unsigned* tmo, const unsigned* ctl, double (&v)[NJ]) {
-    const int base = (int)(seq & 1) * (RES_GRAN_MAX * 16);
-    const int j0 = threadIdx.x;
-    for (unsigned spins = 0;; ++spins) {
-        res_v4u gq[NJ];
-#pragma unroll
-        for (int u = 0; u < NJ; ++u) {
-            const int j = j0 + u * BT;
-            gq[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, base + (j < n ? j : 0) * 16, 0, 16 /* sc1 */);
-        }
-        bool ok = true;
-#pragma unroll
-        for (int u = 0; u < NJ; ++u) {
-            const int j = j0 + u * BT;
-            ok &= (j >= n) | ((gq[u].y == seq) & (gq[u].w == seq));
-            v[u] = __hiloint2double((int)gq[u].z, (int)gq[u].x);
-        }
-        if (__all(ok)) return 0;
-        if ((spins & 15) == 15) {
-            if (__hip_atomic_load(tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return 1;
-            if (ctl && __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return 2;
-            if (spins > (1u << 21)) return 1;   // ~1 s: a sub-cycle leg takes 0.02-0.2 ms
-        }
-        __builtin_amdgcn_s_sleep(16);
-        asm volatile("" ::: "memory");
-    }
-}
 
 // lane-strided slice of one padded row: entries lane, lane+64, ... ; the 16-bit columns are kept
 // as LDS byte offsets (8*column <= 16376), two per register
@@ -440,79 +326,8 @@ __device__ __forceinline__ void res_cs_rows(const double (&A)[RES_WAVES][2], dou
     if ((lane & 7) == 0) part_out[8 * (lane >> 3) + w] = u;
 }
 
-// The tail workgroup of a remote-tail launch: k_subcycle's body as a server.  It loads the LDS
-// image of levels 3..J once, then for every visit waits for r_3 (D.Nt <= BT granules in tin), runs
-// the V or W sub-cycle rooted at level 3 out of LDS (both legs of MG_Wcycle.m:28-30 when level 3 is
-// not the coarsest), and publishes P3 * e_3 for all rows of level 2 (tout).  It leaves when the
-// other workgroups raise the exit word (end of the solve) or the time-out word.
-__device__ __forceinline__ void res_tail_workgroup(const ResDesc& D, char* dyn_raw, PhaseLds* lds,
-                                                   double* red, double* blkpart, int* stat) {
-    const int tid = threadIdx.x, w = tid >> 6;
-    SolveDesc* LD = sol_load_image(D.sub, dyn_raw);
-    SolveCtx c;
-    c.D = LD;
-    c.lds = lds;
-    c.red = red;
-    c.xs = reinterpret_cast<double*>(dyn_raw);
-    c.swapmask = 0;
-    c.zeromask = 0;
-    c.part = blkpart;
-    c.sumr = blkpart + 48;
-    c.dbg = nullptr;
-    c.bm_lds = 0;
-    if (D.tail_bm && LD->bm_bytes) {   // one block-wide level's operator into LDS for the whole solve (SolveDesc::bm_src)
-        const uint4* src = reinterpret_cast<const uint4*>(LD->bm_src);
-        uint4* dst = reinterpret_cast<uint4*>(dyn_raw + LD->bm_off);
-        for (int i = tid; i < LD->bm_bytes / 16; i += BT) dst[i] = src[i];
-        __syncthreads();
-        c.bm_lds = (unsigned)(size_t)(dyn_raw + LD->bm_off);
-    }
-    const int k0 = D.tail_root, N3 = k0 == 5 ? D.N5 : D.Nt, N2 = k0 == 3 ? D.L2.N : D.L3.N;   // inbox / outbox rows
-    const ResCsr& Pout = k0 == 3 ? D.P3 : D.P4;
-    const bool two_legs = D.wcycle && k0 < LD->J;
-    const auto rin = __builtin_amdgcn_make_buffer_rsrc(D.tin, 0, 2 * RES_GRAN_MAX * 16, 0x00020000);
-    const auto rout = __builtin_amdgcn_make_buffer_rsrc(D.tout, 0, 2 * RES_GRAN_MAX * 16, 0x00020000);
-    long long busy = 0;
-    for (unsigned tseq = 1;; ++tseq) {
-        double v[1];
-        const int st = res_wait_slow<1>(rin, tseq, N3, D.tmo, D.tctl, v);
-        if ((tid & 63) == 0) stat[w] = st;
-        __syncthreads();
-        int any = 0;
-#pragma unroll
-        for (int k = 0; k < RES_WAVES; ++k) any |= stat[k];
-        if (any) {                             // uniform: every wave reads the same eight words
-            if (D.dbg && tid == 0) D.dbg[9] = busy;   // (diagnostic build of the bench: clocks between a request's arrival and its answer's stores)
-            return;
-        }
-        const long long tb0 = (D.dbg && tid == 0) ? (long long)__builtin_amdgcn_s_memtime() : 0;
-        if (tid < N3) LD->L[k0].lv.r[tid] = v[0];
-        __syncthreads();
-        sol_cycle(c, k0, false);
-        __syncthreads();
-        if (two_legs) {
-            sol_cycle(c, k0, true);
-            __syncthreads();
-        }
-        const double* e3 = sol_e(c, k0);
-        const int base = (int)(tseq & 1) * (RES_GRAN_MAX * 16);
-        if (D.p3rows) {   // polynomial level 3: its workgroups apply M1 P4 themselves, the answer is e_4
-            if (tid < N3)
-                __builtin_amdgcn_raw_buffer_store_b128(res_pack(e3[tid], tseq), rout, base + tid * 16, 0, 16 /* sc1 */);
-        } else
-        for (int j = tid; j < N2; j += BT) {   // e_2 += P e_3 is finished by the receivers     MG_Vcycle.m:31
-            double sd = 0.0;
-            for (int t = Pout.rp[j]; t < Pout.rp[j + 1]; ++t) sd += Pout.va[t] * e3[Pout.ci[t]];
-            __builtin_amdgcn_raw_buffer_store_b128(res_pack(sd, tseq), rout, base + j * 16, 0, 16 /* sc1 */);
-        }
-        if (D.dbg && tid == 0) busy += (long long)__builtin_amdgcn_s_memtime() - tb0;
-        __syncthreads();                       // stat and e3 are rewritten by the next visit
-    }
-}
-
 // out[0] = it, out[1] = rel_res, out[2] = res0; rel_resk at out[4 ..], rhok at out[4+maxit+2 ..]
-// (the layout of k_solve_small; the last slot: hand-offs of the launch).  fixed_cycles > 0: exactly that many loop bodies, no stopping
-// rules (bench hook).  dbg (optional, 16 words): [0] shader clocks spent waiting in sweeps by
+// (res_stationary; the last slot: hand-offs of the launch).  fixed_cycles > 0: the bench hook.  dbg (optional, 16 words): [0] shader clocks spent waiting in sweeps by
 // workgroup 0, [1] clocks of the whole loop, [2] number of hand-offs, [3] 100 MHz ticks of the loop,
 // [4] clocks in the barrier before the publish, [5] in the store phase, [6] in the closing barrier, [9] in the
 // finishing lanes of the column-slice half sweeps (whose one barrier counts as [4], their receipt as [5]).
@@ -534,7 +349,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         __shared__ double tail_red[16];
         __shared__ double tail_part[48 + SOLVE_ML + 1];
         __shared__ int tail_stat[RES_WAVES];
-        res_tail_workgroup(D, res_smem, &tail_lds, tail_red, tail_part, tail_stat);
+        res_tail_workgroup(D.tail, res_smem, &tail_lds, tail_red, tail_part, tail_stat);
         return;
     }
     // LDS map (doubles): fixed slots of RES_NMAX entries, the gather targets in the first 64 KB so
@@ -694,7 +509,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         rowp[12 * w + 5] = vC ? D.P2.rp[rC + 1] : D.P2.rp[rC];
         // remote tail: row b + G*w of the restriction to its root level, if there is one
         const int rin = b + G * w;
-        const ResCsr& Pin = D.tail_root == 4 ? D.Pt4 : D.Pt3;
+        const ResCsr& Pin = D.tail.root == 4 ? D.Pt4 : D.Pt3;
         rowp[12 * w + 6] = (D.remote && rin < Nt) ? Pin.rp[rin] : 0;
         rowp[12 * w + 7] = (D.remote && rin < Nt) ? Pin.rp[rin + 1] : 0;
         // third resident level: its own row of P3' (restriction 2 -> 3), this wave's level-2 row of P3
@@ -909,7 +724,6 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     double c1 = 0.0, c2s = 0.0;     // kernel-space scalars of the next sweep on level 1 / 2
     double sumr2p = 0.0;            // POLY2: 1'r_2 of the visit
     const double p2ws = POLY2 ? D.p2w[N2] : 0.0;
-    double res = 0.0, res0 = 0.0, prev = 0.0;
     double dum0 = 0.0, dum1 = 0.0;
     (void)dum0;
     (void)dum1;
@@ -1197,8 +1011,8 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
 
     // tail level: restriction, Jacobi-PCG (PCG.m:68-87, zero guess), prolongation -- all of it by
     // every workgroup on its own LDS copies, so no hand-off                     MG_Vcycle.m:27-31,43
-    const auto rtin = __builtin_amdgcn_make_buffer_rsrc(D.tin, 0, 2 * RES_GRAN_MAX * 16, 0x00020000);
-    const auto rtout = __builtin_amdgcn_make_buffer_rsrc(D.tout, 0, 2 * RES_GRAN_MAX * 16, 0x00020000);
+    const auto rtin = __builtin_amdgcn_make_buffer_rsrc(D.tail.tin, 0, 2 * RES_GRAN_MAX * 16, 0x00020000);
+    const auto rtout = __builtin_amdgcn_make_buffer_rsrc(D.tail.tout, 0, 2 * RES_GRAN_MAX * 16, 0x00020000);
     unsigned tseq = 0;      // number of the last visit of the remote tail
     // Remote tail: the residual of the level above the tail's root (LDS offset oRRs) is restricted row
     // by row -- row i of the restriction by wave i / G of workgroup i % G (Nt <= BT <= 8 G rows) --
@@ -1211,18 +1025,10 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         const int rin = b + G * w;
         if (rin < Nt) {
             const double s3 = res_csr_rowdot(Pin, rowp[12 * w + 6], rowp[12 * w + 7], lane, sm, oRRs);
-            if (lane == 0)
-                __builtin_amdgcn_raw_buffer_store_b128(res_pack(s3, tseq), rtin,
-                                                       (int)(tseq & 1) * (RES_GRAN_MAX * 16) + rin * 16, 0,
-                                                       16 /* sc1 */);
+            if (lane == 0) res_tail_post(rtin, tseq, rin, s3);
         }
         double hv[4];
-        int st = 0;
-        if (!dead) st = res_wait_slow<4>(rtout, tseq, Nout, D.tmo, nullptr, hv);
-        if (st) {
-            *fail = 1;
-            if (lane == 0) __hip_atomic_store(D.tmo, 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        const int st = res_tail_wait<4>(rtout, tseq, Nout, D.tmo, fail, dead, lane, hv);
         double p0 = 0.0;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -1328,21 +1134,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             s = wave_sum(s);
             if (lane == 0) red[w] = s;
             __syncthreads();
-            // PCG.m:68-87 on the 1 x 1 system, by every thread (the arithmetic of pcg_single)
-            double r = res_red8(red);
-            double pp = r / h33, d = 0.0;
-            double delta_new = r * pp;
-            const double thresh = 1e-11 * 1e-11 * delta_new;
-            for (long long it = 0; it < D.pcg_maxit && delta_new > thresh; ++it) {
-                const double delta_old = delta_new;
-                const double q = h33 * pp;
-                const double alpha = delta_old / (q * pp);
-                d += alpha * pp;
-                r = r - alpha * q;
-                const double wi = r / h33;
-                delta_new = r * wi;
-                pp = wi + (delta_new / delta_old) * pp;
-            }
+            const double d = res_pcg_1x1(res_red8(red), h33, D.pcg_maxit);
             __syncthreads();   // red is rewritten below
             double p0 = 0.0;
             for (int j = tid; j < N2; j += BT) {                                       // e_2 += P e_3
@@ -1486,44 +1278,20 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 for (int leg = 0; leg < (D.wcycle ? 2 : 1); ++leg) {
                     ++tseq;
                     poly4_rows(2, false);                              // e_4' (row b) and r_5[b] = P5'(r_4 - A_4 e_4')
-                    if (tid == 0 && b < N5)
-                        __builtin_amdgcn_raw_buffer_store_b128(res_pack(sm[oPS4 + 17], tseq), rtin,
-                                                               (int)(tseq & 1) * (RES_GRAN_MAX * 16) + b * 16, 0,
-                                                               16 /* sc1 */);
+                    if (tid == 0 && b < N5) res_tail_post(rtin, tseq, b, sm[oPS4 + 17]);
                     if (tid == 0) sm[oPUB] = sm[oPS4 + 16];
                     RES_HANDOFF4({ sm[oRR3L + j] = v; });
-                    double hv5[1];
-                    int st5 = 0;
-                    if (!dead) st5 = res_wait_slow<1>(rtout, tseq, N5, D.tmo, nullptr, hv5);   // e_5
-                    if (st5) {
-                        *fail = 1;
-                        if (lane == 0) __hip_atomic_store(D.tmo, 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    if (tid < N5) sm[oE5L + tid] = (!dead && !st5) ? hv5[0] : 0.0;
-                    __syncthreads();
-                    if (*fail) dead = true;
+                    res_tail_answer<1>(rtout, tseq, N5, D.tmo, fail, dead, sm, oE5L, tid, lane);   // e_5
                     poly4_rows(1, true);                               // e_4'' = M2a r + M1 e' + (M1 P5) e_5
                     if (tid == 0) sm[oPUB] = sm[oPS4 + 16];
                     RES_HANDOFF4({ sm[oRR3L + j] = v; });
                 }
             } else {
                 ++tseq;
-                if (tid == 0 && b < Nt)
-                    __builtin_amdgcn_raw_buffer_store_b128(res_pack(sm[oR3 + 44], tseq), rtin,
-                                                           (int)(tseq & 1) * (RES_GRAN_MAX * 16) + b * 16, 0,
-                                                           16 /* sc1 */);
+                if (tid == 0 && b < Nt) res_tail_post(rtin, tseq, b, sm[oR3 + 44]);
                 if (tid < 4) sm[oPUB + tid] = sm[oR3 + 40 + tid];
                 RES_HANDOFF3({ sm[oE3L + j] = v; }, 0, dum0);
-                double hv[1];
-                int st = 0;
-                if (!dead) st = res_wait_slow<1>(rtout, tseq, Nt, D.tmo, nullptr, hv);   // e_4 (Nt <= G <= BT values)
-                if (st) {
-                    *fail = 1;
-                    if (lane == 0) __hip_atomic_store(D.tmo, 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                if (tid < Nt) sm[oRR3L + tid] = (!dead && !st) ? hv[0] : 0.0;
-                __syncthreads();
-                if (*fail) dead = true;
+                res_tail_answer<1>(rtout, tseq, Nt, D.tmo, fail, dead, sm, oRR3L, tid, lane);   // e_4 (Nt <= G <= BT values)
             }
             poly3_rows(4, true);                                         // e'' = M2a r + M1 e' + (M1 P4) e_4   :31-41
             if (tid < 4) sm[oPUB + tid] = sm[oR3 + 40 + tid];
@@ -1555,20 +1323,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             s3 = wave_sum(s3);
             if (lane == 0) red[w] = s3;
             __syncthreads();
-            double r = res_red8(red) + p2ws * sumr2p;
-            double pp = r / h33, d = 0.0;
-            double delta_new = r * pp;
-            const double thresh = 1e-11 * 1e-11 * delta_new;
-            for (long long it = 0; it < D.pcg_maxit && delta_new > thresh; ++it) {
-                const double delta_old = delta_new;
-                const double q = h33 * pp;
-                const double alpha = delta_old / (q * pp);
-                d += alpha * pp;
-                r = r - alpha * q;
-                const double wi = r / h33;
-                delta_new = r * wi;
-                pp = wi + (delta_new / delta_old) * pp;
-            }
+            const double d = res_pcg_1x1(res_red8(red) + p2ws * sumr2p, h33, D.pcg_maxit);
             // e_2 = B r_2 + wB (1'r_2) + mp e_3 on the own row: a dense row against R2 (entry lane + 64 q at a
             // constant distance: immediate offsets, no column registers)
             const double* rb = sm + oR2 + lane;
@@ -1715,68 +1470,16 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
 
     // ---- Class_AMG.m:86-109 (one call site of every step: the kernel is large) -----------------
     const int maxit = D.maxit;
-    double* relk = out + 4;
-    double* rhok = out + 4 + (maxit + 2);
     const bool writer = b == 0 && tid == 0;
-    const bool fixed = fixed_cycles > 0;
-    int it = 0, done = 0;
-    double rel_res = 0.0, last_rel = 1.0;
-    bool first = true;
-    for (;;) {
-        const double rnow = top();                                                // :89 / :103
-        if (first) {
-            first = false;
-            res0 = res = rnow;
-            if (!fixed) {
-                if (res0 == 0.0) {                                                // :91-92
-                    if (writer) {
-                        relk[0] = 0.0;
-                        rhok[0] = INFINITY;
-                    }
-                    break;
-                }
-                it = 1;                                                           // :94
-                if (writer) {
-                    relk[0] = 1.0;
-                    rhok[0] = NAN;
-                }
-            }
-        } else {
-            prev = res;
-            res = rnow;
-            rel_res = res / res0;                                                 // :104
-            const double rho = res / prev;                                        // :105
-            if (fixed) {
-                ++done;
-            } else {
-                if (writer) {
-                    relk[it] = rel_res;
-                    rhok[it] = rho;
-                }
-                last_rel = rel_res;
-                ++it;
-                if (rho > 1.0) break;                                             // :106
-            }
-        }
-        if (dead) break;
-        if (fixed ? done >= fixed_cycles : !(last_rel > D.retol && it <= maxit)) break;   // :95
-        if (D.anycycle) {
-            cycle();                                                              // :97-102
-            add_correction();
-        }
-    }
-    if (fixed)
-        it = fixed_cycles;
-    else if (res0 != 0.0)
-        it -= 1;                                                                  // :108
+    const ResSolve sol = res_stationary(top, cycle, add_correction, D.retol, maxit, D.anycycle, fixed_cycles, dead, writer, out);
     if (D.remote && b == 0 && tid == 0)   // release the tail workgroup
-        __hip_atomic_store(D.tctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(D.tail.tctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (b == 0)
         for (int j = tid; j < N1; j += BT) xg[j] = sm[oX + j];
     if (writer) {
-        out[0] = (double)it;
-        out[1] = rel_res;
-        out[2] = res0;
+        out[0] = (double)sol.it;
+        out[1] = sol.rel_res;
+        out[2] = sol.res0;
         // any workgroup's give-up, not only this one's: a workgroup that gave up keeps publishing
         // (tagged, but computed from values it never received), so the iterate is void even when
         // workgroup 0 itself saw every hand-off arrive

@@ -14,8 +14,9 @@
 //   * sums over all rows (1'r, 1'(r - A e) = 1'r - (A1)'e, the norms, the tail's restriction) are taken
 //     from the hand-off itself: every thread holds (A1)_j of the granules it receives, or -- where only
 //     a sum is needed -- the workgroups exchange their partial sums (G or 2G granules instead of N).
-// Protocol (tagged 16-byte granules, two buffers by step parity, bounded spins, give-up word), the
-// one-row tail's PCG and the stationary iteration with its stopping rules are k_resident's.
+// Protocol (tagged 16-byte granules, two buffers by step parity, bounded spins, give-up word), the tail
+// workgroup and its wire, the one-row tail's PCG and the stationary iteration with its stopping rules are
+// k_resident's: ipd_resident_proto.h.
 //
 // Round 4 -- REALISTIC hierarchies at M = 4096 (template argument DEEP; the Newton systems of the m = n =
 // 2048 driver run: levels about 4096 / 2048 / 640 / 190 / 55 / 15, 12 k / 8 k / 3 k entries).  Level 1 and
@@ -74,53 +75,8 @@ struct ResBigDesc {
     int N5;
     const double* p4rows;     // [N4 + N5][RB_P4_LD]
     const double* p4w;        // N4 + N5
-    // ... and what its tail workgroup needs (res_tail_workgroup's fields of ResDesc)
-    const SolveDesc* sub;     // LDS image of levels 4..J
-    unsigned char* tin;       // 2 x RES_GRAN_MAX granules by visit parity: r_4 for the tail
-    unsigned char* tout;      // ... its answer e_4
-    unsigned* tctl;           // [0] != 0: the solve is over, the tail workgroup leaves
+    ResTail tail;             // ... its tail workgroup and the wire to it
 };
-
-__device__ __forceinline__ void rb_publish(__amdgpu_buffer_rsrc_t rs, unsigned seq, int gidx, double v, int ranks = 1) {
-    for (int r = 0; r < ranks; ++r)   // one copy of the buffer per rank group (ResBigDesc::ranks)
-        __builtin_amdgcn_raw_buffer_store_b128(res_pack(v, seq), rs,
-                                               r * (2 * RB_GRAN * 16) + (int)(seq & 1) * (RB_GRAN * 16) + gidx * 16, 0,
-                                               16 /* sc1: write-through */);
-}
-template <int NJ>
-__device__ __forceinline__ bool rb_sweep(__amdgpu_buffer_rsrc_t rs, unsigned seq, int n, bool dead, unsigned* tmo,
-                                         double (&v)[NJ], int pollsleep, int group = 0) {
-    const int base = group * (2 * RB_GRAN * 16) + (int)(seq & 1) * (RB_GRAN * 16);
-    const int j0 = threadIdx.x;
-    unsigned spins = 0;
-    bool bad = false;
-    if (!dead) {
-        for (;;) {
-            res_v4u gq[NJ];
-#pragma unroll
-            for (int u = 0; u < NJ; ++u) {
-                const int j = j0 + u * BT;
-                gq[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, base + (j < n ? j : 0) * 16, 0, 16 /* sc1 */);
-            }
-            bool ok = true;
-#pragma unroll
-            for (int u = 0; u < NJ; ++u) {
-                const int j = j0 + u * BT;
-                ok &= (j >= n) | ((gq[u].y == seq) & (gq[u].w == seq));
-                v[u] = __hiloint2double((int)gq[u].z, (int)gq[u].x);
-            }
-            if (__all(ok)) break;
-            if (++spins > RES_SPIN_MAX ||
-                ((spins & 255) == 255 && __hip_atomic_load(tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-                bad = true;
-                break;
-            }
-            for (int ps = 0; ps < pollsleep; ++ps) __builtin_amdgcn_s_sleep(1);
-            asm volatile("" ::: "memory");
-        }
-    }
-    return bad;
-}
 
 // out[]: the layout of k_resident / k_solve_small.
 template <int KE2, int RPW, bool DEEP>
@@ -138,22 +94,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident_big(const ResBigDesc D, cons
         __shared__ double tail_red[16];
         __shared__ double tail_part[48 + SOLVE_ML + 1];
         __shared__ int tail_stat[RES_WAVES];
-        ResDesc T{};
-        T.sub = D.sub;
-        T.tail_root = D.N5 > 0 ? 5 : 4;
-        T.Nt = D.N5 > 0 ? D.N5 : D.N4;
-        T.N5 = D.N5;             // (res_tail_workgroup: the inbox of a tail rooted at level 5 has N5 rows)
-        T.remote = 1;
-        T.three = 1;
-        T.wcycle = D.wcycle;
-        T.p3rows = D.p3rows;   // (non-NULL: the tail answers with e_4, the resident workgroups apply M1 P4)
-        T.tin = D.tin;
-        T.tout = D.tout;
-        T.tctl = D.tctl;
-        T.tmo = D.tmo;
-        T.L2.N = D.N2;
-        T.L3.N = D.N3;
-        res_tail_workgroup(T, rb_smem, &tail_lds, tail_red, tail_part, tail_stat);
+        res_tail_workgroup(D.tail, rb_smem, &tail_lds, tail_red, tail_part, tail_stat);
         return;
     }
     const int nf = D.nf, nc = D.nc, N1 = nf + nc, N2 = D.N2;
@@ -416,10 +357,11 @@ __global__ __launch_bounds__(BT, 2) void k_resident_big(const ResBigDesc D, cons
             const bool second_ = lane >= PUBW;                                                     \
             if (lane < 2 * PUBW && l8_ < (second_ ? (cB) : (cA)) &&                                \
                 !(seq == D.dbg_skip_seq && b == G - 1))                                            \
-                rb_publish(rs, seq, (second_ ? (gB) : (gA)) + l8_, sm[oPUB + lane], ranks);        \
+                res_publish(rs, seq, (second_ ? (gB) : (gA)) + l8_, sm[oPUB + lane], RB_GRAN * 16, ranks); \
         }                                                                                          \
         for (int ps_ = 0; ps_ < D.presleep; ++ps_) __builtin_amdgcn_s_sleep(1);                    \
-        if (rb_sweep<NJ>(rs, seq, (n), dead, D.tmo, hv_, D.pollsleep, mygroup)) {                   \
+        if (res_sweep<NJ>(rs, seq, (n), dead, D.tmo, hv_, D.pollsleep, RB_GRAN * 16,               \
+                          mygroup * (2 * RB_GRAN * 16))) {                                         \
             *fail = 1;                                                                             \
             if (lane == 0) __hip_atomic_store(D.tmo, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
         }                                                                                          \
@@ -590,8 +532,8 @@ __global__ __launch_bounds__(BT, 2) void k_resident_big(const ResBigDesc D, cons
     };
 
     // ---- DEEP: the polynomial level 3 and the remote tail below it -------------------------------------
-    const auto rtin = __builtin_amdgcn_make_buffer_rsrc(D.tin, 0, 2 * RES_GRAN_MAX * 16, 0x00020000);
-    const auto rtout = __builtin_amdgcn_make_buffer_rsrc(D.tout, 0, 2 * RES_GRAN_MAX * 16, 0x00020000);
+    const auto rtin = __builtin_amdgcn_make_buffer_rsrc(D.tail.tin, 0, 2 * RES_GRAN_MAX * 16, 0x00020000);
+    const auto rtout = __builtin_amdgcn_make_buffer_rsrc(D.tail.tout, 0, 2 * RES_GRAN_MAX * 16, 0x00020000);
     unsigned tseq = 0;
     double sumr3 = 0.0;
     // hand-off among the level-3 rows: N3 values + one "ack" granule per workgroup (a workgroup without a
@@ -714,25 +656,14 @@ __global__ __launch_bounds__(BT, 2) void k_resident_big(const ResBigDesc D, cons
     // waits for the tail's answer (n values) and leaves it at sm[off ..]
     auto tail_answer = [&](int n, int off) __attribute__((always_inline)) {
         RB_FRESH;
-        double hv[1];
-        int st = 0;
-        if (!dead) st = res_wait_slow<1>(rtout, tseq, n, D.tmo, nullptr, hv);
-        if (st) {
-            *fail = 1;
-            if (lane == 0) __hip_atomic_store(D.tmo, 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (tid < n) sm[off + tid] = (!dead && !st) ? hv[0] : 0.0;
-        __syncthreads();
-        if (*fail) dead = true;
+        res_tail_answer<1>(rtout, tseq, n, D.tmo, fail, dead, sm, off, tid, lane);
     };
     // one visit of level 4 (POLY4) and, through the tail workgroup, of everything below it
     auto visit4 = [&]() __attribute__((always_inline)) {
         RB_FRESH;
         ++tseq;
         poly4_rows(3, false);                                        // e_4' and r_5 = P5'(r_4 - A_4 e_4')
-        if (tid == 0 && b < N5)
-            __builtin_amdgcn_raw_buffer_store_b128(res_pack(sm[oPS + 106], tseq), rtin,
-                                                   (int)(tseq & 1) * (RES_GRAN_MAX * 16) + b * 16, 0, 16 /* sc1 */);
+        if (tid == 0 && b < N5) res_tail_post(rtin, tseq, b, sm[oPS + 106]);
         if (tid < 2) sm[oPUB + tid] = sm[oPS + 104 + tid];
         RB_HANDOFF4({ sm[oE4 + j] = v; });
         tail_answer(N5, oE5);                                        // e_5
@@ -754,9 +685,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident_big(const ResBigDesc D, cons
             for (int leg = 0; leg < (D.wcycle ? 2 : 1); ++leg) visit4();              // MG_Wcycle.m:28-30
         } else {
             ++tseq;
-            if (tid == 0 && b < N4)
-                __builtin_amdgcn_raw_buffer_store_b128(res_pack(sm[oPS + 44], tseq), rtin,
-                                                       (int)(tseq & 1) * (RES_GRAN_MAX * 16) + b * 16, 0, 16 /* sc1 */);
+            if (tid == 0 && b < N4) res_tail_post(rtin, tseq, b, sm[oPS + 44]);
             if (tid < 4) sm[oPUB + tid] = sm[oPS + 40 + tid];
             RB_HANDOFF3({ sm[oE3L + j] = v; }, 0, dum0);
             tail_answer(N4, oE4);                                    // e_4
@@ -786,21 +715,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident_big(const ResBigDesc D, cons
             own_pair_sum(mine, 0.0, part, dumA);
             double r3 = 0.0;
             RB_PARTIALS(1, part, 0.0, r3, dum1);
-            // PCG.m:68-87 on the 1 x 1 system, by every thread
-            double r = r3;
-            double pp = r / h33, d = 0.0;
-            double delta_new = r * pp;
-            const double thresh = 1e-11 * 1e-11 * delta_new;
-            for (long long it = 0; it < D.pcg_maxit && delta_new > thresh; ++it) {
-                const double delta_old = delta_new;
-                const double q = h33 * pp;
-                const double alpha = delta_old / (q * pp);
-                d += alpha * pp;
-                r = r - alpha * q;
-                const double wi = r / h33;
-                delta_new = r * wi;
-                pp = wi + (delta_new / delta_old) * pp;
-            }
+            const double d = res_pcg_1x1(r3, h33, D.pcg_maxit);
             // e_2 += P3 e_3 on everybody's copy and on the own scalars; 1'(r - A e) moves by -d kappa
             for (int j = tid; j < N2; j += BT) sm[oE2 + j] = sm[oE2 + j] + sm[oP3C + j] * d;
 #pragma unroll
@@ -928,64 +843,12 @@ __global__ __launch_bounds__(BT, 2) void k_resident_big(const ResBigDesc D, cons
         __syncthreads();
     };
 
-    // ---- Class_AMG.m:86-109 ---------------------------------------------------------------------
+    // ---- Class_AMG.m:86-109 (one call site of every step) ------------------------------------------
     const int maxit = D.maxit;
-    double* relk = out + 4;
-    double* rhok = out + 4 + (maxit + 2);
     const bool writer = b == 0 && tid == 0;
-    const bool fixed = fixed_cycles > 0;
-    int it = 0, done = 0;
-    double rel_res = 0.0, last_rel = 1.0, res = 0.0, res0 = 0.0, prev = 0.0;
-    bool firstp = true;
-    for (;;) {
-        const double rnow = top();                                                // :89 / :103
-        if (firstp) {
-            firstp = false;
-            res0 = res = rnow;
-            if (!fixed) {
-                if (res0 == 0.0) {                                                // :91-92
-                    if (writer) {
-                        relk[0] = 0.0;
-                        rhok[0] = INFINITY;
-                    }
-                    break;
-                }
-                it = 1;                                                           // :94
-                if (writer) {
-                    relk[0] = 1.0;
-                    rhok[0] = NAN;
-                }
-            }
-        } else {
-            prev = res;
-            res = rnow;
-            rel_res = res / res0;                                                 // :104
-            const double rho = res / prev;                                        // :105
-            if (fixed) {
-                ++done;
-            } else {
-                if (writer) {
-                    relk[it] = rel_res;
-                    rhok[it] = rho;
-                }
-                last_rel = rel_res;
-                ++it;
-                if (rho > 1.0) break;                                             // :106
-            }
-        }
-        if (dead) break;
-        if (fixed ? done >= fixed_cycles : !(last_rel > D.retol && it <= maxit)) break;   // :95
-        if (D.anycycle) {
-            cycle();                                                              // :97-102
-            add_correction();
-        }
-    }
-    if (fixed)
-        it = fixed_cycles;
-    else if (res0 != 0.0)
-        it -= 1;                                                                  // :108
+    const ResSolve sol = res_stationary(top, cycle, add_correction, D.retol, maxit, D.anycycle, fixed_cycles, dead, writer, out);
     if (DEEP && b == 0 && tid == 0)   // release the tail workgroup
-        __hip_atomic_store(D.tctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(D.tail.tctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (lane == 0) {   // every workgroup writes its own rows of x
 #pragma unroll
         for (int p = 0; p < RPW; ++p) {
@@ -995,9 +858,9 @@ __global__ __launch_bounds__(BT, 2) void k_resident_big(const ResBigDesc D, cons
     }
     if (writer) {
         const unsigned anytmo = __hip_atomic_load(D.tmo, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        out[0] = (double)it;
-        out[1] = rel_res;
-        out[2] = res0;
+        out[0] = (double)sol.it;
+        out[1] = sol.rel_res;
+        out[2] = sol.res0;
         out[3] = (dead || anytmo != 0) ? 1.0 : 0.0;
         out[4 + 2 * (maxit + 2) - 1] = (double)(seq + tseq);   // hand-offs of this launch (see k_resident)
     }

@@ -121,16 +121,17 @@ static void set_cycle_options(Desc& D, const ipd_amg* h, int presleep) {
 }
 
 // The granule block, zeroed before every launch: [hand-off granules | time-out word] and, with a tail
-// workgroup, [tin | tout: 2 x RES_GRAN_MAX granules each, by visit parity | tctl].  Returns the granules.
-template <class Desc>
-static unsigned char* alloc_resident_block(ipd_amg* h, ResidentState& R, Desc& D, size_t gran_bytes, bool tail) {
+// workgroup, [tin | tout: 2 x RES_GRAN_MAX granules each, by visit parity | tctl].  Fills the wire of T and the
+// descriptor's time-out word and returns the granules.
+static unsigned char* alloc_resident_block(ipd_amg* h, ResidentState& R, ResTail& T, unsigned*& tmo, size_t gran_bytes,
+                                           bool tail) {
     const size_t tbytes = (size_t)RES_GRAN_MAX * 16;
     R.block_bytes = gran_bytes + 16 + (tail ? 4 * tbytes + 16 : 0);
     R.block = reinterpret_cast<unsigned char*>(h->arena->alloc_bytes(R.block_bytes));
-    D.tmo = reinterpret_cast<unsigned*>(R.block + gran_bytes);
-    D.tin = tail ? R.block + gran_bytes + 16 : R.block;                // never touched without
-    D.tout = tail ? R.block + gran_bytes + 16 + 2 * tbytes : R.block;  // a tail workgroup
-    D.tctl = tail ? reinterpret_cast<unsigned*>(R.block + gran_bytes + 16 + 4 * tbytes) : D.tmo;
+    tmo = T.tmo = reinterpret_cast<unsigned*>(R.block + gran_bytes);
+    T.tin = tail ? R.block + gran_bytes + 16 : R.block;                // never touched without
+    T.tout = tail ? R.block + gran_bytes + 16 + 2 * tbytes : R.block;  // a tail workgroup
+    T.tctl = tail ? reinterpret_cast<unsigned*>(R.block + gran_bytes + 16 + 4 * tbytes) : T.tmo;
     return R.block;
 }
 
@@ -177,7 +178,6 @@ static void prepare_resident(ipd_amg* h, CycleState* st, const std::vector<Level
     D.A3 = res_csr(l3.A);
     D.Nt = p.Nin;
     D.three = p.three ? 1 : 0;
-    D.tail_root = p.tail_root;
     D.A4 = res_csr(p.three ? h->L[4].A : l3.A);
     if (p.three) {
         if (p.poly3) {
@@ -214,12 +214,20 @@ static void prepare_resident(ipd_amg* h, CycleState* st, const std::vector<Level
     }
     D.localfirst = 1;
     const size_t gbytes = (size_t)RES_GRAN_MAX * 16;
-    D.gran0 = alloc_resident_block(h, R, D, 2 * gbytes, p.remote);
+    D.gran0 = alloc_resident_block(h, R, D.tail, D.tmo, 2 * gbytes, p.remote);
     D.gran1 = D.gran0 + gbytes;
     D.remote = p.remote ? 1 : 0;
-    D.sub = resident_image(st, p.tail_image);
-    D.tail_bm = p.tail_bm ? 1 : 0;
-    D.dbg = nullptr;
+    // the tail workgroup: rooted at level 3 it answers with P3 e_3 for level 2's rows, at level 4 with P4 e_4 for
+    // level 3's -- or, below a polynomial level, with its root's iterate alone
+    ResTail& T = D.tail;
+    T.sub = resident_image(st, p.tail_image);
+    T.root = p.tail_root;
+    T.nin = p.tail_root == 5 ? D.N5 : D.Nt;
+    T.nout = p.tail_root == 3 ? D.L2.N : D.L3.N;
+    T.answer_root = D.p3rows != nullptr;
+    T.Pout = p.tail_root == 3 ? D.P3 : D.P4;
+    T.wcycle = D.wcycle;
+    T.tail_bm = p.tail_bm ? 1 : 0;
     R.desc = D;
     R.line_ke = p.key.ke;
     R.line_ke3 = p.key.ke3;
@@ -289,7 +297,7 @@ static bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double
     ResidentLease lease(ctx->device, grid, st->num_cu, p.remote ? 0 : 50);
     if (!lease.ok) return false;
     ResDesc D = R.desc;
-    D.dbg = dbg_dev;
+    D.dbg = D.tail.dbg = dbg_dev;
     D.dbg_skip_seq = R.skip_publish;
     ResBigDesc B = R.big;
     B.dbg_skip_seq = R.skip_publish;
@@ -486,9 +494,7 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
             if (rho) {
                 ResBigDesc B = big_desc(h, st, mo, d2, rho);
                 B.ranks = p.ranks;
-                B.gran = alloc_resident_block(h, R, B, (size_t)p.ranks * 2 * RB_GRAN * 16, false);
-                B.tin = B.tout = nullptr;   // (no tail workgroup)
-                B.tctl = nullptr;
+                B.gran = alloc_resident_block(h, R, B.tail, B.tmo, (size_t)p.ranks * 2 * RB_GRAN * 16, false);
                 commit_mask_form(h, R, p, B, sw);
             }
         }
@@ -511,8 +517,14 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
                 B.N5 = p.poly4 ? h->L[5].A.nr : 0;
                 B.p4rows = pb4.M;
                 B.p4w = pb4.W;
-                B.gran = alloc_resident_block(h, R, B, (size_t)2 * RB_GRAN * 16, true);
-                B.sub = resident_image(st, p.tail_image);
+                B.gran = alloc_resident_block(h, R, B.tail, B.tmo, (size_t)2 * RB_GRAN * 16, true);
+                // the tail workgroup answers with its root's iterate (level 3 or 4 applies M1 P itself)
+                ResTail& T = B.tail;
+                T.sub = resident_image(st, p.tail_image);
+                T.root = p.tail_root;
+                T.nin = p.poly4 ? B.N5 : B.N4;
+                T.answer_root = 1;
+                T.wcycle = B.wcycle;
                 commit_mask_form(h, R, p, B, sw);
             }
         }

@@ -203,7 +203,7 @@ def test_bernoulli_eighth_at_the_metric_size_against_the_oracle(ipd, cycle):
 
 
 def test_skipped_publish_gives_up_once_and_is_redone_by_the_launches(ipd):
-    """The recovery that makes the bounded spins safe (ipd_resident.h:res_sweep, run_resident): a test
+    """The recovery that makes the bounded spins safe (ipd_resident_proto.h:res_sweep, run_resident): a test
     hook makes the last workgroup omit ONE publish (hand-off 7), every sweep of that step gives up after
     2^18 polls, the kernel reports it through the time-out word, and ipd_amg_solve redoes the solve from
     the guess on the multi-launch path: same result as a hierarchy that never used the resident kernel,
