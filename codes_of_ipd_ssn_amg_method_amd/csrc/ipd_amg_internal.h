@@ -56,7 +56,7 @@ struct Level {
     double* scal = nullptr; // small device scalars (sum r, partial dots ...)
 };
 
-struct CycleState;   // ipd_cycle.hip
+struct CycleState;   // ipd_cycle_state.h
 struct KrylovState;  // ipd_krylov.hip
 struct BlockState;   // ipd_block.h
 struct BlockKrylovState;   // ipd_block_krylov.hip

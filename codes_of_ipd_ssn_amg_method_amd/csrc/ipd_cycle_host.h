@@ -1,101 +1,9 @@
 // Host-side orchestration of the cycle (included by ipd_cycle.hip only): launch
-// geometry, the recursive V/W schedule, the Class_AMG loop, the C ABI and the
-// measurement hooks.
+// geometry, the recursive V/W schedule, the Class_AMG loop and the C ABI.  (The
+// measurement hooks: ipd_cycle_bench.hip.)
 #pragma once
 
-#include <cstdlib>
-
-#include "ipd_resident_plan.h"
-
-struct LevelRun {  // per-level run state kept next to Level
-    LevelDev dev;
-    bool e_zero = true;      // the iterate is identically zero and is not materialised
-    LaunchLevel plan;        // how the level's phases run on the multi-launch path (ipd_launch_plan.h)
-    int maxoff = 0;          // longest off-diagonal row (k_level_prepare)
-    XferArgs restrict_args;  // r_{k+1} = P' rr_k   (stored on level k)
-    XferArgs prolong_args;   // e_k += P e_{k+1}
-    PcgArgs pcg;             // coarsest only
-};
-
-// The resident solve kernels (ipd_resident.h, ipd_resident_big.h): the whole Class_AMG loop in one launch of
-// co-resident workgroups.  The plan (ipd_resident_plan.h) and what running it needs; ipd_resident_host.h is the
-// only code that looks inside -- the rest of the host asks whether a plan is active (`ok`) and for its grid.
-struct ResidentState {
-    bool ok = false;             // a plan is active
-    bool off = false;            // IPD_NO_RESIDENT=1 when the hierarchy was set up
-    ResidentPlan plan;
-    ResDesc desc{};              // k_resident's descriptor (kept under a mask-form plan that replaced it: its rho)
-    ResBigDesc big{};            // the mask-form kernel's
-    unsigned skip_publish = 0;   // test hook (IPD_RES_DEBUG_SKIP_PUBLISH): fires on ONE launch
-    unsigned char* block = nullptr;   // granule block, zeroed before every launch
-    size_t block_bytes = 0;
-    double* out = nullptr;
-    int timeouts = 0;            // launches whose bounded spins gave up (then: multi-launch path)
-    long long last_handoffs = 0;   // hand-offs and cycles of the last launch (ipd_amg_resident_kernel)
-    int last_cycles = 0;
-    int capacity = -1;   // workgroups of the chosen instantiation the device holds at once (-1: not asked yet)
-    int line_ke = 0, line_ke3 = 0;   // what the "[ipd] resident launch:" line shows as ke / ke3
-    bool mask_form() const { return plan.kind == RESIDENT_BIG || plan.kind == RESIDENT_DEEP; }
-};
-
-struct CycleState {
-    std::vector<LevelRun> run;  // 1-based
-    double* hist = nullptr;
-    // row-block sharding: `shard_ranks` owners per row range.  In emulate mode
-    // one process plays all owners back to back on the shared vectors (the all-gather is
-    // then implicit) -- used by the single-GPU test of the slicing logic.
-    int shard_ranks = 1;
-    int shard_rank = 0;
-    bool shard_emulate = false;
-    int shard_min_rows = 256;
-    int num_cu = 256;
-    // fused single-workgroup program under construction (flushed before any big launch)
-    FusedProg pending;
-    size_t pending_lds = 0;
-    CycleState() { pending.n = 0; }
-    // The LDS images of the single-workgroup kernels (ipd_level_plan.h) by role: the whole solve (k_solve_small,
-    // k_pcg_small), the sub-cycle rooted at level k_sub (k_subcycle), and the images rooted at level 3 (no sub-cycle:
-    // k_sub == 0) and at level 4 (beside a sub-cycle rooted at level 3: `three` mode) that the resident kernels' tail
-    // workgroup takes alone
-    struct Image {
-        SolveDesc* desc = nullptr;
-        size_t lds = 0;   // dynamic LDS of a launch
-        size_t bm = 0;    // ... and what the image's operator copy needs on top of it (SolveDesc::bm_src; 0: none)
-    };
-    Image img[IMG_NONE];
-    double* solve_out = nullptr;   // the whole-solve kernel's outputs
-    bool small_ok = false;
-    bool solve_cached = false;
-    // matrix-free level-1 operator (bit mask + scale vectors), see k_smooth_mask
-    bool mask_ok = false;
-    MaskOp maskop{};
-    int k_sub = 0;                 // root of the IMG_SUB image (0 = none)
-    bool sub_semi_root = false;    // ... which is semi-cached (rows from L2)
-    std::vector<int> level_forms;  // per level, over all images packed: see ipd_amg_level_forms
-    struct PolyOp {                // block-wide polynomial operators packed for the images (ipd_amg_poly_operator)
-        const double* M = nullptr;
-        const double* W = nullptr;
-        int LD = 0, N = 0, Nc = 0;
-    };
-    std::vector<PolyOp> poly_ops;
-    struct RowsOp {                // row-layout polynomial operators of the resident kernels (ipd_amg_packed_operator)
-        const double* M = nullptr; // [N + Nc][ld], W (N + Nc entries) right behind
-        int ld = 0, seg = 0, N = 0, Nc = 0;
-    };
-    std::vector<RowsOp> rows_ops;  // per level: form 64 (level 3 / 4 of k_resident's `three` mode or of DEEP mode)
-    RowsOp poly2_op;               // form 128: level 2 composed over a visit
-    ImageRole sub5 = IMG_NONE;     // the image whose levels 5..J serve a resident kernel's tail rooted at level 5 (POLY4)
-    double* x2 = nullptr;
-    ResidentState res;   // the resident solve kernels: plan and run state (ipd_resident_host.h)
-    hipGraphExec_t gexec[2] = {nullptr, nullptr};  // captured Class_AMG loop bodies (x->x2, x2->x)
-    const double* gb = nullptr;                    // right-hand side the graphs were captured for
-    ~CycleState() {
-        for (auto& g : gexec)
-            if (g) (void)hipGraphExecDestroy(g);
-    }
-};
-
-static CycleState* state_of(ipd_amg* h) { return h->cyc.get(); }
+#include "ipd_cycle_state.h"
 
 __global__ void k_level_prepare(int N, int nf, const int* __restrict__ rp,
                                 const int* __restrict__ ci, const double* __restrict__ va,
@@ -828,28 +736,8 @@ void amg_prepare_levels(ipd_amg* h) {
 // ---------------------------------------------------------------------------
 // launches
 // ---------------------------------------------------------------------------
-#define IPD_LAUNCH_SP(kern, staged, pad, grid, dyn, ...)                                          \
-    do {                                                                                          \
-        if (staged) {                                                                             \
-            if (pad)                                                                              \
-                hipLaunchKernelGGL((kern<true, true>), dim3(grid), dim3(BT), dyn, ctx->stream,     \
-                                   __VA_ARGS__);                                                  \
-            else                                                                                  \
-                hipLaunchKernelGGL((kern<true, false>), dim3(grid), dim3(BT), dyn, ctx->stream,    \
-                                   __VA_ARGS__);                                                  \
-        } else {                                                                                  \
-            if (pad)                                                                              \
-                hipLaunchKernelGGL((kern<false, true>), dim3(grid), dim3(BT), 0, ctx->stream,      \
-                                   __VA_ARGS__);                                                  \
-            else                                                                                  \
-                hipLaunchKernelGGL((kern<false, false>), dim3(grid), dim3(BT), 0, ctx->stream,     \
-                                   __VA_ARGS__);                                                  \
-        }                                                                                         \
-        IPD_KERNEL_CHECK();                                                                       \
-    } while (0)
-
 // ---- fused-program emitter (which phases are queued: phase_is_small, ipd_launch_plan.h) -------
-static void flush_fused(ipd_ctx* ctx, CycleState* st) {
+void flush_fused(ipd_ctx* ctx, CycleState* st) {
     if (st->pending.n == 0) return;
     hipLaunchKernelGGL(k_fused, dim3(1), dim3(BT), st->pending_lds, ctx->stream, st->pending);
     IPD_KERNEL_CHECK();
@@ -894,7 +782,10 @@ static void run_rows(ipd_ctx* ctx, CycleState* st, const RowRange& rg, int L, F 
 
 static void launch_smooth(ipd_ctx* ctx, const SmoothArgs& a, int grid) {
     const size_t dyn = a.staged ? sizeof(double) * (size_t)a.lv.N : 0;
-    IPD_LAUNCH_SP(k_smooth, a.staged, a.lv.S > 0, grid, dyn, a);
+    dispatch_staged_pad(a.staged, a.lv.S > 0, [&](auto S, auto P) {
+        hipLaunchKernelGGL((k_smooth<decltype(S)::value, decltype(P)::value>), dim3(grid), dim3(BT), decltype(S)::value ? dyn : 0, ctx->stream, a);
+    });
+    IPD_KERNEL_CHECK();
 }
 
 // a restriction or prolongation as planned: queued into the fused program or launched over its rows
@@ -920,11 +811,14 @@ static void issue_xfer(ipd_ctx* ctx, CycleState* st, XferArgs a, const XferPlan&
 static void launch_resid(ipd_ctx* ctx, const LevelRun& rn, const double* e, int r0, int r1,
                          int grid) {
     const size_t dyn = rn.plan.staged ? sizeof(double) * (size_t)rn.dev.N : 0;
-    IPD_LAUNCH_SP(k_resid, rn.plan.staged, rn.dev.S > 0, grid, dyn, rn.dev, e, r0, r1);
+    dispatch_staged_pad(rn.plan.staged, rn.dev.S > 0, [&](auto S, auto P) {
+        hipLaunchKernelGGL((k_resid<decltype(S)::value, decltype(P)::value>), dim3(grid), dim3(BT), decltype(S)::value ? dyn : 0, ctx->stream, rn.dev, e, r0, r1);
+    });
+    IPD_KERNEL_CHECK();
 }
 
 // one smoother sweep on level k: Jacobi = one launch, bigraph GS = two half launches
-static void launch_sweep(ipd_amg* h, CycleState* st, int k, int isnsp, bool post) {
+void launch_sweep(ipd_amg* h, CycleState* st, int k, int isnsp, bool post) {
     ipd_ctx* ctx = h->ctx;
     Level& lv = h->L[k];
     LevelRun& rn = st->run[(size_t)k];
@@ -986,6 +880,12 @@ __global__ void k_maskop_scales(int nf, int nc, const double* __restrict__ p,
     }
 }
 
+void launch_subcycle(ipd_ctx* ctx, CycleState* st, bool keep_e) {
+    hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->img[IMG_SUB].lds, ctx->stream,
+                       (const SolveDesc*)st->img[IMG_SUB].desc, keep_e ? 1 : 0);
+    IPD_KERNEL_CHECK();
+}
+
 // Solves A_k e = r_k approximately; r in L[k].r, result in L[k].e.
 // keep_e: start from the current L[k].e (second leg of a W cycle); otherwise the
 // start is e = 0, which is never materialised (the first sweep does not read it).
@@ -998,9 +898,7 @@ void amg_cycle(ipd_amg* h, int k, int isnsp, bool wcycle, bool keep_e) {
     const LaunchLevel& p = rn.plan;
     if (st->k_sub == k) {  // everything from here down: one workgroup, LDS-resident (replicated)
         flush_fused(ctx, st);
-        hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->img[IMG_SUB].lds, ctx->stream,
-                           (const SolveDesc*)st->img[IMG_SUB].desc, keep_e ? 1 : 0);
-        IPD_KERNEL_CHECK();
+        launch_subcycle(ctx, st, keep_e);
         rn.e_zero = false;
         return;
     }
@@ -1070,7 +968,7 @@ void amg_cycle(ipd_amg* h, int k, int isnsp, bool wcycle, bool keep_e) {
     for (int s = 0; s < nu; ++s) launch_sweep(h, st, k, isnsp, true);           // :33-41
 }
 
-static void launch_top(ipd_amg* h, CycleState* st, const double* b, const double* x,
+void launch_top(ipd_amg* h, CycleState* st, const double* b, const double* x,
                        const double* e, double* xnew, bool first) {
     ipd_ctx* ctx = h->ctx;
     LevelRun& rn = st->run[1];
@@ -1091,7 +989,10 @@ static void launch_top(ipd_amg* h, CycleState* st, const double* b, const double
                  [&](int r0, int r1, int grid) {
                      a.row0 = r0;
                      a.row1 = r1;
-                     IPD_LAUNCH_SP(k_top, a.staged, rn.dev.S > 0, grid, dyn, a);
+                     dispatch_staged_pad(a.staged, rn.dev.S > 0, [&](auto S, auto P) {
+                         hipLaunchKernelGGL((k_top<decltype(S)::value, decltype(P)::value>), dim3(grid), dim3(BT), decltype(S)::value ? dyn : 0, ctx->stream, a);
+                     });
+                     IPD_KERNEL_CHECK();
                  },
                  {rn.dev.r, xnew});
     }
@@ -1105,7 +1006,7 @@ static void launch_top(ipd_amg* h, CycleState* st, const double* b, const double
 }
 
 // one Class_AMG loop body (Class_AMG.m:96-105): x_out = x_in + cycle(b - A x_in)
-static void enqueue_loop_body(ipd_amg* h, CycleState* st, const double* b, const double* xin,
+void enqueue_loop_body(ipd_amg* h, CycleState* st, const double* b, const double* xin,
                               double* xout) {
     const bool wc = h->opts.cycle == 'w', vc = h->opts.cycle == 'v';
     const double* ecorr = nullptr;
@@ -1116,10 +1017,8 @@ static void enqueue_loop_body(ipd_amg* h, CycleState* st, const double* b, const
     launch_top(h, st, b, xin, ecorr, xout, false);
 }
 
-static void ensure_graphs(ipd_amg* h, CycleState* st, const double* b_dev);
-
 // the whole solve phase (cycles == 0) or `cycles` cycles without stopping rules as one single-workgroup launch
-static void launch_solve_small(ipd_ctx* ctx, CycleState* st, const double* b_dev, double* x, int cycles) {
+void launch_solve_small(ipd_ctx* ctx, CycleState* st, const double* b_dev, double* x, int cycles) {
     const CycleState::Image& im = st->img[IMG_SOLVE];
     if (st->solve_cached)
         hipLaunchKernelGGL(k_solve_small<true>, dim3(1), dim3(BT), im.lds, ctx->stream, (const SolveDesc*)im.desc,
@@ -1141,28 +1040,6 @@ static void load_guess(ipd_ctx* ctx, double* x, const double* guess_dev, int N) 
     else
         IPD_HIP(hipMemsetAsync(x, 0, sizeof(double) * (size_t)N, ctx->stream));
 }
-
-// Times what the stream is given between construction and stop() with HIP events
-struct StreamTimer {
-    hipStream_t stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    explicit StreamTimer(hipStream_t s) : stream(s) {
-        IPD_HIP(hipEventCreate(&e0));
-        IPD_HIP(hipEventCreate(&e1));
-        IPD_HIP(hipEventRecord(e0, stream));
-    }
-    float stop() {   // milliseconds
-        IPD_HIP(hipEventRecord(e1, stream));
-        IPD_HIP(hipEventSynchronize(e1));
-        float ms = 0.f;
-        IPD_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return ms;
-    }
-    ~StreamTimer() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-};
 
 // Class_AMG.m:86-109
 void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, double* x_dev,
@@ -1194,7 +1071,7 @@ void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, dou
         deliver(out);
         return;
     }
-    if (st->res.ok && st->shard_ranks == 1) {
+    if (resident_active(st) && st->shard_ranks == 1) {
         // dense regime: the whole solve phase is one launch of co-resident workgroups
         std::vector<double> out;
         if (run_resident(h, st, b_dev, xa, 0, &out, nullptr)) {
@@ -1436,42 +1313,6 @@ extern "C" int ipd_pcg(ipd_ctx* ctx, const ipd_csc* H, const double* e, const do
     });
 }
 
-// ---------------------------------------------------------------------------
-// measurement hooks
-// ---------------------------------------------------------------------------
-// S(X) = 12 nnz + 4 (rows+1) + 8 rows + 8 cols per CSR SpMV.
-static double spmv_bytes(const Csr& m) {
-    return 12.0 * m.nnz + 4.0 * (m.nr + 1) + 8.0 * m.nr + 8.0 * m.nc;
-}
-
-// B_V with the fused Gauss-Seidel form (one S(A_1) per level-1 sweep, the stated
-// minimum): per level (2 nu + 1) S(A_k) + S(P) + S(P') + 6 nu 8 N_k, weighted by
-// the visit count (1 for V, 2^(k-1) for W), + coarsest PCG + the outer loop's
-// residual S(A_1) + 32 M.
-static double cycle_bytes(const ipd_amg* h) {
-    const bool wc = h->opts.cycle == 'w';
-    const double nu = h->opts.smoth;
-    double total = 0.0;
-    double visits = 1.0;
-    for (int k = 1; k < h->J; ++k) {
-        const Level& lv = h->L[k];
-        const Level& cl = h->L[k + 1];
-        const double per = (2 * nu + 1) * spmv_bytes(lv.A) + spmv_bytes(cl.P) + spmv_bytes(cl.Pt) +
-                           6 * nu * 8.0 * lv.A.nr;
-        total += visits * per;
-        if (wc && k + 1 < h->J) visits *= 2.0;
-    }
-    total += visits * 2.0 * spmv_bytes(h->L[h->J].A);  // >= 1 PCG iteration + initial residual
-    total += spmv_bytes(h->L[1].A) + 32.0 * h->L[1].A.nr;
-    return total;
-}
-
-extern "C" int ipd_amg_cycle_bytes(const ipd_amg* h, double* bytes_per_cycle) {
-    if (!h || !bytes_per_cycle) return IPD_E_ARG;
-    *bytes_per_cycle = cycle_bytes(h);
-    return IPD_OK;
-}
-
 // How the levels held in the LDS images of this hierarchy run (bit mask over all images packed):
 // 1 thread-per-row sweeps, 2 the same with dense rows in registers, 4 one-wave sweeps, 8 one-wave
 // polynomial form, 16 block-wide polynomial form; 0: the level is in no image.
@@ -1546,200 +1387,5 @@ extern "C" int ipd_amg_packed_operator(const ipd_amg* h, int32_t k, int32_t form
         if (!out) return;   // size query
         IPD_REQUIRE(cap >= need, IPD_E_ARG, "buffer too small");
         h->ctx->fetch(M, out, (size_t)need);
-    });
-}
-
-// Captures the two loop bodies (x -> x2 and x2 -> x) as HIP graphs: one graph launch
-// per cycle instead of ~40 kernel launches, so the host never paces the device.
-static void ensure_graphs(ipd_amg* h, CycleState* st, const double* b_dev) {
-    if (st->gexec[0] && st->gb == b_dev) return;
-    ipd_ctx* ctx = h->ctx;
-    for (auto& g : st->gexec)
-        if (g) {
-            IPD_HIP(hipGraphExecDestroy(g));
-            g = nullptr;
-        }
-    double* xs[2] = {h->x, st->x2};
-    for (int v = 0; v < 2; ++v) {
-        hipGraph_t graph = nullptr;
-        IPD_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-        try {
-            enqueue_loop_body(h, st, b_dev, xs[v], xs[v ^ 1]);
-        } catch (...) {
-            (void)hipStreamEndCapture(ctx->stream, &graph);
-            if (graph) (void)hipGraphDestroy(graph);
-            throw;
-        }
-        IPD_HIP(hipStreamEndCapture(ctx->stream, &graph));
-        hipError_t e = hipGraphInstantiate(&st->gexec[v], graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        IPD_HIP(e);
-    }
-    st->gb = b_dev;
-}
-
-// Times `cycles` loop bodies on x_dev, eager or as the captured graphs, after the initial residual
-// (Class_AMG.m:89); milliseconds
-static float time_loop_bodies(ipd_amg* h, CycleState* st, const double* b_dev, double* x_dev, int cycles,
-                              bool use_graph) {
-    ipd_ctx* ctx = h->ctx;
-    const int N = h->L[1].A.nr;
-    copy_vec(ctx, h->x, x_dev, N);
-    launch_top(h, st, b_dev, h->x, nullptr, st->x2, true);   // x stays in h->x
-    copy_vec(ctx, h->x, st->x2, N);
-    if (use_graph) ensure_graphs(h, st, b_dev);
-    double* xs[2] = {h->x, st->x2};
-    StreamTimer timer(ctx->stream);
-    int v = 0;
-    for (int c = 0; c < cycles; ++c) {
-        if (use_graph)
-            IPD_HIP(hipGraphLaunch(st->gexec[v], ctx->stream));
-        else
-            enqueue_loop_body(h, st, b_dev, xs[v], xs[v ^ 1]);
-        v ^= 1;
-    }
-    const float ms = timer.stop();
-    copy_vec(ctx, x_dev, xs[v], N);
-    return ms;
-}
-
-extern "C" int ipd_amg_bench_cycles(ipd_amg* h, const double* b_dev, double* x_dev, int cycles,
-                                    double* total_ms, double* bytes_per_cycle) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h && b_dev && x_dev && cycles > 0 && total_ms, IPD_E_ARG, "bad argument");
-        ipd_ctx* ctx = h->ctx;
-        CallScope scope(ctx);
-        CycleState* st = state_of(h);
-        IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
-        const int N = h->L[1].A.nr;
-        float ms = 0.f;
-        bool done = false;
-        if (st->small_ok || st->res.ok) {  // one launch runs all the cycles (no stopping rules)
-            copy_vec(ctx, h->x, x_dev, N);
-            if (st->small_ok) {            // ... of one workgroup
-                StreamTimer timer(ctx->stream);
-                launch_solve_small(ctx, st, b_dev, h->x, cycles);
-                ms = timer.stop();
-                done = true;
-            } else {                       // ... of co-resident workgroups
-                done = run_resident(h, st, b_dev, h->x, cycles, nullptr, &ms);
-            }
-            if (done) copy_vec(ctx, x_dev, h->x, N);
-        }
-        if (!done) ms = time_loop_bodies(h, st, b_dev, x_dev, cycles, !switch_on("IPD_NO_GRAPH"));
-        ctx->sync();
-        *total_ms = ms;
-        if (bytes_per_cycle) *bytes_per_cycle = cycle_bytes(h);
-    });
-}
-
-// Times `reps` smoother sweeps of level k (pre-smoothing direction) with HIP events on
-// the context's stream: the per-launch duration of the dominant kernel (k_smooth).
-// launches_per_sweep = 2 for the bigraph Gauss-Seidel level, 1 for Jacobi levels;
-// bytes_per_sweep = S(A_k) + 6*8*N_k (fused-GS form).
-extern "C" int ipd_amg_bench_subcycle(ipd_amg* h, int reps, double* total_ms, int32_t* k_sub,
-                                      int64_t stamps[8]) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h && reps > 0 && total_ms, IPD_E_ARG, "bad argument");
-        ipd_ctx* ctx = h->ctx;
-        ctx->set_device();
-        CycleState* st = state_of(h);
-        IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
-        if (k_sub) *k_sub = st->k_sub;
-        *total_ms = 0.0;
-        if (!st->k_sub) return;
-        CallScope scope(ctx);
-        long long* dbg = ctx->scratch->alloc<long long>(16);
-        IPD_HIP(hipMemsetAsync(dbg, 0, 128, ctx->stream));
-        // patch the debug pointer into the image header
-        const size_t off = offsetof(SolveDesc, dbg);
-        // (a stamp is two s_memrealtime reads and a read-modify-write of global memory, ~0.5 us each: the
-        // per-stage figures are for proportions)
-        ctx->upload_bytes(reinterpret_cast<char*>(st->img[IMG_SUB].desc) + off, &dbg, sizeof(dbg));
-        {   // a right-hand side that is not zero (a zero one ends every coarse PCG at once)
-            std::vector<double> rr((size_t)h->L[st->k_sub].N);
-            unsigned lcg = 12345u;
-            for (auto& v : rr) {
-                lcg = lcg * 1664525u + 1013904223u;
-                v = (double)(lcg >> 8) / (double)(1u << 24) - 0.5;
-            }
-            ctx->upload(h->L[st->k_sub].r, rr.data(), rr.size());
-        }
-        hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->img[IMG_SUB].lds, ctx->stream,
-                           (const SolveDesc*)st->img[IMG_SUB].desc, 0);
-        StreamTimer timer(ctx->stream);
-        for (int r = 0; r < reps; ++r)
-            hipLaunchKernelGGL(k_subcycle, dim3(1), dim3(BT), st->img[IMG_SUB].lds, ctx->stream,
-                               (const SolveDesc*)st->img[IMG_SUB].desc, 0);
-        const float ms = timer.stop();
-        IPD_KERNEL_CHECK();
-        *total_ms = ms;
-        long long hs[16];
-        ctx->fetch(dbg, hs, 16);
-        if (stamps && hs[3] > hs[2])   // shader clock (MHz) seen by the cycle: s_memtime ticks / 10 ns
-            stamps[0] = hs[8] * 100 / (hs[3] - hs[2]), hs[0] = stamps[0];
-        if (stamps)
-            for (int i = 0; i < 8; ++i) stamps[i] = hs[i];
-        long long* none = nullptr;
-        ctx->upload_bytes(reinterpret_cast<char*>(st->img[IMG_SUB].desc) + off, &none, sizeof(none));
-    });
-}
-
-extern "C" int ipd_amg_bench_sweeps(ipd_amg* h, int k, int reps, double* total_ms,
-                                    int* launches_per_sweep, double* bytes_per_sweep) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h && total_ms && reps > 0, IPD_E_ARG, "bad argument");
-        IPD_REQUIRE(k >= 1 && k < h->J, IPD_E_ARG, "level must be a smoothed level (1 <= k < J)");
-        ipd_ctx* ctx = h->ctx;
-        CallScope scope(ctx);
-        CycleState* st = state_of(h);
-        Level& lv = h->L[k];
-        LevelRun& rn = st->run[(size_t)k];
-        fill_f64(ctx, lv.r, 1.0, (size_t)lv.N);
-        rn.e_zero = true;
-        for (int w = 0; w < 4; ++w) launch_sweep(h, st, k, h->opts.isnsp, false);
-        flush_fused(ctx, st);
-        StreamTimer timer(ctx->stream);
-        for (int s = 0; s < reps; ++s) launch_sweep(h, st, k, h->opts.isnsp, false);
-        flush_fused(ctx, st);
-        const float ms = timer.stop();
-        *total_ms = ms;
-        if (launches_per_sweep) *launches_per_sweep = lv.nf > 0 ? 2 : 1;
-        if (bytes_per_sweep) *bytes_per_sweep = spmv_bytes(lv.A) + 6 * 8.0 * lv.A.nr;
-    });
-}
-
-// Row-block sharded loop body (eager launches; RCCL calls are not graph-captured).
-extern "C" int ipd_amg_bench_cycles_sharded(ipd_amg* h, const double* b_dev, double* x_dev,
-                                            int cycles, double* total_ms,
-                                            double* bytes_per_cycle) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h && b_dev && x_dev && cycles > 0 && total_ms, IPD_E_ARG, "bad argument");
-        ipd_ctx* ctx = h->ctx;
-        CallScope scope(ctx);
-        CycleState* st = state_of(h);
-        IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
-        const char* emu = switch_value("IPD_SHARD_EMULATE");
-        const int emu_ranks = emu ? std::atoi(emu) : 0;
-        struct Restore {
-            CycleState* st;
-            ~Restore() {
-                st->shard_ranks = 1;
-                st->shard_rank = 0;
-                st->shard_emulate = false;
-            }
-        } restore{st};
-        if (emu_ranks > 1) {
-            st->shard_ranks = emu_ranks;
-            st->shard_emulate = true;
-        } else {
-            st->shard_ranks = comm_size(ctx);
-            st->shard_rank = comm_rank(ctx);
-            IPD_REQUIRE(st->shard_ranks == 1 || ctx->comm, IPD_E_COMM, "call ipd_comm_init first");
-        }
-        const float ms = time_loop_bodies(h, st, b_dev, x_dev, cycles, false);
-        ctx->sync();
-        *total_ms = ms;
-        if (bytes_per_cycle) *bytes_per_cycle = cycle_bytes(h);
     });
 }

@@ -10,6 +10,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ipd_amg.h"
@@ -525,6 +526,19 @@ __device__ __forceinline__ int scan_head(const int* __restrict__ cnt, int n, int
 void ipd_lds_optin(const void* kernel, int device, int bytes);
 #define IPD_OPTIN_LDS(ctx, kernel, bytes) \
     ipd_lds_optin(reinterpret_cast<const void*>(kernel), (ctx)->device, (bytes))
+
+// The four-way dispatch of the kernels templated on <STAGED, PAD> (gather vector staged in LDS, padded row copy):
+// calls f(S, P) with the run-time pair as std::true_type / std::false_type, for decltype(S)::value in the launch
+template <class F>
+inline void dispatch_staged_pad(bool staged, bool pad, F&& f) {
+    if (staged) {
+        if (pad) f(std::true_type{}, std::true_type{});
+        else f(std::true_type{}, std::false_type{});
+    } else {
+        if (pad) f(std::false_type{}, std::true_type{});
+        else f(std::false_type{}, std::false_type{});
+    }
+}
 
 // ---------------------------------------------------------------------------
 // cross-TU device routines (all asynchronous on ctx->stream unless noted)

@@ -220,26 +220,6 @@ static KrylovState* krylov_state(ipd_amg* h, int N, int G1, int G3) {
     return h->kry.get();
 }
 
-#define KRY_LAUNCH_K1(START, grid, dyn, args)                                                          \
-    do {                                                                                               \
-        if (staged) {                                                                                  \
-            if (pad)                                                                                   \
-                hipLaunchKernelGGL((k_kry_dir_spmv<true, true, START>), dim3(grid), dim3(BT), dyn,     \
-                                   ctx->stream, args);                                                 \
-            else                                                                                       \
-                hipLaunchKernelGGL((k_kry_dir_spmv<true, false, START>), dim3(grid), dim3(BT), dyn,    \
-                                   ctx->stream, args);                                                 \
-        } else {                                                                                       \
-            if (pad)                                                                                   \
-                hipLaunchKernelGGL((k_kry_dir_spmv<false, true, START>), dim3(grid), dim3(BT), 0,      \
-                                   ctx->stream, args);                                                 \
-            else                                                                                       \
-                hipLaunchKernelGGL((k_kry_dir_spmv<false, false, START>), dim3(grid), dim3(BT), 0,     \
-                                   ctx->stream, args);                                                 \
-        }                                                                                              \
-        IPD_KERNEL_CHECK();                                                                            \
-    } while (0)
-
 // [d,it,res,resk] = AMG_PCG(h,e,pcg_options) on device vectors; resk: host, maxit slots or NULL
 static void amg_pcg_dev(ipd_amg* h, const double* e, const double* guess, double tol, long long maxit,
                         double* d_out, long long* it_out, double* res_out, double* resk) {
@@ -269,7 +249,11 @@ static void amg_pcg_dev(ipd_amg* h, const double* e, const double* guess, double
     ka.r = ks->r;
     ka.r1 = r1;
     ka.d = ks->d;
-    KRY_LAUNCH_K1(true, G1, dyn, ka);
+    dispatch_staged_pad(staged, pad, [&](auto S, auto P) {
+        hipLaunchKernelGGL((k_kry_dir_spmv<decltype(S)::value, decltype(P)::value, true>), dim3(G1), dim3(BT),
+                           decltype(S)::value ? dyn : 0, ctx->stream, ka);
+    });
+    IPD_KERNEL_CHECK();
     KryDotArgs kd{};
     kd.N = N;
     kd.r = ks->r;
@@ -300,7 +284,11 @@ static void amg_pcg_dev(ipd_amg* h, const double* e, const double* guess, double
         ka.w = h->L[1].e;
         ka.p_old = have_p ? ks->p[cur] : nullptr;
         ka.p_new = ks->p[cur ^ 1];
-        KRY_LAUNCH_K1(false, G1, dyn, ka);                                        // :77-78, :83
+        dispatch_staged_pad(staged, pad, [&](auto S, auto P) {
+            hipLaunchKernelGGL((k_kry_dir_spmv<decltype(S)::value, decltype(P)::value, false>), dim3(G1), dim3(BT),
+                               decltype(S)::value ? dyn : 0, ctx->stream, ka);
+        });
+        IPD_KERNEL_CHECK();                                        // :77-78, :83
         cur ^= 1;
         have_p = true;
         hipLaunchKernelGGL(k_kry_update, dim3(G3), dim3(BT), 0, ctx->stream, N, (const double*)ks->sc,

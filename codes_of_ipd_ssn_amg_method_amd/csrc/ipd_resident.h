@@ -1,4 +1,4 @@
-// Level-resident solve kernel (included by ipd_cycle.hip only).
+// Level-resident solve kernel (a template: ipd_resident_k2.hip and ipd_resident_k3.hip instantiate it).
 //
 // The multi-launch path pays one kernel boundary plus 2-3 dependent memory round trips per
 // half sweep: 4.6-5.0 us per k_smooth launch at m=n=1024, rho=1, where the 12.7 MB a launch
@@ -32,6 +32,8 @@
 // Arithmetic per row is the multi-launch kernels' (phase_smooth / phase_resid / phase_xfer /
 // phase_top), only the order inside a row's dot product differs (lane-strided entries).
 #pragma once
+
+#include "ipd_resident_proto.h"
 
 static constexpr int RES_P3_LD = 1152;         // row stride of ResDesc::p3rows: 512 + 512 + 128
 static constexpr int RES_P4_LD = 2 * RES_P4_SEG + 64;
@@ -206,53 +208,6 @@ __device__ __forceinline__ double res_csr_rowdot(const ResCsr& M, int e0, int e1
         for (int u = 0; u < 8; ++u) s += (t + 64 * u < e1) ? aa[u] * sm[off + jj[u]] : 0.0;
     }
     return wave_sum(s);
-}
-
-// *bad != 0 unless the level 1 <-> 2 transfers have the bigraph form P = [W; I] (AMG/transfer.m:19-25)
-// entry for entry: every row of P' (level-2 row c) ends with the identity entry (column nf + c, value
-// 1) and row nf + c of P is that identity entry alone.  The kernel then adds the identity parts
-// itself: a 1025-entry row of P' is two 512-entry trips instead of three, and the C rows of P cost
-// no trip at all.
-__global__ void k_res_check_ident(int nf, int N2, ResCsr P, ResCsr Pt, int* __restrict__ bad) {
-    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < N2; c += gridDim.x * blockDim.x) {
-        const int e1 = Pt.rp[c + 1], p0 = P.rp[nf + c];
-        const bool ok = e1 > Pt.rp[c] && Pt.ci[e1 - 1] == nf + c && Pt.va[e1 - 1] == 1.0 &&
-                        P.rp[nf + c + 1] - p0 == 1 && P.ci[p0] == c && P.va[p0] == 1.0;
-        if (!ok) atomicOr(bad, 1);
-    }
-}
-
-// rho of the mask-form transfers and the check of P against W(j,i) = s_ij beta_i rho_j (one wave per F row
-// j: its row of P holds exactly the row's mask entries, in column order, each within 1e-12 of the form)
-__global__ __launch_bounds__(256) void k_res_xmask_rho(int nf, int nc, int isnsp,
-                                                       const unsigned long long* __restrict__ fbits, int nwf,
-                                                       const double* __restrict__ alpha,
-                                                       const double* __restrict__ beta,
-                                                       const double* __restrict__ diag, const int* __restrict__ prp,
-                                                       const int* __restrict__ pci, const double* __restrict__ pva,
-                                                       double* __restrict__ rho, int* __restrict__ bad) {
-    const int lane = threadIdx.x & 63;
-    const int j = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (j >= nf) return;
-    double sb = 0.0;
-    int cnt = 0;
-    for (int w = 0; w < nwf; ++w) {
-        const unsigned long long bits = fbits[(size_t)j * nwf + w];
-        const int i = w * 64 + lane;
-        if ((bits >> lane) & 1ull) sb += beta[i];
-        cnt += __popcll(bits);
-    }
-    sb = wave_sum(sb);
-    const double r = isnsp ? 1.0 / sb : alpha[j] / diag[j];
-    if (lane == 0) rho[j] = r;
-    bool wrong = (prp[j + 1] - prp[j]) != cnt;
-    for (int t = prp[j] + lane; t < prp[j + 1] && !wrong; t += 64) {
-        const int i = pci[t];
-        const bool bit = i >= 0 && i < nc && ((fbits[(size_t)j * nwf + (i >> 6)] >> (i & 63)) & 1ull);
-        const double ref = beta[i < nc ? i : 0] * r;
-        if (!bit || !(fabs(pva[t] - ref) <= 1e-12 * fabs(ref))) wrong = true;
-    }
-    if (wrong) atomicExch(bad, 1);
 }
 
 // Block sums of up to two per-thread partials through red[0..2*RES_WAVES): the caller has

@@ -1,4 +1,5 @@
-// Level-resident solve kernel for level 1 of up to 4096 rows (included by ipd_cycle.hip only).
+// Level-resident solve kernel for level 1 of up to 4096 rows (a template:
+// ipd_resident_kbig.hip instantiates it).
 //
 // k_resident (ipd_resident.h) keeps the FULL vectors of levels 1-2 in every workgroup's LDS and the
 // rows of both levels in registers: at m = n = 2048 (BASELINE config 4's size: M = 4096, regime D) the
@@ -30,6 +31,8 @@
 // owns RPW = 2 rows of each block (rows w and w + 8 of the workgroup's run).
 // Reference: AMG/Class_AMG.m:86-109, AMG/MG_Vcycle.m:12-45, AMG/MG_Wcycle.m:13-46, PCG.m:68-87.
 #pragma once
+
+#include "ipd_resident.h"   // its row slices, row dots and block sums
 
 static constexpr int RB_GRAN = RB_NMAX;                // granules per hand-off buffer
 static constexpr int RB_P3_SEG = RB_N3MAX;             // p3rows layout: [Mr (RB_P3_SEG) | Me (RB_P3_SEG) | Mc (RB_N4MAX)]

@@ -1,15 +1,50 @@
-// Host side of the resident kernels (included by ipd_cycle_host.h, which defines CycleState and its
-// ResidentState member, at the place of the first kernel-template launch of the translation unit): the table of
+// Host side of the resident kernels (included by ipd_cycle_host.h, after ipd_cycle_state.h has declared
+// CycleState and ResidentState, at the place of the first kernel-template launch of the translation unit): the table of
 // their instantiations, the execution of a plan (ipd_resident_plan.h decides, this file does the device work
 // the plan calls for, verifies what only the device can verify and commits it to CycleState::res), the slots
 // and the launch, the attach functions and the introspection entry points.
 #pragma once
 
+// The plan and what running it needs (opaque outside this file: ipd_cycle_state.h)
+struct ResidentState {
+    bool ok = false;             // a plan is active
+    bool off = false;            // IPD_NO_RESIDENT=1 when the hierarchy was set up
+    ResidentPlan plan;
+    ResDesc desc{};              // k_resident's descriptor (kept under a mask-form plan that replaced it: its rho)
+    ResBigDesc big{};            // the mask-form kernel's
+    unsigned skip_publish = 0;   // test hook (IPD_RES_DEBUG_SKIP_PUBLISH): fires on ONE launch
+    unsigned char* block = nullptr;   // granule block, zeroed before every launch
+    size_t block_bytes = 0;
+    double* out = nullptr;
+    int timeouts = 0;            // launches whose bounded spins gave up (then: multi-launch path)
+    long long last_handoffs = 0;   // hand-offs and cycles of the last launch (ipd_amg_resident_kernel)
+    int last_cycles = 0;
+    int capacity = -1;   // workgroups of the chosen instantiation the device holds at once (-1: not asked yet)
+    int line_ke = 0, line_ke3 = 0;   // what the "[ipd] resident launch:" line shows as ke / ke3
+    bool mask_form() const { return plan.kind == RESIDENT_BIG || plan.kind == RESIDENT_DEEP; }
+};
+
 // ---- the instantiations ---------------------------------------------------------------------
+// Three units instantiate the kernels; this one takes their addresses and compiles none of them.
+// ipd_resident_kbig.hip
+extern template __global__ void k_resident_big<4, 2, true>(const ResBigDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident_big<8, 2, true>(const ResBigDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident_big<16, 1, false>(const ResBigDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident_big<32, 1, false>(const ResBigDesc, const double* __restrict__, double*, double*, int);
+// ipd_resident_k2.hip
+extern template __global__ void k_resident<16, 16, 0, true>(const ResDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident<4, 4, 0, false>(const ResDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident<8, 8, 0, false>(const ResDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident<16, 16, 0, false>(const ResDesc, const double* __restrict__, double*, double*, int);
+// ipd_resident_k3.hip
+extern template __global__ void k_resident<4, 4, 1, false>(const ResDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident<8, 8, 1, false>(const ResDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident<4, 4, 4, false>(const ResDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident<4, 4, 8, false>(const ResDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident<8, 8, 4, false>(const ResDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident<8, 8, 8, false>(const ResDesc, const double* __restrict__, double*, double*, int);
 // One row per instantiation: its name as a rocprofv3 kernel trace (and ipd_amg_resident_kernel) spells it, the
-// plan's key, the kernel.  A key without a row is never launched -- the hierarchy takes the launches -- so the
-// development builds (tools/kernel_regs.py) compile a subset by leaving rows out.  (The rows' order is the order
-// of the kernels in the object.)
+// plan's key, the kernel.  A key without a row is never launched -- the hierarchy takes the launches.
 struct ResidentKernel {
     const char* name;
     ResidentKey key;
@@ -17,34 +52,74 @@ struct ResidentKernel {
 };
 #define IPD_KFN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
 static const ResidentKernel RESIDENT_KERNELS[] = {
-#ifndef IPD_DEV_ONLY_RES16   // (development: the metric's instantiations alone)
     {"k_resident_big<4,2,true>", ResidentKey::mask(4, 2, true), IPD_KFN(k_resident_big<4, 2, true>)},
     {"k_resident_big<8,2,true>", ResidentKey::mask(8, 2, true), IPD_KFN(k_resident_big<8, 2, true>)},
     {"k_resident_big<16,1,false>", ResidentKey::mask(16, 1, false), IPD_KFN(k_resident_big<16, 1, false>)},
     {"k_resident_big<32,1,false>", ResidentKey::mask(32, 1, false), IPD_KFN(k_resident_big<32, 1, false>)},
-#endif
-#ifndef IPD_DEV_ONLY_BIG   // (... or the mask-form kernels alone)
     {"k_resident<16,16,0,true>", ResidentKey::k(16, 0, true), IPD_KFN(k_resident<16, 16, 0, true>)},
-#ifndef IPD_DEV_ONLY_RES16
     {"k_resident<4,4,0>", ResidentKey::k(4, 0, false), IPD_KFN(k_resident<4, 4, 0, false>)},
     {"k_resident<8,8,0>", ResidentKey::k(8, 0, false), IPD_KFN(k_resident<8, 8, 0, false>)},
-#endif
     {"k_resident<16,16,0>", ResidentKey::k(16, 0, false), IPD_KFN(k_resident<16, 16, 0, false>)},
-#ifndef IPD_DEV_ONLY_RES16
     {"k_resident<4,4,1>", ResidentKey::k(4, 1, false), IPD_KFN(k_resident<4, 4, 1, false>)},
     {"k_resident<8,8,1>", ResidentKey::k(8, 1, false), IPD_KFN(k_resident<8, 8, 1, false>)},
     {"k_resident<4,4,4>", ResidentKey::k(4, 4, false), IPD_KFN(k_resident<4, 4, 4, false>)},
     {"k_resident<4,4,8>", ResidentKey::k(4, 8, false), IPD_KFN(k_resident<4, 4, 8, false>)},
     {"k_resident<8,8,4>", ResidentKey::k(8, 4, false), IPD_KFN(k_resident<8, 8, 4, false>)},
     {"k_resident<8,8,8>", ResidentKey::k(8, 8, false), IPD_KFN(k_resident<8, 8, 8, false>)},
-#endif
-#endif
 };
 #undef IPD_KFN
 static const ResidentKernel* resident_kernel(const ResidentKey& key) {
     for (const ResidentKernel& k : RESIDENT_KERNELS)
         if (k.key == key) return &k;
     return nullptr;
+}
+
+// ---- the checks a plan's execution launches ---------------------------------------------------
+// *bad != 0 unless the level 1 <-> 2 transfers have the bigraph form P = [W; I] (AMG/transfer.m:19-25)
+// entry for entry: every row of P' (level-2 row c) ends with the identity entry (column nf + c, value
+// 1) and row nf + c of P is that identity entry alone.  The kernel then adds the identity parts
+// itself: a 1025-entry row of P' is two 512-entry trips instead of three, and the C rows of P cost
+// no trip at all.
+__global__ void k_res_check_ident(int nf, int N2, ResCsr P, ResCsr Pt, int* __restrict__ bad) {
+    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < N2; c += gridDim.x * blockDim.x) {
+        const int e1 = Pt.rp[c + 1], p0 = P.rp[nf + c];
+        const bool ok = e1 > Pt.rp[c] && Pt.ci[e1 - 1] == nf + c && Pt.va[e1 - 1] == 1.0 &&
+                        P.rp[nf + c + 1] - p0 == 1 && P.ci[p0] == c && P.va[p0] == 1.0;
+        if (!ok) atomicOr(bad, 1);
+    }
+}
+
+// rho of the mask-form transfers and the check of P against W(j,i) = s_ij beta_i rho_j (one wave per F row
+// j: its row of P holds exactly the row's mask entries, in column order, each within 1e-12 of the form)
+__global__ __launch_bounds__(256) void k_res_xmask_rho(int nf, int nc, int isnsp,
+                                                       const unsigned long long* __restrict__ fbits, int nwf,
+                                                       const double* __restrict__ alpha,
+                                                       const double* __restrict__ beta,
+                                                       const double* __restrict__ diag, const int* __restrict__ prp,
+                                                       const int* __restrict__ pci, const double* __restrict__ pva,
+                                                       double* __restrict__ rho, int* __restrict__ bad) {
+    const int lane = threadIdx.x & 63;
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (j >= nf) return;
+    double sb = 0.0;
+    int cnt = 0;
+    for (int w = 0; w < nwf; ++w) {
+        const unsigned long long bits = fbits[(size_t)j * nwf + w];
+        const int i = w * 64 + lane;
+        if ((bits >> lane) & 1ull) sb += beta[i];
+        cnt += __popcll(bits);
+    }
+    sb = wave_sum(sb);
+    const double r = isnsp ? 1.0 / sb : alpha[j] / diag[j];
+    if (lane == 0) rho[j] = r;
+    bool wrong = (prp[j + 1] - prp[j]) != cnt;
+    for (int t = prp[j] + lane; t < prp[j + 1] && !wrong; t += 64) {
+        const int i = pci[t];
+        const bool bit = i >= 0 && i < nc && ((fbits[(size_t)j * nwf + (i >> 6)] >> (i & 63)) & 1ull);
+        const double ref = beta[i < nc ? i : 0] * r;
+        if (!bit || !(fabs(pva[t] - ref) <= 1e-12 * fabs(ref))) wrong = true;
+    }
+    if (wrong) atomicExch(bad, 1);
 }
 
 // ---- the pieces a plan's execution is made of -------------------------------------------------
@@ -155,8 +230,8 @@ static void commit_resident(ipd_amg* h, ResidentState& R, const ResidentPlan& p,
 
 // ---- k_resident: planned at amg_prepare_levels -------------------------------------------------
 static void prepare_resident(ipd_amg* h, CycleState* st, const std::vector<LevelShape>& shapes, const PlanSwitches& sw) {
-    ResidentState& R = st->res;
-    R.ok = false;
+    st->res = std::make_shared<ResidentState>();
+    ResidentState& R = *st->res;
     R.off = sw.no_resident;   // (remembered: the mask-form kernel is set up later, by amg_attach_maskop)
     const ResidentPlan p = plan_resident(resident_inputs(h, st, shapes), sw);
     if (p.considered && switch_on("IPD_DEBUG_LEVELS"))
@@ -276,14 +351,11 @@ struct ResidentLease {
     }
 };
 
-// Runs the whole solve (fixed_cycles == 0) or exactly fixed_cycles loop bodies on the
-// iterate in x (in: guess, out: result).  Returns false when the kernel could not be used
-// (another resident kernel is running, or a spin gave up): x is then unspecified and the
-// caller takes the multi-launch path.  `ms`: device time of the launch (HIP events), optional.
-static bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double* x, int fixed_cycles,
-                         std::vector<double>* out_host, float* ms, long long* dbg_dev = nullptr) {
+// (ipd_cycle_state.h)
+bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double* x, int fixed_cycles,
+                  std::vector<double>* out_host, float* ms, long long* dbg_dev) {
     ipd_ctx* ctx = h->ctx;
-    ResidentState& R = st->res;
+    ResidentState& R = *st->res;
     const ResidentPlan& p = R.plan;
     const int grid = p.grid();
     if (ctx->res_penalty > 0) {   // an earlier launch of this context gave up: stay on the launches for a while
@@ -360,9 +432,11 @@ static bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double
     return true;
 }
 
+bool resident_active(const CycleState* st) { return st->res->ok; }
+
 // the "resident=..." field of amg_prepare_levels' debug line
 static void print_resident_summary(std::FILE* f, const CycleState* st) {
-    std::fprintf(f, "resident=%d(G=%d,KE=%d)", (int)st->res.ok, st->res.plan.G, st->res.plan.key.ke);
+    std::fprintf(f, "resident=%d(G=%d,KE=%d)", (int)st->res->ok, st->res->plan.G, st->res->plan.key.ke);
 }
 
 // ---- the mask-form kernel: planned by amg_attach_maskop -----------------------------------------
@@ -423,7 +497,7 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
     ipd_ctx* ctx = h->ctx;
     CycleState* st = state_of(h);
     if (!st) return false;
-    ResidentState& R = st->res;
+    ResidentState& R = *st->res;
     const Level& lv = h->L[1];
     const PlanSwitches sw = read_plan_switches();
     const std::vector<LevelShape> shapes = level_shapes(h, st);
@@ -549,8 +623,8 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
 static bool amg_attach_poly2(ipd_amg* h) {
     ipd_ctx* ctx = h->ctx;
     CycleState* st = state_of(h);
-    if (!st || !st->res.ok) return false;
-    ResidentState& R = st->res;
+    if (!st || !st->res->ok) return false;
+    ResidentState& R = *st->res;
     if (!resident_takes_poly2(R.plan, resident_inputs(h, st, level_shapes(h, st)))) return false;
     const int N2 = h->L[2].A.nr;
     const int seg = RES_NMAX / 2, ld = 2 * seg + 128;
@@ -609,9 +683,9 @@ extern "C" int ipd_amg_resident_levels(const ipd_amg* h, int32_t* levels, int32_
     return ipd_guard([&] {
         IPD_REQUIRE(h, IPD_E_ARG, "NULL handle");
         const CycleState* st = h->cyc.get();
-        const bool on = st && st->res.ok;
-        if (levels) *levels = on ? st->res.plan.levels : 0;
-        if (tail_root) *tail_root = on ? st->res.plan.tail_root : 0;
+        const bool on = st && st->res->ok;
+        if (levels) *levels = on ? st->res->plan.levels : 0;
+        if (tail_root) *tail_root = on ? st->res->plan.tail_root : 0;
     });
 }
 
@@ -624,12 +698,12 @@ extern "C" int ipd_amg_resident_kernel(const ipd_amg* h, char* name, int32_t cap
     return ipd_guard([&] {
         IPD_REQUIRE(h && name && cap > 0, IPD_E_ARG, "bad argument");
         const CycleState* st = h->cyc.get();
-        const ResidentKernel* kern = st && st->res.ok ? resident_kernel(st->res.plan.key) : nullptr;
+        const ResidentKernel* kern = st && st->res->ok ? resident_kernel(st->res->plan.key) : nullptr;
         std::snprintf(name, (size_t)cap, "%s", kern ? kern->name : "");
-        if (handoffs) *handoffs = st ? st->res.last_handoffs : 0;
-        if (cycles) *cycles = st ? st->res.last_cycles : 0;
+        if (handoffs) *handoffs = st ? st->res->last_handoffs : 0;
+        if (cycles) *cycles = st ? st->res->last_cycles : 0;
         // level 1 <-> 2 transfers from the bit mask: always in the mask-form kernel, ResDesc::xm otherwise
-        if (mask_transfers) *mask_transfers = (st && st->res.ok && (st->res.mask_form() || st->res.desc.xm)) ? 1 : 0;
+        if (mask_transfers) *mask_transfers = (st && st->res->ok && (st->res->mask_form() || st->res->desc.xm)) ? 1 : 0;
     });
 }
 
@@ -637,9 +711,9 @@ extern "C" int ipd_amg_solve_mode(const ipd_amg* h, int32_t* mode, int32_t* grid
     if (!h || !mode) return IPD_E_ARG;
     const CycleState* st = h->cyc.get();
     if (!st) return IPD_E_ARG;
-    *mode = st->small_ok ? 1 : (st->res.ok ? 2 : 0);
-    if (grid) *grid = st->res.ok ? st->res.plan.grid() : (st->small_ok ? 1 : 0);
-    if (timeouts) *timeouts = st->res.timeouts;
+    *mode = st->small_ok ? 1 : (st->res->ok ? 2 : 0);
+    if (grid) *grid = st->res->ok ? st->res->plan.grid() : (st->small_ok ? 1 : 0);
+    if (timeouts) *timeouts = st->res->timeouts;
     return IPD_OK;
 }
 
@@ -650,7 +724,7 @@ extern "C" int ipd_amg_bench_resident(ipd_amg* h, const double* b_dev, double* x
         ipd_ctx* ctx = h->ctx;
         CallScope scope(ctx);
         CycleState* st = state_of(h);
-        IPD_REQUIRE(st && st->res.ok, IPD_E_ARG, "hierarchy does not run in resident mode");
+        IPD_REQUIRE(st && st->res->ok, IPD_E_ARG, "hierarchy does not run in resident mode");
         const int N = h->L[1].A.nr;
         long long* dbg = ctx->scratch->alloc<long long>(16);
         IPD_HIP(hipMemsetAsync(dbg, 0, 128, ctx->stream));

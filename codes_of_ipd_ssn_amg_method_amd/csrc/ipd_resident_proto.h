@@ -1,5 +1,4 @@
-// What the level-resident solve kernels share (included by ipd_cycle.hip only, before ipd_resident.h and
-// ipd_resident_big.h): the hand-off protocol, the wire to the tail workgroup and that workgroup itself, the
+// What the level-resident solve kernels share (device only; ipd_resident.h and ipd_resident_big.h include it): the hand-off protocol, the wire to the tail workgroup and that workgroup itself, the
 // one-row tail's PCG and the stationary iteration with its stopping rules.
 //
 // Hand-off.  The only global traffic of a resident solve is the result of each step (a half sweep, a residual,
@@ -23,6 +22,8 @@
 // they wait for it with long sleeps (res_tail_answer).  Both boxes are 2 x RES_GRAN_MAX granules by visit
 // parity; tctl[0] != 0 tells the tail workgroup that the solve is over.
 #pragma once
+
+#include "ipd_interp.h"
 
 typedef unsigned int res_v4u __attribute__((ext_vector_type(4)));
 
@@ -184,17 +185,7 @@ __device__ __forceinline__ void res_tail_workgroup(const ResTail& T, char* dyn_r
                                                    double* red, double* blkpart, int* stat) {
     const int tid = threadIdx.x, w = tid >> 6;
     SolveDesc* LD = sol_load_image(T.sub, dyn_raw);
-    SolveCtx c;
-    c.D = LD;
-    c.lds = lds;
-    c.red = red;
-    c.xs = reinterpret_cast<double*>(dyn_raw);
-    c.swapmask = 0;
-    c.zeromask = 0;
-    c.part = blkpart;
-    c.sumr = blkpart + 48;
-    c.dbg = nullptr;
-    c.bm_lds = 0;
+    SolveCtx c = sol_ctx(LD, lds, red, blkpart, dyn_raw, nullptr);
     if (T.tail_bm && LD->bm_bytes) {   // one block-wide level's operator into LDS for the whole solve (SolveDesc::bm_src)
         const uint4* src = reinterpret_cast<const uint4*>(LD->bm_src);
         uint4* dst = reinterpret_cast<uint4*>(dyn_raw + LD->bm_off);

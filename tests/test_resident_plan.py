@@ -29,17 +29,14 @@ def spelled(big, a, b, flag):
 
 
 def resident_table():
-    """The rows of RESIDENT_KERNELS that a build without any IPD_DEV_ONLY_* macro compiles, as a list of
-    (name, name spelled from the row's key, name spelled from the row's kernel).  The only conditionals the table
-    may contain are #ifndef IPD_DEV_ONLY_* ... #endif, whose lines such a build keeps."""
+    """The rows of RESIDENT_KERNELS as a list of (name, name spelled from the row's key, name spelled from the
+    row's kernel).  The table contains no conditionals: every row is compiled."""
     text = open(os.path.join(CSRC, "ipd_resident_host.h")).read()
     start = text.index("static const ResidentKernel RESIDENT_KERNELS[] = {")
     rows = []
     for line in text[start:text.index("\n};", start)].splitlines()[1:]:
         t = line.strip()
-        if t.startswith("#"):
-            assert re.fullmatch(r"#ifndef IPD_DEV_ONLY_\w+(\s*//.*)?|#endif", t), ("unexpected conditional", t)
-            continue
+        assert not t.startswith("#"), ("unexpected conditional", t)
         m = re.fullmatch(r'\{"([^"]+)", ResidentKey::(k|mask)\((\d+), (\d+), (true|false)\), '
                          r'IPD_KFN\((k_resident(?:_big)?)<([^>]*)>\)\},', t)
         assert m, ("unexpected row", t)

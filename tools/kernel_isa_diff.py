@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Compares the gfx950 kernels of two builds (no GPU needed): for every kernel symbol the sequence of instruction
+encodings of a plain llvm-objdump -d, and the register / scratch / LDS figures of tools/kernel_regs.py.  Addresses
+and file offsets are not compared, so a kernel may sit in another object, or at another place in it.
+  python tools/kernel_isa_diff.py --a FILE [FILE ...] --b FILE [FILE ...] [--out REPORT]
+FILE: object files or libipdamg.so.  Exit status 1 when a kernel is missing on one side or differs."""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_regs import LLVM, code_objects, kernel_rows  # noqa: E402
+
+
+def demangle(names):
+    out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
+    return dict(zip(names, out))
+
+
+def kernel_code(paths, kernels):
+    """mangled kernel symbol -> its bodies (a template that two units instantiate has one in each), sorted; a body
+    is a list of instruction encodings"""
+    code = {}
+    for path in paths:
+        for co in code_objects(path):
+            with tempfile.NamedTemporaryFile(suffix=".co") as f:
+                f.write(co)
+                f.flush()
+                txt = subprocess.run([LLVM + "/llvm-objdump", "-d", f.name], capture_output=True, text=True).stdout
+            sym = None
+            for line in txt.split("\n"):
+                m = re.match(r"[0-9a-f]+ <(\S+)>:$", line)
+                if m:
+                    # (labels inside a kernel carry no symbol of their own in these objects: a new symbol is a new function)
+                    sym = m.group(1)
+                    if sym in kernels:
+                        code.setdefault(sym, []).append([])
+                    continue
+                m = re.search(r"// [0-9A-F]+: ((?:[0-9A-F]{8} ?)+)$", line)
+                if m and sym in code:
+                    code[sym][-1].append(m.group(1).strip())
+    for bodies in code.values():   # the filler behind a function's last instruction (s_nop 0, s_code_end: up to the
+        for b in bodies:           # next function's alignment, or to the end of the section) is not its code
+            while b and b[-1] in ("BF800000", "BF9F0000"):
+                b.pop()
+    return {s: sorted(b) for s, b in code.items()}
+
+
+def kernel_symbols(paths):
+    syms = set()
+    for path in paths:
+        for co in code_objects(path):
+            with tempfile.NamedTemporaryFile(suffix=".co") as f:
+                f.write(co)
+                f.flush()
+                txt = subprocess.run([LLVM + "/llvm-readelf", "--notes", f.name], capture_output=True, text=True).stdout
+            syms.update(re.findall(r"\.name:\s+(\S+)", txt))
+    return syms
+
+
+def figures(paths):
+    rows = {}
+    for dem, fig in kernel_rows(paths):
+        rows.setdefault(dem, []).append(fig)
+    return {d: sorted(f) for d, f in rows.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--a", nargs="+", required=True)
+    ap.add_argument("--b", nargs="+", required=True)
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    ka, kb = kernel_symbols(args.a), kernel_symbols(args.b)
+    ca, cb = kernel_code(args.a, ka), kernel_code(args.b, kb)
+    ra, rb = figures(args.a), figures(args.b)
+    names = demangle(sorted(ka | kb))
+    lines, bad = [], 0
+    for sym in sorted(ka | kb, key=lambda s: names[s]):
+        dem = names[sym].replace("(anonymous namespace)", "{anonymous}").split("(")[0]
+        if sym in ka and sym in kb and (sym not in ca or sym not in cb):
+            lines.append("%-72s NO CODE FOUND IN %s" % (dem[-72:], "a" if sym not in ca else "b"))
+            bad += 1
+            continue
+        if sym not in ka or sym not in kb:
+            lines.append("%-72s ONLY IN %s" % (dem[-72:], "a" if sym in ka else "b"))
+            bad += 1
+            continue
+        na, nb = [len(b) for b in ca[sym]], [len(b) for b in cb[sym]]
+        if ca[sym] == cb[sym] and min(na) > 0 and ra.get(dem) == rb.get(dem):
+            lines.append("%-72s identical  %6d instructions  %s%s" % (dem[-72:], na[0], ra[dem][0],
+                                                                      "  (x%d)" % len(na) if len(na) > 1 else ""))
+        else:
+            bad += 1
+            lines.append("%-72s DIFFERS    %s -> %s instructions (%+d)" % (dem[-72:], na, nb, sum(nb) - sum(na)))
+            lines.append("    a: %s" % "; ".join(ra.get(dem, [])))
+            lines.append("    b: %s" % "; ".join(rb.get(dem, [])))
+    head = ["a: " + " ".join(args.a), "b: " + " ".join(args.b),
+            "%d kernels in a, %d in b, %d in both; %d missing or different" % (len(ka), len(kb), len(ka & kb), bad), ""]
+    text = "\n".join(head + lines) + "\n"
+    if args.out:
+        open(args.out, "w").write(text)
+    sys.stdout.write(text if not args.out else "\n".join(head) + "\n")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

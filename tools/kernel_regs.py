@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Register / scratch figures of the gfx950 kernels in an object file or in libipdamg.so (no GPU needed):
-splits the clang offload bundle out of the .hip_fatbin section and reads the kernels' metadata notes.
-  python tools/kernel_regs.py [FILE] [NAME-SUBSTRING ...]      (default FILE: csrc/build/ipd_cycle.o)"""
+"""Register / scratch figures of the gfx950 kernels in object files or in libipdamg.so (no GPU needed):
+splits the clang offload bundles out of the .hip_fatbin section and reads the kernels' metadata notes.
+  python tools/kernel_regs.py [FILE ...] [NAME-SUBSTRING ...]      (default FILE: libipdamg.so)"""
 import os
 import re
 import struct
@@ -31,27 +31,33 @@ def code_objects(path):
     return out
 
 
+def kernel_rows(paths):
+    """(demangled kernel name without arguments, figures) of every gfx950 kernel in the files"""
+    rows = []
+    for path in paths:
+        for co in code_objects(path):
+            with tempfile.NamedTemporaryFile(suffix=".co") as f:
+                f.write(co)
+                f.flush()
+                txt = subprocess.run([LLVM + "/llvm-readelf", "--notes", f.name], capture_output=True, text=True).stdout
+            for blk in re.split(r"\n\s+- \.agpr_count", txt)[1:]:
+                name = re.search(r"\.name:\s+(\S+)", blk)
+                if not name:
+                    continue
+                dem = subprocess.run(["c++filt", name.group(1)], capture_output=True, text=True).stdout.strip()
+                g = lambda k: (re.search(r"\.%s:\s+(\d+)" % k, blk) or [0, "?"])[1]
+                rows.append((dem.replace("(anonymous namespace)", "{anonymous}").split("(")[0], "vgpr %3s spill %3s sgpr_spill %3s scratch %4s B lds %6s" % (
+                    g("vgpr_count"), g("vgpr_spill_count"), g("sgpr_spill_count"),
+                    g("private_segment_fixed_size"), g("group_segment_fixed_size"))))
+    return rows
+
+
 def main():
-    path = sys.argv[1] if len(sys.argv) > 1 and os.path.exists(sys.argv[1]) else os.path.join(
-        ROOT, "codes_of_ipd_ssn_amg_method_amd", "csrc", "build", "ipd_cycle.o")
-    pats = [a for a in sys.argv[1:] if a != path]
-    for co in code_objects(path):
-        with tempfile.NamedTemporaryFile(suffix=".co") as f:
-            f.write(co)
-            f.flush()
-            txt = subprocess.run([LLVM + "/llvm-readelf", "--notes", f.name], capture_output=True, text=True).stdout
-        for blk in re.split(r"\n\s+- \.agpr_count", txt)[1:]:
-            name = re.search(r"\.name:\s+(\S+)", blk)
-            if not name:
-                continue
-            dem = subprocess.run(["c++filt", name.group(1)], capture_output=True, text=True).stdout.strip()
-            dem = dem.split("(")[0]
-            if pats and not any(p in dem for p in pats):
-                continue
-            g = lambda k: (re.search(r"\.%s:\s+(\d+)" % k, blk) or [0, "?"])[1]
-            print("%-60s vgpr %3s spill %3s sgpr_spill %3s scratch %4s B lds %6s" % (
-                dem[-60:], g("vgpr_count"), g("vgpr_spill_count"), g("sgpr_spill_count"),
-                g("private_segment_fixed_size"), g("group_segment_fixed_size")))
+    paths = [a for a in sys.argv[1:] if os.path.exists(a)]
+    pats = [a for a in sys.argv[1:] if a not in paths]
+    for dem, figures in kernel_rows(paths or [os.path.join(ROOT, "codes_of_ipd_ssn_amg_method_amd", "libipdamg.so")]):
+        if not pats or any(p in dem for p in pats):
+            print("%-60s %s" % (dem[-60:], figures))
 
 
 if __name__ == "__main__":
