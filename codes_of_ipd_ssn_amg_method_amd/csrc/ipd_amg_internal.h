@@ -104,7 +104,7 @@ ipd_amg* amg_setup(ipd_ctx* ctx, const Csr& A, const AmgOpts& o, ipd_rng* rng,
                    const std::shared_ptr<ipd_amg>& donor = nullptr);
 int amg_coarsest_threshold(int N);
 
-// ipd_cycle.hip
+// ipd_cycle.hip (amg_attach_maskop: ipd_resident_host.hip; amg_pcg_small_ok, amg_pcg_small_launch: ipd_small.hip)
 void amg_prepare_levels(ipd_amg* h);  // dinv, Axi, xx, work vectors
 void amg_cycle(ipd_amg* h, int k, int isnsp, bool wcycle, bool keep_e);
 bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int m, int n, double tk,

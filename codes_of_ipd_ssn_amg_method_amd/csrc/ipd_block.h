@@ -599,7 +599,7 @@ struct BlockRun {
     ipd_ctx* ctx;
     BlockState* bs;
 
-    void sweep(int k, bool post) {   // launch_sweep (ipd_cycle_host.h), CSR form
+    void sweep(int k, bool post) {   // launch_sweep (ipd_cycle.hip), CSR form
         const BlockLevel& bl = bs->lv[(size_t)k];
         BlockVecs& v = bs->v[(size_t)k];
         BlkSmoothArgs a;
@@ -655,7 +655,7 @@ struct BlockRun {
             BLK_GO(k_blk_xfer, W, staged, m.grid, dyn, a);
     }
 
-    // amg_cycle (ipd_cycle_host.h): A_k e = r_k on the block; keep_e: start from the current e
+    // amg_cycle (ipd_cycle.hip): A_k e = r_k on the block; keep_e: start from the current e
     void cycle(int k, bool wc, bool keep_e) {
         const BlockLevel& bl = bs->lv[(size_t)k];
         BlockVecs& v = bs->v[(size_t)k];

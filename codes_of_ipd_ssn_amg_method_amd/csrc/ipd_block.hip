@@ -1,7 +1,7 @@
 // Several right-hand sides through one hierarchy: the solve phase of Class_AMG (Class_AMG.m:86-109)
 // for every column of B at once, each column as if it were solved alone.
 //
-// The cycle is the launch-path amg_cycle (ipd_cycle_host.h) with every vector widened to a block of
+// The cycle is the launch-path amg_cycle (ipd_cycle.hip) with every vector widened to a block of
 // W columns, W in {1, 2, 4, 8}: N x W row-major ("row-interleaved"), so the column index of one
 // matrix entry fetches W contiguous doubles, and each matrix entry is read once per row walk for all
 // W columns.  A launch of these kernels is bound by its dependent round trips, not its bytes

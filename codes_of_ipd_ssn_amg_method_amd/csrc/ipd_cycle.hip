@@ -19,14 +19,11 @@
 //    short rows do not idle a wave and long rows still fill the chip.
 // Solve-phase results differ from the oracle only by summation order: tests
 // compare residual histories to 1e-10.
-#include "ipd_amg_internal.h"
+#include "ipd_cycle_state.h"
 
-#include <chrono>
 #include <cmath>
-#include <condition_variable>
-#include <mutex>
 
-#include "ipd_interp.h"   // and ipd_cycle_args.h, ipd_cycle_pcg.h, ipd_cycle_phases.h, ipd_cycle_dev.h
+#include "ipd_cycle_pcg.h"
 
 // Dynamic LDS = the staged gather vector (N doubles) when STAGED, else nothing.
 template <bool STAGED, bool PAD>
@@ -90,14 +87,6 @@ __device__ __forceinline__ void pad_build_rows(int vb, int nvb, int N, int S, co
         }
         if (lane == 0) diag[r] = hasd ? va[dpos] : 0.0;
     }
-}
-__global__ __launch_bounds__(256) void k_pad_build(int N, int S, const int* __restrict__ rp,
-                                                   const int* __restrict__ ci,
-                                                   const double* __restrict__ va,
-                                                   unsigned short* __restrict__ pci,
-                                                   double* __restrict__ pva,
-                                                   double* __restrict__ diag) {
-    pad_build_rows(blockIdx.x, gridDim.x, N, S, rp, ci, va, pci, pva, diag);
 }
 // the padded copies of all the levels of a hierarchy in one launch (blockIdx.y = entry)
 constexpr int PAD_BATCH = 8;
@@ -534,6 +523,17 @@ __global__ __launch_bounds__(256) void k_maskop_build(int N, int nf, const int* 
     }
 }
 
+__global__ void k_maskop_scales(int nf, int nc, const double* __restrict__ p,
+                                const double* __restrict__ q, double itk,
+                                double* __restrict__ alpha, double* __restrict__ beta) {
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nf + nc; t += gridDim.x * blockDim.x) {
+        if (t < nf)
+            alpha[t] = q[t] * q[t] * itk;
+        else
+            beta[t - nf] = p[t - nf] * p[t - nf];
+    }
+}
+
 // One half (F rows or C rows) of the bigraph Gauss-Seidel sweep, same arithmetic as
 // phase_smooth (SmoothArgs semantics) with the row sums taken from the bit mask.  A wave owns
 // a row; lane l walks 16 bits of word l/4; the operand half vector is staged pre-scaled.
@@ -617,805 +617,895 @@ __global__ __launch_bounds__(BT) void k_smooth_mask(const SmoothArgs a, const Ma
     }
 }
 
-struct PackEntry {
-    const void* src;
-    unsigned dst_off, bytes;  // multiples of 4
+// All levels of a hierarchy in two launches instead of two per level (the hierarchy is rebuilt at every
+// Newton step): workgroup b of k_levels_prepare belongs to the level whose block range holds b, workgroup
+// k of k_levels_sum adds A*1 of level k in k_vec_sum's order (same bits).
+constexpr int PREP_ML = 24;
+struct PrepLevels {
+    int n;
+    int first_block[PREP_ML + 1];
+    int N[PREP_ML], nf[PREP_ML];
+    const int* rp[PREP_ML];
+    const int* ci[PREP_ML];
+    const double* va[PREP_ML];
+    double* dinv[PREP_ML];
+    double* Axi[PREP_ML];
+    double* xx[PREP_ML];
+    int* maxoff[PREP_ML];
 };
-// compact copy of a block-wide polynomial operator (column-major, gld rows per column) with ld rows per column
-// (SolveDesc::bm_src): one workgroup per column
-// (the last workgroup copies the vector W behind the columns)
-__global__ __launch_bounds__(128) void k_bm_compact(const double* __restrict__ src, int gld, double* __restrict__ dst,
-                                                    int ld, const double* __restrict__ W, int rows) {
-    const int c = blockIdx.x, r = threadIdx.x;
-    if (c == (int)gridDim.x - 1) {
-        if (r < ld) dst[(size_t)c * ld + r] = r < rows ? W[r] : 0.0;
-        return;
-    }
-    if (r < ld) dst[(size_t)c * ld + r] = src[(size_t)c * gld + r];
-}
-// gathers the constant arrays of the cached levels into the image (one workgroup per array)
-__global__ __launch_bounds__(256) void k_pack_image(const PackEntry* __restrict__ ents,
-                                                    char* __restrict__ img) {
-    const PackEntry e = ents[blockIdx.x];
-    const int* src = reinterpret_cast<const int*>(e.src);
-    int* dst = reinterpret_cast<int*>(img + e.dst_off);
-    for (unsigned i = threadIdx.x; i < e.bytes / 4; i += 256) dst[i] = src[i];
-}
-
-struct DenseEntry {
-    const int* rp;
-    const int* ci;
-    const double* va;
-    int rows, cols;
-    unsigned dst_off;
-    int ld_row;   // 0: column-major; > 0: row-major with this leading dimension (dense thread-per-row levels)
-};
-// dense column-major copies of the tiny levels' operators (one workgroup per matrix)
-__global__ __launch_bounds__(256) void k_pack_dense(const DenseEntry* __restrict__ ents,
-                                                    char* __restrict__ img) {
-    const DenseEntry e = ents[blockIdx.x];
-    double* dst = reinterpret_cast<double*>(img + e.dst_off);
-    const int total = e.ld_row ? e.rows * e.ld_row : e.rows * e.cols;
-    for (int t = threadIdx.x; t < total; t += 256) dst[t] = 0.0;
-    __syncthreads();
-    for (int r = threadIdx.x; r < e.rows; r += 256)
-        for (int t = e.rp[r]; t < e.rp[r + 1]; ++t) {
-            if (e.ld_row) dst[(size_t)r * e.ld_row + e.ci[t]] = e.va[t];
-            else dst[r + (size_t)e.ci[t] * e.rows] = e.va[t];
-        }
-}
-
-// Lane map of a thread-per-row level (see blk_sweeps): one workgroup per level.
-struct LmapEntry {
-    const int* rp;
-    int N;
-    unsigned off;
-};
-__global__ __launch_bounds__(BT) void k_pack_lmap(const LmapEntry* __restrict__ ents, char* __restrict__ img) {
-    __shared__ int wsum[BT / 64];
-    __shared__ int cnt[5], base[5];
-    const LmapEntry e = ents[blockIdx.x];
-    unsigned* map = reinterpret_cast<unsigned*>(img + e.off);
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int len = t < e.N ? e.rp[t + 1] - e.rp[t] : 0;
-    auto block_sum = [&](int v) {
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        __syncthreads();
-        if (lane == 0) wsum[wv] = v;
-        __syncthreads();
-        int s = 0;
-        for (int w = 0; w < BT / 64; ++w) s += wsum[w];
-        return s;
-    };
-    auto block_max = [&](int v) {
-        for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-        __syncthreads();
-        if (lane == 0) wsum[wv] = v;
-        __syncthreads();
-        int s = 0;
-        for (int w = 0; w < BT / 64; ++w) s = max(s, wsum[w]);
-        return s;
-    };
-    const int maxlen = block_max(len);
-    int E = 2, need = 0;
-    for (;; E <<= 1) {
-        int n = 1;
-        while (n < 16 && n * E < len) n <<= 1;
-        need = t < e.N ? n : 0;
-        if (block_sum(need) <= BT || E >= (1 << 20)) break;   // (uniform)
-    }
-    int lg = 0;
-    while ((1 << lg) < need) ++lg;
-    if (t < 5) cnt[t] = 0;
-    map[t] = 0u;
-    __syncthreads();
-    // rank of the row among the rows of its class, in row order
-    int rank = 0;
-    for (int c = 0; c < 5; ++c) {
-        const bool mine = t < e.N && lg == c;
-        const unsigned long long b = __ballot(mine);
-        const int before = __popcll(b & ((1ull << lane) - 1ull));
-        __syncthreads();
-        if (lane == 0) wsum[wv] = __popcll(b);
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int w = 0; w < BT / 64; ++w) {
-            if (w < wv) woff += wsum[w];
-            tot += wsum[w];
-        }
-        if (mine) rank = woff + before;
-        if (t == 0) cnt[c] = tot;
-    }
-    __syncthreads();
-    if (t == 0) {   // classes by descending group size: every group is aligned to its size
-        int off = 0;
-        for (int c = 4; c >= 0; --c) {
-            base[c] = off;
-            off += cnt[c] << c;
-        }
-        map[BT] = (E <= 16 && maxlen <= 16 * E) ? (unsigned)E : 0u;
-    }
-    __syncthreads();
-    if (t < e.N) {
-        const int b0 = base[lg] + (rank << lg);
-        for (int s = 0; s < (1 << lg); ++s)
-            map[b0 + s] = (unsigned)t | ((unsigned)s << 10) | ((unsigned)lg << 14) | (1u << 31);
-    }
-}
-
-// Polynomial form of a one-wave level (see poly_pre / poly_post): one workgroup per level forms
-//   Rg = R + u 1', u = (1 - R A1) / xx (isnsp) or 0 ;  S = I - Rg A ;  M1 = S^nu ;
-//   M2 = sum_{j<nu} S^j Rg = M2a + w 1'  with  M2a = sum S^j R ,  w = sum S^j u
-//   T1 = P'A ;  Mr = [M2a; P' - T1 M2a] ;  W = [w; -T1 w] ;  Me = [M1; -T1 M1] ;  Mc = M1 P
-// with dense column-major matrices in LDS and writes Mr, Me, Mc, W into the image.  The rank-one part
-// w 1' stays apart because u ~ 1/xx is large (xx = 1'A1 ~ N bk1): added into every entry of M2 it
-// would cost the cancellation inside 1'r that the sweeps' own xig = 1'g enjoys (MG_Vcycle.m:17).
-struct PolyEntry {
-    const int *Arp, *Aci;
-    const double* Ava;
-    const int *Prp, *Pci;   // P  : N x Nc  (CSR)
-    const double* Pva;
-    const double* dinv;
-    const double* Axi;
-    const double* xx;
-    int N, Nc, nu, isnsp, LD;
-    unsigned offMr, offMe, offMc, offW;
-};
-__global__ __launch_bounds__(BT) void k_pack_poly(const PolyEntry* __restrict__ ents, char* __restrict__ img) {
-    extern __shared__ __attribute__((aligned(16))) char poly_raw[];
-    const PolyEntry e = ents[blockIdx.x];
-    const int N = e.N, Nc = e.Nc, R = N + Nc, LD = e.LD, t = threadIdx.x;
-    const int N8 = (N + 7) / 8 * 8, Nc8 = (Nc + 7) / 8 * 8;
-    double* A = reinterpret_cast<double*>(poly_raw);   // N x N, column-major like everything here
-    double* S = A + N * N;
-    double* M1 = S + N * N;
-    double* M2 = M1 + N * N;                            // M2a
-    double* T = M2 + N * N;                             // product scratch
-    double* P = T + N * N;                              // N x Nc
-    double* T1 = P + N * Nc;                            // Nc x N
-    double* u = T1 + Nc * N;                            // N
-    double* dv = u + N;                                 // N
-    double* w = dv + N;                                 // N
-    double* w2 = w + N;                                 // N
-    for (int i = t; i < N * N; i += BT) A[i] = 0.0;
-    for (int i = t; i < N * Nc; i += BT) P[i] = 0.0;
-    __syncthreads();
-    for (int r = t; r < N; r += BT) {
-        for (int q = e.Arp[r]; q < e.Arp[r + 1]; ++q) A[r + e.Aci[q] * N] = e.Ava[q];
-        for (int q = e.Prp[r]; q < e.Prp[r + 1]; ++q) P[r + e.Pci[q] * N] = e.Pva[q];
-        const double d = e.dinv[r];
-        dv[r] = d;
-        u[r] = e.isnsp ? (1.0 - d * e.Axi[r]) / e.xx[0] : 0.0;
-        w[r] = 0.0;
-    }
-    __syncthreads();
-    // S = I - Rg A,  (Rg A)[i][j] = dinv_i A[i][j] + u_i (1'A)_j ;  M1 = I ;  M2a = 0 ;  w = 0
-    for (int q = t; q < N * N; q += BT) {
-        const int i = q % N, j = q / N;
-        double cs = 0.0;
-        for (int k = 0; k < N; ++k) cs += A[k + j * N];
-        S[q] = (i == j ? 1.0 : 0.0) - (dv[i] * A[q] + u[i] * cs);
-        M1[q] = i == j ? 1.0 : 0.0;
-        M2[q] = 0.0;
-    }
-    __syncthreads();
-    for (int s = 0; s < e.nu; ++s) {
-        // M2a <- R + S M2a ;  w <- u + S w ;  M1 <- S M1     (results parked: all read the old values)
-        for (int q = t; q < 2 * N * N + N; q += BT) {
-            if (q >= 2 * N * N) {
-                const int i = q - 2 * N * N;
-                double acc = 0.0;
-                for (int k = 0; k < N; ++k) acc += S[i + k * N] * w[k];
-                w2[i] = u[i] + acc;
-                continue;
-            }
-            const bool second = q >= N * N;
-            const int qq = second ? q - N * N : q;
-            const int i = qq % N, j = qq / N;
-            const double* B = second ? M1 : M2;
-            double acc = 0.0;
-            for (int k = 0; k < N; ++k) acc += S[i + k * N] * B[k + j * N];
-            if (second)
-                T[qq] = acc;
-            else
-                A[qq] = acc + (i == j ? dv[i] : 0.0);   // A is rebuilt below; until then: second scratch
-        }
-        __syncthreads();
-        for (int q = t; q < N * N; q += BT) {
-            M1[q] = T[q];
-            M2[q] = A[q];
-        }
-        for (int i = t; i < N; i += BT) w[i] = w2[i];
-        __syncthreads();
-    }
-    // A again (it was scratch), then T1 = P'A
-    for (int i = t; i < N * N; i += BT) A[i] = 0.0;
-    __syncthreads();
-    for (int r = t; r < N; r += BT)
-        for (int q = e.Arp[r]; q < e.Arp[r + 1]; ++q) A[r + e.Aci[q] * N] = e.Ava[q];
-    __syncthreads();
-    for (int q = t; q < Nc * N; q += BT) {
-        const int c = q % Nc, j = q / Nc;
-        double acc = 0.0;
-        for (int k = 0; k < N; ++k) acc += P[k + c * N] * A[k + j * N];
-        T1[q] = acc;
-    }
-    __syncthreads();
-    double* Mr = reinterpret_cast<double*>(img + e.offMr);
-    double* Me = reinterpret_cast<double*>(img + e.offMe);
-    double* Mc = reinterpret_cast<double*>(img + e.offMc);
-    double* W = reinterpret_cast<double*>(img + e.offW);
-    for (int q = t; q < LD * N8; q += BT) {
-        const int row = q % LD, j = q / LD;
-        double vr = 0.0, ve = 0.0;
-        if (j < N && row < N) {
-            vr = M2[row + j * N];
-            ve = M1[row + j * N];
-        } else if (j < N && row < R) {
-            const int c = row - N;
-            double a2 = 0.0, a1 = 0.0;
-            for (int k = 0; k < N; ++k) {
-                a2 += T1[c + k * Nc] * M2[k + j * N];
-                a1 += T1[c + k * Nc] * M1[k + j * N];
-            }
-            vr = P[j + c * N] - a2;
-            ve = -a1;
-        }
-        Mr[q] = vr;
-        Me[q] = ve;
-    }
-    for (int q = t; q < LD * Nc8; q += BT) {
-        const int i = q % LD, c = q / LD;
-        double acc = 0.0;
-        if (i < N && c < Nc)
-            for (int k = 0; k < N; ++k) acc += M1[i + k * N] * P[k + c * N];
-        Mc[q] = acc;
-    }
-    for (int row = t; row < LD; row += BT) {
-        double v = 0.0;
-        if (row < N) {
-            v = w[row];
-        } else if (row < R) {
-            const int c = row - N;
-            for (int k = 0; k < N; ++k) v += T1[c + k * Nc] * w[k];
-            v = -v;
-        }
-        W[row] = v;
-    }
-}
-
-// Block-wide polynomial form of a 33..144-row level (SolveLevel::gM): the recurrences of k_pack_poly
-// as dense products on the f64 matrix cores.  All operands live in global scratch, column-major, padded
-// with zeros to multiples of 16 (Np rows; no edge cases in the tiles).  M1 = S^nu by nu - 1 products
-// S^j = S S^(j-1); their running sum I + S + ... + S^(nu-1) gives M2a (columns scaled by D^-1) and w
-// (applied to u).  Y = [sum | S^nu | w, 15 zero columns] is one matrix of 2 Np + 16 columns, so that the
-// rows below N of the output are one more product, T1 Y.  One wave per 16 x 16 tile
-// (v_mfma_f64_16x16x4_f64: lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; result
-// register g of lane l is C[(l >> 4) + 4 g][l & 15]), the operand loads of 64 k in flight.
-struct BPolyEntry {
-    const int* Arp;
-    const int* Aci;
-    const double* Ava;
-    const int* Prp;
-    const int* Pci;
-    const double* Pva;
-    const double* dinv;
-    const double* Axi;
-    const double* xx;
-    int N, Nc, Np, Ncp, nu, isnsp, LD;
-    double* A;    // Np x Np
-    double* S;    // Np x Np
-    double* P;    // Np x Ncp
-    double* T1;   // Ncp x Np = P'A
-    double* Pw[2]; // Np x Np: the powers of S, ping-pong
-    double* Y;     // Np x (2 Np + 16): [I + S + ... + S^(nu-1) | S^nu | w, 15 zero columns]
-    double* dv;
-    double* u;
-    double* cs;   // column sums of A
-    double* M;    // out: [Mr | Me | Mc], LD rows, 8-padded column counts (zeroed by the host)
-    double* W;    // out: LD
-    // out, instead of M: row-major [N + Nc][RES_P3_LD] with Mr in columns 0..N-1, Me in 512..512+N-1
-    // and Mc in 1024..1024+Nc-1 (the resident kernels' third level: a thread holds entries t, 512 + t
-    // and 1024 + t of its workgroup's rows, ipd_resident.h POLY3); W then has N + Nc entries
-    double* rows;
-    int rows_seg;   // segment length of that layout: 512 (k_resident, Mc at most 128 columns) or RB_P3_SEG
-    int rows_ld;    // its row stride
-};
-typedef double bp_d4 __attribute__((ext_vector_type(4)));
-// (the k index of MFMA u in a group of four is k0 + 4 (l >> 4) + u, not k0 + 4 u + (l >> 4): a lane's four
-// B values are then 32 contiguous bytes and the four lanes of a column share one 128-byte line -- with
-// the natural order every load touched sixteen lines for 32 bytes each and a product of 288^3 took 14 us)
-// One tile per WORKGROUP: wave w takes the 16-k groups w, w + 4, ... (a product is a chain of dependent
-// batches of loads otherwise: 288 / 64 = 5 round trips to L2), the four partial tiles are added in wave
-// order through LDS; the sum is returned to wave 0 only.
-__device__ __forceinline__ bp_d4 bp_tile(const double* __restrict__ A, int a_is, int a_ks,
-                                         const double* __restrict__ B, int b_ks, int b_js, int K, int I0, int J0) {
-    typedef double bp_v2 __attribute__((ext_vector_type(2)));
-    __shared__ double bp_part[3][4][64];
-    const int l = threadIdx.x & 63, r = l & 15, q = l >> 4, wv = threadIdx.x >> 6;
-    const double* ap = A + (size_t)(I0 + r) * a_is + (size_t)(4 * q) * a_ks;
-    const double* bp = B + (size_t)(4 * q) * b_ks + (size_t)(J0 + r) * b_js;   // b_ks == 1
-    bp_d4 c = {0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < K; k0 += 256) {
-        double a[16], b[16];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int k = k0 + 16 * (4 * g + wv);
-            const bool in = k < K;   // uniform (K is a multiple of 16)
-            if (in) {
-                const bp_v2 b01 = *reinterpret_cast<const bp_v2*>(bp + k);
-                const bp_v2 b23 = *reinterpret_cast<const bp_v2*>(bp + k + 2);
-                b[4 * g] = b01.x;
-                b[4 * g + 1] = b01.y;
-                b[4 * g + 2] = b23.x;
-                b[4 * g + 3] = b23.y;
-                if (a_ks == 1) {
-                    const bp_v2 a01 = *reinterpret_cast<const bp_v2*>(ap + k);
-                    const bp_v2 a23 = *reinterpret_cast<const bp_v2*>(ap + k + 2);
-                    a[4 * g] = a01.x;
-                    a[4 * g + 1] = a01.y;
-                    a[4 * g + 2] = a23.x;
-                    a[4 * g + 3] = a23.y;
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) a[4 * g + u] = ap[(size_t)(k + u) * a_ks];
-                }
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) a[4 * g + u] = b[4 * g + u] = 0.0;
+__global__ void k_levels_prepare(const PrepLevels P) {
+    int k = 0;
+    while (k + 1 < P.n && (int)blockIdx.x >= P.first_block[k + 1]) ++k;
+    const int nb = P.first_block[k + 1] - P.first_block[k], lb = blockIdx.x - P.first_block[k];
+    const int N = P.N[k], nf = P.nf[k];
+    const int* __restrict__ rp = P.rp[k];
+    const int* __restrict__ ci = P.ci[k];
+    const double* __restrict__ va = P.va[k];
+    const int lane = threadIdx.x & 63;
+    const int wave = (lb * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (nb * blockDim.x) >> 6;
+    int longest = 0;
+    for (int r = wave; r < N; r += nwaves) {
+        double s = 0.0, dg = 0.0;
+        int hasd = 0;
+        for (int t = rp[r] + lane; t < rp[r + 1]; t += 64) {
+            s += va[t];
+            if (ci[t] == r) {
+                dg = va[t];
+                hasd = 1;
             }
         }
-#pragma unroll
-        for (int u = 0; u < 16; ++u)
-            if (k0 + 16 * (4 * (u / 4) + wv) < K) c = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], c, 0, 0, 0);
+        s = wave_sum(s);
+        dg = wave_sum(dg);
+        hasd = __any(hasd) ? 1 : 0;
+        longest = max(longest, rp[r + 1] - rp[r] - hasd);
+        if (lane == 0) {
+            P.Axi[k][r] = s;
+            P.dinv[k][r] = nf > 0 ? 1.0 / dg : 0.5 * (1.0 / dg);
+        }
     }
-    if (wv > 0) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bp_part[wv - 1][g][l] = c[g];
-    }
+    // one atomic per workgroup (one per wave on one address cost 35 of the kernel's 41 us)
+    __shared__ int bmax;
+    if (threadIdx.x == 0) bmax = 0;
     __syncthreads();
-    if (wv == 0) {
-#pragma unroll
-        for (int ww = 0; ww < 3; ++ww)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) c[g] += bp_part[ww][g][l];
-    }
-    return c;
+    if (lane == 0 && longest > 0) atomicMax(&bmax, longest);
+    __syncthreads();
+    if (threadIdx.x == 0 && bmax > 0) atomicMax(P.maxoff[k], bmax);
 }
-// dense copies of A and P, D^-1, u, and the parts of the state after the first sweep that are not S:
-// M2a = D^-1, w = u
-__global__ __launch_bounds__(256) void k_bpoly_scatter(const BPolyEntry e) {   // one wave per row
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, Np = e.Np;
-    if (r >= e.N) return;
-    for (int q = e.Arp[r] + lane; q < e.Arp[r + 1]; q += 64) e.A[r + (size_t)e.Aci[q] * Np] = e.Ava[q];
-    for (int q = e.Prp[r] + lane; q < e.Prp[r + 1]; q += 64) e.P[r + (size_t)e.Pci[q] * Np] = e.Pva[q];
-    if (lane == 0) {
-        const double d = e.dinv[r];
-        const double ui = e.isnsp ? (1.0 - d * e.Axi[r]) / e.xx[0] : 0.0;
-        e.dv[r] = d;
-        e.u[r] = ui;
-        if (e.nu == 1) e.Y[r + (size_t)(2 * Np) * Np] = ui;   // w = u
-    }
-}
-__global__ __launch_bounds__(256) void k_bpoly_colsum(const BPolyEntry e) {   // one wave per column
-    const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (j >= e.N) return;
-    const double* aj = e.A + (size_t)j * e.Np;
-    double cs = 0.0;
-    for (int k = lane; k < e.N; k += 64) cs += aj[k];
-    cs = wave_sum(cs);
-    if (lane == 0) e.cs[j] = cs;
-}
-// S = I - Rg A with (Rg A)[i][j] = dinv_i A[i][j] + u_i (1'A)_j, the first power and the sum so far
-// (blocks below nS: one thread per entry); T1 = P'A (the tiles behind)
-__global__ __launch_bounds__(256) void k_bpoly_S_T1(const BPolyEntry e, int nS) {
-    const int N = e.N, Np = e.Np;
-    if ((int)blockIdx.x < nS) {
-        const int q = blockIdx.x * 256 + threadIdx.x;
-        if (q >= N * N) return;
-        const int i = q % N, j = q / N;
-        const size_t at = i + (size_t)j * Np;
-        const double id = i == j ? 1.0 : 0.0;
-        const double sv = id - (e.dv[i] * e.A[at] + e.u[i] * e.cs[j]);
-        e.S[at] = sv;
-        e.Pw[0][at] = sv;
-        e.Y[at] = e.nu >= 2 ? id + sv : id;
-        if (e.nu == 1) e.Y[at + (size_t)Np * Np] = sv;
-        return;
-    }
-    const int tile = (int)blockIdx.x - nS, ni = e.Ncp / 16;
-    const int I0 = 16 * (tile % ni), J0 = 16 * (tile / ni), l = threadIdx.x & 63;
-    const bp_d4 c = bp_tile(e.P, Np, 1, e.A, 1, Np, Np, I0, J0);   // A-operand (c, k) = P[k + c Np]
-    if (threadIdx.x >= 64) return;
-    for (int g = 0; g < 4; ++g) e.T1[(I0 + (l >> 4) + 4 * g) + (size_t)(J0 + (l & 15)) * e.Ncp] = c[g];
-}
-// S^s = S S^(s-1) (s = 2 .. nu; the last one lands in Y's second block), added to the sum while s < nu;
-// beside the last product: w = (I + ... + S^(nu-1)) u, one wave per row
-__global__ __launch_bounds__(256) void k_bpoly_step(const BPolyEntry e, int s, int src, int nT) {
-    const int Np = e.Np, ni = Np / 16, l = threadIdx.x & 63;
-    if ((int)blockIdx.x >= nT) {
-        const int i = ((int)blockIdx.x - nT) * 4 + (threadIdx.x >> 6);
-        if (i >= e.N) return;
-        double acc = 0.0;
-        for (int j = l; j < e.N; j += 64) acc += e.Y[i + (size_t)j * Np] * e.u[j];
-        acc = wave_sum(acc);
-        if (l == 0) e.Y[i + (size_t)(2 * Np) * Np] = acc;
-        return;
-    }
-    const int tile = blockIdx.x;
-    const int I0 = 16 * (tile % ni), J0 = 16 * (tile / ni);
-    const bp_d4 c = bp_tile(e.S, 1, Np, e.Pw[src], 1, Np, Np, I0, J0);
-    if (threadIdx.x >= 64) return;
-    double* dst = s == e.nu ? e.Y + (size_t)Np * Np : e.Pw[src ^ 1];
-    const int j = J0 + (l & 15);
-    for (int g = 0; g < 4; ++g) {
-        const size_t at = (size_t)(I0 + (l >> 4) + 4 * g) + (size_t)j * Np;
-        dst[at] = c[g];
-        if (s < e.nu) e.Y[at] += c[g];
-    }
-}
-// the stacked output: rows below N from -T1 Y (+ P' in the Mr block), Mc = M1 P, copies above
-__global__ __launch_bounds__(256) void k_bpoly_final(const BPolyEntry e, int nZ, int nC) {
-    const int N = e.N, Nc = e.Nc, Np = e.Np, Ncp = e.Ncp, LD = e.LD, l = threadIdx.x & 63;
-    const int N8 = (N + 7) / 8 * 8;
-    const double* Y = e.Y;
-    auto put = [&](int row, bool me, int j, double v) {
-        if (e.rows)
-            e.rows[(size_t)row * e.rows_ld + (me ? e.rows_seg : 0) + j] = v;
-        else
-            e.M[row + (size_t)((me ? N8 : 0) + j) * LD] = v;
-    };
-    int blk = blockIdx.x;
-    if (blk < nZ) {   // Z = T1 Y: Ncp x (2 Np + 16)
-        const int ni = Ncp / 16, tile = blk;
-        const int I0 = 16 * (tile % ni), J0 = 16 * (tile / ni);
-        const bp_d4 c = bp_tile(e.T1, 1, Ncp, Y, 1, Np, Np, I0, J0);
-        if (threadIdx.x >= 64) return;
-        const int j = J0 + (l & 15);
-        for (int g = 0; g < 4; ++g) {
-            const int cc = I0 + (l >> 4) + 4 * g;
-            if (cc >= Nc) continue;
-            if (j < Np) {
-                if (j < N) put(N + cc, false, j, e.P[j + (size_t)cc * Np] - c[g] * e.dv[j]);
-            } else if (j < 2 * Np) {
-                if (j - Np < N) put(N + cc, true, j - Np, -c[g]);
-            } else if (j == 2 * Np) {
-                e.W[N + cc] = -c[g];
-            }
-        }
-        return;
-    }
-    blk -= nZ;
-    if (blk < nC) {   // Mc = M1 P: Np x Ncp
-        const int ni = Np / 16, tile = blk;
-        const int I0 = 16 * (tile % ni), J0 = 16 * (tile / ni);
-        const bp_d4 c = bp_tile(Y + (size_t)Np * Np, 1, Np, e.P, 1, Np, Np, I0, J0);
-        if (threadIdx.x >= 64) return;
-        const int j = J0 + (l & 15);
-        for (int g = 0; g < 4; ++g) {
-            const int i = I0 + (l >> 4) + 4 * g;
-            if (i < N && j < Nc) {
-                if (e.rows)
-                    e.rows[(size_t)i * e.rows_ld + 2 * e.rows_seg + j] = c[g];
-                else
-                    e.M[i + (size_t)(2 * N8 + j) * LD] = c[g];
-            }
-        }
-        return;
-    }
-    blk -= nC;
-    const int q = blk * 256 + threadIdx.x;   // copies: M2a = sum D^-1, M1, w
-    if (q < N * N) {
-        const int i = q % N, j = q / N;
-        put(i, false, j, Y[i + (size_t)j * Np] * e.dv[j]);
-        put(i, true, j, Y[i + (size_t)(Np + j) * Np]);
-    } else if (q < N * N + N) {
-        const int i = q - N * N;
-        e.W[i] = Y[i + (size_t)(2 * Np) * Np];
-    }
-}
-
-// Level 2 of the resident kernel, composed over a whole visit (ResDesc::p2rows; pack_bpoly in its row layout
-// has run): B = M1 M2a + M2a into the Me segment of the rows (tiles below nT), wB = M1 w + w into W (one wave
-// per row behind).  M1 = Y's second block, M2a = Y's first block with columns scaled by D^-1, w = Y's column 2 Np.
-__global__ __launch_bounds__(256) void k_bpoly_compose(const BPolyEntry e, int nT) {
-    const int N = e.N, Np = e.Np, l = threadIdx.x & 63;
-    const double* Y = e.Y;
-    if ((int)blockIdx.x >= nT) {
-        const int i = ((int)blockIdx.x - nT) * 4 + (threadIdx.x >> 6);
-        if (i >= N) return;
-        double acc = 0.0;
-        for (int j = l; j < N; j += 64) acc += Y[i + (size_t)(Np + j) * Np] * Y[j + (size_t)(2 * Np) * Np];
-        acc = wave_sum(acc);
-        if (l == 0) e.W[i] = acc + Y[i + (size_t)(2 * Np) * Np];
-        return;
-    }
-    const int ni = Np / 16, tile = blockIdx.x;
-    const int I0 = 16 * (tile % ni), J0 = 16 * (tile / ni);
-    const bp_d4 c = bp_tile(Y + (size_t)Np * Np, 1, Np, Y, 1, Np, Np, I0, J0);
-    if (threadIdx.x >= 64) return;
-    const int j = J0 + (l & 15);
-    for (int g = 0; g < 4; ++g) {
-        const int i = I0 + (l >> 4) + 4 * g;
-        if (i < N && j < N)
-            e.rows[(size_t)i * e.rows_ld + e.rows_seg + j] = (c[g] + Y[i + (size_t)j * Np]) * e.dv[j];
-    }
-}
-
-// out[0] = it, out[1] = rel_res, out[2] = res0; rel_resk at out[4 ..], rhok at out[4+maxit+2 ..]
-// fixed_cycles > 0: run exactly that many loop bodies without the stopping rules (bench hook)
-template <bool CACHED>
-__global__ __launch_bounds__(BT) void k_solve_small(const SolveDesc* __restrict__ D_global,
-                                                    const double* __restrict__ b, double* xa,
-                                                    double* xb, double* hist, double* out,
-                                                    int fixed_cycles) {
-    __shared__ PhaseLds lds;
+__global__ __launch_bounds__(BT) void k_levels_sum(const PrepLevels P) {
     __shared__ double red[16];
-    __shared__ double blkpart[48 + SOLVE_ML + 1];
-    extern __shared__ __attribute__((aligned(16))) char dyn_raw[];
-    // dynamic LDS: [ staging vector | descriptor copy | cached levels ]
-    const SolveDesc* D = D_global;
-    SolveDesc* LD = nullptr;
-    if (CACHED) LD = sol_load_image(D_global, dyn_raw);
-    // without cached levels the descriptor stays in global memory: its (uniform) fields
-    // are then fetched with scalar loads and live in SGPRs instead of VGPRs
-    SolveCtx c = sol_ctx(CACHED ? LD : D_global, &lds, red, blkpart, dyn_raw, nullptr);
-    D = c.D;
-    const int N = D->L[1].lv.N;
-    const int maxit = D->maxit;
-    double* const x_home = xa;
-    double* relk = out + 4;
-    double* rhok = out + 4 + (maxit + 2);
-    sol_top(c, b, xa, nullptr, xb, hist, 1);                              // Class_AMG.m:89
-    {
-        double* t = xa;
-        xa = xb;
-        xb = t;
+    const int k = blockIdx.x;
+    const double* v = P.Axi[k];
+    double s = 0.0;
+    for (int t = threadIdx.x; t < P.N[k]; t += BT) s += v[t];
+    const double tot = block_sum(s, red);
+    if (threadIdx.x == 0) P.xx[k][0] = tot;
+}
+
+// Builds the padded off-diagonal copy of width S (pad_width, ipd_launch_plan.h; 0: none)
+static void pad_flush(ipd_ctx* ctx, PadBatch* b) {
+    if (b->n == 0) return;
+    int rows = 1;
+    for (int q = 0; q < b->n; ++q) rows = std::max(rows, b->N[q]);
+    hipLaunchKernelGGL(k_pad_build_batch, dim3(std::max(1, std::min(cdiv(rows, 4), 4096)), b->n), dim3(256), 0,
+                       ctx->stream, *b);
+    IPD_KERNEL_CHECK();
+    b->n = 0;
+}
+static void build_padded(ipd_ctx* ctx, Arena& ar, const Csr& A, int S, LevelDev* dev, PadBatch* batch) {
+    dev->pci = nullptr;
+    dev->pva = nullptr;
+    dev->diag = nullptr;
+    if (S == 0) return;
+    unsigned short* pci = ar.alloc<unsigned short>((size_t)A.nr * S);
+    double* pva = ar.alloc<double>((size_t)A.nr * S);
+    double* diag = ar.alloc<double>((size_t)A.nr);
+    {   // (launched with the other levels' copies: pad_flush)
+        if (batch->n == PAD_BATCH) pad_flush(ctx, batch);
+        const int q = batch->n++;
+        batch->N[q] = A.nr;
+        batch->S[q] = S;
+        batch->rp[q] = A.rp;
+        batch->ci[q] = A.ci;
+        batch->va[q] = A.va;
+        batch->pci[q] = pci;
+        batch->pva[q] = pva;
+        batch->diag[q] = diag;
     }
-    const double res0 = hist[0];
+    dev->pci = pci;
+    dev->pva = pva;
+    dev->diag = diag;
+}
+
+// a batch of one (ipd_cycle_state.h)
+void build_padded_private(ipd_amg* h, const Csr& A, int S, LevelDev* dev) {
+    PadBatch one;
+    build_padded(h->ctx, *h->arena, A, S, dev, &one);
+    pad_flush(h->ctx, &one);
+}
+
+// The planners' switches, read at the call in which they take effect (amg_prepare_levels, amg_attach_maskop): the
+// one place that reads them
+PlanSwitches read_plan_switches() {
+    PlanSwitches s;
+    s.no_pad = switch_on("IPD_NO_PAD");
+    s.no_stage = switch_on("IPD_NO_STAGE");
+    s.no_rrc = switch_on("IPD_NO_RRC");
+    s.no_poly = switch_on("IPD_NO_POLY");
+    s.no_blk = switch_on("IPD_NO_BLK");
+    s.no_bpoly = switch_on("IPD_NO_BPOLY");
+    s.no_blkdense = switch_on("IPD_NO_BLKDENSE");
+    s.no_small = switch_on("IPD_NO_SMALL");
+    s.no_subcycle = switch_on("IPD_NO_SUBCYCLE");
+    s.no_resident = switch_on("IPD_NO_RESIDENT");
+    s.no_resident_remote = switch_on("IPD_NO_RESIDENT_REMOTE");
+    s.no_resident_three = switch_on("IPD_NO_RESIDENT_THREE");
+    s.no_resident_deep = switch_on("IPD_NO_RESIDENT_DEEP");
+    s.no_resident_big = switch_on("IPD_NO_RESIDENT_BIG");
+    s.no_res_poly4 = switch_on("IPD_NO_RES_POLY4");
+    s.resident_big = switch_on("IPD_RESIDENT_BIG");
+    s.maskop = switch_on("IPD_MASKOP");
+    if (const char* e = switch_value("IPD_RESIDENT_G")) s.resident_g = std::atoi(e);
+    if (const char* e = switch_value("IPD_RESIDENT_RANKS")) s.resident_ranks = std::atoi(e);
+    if (const char* e = switch_value("IPD_RES_PRESLEEP")) s.res_presleep = std::max(0, std::atoi(e));
+    if (const char* e = switch_value("IPD_RES_DEBUG_SKIP_PUBLISH")) s.res_skip_publish = (unsigned)std::max(0, std::atoi(e));
+    return s;
+}
+
+// the levels as the planners look at them (ipd_cycle_state.h)
+std::vector<LevelShape> level_shapes(const ipd_amg* h, const CycleState* st) {
+    std::vector<LevelShape> shapes((size_t)h->J + 1);
+    for (int k = 1; k <= h->J; ++k) {
+        const Level& lv = h->L[k];
+        LevelShape& s = shapes[(size_t)k];
+        s.nr = lv.A.nr;
+        s.nnz = lv.A.nnz;
+        s.nf = lv.nf;
+        s.maxoff = st->run[(size_t)k].maxoff;
+        s.p_nnz = k >= 2 ? lv.P.nnz : 0;
+    }
+    return shapes;
+}
+
+// launches the batch of levels and starts a new one (a hierarchy of more than PREP_ML levels takes several)
+static void prep_flush(ipd_ctx* ctx, PrepLevels* p) {
+    if (p->n == 0) return;
+    hipLaunchKernelGGL(k_levels_prepare, dim3(p->first_block[p->n]), dim3(256), 0, ctx->stream, *p);
+    IPD_KERNEL_CHECK();
+    hipLaunchKernelGGL(k_levels_sum, dim3(p->n), dim3(BT), 0, ctx->stream, *p);
+    IPD_KERNEL_CHECK();
+    p->n = 0;
+}
+// Per-level vectors and constants (k_levels_prepare), the launch plan of every level and the padded copies
+// it asks for: st->run[k].plan, st->run[k].dev
+static void prepare_level_runs(ipd_amg* h, CycleState* st, const LaunchSwitches& sw) {
+    ipd_ctx* ctx = h->ctx;
+    Arena& ar = *h->arena;
+    // first pass: per-level vectors and the longest off-diagonal row of every level (one
+    // readback for all levels), then the launch plan, second pass: padded copies and launch geometry
+    int* maxoff = zeroed<int>(ctx, (size_t)h->J + 1);
+    // levels whose constant data come from the donor hierarchy (see ipd_amg::donor)
+    const ipd_amg* donor = h->donor.get();
+    const CycleState* dst_ = donor ? donor->cyc.get() : nullptr;
+    auto shared_level = [&](int k) { return dst_ && k <= 2 && k <= donor->J; };
+    PrepLevels prep;
+    prep.n = 0;
+    prep.first_block[0] = 0;
+    for (int k = 1; k <= h->J; ++k) {
+        Level& lv = h->L[k];
+        const int N = lv.A.nr;
+        lv.N = N;
+        lv.nf = (k == 1 && h->opts.bigph) ? (int)h->opts.fnode : 0;
+        IPD_REQUIRE(lv.nf < N, IPD_E_ARG, "fnode must be smaller than the matrix size");
+        const Level* dl = shared_level(k) ? &donor->L[k] : nullptr;
+        lv.dinv = dl ? dl->dinv : ar.alloc<double>((size_t)N);
+        lv.Axi = dl ? dl->Axi : ar.alloc<double>((size_t)N);
+        lv.xx = dl ? dl->xx : ar.alloc<double>(1);
+        lv.r = ar.alloc<double>((size_t)N);
+        lv.e = ar.alloc<double>((size_t)N);
+        lv.e2 = ar.alloc<double>((size_t)N);
+        lv.w = ar.alloc<double>((size_t)N);
+        lv.rr = ar.alloc<double>((size_t)N);
+        if (dl) continue;
+        if (prep.n == PREP_ML) prep_flush(ctx, &prep);
+        const int q = prep.n++;
+        prep.N[q] = N;
+        prep.nf[q] = lv.nf;
+        prep.rp[q] = lv.A.rp;
+        prep.ci[q] = lv.A.ci;
+        prep.va[q] = lv.A.va;
+        prep.dinv[q] = lv.dinv;
+        prep.Axi[q] = lv.Axi;
+        prep.xx[q] = lv.xx;
+        prep.maxoff[q] = maxoff + k;
+        prep.first_block[q + 1] = prep.first_block[q] + std::max(1, std::min(cdiv(N, 16), 4096));
+    }
+    prep_flush(ctx, &prep);
+    std::vector<int> hmax((size_t)h->J + 1);
+    ctx->fetch(maxoff, hmax.data(), (size_t)h->J + 1);
+    std::vector<LaunchShape> shapes((size_t)h->J + 1);
+    for (int k = 1; k <= h->J; ++k) {
+        const Level& lv = h->L[k];
+        LaunchShape& s = shapes[(size_t)k] = LaunchShape{lv.A.nr, lv.A.nnz, lv.nf, hmax[(size_t)k]};
+        if (k == h->J) break;
+        const Level& cl = h->L[k + 1];
+        s.Pt = MatShape{cl.Pt.nr, cl.Pt.nc, cl.Pt.nnz};
+        s.P = MatShape{cl.P.nr, cl.P.nc, cl.P.nnz};
+        s.t1 = cl.T1.rp != nullptr;
+        s.T1 = MatShape{cl.T1.nr, cl.T1.nc, cl.T1.nnz};
+    }
+    LaunchLevel dplan[3];   // the donor's records: its padded copy goes with its geometry
+    int dlevels = 0;
+    for (int k = 1; k <= 2 && shared_level(k); ++k) dplan[dlevels = k] = dst_->run[(size_t)k].plan;
+    const std::vector<LaunchLevel> plan = plan_launches(shapes.data(), h->J, ctx->num_cu, sw, dplan, dlevels);
+    PadBatch pads;   // the levels' padded copies: one launch after the loop
+    for (int k = 1; k <= h->J; ++k) {
+        Level& lv = h->L[k];
+        LevelRun& rn = st->run[(size_t)k];
+        rn.plan = plan[(size_t)k];
+        rn.dev.N = lv.N;
+        rn.dev.nf = lv.nf;
+        rn.dev.S = rn.plan.S;
+        rn.dev.L = rn.plan.L;
+        rn.dev.G = rn.plan.G;
+        rn.dev.rp = lv.A.rp;
+        rn.dev.ci = lv.A.ci;
+        rn.dev.va = lv.A.va;
+        rn.dev.dinv = lv.dinv;
+        rn.dev.Axi = lv.Axi;
+        rn.dev.xx = lv.xx;
+        rn.dev.r = lv.r;
+        rn.dev.rr = lv.rr;
+        if (shared_level(k)) {
+            const LevelDev& dd = dst_->run[(size_t)k].dev;
+            rn.dev.pci = dd.pci;
+            rn.dev.pva = dd.pva;
+            rn.dev.diag = dd.diag;
+        } else {
+            build_padded(ctx, ar, lv.A, rn.plan.S, &rn.dev, &pads);
+            rn.maxoff = hmax[(size_t)k];
+        }
+    }
+    pad_flush(ctx, &pads);
+}
+
+// Restriction / prolongation arguments of the launches, the coarsest level's PCG, the solve's vectors
+static void prepare_transfers(ipd_amg* h, CycleState* st) {
+    Arena& ar = *h->arena;
+    auto xfer = [](const Csr& m, const XferPlan& xp, const double* x, double* y, int add) {
+        // nrows, ncols, L, G, row0, row1, rp, ci, va, x, y, add, staged
+        return XferArgs{m.nr, m.nc, xp.L, xp.G, 0, m.nr, m.rp, m.ci, m.va, x, y, add, xp.staged ? 1 : 0};
+    };
+    for (int k = 1; k < h->J; ++k) {
+        Level& fine = h->L[k];
+        Level& coarse = h->L[k + 1];
+        LevelRun& rn = st->run[(size_t)k];
+        // restriction: rows of P' (coarse rows), gathers the fine residual
+        rn.restrict_args = xfer(coarse.Pt, rn.plan.rest, fine.rr, coarse.r, 0);
+        // prolongation: rows of P (fine rows), gathers the coarse correction
+        rn.prolong_args = xfer(coarse.P, rn.plan.prol, coarse.e, fine.e, 1);
+    }
+    {   // coarsest level: PCG(A,r) with the 2-argument defaults (PCG.m:18-23)
+        Level& cl = h->L[h->J];
+        PcgArgs a;
+        a.N = cl.A.nr;
+        a.L = st->run[(size_t)h->J].plan.pcg_L;
+        a.rp = cl.A.rp;
+        a.ci = cl.A.ci;
+        a.va = cl.A.va;
+        a.rhs = cl.r;
+        a.guess = nullptr;
+        a.d = cl.e;
+        a.work = ar.alloc<double>(4 * (size_t)cl.A.nr);
+        a.tol = 1e-11;
+        a.maxit = h->opts.pcg_maxit;
+        a.precd = 2;
+        a.out = nullptr;
+        a.nresk = 0;
+        st->run[(size_t)h->J].pcg = a;
+    }
+    st->num_cu = h->ctx->num_cu;
+    st->hist = ar.alloc<double>(8);
+    st->x2 = ar.alloc<double>((size_t)h->L[1].A.nr);
+    h->x = ar.alloc<double>((size_t)h->L[1].A.nr);
+    h->b = ar.alloc<double>((size_t)h->L[1].A.nr);
+}
+
+static const char* const IMAGE_ROLE_NAMES[] = {"solve", "sub", "sub3", "sub4", "none"};
+
+void amg_prepare_levels(ipd_amg* h) {
+    std::unique_ptr<CycleState> st(new CycleState());
+    st->run.resize((size_t)h->J + 1);
+    const PlanSwitches sw = read_plan_switches();
+    prepare_level_runs(h, st.get(), sw);
+    prepare_transfers(h, st.get());
+    // single-workgroup kernels: which levels, in which form, in which LDS images (ipd_level_plan.h)
+    const std::vector<LevelShape> shapes = level_shapes(h, st.get());
+    PlanOptions po;
+    po.cycle = h->opts.cycle;
+    po.smoth = h->opts.smoth;
+    po.twogrid = h->opts.twogrid;
+    po.concurrent_pair = h->opts.concurrent_pair;
+    const LevelPlan plan = plan_levels(shapes.data(), h->J, po, sw);
+    const bool debug = switch_on("IPD_DEBUG_LEVELS");
+    if (debug)
+        for (int k = 1; k <= h->J; ++k)
+            std::fprintf(stderr, "[ipd] launch plan: %s\n", launch_plan_line(st->run[(size_t)k].plan, k, h->J).c_str());
+    if (debug)
+        for (const ImageSpec& s : plan.images)
+            std::fprintf(stderr, "[ipd] image %s: k_lds=%d k_semi=%d k_tiny=%d k_blk=%d stage=%zu lds=%zu%s\n",
+                         IMAGE_ROLE_NAMES[s.role], s.k_lds, s.k_semi, s.k_tiny, s.k_blk, s.stage_bytes, s.lds,
+                         plan.sub5 == s.role ? " (level-5 tail)" : "");
+    ipd_ctx* ctx = h->ctx;
+    optin_small_kernels(ctx);
+    st->k_sub = plan.k_sub;
+    st->sub_semi_root = plan.sub_semi_root;
+    for (const ImageSpec& s : plan.images) pack_image(ctx, h, st.get(), shapes, plan, s);
+    if (plan.small_ok) {
+        st->solve_out = h->arena->alloc<double>(4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2));
+        st->small_ok = true;
+    }
+    st->sub5 = plan.sub5;
+    prepare_resident(h, st.get(), shapes, sw);
+    if (debug) {
+        std::fprintf(stderr, "[ipd] J=%d small=%d k_sub=%d ", h->J, (int)st->small_ok, st->k_sub);
+        print_resident_summary(stderr, st.get());
+        std::fprintf(stderr, " levels:");
+        for (int k = 1; k <= h->J; ++k) std::fprintf(stderr, " %d/%d", h->L[k].A.nr, h->L[k].A.nnz);
+        std::fprintf(stderr, "\n");
+    }
+    h->cyc = std::shared_ptr<CycleState>(st.release());
+}
+
+// ---------------------------------------------------------------------------
+// launches
+// ---------------------------------------------------------------------------
+// ---- fused-program emitter (which phases are queued: phase_is_small, ipd_launch_plan.h) -------
+void flush_fused(ipd_ctx* ctx, CycleState* st) {
+    if (st->pending.n == 0) return;
+    hipLaunchKernelGGL(k_fused, dim3(1), dim3(BT), st->pending_lds, ctx->stream, st->pending);
+    IPD_KERNEL_CHECK();
+    st->pending.n = 0;
+    st->pending_lds = 0;
+}
+
+static PhaseDesc& push_phase(ipd_ctx* ctx, CycleState* st, int type, int stage_len) {
+    if (st->pending.n == FUSED_MAX) flush_fused(ctx, st);
+    PhaseDesc& d = st->pending.d[st->pending.n++];
+    d.type = type;
+    d.pad_ = 0;
+    st->pending_lds = std::max(st->pending_lds, sizeof(double) * (size_t)stage_len);
+    return d;
+}
+
+// Runs `launch(r0, r1, grid)` over the row range `rg` of a matrix walked by L lanes per row.  Unsharded: one
+// call with the planned grid.  Sharded: this rank's slice only (its grid: the slice's own), followed by one
+// grouped RCCL all-gather of the vectors the launch produced (each rank wrote its own slice of every one of them).
+template <class F>
+static void run_rows(ipd_ctx* ctx, CycleState* st, const RowRange& rg, int L, F launch,
+                     std::initializer_list<double*> produced) {
+    flush_fused(ctx, st);  // big launch: everything queued before it must run first
+    const int G = st->shard_ranks;
+    const int lo = rg.r0, rows = rg.r1 - rg.r0;
+    if (G <= 1 || rows % G != 0 || rows < st->shard_min_rows) {  // replicated level
+        launch(rg.r0, rg.r1, rg.G);
+        return;
+    }
+    const int cnt = rows / G, grid = pick_blocks(cnt, L, st->num_cu);
+    if (st->shard_emulate) {
+        for (int vr = 0; vr < G; ++vr) launch(lo + vr * cnt, lo + (vr + 1) * cnt, grid);
+        return;
+    }
+    launch(lo + st->shard_rank * cnt, lo + (st->shard_rank + 1) * cnt, grid);
+    double* bases[4];
+    int nv = 0;
+    for (double* v : produced)
+        if (v) bases[nv++] = v + lo;
+    comm_allgather_inplace(ctx, bases, nv, cnt);
+}
+
+static void launch_smooth(ipd_ctx* ctx, const SmoothArgs& a, int grid) {
+    const size_t dyn = a.staged ? sizeof(double) * (size_t)a.lv.N : 0;
+    dispatch_staged_pad(a.staged, a.lv.S > 0, [&](auto S, auto P) {
+        hipLaunchKernelGGL((k_smooth<decltype(S)::value, decltype(P)::value>), dim3(grid), dim3(BT), decltype(S)::value ? dyn : 0, ctx->stream, a);
+    });
+    IPD_KERNEL_CHECK();
+}
+
+// a restriction or prolongation as planned: queued into the fused program or launched over its rows
+static void issue_xfer(ipd_ctx* ctx, CycleState* st, XferArgs a, const XferPlan& xp) {
+    if (xp.queued) {
+        push_phase(ctx, st, PH_XFER, a.ncols).u.x = a;
+        return;
+    }
+    const size_t dyn = a.staged ? sizeof(double) * (size_t)a.ncols : 0;
+    run_rows(ctx, st, RowRange{0, a.nrows, xp.G}, a.L,
+             [&](int r0, int r1, int grid) {
+                 a.row0 = r0;
+                 a.row1 = r1;
+                 if (a.staged)
+                     hipLaunchKernelGGL(k_xfer<true>, dim3(grid), dim3(BT), dyn, ctx->stream, a);
+                 else
+                     hipLaunchKernelGGL(k_xfer<false>, dim3(grid), dim3(BT), 0, ctx->stream, a);
+                 IPD_KERNEL_CHECK();
+             },
+             {a.y});
+}
+
+static void launch_resid(ipd_ctx* ctx, const LevelRun& rn, const double* e, int r0, int r1,
+                         int grid) {
+    const size_t dyn = rn.plan.staged ? sizeof(double) * (size_t)rn.dev.N : 0;
+    dispatch_staged_pad(rn.plan.staged, rn.dev.S > 0, [&](auto S, auto P) {
+        hipLaunchKernelGGL((k_resid<decltype(S)::value, decltype(P)::value>), dim3(grid), dim3(BT), decltype(S)::value ? dyn : 0, ctx->stream, rn.dev, e, r0, r1);
+    });
+    IPD_KERNEL_CHECK();
+}
+
+// one smoother sweep on level k: Jacobi = one launch, bigraph GS = two half launches
+void launch_sweep(ipd_amg* h, CycleState* st, int k, int isnsp, bool post) {
+    ipd_ctx* ctx = h->ctx;
+    Level& lv = h->L[k];
+    LevelRun& rn = st->run[(size_t)k];
+    SmoothArgs a;
+    a.lv = rn.dev;
+    a.eold = lv.e;
+    a.enew = lv.e2;
+    a.win = lv.w;
+    a.wout = lv.w;
+    a.isnsp = isnsp;
+    a.staged = rn.plan.staged;
+    a.eold_zero = rn.e_zero ? 1 : 0;
+    const LaunchLevel& p = rn.plan;
+    // How a range is issued: queued into the fused program (replicated on every rank), or as launches of the
+    // bit-mask kernel (level 1 with a mask operator: same two half sweeps, 1 bit per matrix entry; sharded runs
+    // give each owner its block of the half's rows -- a row range inside one half is all the kernel needs) or
+    // of the rows kernel
+    const bool mask = k == 1 && lv.nf > 0 && st->mask_ok;
+    const MaskOp& mo = st->maskop;
+    auto rows = [&](int r0, int r1, int grid) {
+        a.row0 = r0;
+        a.row1 = r1;
+        if (p.sweep_queued) {
+            push_phase(ctx, st, PH_SMOOTH, lv.N).u.s = a;
+        } else if (!mask) {
+            launch_smooth(ctx, a, grid);
+        } else {
+            const size_t dyn = sizeof(double) * 64 * (size_t)std::max(mo.nwf, mo.nwc);
+            const int nwh = (r0 < mo.nf) ? mo.nwf : mo.nwc;
+            const int mgrid = std::max(1, cdiv(r1 - r0, std::min(MASK_RW, 64 / nwh) * (BT / 64)));
+            hipLaunchKernelGGL(k_smooth_mask, dim3(mgrid), dim3(BT), dyn, ctx->stream, a, mo);
+            IPD_KERNEL_CHECK();
+        }
+    };
+    // Jacobi: one range.  Bigraph GS: the first half hands its result (wout) to the second, which updates with it
+    const HalfRanges& hr = p.sweep[post ? 1 : 0];
+    a.u0 = a.u1 = 0;
+    for (int i = 0; i < hr.n; ++i) {
+        if (i == hr.n - 1) a.wout = nullptr;
+        if (p.sweep_queued)
+            rows(hr.r[i].r0, hr.r[i].r1, 0);
+        else
+            run_rows(ctx, st, hr.r[i], a.lv.L, rows, {a.enew, a.wout});
+        a.u0 = hr.r[i].r0;
+        a.u1 = hr.r[i].r1;
+    }
+    rn.e_zero = false;
+    std::swap(lv.e, lv.e2);
+}
+
+// (ipd_cycle_state.h)
+bool build_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int m, int n, double tk, int* bad, MaskOp* out) {
+    ipd_ctx* ctx = h->ctx;
+    const Level& lv = h->L[1];
+    Arena& ar = *h->arena;
+    MaskOp mo;
+    mo.nf = n;
+    mo.nc = m;
+    mo.nwf = cdiv(m, 64);
+    mo.nwc = cdiv(n, 64);
+    unsigned long long* fb = ar.alloc<unsigned long long>((size_t)n * mo.nwf);
+    unsigned long long* cb = ar.alloc<unsigned long long>((size_t)m * mo.nwc);
+    double* alpha = ar.alloc<double>((size_t)n);
+    double* beta = ar.alloc<double>((size_t)m);
+    double* diag = ar.alloc<double>((size_t)lv.N);
+    IPD_HIP(hipMemsetAsync(fb, 0, sizeof(unsigned long long) * (size_t)n * mo.nwf, ctx->stream));
+    IPD_HIP(hipMemsetAsync(cb, 0, sizeof(unsigned long long) * (size_t)m * mo.nwc, ctx->stream));
+    IPD_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(k_maskop_scales, dim3(cdiv(lv.N, 256)), dim3(256), 0, ctx->stream, n, m, p_dev,
+                       q_dev, 1.0 / tk, alpha, beta);
+    hipLaunchKernelGGL(k_maskop_build, dim3(std::max(1, std::min(cdiv(lv.N, 4), 2048))), dim3(256), 0,
+                       ctx->stream, lv.N, n, lv.A.rp, lv.A.ci, lv.A.va, (const double*)alpha,
+                       (const double*)beta, mo.nwf, mo.nwc, fb, cb, diag, bad);
+    IPD_KERNEL_CHECK();
+    if (ctx->fetch1(bad) != 0) return false;
+    mo.fbits = fb;
+    mo.cbits = cb;
+    mo.alpha = alpha;
+    mo.beta = beta;
+    mo.diag = diag;
+    *out = mo;
+    return true;
+}
+
+// Solves A_k e = r_k approximately; r in L[k].r, result in L[k].e.
+// keep_e: start from the current L[k].e (second leg of a W cycle); otherwise the
+// start is e = 0, which is never materialised (the first sweep does not read it).
+void amg_cycle(ipd_amg* h, int k, int isnsp, bool wcycle, bool keep_e) {
+    ipd_ctx* ctx = h->ctx;
+    CycleState* st = state_of(h);
+    IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
+    Level& lv = h->L[k];
+    LevelRun& rn = st->run[(size_t)k];
+    const LaunchLevel& p = rn.plan;
+    if (st->k_sub == k) {  // everything from here down: one workgroup, LDS-resident (replicated)
+        flush_fused(ctx, st);
+        launch_subcycle(ctx, st, keep_e);
+        rn.e_zero = false;
+        return;
+    }
+    if (k == h->J) {                                   // MG_Vcycle.m:43 / MG_Wcycle.m:44
+        PcgArgs a = rn.pcg;                            // replicated on every rank
+        a.rhs = lv.r;
+        a.d = lv.e;
+        push_phase(ctx, st, PH_PCG, 0).u.p = a;
+        return;
+    }
+    const int nu = h->opts.smoth;
+    if (!keep_e) {
+        rn.e_zero = true;
+        if (nu == 0) {  // no sweep will overwrite the iterate: materialise the zero
+            flush_fused(ctx, st);
+            IPD_HIP(hipMemsetAsync(lv.e, 0, sizeof(double) * (size_t)lv.N, ctx->stream));
+            rn.e_zero = false;
+        }
+    }
+    for (int s = 0; s < nu; ++s) launch_sweep(h, st, k, isnsp, false);          // :14-25
+    XferArgs ra = rn.restrict_args;
+    if (p.rrc) {
+        // r_{k+1} = P'r - (P'A) e: one launch instead of residual + restriction           :27
+        const Csr& T1 = h->L[k + 1].T1;
+        RrcArgs rc;
+        rc.p = ra;
+        rc.p.x = lv.r;
+        rc.p.L = p.rrc_walk.L;
+        rc.rp2 = T1.rp;
+        rc.ci2 = T1.ci;
+        rc.va2 = T1.va;
+        rc.e = lv.e;
+        const bool staged = p.rrc_walk.staged;
+        const size_t dyn = staged ? 2 * sizeof(double) * (size_t)ra.ncols : 0;
+        run_rows(ctx, st, RowRange{0, ra.nrows, p.rrc_walk.G}, rc.p.L,
+                 [&](int r0, int r1, int grid) {
+                     rc.p.row0 = r0;
+                     rc.p.row1 = r1;
+                     if (staged)
+                         hipLaunchKernelGGL(k_rrc<true>, dim3(grid), dim3(BT), dyn, ctx->stream, rc);
+                     else
+                         hipLaunchKernelGGL(k_rrc<false>, dim3(grid), dim3(BT), 0, ctx->stream, rc);
+                     IPD_KERNEL_CHECK();
+                 },
+                 {ra.y});
+    } else {
+        if (p.resid_queued) {                                                           // :27
+            ResidDesc& rd = push_phase(ctx, st, PH_RESID, lv.N).u.r;
+            rd.lv = rn.dev;
+            rd.e = lv.e;
+            rd.row0 = 0;
+            rd.row1 = lv.N;
+        } else {
+            run_rows(ctx, st, RowRange{0, lv.N, p.G_all}, rn.dev.L,
+                     [&](int r0, int r1, int grid) { launch_resid(ctx, rn, lv.e, r0, r1, grid); }, {lv.rr});
+        }
+        issue_xfer(ctx, st, ra, p.rest);
+    }
+    amg_cycle(h, k + 1, isnsp, wcycle, false);                                   // :29
+    // MG_Wcycle.m:30 -- the second correction; on the coarsest level it repeats the
+    // identical zero-guess PCG solve, so it is skipped there (same bits).
+    if (wcycle && k + 1 < h->J) amg_cycle(h, k + 1, isnsp, wcycle, true);
+    XferArgs pa = rn.prolong_args;                                               // :31
+    pa.x = h->L[k + 1].e;
+    pa.y = lv.e;
+    issue_xfer(ctx, st, pa, p.prol);
+    for (int s = 0; s < nu; ++s) launch_sweep(h, st, k, isnsp, true);           // :33-41
+}
+
+void launch_top(ipd_amg* h, CycleState* st, const double* b, const double* x,
+                       const double* e, double* xnew, bool first) {
+    ipd_ctx* ctx = h->ctx;
+    LevelRun& rn = st->run[1];
+    TopArgs a;
+    a.lv = rn.dev;
+    a.b = b;
+    a.x = x;
+    a.e = e;
+    a.xnew = xnew;
+    a.staged = rn.plan.staged;
+    const size_t dyn = a.staged ? sizeof(double) * (size_t)rn.dev.N : 0;
+    if (rn.plan.top_queued) {
+        a.row0 = 0;
+        a.row1 = rn.dev.N;
+        push_phase(ctx, st, PH_TOP, rn.dev.N).u.t = a;
+    } else {
+        run_rows(ctx, st, RowRange{0, rn.dev.N, rn.plan.G_all}, rn.dev.L,
+                 [&](int r0, int r1, int grid) {
+                     a.row0 = r0;
+                     a.row1 = r1;
+                     dispatch_staged_pad(a.staged, rn.dev.S > 0, [&](auto S, auto P) {
+                         hipLaunchKernelGGL((k_top<decltype(S)::value, decltype(P)::value>), dim3(grid), dim3(BT), decltype(S)::value ? dyn : 0, ctx->stream, a);
+                     });
+                     IPD_KERNEL_CHECK();
+                 },
+                 {rn.dev.r, xnew});
+    }
+    ConvArgs ca;
+    ca.r = rn.dev.r;
+    ca.n = rn.dev.N;
+    ca.hist = st->hist;
+    ca.first = first ? 1 : 0;
+    push_phase(ctx, st, PH_CONV, 0).u.c = ca;
+    flush_fused(ctx, st);  // the loop body ends here: nothing stays queued across calls
+}
+
+// one Class_AMG loop body (Class_AMG.m:96-105): x_out = x_in + cycle(b - A x_in)
+void enqueue_loop_body(ipd_amg* h, CycleState* st, const double* b, const double* xin,
+                              double* xout) {
+    const bool wc = h->opts.cycle == 'w', vc = h->opts.cycle == 'v';
+    const double* ecorr = nullptr;
+    if (vc || wc) {
+        amg_cycle(h, 1, h->opts.isnsp, wc, false);
+        ecorr = h->L[1].e;
+    }
+    launch_top(h, st, b, xin, ecorr, xout, false);
+}
+
+static void copy_vec(ipd_ctx* ctx, double* dst, const double* src, int N) {
+    IPD_HIP(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, ctx->stream));
+}
+
+// x = the initial guess (NULL: zeros)
+static void load_guess(ipd_ctx* ctx, double* x, const double* guess_dev, int N) {
+    if (guess_dev)
+        copy_vec(ctx, x, guess_dev, N);
+    else
+        IPD_HIP(hipMemsetAsync(x, 0, sizeof(double) * (size_t)N, ctx->stream));
+}
+
+// Class_AMG.m:86-109
+void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, double* x_dev,
+                   int32_t* it_out, double* rel_res_out, double* rel_resk, double* rhok) {
+    ipd_ctx* ctx = h->ctx;
+    CycleState* st = state_of(h);
+    IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
+    const AmgOpts& o = h->opts;
+    const int N = h->L[1].A.nr;
+    double* xa = h->x;
+    double* xb = st->x2;
+    load_guess(ctx, xa, guess_dev, N);
+    // what a one-launch solve read back: iterations, last relative residual, then the two histories
+    auto deliver = [&](const std::vector<double>& out) {
+        const int its = (int)out[0];
+        if (rel_resk) std::memcpy(rel_resk, out.data() + 4, sizeof(double) * ((size_t)its + 1));
+        if (rhok) std::memcpy(rhok, out.data() + 4 + (o.maxit + 2), sizeof(double) * ((size_t)its + 1));
+        if (x_dev) copy_vec(ctx, x_dev, xa, N);
+        if (it_out) *it_out = its;
+        if (rel_res_out) *rel_res_out = out[1];
+        ctx->sync();
+    };
+    if (st->small_ok && st->shard_ranks == 1) {
+        // small hierarchy: the whole solve phase is one single-workgroup launch
+        launch_solve_small(ctx, st, b_dev, xa, 0);
+        const size_t nout = 4 + 2 * ((size_t)o.maxit + 2);
+        std::vector<double> out(nout);
+        ctx->fetch(st->solve_out, out.data(), nout);
+        deliver(out);
+        return;
+    }
+    if (resident_active(st) && st->shard_ranks == 1) {
+        // dense regime: the whole solve phase is one launch of co-resident workgroups
+        std::vector<double> out;
+        if (run_resident(h, st, b_dev, xa, 0, &out, nullptr)) {
+            deliver(out);
+            return;
+        }
+        // not usable right now: restore the initial guess and take the multi-launch path
+        load_guess(ctx, xa, guess_dev, N);
+    }
+    launch_top(h, st, b_dev, xa, nullptr, xb, true);                            // :89
+    std::swap(xa, xb);
+    double hh[5];
+    ctx->fetch(st->hist, hh, 5);
     int it = 0;
     double rel_res = 0.0;
-    if (fixed_cycles > 0) {
-        for (int cyc = 0; cyc < fixed_cycles; ++cyc) {
-            const double* ecorr = nullptr;
-            if (D->anycycle) {
-                sol_cycle(c);
-                ecorr = sol_e(c, 1);
-            }
-            sol_top(c, b, xa, ecorr, xb, hist, 0);
-            double* t = xa;
-            xa = xb;
-            xb = t;
-        }
-        it = fixed_cycles;
-        rel_res = hist[3];
-    } else if (res0 == 0.0) {                                             // :91-92
-        if (threadIdx.x == 0) {
-            relk[0] = 0.0;
-            rhok[0] = INFINITY;
-        }
+    if (hh[0] == 0.0) {                                                          // :91-92
+        if (rel_resk) rel_resk[0] = 0.0;
+        if (rhok) rhok[0] = INFINITY;
     } else {
-        it = 1;                                                           // :94
+        it = 1;                                                                  // :94
         double last_rel = 1.0;
-        if (threadIdx.x == 0) {
-            relk[0] = 1.0;
-            rhok[0] = NAN;
-        }
-        while (last_rel > D->retol && it <= maxit) {                      // :95
-            const double* ecorr = nullptr;
-            if (D->anycycle) {
-                sol_cycle(c);                                             // :96-102
-                ecorr = sol_e(c, 1);
-            }
-            sol_top(c, b, xa, ecorr, xb, hist, 0);                        // :103-105
-            double* t = xa;
-            xa = xb;
-            xb = t;
-            rel_res = hist[3];
-            const double rho = hist[4];
-            if (threadIdx.x == 0) {
-                relk[it] = rel_res;
-                rhok[it] = rho;
-            }
+        if (rel_resk) rel_resk[0] = 1.0;
+        if (rhok) rhok[0] = NAN;
+        while (last_rel > o.retol && it <= o.maxit) {                            // :95
+            enqueue_loop_body(h, st, b_dev, xa, xb);                             // :96-105
+            std::swap(xa, xb);
+            ctx->fetch(st->hist, hh, 5);
+            rel_res = hh[3];
             last_rel = rel_res;
+            if (rel_resk) rel_resk[it] = rel_res;
+            if (rhok) rhok[it] = hh[4];
             ++it;
-            if (rho > 1.0) break;                                         // :106
-            __syncthreads();  // hist is rewritten by the next conv_block
+            if (hh[4] > 1.0) break;                                              // :106
         }
-        it -= 1;                                                          // :108
+        it -= 1;                                                                 // :108
     }
-    __syncthreads();
-    if (xa != x_home)
-        for (int i = threadIdx.x; i < N; i += BT) x_home[i] = xa[i];
-    if (threadIdx.x == 0) {
-        out[0] = (double)it;
-        out[1] = rel_res;
-        out[2] = res0;
-    }
+    if (x_dev) copy_vec(ctx, x_dev, xa, N);
+    if (xa != h->x) std::swap(h->x, st->x2);  // keep h->x pointing at the current iterate
+    if (it_out) *it_out = it;
+    if (rel_res_out) *rel_res_out = rel_res;
+    ctx->sync();
 }
 
 // ---------------------------------------------------------------------------
-// whole AMG-PCG solve in ONE workgroup (ipd_amg_pcg_planned)
+// C ABI
 // ---------------------------------------------------------------------------
-// The loop of ipd_krylov.hip (PCG.m:68-87, flexible beta) run by the workgroup that k_solve_small is, on
-// the same SolveDesc / LDS image, with M(r) = sol_cycle(c) from a zero guess: one launch and one
-// read-back per solve.  The PCG's own vectors (d, r, p, q, w_old) are the hierarchy's krylov_state
-// vectors in global memory (<= 8 KB each, L2-resident): the image's LDS budget is planned to the byte
-// for the stationary solve, and five more level-1 vectors would push level 1 of the larger mode-1
-// hierarchies out of it.  The PCG keeps its own r apart from the cycle's input L[1].lv.r.
-// Reductions are block_sum's (per-thread strided partials, wave sums, the waves summed in fixed
-// order, every thread reading the same total), so the loop test is uniform and the bits repeat.
-struct PcgSmallArgs {
-    const double* e;   // right-hand side
-    double* d;         // in: initial guess, out: solution
-    double* r;         // the PCG's residual
-    double* p;
-    double* q;
-    double* w_old;
-    double tol2;       // retol^2
-    int maxit;
-    double* out;       // out[0] = it, out[1] = res, out[2] = delta_0; resk at out[4 .. 4 + maxit)
-};
-
-// p = w + beta p (p not read for the first direction), w_old = w, q = A_1 p by the level-1 row walk
-// with the gather staged in c.xs; returns the thread's share of p'q.  k_kry_dir_spmv for one workgroup.
-__device__ __forceinline__ double pcgs_dir_spmv(SolveCtx& c, const PcgSmallArgs& a,
-                                                const double* __restrict__ w, double beta,
-                                                bool have_p) {
-    const LevelDev& lv = c.D->L[1].lv;
-    double* xs = c.xs;
-    const int tid = threadIdx.x;
-    const int N = lv.N, L = lv.L, gpb = BT / L;
-    const int g = tid / L, gl = tid - g * L;
-    const bool uni = L >= 64;
-    const int niter = (N + gpb - 1) / gpb;
-    const double* po = a.p;
-    auto xlds = [&](int j) { return xs[j]; };
-    int row = uniform_if(g, uni);
-    bool valid = row < N;
-    bool owner = valid && gl == 0;
-    RowCursor rc;
-    RowBatch bt;
-    row_open<false>(lv, row, valid, owner, gl, L, rc, bt);
-    if (have_p)
-        vec_pass(N, [&](int j) { return w[j] + beta * po[j]; }, [&](int j, double v) { xs[j] = v; });
-    else
-        vec_pass(N, [&](int j) { return w[j]; }, [&](int j, double v) { xs[j] = v; });
-    __syncthreads();   // every p_old is read before an owner stores its p_new
-    double acc = 0.0;
-    for (int it = 0; it < niter; ++it) {
-        if (it > 0) {
-            row = uniform_if(it * gpb + g, uni);
-            valid = row < N;
-            owner = valid && gl == 0;
-            row_open<false>(lv, row, valid, owner, gl, L, rc, bt);
-        }
-        double s = row_finish<false>(lv, rc, bt, gl, L, xlds);
-        double dummy;
-        s = reduce_rows(s, L, false, 0.0, &dummy, c.lds);
-        if (owner) {
-            const double xo = xs[row];
-            a.p[row] = xo;
-            a.w_old[row] = w[row];
-            a.q[row] = s;                                                     // PCG.m:77
-            acc += xo * s;
-        }
-    }
-    return acc;
+extern "C" int ipd_amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev,
+                                 double* x_dev, int32_t* it, double* rel_res, double* rel_resk,
+                                 double* rhok) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && b_dev && x_dev, IPD_E_ARG, "NULL argument");
+        CallScope scope(h->ctx);
+        amg_solve_dev(h, b_dev, guess_dev, x_dev, it, rel_res, rel_resk, rhok);
+    });
 }
 
-template <bool CACHED>
-__global__ __launch_bounds__(BT) void k_pcg_small(const SolveDesc* __restrict__ D_global,
-                                                  const PcgSmallArgs a) {
-    __shared__ PhaseLds lds;
-    __shared__ double red[16];
-    __shared__ double blkpart[48 + SOLVE_ML + 1];
-    extern __shared__ __attribute__((aligned(16))) char dyn_raw[];
-    SolveDesc* LD = nullptr;
-    if (CACHED) LD = sol_load_image(D_global, dyn_raw);
-    SolveCtx c = sol_ctx(CACHED ? LD : D_global, &lds, red, blkpart, dyn_raw, nullptr);
-    const SolveDesc* D = c.D;
-    const int N = D->L[1].lv.N;
-    double* const r1 = D->L[1].lv.r;   // the cycle's input
-    {   // r = e - A_1 d0 (PCG.m:68); the walk's copy of d0 goes to p, which the first direction overwrites
-        TopArgs ta;
-        ta.lv = D->L[1].lv;
-        ta.b = a.e;
-        ta.x = a.d;
-        ta.e = nullptr;
-        ta.xnew = a.p;
-        ta.row0 = 0;
-        ta.row1 = N;
-        ta.staged = 1;
-        phase_top<true, false>(ta, 0, 1, c.lds, c.xs);
-        __syncthreads();
-    }
-    for (int i = threadIdx.x; i < N; i += BT) a.r[i] = r1[i];
-    __syncthreads();
-    sol_cycle(c);                                                             // :69
-    const double* w = sol_e(c, 1);
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < N; i += BT) acc += a.r[i] * w[i];
-    double delta = block_sum(acc, red);                                       // :70
-    const double delta0 = delta;
-    double beta = 0.0;
-    double res = sqrt(fabs(delta / delta0));
-    int it = 0;
-    while (it < a.maxit && delta > a.tol2 * delta0) {                         // :76
-        const double pq = block_sum(pcgs_dir_spmv(c, a, w, beta, it > 0), red);   // :77, :83
-        const double alpha = delta / pq;                                      // :78
-        for (int i = threadIdx.x; i < N; i += BT) {                           // :79
-            a.d[i] = a.d[i] + alpha * a.p[i];
-            const double ri = a.r[i] - alpha * a.q[i];
-            a.r[i] = ri;
-            r1[i] = ri;
+extern "C" int ipd_amg_solve(ipd_amg* h, const double* b, const double* guess, double* x,
+                             int32_t* it, double* rel_res, double* rel_resk, double* rhok) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && b && x, IPD_E_ARG, "NULL argument");
+        ipd_ctx* ctx = h->ctx;
+        CallScope scope(ctx);
+        const size_t N = (size_t)h->L[1].A.nr;
+        double* db = ctx->scratch->alloc<double>(N);
+        double* dg = nullptr;
+        double* dx = ctx->scratch->alloc<double>(N);
+        ctx->upload(db, b, N);
+        if (guess) {
+            dg = ctx->scratch->alloc<double>(N);
+            ctx->upload(dg, guess, N);
         }
-        __syncthreads();
-        sol_cycle(c);                                                         // :80
-        w = sol_e(c, 1);
-        double rw = 0.0, rwo = 0.0;
-        for (int i = threadIdx.x; i < N; i += BT) {
-            const double ri = a.r[i];
-            rw += ri * w[i];
-            rwo += ri * a.w_old[i];
-        }
-        const double dn = block_sum(rw, red);                                 // :81
-        const double s_wo = block_sum(rwo, red);
-        beta = (dn - s_wo) / delta;                                           // flexible :82
-        delta = dn;
-        ++it;                                                                 // :84
-        res = sqrt(fabs(dn / delta0));                                        // :85
-        if (threadIdx.x == 0) a.out[4 + it - 1] = res;
-    }
-    if (threadIdx.x == 0) {
-        a.out[0] = (double)it;
-        a.out[1] = res;                                                       // :88
-        a.out[2] = delta0;
-    }
+        amg_solve_dev(h, db, dg, dx, it, rel_res, rel_resk, rhok);
+        ctx->fetch(dx, x, N);
+    });
 }
 
-// Sub-cycle rooted at level k_lds >= 2 of a hierarchy whose upper levels run as multi-workgroup
-// launches: ONE workgroup, every level from the root down cached in LDS.  r_{root} is read from
-// and the correction written to the global vectors the surrounding launches use.
-__global__ __launch_bounds__(BT) void k_subcycle(const SolveDesc* __restrict__ D_global, int keep) {
-    __shared__ PhaseLds lds;
-    __shared__ double red[16];
-    __shared__ double blkpart[48 + SOLVE_ML + 1];
-    extern __shared__ __attribute__((aligned(16))) char dyn_raw[];
-    const SolveDesc* D = D_global;
-    long long* dbg = D->dbg;
-    if (dbg && threadIdx.x == 0) dbg[0] = wall_clock64();
-    SolveDesc* LD = sol_load_image(D_global, dyn_raw);
-    if (dbg && threadIdx.x == 0) dbg[1] = wall_clock64();
-    const int k0 = D->k_lds, N0 = D->L[k0].lv.N;
-    {
-        double* r = LD->L[k0].lv.r;
-        double* e = LD->L[k0].e;
-        const double* gr = D->root_r;
-        const double* ge = D->root_e;
-        for (int i = threadIdx.x; i < N0; i += BT) {
-            r[i] = gr[i];
-            if (keep) e[i] = ge[i];
-        }
+static void run_cycle_api(ipd_amg* h, const double* r, int isnsp, int k, const double* e_in,
+                          double* e_out, bool wc) {
+    IPD_REQUIRE(h && r && e_out, IPD_E_ARG, "NULL argument");
+    IPD_REQUIRE(k >= 1 && k <= h->J, IPD_E_ARG, "level k out of range");
+    ipd_ctx* ctx = h->ctx;
+    CallScope scope(ctx);
+    CycleState* st = state_of(h);
+    IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
+    Level& lv = h->L[k];
+    const size_t N = (size_t)lv.A.nr;
+    ctx->upload(lv.r, r, N);
+    LevelRun& rn = st->run[(size_t)k];
+    bool keep = false;
+    if (e_in && wc) {  // MG_Wcycle(r,isnsp,k,e): start from the caller's iterate
+        ctx->upload(lv.e, e_in, N);
+        rn.e_zero = false;
+        keep = true;
     }
-    __syncthreads();
-    SolveCtx c = sol_ctx(LD, &lds, red, blkpart, dyn_raw, dbg);
-    if (dbg && threadIdx.x == 0) {
-        dbg[4] = dbg[5] = dbg[6] = dbg[7] = 0;
-        dbg[9] = dbg[10] = dbg[11] = dbg[12] = dbg[13] = 0;
-        dbg[2] = wall_clock64();
-        dbg[8] = clock64();
-    }
-    sol_cycle(c, k0, keep != 0);
-    __syncthreads();
-    if (dbg && threadIdx.x == 0) {
-        dbg[3] = wall_clock64();
-        dbg[8] = clock64() - dbg[8];
-    }
-    const double* res = sol_e(c, k0);
-    double* ge = D->root_e;
-    for (int i = threadIdx.x; i < N0; i += BT) ge[i] = res[i];
+    amg_cycle(h, k, isnsp, wc, keep);
+    flush_fused(ctx, st);
+    ctx->fetch(h->L[k].e, e_out, N);
 }
 
-#include "ipd_resident_big.h"   // (and ipd_resident.h: the descriptors; ipd_resident_k*.hip instantiate the kernels)
-#include "ipd_cycle_host.h"
+// ---- the cycle as a preconditioner (ipd_krylov.hip) -------------------------------------
+bool amg_level1_walk(ipd_amg* h, LevelDev* lv, int* staged, int* grid) {
+    CycleState* st = state_of(h);
+    IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
+    if (st->shard_ranks > 1 && !st->shard_emulate) return false;
+    const LevelRun& rn = st->run[1];
+    *lv = rn.dev;
+    *staged = rn.plan.staged ? 1 : 0;
+    *grid = rn.plan.G_all;
+    return true;
+}
+
+// ---- the launch-path cycle's CSR forms, for the block solve (ipd_block.hip) ----------------
+bool amg_block_levels(ipd_amg* h, std::vector<BlockLevel>* out) {
+    CycleState* st = state_of(h);
+    IPD_REQUIRE(st, IPD_E_ARG, "hierarchy has no cycle state");
+    if (st->shard_ranks > 1) return false;
+    if (!out) return true;
+    auto csr_of = [](const Csr& m, int L, int grid) { return BlockCsr{m.nr, m.nc, L, grid, m.rp, m.ci, m.va}; };
+    out->assign((size_t)h->J + 1, BlockLevel{});
+    for (int k = 1; k <= h->J; ++k) {
+        const Level& lv = h->L[k];
+        const LevelRun& rn = st->run[(size_t)k];
+        BlockLevel& bl = (*out)[(size_t)k];
+        bl.N = lv.N;
+        bl.nf = lv.nf;
+        const LaunchLevel& p = rn.plan;
+        bl.A = csr_of(lv.A, p.L, p.G_all);
+        bl.sweep[0] = p.sweep[0];
+        bl.sweep[1] = p.sweep[1];
+        bl.dinv = lv.dinv;
+        bl.Axi = lv.Axi;
+        bl.xx = lv.xx;
+        if (k < h->J) {
+            const Level& cl = h->L[k + 1];
+            bl.Pt = csr_of(cl.Pt, p.rest.L, p.rest.G);
+            bl.P = csr_of(cl.P, p.prol.L, p.prol.G);
+            if (p.rrc_rule) bl.T1 = csr_of(cl.T1, p.rrc_walk.L, p.rrc_walk.G);
+        } else {
+            const PcgArgs& a = rn.pcg;
+            bl.pcg_L = a.L;
+            bl.pcg_precd = a.precd;
+            bl.pcg_tol = a.tol;
+            bl.pcg_maxit = a.maxit;
+        }
+    }
+    return true;
+}
+
+void amg_apply_cycle(ipd_amg* h) {
+    const int cyc = h->opts.cycle;
+    IPD_REQUIRE(cyc == 'v' || cyc == 'w', IPD_E_ARG, "AMG-PCG: the hierarchy's cycle must be 'v' or 'w'");
+    amg_cycle(h, 1, h->opts.isnsp, cyc == 'w', false);   // what run_cycle_api(h, r, isnsp, 1, NULL, ..) runs
+    flush_fused(h->ctx, state_of(h));
+}
+
+extern "C" int ipd_amg_vcycle(ipd_amg* h, const double* r, int isnsp, int k, double* e) {
+    return ipd_guard([&] { run_cycle_api(h, r, isnsp, k, nullptr, e, false); });
+}
+
+extern "C" int ipd_amg_wcycle(ipd_amg* h, const double* r, int isnsp, int k, const double* e_in,
+                              double* e_out) {
+    return ipd_guard([&] { run_cycle_api(h, r, isnsp, k, e_in, e_out, true); });
+}
+
+extern "C" int ipd_class_amg(ipd_ctx* ctx, const ipd_csc* A, const double* b, const double* guess,
+                             const ipd_amg_opts* o, ipd_rng* rng, double* x, int32_t* it,
+                             double* rel_res, double* rel_resk, double* rhok) {
+    ipd_amg* h = nullptr;
+    int rc = ipd_amg_setup(ctx, A, o, rng, &h);
+    if (rc != IPD_OK) return rc;
+    rc = ipd_amg_solve(h, b, guess, x, it, rel_res, rel_resk, rhok);
+    ipd_amg_destroy(h);
+    return rc;
+}
+
+extern "C" int ipd_pcg(ipd_ctx* ctx, const ipd_csc* H, const double* e, const double* guess,
+                       const ipd_pcg_opts* o, double* d, int64_t* it, double* res, double* resk) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(ctx && H && e && d, IPD_E_ARG, "NULL argument");
+        CallScope scope(ctx);
+        Arena& tmp = *ctx->scratch;
+        double tol = 1e-11;
+        long long maxit = 10000;
+        int precd = 2;  // PCG.m:24-27 defaults
+        long long nf = 0;
+        if (o) {
+            if (o->retol >= 0) tol = o->retol;
+            if (o->maxit >= 0) maxit = o->maxit;
+            if (o->precd >= 0) precd = o->precd;
+            nf = o->nf;
+        }
+        Csr hm;
+        csr_upload_from_csc(ctx, tmp, H, false, &hm);  // true rows of H
+        const size_t N = (size_t)hm.nr;
+        double* de = tmp.alloc<double>(N);
+        double* dd = tmp.alloc<double>(N);
+        double* dg = nullptr;
+        ctx->upload(de, e, N);
+        if (guess) {
+            dg = tmp.alloc<double>(N);
+            ctx->upload(dg, guess, N);
+        }
+        long long its = 0;
+        pcg_dev(ctx, hm, de, dg, tol, maxit, precd, dd, &its, res, resk, nf);
+        if (it) *it = its;
+        ctx->fetch(dd, d, N);
+    });
+}

@@ -25,7 +25,7 @@
 //
 // Always the launch-path cycle: the resident kernels (k_resident*, k_solve_small) run whole
 // Class_AMG loops and are not used here.  ipd_amg_pcg_planned (below) is the form that runs the same
-// loop as ONE single-workgroup launch (k_pcg_small, ipd_cycle.hip) on a hierarchy planned for the
+// loop as ONE single-workgroup launch (k_pcg_small, ipd_small.hip) on a hierarchy planned for the
 // single-workgroup solve, and is this file's amg_pcg_dev on every other hierarchy.
 #include "ipd_amg_internal.h"
 

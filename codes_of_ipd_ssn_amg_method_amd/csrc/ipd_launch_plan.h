@@ -1,4 +1,4 @@
-// Planner of the multi-launch path (amg_cycle, launch_top, the block solve: ipd_cycle_host.h, ipd_block.h): from
+// Planner of the multi-launch path (amg_cycle, launch_top, the block solve: ipd_cycle.hip, ipd_block.h): from
 // the shapes of the levels and of their transfers, the device's CU count and three switches it decides, once per
 // hierarchy, how every level's phases run -- lanes per row and grids of the row walks, the padded copy, LDS
 // staging, which phases are queued into the fused single-workgroup program and which are launches of their own,
@@ -69,7 +69,7 @@ static inline int pad_stride(int maxoff) { return (maxoff + 3) / 4 * 4; }
 
 // Width S of the padded off-diagonal copy of a level, 0 where it has none: the level is big and regular
 // enough (see ipd_cycle_phases.h, item 2)
-static inline int pad_width(int nr, int nnz, int maxoff /* longest off-diagonal row, from k_level_prepare */) {
+static inline int pad_width(int nr, int nnz, int maxoff /* longest off-diagonal row, from k_levels_prepare */) {
     if (nr > PAD_ROWS_MAX || nr == 0) return 0;
     const double avg_off = (double)(nnz - nr) / (double)nr;
     // small levels too: one dependent round trip less per launch (measured -6 % solve time on

@@ -2,7 +2,7 @@
 // each level's form (polynomial, block-wide polynomial, dense thread-per-row, thread-per-row, tiny
 // dense) and which LDS images are packed -- the whole solve, the sub-cycle and the images rooted at
 // levels 3 and 4 the resident kernels take -- with their LDS budget.  amg_prepare_levels packs what it
-// returns (pack_image, ipd_cycle_host.h).  What an image holds -- its pieces, their sizes and LDS offsets
+// returns (pack_image, ipd_image.hip).  What an image holds -- its pieces, their sizes and LDS offsets
 // -- is written down here once (image_layout): plan_lds sums the pieces to decide what fits, pack_image
 // binds them to the descriptor.  Host-clean, no HIP: tests/level_plan_driver.cpp runs it on the CPU.
 #pragma once

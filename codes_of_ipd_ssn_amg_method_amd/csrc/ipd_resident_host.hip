@@ -1,11 +1,17 @@
-// Host side of the resident kernels (included by ipd_cycle_host.h, after ipd_cycle_state.h has declared
-// CycleState and ResidentState, at the place of the first kernel-template launch of the translation unit): the table of
-// their instantiations, the execution of a plan (ipd_resident_plan.h decides, this file does the device work
-// the plan calls for, verifies what only the device can verify and commits it to CycleState::res), the slots
-// and the launch, the attach functions and the introspection entry points.
-#pragma once
+// Host side of the resident kernels: the table of their instantiations, the execution of a plan
+// (ipd_resident_plan.h decides, this file does the device work the plan calls for, verifies what only the device
+// can verify and commits it to CycleState::res), the slots and the launch, the attach functions and the
+// introspection entry points.  Its own kernels are the two checks; what it needs of the launch path's and the
+// image unit's kernels it gets through their host functions (ipd_cycle_state.h).
+#include "ipd_cycle_state.h"
 
-// The plan and what running it needs (opaque outside this file: ipd_cycle_state.h)
+#include <chrono>
+#include <condition_variable>
+#include <mutex>
+
+#include "ipd_resident_big.h"   // (and ipd_resident.h: the descriptors and the kernel templates; ipd_resident_k*.hip instantiate them)
+
+// The plan and what running it needs (opaque outside this unit: ipd_cycle_state.h)
 struct ResidentState {
     bool ok = false;             // a plan is active
     bool off = false;            // IPD_NO_RESIDENT=1 when the hierarchy was set up
@@ -144,22 +150,12 @@ static const SolveDesc* resident_image(const CycleState* st, ImageRole r) {
     return r == IMG_SUB || r == IMG_SUB3 || r == IMG_SUB4 ? st->img[r].desc : nullptr;
 }
 
-// level k's rows as the plan wants them: the launches' padded copy or a private one with stride p.S[k] (k_pad_build)
+// level k's rows as the plan wants them: the launches' padded copy or a private one with stride p.S[k]
 static LevelDev resident_rows(ipd_amg* h, const CycleState* st, const ResidentPlan& p, int k) {
     LevelDev d = st->run[(size_t)k].dev;
     if (!p.priv[k]) return d;
-    const Csr& A = h->L[k].A;
-    Arena& ar = *h->arena;
     d.S = p.S[k];
-    unsigned short* pci = ar.alloc<unsigned short>((size_t)A.nr * d.S);
-    double* pva = ar.alloc<double>((size_t)A.nr * d.S);
-    double* dg = ar.alloc<double>((size_t)A.nr);
-    hipLaunchKernelGGL(k_pad_build, dim3(std::max(1, std::min(cdiv(A.nr, 4), 4096))), dim3(256), 0, h->ctx->stream,
-                       A.nr, d.S, A.rp, A.ci, A.va, pci, pva, dg);
-    IPD_KERNEL_CHECK();
-    d.pci = pci;
-    d.pva = pva;
-    d.diag = dg;
+    build_padded_private(h, h->L[k].A, d.S, &d);
     return d;
 }
 
@@ -211,8 +207,8 @@ static unsigned char* alloc_resident_block(ipd_amg* h, ResidentState& R, ResTail
 }
 
 // level k in polynomial form, row layout (pack_bpoly), for the resident workgroups: form 64
-static BPolyDev pack_resident_poly(ipd_amg* h, CycleState* st, int k, int seg, int ld) {
-    const BPolyDev pb = pack_bpoly(h->ctx, h, st, k, h->opts.isnsp, 0, true, seg, ld);
+static BPolyPack pack_resident_poly(ipd_amg* h, CycleState* st, int k, int seg, int ld) {
+    const BPolyPack pb = pack_bpoly(h->ctx, h, st, k, h->opts.isnsp, 0, true, seg, ld);
     record_rows_op(st, h, k, pb);
     st->level_forms.resize((size_t)h->J + 1, 0);
     st->level_forms[(size_t)k] |= 64;
@@ -228,8 +224,8 @@ static void commit_resident(ipd_amg* h, ResidentState& R, const ResidentPlan& p,
     R.ok = true;
 }
 
-// ---- k_resident: planned at amg_prepare_levels -------------------------------------------------
-static void prepare_resident(ipd_amg* h, CycleState* st, const std::vector<LevelShape>& shapes, const PlanSwitches& sw) {
+// ---- k_resident: planned at amg_prepare_levels (ipd_cycle_state.h) -----------------------------
+void prepare_resident(ipd_amg* h, CycleState* st, const std::vector<LevelShape>& shapes, const PlanSwitches& sw) {
     st->res = std::make_shared<ResidentState>();
     ResidentState& R = *st->res;
     R.off = sw.no_resident;   // (remembered: the mask-form kernel is set up later, by amg_attach_maskop)
@@ -256,11 +252,11 @@ static void prepare_resident(ipd_amg* h, CycleState* st, const std::vector<Level
     D.A4 = res_csr(p.three ? h->L[4].A : l3.A);
     if (p.three) {
         if (p.poly3) {
-            const BPolyDev pb = pack_resident_poly(h, st, 3, 512, RES_P3_LD);
+            const BPolyPack pb = pack_resident_poly(h, st, 3, 512, RES_P3_LD);
             D.p3rows = pb.M;
             D.p3w = pb.W;
             if (p.poly4) {
-                const BPolyDev pb4 = pack_resident_poly(h, st, 4, RES_P4_SEG, RES_P4_LD);
+                const BPolyPack pb4 = pack_resident_poly(h, st, 4, RES_P4_SEG, RES_P4_LD);
                 D.p4rows = pb4.M;
                 D.p4w = pb4.W;
                 D.N5 = h->L[5].A.nr;
@@ -435,7 +431,7 @@ bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double* x, in
 bool resident_active(const CycleState* st) { return st->res->ok; }
 
 // the "resident=..." field of amg_prepare_levels' debug line
-static void print_resident_summary(std::FILE* f, const CycleState* st) {
+void print_resident_summary(std::FILE* f, const CycleState* st) {
     std::fprintf(f, "resident=%d(G=%d,KE=%d)", (int)st->res->ok, st->res->plan.G, st->res->plan.key.ke);
 }
 
@@ -475,9 +471,6 @@ static void commit_mask_form(ipd_amg* h, ResidentState& R, const ResidentPlan& p
     R.line_ke3 = p.kind == RESIDENT_DEEP ? 1 : 0;   // (the launch line's ke stays a replaced plan's)
     commit_resident(h, R, p, sw);
 }
-
-__global__ void k_maskop_scales(int nf, int nc, const double* __restrict__ p, const double* __restrict__ q, double itk,
-                                double* __restrict__ alpha, double* __restrict__ beta);   // (ipd_cycle_host.h)
 
 // Derives the bit-mask form of level 1 from its CSR arrays; keeps the CSR kernels (returns
 // false) unless A_1 is exactly Hybrid_AMG's rescaled operator for these p, q, tk.
@@ -521,42 +514,18 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
         sweeps_too = false;
     }
     if (std::max(m, n) > 4096) return false;   // a row's mask words must fit one wave (64 words)
-    Arena& ar = *h->arena;
-    MaskOp mo;
-    mo.nf = n;
-    mo.nc = m;
-    mo.nwf = cdiv(m, 64);
-    mo.nwc = cdiv(n, 64);
-    unsigned long long* fb = ar.alloc<unsigned long long>((size_t)n * mo.nwf);
-    unsigned long long* cb = ar.alloc<unsigned long long>((size_t)m * mo.nwc);
-    double* alpha = ar.alloc<double>((size_t)n);
-    double* beta = ar.alloc<double>((size_t)m);
-    double* diag = ar.alloc<double>((size_t)lv.N);
     int* bad = ctx->scratch->alloc<int>(1);
-    IPD_HIP(hipMemsetAsync(fb, 0, sizeof(unsigned long long) * (size_t)n * mo.nwf, ctx->stream));
-    IPD_HIP(hipMemsetAsync(cb, 0, sizeof(unsigned long long) * (size_t)m * mo.nwc, ctx->stream));
-    IPD_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(k_maskop_scales, dim3(cdiv(lv.N, 256)), dim3(256), 0, ctx->stream, n, m, p_dev,
-                       q_dev, 1.0 / tk, alpha, beta);
-    hipLaunchKernelGGL(k_maskop_build, dim3(std::max(1, std::min(cdiv(lv.N, 4), 2048))), dim3(256), 0,
-                       ctx->stream, lv.N, n, lv.A.rp, lv.A.ci, lv.A.va, (const double*)alpha,
-                       (const double*)beta, mo.nwf, mo.nwc, fb, cb, diag, bad);
-    IPD_KERNEL_CHECK();
-    if (ctx->fetch1(bad) != 0) return false;
-    mo.fbits = fb;
-    mo.cbits = cb;
-    mo.alpha = alpha;
-    mo.beta = beta;
-    mo.diag = diag;
+    MaskOp mo;
+    if (!build_maskop(h, p_dev, q_dev, m, n, tk, bad, &mo)) return false;
     if (for_resident && resident_mask_transfers_fit(in, facts)) {
         if (double* rho = mask_transfer_rho(h, mo, bad)) {
             ResDesc& D = R.desc;
             D.xm = 1;
             D.xm_nwf = mo.nwf;
             D.xm_nwc = mo.nwc;
-            D.xm_fbits = fb;
-            D.xm_cbits = cb;
-            D.xm_beta = beta;
+            D.xm_fbits = mo.fbits;
+            D.xm_cbits = mo.cbits;
+            D.xm_beta = mo.beta;
             D.xm_rho = rho;
         }
     }
@@ -578,8 +547,8 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
         if (p.kind == RESIDENT_DEEP) {
             const LevelDev d2 = resident_rows(h, st, p, 2);
             if (const double* rho = mask_transfer_rho(h, mo, bad)) {
-                const BPolyDev pb = pack_resident_poly(h, st, 3, RB_P3_SEG, RB_P3_LD);
-                BPolyDev pb4;
+                const BPolyPack pb = pack_resident_poly(h, st, 3, RB_P3_SEG, RB_P3_LD);
+                BPolyPack pb4;
                 if (p.poly4) pb4 = pack_resident_poly(h, st, 4, RB_P4_SEG, RB_P4_LD);
                 ResBigDesc B = big_desc(h, st, mo, d2, rho);
                 B.N3 = h->L[3].A.nr;
@@ -626,13 +595,9 @@ static bool amg_attach_poly2(ipd_amg* h) {
     if (!st || !st->res->ok) return false;
     ResidentState& R = *st->res;
     if (!resident_takes_poly2(R.plan, resident_inputs(h, st, level_shapes(h, st)))) return false;
-    const int N2 = h->L[2].A.nr;
     const int seg = RES_NMAX / 2, ld = 2 * seg + 128;
-    const BPolyDev pb = pack_bpoly(ctx, h, st, 2, h->opts.isnsp, 0, true, seg, ld);
-    const int Np = pb.e.Np, nT = (Np / 16) * (Np / 16);
-    // (IPD_OPTIN_LDS is not needed: the tiles use static LDS only)
-    hipLaunchKernelGGL(k_bpoly_compose, dim3((unsigned)(nT + (N2 + 3) / 4)), dim3(256), 0, ctx->stream, pb.e, nT);
-    IPD_KERNEL_CHECK();
+    const BPolyPack pb = pack_bpoly(ctx, h, st, 2, h->opts.isnsp, 0, true, seg, ld);
+    bpoly_compose(ctx, pb);
     R.desc.p2rows = pb.M;
     R.desc.p2w = pb.W;
     R.desc.p2seg = seg;

@@ -1,4 +1,4 @@
-// The two-level forms of k_resident (KE3 == 0): four rows of RESIDENT_KERNELS (ipd_resident_host.h), nothing else.
+// The two-level forms of k_resident (KE3 == 0): four rows of RESIDENT_KERNELS (ipd_resident_host.hip), nothing else.
 #include "ipd_amg_internal.h"
 
 #include "ipd_resident.h"

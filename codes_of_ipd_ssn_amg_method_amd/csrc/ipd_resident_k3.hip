@@ -1,4 +1,4 @@
-// The three-level forms of k_resident (KE3 != 0): six rows of RESIDENT_KERNELS (ipd_resident_host.h), nothing else.
+// The three-level forms of k_resident (KE3 != 0): six rows of RESIDENT_KERNELS (ipd_resident_host.hip), nothing else.
 #include "ipd_amg_internal.h"
 
 #include "ipd_resident.h"

@@ -1,4 +1,4 @@
-// The mask-form kernel k_resident_big: four rows of RESIDENT_KERNELS (ipd_resident_host.h), nothing else.
+// The mask-form kernel k_resident_big: four rows of RESIDENT_KERNELS (ipd_resident_host.hip), nothing else.
 #include "ipd_amg_internal.h"
 
 #include "ipd_resident_big.h"

@@ -1,7 +1,7 @@
 // Planner of the resident kernels (ipd_resident.h, ipd_resident_big.h): from the level shapes, the
 // options, the switches, the device's CU count and the LDS images the level plan packed it decides
 // which resident mode a hierarchy runs -- none, k_resident, the mask-form kernel's three-level or deep
-// mode --, which instantiation, how many workgroups, which tail.  ipd_resident_host.h does the device work a
+// mode --, which instantiation, how many workgroups, which tail.  ipd_resident_host.hip does the device work a
 // plan calls for and commits it.  Host-clean, no HIP, no getenv: tests/resident_plan_driver.cpp runs it
 // on the CPU.
 //

@@ -2,7 +2,7 @@
 built with the system g++ against the header and run on level shapes.  What the planner returns is checked by
 execution: the width rules against their Python mirrors for every stride, the cut-offs at the value and one
 past it, invariants over the shapes, options and switches of test_level_plan.py on two CU counts, every key
-against the table of instantiations (RESIDENT_KERNELS, csrc/ipd_resident_host.h, read from the source the
+against the table of instantiations (RESIDENT_KERNELS, csrc/ipd_resident_host.hip, read from the source the
 normal build compiles), and named hierarchies against committed records.  CPU only."""
 import os
 import re
@@ -31,7 +31,7 @@ def spelled(big, a, b, flag):
 def resident_table():
     """The rows of RESIDENT_KERNELS as a list of (name, name spelled from the row's key, name spelled from the
     row's kernel).  The table contains no conditionals: every row is compiled."""
-    text = open(os.path.join(CSRC, "ipd_resident_host.h")).read()
+    text = open(os.path.join(CSRC, "ipd_resident_host.hip")).read()
     start = text.index("static const ResidentKernel RESIDENT_KERNELS[] = {")
     rows = []
     for line in text[start:text.index("\n};", start)].splitlines()[1:]:
