@@ -76,6 +76,11 @@ class ipd_ssn_rec(Structure):
                 ("resamg", c_double), ("bk1", c_double), ("tk", c_double)]
 
 
+class ipd_plan_stats(Structure):
+    _fields_ = [("nnz", c_int64), ("sum_kept", c_double), ("sum_dropped", c_double),
+                ("max_dropped", c_double), ("fval_kept", c_double)]
+
+
 class ipd_apd_result(Structure):
     _fields_ = [("converged", c_int32), ("k", c_int32), ("fval", c_double),
                 ("kkt", c_double * 4), ("rr", c_double), ("sum_amg", c_int64),
@@ -114,6 +119,9 @@ _pcg_multi_args = [c_void_p, POINTER(c_double), c_int64, c_int64, POINTER(c_doub
 lib.ipd_amg_pcg_multi.argtypes = _pcg_multi_args
 lib.ipd_amg_pcg_multi_dev.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_void_p, POINTER(ipd_pcg_opts),
                                       c_void_p] + _pcg_multi_args[7:]
+lib.ipd_apd_plan.argtypes = [c_void_p, c_double, c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_plan_dev.argtypes = [c_void_p, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_set_plan.argtypes = [c_void_p, c_void_p]
 
 # every symbol the header declares (tests check that they all resolve)
 EXPORTS = [
@@ -139,6 +147,7 @@ EXPORTS = [
     "ipd_amg_attach_mask_operator", "ipd_amg_attach_mask_transfers", "ipd_amg_attach_level2_poly", "ipd_twogrid_bigph", "ipd_twogrid", "ipd_hybrid_twogrid", "ipd_amg4pot_twogrid",
     "ipd_aug_pcg", "ipd_pcg4pot", "ipd_spd_solve", "ipd_amg_resident_levels", "ipd_amg_resident_kernel", "ipd_amg_level_forms", "ipd_amg_poly_operator",
     "ipd_amg_packed_operator",
+    "ipd_apd_plan", "ipd_apd_plan_dev", "ipd_apd_set_plan",
 ]
 
 

@@ -802,6 +802,68 @@ class APDWorkspace:
         check(lib.ipd_apd_get_state(self.handle, dptr(u), dptr(v), dptr(lam), byref(bk)))
         return u, v, lam, bk.value
 
+    # -- the transport plan as a sparse matrix ---------------------------------
+    @staticmethod
+    def _plan_stats(st: L.ipd_plan_stats) -> dict:
+        return dict(nnz=int(st.nnz), sum_kept=st.sum_kept, sum_dropped=st.sum_dropped,
+                    max_dropped=st.max_dropped, fval_kept=st.fval_kept)
+
+    def plan(self, tol: float = 0.0, stats: bool = False):
+        """``sparse(reshape(xk,m,n))`` restricted to ``~(abs(x) <= tol)`` as a ``csc_matrix``, built on
+        the device: only the kept entries cross to the host (``ipd_apd_plan``).  ``tol = 0`` is
+        MATLAB's ``sparse()``.  ``stats=True`` -> ``(X, dict(nnz, sum_kept, sum_dropped, max_dropped,
+        fval_kept), ax)`` with ``ax = Ax(x_kept, p, q)``."""
+        out = L.ipd_csc_out()
+        st = L.ipd_plan_stats()
+        ax = np.empty(self.M) if stats else None
+        check(lib.ipd_apd_plan(self.handle, c_double(float(tol)), byref(out), byref(st),
+                               dptr(ax) if stats else None))
+        X = L.csc_out_to_scipy(out)
+        return (X, self._plan_stats(st), ax) if stats else X
+
+    def plan_dev(self, tol, jc, ir, pr, ax=None) -> dict:
+        """The same into caller-owned device arrays (``ipd_apd_plan_dev``): ``jc`` n+1 int64, ``ir``
+        int64 and ``pr`` float64 of equal capacity, ``ax`` n+m float64 or None -- torch tensors on
+        the workspace's GPU, ``DeviceBuffer`` objects, or raw device pointers given as
+        ``(pointer, entries)`` pairs (``jc`` and ``ax``: a plain pointer will do).  Returns the
+        statistics; raises ``IpdError`` with code ``IPD_E_LIMIT`` when the capacity is too small
+        (the statistics are then in the exception's ``stats`` attribute and ``jc`` is valid)."""
+        def ptr_cap(a, itemsize):
+            if a is None:
+                return None, 0
+            if isinstance(a, tuple):
+                return c_void_p(int(a[0])), int(a[1])
+            if isinstance(a, L.DeviceBuffer):
+                return a.ptr, a.nbytes // itemsize
+            if hasattr(a, "data_ptr"):
+                if a.element_size() != itemsize or not a.is_contiguous():
+                    raise ValueError("plan_dev: tensors must be contiguous int64 / float64")
+                return c_void_p(a.data_ptr()), a.numel()
+            return c_void_p(int(a)), 0
+        jc_p, _ = ptr_cap(jc, 8)
+        ir_p, ir_cap = ptr_cap(ir, 8)
+        pr_p, pr_cap = ptr_cap(pr, 8)
+        ax_p, _ = ptr_cap(ax, 8)
+        st = L.ipd_plan_stats()
+        try:
+            check(lib.ipd_apd_plan_dev(self.handle, c_double(float(tol)), c_int64(min(ir_cap, pr_cap)),
+                                       jc_p, ir_p, pr_p, byref(st), ax_p))
+        except L.IpdError as e:
+            e.stats = self._plan_stats(st)
+            raise
+        return self._plan_stats(st)
+
+    def set_plan(self, X):
+        """``xk = vk = full(X)`` from a sparse m x n matrix (``ipd_apd_set_plan``): a warm start or a
+        checkpoint of about m+n numbers; ``lk`` and ``bk`` are kept, the iteration count starts over
+        as after ``set_state``."""
+        if not sp.issparse(X):
+            X = sp.csc_matrix(np.asarray(X, dtype=np.float64))
+        if X.shape != (self.m, self.n):
+            raise ValueError(f"X must be {self.m} x {self.n}")
+        A = L.CscIn(X)
+        check(lib.ipd_apd_set_plan(self.handle, A.ref()))
+
     # -- the loop -------------------------------------------------------------
     def options(self, **kw) -> L.ipd_apd_opts:
         o = L.ipd_apd_opts()
@@ -901,7 +963,8 @@ def warmup_class2(c, r, l, p, q, mu, phi, res=None, maxit=None):
         ws.close()
 
 
-def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool = False) -> dict:
+def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool = False,
+                plan_tol=None) -> dict:
     try:
         if warm is not None:
             ws.warmup(*warm)
@@ -910,31 +973,35 @@ def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool 
         out.update(ws.history())
         out.update(uk=u, vk=v, lk=lam, bk=bk, records=ws.records(), reuse_stats=ws.reuse_stats())
         out["xk"] = u[:ws.m * ws.n]
+        if plan_tol is not None:
+            out["plan"], out["plan_stats"], out["plan_ax"] = ws.plan(plan_tol, stats=True)
         return out
     finally:
         ws.close()
 
 
 def APD_SsN_Class1(c, r, l, p, q, gama=np.inf, prob=2, rng: MatlabRand | None = None,
-                   amg_opts: dict | None = None, krylov: bool = False, **opts) -> dict:
+                   amg_opts: dict | None = None, krylov: bool = False, plan_tol=None, **opts) -> dict:
     """The script ``Class1/APD_SsN_Class1.m`` with ``inner_solver = 4`` on the workspace it
     loads (``:27``); returns the variables it leaves behind.  Warm start as ``:53-59``.
-    ``krylov``: see ``APDWorkspace.run``."""
+    ``krylov``: see ``APDWorkspace.run``.  ``plan_tol``: when given, the result gains ``plan`` (the
+    final ``xk`` as a sparse m x n matrix without the entries with ``abs(x) <= plan_tol``),
+    ``plan_stats`` and ``plan_ax`` (``APDWorkspace.plan``)."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=30, theta=1 / 4, smoth=5, cycle="w",
                                 isnsp=1, inter=1, guess=None)                          # :87-88
     warm = (0.0, 100) if prob > 0 else (5e-2, np.inf)                                  # :53-58
     ws = APDWorkspace(1, c, r, l, p, q, gama=gama)
-    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov)
+    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol)
 
 
 def APD_SsN_Class2(c, r, l, p, q, mu, phi, rng: MatlabRand | None = None,
-                   amg_opts: dict | None = None, krylov: bool = False, **opts) -> dict:
+                   amg_opts: dict | None = None, krylov: bool = False, plan_tol=None, **opts) -> dict:
     """The script ``Class2/APD_SsN_Class2.m`` with ``inner_solver = 4`` (AMG4POT 'amg', or
-    'amg_pcg' with ``krylov``)."""
+    'amg_pcg' with ``krylov``).  ``plan_tol``: as in ``APD_SsN_Class1``."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=40, theta=1 / 4, smoth=10, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     ws = APDWorkspace(2, c, r, l, p, q, mu=mu, phi=phi)
-    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov)
+    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol)
 
 
 def load_input(path: str) -> dict:

@@ -26,6 +26,7 @@
 
 #include "ipd_amg_internal.h"
 #include "ipd_cycle_dev.h"
+#include "ipd_plan.h"
 
 namespace {
 
@@ -1746,13 +1747,31 @@ extern "C" int ipd_apd_set_state(ipd_apd* h, const double* u, const double* v, c
         if (v) h->ctx->upload(h->v, v, h->U);
         if (lam) h->ctx->upload(h->lam, lam, (size_t)h->L);
         h->bk = bk;
-        h->k = 0;
-        h->have_kkt = false;
-        h->converged = false;
-        h->recs.clear();
-        h->sum_amg = h->total_amg = h->fail_amg = h->max_amg = 0;
-        h->restarts = 0;
+        apd_restart_script(h);
     });
+}
+
+void apd_restart_script(ipd_apd* h) {
+    h->k = 0;
+    h->have_kkt = false;
+    h->converged = false;
+    h->recs.clear();
+    h->sum_amg = h->total_amg = h->fail_amg = h->max_amg = 0;
+    h->restarts = 0;
+}
+
+ApdPlanView apd_plan_view(ipd_apd* h) {
+    ApdPlanView w;
+    w.ctx = h->ctx;
+    w.m = h->m;
+    w.n = h->n;
+    w.mn = h->mn;
+    w.c = h->c;
+    w.p = h->p;
+    w.q = h->q;
+    w.u = h->u;
+    w.v = h->v;
+    return w;
 }
 
 extern "C" int ipd_apd_set_krylov(ipd_apd* h, int32_t on) {

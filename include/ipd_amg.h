@@ -467,6 +467,38 @@ int ipd_apd_eval(ipd_apd* h, const double* lam, uint8_t* s_out, double* t_out, d
 /* HIP-event timing of `reps` eval passes on the current workspace (bench.py).   */
 int ipd_apd_bench_eval(ipd_apd* h, int32_t reps, double* total_ms, double* bytes_per_pass);
 
+/* The transport plan as a sparse matrix, out of and into the device workspace:
+ * the dense iterate stays in HBM, only the kept entries and n+1 column pointers cross.          */
+typedef struct ipd_plan_stats {
+    int64_t nnz;         /* entries kept                                         */
+    double sum_kept;     /* sum of x over kept entries                           */
+    double sum_dropped;  /* sum of |x| over dropped entries                      */
+    double max_dropped;  /* largest |x| dropped, 0 if none                       */
+    double fval_kept;    /* sum of c.*x over kept entries                        */
+} ipd_plan_stats;
+
+/* X = sparse(reshape(xk,m,n)) restricted to entries with !(|x| <= tol): m x n CSC, rows ascending in
+ * every column, library-owned (ipd_csc_free).  xk is the first mn entries of the workspace's u
+ * (class 2: the x block of uk).  tol = 0 is exactly MATLAB's sparse(): nonzeros and NaNs are kept.
+ * ax (n+m, or NULL) receives Ax(x_kept,p,q) = [X'*p ; X*q].  IPD_E_ARG for NULL h, X or st, and
+ * for tol negative or NaN.                                                                       */
+int ipd_apd_plan(ipd_apd* h, double tol, ipd_csc_out* X, ipd_plan_stats* st, double* ax);
+
+/* Same, into caller-owned DEVICE arrays: jc_dev n+1, ir_dev / pr_dev cap entries.  *st is filled in
+ * either case; when st->nnz > cap only jc_dev is written and the call returns IPD_E_LIMIT (so a
+ * first call with cap = 0 is the size query; ir_dev / pr_dev may then be NULL).  ax_dev: n+m or
+ * NULL.  IPD_E_ARG for NULL h, st or jc_dev, cap < 0, tol negative or NaN.                       */
+int ipd_apd_plan_dev(ipd_apd* h, double tol, int64_t cap, int64_t* jc_dev, int64_t* ir_dev,
+                     double* pr_dev, ipd_plan_stats* st, double* ax_dev);
+
+/* xk = vk = full(X) (Class1 :60); class 2: the x blocks of uk and vk, the y and z blocks untouched.
+ * lk, bk, histories and records are left exactly as ipd_apd_set_state(u, v, NULL, bk_unchanged)
+ * with the dense equivalent would leave them.  X is validated on the host before anything is
+ * uploaded: IPD_E_ARG (state unchanged) for dimensions other than m x n, jc[0] != 0, jc not
+ * non-decreasing, jc[n] != nnz, a row index outside [0, m), rows not strictly ascending within a
+ * column.                                                                                        */
+int ipd_apd_set_plan(ipd_apd* h, const ipd_csc* X);
+
 /* Matrix-free level-1 operator.  If level 1 of `h` is exactly Hybrid_AMG's
  * rescaled operator Ae = bk1*Q0^2 + (Q0*T*Q0 + Q0*H0*Q0)/tk for these p, q, tk (checked entry by
  * entry against A_1's CSR values), the level-1 Gauss-Seidel sweeps read one BIT per entry (the
