@@ -92,7 +92,7 @@ struct ipd_amg {
     std::shared_ptr<BlockKrylovState> bkry;
 };
 
-// ipd_setup.hip
+// ipd_coarsen.hip, ipd_setup.hip (what they call each other through: ipd_setup_internal.h)
 void amg_strength_mask(ipd_ctx* ctx, const Csr& A, double theta, uint8_t* strong, int* degi,
                        int* rowcnt);
 void amg_mis_set(ipd_ctx* ctx, const Csr& A, double theta, ipd_rng* rng, uint8_t* isC,

@@ -22,10 +22,6 @@
 #include <cmath>
 #include <numeric>
 
-static inline int rows_grid(int nr) { return std::max(1, std::min(cdiv(nr, 4), 4096)); }
-static inline int elems_grid(long long n) {
-    return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096));
-}
 
 // ---------------------------------------------------------------------------
 // Ae assembly                                             (Hybrid_AMG.m:17-24)

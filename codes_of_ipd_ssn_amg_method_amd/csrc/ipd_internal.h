@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ipd_amg.h"
+#include "ipd_setup_plan.h"   // RowCountMode, the setup's limits (ipd_limits.h)
 #include "ipd_switches.h"
 
 // ---------------------------------------------------------------------------
@@ -150,7 +151,7 @@ struct ipd_ctx {
     long long asat_nnz_hint = 0;   // entries of the last ASAt result (sizes the next one's arrays)
     // entries of P, Pt*A and Ac of the last hierarchy's level k (amg_transfer's lazy counts: the kernel-choice
     // heuristics of the next hierarchy's products run on these estimates; 0 = none yet)
-    int xfer_hint[40][4] = {};   // [3]: longest row of P'A
+    int xfer_hint[XFER_HINT_LEVELS][4] = {};   // [3]: longest row of P'A
     void* asat_agg = nullptr;      // k_asat_small's chained-scan words (ipd_kkt.hip)
     // Zero pool: temporaries that must start out as zeros (transpose bitmaps, dense operand blocks, flags) are
     // bumped out of one block that a single memset clears again at the start of the next hierarchy build --
@@ -241,6 +242,16 @@ struct ProfScope {
 };
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// grids of the 256-thread walks: a wave per row / a thread per element, grid-stride beyond 4096 workgroups
+static inline int rows_grid(int nr) { return std::max(1, std::min(cdiv(nr, 4), 4096)); }
+static inline int elems_grid(long long n) {
+    return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096));
+}
+
+// IPD_INTERP, IPD_PRODUCT and IPD_NO_MIS_SMALL for the setup's planner: once per amg_transfer / csr_spgemm call
+static inline SetupSwitches read_setup_switches() {
+    return setup_switches(switch_value("IPD_INTERP"), switch_value("IPD_PRODUCT"), switch_on("IPD_NO_MIS_SMALL"));
+}
 
 // scratch temporaries that start out as zeros: out of the zero pool when it has room
 template <class T>
@@ -326,6 +337,34 @@ static inline ScanTail scan_tail_lazy(const int* in, int* out, int n, int* total
     t.extra = total_dev;
     return t;
 }
+// Host side of the row pointers of a counted matrix of n rows, in the mode plan_row_count chose.  Before the
+// producer runs: `cnt` is the counts array it fills (zero-pool memory where its tail scans, scratch otherwise)
+// and `tail` the ScanTail it ends with (empty: plain counts).  After it: finish() queues the scan launch where
+// the mode has one and returns the entry count to size the arrays by -- the caller's bound while the count is
+// lazy (it is at *total_dev once the consumer or the tail has run), else the waited or fetched total, with the
+// tail's flag word -- and head() is what the compaction takes as the plain counts it scans itself.
+struct RowCounts {
+    ipd_ctx* ctx;
+    RowCountMode mode;
+    int n;
+    int* rp;
+    int* total_dev;
+    int* cnt;
+    ScanTail tail;
+    std::unique_ptr<TailTotal> tt;
+    RowCounts(ipd_ctx* c, RowCountMode m, int n_, int* rp_, int* total_dev_)
+        : ctx(c), mode(m), n(n_), rp(rp_), total_dev(total_dev_) {
+        cnt = row_count_has_tail(m) ? zeroed<int>(c, (size_t)n + 1) : c->scratch->alloc<int>((size_t)n + 1);
+        if (m == RC_TAIL_LAZY)
+            tail = scan_tail_lazy(cnt, rp, n, total_dev);
+        else if (m == RC_TAIL_WAIT) {
+            tt.reset(new TailTotal(c, cnt, rp, n));
+            tail = tt->t;
+        }
+    }
+    int finish(size_t bound, int* flag = nullptr);   // ipd_sparse.hip
+    const int* head() const { return mode == RC_HEAD ? cnt : nullptr; }
+};
 
 #ifdef __HIPCC__
 __device__ __forceinline__ void scan_put(int* cnt, int i, int count, bool flag = false) {
@@ -459,7 +498,6 @@ __device__ __forceinline__ void scan_tail(const ScanTail& s) {
 // The other way round, for producers with one-wave workgroups: the CONSUMER's workgroups each scan the (plain)
 // counts for themselves -- n <= SCAN_HEAD_MAX ints out of L2, a microsecond -- and workgroup 0 also stores the
 // row pointers and the total for whoever comes later.  256 threads.
-constexpr int SCAN_HEAD_MAX = 4096;
 struct ScanHeadLds {
     int rp[SCAN_HEAD_MAX + 1];
     int wsum[4];
@@ -557,12 +595,11 @@ void fill_f64(ipd_ctx* ctx, double* p, double v, size_t n);
 // total_dev != NULL ("lazy count"): no host round trip -- C's arrays are sized by the dense bound nr*nc (the
 // caller has checked SPGEMM_LAZY_MAX), C->nnz is that bound until the caller has fetched *total_dev; the nnz of
 // X and Y are then only read by the kernel-choice heuristic (estimates will do: both kernels give the same bits)
-constexpr size_t SPGEMM_LAZY_MAX = size_t(1) << 21;
 // maxrow_dev (lazy only): the longest row of C is stored there; x_maxrow: the longest row of X if known (estimate)
 void csr_spgemm(ipd_ctx* ctx, Arena& dst, const Csr& X, const Csr& Y, Csr* C, int* total_dev = nullptr,
                 LazyPost* post = nullptr, int* maxrow_dev = nullptr, int x_maxrow = 0);
 // the caller's check of a fetched lazy count against the bound C's arrays were sized by (C.nnz before the fetch):
-// a count outside [0, C.nnz] (a ScanTail total of -1) raises IPD_E_HIP naming the product and the level
+// a count outside [0, C.nnz] (a ScanTail total of -1) raises IPD_E_HIP naming the matrix and the level
 void spgemm_check_lazy_count(const Csr& C, int fetched, const char* product, int level);
 void csr_expand_dense(ipd_ctx* ctx, const Csr& A, double* dense, int ld);  // dense pre-zeroed
 // st.out != NULL: rowcnt is zeroed<int> and the launch's tail scans the (biased) counts into st.out (nr > 0);

@@ -34,6 +34,21 @@ static constexpr double PAD_SLACK_FACTOR = 1.3, PAD_SLACK = 16.0;   // pad width
 static constexpr int PAD_BATCHES = 8;              // ROW_U batches per lane of a padded row before the chip-filling rule
 static constexpr int PCG_LANES_MAX = 64;           // lanes per row of the coarsest level's PCG
 
+// Thresholds of the setup's rules (ipd_setup_plan.h; the measurements behind them are recorded there and where
+// the kernels they choose between are defined)
+static constexpr size_t SPGEMM_LAZY_MAX = size_t(1) << 21;   // dense bound nr*nc up to which a product's arrays are sized by it
+static constexpr int SCAN_HEAD_MAX = 4096;                   // rows a consumer scans itself (scan_head: ScanHeadLds::rp)
+static constexpr int MIS_SMALL_ROWS = 1024;                  // rows / entries of a level up to which mis_set is one launch
+static constexpr int MIS_SMALL_NNZ = 40000;                  // (k_mis_small: a thread per node, the strong lists in LDS)
+static constexpr double SPLIT_ROW_MIN = 256.0;               // mean row length from which the interpolation is built as a product
+static constexpr double WIDE_ROW_MIN = 96.0;                 // mean row length from which a row gets 256 threads, not one wave
+static constexpr int SPGEMM_TILE = 64, SPGEMM_TILE_K = 16;   // the tile product's output tile edge and inner-index tile
+static constexpr size_t SPGEMM_TILE_BYTES_MAX = size_t(12) << 30;     // dense operand blocks of the tile product
+static constexpr size_t DENSE_SCRATCH_BYTES_MAX = size_t(2) << 30;    // dense rows of a row product / an interpolation build
+static constexpr int SPGEMM_COLS_MAX = 16384;                // columns of a row product (one LDS accumulator row)
+static constexpr int XFER_COARSE_MAX = 8192;                 // coarse nodes of a non-bigraph level (two LDS rows in k_build_W*)
+static constexpr int XFER_HINT_LEVELS = 40;                  // levels ipd_ctx::xfer_hint keeps the last hierarchy's counts of
+
 // levels a single-workgroup image (SolveDesc) holds
 static constexpr int SOLVE_ML = 24;
 // An LDS image (ipd_level_plan.h): the planner admits levels while the predicted dynamic LDS stays within the

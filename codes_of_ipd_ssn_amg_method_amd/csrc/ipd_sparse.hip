@@ -477,8 +477,8 @@ __global__ __launch_bounds__(256) void k_dense_compact(int nr, int nc, int ld,
 // at a time for k = 0,1,2,...  The terms a structural zero contributes are +0.0, which leave a
 // partial sum unchanged, so the result is bit-identical to the row kernel's (this translation
 // unit is compiled with -ffp-contract=off: multiply, round, add, round).
-constexpr int GT = 64;   // output tile edge
-constexpr int GK = 16;   // inner-index tile
+constexpr int GT = SPGEMM_TILE;     // output tile edge
+constexpr int GK = SPGEMM_TILE_K;   // inner-index tile
 
 // both operands of a tile product in one launch (blockIdx.y picks the matrix)
 struct ExpandPair {
@@ -736,42 +736,6 @@ __global__ __launch_bounds__(64) void k_spgemm_rows_w(int nr, int nc, const int*
     }
 }
 
-static inline size_t round_up(size_t v, size_t q) { return (v + q - 1) / q * q; }
-
-// Which product kernel is expected to finish first (measured on MI355X, round 4).  The row kernels are a
-// dependent chain per output row, one step per entry of X's row: the one-wave kernel (short rows of Y) takes
-// about 0.16 us per entry with the rows of Y prefetched eight deep, the 256-thread kernel 0.35 us + 0.25 us per
-// 256 entries of Y's row with a barrier per step; rows are spread over the CUs as LDS allows.  The tile kernel
-// walks the padded rows x inner x columns box 16 inner indices at a time -- about 0.9 us per step and wave of
-// 256 64-edge tiles, 0.23 us with the 32-edge tiles small products get -- plus 20-40 us for the expansion of
-// the operands and the row count.  IPD_PRODUCT=rows|tiles overrides the choice (tests compare the two bit for bit).
-static bool spgemm_prefers_tiles(const Csr& X, const Csr& Y, size_t* bytes, int x_maxrow) {
-    const size_t nrp = round_up((size_t)X.nr, GT), nkp = round_up((size_t)X.nc, GT),
-                 ncp = round_up((size_t)Y.nc, GT);
-    *bytes = 8 * (nrp * nkp + nkp * ncp + nrp * ncp);
-    if (X.nr == 0 || X.nc == 0 || Y.nc == 0 || X.nnz == 0) return false;
-    if (*bytes > (size_t(12) << 30)) return false;   // 12 GiB of dense scratch at most
-    if (const char* e = switch_value("IPD_PRODUCT")) {
-        if (!strcmp(e, "tiles")) return true;
-        if (!strcmp(e, "rows")) return false;
-    }
-    // (one round of rows: the launch is as slow as its longest row)
-    const double ylen = (double)Y.nnz / Y.nr;
-    const double xlen = (X.nr <= 256 * 8) ? std::max((double)X.nnz / X.nr, (double)x_maxrow) : (double)X.nnz / X.nr;
-    const double lds_rows = std::max(1.0, std::min(ylen < 96.0 ? 32.0 : 8.0, 160.0 * 1024 / (8.0 * Y.nc + 64)));
-    const double row_rounds = std::ceil(X.nr / (256.0 * lds_rows));
-    const double t_rows = row_rounds * xlen * (ylen < 96.0 ? 0.16 : 0.35 + 0.25 * std::ceil(ylen / 256.0));
-    const double tiles = (double)(nrp / GT) * (double)(ncp / GT);
-    const double steps = (double)(nkp / GK);
-    const double t_walk = tiles >= 256.0 ? 20.0 + std::ceil(tiles / 256.0) * steps * 0.9
-                                         : std::ceil(4.0 * tiles / 1024.0) * steps * 0.23;
-    const double t_tiles = 20.0 + t_walk + (double)*bytes / 3.0e6;   // (operand block zeroed and written at ~3 TB/s)
-    if (switch_on("IPD_DEBUG_LEVELS"))
-        std::fprintf(stderr, "[ipd] product %d x %d x %d: x row %.1f, y row %.1f entries; model rows %.1f us, tiles %.1f us\n",
-                     X.nr, X.nc, Y.nc, xlen, ylen, t_rows, t_tiles);
-    return t_tiles < t_rows;
-}
-
 void csr_spgemm(ipd_ctx* ctx, Arena& dst, const Csr& X, const Csr& Y, Csr* C, int* total_dev, LazyPost* post,
                 int* maxrow_dev, int x_maxrow) {
     if (post) post->box = nullptr;
@@ -794,29 +758,19 @@ void csr_spgemm(ipd_ctx* ctx, Arena& dst, const Csr& X, const Csr& Y, Csr* C, in
     double* dense = nullptr;
     unsigned long long* rowbits = nullptr;   // row kernel only: the 64-column blocks a row touched
     int ld = nc;
-    size_t tile_bytes = 0;
-    const bool tiles = spgemm_prefers_tiles(X, Y, &tile_bytes, x_maxrow);
-    const int threads = (Y.nr > 0 && (double)Y.nnz / Y.nr >= 96.0) ? 256 : 64;
-    // The row pointers.  With a lazy count (total_dev) the compaction scans the plain counts on its way in
-    // (scan_head).  Otherwise the host needs the total to size the arrays: producers with 256-thread workgroups
-    // scan their own counts at the end of the launch and post it (ScanTail); the one-wave row kernel is followed
-    // by a scan launch.
-    const bool head_ok = total_dev && nr <= SCAN_HEAD_MAX;
-    const bool tail = !head_ok && (tiles || threads == 256);
-    int* rowcnt = tail ? zeroed<int>(ctx, (size_t)nr + 1) : tmp.alloc<int>((size_t)nr + 1);
-    ScanTail st;
-    std::unique_ptr<TailTotal> tt;
-    if (tail) {
-        if (total_dev)
-            st = scan_tail_lazy(rowcnt, out.rp, nr, total_dev);
-        else {
-            tt.reset(new TailTotal(ctx, rowcnt, out.rp, nr));
-            st = tt->t;
-        }
-    }
+    // kernel, workgroup size and row-count mode (total_dev: a lazy count): ipd_setup_plan.h
+    const ProductShape xs{X.nr, X.nc, X.nnz}, ys{Y.nr, Y.nc, Y.nnz};
+    const ProductPlan plan = plan_product(xs, ys, x_maxrow, read_setup_switches().product, total_dev != nullptr);
+    if (plan.modelled && switch_on("IPD_DEBUG_LEVELS"))
+        std::fprintf(stderr, "%s\n", product_plan_line(xs, ys, plan).c_str());
+    const bool tiles = plan.tiles;
+    const int threads = plan.threads;
+    RowCounts rc(ctx, plan.rows, nr, out.rp, total_dev);
+    int* const rowcnt = rc.cnt;
+    const ScanTail& st = rc.tail;
     if (tiles) {
-        const size_t nrp = round_up((size_t)nr, GT), nkp = round_up((size_t)X.nc, GT),
-                     ncp = round_up((size_t)nc, GT);
+        const size_t nrp = plan_round_up((size_t)nr, GT), nkp = plan_round_up((size_t)X.nc, GT),
+                     ncp = plan_round_up((size_t)nc, GT);
         double* xd = zeroed<double>(ctx, nrp * nkp + nkp * ncp);   // both operands
         double* yd = xd + nrp * nkp;
         dense = tmp.alloc<double>(nrp * ncp);
@@ -826,7 +780,7 @@ void csr_spgemm(ipd_ctx* ctx, Arena& dst, const Csr& X, const Csr& Y, Csr* C, in
         ep.nr[1] = Y.nr, ep.ld[1] = (int)ncp, ep.rp[1] = Y.rp, ep.ci[1] = Y.ci, ep.va[1] = Y.va, ep.dense[1] = yd;
         hipLaunchKernelGGL(k_csr_expand2, dim3(std::max(1, std::min(cdiv(std::max(X.nr, Y.nr), 4), 4096)), 2),
                            dim3(256), 0, ctx->stream, ep);
-        if ((nrp / GT) * (ncp / GT) >= 256)
+        if (plan.edge == GT)
             hipLaunchKernelGGL(k_gemm_ordered<4>, dim3((unsigned)(ncp / GT), (unsigned)(nrp / GT)),
                                dim3(256), 0, ctx->stream, (int)nkp, (int)ncp, xd, yd, dense);
         else   // few 64-edge tiles: 32-edge ones spread the inner-index walk over four times the CUs
@@ -836,10 +790,10 @@ void csr_spgemm(ipd_ctx* ctx, Arena& dst, const Csr& X, const Csr& Y, Csr* C, in
                            ctx->stream, nr, nc, ld, dense, rowcnt, st);
         IPD_KERNEL_CHECK();
     } else {
-        IPD_REQUIRE((size_t)nc * 8 <= 128 * 1024, IPD_E_LIMIT,
+        IPD_REQUIRE(nc <= SPGEMM_COLS_MAX, IPD_E_LIMIT,
                     "spgemm: more than 16384 columns (LDS accumulator row limit)");
         const size_t dense_elems = (size_t)nr * (size_t)(nc ? nc : 1);
-        IPD_REQUIRE(dense_elems * 8 <= (size_t(2) << 30), IPD_E_LIMIT,
+        IPD_REQUIRE(dense_elems * 8 <= DENSE_SCRATCH_BYTES_MAX, IPD_E_LIMIT,
                     "spgemm: dense scratch above 2 GiB");
         dense = tmp.alloc<double>(dense_elems);
         rowbits = tmp.alloc<unsigned long long>((size_t)nr * (size_t)((nc + 4095) / 4096 + 1));
@@ -856,24 +810,8 @@ void csr_spgemm(ipd_ctx* ctx, Arena& dst, const Csr& X, const Csr& Y, Csr* C, in
         }
         IPD_KERNEL_CHECK();
     }
-    const int* head = nullptr;   // plain counts the compaction scans itself
-    if (head_ok) {   // lazy count: dense bound, no round trip
-        out.nnz = (int)((size_t)nr * (size_t)nc);
-        head = rowcnt;
-    } else if (tail) {
-        if (total_dev) {
-            out.nnz = (int)((size_t)nr * (size_t)nc);
-        } else {
-            int two[2] = {0, 0};
-            tt->wait(two);
-            out.nnz = two[0];
-        }
-    } else if (total_dev) {
-        out.nnz = (int)((size_t)nr * (size_t)nc);
-        exclusive_scan_i32(ctx, rowcnt, out.rp, nr, total_dev);
-    } else {
-        out.nnz = exclusive_scan_total(ctx, rowcnt, out.rp, nr);
-    }
+    out.nnz = rc.finish(plan.bound);
+    const int* head = rc.head();   // plain counts the compaction scans itself
     out.ci = dst.alloc<int>((size_t)out.nnz);
     out.va = dst.alloc<double>((size_t)out.nnz);
     if (out.nnz || head) {
@@ -891,6 +829,26 @@ void csr_spgemm(ipd_ctx* ctx, Arena& dst, const Csr& X, const Csr& Y, Csr* C, in
     *C = out;
 }
 
+int RowCounts::finish(size_t bound, int* flag) {
+    switch (mode) {
+        case RC_HEAD:
+        case RC_TAIL_LAZY:
+            return (int)bound;
+        case RC_SCAN_LAZY:
+            exclusive_scan_i32(ctx, cnt, rp, n, total_dev);
+            return (int)bound;
+        case RC_TAIL_WAIT: {
+            int two[2] = {0, 0};
+            tt->wait(two);
+            if (flag) *flag = two[1];
+            return two[0];
+        }
+        case RC_SCAN_TOTAL:
+            break;
+    }
+    return exclusive_scan_total(ctx, cnt, rp, n);
+}
+
 void spgemm_check_lazy_count(const Csr& C, int fetched, const char* product, int level) {
     if (fetched < 0 || fetched > C.nnz)
         throw IpdError(IPD_E_HIP, std::string("spgemm: lazily fetched entry count of ") + product + " on level " +
@@ -898,7 +856,7 @@ void spgemm_check_lazy_count(const Csr& C, int fetched, const char* product, int
                                       std::to_string(C.nnz) + "]");
 }
 
-// dense-row helpers shared with the interpolation build (ipd_setup.hip)
+// dense-row helpers shared with the interpolation build (ipd_prolong.hip)
 void csr_expand_dense(ipd_ctx* ctx, const Csr& A, double* dense, int ld) {
     if (A.nr == 0 || A.nnz == 0) return;
     hipLaunchKernelGGL(k_csr_expand, dim3(std::min(cdiv(A.nr, 4), 4096)), dim3(256), 0, ctx->stream,

@@ -235,7 +235,7 @@ def test_hierarchy_bit_exact_tile_product(ipd, monkeypatch, name, m, n, mk, t):
 
 @pytest.mark.parametrize("name,m,n,mk,t", CASES, ids=[c[0] for c in CASES])
 def test_hierarchy_bit_exact_split_interpolation(ipd, monkeypatch, name, m, n, mk, t):
-    """The interpolation build in product form (csrc/ipd_setup.hip k_w_split_*; default only for
+    """The interpolation build in product form (csrc/ipd_prolong.hip k_w_split_*; default only for
     long rows) on every setup case, sparse ones included, with the row product kernel."""
     monkeypatch.setenv("IPD_INTERP", "split")
     monkeypatch.setenv("IPD_PRODUCT", "rows")
@@ -278,7 +278,7 @@ def test_hierarchy_bit_exact_block_interpolation(ipd, monkeypatch, name, m, n, m
 def test_first_and_later_hierarchies_of_a_context(ipd):
     """The first hierarchy a context builds fetches every entry count as it goes (the counting launches' tails post
     them); from the second on the counts of a level stay on the device until its last compaction posts them, the
-    arrays are sized by dense bounds and the consumers scan the row counts themselves (csrc/ipd_setup.hip "lazy
+    arrays are sized by dense bounds and the consumers scan the row counts themselves (csrc/ipd_setup_plan.h "lazy
     counts", ipd_internal.h scan_head / ScanTail).  Same bits either way, on a fresh context so that the first
     build really is one."""
     from codes_of_ipd_ssn_amg_method_amd import _lib

@@ -5,24 +5,23 @@ unknowns: below the sizes where the setup's size-gated paths switch on.  Here th
 A(k), P(k), cmask(k) with the same indptr, indices and data bits, and the same number of random numbers
 consumed -- is applied to systems that reach each gate:
 
-  lazy counts        N*Nc <= SPGEMM_LAZY_MAX and a previous hierarchy's hints (ipd_setup.hip amg_transfer)
-  head scans         N <= SCAN_HEAD_MAX (the consumers scan plain counts themselves)
+  lazy counts        N*Nc <= SPGEMM_LAZY_MAX and a previous hierarchy's hints (plan_transfer, csrc/ipd_setup_plan.h)
+  head scans         N <= SCAN_HEAD_MAX (the consumers scan plain counts themselves: plan_row_count)
   ScanTail products  N > SCAN_HEAD_MAX (the last workgroup scans the counts)
-  large mis_set      N > MIS_SMALL_ROWS or nnz > MIS_SMALL_NNZ (amg_mis_set instead of mis_set_small)
+  large mis_set      N > MIS_SMALL_ROWS or nnz > MIS_SMALL_NNZ (amg_mis_set instead of mis_set_small: plan_mis_small)
   split interpolation  nnz / N >= 256
 
 Every system asserts, from the ORACLE's hierarchy, that it reaches the gates it is listed for (`GATES`), so a
-moved threshold or a changed generator fails here instead of silently testing something else; the thresholds
-are mirrored below and test_thresholds_match_the_sources pins them to the sources (CPU only, like
-test_oracle_systems_reach_their_gates).
+moved threshold or a changed generator fails here instead of silently testing something else.  The thresholds
+and the three gate helpers below are the planner's own: tests/setup_plan_driver.cpp, built against the header the
+library compiles, reports its limits and the plan of a level shape, and test_planner_reports_the_gates holds the
+planner's decisions to what `GATES` asserts (CPU only, like test_oracle_systems_reach_their_gates).
 
 Oracle CPU time per call measured for this file (one x86 core): amg_setup 0.02 s (5 components) / 0.05-0.1 s
 (trees 1024-2048) / 0.36 s (tree 4096) / 0.45 s (Bernoulli 1024 and 2048) / 1.4 s (hub 1024, level 2 fully
 dense); Hybrid_AMG 0.07-0.75 s on the same systems; ASAt up to ~1 s at 4096 x 4096.  The GPU tests of the
 file (76) ran in 13 s on one MI355X, the two driver captures included."""
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -30,17 +29,15 @@ import scipy.sparse as sp
 
 from oracle import ipd_oracle as O
 from tests import problems as PR
+from tests import test_setup_plan as SP
 
 gpu = pytest.mark.gpu
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                    "codes_of_ipd_ssn_amg_method_amd", "csrc")
 
-# thresholds mirrored from the sources (test_thresholds_match_the_sources checks them)
-SPGEMM_LAZY_MAX = 1 << 21     # csrc/ipd_internal.h:546  (lazy: ipd_setup.hip:1268-1270, :1329-1331, :1496-1497)
-SCAN_HEAD_MAX = 4096          # csrc/ipd_internal.h:461  (ipd_sparse.hip:804, ipd_setup.hip:1351)
-MIS_SMALL_ROWS = 1024         # csrc/ipd_setup.hip:257   (mis_set_small's gate: ipd_setup.hip:520)
-MIS_SMALL_NNZ = 40000         # csrc/ipd_setup.hip:258
-SPLIT_ROW = 256.0             # csrc/ipd_setup.hip:1343  (split interpolation by default)
+# the thresholds, from the planner (the `limits` line of tests/setup_plan_driver.cpp)
+SPGEMM_LAZY_MAX = SP.limits()["SPGEMM_LAZY_MAX"]
+SCAN_HEAD_MAX = SP.limits()["SCAN_HEAD_MAX"]
+MIS_SMALL_ROWS = SP.limits()["MIS_SMALL_ROWS"]
+MIS_SMALL_NNZ = SP.limits()["MIS_SMALL_NNZ"]
 
 
 @pytest.fixture(scope="module")
@@ -148,19 +145,27 @@ def assert_same_hierarchy(h, ho, rng, tag):
 # the gates each system is listed for, read off the oracle's hierarchy.  Level k (1-based) has N = sizes[k-1]
 # rows and nnz[k-1] entries; its transfer builds a P of N x Nc with Nc = sizes[k].
 # ---------------------------------------------------------------------------------------------------------------
+ANY_HINTS = (1, 1, 1, 1)   # the size part of a gate: what the planner says once a previous hierarchy left counts
+
+
+def level_plan(sizes, nnz, k, hints=ANY_HINTS):
+    """The planner's record of the transfer out of level k (level 1 is the bigraph level, as in every hierarchy
+    of this file)."""
+    z = nnz[k - 1] if nnz is not None else sizes[k - 1]
+    return SP.transfer(k, sizes[k - 1], z, sizes[k], hints, bigph=1, fnode=sizes[0] - sizes[1])
+
+
 def lazy_bounds_ok(sizes, k):
     """The size part of the lazy-count choice for the transfer out of level k (the hints are the other part)."""
-    N, Nc = sizes[k - 1], sizes[k]
-    ok = N * Nc <= SPGEMM_LAZY_MAX and Nc * Nc <= SPGEMM_LAZY_MAX
-    return ok and (k > 1 or N <= SCAN_HEAD_MAX)       # level 1 (bigraph): ipd_setup.hip:1268-1270
+    return level_plan(sizes, None, k)["lazy"] == 1
 
 
 def large_mis(sizes, nnz, k):
-    return sizes[k - 1] > MIS_SMALL_ROWS or nnz[k - 1] > MIS_SMALL_NNZ
+    return level_plan(sizes, nnz, k)["mis_small"] == 0
 
 
 def split_interp(sizes, nnz, k):
-    return nnz[k - 1] / sizes[k - 1] >= SPLIT_ROW
+    return level_plan(sizes, nnz, k)["form"] == "SPLIT"
 
 
 def _g_tree1024(s, z, nc):      # level 1 lazy with N*Nc = 2^21 exactly
@@ -219,29 +224,55 @@ def assert_gates(name, ho, ncomp):
     GATES[name](ho.level_sizes(), ho.level_nnz(), ncomp)
 
 
-def test_thresholds_match_the_sources():
-    def src(f):
-        with open(os.path.join(CSRC, f)) as fh:
-            return fh.read()
-    internal, setup, sparse = src("ipd_internal.h"), src("ipd_setup.hip"), src("ipd_sparse.hip")
-    assert re.search(r"constexpr size_t SPGEMM_LAZY_MAX = size_t\(1\) << 21;", internal)
-    assert 1 << 21 == SPGEMM_LAZY_MAX
-    assert re.search(r"constexpr int SCAN_HEAD_MAX = %d;" % SCAN_HEAD_MAX, internal)
-    assert re.search(r"constexpr int MIS_SMALL_ROWS = %d;" % MIS_SMALL_ROWS, setup)
-    assert re.search(r"constexpr int MIS_SMALL_NNZ = %d;" % MIS_SMALL_NNZ, setup)
-    assert "if (N > MIS_SMALL_ROWS || A.nnz > MIS_SMALL_NNZ || N < 1) return false;" in setup
-    assert "bool split = (double)A.nnz / std::max(N, 1) >= %.1f;" % SPLIT_ROW in setup
-    assert "const bool head_ok = total_dev && nr <= SCAN_HEAD_MAX;" in sparse
-    assert "N <= SCAN_HEAD_MAX && (size_t)N * (size_t)P.nc <= SPGEMM_LAZY_MAX" in setup
-    assert "(size_t)N * (size_t)Nc <= SPGEMM_LAZY_MAX" in setup
+@functools.lru_cache(maxsize=None)
+def oracle_hierarchy_cpu(name):
+    """The oracle's hierarchy of a system of SYSTEMS with isnsp = 1 (no device: the captured Newton systems
+    are not for this)."""
+    Ae, fnode, _ = system(name)
+    return O.amg_setup(Ae, setup_options(fnode, 1), O.matlab_rng())
+
+
+# what GATES asserts of each system, as the planner's decisions: per level (form, mis_set in one launch, lazy
+# with hints, P's row-count mode with hints and without); None: the gate does not speak of that level
+PLANNED_GATES = {
+    "tree1024": {1: ("BIGRAPH", None, 1, "HEAD", "TAIL_WAIT")},              # lazy at N*Nc = 2^21 exactly
+    "tree1024x1025": {1: ("BIGRAPH", None, 0, "TAIL_WAIT", "TAIL_WAIT")},    # just over: counted, hints or not
+    "hub1024": {2: ("SPLIT", 0, 1, "HEAD", "TAIL_WAIT")},                    # split, large mis_set by entries
+    "bern1024": {2: ("SPLIT", 0, 1, "HEAD", "TAIL_WAIT")},                   # split, large mis_set, lazy
+    "tree2048": {1: ("BIGRAPH", None, 0, "TAIL_WAIT", "TAIL_WAIT"),          # N = SCAN_HEAD_MAX, but 2^23 dense
+                 2: ("WAVE", 0, 1, "HEAD", "SCAN_TOTAL")},                   # large mis_set by rows
+    "tree2048x2049": {1: ("BIGRAPH", None, 0, "TAIL_WAIT", "TAIL_WAIT")},
+    "bern2048": {2: ("SPLIT", 0, 1, "HEAD", "TAIL_WAIT")},
+    "tree4096": {1: ("BIGRAPH", None, 0, "TAIL_WAIT", "TAIL_WAIT"),          # counted through ScanTail
+                 2: ("WAVE", 0, 0, "SCAN_TOTAL", "SCAN_TOTAL")},             # head-scan size, but not lazy
+    "comp2048": {k: ("WAVE", 1, 1, "HEAD", "SCAN_TOTAL") for k in range(3, 7)},   # the small levels of seven
+}
+
+
+def test_planner_reports_the_gates():
+    """The rule behind every gate is run, not read: on the oracle's level shapes of every system the planner
+    takes the paths `GATES` lists the system for, with hints (the second and third build of
+    test_setup_at_the_gates) and without (the first)."""
+    assert set(PLANNED_GATES) == set(SYSTEMS)
+    for name in SYSTEMS:
+        ho = oracle_hierarchy_cpu(name)
+        sizes, nnz = ho.level_sizes(), ho.level_nnz()
+        assert_gates(name, ho, system(name)[2])
+        for k, (form, small, lazy, rows_hinted, rows_counted) in PLANNED_GATES[name].items():
+            h, c = level_plan(sizes, nnz, k), level_plan(sizes, nnz, k, (0, 0, 0, 0))
+            assert (h["form"], h["lazy"], h["lazy_prod"], h["rows"]) == (form, lazy, lazy, rows_hinted), (name, k, h)
+            assert (c["form"], c["lazy"], c["lazy_prod"], c["rows"]) == (form, 0, 0, rows_counted), (name, k, c)
+            if small is not None:
+                assert h["mis_small"] == c["mis_small"] == small, (name, k, h)
+    # the thresholds the gates were written against
+    assert (SPGEMM_LAZY_MAX, SCAN_HEAD_MAX, MIS_SMALL_ROWS, MIS_SMALL_NNZ) == (1 << 21, 4096, 1024, 40000)
+    assert SP.limits()["SPLIT_ROW_MIN"] == 256
 
 
 @pytest.mark.parametrize("name", list(SYSTEMS))
 def test_oracle_systems_reach_their_gates(name):
     """The gate half of test_setup_at_the_gates, oracle only (the captured Newton systems need the device)."""
-    Ae, fnode, ncomp = system(name)
-    ho = O.amg_setup(Ae, setup_options(fnode, 1), O.matlab_rng())
-    assert_gates(name, ho, ncomp)
+    assert_gates(name, oracle_hierarchy_cpu(name), system(name)[2])
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -415,9 +446,10 @@ MIS_CASES = [(1024, 40000), (1024, 40002), (1025, 39999), (1025, 40001)]
 def test_mis_set_and_transfer_at_the_small_gate(ipd, N, nnz, isnsp):
     """mis_set against the oracle (C, F, As, random numbers consumed), and a non-bigraph transfer, which takes
     the one-launch mis_set_small exactly when N <= MIS_SMALL_ROWS and nnz <= MIS_SMALL_NNZ
-    (ipd_setup.hip:520): one case inside, three just outside."""
+    (plan_mis_small, csrc/ipd_setup_plan.h): one case inside, three just outside."""
     A = laplacian_with_nnz(N, nnz)
     assert (N > MIS_SMALL_ROWS or nnz > MIS_SMALL_NNZ) == ((N, nnz) != (1024, 40000))
+    assert SP.transfer(2, N, nnz, N // 2)["mis_small"] == ((N, nnz) == (1024, 40000))
     refC, refF, refAs, info = O.mis_set(A, 0.25, O.matlab_rng())
     rng = ipd.MatlabRand()
     gotC, gotF, gotAs = ipd.mis_set(A, 0.25, rng)
