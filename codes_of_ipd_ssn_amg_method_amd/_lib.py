@@ -81,6 +81,15 @@ class ipd_plan_stats(Structure):
                 ("max_dropped", c_double), ("fval_kept", c_double)]
 
 
+class ipd_cost_spec(Structure):
+    _fields_ = [("metric", c_int32), ("dim", c_int32), ("m", c_int64), ("n", c_int64),
+                ("xs", POINTER(c_double)), ("ys", POINTER(c_double)), ("scale", c_int32)]
+
+
+class ipd_cost_stats(Structure):
+    _fields_ = [("min", c_double), ("max", c_double), ("sum", c_double)]
+
+
 class ipd_apd_result(Structure):
     _fields_ = [("converged", c_int32), ("k", c_int32), ("fval", c_double),
                 ("kkt", c_double * 4), ("rr", c_double), ("sum_amg", c_int64),
@@ -122,6 +131,9 @@ lib.ipd_amg_pcg_multi_dev.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_vo
 lib.ipd_apd_plan.argtypes = [c_void_p, c_double, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_plan_dev.argtypes = [c_void_p, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_set_plan.argtypes = [c_void_p, c_void_p]
+lib.ipd_cost_points_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_create_points.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_get_cost.argtypes = [c_void_p, c_void_p, c_void_p]
 
 # every symbol the header declares (tests check that they all resolve)
 EXPORTS = [
@@ -148,6 +160,7 @@ EXPORTS = [
     "ipd_aug_pcg", "ipd_pcg4pot", "ipd_spd_solve", "ipd_amg_resident_levels", "ipd_amg_resident_kernel", "ipd_amg_level_forms", "ipd_amg_poly_operator",
     "ipd_amg_packed_operator",
     "ipd_apd_plan", "ipd_apd_plan_dev", "ipd_apd_set_plan",
+    "ipd_cost_points_dev", "ipd_apd_create_points", "ipd_apd_get_cost",
 ]
 
 

@@ -31,6 +31,7 @@ __all__ = [
     "warmup_class2", "APD_SsN_Class1", "APD_SsN_Class2", "twogrid_bigph", "twogrid", "Hybrid_twogrid",
     "aug_PCG", "PCG4POT", "load_input", "sparse_multiply", "spd_solve", "AMG_PCG",
     "Class_AMG_multi", "AMG_PCG_multi", "Hybrid_AMG_PCG",
+    "point_cost", "APD_SsN_Class1_points", "APD_SsN_Class2_points",
 ]
 
 
@@ -724,17 +725,30 @@ class APDWorkspace:
     def __init__(self, cls, c, r, l, p, q, gama=np.inf, mu=0.0, phi=None, ctx=None):
         # ctx: an own L.Context (own HIP stream and arenas) lets several workspaces run
         # concurrently from several host threads; default = the process-wide context
+        c_ = f64(c)
+        d = self._data(cls, r, l, p, q, gama, mu, phi, ctx)
+        if c_.size != self.m * self.n:
+            raise ValueError("APDWorkspace: need length(l)=length(p)=m, length(r)=length(q)=n, "
+                             "length(c)=m*n")
+        if self.cls == 2 and phi is None:
+            raise ValueError("class 2 needs phi")
+        self._keep.append(c_)
+        d.c = dptr(c_)
+        check(lib.ipd_apd_create((ctx or get_ctx()).handle, byref(d), byref(self.handle)))
+
+    def _data(self, cls, r, l, p, q, gama, mu, phi, ctx) -> L.ipd_apd_data:
+        """Everything of ``ipd_apd_data`` but ``c``; sets the sizes and an empty handle."""
         self._ctx = ctx
         self.cls = int(cls)
-        self._keep = [f64(c), f64(r), f64(l), f64(p), f64(q)]
-        c_, r_, l_, p_, q_ = self._keep
+        self._keep = [f64(r), f64(l), f64(p), f64(q)]
+        r_, l_, p_, q_ = self._keep
         m, n = p_.size, q_.size
-        if l_.size != m or r_.size != n or c_.size != m * n:
+        if l_.size != m or r_.size != n:
             raise ValueError("APDWorkspace: need length(l)=length(p)=m, length(r)=length(q)=n, "
                              "length(c)=m*n")
         d = L.ipd_apd_data()
         d.cls, d.m, d.n = self.cls, m, n
-        d.c, d.r, d.l, d.p, d.q = dptr(c_), dptr(r_), dptr(l_), dptr(p_), dptr(q_)
+        d.r, d.l, d.p, d.q = dptr(r_), dptr(l_), dptr(p_), dptr(q_)
         d.mu = float(mu)
         d.gama_scalar = np.inf
         if self.cls == 1:
@@ -746,9 +760,7 @@ class APDWorkspace:
                     raise ValueError("gama must be a scalar or an m*n vector")
                 self._keep.append(g)
                 d.gama = dptr(g)
-        else:
-            if phi is None:
-                raise ValueError("class 2 needs phi")
+        elif phi is not None:
             ph = f64(phi)
             if ph.size != m * n:
                 raise ValueError("phi must have m*n entries")
@@ -759,7 +771,31 @@ class APDWorkspace:
         self.L = self.M + (1 if self.cls == 2 else 0)
         self.U = m * n + (self.M if self.cls == 2 else 0)
         self.handle = c_void_p()
-        check(lib.ipd_apd_create((ctx or get_ctx()).handle, byref(d), byref(self.handle)))
+        return d
+
+    @classmethod
+    def from_points(klass, cls, xs, ys, r, l, p, q, metric="sqeuclidean", scale=False, gama=np.inf,
+                    mu=0.0, phi=None, ctx=None):
+        """The workspace of problem class ``cls`` with ``c = point_cost(xs, ys, metric, scale)`` built on
+        the device (``ipd_apd_create_points``): (m+n)*d coordinates go up, nothing mn-sized.  ``xs`` is
+        (m, d), ``ys`` (n, d), one point per row (1-D for d = 1); class 2 with ``phi=None`` takes
+        ``phi`` as all ones."""
+        self = klass.__new__(klass)
+        d = self._data(cls, r, l, p, q, gama, mu, phi, ctx)
+        spec, keep = _cost_spec(xs, ys, metric, scale)
+        if (spec.m, spec.n) != (self.m, self.n):
+            raise ValueError(f"from_points: xs, ys must hold {self.m} and {self.n} points")
+        check(lib.ipd_apd_create_points((ctx or get_ctx()).handle, byref(d), byref(spec), byref(self.handle)))
+        return self
+
+    def cost(self, stats: bool = False):
+        """``c`` as an (m, n) array, read back from the workspace (``ipd_apd_get_cost``);
+        ``stats=True`` -> ``(c, dict(min, max, sum))``, the statistics computed on the device."""
+        c = np.empty(self.m * self.n)
+        st = L.ipd_cost_stats()
+        check(lib.ipd_apd_get_cost(self.handle, dptr(c), byref(st) if stats else None))
+        C = c.reshape(self.n, self.m).T
+        return (C, _cost_stats(st)) if stats else C
 
     def close(self):
         if getattr(self, "handle", None):
@@ -1001,6 +1037,73 @@ def APD_SsN_Class2(c, r, l, p, q, mu, phi, rng: MatlabRand | None = None,
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=40, theta=1 / 4, smoth=10, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     ws = APDWorkspace(2, c, r, l, p, q, mu=mu, phi=phi)
+    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol)
+
+
+# ---------------------------------------------------------------------------
+# the cost out of point clouds
+# ---------------------------------------------------------------------------
+COST_METRICS = {"sqeuclidean": 1, "euclidean": 2, "cityblock": 3, "chebyshev": 4}
+
+
+def _cost_stats(st: L.ipd_cost_stats) -> dict:
+    return dict(min=st.min, max=st.max, sum=st.sum)
+
+
+def _cost_spec(xs, ys, metric, scale):
+    """``ipd_cost_spec`` of (m, d) / (n, d) point arrays (1-D: d = 1), made coordinate-major, and the
+    arrays it points to."""
+    if metric not in COST_METRICS:
+        raise ValueError(f"metric must be one of {sorted(COST_METRICS)}")
+    X, Y = np.asarray(xs, dtype=np.float64), np.asarray(ys, dtype=np.float64)
+    X = X[:, None] if X.ndim == 1 else X
+    Y = Y[:, None] if Y.ndim == 1 else Y
+    if X.ndim != 2 or Y.ndim != 2 or X.shape[1] != Y.shape[1]:
+        raise ValueError("xs must be (m, d) and ys (n, d), one point per row")
+    keep = [np.ascontiguousarray(X.T).reshape(-1), np.ascontiguousarray(Y.T).reshape(-1)]
+    spec = L.ipd_cost_spec()
+    spec.metric, spec.dim = COST_METRICS[metric], X.shape[1]
+    spec.m, spec.n = X.shape[0], Y.shape[0]
+    spec.xs, spec.ys = dptr(keep[0]), dptr(keep[1])
+    spec.scale = 1 if scale else 0
+    return spec, keep
+
+
+def point_cost(xs, ys, metric="sqeuclidean", scale=False, stats=False, ctx=None):
+    """The (m, n) cost matrix of two point clouds, computed on the device (``ipd_cost_points_dev``):
+    ``metric`` in ``sqeuclidean, euclidean, cityblock, chebyshev``; ``scale`` divides by the largest
+    entry.  ``stats=True`` -> ``(c, dict(min, max, sum))``."""
+    spec, keep = _cost_spec(xs, ys, metric, scale)
+    ctx = ctx or get_ctx()
+    m, n = int(spec.m), int(spec.n)
+    buf = L.DeviceBuffer(8 * max(m * n, 1), ctx)
+    try:
+        st = L.ipd_cost_stats()
+        check(lib.ipd_cost_points_dev(ctx.handle, byref(spec), buf.ptr, byref(st)))
+        C = buf.to_array(np.float64, m * n).reshape(n, m).T
+    finally:
+        buf.free()
+    return (C, _cost_stats(st)) if stats else C
+
+
+def APD_SsN_Class1_points(xs, ys, r, l, p, q, metric="sqeuclidean", scale=False, gama=np.inf, prob=2,
+                          rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
+                          plan_tol=None, **opts) -> dict:
+    """``APD_SsN_Class1`` with ``c = point_cost(xs, ys, metric, scale)`` built on the device."""
+    amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=30, theta=1 / 4, smoth=5, cycle="w",
+                                isnsp=1, inter=1, guess=None)
+    warm = (0.0, 100) if prob > 0 else (5e-2, np.inf)
+    ws = APDWorkspace.from_points(1, xs, ys, r, l, p, q, metric=metric, scale=scale, gama=gama)
+    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol)
+
+
+def APD_SsN_Class2_points(xs, ys, r, l, p, q, mu, phi=None, metric="sqeuclidean", scale=False,
+                          rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
+                          plan_tol=None, **opts) -> dict:
+    """``APD_SsN_Class2`` with the cost built on the device; ``phi=None`` is all ones."""
+    amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=40, theta=1 / 4, smoth=10, cycle="w",
+                                isnsp=1, inter=1, guess=None)
+    ws = APDWorkspace.from_points(2, xs, ys, r, l, p, q, metric=metric, scale=scale, mu=mu, phi=phi)
     return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol)
 
 

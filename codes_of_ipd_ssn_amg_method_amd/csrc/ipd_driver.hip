@@ -26,6 +26,7 @@
 
 #include "ipd_amg_internal.h"
 #include "ipd_cycle_dev.h"
+#include "ipd_cost.h"
 #include "ipd_plan.h"
 
 namespace {
@@ -994,6 +995,8 @@ struct ipd_apd {
     bool merit3 = false;   // class 1, prob 3: the merit needs |zk|^2 and |zk - prox(zk)|^2 (:186)
     double *phi_l = nullptr, *phi_part = nullptr;  // Ax(phi), partial sums of |phi|^2
     int phi_npart = 0;
+    ipd_cost_stats cost_stats{};   // min, max, sum of c: from the build out of points, or on demand (ipd_apd_get_cost)
+    bool have_cost_stats = false;
     // script variables
     int k = 0;
     double bk = 1.0;
@@ -1612,101 +1615,109 @@ extern "C" void ipd_apd_opts_init(int32_t cls, ipd_apd_opts* o) {
     o->pcg_maxit = 10000;
 }
 
+// The one body of ipd_apd_create and ipd_apd_create_points (ipd_cost.hip): fill == nullptr takes c (and phi) from
+// the host arrays of *d, otherwise fill makes them on the device.
+void apd_create_common(ipd_ctx* ctx, const ipd_apd_data* d, const ApdCostFill* fill, ipd_apd** out) {
+    IPD_REQUIRE(ctx && d && out, IPD_E_ARG, "NULL argument");
+    IPD_REQUIRE(d->cls == 1 || d->cls == 2, IPD_E_ARG, "cls must be 1 or 2");
+    IPD_REQUIRE(d->m > 0 && d->n > 0 && d->m <= IPD_APD_SIDE_MAX && d->n <= IPD_APD_SIDE_MAX, IPD_E_LIMIT,
+                "m, n must be in [1, 16384]");
+    IPD_REQUIRE((fill || d->c) && d->r && d->l && d->p && d->q, IPD_E_ARG, "NULL problem vector");
+    IPD_REQUIRE(d->cls == 1 || d->phi || fill, IPD_E_ARG, "class 2 needs phi");
+    ctx->set_device();
+    std::unique_ptr<ipd_apd> h(new ipd_apd);
+    h->ctx = ctx;
+    h->arena.reset(new Arena(&ctx->pool));
+    Arena& A = *h->arena;
+    const int m = (int)d->m, n = (int)d->n;
+    h->cls = d->cls;
+    h->m = m;
+    h->n = n;
+    h->M = m + n;
+    h->L = h->M + (d->cls == 2 ? 1 : 0);
+    h->mn = (size_t)m * n;
+    h->U = h->mn + (d->cls == 2 ? (size_t)h->M : 0);
+    h->mu = d->mu;
+    h->geo = make_geo(m, n);
+    const size_t mn = h->mn, U = h->U;
+    const int L = h->L;
+    h->c = A.alloc<double>(mn);
+    h->p = A.alloc<double>((size_t)m);
+    h->q = A.alloc<double>((size_t)n);
+    h->b = A.alloc<double>((size_t)L);
+    if (!fill) ctx->upload(h->c, d->c, mn);
+    ctx->upload(h->p, d->p, (size_t)m);
+    ctx->upload(h->q, d->q, (size_t)n);
+    ctx->upload(h->b, d->r, (size_t)n);            // b = [r;l(;mu)]  (:33 / Class2 :29)
+    ctx->upload(h->b + n, d->l, (size_t)m);
+    if (d->cls == 2) {
+        ctx->upload(h->b + h->M, &d->mu, 1);
+        h->phi = A.alloc<double>(mn);
+        if (d->phi) ctx->upload(h->phi, d->phi, mn);
+        h->tmask = A.alloc<double>((size_t)h->M);
+        h->phi_l = A.alloc<double>((size_t)h->M);
+        h->phi_part = A.alloc<double>(1024);
+    } else if (d->gama) {
+        h->gama = A.alloc<double>(mn);
+        ctx->upload(h->gama, d->gama, mn);
+    }
+    h->u = A.alloc<double>(U);
+    h->u2 = A.alloc<double>(U);
+    h->v = A.alloc<double>(U);
+    h->w = A.alloc<double>(U);
+    for (double* a : {h->u, h->u2, h->v, h->w})
+        IPD_HIP(hipMemsetAsync(a, 0, U * sizeof(double), ctx->stream));
+    h->lam = A.alloc<double>((size_t)L);
+    h->lam_a = A.alloc<double>((size_t)L);
+    h->lam_b = A.alloc<double>((size_t)L);
+    h->wlk = A.alloc<double>((size_t)L);
+    h->F_a = A.alloc<double>((size_t)L);
+    h->F_b = A.alloc<double>((size_t)L);
+    h->zeta = A.alloc<double>((size_t)L);
+    h->negF = A.alloc<double>((size_t)L);
+    for (double* a : {h->lam, h->lam_a, h->lam_b, h->wlk, h->F_a, h->F_b, h->zeta, h->negF})
+        IPD_HIP(hipMemsetAsync(a, 0, (size_t)L * sizeof(double), ctx->stream));
+    h->s_words = (mn + 7) / 8;                      // compared in 8-byte words (row f3)
+    h->s = A.alloc<uint8_t>(h->s_words * 8);
+    IPD_HIP(hipMemsetAsync(h->s, 0, h->s_words * 8, ctx->stream));
+    h->s_prev = A.alloc<unsigned long long>(h->s_words);
+    if (d->cls == 2) h->t_prev = A.alloc<unsigned long long>((size_t)h->M);
+    h->step_changed = A.alloc<int>(1);
+    h->step_reuse = !switch_on("IPD_NO_STEP_DONOR");
+    const Geo& g = h->geo;
+    h->lpart = A.alloc<double>((size_t)g.njg * m);
+    h->rpart = A.alloc<double>((size_t)g.nib * 4 * n);
+    IPD_HIP(hipMemsetAsync(h->rpart, 0, sizeof(double) * (size_t)g.nib * 4 * n, ctx->stream));
+    h->spart = A.alloc<double>((size_t)g.nib * g.njg * NSC);
+    h->dscal = reinterpret_cast<ApdScal*>(A.alloc<double>(sizeof(ApdScal) / sizeof(double) + 1));
+    h->fpart = A.alloc<double>((size_t)cdiv(L, EB) * NFS);
+    h->merit = A.alloc<double>(MK);
+    h->counter = A.alloc<int>(4);
+    IPD_HIP(hipMemsetAsync(h->counter, 0, 16, ctx->stream));
+    Prob& P = h->P;
+    P.cls2 = d->cls == 2 ? 1 : 0;
+    P.m = m;
+    P.n = n;
+    P.p = h->p;
+    P.q = h->q;
+    P.c = h->c;
+    P.phi = h->phi;
+    P.gama = h->gama;
+    P.gs = d->cls == 2 ? std::numeric_limits<double>::infinity() : d->gama_scalar;
+    if (fill) {
+        (*fill)(h->c, d->cls == 2 && !d->phi ? h->phi : nullptr, &h->cost_stats);
+        h->have_cost_stats = true;
+    }
+    if (d->cls == 2) {
+        CallScope scope(ctx);
+        h->phi_npart = kkt_phi_consts(ctx, h->phi, h->p, h->q, m, n, h->phi_l, h->phi_part);
+    }
+    ctx->sync();
+    *out = h.release();
+}
+
 extern "C" int ipd_apd_create(ipd_ctx* ctx, const ipd_apd_data* d, ipd_apd** out) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(ctx && d && out, IPD_E_ARG, "NULL argument");
-        IPD_REQUIRE(d->cls == 1 || d->cls == 2, IPD_E_ARG, "cls must be 1 or 2");
-        IPD_REQUIRE(d->m > 0 && d->n > 0 && d->m <= 16384 && d->n <= 16384, IPD_E_LIMIT,
-                    "m, n must be in [1, 16384]");
-        IPD_REQUIRE(d->c && d->r && d->l && d->p && d->q, IPD_E_ARG, "NULL problem vector");
-        IPD_REQUIRE(d->cls == 1 || d->phi, IPD_E_ARG, "class 2 needs phi");
-        ctx->set_device();
-        std::unique_ptr<ipd_apd> h(new ipd_apd);
-        h->ctx = ctx;
-        h->arena.reset(new Arena(&ctx->pool));
-        Arena& A = *h->arena;
-        const int m = (int)d->m, n = (int)d->n;
-        h->cls = d->cls;
-        h->m = m;
-        h->n = n;
-        h->M = m + n;
-        h->L = h->M + (d->cls == 2 ? 1 : 0);
-        h->mn = (size_t)m * n;
-        h->U = h->mn + (d->cls == 2 ? (size_t)h->M : 0);
-        h->mu = d->mu;
-        h->geo = make_geo(m, n);
-        const size_t mn = h->mn, U = h->U;
-        const int L = h->L;
-        h->c = A.alloc<double>(mn);
-        h->p = A.alloc<double>((size_t)m);
-        h->q = A.alloc<double>((size_t)n);
-        h->b = A.alloc<double>((size_t)L);
-        ctx->upload(h->c, d->c, mn);
-        ctx->upload(h->p, d->p, (size_t)m);
-        ctx->upload(h->q, d->q, (size_t)n);
-        ctx->upload(h->b, d->r, (size_t)n);            // b = [r;l(;mu)]  (:33 / Class2 :29)
-        ctx->upload(h->b + n, d->l, (size_t)m);
-        if (d->cls == 2) {
-            ctx->upload(h->b + h->M, &d->mu, 1);
-            h->phi = A.alloc<double>(mn);
-            ctx->upload(h->phi, d->phi, mn);
-            h->tmask = A.alloc<double>((size_t)h->M);
-            h->phi_l = A.alloc<double>((size_t)h->M);
-            h->phi_part = A.alloc<double>(1024);
-        } else if (d->gama) {
-            h->gama = A.alloc<double>(mn);
-            ctx->upload(h->gama, d->gama, mn);
-        }
-        h->u = A.alloc<double>(U);
-        h->u2 = A.alloc<double>(U);
-        h->v = A.alloc<double>(U);
-        h->w = A.alloc<double>(U);
-        for (double* a : {h->u, h->u2, h->v, h->w})
-            IPD_HIP(hipMemsetAsync(a, 0, U * sizeof(double), ctx->stream));
-        h->lam = A.alloc<double>((size_t)L);
-        h->lam_a = A.alloc<double>((size_t)L);
-        h->lam_b = A.alloc<double>((size_t)L);
-        h->wlk = A.alloc<double>((size_t)L);
-        h->F_a = A.alloc<double>((size_t)L);
-        h->F_b = A.alloc<double>((size_t)L);
-        h->zeta = A.alloc<double>((size_t)L);
-        h->negF = A.alloc<double>((size_t)L);
-        for (double* a : {h->lam, h->lam_a, h->lam_b, h->wlk, h->F_a, h->F_b, h->zeta, h->negF})
-            IPD_HIP(hipMemsetAsync(a, 0, (size_t)L * sizeof(double), ctx->stream));
-        h->s_words = (mn + 7) / 8;                      // compared in 8-byte words (row f3)
-        h->s = A.alloc<uint8_t>(h->s_words * 8);
-        IPD_HIP(hipMemsetAsync(h->s, 0, h->s_words * 8, ctx->stream));
-        h->s_prev = A.alloc<unsigned long long>(h->s_words);
-        if (d->cls == 2) h->t_prev = A.alloc<unsigned long long>((size_t)h->M);
-        h->step_changed = A.alloc<int>(1);
-        h->step_reuse = !switch_on("IPD_NO_STEP_DONOR");
-        const Geo& g = h->geo;
-        h->lpart = A.alloc<double>((size_t)g.njg * m);
-        h->rpart = A.alloc<double>((size_t)g.nib * 4 * n);
-        IPD_HIP(hipMemsetAsync(h->rpart, 0, sizeof(double) * (size_t)g.nib * 4 * n, ctx->stream));
-        h->spart = A.alloc<double>((size_t)g.nib * g.njg * NSC);
-        h->dscal = reinterpret_cast<ApdScal*>(A.alloc<double>(sizeof(ApdScal) / sizeof(double) + 1));
-        h->fpart = A.alloc<double>((size_t)cdiv(L, EB) * NFS);
-        h->merit = A.alloc<double>(MK);
-        h->counter = A.alloc<int>(4);
-        IPD_HIP(hipMemsetAsync(h->counter, 0, 16, ctx->stream));
-        Prob& P = h->P;
-        P.cls2 = d->cls == 2 ? 1 : 0;
-        P.m = m;
-        P.n = n;
-        P.p = h->p;
-        P.q = h->q;
-        P.c = h->c;
-        P.phi = h->phi;
-        P.gama = h->gama;
-        P.gs = d->cls == 2 ? std::numeric_limits<double>::infinity() : d->gama_scalar;
-        if (d->cls == 2) {
-            CallScope scope(ctx);
-            h->phi_npart = kkt_phi_consts(ctx, h->phi, h->p, h->q, m, n, h->phi_l, h->phi_part);
-        }
-        ctx->sync();
-        *out = h.release();
-    });
+    return ipd_guard([&] { apd_create_common(ctx, d, nullptr, out); });
 }
 
 extern "C" void ipd_apd_destroy(ipd_apd* h) {
@@ -1758,6 +1769,18 @@ void apd_restart_script(ipd_apd* h) {
     h->recs.clear();
     h->sum_amg = h->total_amg = h->fail_amg = h->max_amg = 0;
     h->restarts = 0;
+}
+
+ApdCostView apd_cost_view(ipd_apd* h) {
+    ApdCostView w;
+    w.ctx = h->ctx;
+    w.m = h->m;
+    w.n = h->n;
+    w.mn = h->mn;
+    w.c = h->c;
+    w.stats = &h->cost_stats;
+    w.have_stats = &h->have_cost_stats;
+    return w;
 }
 
 ApdPlanView apd_plan_view(ipd_apd* h) {

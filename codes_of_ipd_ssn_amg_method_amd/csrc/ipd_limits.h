@@ -49,6 +49,11 @@ static constexpr int SPGEMM_COLS_MAX = 16384;                // columns of a row
 static constexpr int XFER_COARSE_MAX = 8192;                 // coarse nodes of a non-bigraph level (two LDS rows in k_build_W*)
 static constexpr int XFER_HINT_LEVELS = 40;                  // levels ipd_ctx::xfer_hint keeps the last hierarchy's counts of
 
+// the drivers (ipd_apd_create): rows and columns of the transport problem; the cost out of point clouds
+// (ipd_cost_plan.h): coordinates per point
+static constexpr int IPD_APD_SIDE_MAX = 16384;
+static constexpr int IPD_COST_DIM_MAX = 16;
+
 // levels a single-workgroup image (SolveDesc) holds
 static constexpr int SOLVE_ML = 24;
 // An LDS image (ipd_level_plan.h): the planner admits levels while the predicted dynamic LDS stays within the

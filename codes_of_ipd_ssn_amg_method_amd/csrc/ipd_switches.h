@@ -44,6 +44,7 @@ static constexpr SwitchInfo IPD_SWITCHES[] = {
     {"IPD_NO_DONOR", SW_FLAG, "AMG4POT's shared levels 1-2 off: the bit-identity tests"},
     {"IPD_NO_STEP_DONOR", SW_FLAG, "the drivers' step donors off: the bit-identity tests"},
     {"IPD_NO_POT_CONCURRENT", SW_FLAG, "AMG4POT's two concurrent solves off: the bit-identity tests"},
+    {"IPD_COST_STORE", SW_VALUE, "8|16: the store width of the point-cloud cost build where both are possible (measurement, tests)"},
     {"IPD_SHARD_EMULATE", SW_VALUE, "<G>: one process plays G row-block owners (the sharded path's test on one GPU)"},
     {"IPD_DEBUG_SKIP", SW_VALUE, "<mask>: timing by elimination inside the tail's sub-cycle (results void)"},
     {"IPD_PROFILE", SW_VALUE, "phase wall clocks (ipd_prof_read); on unless empty or starting with '0'"},

@@ -499,6 +499,37 @@ int ipd_apd_plan_dev(ipd_apd* h, double tol, int64_t cap, int64_t* jc_dev, int64
  * column.                                                                                        */
 int ipd_apd_set_plan(ipd_apd* h, const ipd_csc* X);
 
+/* The cost matrix built on the device from two point clouds: a driver run is created
+ * from (m+n)*d coordinates, nothing mn-sized crosses the host boundary.  With t_k = xs(i,k) - ys(j,k)
+ * folded in ascending k into an accumulator that starts at +0.0, multiply and add separate:
+ *   1  acc + t_k*t_k        2  the correctly rounded sqrt of metric 1
+ *   3  acc + |t_k|          4  max(acc, |t_k|)
+ * scale = 1 divides every entry by the largest entry of the unscaled matrix (one IEEE division).  */
+typedef struct ipd_cost_spec {
+    int32_t metric;      /* 1 sq. Euclidean, 2 Euclidean, 3 city block, 4 Chebyshev */
+    int32_t dim;         /* d, 1 .. 16                                               */
+    int64_t m, n;
+    const double* xs;    /* m*d, xs[i + k*m] (host)                                  */
+    const double* ys;    /* n*d, ys[j + k*n] (host)                                  */
+    int32_t scale;       /* 0 none, 1 divide by the largest entry                    */
+} ipd_cost_spec;
+typedef struct ipd_cost_stats { double min, max, sum; } ipd_cost_stats;  /* of what is stored */
+
+/* c_dev[i + j*m] (DEVICE, mn doubles) = the cost of spec *s; *st (or NULL) its statistics, the same
+ * bits on every call.  The (m+n)*d coordinates are checked on the host before any launch.  IPD_E_ARG
+ * for a NULL ctx, s, c_dev, xs or ys, an unknown metric, dim outside [1, 16], a scale other than 0 or
+ * 1, a coordinate that is not finite, and, with scale = 1, a largest entry that is 0 or not finite
+ * (c_dev is then unspecified); IPD_E_LIMIT for m or n outside [1, 16384].                         */
+int ipd_cost_points_dev(ipd_ctx*, const ipd_cost_spec* s, double* c_dev, ipd_cost_stats* st);
+/* ipd_apd_create with the cost made from *s: d->c must be NULL, s->m == d->m and s->n == d->n
+ * (IPD_E_ARG otherwise, and for everything ipd_cost_points_dev refuses); for class 2 a NULL d->phi
+ * is all ones, filled on the device.  Everything else as ipd_apd_create.  After an error *out is
+ * untouched and no workspace exists.                                                               */
+int ipd_apd_create_points(ipd_ctx*, const ipd_apd_data* d, const ipd_cost_spec* s, ipd_apd** out);
+/* The cost of any workspace: c (mn, host, or NULL) and its statistics (or NULL); a workspace made
+ * from a host c computes them at the first call.                                                   */
+int ipd_apd_get_cost(ipd_apd* h, double* c, ipd_cost_stats* st);
+
 /* Matrix-free level-1 operator.  If level 1 of `h` is exactly Hybrid_AMG's
  * rescaled operator Ae = bk1*Q0^2 + (Q0*T*Q0 + Q0*H0*Q0)/tk for these p, q, tk (checked entry by
  * entry against A_1's CSR values), the level-1 Gauss-Seidel sweeps read one BIT per entry (the

@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""The cost matrix built on the device from point clouds (csrc/ipd_cost.hip) against the route it replaces: the
+host builds c and the workspace uploads it.
+
+  python tools/bench_cost.py [--sizes 1024,4096,8192] [--reps 2] [--out FILE]
+
+d = 2, squared Euclidean, scale on and off, m = n.  Timed with a host clock around calls that end in a device
+synchronise, the variants alternating `--reps` times.  Per size:
+  (a) numpy_c        the host builds c with numpy (the reference of tests/test_gpu_cost.py)
+      from_matrix    APDWorkspace(1, c, ...): 8*mn bytes cross to the device
+  (b) from_points    APDWorkspace.from_points: (m+n)*d coordinates cross, c is made in HBM
+  (c) the kernel alone: ipd_cost_points_dev into a preallocated device array, 20 calls after a warm-up, for the
+      8-byte and the 16-byte store form (IPD_COST_STORE) and scale off and on, as bytes per second over the
+      8*mn bytes written (with scale the entries are computed twice and written once; a call also uploads the
+      coordinates, reduces the statistics and reads them back).  COPY_TBPS is the guide's measured rate of a
+      float4 copy on MI355X -- a read plus a write, named here for orientation; it is not a write ceiling.
+The condition of DESIGN.md section 4g: in every repetition (b) is faster than from_matrix alone.
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import codes_of_ipd_ssn_amg_method_amd as ipd   # noqa: E402
+from codes_of_ipd_ssn_amg_method_amd import _lib as L   # noqa: E402
+from codes_of_ipd_ssn_amg_method_amd.api import _cost_spec   # noqa: E402
+
+COPY_TBPS = 6.29
+
+
+def numpy_cost(xs, ys, scale):
+    acc = np.zeros((xs.shape[0], ys.shape[0]))
+    for k in range(xs.shape[1]):
+        t = xs[:, k][:, None] - ys[:, k][None, :]
+        acc = acc + t * t
+    return acc / acc.max() if scale else acc
+
+
+def clock(fn, inner=1):
+    ipd.get_ctx().sync()
+    t0 = time.perf_counter()
+    for _ in range(inner):
+        out = fn()
+    ipd.get_ctx().sync()
+    return (time.perf_counter() - t0) / inner, out
+
+
+def bench_size(N, reps, emit):
+    rs = np.random.RandomState(1)
+    xs, ys = rs.standard_normal((N, 2)), rs.standard_normal((N, 2))
+    r, l = rs.random_sample(N), rs.random_sample(N)
+    l = l * r.sum() / l.sum()
+    one = np.ones(N)
+    mn = N * N
+    for scale in (False, True):
+        t_np, c = clock(lambda: numpy_cost(xs, ys, scale))
+        c = np.asfortranarray(c).reshape(-1, order="F")
+
+        def from_matrix():
+            ipd.APDWorkspace(1, c, r, l, one, one, gama=np.inf).close()
+
+        def from_points():
+            ipd.APDWorkspace.from_points(1, xs, ys, r, l, one, one, metric="sqeuclidean", scale=scale).close()
+
+        variants = [("from_matrix", from_matrix), ("from_points", from_points)]
+        for _, fn in variants:       # every variant once before the clock runs
+            fn()
+        times = {name: [] for name, _ in variants}
+        for _ in range(reps):
+            for name, fn in variants:
+                times[name].append(clock(fn)[0])
+        # the results agree bit for bit
+        ws = ipd.APDWorkspace.from_points(1, xs, ys, r, l, one, one, metric="sqeuclidean", scale=scale)
+        same = bool(np.array_equal(ws.cost().reshape(-1, order="F").view(np.int64), c.view(np.int64)))
+        ws.close()
+        emit(dict(bench="cost_workspace", N=N, d=2, metric="sqeuclidean", scale=scale, numpy_c_seconds=round(t_np, 6),
+                  seconds={k: [round(t, 6) for t in v] for k, v in times.items()}, bit_equal_to_numpy=same,
+                  matrix_over_points=min(times["from_matrix"]) / min(times["from_points"]),
+                  points_faster_in_every_rep=bool(all(p < m for p, m in zip(times["from_points"], times["from_matrix"])))))
+        del c
+
+    # (c) the kernel alone
+    buf = L.DeviceBuffer(8 * mn)
+    ctx = ipd.get_ctx().handle
+    for scale in (False, True):
+        spec, keep = _cost_spec(xs, ys, "sqeuclidean", scale)
+        st = L.ipd_cost_stats()
+
+        def call():
+            L.check(L.lib.ipd_cost_points_dev(ctx, ctypes.byref(spec), buf.ptr, ctypes.byref(st)))
+
+        times = {"8": [], "16": []}
+        for form in times:           # warm-up of both forms
+            os.environ["IPD_COST_STORE"] = form
+            call()
+        for _ in range(reps):
+            for form in times:
+                os.environ["IPD_COST_STORE"] = form
+                times[form].append(clock(call, 20)[0])
+        os.environ.pop("IPD_COST_STORE", None)
+        emit(dict(bench="cost_kernel", N=N, d=2, metric="sqeuclidean", scale=scale, calls=20,
+                  seconds_per_call={k: [round(t, 8) for t in v] for k, v in times.items()},
+                  store8_TBps=8.0 * mn / min(times["8"]) / 1e12, store16_TBps=8.0 * mn / min(times["16"]) / 1e12,
+                  copy_read_plus_write_TBps=COPY_TBPS))
+    buf.free()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="1024,4096,8192")
+    ap.add_argument("--reps", type=int, default=2, help="alternating repetitions of the variants")
+    ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
+    a = ap.parse_args()
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+
+    for N in [int(s) for s in a.sizes.split(",") if s]:
+        bench_size(N, a.reps, emit)
+
+
+if __name__ == "__main__":
+    main()
