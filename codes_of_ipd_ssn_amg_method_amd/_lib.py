@@ -134,6 +134,11 @@ lib.ipd_apd_set_plan.argtypes = [c_void_p, c_void_p]
 lib.ipd_cost_points_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_create_points.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_get_cost.argtypes = [c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_get_w.argtypes = [c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_eval_trial.argtypes = [c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int32, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_merit.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_end.argtypes = [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
 
 # every symbol the header declares (tests check that they all resolve)
 EXPORTS = [
@@ -161,6 +166,7 @@ EXPORTS = [
     "ipd_amg_packed_operator",
     "ipd_apd_plan", "ipd_apd_plan_dev", "ipd_apd_set_plan",
     "ipd_cost_points_dev", "ipd_apd_create_points", "ipd_apd_get_cost",
+    "ipd_apd_get_w", "ipd_apd_eval_trial", "ipd_apd_merit", "ipd_apd_end",
 ]
 
 

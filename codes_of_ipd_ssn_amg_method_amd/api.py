@@ -971,6 +971,62 @@ class APDWorkspace:
         return dict(s=s.astype(bool), t=(t != 0) if self.cls == 2 else None, Fk=F, bk1=vals[0],
                     tk=vals[1], ak=vals[2], Fk_norm=vals[3], cFk=vals[4], E=int(vals[5]))
 
+    def _lam_sized(self, a, name):
+        a = f64(a)
+        if a.size != self.L:
+            raise ValueError(f"{name} must have {self.L} entries")
+        return a
+
+    def get_w(self):
+        """``(wk, wlk)`` as ``begin`` left them (``ipd_apd_get_w``)."""
+        w, wlk = np.empty(self.U), np.empty(self.L)
+        check(lib.ipd_apd_get_w(self.handle, w.ctypes.data, wlk.ctypes.data))
+        return w, wlk
+
+    def eval_trial(self, lam, zeta=None, step=0.0, Fk_old=None, merit3=False):
+        """``eval`` at the line search's trial point ``lam + step*zeta`` (``ipd_apd_eval_trial``):
+        what ``eval`` returns plus ``lam_out``, ``fold_zeta = Fk_old'*zeta``, the prob-3 sums
+        ``z2``, ``zmp2`` (``merit3=True``: ``cFk`` is that merit) and the raw sums ``lam2``,
+        ``wlk_lam``, ``prox2``."""
+        lam = self._lam_sized(lam, "lam")
+        zeta = self._lam_sized(zeta, "zeta") if zeta is not None else None
+        Fo = self._lam_sized(Fk_old, "Fk_old") if Fk_old is not None else None
+        s = np.empty(self.m * self.n, np.uint8)
+        t, F, lo = np.empty(self.M), np.empty(self.L), np.empty(self.L)
+        vals = np.empty(12)
+        check(lib.ipd_apd_eval_trial(self.handle, lam.ctypes.data, zeta.ctypes.data if zeta is not None else None,
+                                     c_double(float(step)), Fo.ctypes.data if Fo is not None else None,
+                                     c_int32(1 if merit3 else 0), s.ctypes.data,
+                                     t.ctypes.data if self.cls == 2 else None, F.ctypes.data, lo.ctypes.data,
+                                     vals.ctypes.data))
+        return dict(s=s.astype(bool), t=(t != 0) if self.cls == 2 else None, Fk=F, lam_out=lo, bk1=vals[0],
+                    tk=vals[1], ak=vals[2], Fk_norm=vals[3], cFk=vals[4], E=int(vals[5]), z2=vals[6],
+                    zmp2=vals[7], fold_zeta=vals[8], lam2=vals[9], wlk_lam=vals[10], prox2=vals[11])
+
+    def merit(self, lam, zeta, steps):
+        """The merit ``cFk`` at ``lam + steps[k]*zeta`` for the 8 trial steps of one line-search pass
+        (``ipd_apd_merit``)."""
+        lam, zeta, steps = self._lam_sized(lam, "lam"), self._lam_sized(zeta, "zeta"), f64(steps)
+        if steps.size != 8:
+            raise ValueError("steps must have 8 entries")
+        out = np.empty(8)
+        check(lib.ipd_apd_merit(self.handle, lam.ctypes.data, zeta.ctypes.data, steps.ctypes.data, out.ctypes.data))
+        return out
+
+    def end(self, lam, from_w=True, u=None):
+        """``from_w=True``: ``uk1 = prox(zk)``, ``vk1`` at the multiplier ``lam`` become the state
+        (with ``lam``); ``from_w=False``: measures the iterate ``u`` (None: the state's).  Returns
+        ``dict(kkt=[KKT_xk, KKT_lk, KKT_yk, KKT_zk], fx=c'*x)`` (``ipd_apd_end``)."""
+        lam = self._lam_sized(lam, "lam")
+        u_ = f64(u) if u is not None else None
+        if u_ is not None and u_.size != self.U:
+            raise ValueError(f"u must have {self.U} entries")
+        kkt = np.empty(4)
+        fx = c_double()
+        check(lib.ipd_apd_end(self.handle, c_int32(1 if from_w else 0), lam.ctypes.data,
+                              u_.ctypes.data if u_ is not None else None, kkt.ctypes.data, byref(fx)))
+        return dict(kkt=kkt, fx=fx.value)
+
     def bench_eval(self, reps: int = 100):
         ms, by = c_double(), c_double()
         check(lib.ipd_apd_bench_eval(self.handle, c_int32(int(reps)), byref(ms), byref(by)))

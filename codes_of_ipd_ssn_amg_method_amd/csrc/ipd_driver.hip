@@ -25,33 +25,17 @@
 #include <limits>
 
 #include "ipd_amg_internal.h"
+#include "ipd_apd_geo.h"
 #include "ipd_cycle_dev.h"
 #include "ipd_cost.h"
 #include "ipd_plan.h"
 
 namespace {
 
-constexpr int TR = 256;        // tile rows
-constexpr int TC = 16;         // tile columns per sub-tile
+// TR, TC, Geo and make_geo: ipd_apd_geo.h
 constexpr int NSC = 8;         // scalar accumulators per workgroup
 constexpr int MK = 8;          // line-search trial points evaluated by one merit pass
-
-struct Geo {
-    int m, n, nib, njg, reps;  // njg column groups of reps*TC columns
-};
-
-static Geo make_geo(int m, int n) {
-    Geo g;
-    g.m = m;
-    g.n = n;
-    g.nib = cdiv(m, TR);
-    const int njb = cdiv(n, TC);
-    int reps = 1;
-    while (reps < 8 && (long long)g.nib * cdiv(njb, reps * 2) >= 4096) reps *= 2;
-    g.reps = reps;
-    g.njg = cdiv(njb, reps);
-    return g;
-}
+static_assert(MK == IPD_APD_MERIT_STEPS, "ipd_apd_merit takes MK steps");
 
 // problem constants shared by all passes
 struct Prob {
@@ -1018,7 +1002,7 @@ struct ipd_apd {
     size_t s_words = 0;
     unsigned long long *s_prev = nullptr, *t_prev = nullptr;
     int* step_changed = nullptr;
-    int nblk() const { return geo.nib * geo.njg; }
+    int nblk() const { return (int)apd_nblk(geo); }
 };
 
 namespace {
@@ -1638,7 +1622,9 @@ void apd_create_common(ipd_ctx* ctx, const ipd_apd_data* d, const ApdCostFill* f
     h->mn = (size_t)m * n;
     h->U = h->mn + (d->cls == 2 ? (size_t)h->M : 0);
     h->mu = d->mu;
-    h->geo = make_geo(m, n);
+    const int forced_reps = apd_reps_switch(switch_value("IPD_APD_REPS"));
+    IPD_REQUIRE(forced_reps >= 0, IPD_E_ARG, "IPD_APD_REPS must be 1, 2, 4 or 8");
+    h->geo = make_geo(m, n, forced_reps);
     const size_t mn = h->mn, U = h->U;
     const int L = h->L;
     h->c = A.alloc<double>(mn);
@@ -1685,10 +1671,10 @@ void apd_create_common(ipd_ctx* ctx, const ipd_apd_data* d, const ApdCostFill* f
     h->step_changed = A.alloc<int>(1);
     h->step_reuse = !switch_on("IPD_NO_STEP_DONOR");
     const Geo& g = h->geo;
-    h->lpart = A.alloc<double>((size_t)g.njg * m);
-    h->rpart = A.alloc<double>((size_t)g.nib * 4 * n);
-    IPD_HIP(hipMemsetAsync(h->rpart, 0, sizeof(double) * (size_t)g.nib * 4 * n, ctx->stream));
-    h->spart = A.alloc<double>((size_t)g.nib * g.njg * NSC);
+    h->lpart = A.alloc<double>(apd_lpart_len(g));
+    h->rpart = A.alloc<double>(apd_rpart_len(g));
+    IPD_HIP(hipMemsetAsync(h->rpart, 0, sizeof(double) * apd_rpart_len(g), ctx->stream));
+    h->spart = A.alloc<double>(apd_nblk(g) * NSC);
     h->dscal = reinterpret_cast<ApdScal*>(A.alloc<double>(sizeof(ApdScal) / sizeof(double) + 1));
     h->fpart = A.alloc<double>((size_t)cdiv(L, EB) * NFS);
     h->merit = A.alloc<double>(MK);
@@ -1916,6 +1902,96 @@ extern "C" int ipd_apd_eval(ipd_apd* h, const double* lam, uint8_t* s_out, doubl
             vals[4] = h->bk1 / 2.0 * e.lam2 - e.wlk_lam + 0.5 * h->tk * e.prox2;
             vals[5] = (double)e.E;
         }
+    });
+}
+
+extern "C" int ipd_apd_get_w(ipd_apd* h, double* wk, double* wlk) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h, IPD_E_ARG, "NULL handle");
+        IPD_REQUIRE(h->tk > 0.0, IPD_E_ARG, "ipd_apd_begin must run first");
+        h->ctx->set_device();
+        if (wk) h->ctx->fetch(h->w, wk, h->U);
+        if (wlk) h->ctx->fetch(h->wlk, wlk, (size_t)h->L);
+    });
+}
+
+extern "C" int ipd_apd_eval_trial(ipd_apd* h, const double* lam, const double* zeta, double step,
+                                  const double* Fk_old, int32_t merit3, uint8_t* s_out, double* t_out,
+                                  double* Fk_out, double* lam_out, double vals[12]) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && lam, IPD_E_ARG, "NULL argument");
+        IPD_REQUIRE(h->tk > 0.0, IPD_E_ARG, "ipd_apd_begin must run first");
+        IPD_REQUIRE(!(merit3 && h->cls == 2), IPD_E_ARG, "the prob-3 merit belongs to class 1");
+        ipd_ctx* ctx = h->ctx;
+        ctx->set_device();
+        // the buffers of apd_iterate's line search: lk_old, zeta, Fk_old in; lk_new, Fk_new out
+        ctx->upload(h->lam_b, lam, (size_t)h->L);
+        if (zeta) ctx->upload(h->zeta, zeta, (size_t)h->L);
+        if (zeta && Fk_old) ctx->upload(h->F_b, Fk_old, (size_t)h->L);
+        const bool keep = h->merit3;
+        h->merit3 = merit3 != 0;
+        EvalRes e;
+        try {
+            e = apd_eval(h, h->lam_b, zeta ? h->zeta : nullptr, step, h->lam_a, h->F_a,
+                         zeta && Fk_old ? h->F_b : nullptr);
+        } catch (...) {
+            h->merit3 = keep;
+            throw;
+        }
+        h->merit3 = keep;
+        if (s_out) ctx->fetch(h->s, s_out, h->mn);
+        if (t_out && h->tmask) ctx->fetch(h->tmask, t_out, (size_t)h->M);
+        if (Fk_out) ctx->fetch(h->F_a, Fk_out, (size_t)h->L);
+        if (lam_out) ctx->fetch(h->lam_a, lam_out, (size_t)h->L);
+        if (vals) {
+            const double f0 = h->bk1 / 2.0 * e.lam2 - e.wlk_lam;               // as apd_iterate's merit()
+            vals[0] = h->bk1;
+            vals[1] = h->tk;
+            vals[2] = h->ak;
+            vals[3] = e.normF;
+            vals[4] = merit3 ? f0 + 0.5 * h->tk * (e.z2 - e.zmp2) : f0 + 0.5 * h->tk * e.prox2;
+            vals[5] = (double)e.E;
+            vals[6] = e.z2;
+            vals[7] = e.zmp2;
+            vals[8] = e.fold_zeta;
+            vals[9] = e.lam2;
+            vals[10] = e.wlk_lam;
+            vals[11] = e.prox2;
+        }
+    });
+}
+
+extern "C" int ipd_apd_merit(ipd_apd* h, const double* lam, const double* zeta,
+                             const double steps[IPD_APD_MERIT_STEPS], double merit[IPD_APD_MERIT_STEPS]) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && lam && zeta && steps && merit, IPD_E_ARG, "NULL argument");
+        IPD_REQUIRE(h->tk > 0.0, IPD_E_ARG, "ipd_apd_begin must run first");
+        ipd_ctx* ctx = h->ctx;
+        ctx->set_device();
+        ctx->upload(h->lam_b, lam, (size_t)h->L);
+        ctx->upload(h->zeta, zeta, (size_t)h->L);
+        apd_merit(h, h->lam_b, h->zeta, steps, merit);
+    });
+}
+
+extern "C" int ipd_apd_end(ipd_apd* h, int32_t from_w, const double* lam, const double* u, double kkt[4],
+                           double* fx) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && lam && kkt && fx, IPD_E_ARG, "NULL argument");
+        IPD_REQUIRE(!from_w || h->tk > 0.0, IPD_E_ARG, "ipd_apd_begin must run first");
+        IPD_REQUIRE(!(from_w && u), IPD_E_ARG, "from_w measures the iterate it forms: u must be NULL");
+        ipd_ctx* ctx = h->ctx;
+        ctx->set_device();
+        ctx->upload(h->lam_a, lam, (size_t)h->L);
+        if (from_w) {
+            apd_end(h, true, nullptr, h->lam_a, kkt, fx);
+            std::swap(h->u, h->u2);                                            // as apd_iterate without a restart
+            copy_dev(h, h->lam, h->lam_a, (size_t)h->L);
+        } else {
+            if (u) ctx->upload(h->u2, u, h->U);                                // u2 is free between iterations
+            apd_end(h, false, u ? h->u2 : h->u, h->lam_a, kkt, fx);
+        }
+        ctx->sync();
     });
 }
 

@@ -45,6 +45,7 @@ static constexpr SwitchInfo IPD_SWITCHES[] = {
     {"IPD_NO_STEP_DONOR", SW_FLAG, "the drivers' step donors off: the bit-identity tests"},
     {"IPD_NO_POT_CONCURRENT", SW_FLAG, "AMG4POT's two concurrent solves off: the bit-identity tests"},
     {"IPD_COST_STORE", SW_VALUE, "8|16: the store width of the point-cloud cost build where both are possible (measurement, tests)"},
+    {"IPD_APD_REPS", SW_VALUE, "1|2|4|8: column chunks a wave of the drivers' tile walker takes (ipd_apd_geo.h), read when a workspace is created; the natural rule leaves 1 below about 1793 x 16353 entries, so this is how tests run the rep loop and its partly filled last group at small shapes"},
     {"IPD_SHARD_EMULATE", SW_VALUE, "<G>: one process plays G row-block owners (the sharded path's test on one GPU)"},
     {"IPD_DEBUG_SKIP", SW_VALUE, "<mask>: timing by elimination inside the tail's sub-cycle (results void)"},
     {"IPD_PROFILE", SW_VALUE, "phase wall clocks (ipd_prof_read); on unless empty or starting with '0'"},

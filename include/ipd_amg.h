@@ -464,6 +464,31 @@ int ipd_apd_reuse_stats(const ipd_apd* h, int64_t* steps, int64_t* same_system, 
 int ipd_apd_begin(ipd_apd* h, int32_t k, double vals[3]);
 int ipd_apd_eval(ipd_apd* h, const double* lam, uint8_t* s_out, double* t_out, double* Fk_out,
                  double vals[6]);
+/* The other blocks of an iteration, for the same two uses.  All need `begin` first (except `end`
+ * with from_w = 0); vectors are host arrays, lam / zeta / Fk of ipd_apd_dims' len_lam entries,
+ * u / wk of len_u; NULL outputs are skipped.
+ * `get_w`: wk and wlk as `begin` left them.
+ * `eval_trial`: `eval` at the line search's trial point lam + step*zeta (:189,200; zeta NULL: at
+ *   lam), as apd's Newton loop calls it: lam_out is the multiplier the pass used, Fk_old (with
+ *   zeta; may be NULL) gives fold_zeta = Fk_old'*zeta (:198), merit3 != 0 (class 1) takes the
+ *   prob-3 merit |zk|^2 - |zk - prox(zk)|^2 (:183-187), whose sums z2, zmp2 are 0 otherwise.
+ *   vals = {bk1, tk, ak, |Fk|, cFk, E, z2, zmp2, fold_zeta, lam2, wlk_lam, prox2}; the last
+ *   three are the raw sums |lam|^2, wlk'*lam, |prox(zk)|^2 that cFk is made of.
+ * `merit`: cFk at lam + steps[k]*zeta for the IPD_APD_MERIT_STEPS trial steps one pass of the
+ *   line search takes together (:199-207).
+ * `end`: from_w != 0 forms uk1 = prox(zk) and vk1 at the multiplier lam (:239-242) -- u must be
+ *   NULL -- and makes (uk1, vk1, lam) the state ipd_apd_get_state reads, as an iteration
+ *   without a restart does; from_w = 0 measures the iterate u (NULL: the state's) at lam and
+ *   changes nothing.  kkt = {KKT_xk, KKT_lk, KKT_yk, KKT_zk}, *fx = c'*x.                      */
+#define IPD_APD_MERIT_STEPS 8
+int ipd_apd_get_w(ipd_apd* h, double* wk, double* wlk);
+int ipd_apd_eval_trial(ipd_apd* h, const double* lam, const double* zeta, double step,
+                       const double* Fk_old, int32_t merit3, uint8_t* s_out, double* t_out,
+                       double* Fk_out, double* lam_out, double vals[12]);
+int ipd_apd_merit(ipd_apd* h, const double* lam, const double* zeta,
+                  const double steps[IPD_APD_MERIT_STEPS], double merit[IPD_APD_MERIT_STEPS]);
+int ipd_apd_end(ipd_apd* h, int32_t from_w, const double* lam, const double* u, double kkt[4],
+                double* fx);
 /* HIP-event timing of `reps` eval passes on the current workspace (bench.py).   */
 int ipd_apd_bench_eval(ipd_apd* h, int32_t reps, double* total_ms, double* bytes_per_pass);
 

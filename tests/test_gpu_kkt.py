@@ -97,16 +97,19 @@ def test_asat_errors(ipd):
 
 
 def test_inv_aat_hht(ipd):
+    """(70, 45) keeps every thread of the 1024-thread kernels at one element; the other shapes make the stride loops
+    of k_inv_aat / k_inv_hht_combine take a second element on the column side, on both sides and on the row side,
+    and give invHHt more than one partial sum of |phi|^2 (npart = 4101, 1024 (capped), 8)."""
     rs = np.random.RandomState(3)
-    m, n = 70, 45
-    p, q = 0.5 + rs.random_sample(m), 0.5 + rs.random_sample(n)
-    x = rs.randn(m + n)
-    for args in [(), (0.7,), (0.7, 1.9)]:
-        ref = O.invAAt(x, p, q, *args)
-        got = ipd.invAAt(x, p, q, *args)
-        assert np.allclose(got, ref, rtol=1e-12, atol=1e-13)
-    phi = rs.random_sample(m * n)
-    v = rs.randn(m + n + 1)
-    ref = O.invHHt(v, p, q, 0.3, phi)
-    got = ipd.invHHt(v, p, q, 0.3, phi)
-    assert np.allclose(got, ref, rtol=1e-11, atol=1e-13)
+    for m, n in [(70, 45), (1024, 1025), (1500, 1100), (1, 2000)]:
+        p, q = 0.5 + rs.random_sample(m), 0.5 + rs.random_sample(n)
+        x = rs.randn(m + n)
+        for args in [(), (0.7,), (0.7, 1.9)]:
+            ref = O.invAAt(x, p, q, *args)
+            got = ipd.invAAt(x, p, q, *args)
+            assert np.allclose(got, ref, rtol=1e-12, atol=1e-13), (m, n, args)
+        phi = rs.random_sample(m * n)
+        v = rs.randn(m + n + 1)
+        ref = O.invHHt(v, p, q, 0.3, phi)
+        got = ipd.invHHt(v, p, q, 0.3, phi)
+        assert np.allclose(got, ref, rtol=1e-11, atol=1e-13), (m, n)
