@@ -281,15 +281,29 @@ __device__ __forceinline__ void res_cs_rows(const double (&A)[RES_WAVES][2], dou
     if ((lane & 7) == 0) part_out[8 * (lane >> 3) + w] = u;
 }
 
+// Classes of chip-wide hand-offs, for the stamps by class (ipd_amg_bench_resident_classes, column-slice kernels):
+// workgroup 0 charges the clocks from the start of a hand-off's own work to the start of the next one's to its class.
+enum res_class {
+    RES_CL_HALF = 0,    // a level-1 half sweep published behind the barrier of the hand-off before it
+    RES_CL_START = 1,   // ... the first of a run: its totals come from LDS behind a barrier of its own
+    RES_CL_RR = 2,      // rr = r - A e
+    RES_CL_RESTRICT = 3,   // r_2 = P' rr
+    RES_CL_LEVEL2 = 4,  // level 2: the composed pass, or each of its sweeps and its residual (with the tail)
+    RES_CL_PROLONG = 5, // e_1 += P e_2
+    RES_CL_TOP = 6,     // r = b - A x
+    RES_NCLASS = 8
+};
+
 // out[0] = it, out[1] = rel_res, out[2] = res0; rel_resk at out[4 ..], rhok at out[4+maxit+2 ..]
 // (res_stationary; the last slot: hand-offs of the launch).  fixed_cycles > 0: the bench hook.  dbg (optional, 16 words): [0] shader clocks spent waiting in sweeps by
 // workgroup 0, [1] clocks of the whole loop, [2] number of hand-offs, [3] 100 MHz ticks of the loop,
 // [4] clocks in the barrier before the publish, [5] in the store phase, [6] in the closing barrier, [9] in the
 // finishing lanes of the column-slice half sweeps (whose one barrier counts as [4], their receipt as [5]).
+// Column slices: dbg has 32 words, [16 + c] the clocks and [24 + c] the hand-offs of class c (res_class).
 template <int KE1, int KE2, int KE3 = 0, bool POLY2 = false>
 __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const double* __restrict__ bvec,
                                                     double* xg, double* out, int fixed_cycles) {
-    static_assert(!POLY2 || KE3 == 0, "POLY2: three-level hierarchies");
+    static_assert(!POLY2 || (KE3 == 0 && KE1 == 16), "POLY2: three-level hierarchies in column slices (resident_takes_poly2)");
     constexpr bool THREE = KE3 > 0;
     constexpr bool POLY3 = KE3 == 1;   // level 3 in polynomial form (ResDesc::p3rows)
     constexpr int K3 = (THREE && !POLY3) ? KE3 : 2;
@@ -329,6 +343,9 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     // entry ranges of this wave's rows of the transfer operators: read once, a walk then starts
     // with its entries instead of a dependent trip for the row pointers
     int* rowp = reinterpret_cast<int*>(sm + oOWN + 10 * RES_WAVES + 12);                 // 12 ints per wave
+    // stamps by class, 32-bit words (a class's clocks of one launch stay far below 2^32, and sums of differences of
+    // low words are exact modulo 2^32): clocks [0 .. 8), hand-offs [8 .. 16)
+    unsigned* cls_acc = reinterpret_cast<unsigned*>(sm + oOWN + 10 * RES_WAVES + 12 + 6 * RES_WAVES);
     // third resident level (THREE): its vectors sit in the upper halves of level 2's slots (N2 <= 1024,
     // N3 <= 512); E3 is a gather target and must lie below 64 KB
     constexpr int oE3L = oE2 + RES_NMAX / 2, oR3L = oRR2 + RES_NMAX / 2, oRR3L = oRR2 + 3 * RES_NMAX / 4;
@@ -402,15 +419,21 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         res_load_slice<KR1>(D.L1, rF, vF, lane, cF, aF);
         res_load_slice<KR1>(D.L1, rC, vC, lane, cC, aC);
     }
-    if (POLY2) {
+    // The composed level 2 is held in column slices as well: thread t holds columns t and t + BT of the workgroup's
+    // rows of B -- the 16 doubles the row slice a2 costs the sweep form -- and the received r_2 meets them in the
+    // registers it arrived in (poly2_fed).
+    double B2[RES_WAVES][2];
+    (void)B2;
+    if constexpr (POLY2) {
 #pragma unroll
-        for (int q = 0; q < KE2; ++q) {
-            const int e = lane + 64 * q;
-            const double bv = D.p2rows[(size_t)r2 * D.p2ld + D.p2seg + (e < N2 ? e : 0)];
-            a2[q] = (v2 && e < N2) ? bv : 0.0;
-        }
+        for (int r = 0; r < RES_WAVES; ++r)
 #pragma unroll
-        for (int q = 0; q < KE2 / 2; ++q) c2[q] = 0u;
+            for (int u = 0; u < 2; ++u) {
+                const int col = tid + u * BT;
+                const bool ok = lo2 + r < hi2 && col < N2;
+                const double bv = D.p2rows[(size_t)(ok ? lo2 + r : 0) * D.p2ld + D.p2seg + (ok ? col : 0)];
+                B2[r][u] = ok ? bv : 0.0;
+            }
     } else {
         res_load_slice<KE2>(D.L2, r2, v2, lane, c2, a2);
     }
@@ -558,8 +581,6 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         for (int t = D.A3.rp[0]; t < D.A3.rp[1]; ++t)
             if (D.A3.ci[t] == 0) h33 = D.A3.va[t];
     }
-    if (POLY2)   // the dense rows of B are walked in whole 64-entry steps: zeros behind r_2
-        for (int j = N2 + tid; j < RES_NMAX / 2; j += BT) sm[oR2 + j] = 0.0;
     if (tid == 0) *fail = 0;
     __syncthreads();
 
@@ -571,7 +592,24 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         dbg_acc[0] = dbg_acc[3] = dbg_acc[4] = dbg_acc[5] = dbg_acc[6] = dbg_acc[7] = dbg_acc[8] = 0;
         dbg_acc[1] = __builtin_amdgcn_s_memtime();
         dbg_acc[2] = __builtin_amdgcn_s_memrealtime();
+        if constexpr (KE1 == 16)
+            for (int k = 0; k < 2 * RES_NCLASS; ++k) cls_acc[k] = 0u;
     }
+    // start and end of a hand-off of class c (the end of one is the start of the next): LDS adds without a result,
+    // so a stamp holds two registers and no state
+    auto cls_begin = [&](int c) __attribute__((always_inline)) {
+        if constexpr (KE1 == 16) {
+            if (dbg) __hip_atomic_fetch_sub(cls_acc + c, (unsigned)__builtin_amdgcn_s_memtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    };
+    auto cls_end = [&](int c) __attribute__((always_inline)) {
+        if constexpr (KE1 == 16) {
+            if (dbg) {
+                __hip_atomic_fetch_add(cls_acc + c, (unsigned)__builtin_amdgcn_s_memtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(cls_acc + RES_NCLASS + c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+    };
 
     // ---- hand-off wrapper: sweep + barrier + store + (optional) block sums + barrier ------------
     // STORE(j, v) is called for every granule of the thread; EXTRA() runs once per thread (fix-ups on
@@ -593,6 +631,9 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     RES_HANDOFF_PV(NJ, n, gA, cA, gB, cB, sm[oPUB + lane], PRE, STORE, EXTRA, want_sums, t0, t1)
     // PUBV: the value lane 8 * block + row of wave 0 publishes (column slices: formed in the lane from PART)
 #define RES_HANDOFF_PV(NJ, n, gA, cA, gB, cB, PUBV, PRE, STORE, EXTRA, want_sums, t0, t1)          \
+    RES_HANDOFF_PVA(NJ, n, gA, cA, gB, cB, PUBV, PRE, STORE, {}, EXTRA, want_sums, t0, t1)
+    // AFTER: runs once per thread behind the STOREs, ahead of the closing barrier (what the received values feed)
+#define RES_HANDOFF_PVA(NJ, n, gA, cA, gB, cB, PUBV, PRE, STORE, AFTER, EXTRA, want_sums, t0, t1)  \
     do {                                                                                           \
         double hv_[NJ], pa_[NJ], pb_[NJ];                                                          \
         (void)pa_;                                                                                 \
@@ -635,6 +676,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 STORE;                                                                             \
             }                                                                                      \
         }                                                                                          \
+        AFTER;                                                                                     \
         if (want_sums) {                                                                           \
             p0 = wave_sum(p0);                                                                     \
             if ((want_sums) > 1) p1 = wave_sum(p1);                                                \
@@ -677,7 +719,10 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         return wave_sum(s0 + s1);
     };
     double c1 = 0.0, c2s = 0.0;     // kernel-space scalars of the next sweep on level 1 / 2
-    double sumr2p = 0.0;            // POLY2: 1'r_2 of the visit
+    // (1'r_2 of the visit: the composed pass now forms it in its finishing lanes and nothing reads this copy, but the
+    // encodings of the sweep-form instantiations hang on the store -- without it every one of them is scheduled anew)
+    double sumr2p = 0.0;
+    (void)sumr2p;
     const double p2ws = POLY2 ? D.p2w[N2] : 0.0;
     double dum0 = 0.0, dum1 = 0.0;
     (void)dum0;
@@ -718,6 +763,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
 
     auto top = [&]() __attribute__((always_inline)) {
         if constexpr (CS1) {
+            cls_begin(RES_CL_TOP);
             cs_both_rows(oX);
         } else {
         const double sF = wave_sum(res_rowdot_fma<KR1, 8 * oX>(cF, aF, smb));
@@ -742,6 +788,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             }
             __syncthreads();
         }
+        cls_end(RES_CL_TOP);
         return sqrt(nrm2);
     };
 
@@ -787,10 +834,12 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         }
         if (dbg) dbg_acc[8] += __builtin_amdgcn_s_memtime();
     };
-    auto half1_cs = [&](bool frows, bool first, bool ezero, bool feed) __attribute__((always_inline)) {
+    // `start`: the first hand-off of a run (csFed != me), for the stamps by class
+    auto half1_cs = [&](bool frows, bool first, bool ezero, bool feed, bool start) __attribute__((always_inline)) {
         const int blk0 = frows ? 0 : nf, nblk = frows ? nf : nc;
         const int oth0 = frows ? nf : 0, noth = frows ? nc : nf;
         const int me = frows ? 0 : 1;
+        cls_begin(start ? RES_CL_START : RES_CL_HALF);
         ++seq;
         if (*fail) dead = true;           // (a give-up of the previous hand-off: its barrier has ordered the flag)
         if (ezero && first) {             // zero start: the row's sum and its own entry are zero
@@ -886,6 +935,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             cs_finish(!frows, !first, false, seq + 1);
         else
             eFo = eCo = 0.0;   // (dead outside a run of half sweeps: its first one reloads them)
+        cls_end(start ? RES_CL_START : RES_CL_HALF);
     };
     auto half1 = [&](bool frows, bool first, bool ezero) __attribute__((always_inline)) {
         if constexpr (!CS1) {   // (16-entry rows: half1_cs)
@@ -931,10 +981,12 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         }
         }
     };
-    auto sweep1 = [&](bool post, bool ezero, bool last) __attribute__((always_inline)) {
+    auto sweep1 = [&](bool post, bool ezero, bool last, bool start) __attribute__((always_inline)) {
+        (void)start;
         if constexpr (CS1) {
-            if (!(lfirst && ezero && !post)) half1_cs(!post, true, ezero, true);
-            half1_cs(post, false, ezero, !last);   // (the run's next sweep starts with the other block)
+            const bool local = lfirst && ezero && !post;   // (the first half: done by top())
+            if (!local) half1_cs(!post, true, ezero, true, start);
+            half1_cs(post, false, ezero, !last, local);   // (the run's next sweep starts with the other block)
         } else {
         if (!(lfirst && ezero && !post)) half1(!post, true, ezero);   // else: done by top()    // pre: F rows first (Rk{1}); post: C rows first (Rk{1}')
         half1(post, false, ezero);
@@ -943,6 +995,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
 
     // weighted-Jacobi sweep on level 2                                   MG_Vcycle.m:15-21; Class_AMG.m:84
     auto sweep2 = [&](bool ezero) __attribute__((always_inline)) {
+        cls_begin(RES_CL_LEVEL2);
         double s = 0.0, eo = 0.0;
         if (!ezero) {
             s = wave_sum(res_rowdot_fma<KE2, 8 * oE2>(c2, a2, smb));
@@ -962,6 +1015,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                       },
                       {}, (nsp ? 1 : 0), xig, dum1);
         c2s = nsp ? xig * rxx2 : 0.0;
+        cls_end(RES_CL_LEVEL2);
     };
 
     // tail level: restriction, Jacobi-PCG (PCG.m:68-87, zero guess), prolongation -- all of it by
@@ -1271,35 +1325,10 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     // one visit of level 2 and everything below it
     auto visit2 = [&](bool keep) __attribute__((always_inline)) {
         const int nu = D.nu;
-        if (POLY2) {   // the whole visit as one composed pass (ResDesc::p2rows): ONE hand-off
-            // r_3 = s'r_2 + ws (1'r_2) and the one-row tail's PCG (PCG.m:68-87) by every workgroup
-            double s3 = 0.0;
-            for (int j = tid; j < N2; j += BT) s3 += sm[oP3C + j] * sm[oR2 + j];
-            s3 = wave_sum(s3);
-            if (lane == 0) red[w] = s3;
-            __syncthreads();
-            const double d = res_pcg_1x1(res_red8(red) + p2ws * sumr2p, h33, D.pcg_maxit);
-            // e_2 = B r_2 + wB (1'r_2) + mp e_3 on the own row: a dense row against R2 (entry lane + 64 q at a
-            // constant distance: immediate offsets, no column registers)
-            const double* rb = sm + oR2 + lane;
-            double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
-#pragma unroll
-            for (int q = 0; q < KE2; q += 4) {
-                t0 += a2[q] * rb[64 * q];
-                t1 += a2[q + 1] * rb[64 * (q + 1)];
-                t2 += a2[q + 2] * rb[64 * (q + 2)];
-                t3 += a2[q + 3] * rb[64 * (q + 3)];
-            }
-            const double val = wave_sum((t0 + t1) + (t2 + t3)) + dg2 * sumr2p + dv2 * d;
-            if (lane == 0) sm[oPUB + w] = val;
-            RES_HANDOFF(4, N2, lo2, hi2 - lo2, 0, 0, { sm[oE2 + j] = v; }, {}, 0, dum0, dum1);
-            (void)keep;
-            (void)nu;
-            return;
-        }
         for (int s = (lfirst2 && !keep) ? 1 : 0; s < nu; ++s) sweep2(!keep && s == 0);
         // rr = r - A e                                                           MG_Vcycle.m:27
         {
+            cls_begin(RES_CL_LEVEL2);
             const double s = wave_sum(res_rowdot_fma<KE2, 8 * oE2>(c2, a2, smb)) + dg2 * sm[oE2 + r2];
             if (lane == 0) sm[oPUB + w] = sm[oR2 + r2] - s;
             RES_HANDOFF(4, N2, lo2, hi2 - lo2, 0, 0, { sm[oRR2 + j] = v; }, {}, 0, dum0, dum1);
@@ -1327,15 +1356,99 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             tail();
         }
         if (dbg) dbg_acc[7] += __builtin_amdgcn_s_memtime();
+        cls_end(RES_CL_LEVEL2);   // (the residual's hand-off, with the tail behind it)
         for (int s = 0; s < nu; ++s) sweep2(false);
+    };
+
+    // Level 2 composed over a visit (POLY2), fed from the polls of r_2: r_2's hand-off is published from oPUB like any
+    // other, and what arrives meets the column slices of B in the registers it arrived in.  res_cs_rows leaves the
+    // waves' row totals in PART, the waves' parts of s'r_2 and 1'r_2 go to red, and after ONE barrier the finishing
+    // lanes (wave 0, lane r < RES_WAVES) hold all of
+    //     e_2 = B r_2 + wB (1'r_2) + mp e_3,   e_3 = PCG(h33, s'r_2 + ws (1'r_2))            (PCG.m:68-87, one row)
+    // for their rows: they publish e_2's hand-off from registers, and its receipt is the visit's only LDS store.
+    // Nothing reads r_2 afterwards, so it is not kept.  (PART and red are free here: the hand-offs on either side
+    // have a barrier between their use of them and this one.)
+    auto poly2_fed = [&]() __attribute__((always_inline)) {
+        if constexpr (POLY2) {
+            ++seq;
+            if (*fail) dead = true;
+            if (dbg) dbg_acc[3] -= __builtin_amdgcn_s_memtime();
+            __syncthreads();
+            if (dbg) dbg_acc[3] += __builtin_amdgcn_s_memtime();
+            const bool pub = w == 0 && lane < RES_WAVES && lane < hi2 - lo2;
+            if (pub && !(seq == D.dbg_skip_seq && b == G - 1)) res_publish(rs, seq, lo2 + lane, sm[oPUB + lane]);
+            // (between the publish and the wait: the stacked restriction row s at the thread's two columns)
+            const double s0 = tid < N2 ? sm[oP3C + tid] : 0.0, s1 = tid + BT < N2 ? sm[oP3C + tid + BT] : 0.0;
+            double hv[2] = {0.0, 0.0};
+            if (dbg) dbg_acc[0] -= __builtin_amdgcn_s_memtime();
+            for (int ps = 0; ps < D.presleep; ++ps) __builtin_amdgcn_s_sleep(1);
+            if (res_sweep<2>(rs, seq, N2, dead, D.tmo, hv, D.pollsleep)) {
+                *fail = 1;
+                if (lane == 0) __hip_atomic_store(D.tmo, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (dbg) {
+                const long long t_ = __builtin_amdgcn_s_memtime();
+                dbg_acc[0] += t_;
+                dbg_acc[4] -= t_;
+            }
+            const double v0 = tid < N2 ? hv[0] : 0.0, v1 = tid + BT < N2 ? hv[1] : 0.0;
+            res_cs_rows(B2, v0, v1, sm + oPART, w, lane);
+            const double ps = wave_sum(s0 * v0 + s1 * v1);
+            const double p1 = nsp ? wave_sum(v0 + v1) : 0.0;
+            if (lane == 0) {
+                red[w] = ps;
+                red[RES_WAVES + w] = p1;
+            }
+            if (dbg) {
+                const long long t_ = __builtin_amdgcn_s_memtime();
+                dbg_acc[4] += t_;
+                dbg_acc[3] -= t_;
+            }
+            __syncthreads();
+            if (dbg) dbg_acc[3] += __builtin_amdgcn_s_memtime();
+            cls_end(RES_CL_RESTRICT);
+            cls_begin(RES_CL_LEVEL2);
+            ++seq;
+            if (*fail) dead = true;   // (a give-up of r_2's sweep: the barrier has ordered the flag)
+            if (w == 0 && lane < RES_WAVES) {
+                const double wB = sm[oOWN + 6 * RES_WAVES + lane], mp = sm[oOWN + 7 * RES_WAVES + lane];
+                const double T = res_red8_tree(sm + oPART + RES_WAVES * lane);
+                const double sr = res_red8_tree(red), sum1 = res_red8_tree(red + RES_WAVES);
+                const double d = res_pcg_1x1(sr + p2ws * sum1, h33, D.pcg_maxit);
+                const double val = T + wB * sum1 + mp * d;
+                if (pub && !(seq == D.dbg_skip_seq && b == G - 1)) res_publish(rs, seq, lo2 + lane, val);
+            }
+            if (dbg) dbg_acc[0] -= __builtin_amdgcn_s_memtime();
+            for (int ps = 0; ps < D.presleep; ++ps) __builtin_amdgcn_s_sleep(1);
+            if (res_sweep<2>(rs, seq, N2, dead, D.tmo, hv, D.pollsleep)) {
+                *fail = 1;
+                if (lane == 0) __hip_atomic_store(D.tmo, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (dbg) {
+                const long long t_ = __builtin_amdgcn_s_memtime();
+                dbg_acc[0] += t_;
+                dbg_acc[4] -= t_;
+            }
+            if (tid < N2) sm[oE2 + tid] = hv[0];
+            if (tid + BT < N2) sm[oE2 + tid + BT] = hv[1];
+            if (dbg) {
+                const long long t_ = __builtin_amdgcn_s_memtime();
+                dbg_acc[4] += t_;
+                dbg_acc[5] -= t_;
+            }
+            __syncthreads();
+            if (dbg) dbg_acc[5] += __builtin_amdgcn_s_memtime();
+            cls_end(RES_CL_LEVEL2);
+        }
     };
 
     // MG_Vcycle / MG_Wcycle from level 1 down; the correction ends in E1
     auto cycle = [&]() __attribute__((always_inline)) {
         const int nu = D.nu;
-        for (int s = 0; s < nu; ++s) sweep1(false, s == 0, s == nu - 1);
+        for (int s = 0; s < nu; ++s) sweep1(false, s == 0, s == nu - 1, s == 0);
         {   // rr = r - A e on both blocks
             if constexpr (CS1) {
+                cls_begin(RES_CL_RR);
                 cs_both_rows(oE1);
             } else {
             const double sF = wave_sum(res_rowdot_fma<KR1, 8 * oE1>(cF, aF, smb)) + dgF * sm[oE1 + rF];
@@ -1363,6 +1476,8 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             }
         }
         {   // r_2 = P' rr ; E2 := 0 ; c for the zero start
+            cls_end(RES_CL_RR);
+            cls_begin(RES_CL_RESTRICT);
             if (dbg) dbg_acc[6] -= __builtin_amdgcn_s_memtime();
             // row r2 of P' is [W(:,r2)' , 1 at nf + r2]; rowC == nf + row2 (level 2 = the C nodes)
             const double s = xm ? sm[oBETA + r2] * masked_sum(xbits >> 16, oRR1, nf) + sm[oRR1 + rC]
@@ -1370,6 +1485,9 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                                       (D.wident ? sm[oRR1 + rC] : 0.0);
             if (dbg) dbg_acc[6] += __builtin_amdgcn_s_memtime();
             if (lane == 0) sm[oPUB + w] = s;
+            if constexpr (POLY2) {   // ... and the whole visit of level 2 behind the one barrier of its receipt
+                poly2_fed();
+            } else {
             double sumr = 0.0;
             RES_HANDOFF(4, N2, lo2, hi2 - lo2, 0, 0, { sm[oR2 + j] = v; sm[oE2 + j] = 0.0; p0 += v; }, {},
                         (nsp ? 1 : 0), sumr, dum1);
@@ -1392,9 +1510,13 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 if (nsp) c2s = res_red8(red) / xx2;
                 __syncthreads();   // red is rewritten by the next hand-off
             }
+            cls_end(RES_CL_RESTRICT);
+            }
         }
-        for (int leg = 0; leg < (D.wcycle ? 2 : 1); ++leg) visit2(leg == 1);      // MG_Wcycle.m:28-30
+        if constexpr (!POLY2)
+            for (int leg = 0; leg < (D.wcycle ? 2 : 1); ++leg) visit2(leg == 1);      // MG_Wcycle.m:28-30
         {   // e_1 += P e_2                                                        MG_Vcycle.m:31
+            cls_begin(RES_CL_PROLONG);
             if (dbg) dbg_acc[6] -= __builtin_amdgcn_s_memtime();
             // F rows: W(rowF,:) against E2 (A's columns nf + i are level-2 indices i); C rows: identity
             if (xm) {   // beta .* e_2 once per workgroup, then one masked sum per F row
@@ -1411,11 +1533,42 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 sm[oPUB + RES_WAVES + w] = sm[oE1 + rC] + sC;
             }
             double xig = 0.0;
+            if constexpr (CS1) {
+                // The F block as it arrives (granules t and t + BT of the hand-off: nf <= 2 BT) feeds the C rows of
+                // the first post-smoothing half sweep, as a half sweep's receipt feeds the next one: behind the
+                // closing barrier the finishing lanes publish it, and the run starts without a barrier of its own.
+                const bool fedpost = nu >= 1 && nf <= 2 * BT;
+                double fe[2] = {0.0, 0.0};
+                RES_HANDOFF_PVA(4, N1, loF, hiF - loF, loC, hiC - loC, sm[oPUB + lane],
+                                { pa_[u_] = sm[oR1 + j]; pb_[u_] = sm[oAX1 + j]; },
+                                {
+                                    sm[oE1 + j] = v;
+                                    p0 += pa_[u_] - pb_[u_] * v;
+                                    if (u_ < 2 && j < nf) fe[u_] = v;
+                                },
+                                {
+                                    if (fedpost) {
+                                        csBuf ^= 1;
+                                        res_cs_rows(AC, fe[0], fe[1], sm + oPART + RES_WAVES * RES_WAVES * csBuf, w, lane);
+                                    }
+                                },
+                                {}, (nsp ? 1 : 0), xig, dum1);
+                c1 = nsp ? xig * rxx1 : 0.0;
+                if (fedpost) {
+                    eFo = sm[oE1 + (loF + lane < hiF ? loF + lane : hiF - 1)];
+                    eCo = sm[oE1 + (loC + lane < hiC ? loC + lane : hiC - 1)];
+                    cs_finish(false, true, false, seq + 1);
+                    csFed = 1;
+                }
+                cls_end(RES_CL_PROLONG);
+            } else {
             RES_HANDOFF_P(4, N1, loF, hiF - loF, loC, hiC - loC, { pa_[u_] = sm[oR1 + j]; pb_[u_] = sm[oAX1 + j]; },
                           { sm[oE1 + j] = v; p0 += pa_[u_] - pb_[u_] * v; }, {}, (nsp ? 1 : 0), xig, dum1);
             c1 = nsp ? xig * rxx1 : 0.0;
+            }
         }
-        for (int s = 0; s < nu; ++s) sweep1(true, false, s == nu - 1);
+        // (column slices: the post run's first half sweep is fed by the prolongation, see above)
+        for (int s = 0; s < nu; ++s) sweep1(true, false, s == nu - 1, s == 0 && csFed != 1);
     };
 
     auto add_correction = [&]() __attribute__((always_inline)) {   // x += e                                       Class_AMG.m:98,101
@@ -1458,6 +1611,8 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         D.dbg[7] = dbg_acc[6];
         D.dbg[8] = dbg_acc[7];
         if (CS1 && !D.remote) D.dbg[9] = dbg_acc[8];   // (a remote tail reports its busy time there)
+        if constexpr (CS1)
+            for (int k = 0; k < 2 * RES_NCLASS; ++k) D.dbg[16 + k] = (long long)cls_acc[k];
     }
 #undef RES_HANDOFF3
 #undef RES_HANDOFF3R
@@ -1465,6 +1620,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
 #undef RES_HANDOFF
 #undef RES_HANDOFF_P
 #undef RES_HANDOFF_PV
+#undef RES_HANDOFF_PVA
 #undef dgF
 #undef dvF
 #undef bF

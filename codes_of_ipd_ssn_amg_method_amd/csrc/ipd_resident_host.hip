@@ -682,8 +682,9 @@ extern "C" int ipd_amg_solve_mode(const ipd_amg* h, int32_t* mode, int32_t* grid
     return IPD_OK;
 }
 
-extern "C" int ipd_amg_bench_resident(ipd_amg* h, const double* b_dev, double* x_dev, int cycles,
-                                      double* total_ms, int64_t stamps[10]) {
+// nst: words fetched (the column-slice kernels leave their stamps by class of hand-off in words 16 .. 31)
+static int bench_resident_stamped(ipd_amg* h, const double* b_dev, double* x_dev, int cycles, double* total_ms,
+                                  int64_t* stamps, int nst) {
     return ipd_guard([&] {
         IPD_REQUIRE(h && b_dev && x_dev && cycles > 0 && total_ms && stamps, IPD_E_ARG, "bad argument");
         ipd_ctx* ctx = h->ctx;
@@ -691,8 +692,8 @@ extern "C" int ipd_amg_bench_resident(ipd_amg* h, const double* b_dev, double* x
         CycleState* st = state_of(h);
         IPD_REQUIRE(st && st->res->ok, IPD_E_ARG, "hierarchy does not run in resident mode");
         const int N = h->L[1].A.nr;
-        long long* dbg = ctx->scratch->alloc<long long>(16);
-        IPD_HIP(hipMemsetAsync(dbg, 0, 128, ctx->stream));
+        long long* dbg = ctx->scratch->alloc<long long>(32);
+        IPD_HIP(hipMemsetAsync(dbg, 0, 256, ctx->stream));
         IPD_HIP(hipMemcpyAsync(h->x, x_dev, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
                                ctx->stream));
         float msf = 0.f;
@@ -700,9 +701,19 @@ extern "C" int ipd_amg_bench_resident(ipd_amg* h, const double* b_dev, double* x
                     "resident kernel gave up (not every workgroup was resident)");
         IPD_HIP(hipMemcpyAsync(x_dev, h->x, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice,
                                ctx->stream));
-        long long hs[10];
-        ctx->fetch(dbg, hs, 10);
-        for (int i = 0; i < 10; ++i) stamps[i] = hs[i];
+        long long hs[32];
+        ctx->fetch(dbg, hs, (size_t)nst);
+        for (int i = 0; i < nst; ++i) stamps[i] = hs[i];
         *total_ms = msf;
     });
+}
+
+extern "C" int ipd_amg_bench_resident(ipd_amg* h, const double* b_dev, double* x_dev, int cycles,
+                                      double* total_ms, int64_t stamps[10]) {
+    return bench_resident_stamped(h, b_dev, x_dev, cycles, total_ms, stamps, 10);
+}
+
+extern "C" int ipd_amg_bench_resident_classes(ipd_amg* h, const double* b_dev, double* x_dev, int cycles,
+                                              double* total_ms, int64_t stamps[32]) {
+    return bench_resident_stamped(h, b_dev, x_dev, cycles, total_ms, stamps, 32);
 }

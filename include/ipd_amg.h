@@ -651,6 +651,17 @@ int ipd_amg_packed_operator(const ipd_amg* h, int32_t k, int32_t form, double* o
  * remote tail: the tail workgroup's busy clocks); the rest is the row work.  total_ms: HIP events. */
 int ipd_amg_bench_resident(ipd_amg* h, const double* b_dev, double* x_dev, int cycles,
                            double* total_ms, int64_t stamps[10]);
+/* The same launch, and the stamps by class of hand-off that the column-slice kernels (k_resident<16,16,0[,true]>)
+ * take with it (zeros from the other kernels): stamps[0 .. 9] as above, stamps[16 + c] workgroup 0's shader clocks
+ * from the start of the own work of a hand-off of class c to the start of the next hand-off's, stamps[24 + c] the
+ * hand-offs of class c.  Classes: 0 a level-1 half sweep published behind the barrier of the hand-off before it,
+ * 1 the first half sweep of a run (its totals come from LDS, behind a barrier of its own), 2 rr = r - A e, 3 the
+ * restriction, 4 level 2 (the composed pass, or each sweep, and the residual with the tail behind it), 5 the
+ * prolongation, 6 r = b - A x.  The counts add up to stamps[2]; the clocks add up to stamps[1] less the prologue
+ * and the additions of the correction.  Stamps cost LDS operations on the chain: timings come from
+ * ipd_amg_bench_cycles.                                                                                      */
+int ipd_amg_bench_resident_classes(ipd_amg* h, const double* b_dev, double* x_dev, int cycles,
+                                   double* total_ms, int64_t stamps[32]);
 
 /* Wall-clock attribution of the driver's phases when IPD_PROFILE=1 (each phase is then
  * bracketed by stream synchronisations).  Slots: 0 ASAt, 1 build Ae, 2 components,
