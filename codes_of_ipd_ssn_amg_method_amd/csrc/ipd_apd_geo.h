@@ -1,4 +1,4 @@
-// Launch geometry of the drivers' tile walker (k_tiles, ipd_driver.hip) and the sizes of the partial-sum buffers
+// Launch geometry of the drivers' tile walker (k_tiles, ipd_apd_tiles.h) and the sizes of the partial-sum buffers
 // that follow from it.  x(i,j) = x[i + j*m]; a workgroup is 4 waves of 64 consecutive rows each (TR rows), a wave
 // walks reps chunks of TC columns alone; the grid is nib x njg.  The walk itself: chunk `rep` of column group `jg`
 // starts at column apd_step_col(g, jg, rep) and ends the walk when that is >= n.  Host-clean: no HIP types, no

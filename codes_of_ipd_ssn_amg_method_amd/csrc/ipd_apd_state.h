@@ -1,0 +1,131 @@
+// Host side of the drivers, shared by their units: the handle, the records the passes hand back, and the host
+// functions that cross from one unit to another.  A kernel is launched only by the unit that defines it, so
+// another unit goes through one of these functions.
+//   ipd_driver.hip       workspace creation, apd_iterate, the step-reuse test, the ABI
+//   ipd_apd_passes.hip   the four pass families of an iteration (begin, eval, merit, end) and their epilogues
+//   ipd_apd_warm.hip     the A-ADMM warm start
+//   ipd_plan.hip         the transport plan as a sparse matrix, out of and into the workspace
+//   ipd_cost.hip         the cost matrix from point clouds
+#pragma once
+
+#include <functional>
+
+#include "ipd_amg_internal.h"
+#include "ipd_apd_script.h"
+#include "ipd_apd_tiles.h"
+
+// device-side scalar results (read back through pinned memory)
+struct ApdScal {
+    double normF2, lam2, wlk_lam, prox2, z2, zmp2, count, fold_zeta;  // eval
+    double kx2, ky2, kz2, kl2, fx;                                     // end
+};
+
+struct EvalRes {
+    double normF = 0, lam2 = 0, wlk_lam = 0, prox2 = 0, z2 = 0, zmp2 = 0, fold_zeta = 0;
+    long long E = 0;
+};
+
+struct ipd_apd {
+    ipd_ctx* ctx = nullptr;
+    std::unique_ptr<Arena> arena;
+    int cls = 1, m = 0, n = 0, M = 0, L = 0;
+    size_t mn = 0, U = 0;
+    Prob P{};
+    Geo geo{};
+    double mu = 0.0;
+    // problem data
+    double *c = nullptr, *gama = nullptr, *phi = nullptr, *p = nullptr, *q = nullptr, *b = nullptr;
+    // workspace; the x block is the first mn entries of u and v (class 2: of uk = [xk;yk;zk])
+    double *u = nullptr, *u2 = nullptr, *v = nullptr, *w = nullptr;
+    double *lam = nullptr, *lam_a = nullptr, *lam_b = nullptr, *wlk = nullptr;
+    double *F_a = nullptr, *F_b = nullptr, *zeta = nullptr, *negF = nullptr, *tmask = nullptr;
+    uint8_t* s = nullptr;
+    double *lpart = nullptr, *rpart = nullptr, *spart = nullptr;
+    ApdScal* dscal = nullptr;
+    double* fpart = nullptr;
+    int* counter = nullptr;
+    double* merit = nullptr;
+    bool merit3 = false;   // of the last ipd_apd_run -- class 1, prob 3: the merit needs |zk|^2 and |zk - prox(zk)|^2 (:186)
+    double *phi_l = nullptr, *phi_part = nullptr;  // Ax(phi), partial sums of |phi|^2
+    int phi_npart = 0;
+    ipd_cost_stats cost_stats{};   // min, max, sum of c: from the build out of points, or on demand (ipd_apd_get_cost)
+    bool have_cost_stats = false;  // (c never changes after the create)
+    // script variables
+    int k = 0;
+    double bk = 1.0;
+    double ak = 0, bk1 = 0, tk = 0;  // of the iteration opened by begin()
+    bool have_kkt = false;
+    double kkt0[4] = {0, 0, 0, 0};   // KKT_xk(1), KKT_lk(1), KKT_yk(1), KKT_zk(1)
+    double kkt[4] = {0, 0, 0, 0};
+    double fval = 0.0;
+    bool converged = false;
+    std::vector<double> h_fx, h_kx, h_kl, h_ky, h_kz, h_ssn;
+    std::vector<ipd_ssn_rec> recs;
+    long long sum_amg = 0, total_amg = 0, fail_amg = 0, max_amg = 0;
+    int restarts = 0;
+    // row f3: hierarchies of the previous Newton step and what its system was built from
+    StepDonors step;
+    bool krylov = false;   // ipd_apd_set_krylov: inner_solver 4 runs AMG-PCG behind Hybrid_AMG / AMG4POT
+    bool step_reuse = true, have_prev = false;
+    double prev_bk1 = 0.0, prev_tk = 0.0;
+    size_t s_words = 0;
+    unsigned long long *s_prev = nullptr, *t_prev = nullptr;
+    int* step_changed = nullptr;
+    int nblk() const { return (int)apd_nblk(geo); }
+};
+
+inline Parts parts_of(const ipd_apd* h) {
+    Parts pt;
+    pt.g = h->geo;
+    pt.lpart = h->lpart;
+    pt.rpart = h->rpart;
+    pt.spart = h->spart;
+    pt.nblk = h->nblk();
+    return pt;
+}
+
+inline void copy_dev(ipd_apd* h, double* dst, const double* src, size_t n) {
+    IPD_HIP(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, h->ctx->stream));
+}
+
+namespace {   // as k_tiles: the calling unit's own instantiation
+
+template <class Op>
+void launch_tiles(ipd_apd* h, const Op& op) {
+    const Geo& g = h->geo;
+    hipLaunchKernelGGL(k_tiles<Op>, dim3(g.nib, g.njg), dim3(256), 0, h->ctx->stream, op, g,
+                       h->lpart, h->rpart, h->spart);
+    IPD_KERNEL_CHECK();
+}
+
+}  // namespace
+
+// ---- ipd_driver.hip ------------------------------------------------------------------------
+// Fills the device arrays of a workspace under construction: c (mn), phi_ones (mn, to be set to ones; nullptr
+// when the workspace has no phi or the caller gave one), *st the statistics of c.  A throw abandons the create.
+using ApdCostFill = std::function<void(double* c_dev, double* phi_ones_dev, ipd_cost_stats* st)>;
+// The one body of ipd_apd_create and ipd_apd_create_points.  Allocates and uploads everything but c: fill == nullptr
+// uploads d->c (and needs d->phi for class 2), otherwise fill makes c (and the phi the caller left out).
+void apd_create_common(ipd_ctx* ctx, const ipd_apd_data* d, const ApdCostFill* fill, ipd_apd** out);
+// the script variables after a new state went in: what ipd_apd_set_state does besides the uploads
+// (k, the KKT reference, the records and the AMG counters start over; bk, lk, histories stay)
+void apd_restart_script(ipd_apd* h);
+
+// ---- ipd_apd_passes.hip --------------------------------------------------------------------
+size_t apd_fpart_len(int L);   // doubles of ipd_apd::fpart, the evaluation epilogue's per-workgroup partials
+// wk, wlk of iteration k; sets h->ak, bk1, tk                    Class1 :113-126, Class2 :110-120
+void apd_begin(ipd_apd* h, int k);
+// one pass at lam_base (+ step*zeta): F -> F_out, multiplier -> lam_out, mask -> h->s.  merit3: the pass also
+// sums |zk|^2 and |zk - prox(zk)|^2 (class 1)
+EvalRes apd_eval(ipd_apd* h, bool merit3, const double* lam_base, const double* zeta, double step, double* lam_out,
+                 double* F_out, const double* F_old);
+// merit cFk at lam_base + step[k]*zeta for MK steps (class 1 prob < 3 and class 2)
+void apd_merit(ipd_apd* h, const double* lam_base, const double* zeta, const double step[MK], double merit[MK]);
+// uk1/vk1 (from_w) and the KKT residuals of the iterate at multiplier `lam`
+void apd_end(ipd_apd* h, bool from_w, const double* src_u, const double* lam, double out_kkt[4], double* fx);
+// device time of `reps` evaluation passes at h->lam, without their epilogue
+float apd_bench_eval(ipd_apd* h, bool merit3, int reps);
+
+// ---- ipd_apd_warm.hip ----------------------------------------------------------------------
+// A-ADMM warm start                       warmup_class1.m:22-96 / warmup_class2.m:19-100
+void apd_warmup(ipd_apd* h, double res, long long maxit);

@@ -23,7 +23,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "ipd_cost.h"
+#include "ipd_apd_state.h"
 #include "ipd_cost_plan.h"
 
 namespace {
@@ -362,23 +362,23 @@ extern "C" int ipd_apd_create_points(ipd_ctx* ctx, const ipd_apd_data* d, const 
 extern "C" int ipd_apd_get_cost(ipd_apd* h, double* c, ipd_cost_stats* st) {
     return ipd_guard([&] {
         IPD_REQUIRE(h, IPD_E_ARG, "ipd_apd_get_cost: NULL handle");
-        const ApdCostView w = apd_cost_view(h);
-        ipd_ctx* ctx = w.ctx;
+        ipd_ctx* ctx = h->ctx;
         CallScope scope(ctx);
-        if (c) ctx->fetch(w.c, c, w.mn);
+        if (c) ctx->fetch(h->c, c, h->mn);
         if (!st) return;
-        if (!*w.have_stats) {
+        if (!h->have_cost_stats) {
             Arena& S = *ctx->scratch;
             CostArgs a{};
-            a.g = cost_geo(w.m, w.n, 1);
+            a.g = cost_geo(h->m, h->n, 1);
             a.part = S.alloc<double>((size_t)a.g.nib * a.g.njg * CSC);
             ipd_cost_stats* dst =
                 reinterpret_cast<ipd_cost_stats*>(S.alloc<double>(sizeof(ipd_cost_stats) / sizeof(double)));
-            hipLaunchKernelGGL(k_cost_stats, dim3(a.g.nib, a.g.njg), dim3(256), 0, ctx->stream, a, w.c);
+            hipLaunchKernelGGL(k_cost_stats, dim3(a.g.nib, a.g.njg), dim3(256), 0, ctx->stream, a,
+                               (const double*)h->c);
             IPD_KERNEL_CHECK();
-            finish_stats(ctx, a, dst, w.stats);
-            *w.have_stats = true;
+            finish_stats(ctx, a, dst, &h->cost_stats);
+            h->have_cost_stats = true;
         }
-        *st = *w.stats;
+        *st = h->cost_stats;
     });
 }

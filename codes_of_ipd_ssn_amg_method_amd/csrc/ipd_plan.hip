@@ -5,13 +5,14 @@
 // built where xk lives: the dense iterate never crosses the host boundary, only the kept entries
 // and n+1 column pointers do.
 //
-//   count   one streaming read of x and c.  Layout and walk are k_tiles' (ipd_driver.hip):
+//   count   one streaming read of x and c.  Layout and walk are k_tiles' (ipd_apd_tiles.h):
 //           x(i,j) = x[i + j*m], a wave owns 64 consecutive rows (one SEGMENT) and walks
 //           16*reps columns alone, lanes along i (coalesced), 16 loads per lane and array in
 //           flight, no LDS tile, no barrier inside the column loop.  The kept count of a
 //           (column, segment) pair is a wave ballot and a population count; the sums of the
 //           statistics leave as per-workgroup partials, the marginals Ax(x_kept) as the row /
-//           column partials the driver's passes write (lpart / rpart).
+//           column partials the driver's passes write (lpart / rpart): the geometry is the
+//           driver's make_geo and the column butterfly is the tile walker's own.
 //   offsets column-major order (columns outer, segments inner) in two levels: a wave per column
 //           scans the column's segment counts in place and leaves the column total, and
 //           exclusive_scan_i32 turns the n totals into the column pointers.  offset(j, seg) =
@@ -27,29 +28,27 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "ipd_plan.h"
+#include "ipd_apd_state.h"
 
 namespace {
 
-constexpr int TR = 256;   // rows of a workgroup: 4 waves x 64
-constexpr int TC = 16;    // columns in flight per wave
+// TR, TC: ipd_apd_geo.h; colsum16, colsum_index: ipd_apd_tiles.h
 constexpr int PSC = 4;    // statistics per workgroup: sum_kept, sum_dropped, max_dropped, fval_kept
 
 struct PlanGeo {
     int m, n, nseg, nib, njg, reps;   // njg column groups of reps*TC columns
 };
 
+// the natural geometry of the driver's walker (IPD_APD_REPS is not read) plus the 64-row segments
 PlanGeo plan_geo(int m, int n) {
+    const Geo d = make_geo(m, n);
     PlanGeo g;
     g.m = m;
     g.n = n;
     g.nseg = cdiv(m, 64);
-    g.nib = cdiv(m, TR);
-    const int njb = cdiv(n, TC);
-    int reps = 1;   // a wave walks more columns once the grid is large anyway (as the driver's make_geo)
-    while (reps < 8 && (long long)g.nib * cdiv(njb, reps * 2) >= 4096) reps *= 2;
-    g.reps = reps;
-    g.njg = cdiv(njb, reps);
+    g.nib = d.nib;
+    g.njg = d.njg;
+    g.reps = d.reps;
     return g;
 }
 
@@ -71,39 +70,6 @@ __device__ __forceinline__ double wave_max(double v) {
         v = o > v ? o : v;
     }
     return v;
-}
-
-// The 16 column sums over a wave's 64 rows out of 16 values per lane: the register butterfly of
-// the driver's tile walker (17 exchanges instead of 16 wave reductions), restated here so that
-// this unit shares no device code with another one.  Lane l < 16 ends with column
-// colsum_index(l).
-__device__ __forceinline__ double colsum16(const double (&xv)[TC], int lane) {
-    double a8[8], a4[4], a2[2], a1;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const bool hi = lane & 1;
-        a8[k] = (hi ? xv[k + 8] : xv[k]) + __shfl_xor(hi ? xv[k] : xv[k + 8], 1);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const bool hi = lane & 2;
-        a4[k] = (hi ? a8[k + 4] : a8[k]) + __shfl_xor(hi ? a8[k] : a8[k + 4], 2);
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const bool hi = lane & 4;
-        a2[k] = (hi ? a4[k + 2] : a4[k]) + __shfl_xor(hi ? a4[k] : a4[k + 2], 4);
-    }
-    {
-        const bool hi = lane & 8;
-        a1 = (hi ? a2[1] : a2[0]) + __shfl_xor(hi ? a2[0] : a2[1], 8);
-    }
-    a1 += __shfl_xor(a1, 16);
-    a1 += __shfl_xor(a1, 32);
-    return a1;
-}
-__device__ __forceinline__ int colsum_index(int lane) {
-    return ((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3);
 }
 
 // ---------------------------------------------------------------------------
@@ -252,8 +218,9 @@ struct PlanFin {
     PlanScal* out;
 };
 
-// sum of `count` partials `stride` apart, in index order; the loads go out 8 at a time
-__device__ __forceinline__ double sum_strided(const double* __restrict__ base, int count, size_t stride) {
+// sum of `count` partials `stride` apart, in index order; the loads go out 8 at a time (the tile walker's
+// sum_strided adds in the same order with 32 loads in flight)
+__device__ __forceinline__ double sum_strided8(const double* __restrict__ base, int count, size_t stride) {
     double s = 0.0;
     int k = 0;
     for (; k + 8 <= count; k += 8) {
@@ -275,8 +242,8 @@ __global__ __launch_bounds__(256) void k_plan_fin(const PlanFin a) {
     if (t <= g.n) a.jc[t] = a.jc32[t];
     if (a.ax && t < g.n + g.m) {
         // [X'*p ; X*q]: the segment slots of a column, then the column groups of a row, in index order
-        a.ax[t] = t < g.n ? sum_strided(a.rpart + t, 4 * g.nib, (size_t)g.n)
-                          : sum_strided(a.lpart + (t - g.n), g.njg, (size_t)g.m);
+        a.ax[t] = t < g.n ? sum_strided8(a.rpart + t, 4 * g.nib, (size_t)g.n)
+                          : sum_strided8(a.lpart + (t - g.n), g.njg, (size_t)g.m);
     }
     if (blockIdx.x != 0) return;
     // the statistics: thread t adds workgroups t, t+256, ... in that order, then the 256 threads'
@@ -398,13 +365,13 @@ struct PlanWork {
 };
 
 // count, offsets and the finishing kernel; *st is filled (the stream is waited for)
-void plan_count_phase(const ApdPlanView& w, double tol, int64_t* jc_dev, double* ax_dev, PlanWork* wk,
+void plan_count_phase(ipd_apd* h, double tol, int64_t* jc_dev, double* ax_dev, PlanWork* wk,
                       ipd_plan_stats* st) {
-    ipd_ctx* ctx = w.ctx;
+    ipd_ctx* ctx = h->ctx;
     Arena& S = *ctx->scratch;
     // the counts and offsets are 32-bit; m, n <= 16384 (ipd_apd_create) keeps mn below 2^31
-    IPD_REQUIRE(w.mn < (size_t(1) << 31), IPD_E_LIMIT, "ipd_apd_plan: 2^31 entries or more");
-    const PlanGeo g = plan_geo(w.m, w.n);
+    IPD_REQUIRE(h->mn < (size_t(1) << 31), IPD_E_LIMIT, "ipd_apd_plan: 2^31 entries or more");
+    const PlanGeo g = plan_geo(h->m, h->n);
     wk->g = g;
     const int nblk = g.nib * g.njg;
     int* cnt = S.alloc<int>((size_t)g.n * g.nseg);
@@ -414,10 +381,10 @@ void plan_count_phase(const ApdPlanView& w, double tol, int64_t* jc_dev, double*
     PlanScal* dscal = reinterpret_cast<PlanScal*>(S.alloc<double>(sizeof(PlanScal) / sizeof(double)));
     PlanCount a;
     a.g = g;
-    a.x = w.u;
-    a.c = w.c;
-    a.p = w.p;
-    a.q = w.q;
+    a.x = h->u;
+    a.c = h->c;
+    a.p = h->p;
+    a.q = h->q;
     a.tol = tol;
     a.cnt = cnt;
     a.spart = spart;
@@ -453,21 +420,21 @@ void plan_count_phase(const ApdPlanView& w, double tol, int64_t* jc_dev, double*
     st->sum_dropped = s.sum_dropped;
     st->max_dropped = s.max_dropped;
     st->fval_kept = s.fval_kept;
-    IPD_REQUIRE(s.nnz >= 0 && (size_t)s.nnz <= w.mn, IPD_E_HIP, "ipd_apd_plan: the kept count is out of range");
+    IPD_REQUIRE(s.nnz >= 0 && (size_t)s.nnz <= h->mn, IPD_E_HIP, "ipd_apd_plan: the kept count is out of range");
     wk->segpre = cnt;
     wk->jc32 = jc32;
 }
 
-void plan_fill_phase(const ApdPlanView& w, double tol, const PlanWork& wk, int64_t* ir_dev, double* pr_dev) {
+void plan_fill_phase(ipd_apd* h, double tol, const PlanWork& wk, int64_t* ir_dev, double* pr_dev) {
     PlanFill f;
     f.g = wk.g;
-    f.x = w.u;
+    f.x = h->u;
     f.tol = tol;
     f.segpre = wk.segpre;
     f.jc32 = wk.jc32;
     f.ir = ir_dev;
     f.pr = pr_dev;
-    hipLaunchKernelGGL(k_plan_fill, dim3(wk.g.nib, wk.g.njg), dim3(256), 0, w.ctx->stream, f);
+    hipLaunchKernelGGL(k_plan_fill, dim3(wk.g.nib, wk.g.njg), dim3(256), 0, h->ctx->stream, f);
     IPD_KERNEL_CHECK();
 }
 
@@ -483,17 +450,16 @@ extern "C" int ipd_apd_plan_dev(ipd_apd* h, double tol, int64_t cap, int64_t* jc
         IPD_REQUIRE(tol >= 0.0, IPD_E_ARG, "ipd_apd_plan_dev: tol must be >= 0");   // false for a NaN
         IPD_REQUIRE(cap >= 0, IPD_E_ARG, "ipd_apd_plan_dev: cap must be >= 0");
         IPD_REQUIRE(cap == 0 || (ir_dev && pr_dev), IPD_E_ARG, "ipd_apd_plan_dev: ir_dev / pr_dev are NULL");
-        const ApdPlanView w = apd_plan_view(h);
-        CallScope scope(w.ctx);
+        CallScope scope(h->ctx);
         PlanWork wk;
-        plan_count_phase(w, tol, jc_dev, ax_dev, &wk, st);
+        plan_count_phase(h, tol, jc_dev, ax_dev, &wk, st);
         if (st->nnz > cap) {
-            w.ctx->sync();
+            h->ctx->sync();
             throw IpdError(IPD_E_LIMIT, "ipd_apd_plan_dev: the plan has " + std::to_string(st->nnz) +
                                             " entries, cap is " + std::to_string(cap));
         }
-        if (st->nnz > 0) plan_fill_phase(w, tol, wk, ir_dev, pr_dev);
-        w.ctx->sync();   // the scratch arrays are the next call's
+        if (st->nnz > 0) plan_fill_phase(h, tol, wk, ir_dev, pr_dev);
+        h->ctx->sync();   // the scratch arrays are the next call's
     });
 }
 
@@ -506,31 +472,30 @@ extern "C" int ipd_apd_plan(ipd_apd* h, double tol, ipd_csc_out* X, ipd_plan_sta
     const int rc = ipd_guard([&] {
         IPD_REQUIRE(h && X && st, IPD_E_ARG, "ipd_apd_plan: NULL argument");
         IPD_REQUIRE(tol >= 0.0, IPD_E_ARG, "ipd_apd_plan: tol must be >= 0");   // false for a NaN
-        const ApdPlanView w = apd_plan_view(h);
-        ipd_ctx* ctx = w.ctx;
+        ipd_ctx* ctx = h->ctx;
         CallScope scope(ctx);
         Arena& S = *ctx->scratch;
-        const int M = w.m + w.n;
-        int64_t* jc_dev = S.alloc<int64_t>((size_t)w.n + 1);
+        const int M = h->m + h->n;
+        int64_t* jc_dev = S.alloc<int64_t>((size_t)h->n + 1);
         double* ax_dev = ax ? S.alloc<double>((size_t)M) : nullptr;
         PlanWork wk;
-        plan_count_phase(w, tol, jc_dev, ax_dev, &wk, st);
+        plan_count_phase(h, tol, jc_dev, ax_dev, &wk, st);
         const size_t nnz = (size_t)st->nnz;
-        X->jc = (int64_t*)std::malloc(sizeof(int64_t) * ((size_t)w.n + 1));
+        X->jc = (int64_t*)std::malloc(sizeof(int64_t) * ((size_t)h->n + 1));
         X->ir = (int64_t*)std::malloc(sizeof(int64_t) * (nnz ? nnz : 1));
         X->pr = (double*)std::malloc(sizeof(double) * (nnz ? nnz : 1));
         if (!X->jc || !X->ir || !X->pr) throw IpdError(IPD_E_NOMEM, "out of host memory");
         if (nnz) {
             int64_t* ir_dev = S.alloc<int64_t>(nnz);
             double* pr_dev = S.alloc<double>(nnz);
-            plan_fill_phase(w, tol, wk, ir_dev, pr_dev);
+            plan_fill_phase(h, tol, wk, ir_dev, pr_dev);
             ctx->fetch(ir_dev, X->ir, nnz);
             ctx->fetch(pr_dev, X->pr, nnz);
         }
-        ctx->fetch(jc_dev, X->jc, (size_t)w.n + 1);
+        ctx->fetch(jc_dev, X->jc, (size_t)h->n + 1);
         if (ax) ctx->fetch(ax_dev, ax, (size_t)M);
-        X->nrows = w.m;
-        X->ncols = w.n;
+        X->nrows = h->m;
+        X->ncols = h->n;
         X->nnz = st->nnz;
     });
     if (rc != IPD_OK && X) ipd_csc_free(X);
@@ -540,43 +505,42 @@ extern "C" int ipd_apd_plan(ipd_apd* h, double tol, ipd_csc_out* X, ipd_plan_sta
 extern "C" int ipd_apd_set_plan(ipd_apd* h, const ipd_csc* X) {
     return ipd_guard([&] {
         IPD_REQUIRE(h && X, IPD_E_ARG, "ipd_apd_set_plan: NULL argument");
-        const ApdPlanView w = apd_plan_view(h);
         // everything is checked on the host before the workspace is touched
-        IPD_REQUIRE(X->nrows == w.m && X->ncols == w.n, IPD_E_ARG, "ipd_apd_set_plan: X must be m x n");
+        IPD_REQUIRE(X->nrows == h->m && X->ncols == h->n, IPD_E_ARG, "ipd_apd_set_plan: X must be m x n");
         IPD_REQUIRE(X->nnz >= 0 && X->jc && (X->nnz == 0 || (X->ir && X->pr)), IPD_E_ARG,
                     "ipd_apd_set_plan: NULL array or negative nnz");
         IPD_REQUIRE(X->jc[0] == 0, IPD_E_ARG, "ipd_apd_set_plan: jc[0] must be 0");
-        for (int j = 0; j < w.n; ++j)
+        for (int j = 0; j < h->n; ++j)
             IPD_REQUIRE(X->jc[j + 1] >= X->jc[j], IPD_E_ARG, "ipd_apd_set_plan: jc must be non-decreasing");
-        IPD_REQUIRE(X->jc[w.n] == X->nnz, IPD_E_ARG, "ipd_apd_set_plan: jc[n] must be nnz");
-        for (int j = 0; j < w.n; ++j) {
+        IPD_REQUIRE(X->jc[h->n] == X->nnz, IPD_E_ARG, "ipd_apd_set_plan: jc[n] must be nnz");
+        for (int j = 0; j < h->n; ++j) {
             int64_t prev = -1;
             for (int64_t t = X->jc[j]; t < X->jc[j + 1]; ++t) {
                 const int64_t r = X->ir[t];
-                IPD_REQUIRE(r >= 0 && r < w.m, IPD_E_ARG, "ipd_apd_set_plan: row index outside [0, m)");
+                IPD_REQUIRE(r >= 0 && r < h->m, IPD_E_ARG, "ipd_apd_set_plan: row index outside [0, m)");
                 IPD_REQUIRE(r > prev, IPD_E_ARG, "ipd_apd_set_plan: rows must be strictly ascending in a column");
                 prev = r;
             }
         }
-        ipd_ctx* ctx = w.ctx;
+        ipd_ctx* ctx = h->ctx;
         CallScope scope(ctx);
         const size_t nnz = (size_t)X->nnz;
         if (nnz) {
             Arena& S = *ctx->scratch;
-            int64_t* jc_dev = S.alloc<int64_t>((size_t)w.n + 1);
+            int64_t* jc_dev = S.alloc<int64_t>((size_t)h->n + 1);
             int64_t* ir_dev = S.alloc<int64_t>(nnz);
             double* pr_dev = S.alloc<double>(nnz);
-            ctx->upload(jc_dev, X->jc, (size_t)w.n + 1);
+            ctx->upload(jc_dev, X->jc, (size_t)h->n + 1);
             ctx->upload(ir_dev, X->ir, nnz);
             ctx->upload(pr_dev, X->pr, nnz);
-            IPD_HIP(hipMemsetAsync(w.u, 0, w.mn * sizeof(double), ctx->stream));
-            hipLaunchKernelGGL(k_plan_scatter, dim3(cdiv((long long)nnz, 256)), dim3(256), 0, ctx->stream, w.m,
-                               w.n, (long long)nnz, jc_dev, ir_dev, pr_dev, w.u);
+            IPD_HIP(hipMemsetAsync(h->u, 0, h->mn * sizeof(double), ctx->stream));
+            hipLaunchKernelGGL(k_plan_scatter, dim3(cdiv((long long)nnz, 256)), dim3(256), 0, ctx->stream, h->m,
+                               h->n, (long long)nnz, jc_dev, ir_dev, pr_dev, h->u);
             IPD_KERNEL_CHECK();
         } else {
-            IPD_HIP(hipMemsetAsync(w.u, 0, w.mn * sizeof(double), ctx->stream));
+            IPD_HIP(hipMemsetAsync(h->u, 0, h->mn * sizeof(double), ctx->stream));
         }
-        IPD_HIP(hipMemcpyAsync(w.v, w.u, w.mn * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        IPD_HIP(hipMemcpyAsync(h->v, h->u, h->mn * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
         ctx->sync();   // the scratch arrays are the next call's
         apd_restart_script(h);
     });
