@@ -109,8 +109,6 @@ void amg_prepare_levels(ipd_amg* h);  // dinv, Axi, xx, work vectors
 void amg_cycle(ipd_amg* h, int k, int isnsp, bool wcycle, bool keep_e);
 bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int m, int n, double tk,
                        bool policy, bool transfers_only = false);
-// a component's mask form is only of use beyond k_resident's 2048 rows (the mask-form kernel's deep mode)
-static constexpr int RES_MASK_MIN_ROWS = 2048;
 void amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev, double* x_dev,
                    int32_t* it, double* rel_res, double* rel_resk, double* rhok);
 // Level 1's launch-path row walk (descriptor, LDS staging, grid of a whole-level pass); false when
@@ -166,50 +164,7 @@ void pcg_dev(ipd_ctx* ctx, const Csr& H, const double* e, const double* guess, d
              long long maxit, int precd, double* d, long long* it, double* res, double* resk_host,
              long long nf = 0);
 
-// ipd_hybrid.hip: problem-level solvers on device-resident data
-struct HybridOut {
-    int itamg = 0;
-    double resamg = 0.0;
-    long long num_comp = 0, it_num = 0;
-};
-// Row f3, reuse across Newton steps: the hierarchies of the previous Hybrid_AMG / AMG4POT call of
-// a driver, kept alive so that a step whose system is the SAME (same active set, T, bk1, tk: the
-// caller says so in `same`) shares their rand-independent levels 1-2 through amg_setup's donor
-// mechanism.  Guesses and levels >= 3 still draw the stream's next numbers, so results and the
-// count of consumed numbers are those of a full setup, bit for bit.
-struct StepDonors {
-    std::vector<std::shared_ptr<ipd_amg>> prev;   // in order of use (large components)
-    bool same = false;                            // set by the caller before each call
-    long long steps = 0, same_steps = 0, shared = 0;   // calls, calls with `same`, donated setups
-};
-// opts.twogrid selects Hybrid_twogrid.m (twogrid_bigph on every large component)
-void hybrid_amg_dev(ipd_ctx* ctx, const Csr& H0, const double* tdiag, const double* p,
-                    const double* q, int m, int n, double bk1, double tk, const double* z,
-                    const AmgOpts& opts, ipd_rng* rng, double* zeta, HybridOut* out,
-                    StepDonors* step = nullptr);
-void amg4pot_dev(ipd_ctx* ctx, const Csr& H0, const double* tdiag, const double* p,
-                 const double* q, int m, int n, double bk1, double tk, const double* z,
-                 const uint8_t* s, const double* phi, const AmgOpts& opts, ipd_rng* rng,
-                 double* zeta, HybridOut* out, StepDonors* step = nullptr);
-// aug_PCG.m / Class2/PCG4POT.m (inner_solver = 3): PCG on the kernel-augmented system
-void aug_pcg_dev(ipd_ctx* ctx, const Csr& H0, const double* tdiag, const double* p, const double* q,
-                 int m, int n, double bk1, double tk, const double* z, double tol, long long maxit,
-                 double* zeta, HybridOut* out);
-void pcg4pot_dev(ipd_ctx* ctx, const Csr& H0, const double* tdiag, const double* p, const double* q,
-                 int m, int n, double bk1, double tk, const double* z, const uint8_t* s,
-                 const double* phi, double tol, long long maxit, double* zeta, HybridOut* out);
-// Class 2, inner_solver = 1 / 2: direct solve resp. PCG on the bordered Jacobian itself
-// (APD_SsN_Class2.m:152-161)
-void direct_pot_dev(ipd_ctx* ctx, const Csr& H0, const double* tdiag, const double* p, const double* q,
-                    int m, int n, double bk1, double tk, const double* z, const uint8_t* s,
-                    const double* phi, double* zeta);
-void pcg_pot_dev(ipd_ctx* ctx, const Csr& H0, const double* tdiag, const double* p, const double* q,
-                 int m, int n, double bk1, double tk, const double* z, const uint8_t* s,
-                 const double* phi, double tol, long long maxit, double* zeta, HybridOut* out);
 // ipd_dense.hip: dense Cholesky (MATLAB's `\` on the cold paths' SPD systems)
 void dense_chol_factor(ipd_ctx* ctx, double* A, int n, int ld);              // lower triangle, in place
 void dense_chol_solve(ipd_ctx* ctx, const double* L, int n, int ld, double* B, int nrhs, int ldb);
 void spd_solve_dev(ipd_ctx* ctx, const Csr& A, const double* b, double* x);  // x = A \ b
-// Jk = bk1*I + (T + H0)/tk (APD_SsN_Class1.m:151, inner_solver = 2)
-void build_jk(ipd_ctx* ctx, Arena& dst, const Csr& H0, const double* tdiag, double bk1, double tk,
-              Csr* J);

@@ -11,6 +11,7 @@
 #include <functional>
 
 #include "ipd_amg_internal.h"
+#include "ipd_hybrid_state.h"
 #include "ipd_apd_script.h"
 #include "ipd_apd_tiles.h"
 

@@ -86,26 +86,33 @@ bool step_same_system(ipd_apd* h, double bk1, double tk) {
 void newton_direction(ipd_apd* h, const ipd_apd_opts& o, const AmgOpts& amg, ipd_rng* rng, const Csr& H0,
                       StepDonors* step, HybridOut* ho) {
     ipd_ctx* ctx = h->ctx;
-    const double bk1 = h->bk1, tk = h->tk;
-    const double *p = h->p, *q = h->q, *z = h->negF;
-    const int m = h->m, n = h->n;
+    const double* z = h->negF;
+    NewtonSys sys;
+    sys.H0 = H0;
+    sys.tdiag = h->cls == 2 ? h->tmask : nullptr;
+    sys.p = h->p;
+    sys.q = h->q;
+    sys.m = h->m;
+    sys.n = h->n;
+    sys.bk1 = h->bk1;
+    sys.tk = h->tk;
     switch (apd_route(h->cls == 2, o.inner_solver)) {
         case ROUTE_DIRECT: {                                       // :146-148
             Csr Jk;
-            build_jk(ctx, *ctx->scratch, H0, nullptr, bk1, tk, &Jk);
+            build_jk(ctx, *ctx->scratch, sys, &Jk);
             spd_solve_dev(ctx, Jk, z, h->zeta);
             ho->itamg = 1;                                         // itpcg = 1; respcg = 0; info = [0,0]
             ho->resamg = 0.0;
             break;
         }
         case ROUTE_DIRECT_POT:                                     // Class2 :152-156
-            direct_pot_dev(ctx, H0, h->tmask, p, q, m, n, bk1, tk, z, h->s, h->phi, h->zeta);
+            direct_pot_dev(ctx, sys, z, h->s, h->phi, h->zeta);
             ho->itamg = 1;
             ho->resamg = 0.0;
             break;
         case ROUTE_PCG: {                                          // :149-152  PCG(Jk,-Fk_old)
             Csr Jk;
-            build_jk(ctx, *ctx->scratch, H0, nullptr, bk1, tk, &Jk);
+            build_jk(ctx, *ctx->scratch, sys, &Jk);
             long long it2 = 0;
             double res2 = 0.0;
             pcg_dev(ctx, Jk, z, nullptr, o.pcg_retol, o.pcg_maxit, 2, h->zeta, &it2, &res2, nullptr);
@@ -114,21 +121,19 @@ void newton_direction(ipd_apd* h, const ipd_apd_opts& o, const AmgOpts& amg, ipd
             break;
         }
         case ROUTE_PCG_POT:                                        // Class2 :157-161  PCG on the bordered Jk
-            pcg_pot_dev(ctx, H0, h->tmask, p, q, m, n, bk1, tk, z, h->s, h->phi, o.pcg_retol, o.pcg_maxit,
-                        h->zeta, ho);
+            pcg_pot_dev(ctx, sys, z, h->s, h->phi, o.pcg_retol, o.pcg_maxit, h->zeta, ho);
             break;
         case ROUTE_AUG_PCG:                                        // :157-159
-            aug_pcg_dev(ctx, H0, nullptr, p, q, m, n, bk1, tk, z, o.pcg_retol, o.pcg_maxit, h->zeta, ho);
+            aug_pcg_dev(ctx, sys, z, o.pcg_retol, o.pcg_maxit, h->zeta, ho);
             break;
         case ROUTE_PCG4POT:                                        // Class2 :167-169
-            pcg4pot_dev(ctx, H0, h->tmask, p, q, m, n, bk1, tk, z, h->s, h->phi, o.pcg_retol, o.pcg_maxit,
-                        h->zeta, ho);
+            pcg4pot_dev(ctx, sys, z, h->s, h->phi, o.pcg_retol, o.pcg_maxit, h->zeta, ho);
             break;
         case ROUTE_HYBRID_AMG:                                     // Class1 :161
-            hybrid_amg_dev(ctx, H0, nullptr, p, q, m, n, bk1, tk, z, amg, rng, h->zeta, ho, step);
+            hybrid_amg_dev(ctx, sys, z, amg, rng, h->zeta, ho, step);
             break;
         case ROUTE_AMG4POT:                                        // Class2 :171
-            amg4pot_dev(ctx, H0, h->tmask, p, q, m, n, bk1, tk, z, h->s, h->phi, amg, rng, h->zeta, ho, step);
+            amg4pot_dev(ctx, sys, z, h->s, h->phi, amg, rng, h->zeta, ho, step);
             break;
     }
 }

@@ -104,3 +104,13 @@ static constexpr size_t RB_LDS_DOUBLES = (size_t)2 * RB_NMAX + 3 * RB_HALF + 2 *
                                          2 * 8 * RB_RPW_MAX + 20 * 8 * RB_RPW_MAX + 8 +
                                          2 * RB_N3MAX + 2 * RB_N4MAX + RB_N5MAX + 128;
 static constexpr size_t RB_LDS_BYTES = sizeof(double) * RB_LDS_DOUBLES;
+
+// Hybrid_AMG's routing (ipd_hybrid_plan.h): a component of more than HYBRID_N0 nodes gets its own AMG solve, the
+// others are solved together, one workgroup per block with the block's dense copy in LDS (Hybrid_AMG.m:51-53, :85)
+static constexpr int HYBRID_N0 = 100;
+// a component's mask form is only of use beyond k_resident's 2048 rows (the mask-form kernel's deep mode)
+static constexpr int RES_MASK_MIN_ROWS = 2048;
+static constexpr size_t HYBRID_SMALL_LDS_OPTIN = (size_t)96 * 1024;   // dynamic LDS k_small_blocks opts in to
+// k_small_blocks' dynamic LDS for blocks of up to nb rows: the nb x (nb + 1) matrix and the right-hand side
+static constexpr size_t hybrid_small_lds(int nb) { return sizeof(double) * ((size_t)nb * (nb + 1) + nb); }
+static_assert(hybrid_small_lds(HYBRID_N0) <= HYBRID_SMALL_LDS_OPTIN, "a small block of HYBRID_N0 rows must fit the LDS opted in to");

@@ -82,6 +82,31 @@ def test_hybrid_amg(ipd, name, m, n, mk, tfrac, cycle, pq_random):
     assert rng.consumed == used        # (the rand stream does not depend on the cycle count)
 
 
+def test_hybrid_amg_at_the_n0_boundary(ipd):
+    """The system of tests/test_hybrid_plan.py whose route is checked on the CPU: a component of exactly HYBRID_N0
+    nodes (solved with the small blocks) next to one of HYBRID_N0 + 1 (its own AMG solve, T != 0: isnsp = 0),
+    singletons, and a second large component with T = 0 behind them (Hybrid_AMG.m:53/85)."""
+    from tests.test_hybrid_plan import limits, mixed_system
+    N0 = limits()["HYBRID_N0"]
+    pd = mixed_system()
+    opts = O.amg_options_class2("v")
+    tr = []
+    zo, ito, reso, infoo = O.Hybrid_AMG(pd, opts, O.matlab_rng(), N0=N0, trace=tr)
+    assert [len(t_["pk"]) for t_ in tr] == [N0 + 1, 130] and [t_["isnsp"] for t_ in tr] == [0, 1]
+    rng = ipd.MatlabRand()
+    z, it, res, info = ipd.Hybrid_AMG(pd, opts, rng)
+    assert np.array_equal(info, infoo)
+    noise_floor = res <= 1e-10 and reso <= 1e-10
+    assert abs(it - ito) <= 1 or (noise_floor and abs(it - ito) <= 3), (it, ito, res, reso)
+    He = _he(pd)
+    nz = np.linalg.norm(pd["z"])
+    assert np.linalg.norm(He @ z - pd["z"]) <= max(1e-9, 20 * np.linalg.norm(He @ zo - pd["z"]) / nz) * nz
+    assert np.linalg.norm(z - zo) <= 1e-5 * max(1.0, np.linalg.norm(zo))
+    used = sum(len(t_["guess"]) + sum(len(i["mis"]["rand"]) for i in t_["h"].info[2:] if i and i.get("mis"))
+               for t_ in tr)
+    assert rng.consumed == used
+
+
 def test_hybrid_amg_zero_in_pq(ipd):
     m = n = 16
     s = PR.mask_tree(m, n, seed=1)
