@@ -90,6 +90,11 @@ class ipd_cost_stats(Structure):
     _fields_ = [("min", c_double), ("max", c_double), ("sum", c_double)]
 
 
+class ipd_cost_info(Structure):
+    _fields_ = [("form", c_int32), ("dim", c_int32), ("metric", c_int32), ("scale", c_int32),
+                ("device_bytes", c_int64)]
+
+
 class ipd_apd_result(Structure):
     _fields_ = [("converged", c_int32), ("k", c_int32), ("fval", c_double),
                 ("kkt", c_double * 4), ("rr", c_double), ("sum_amg", c_int64),
@@ -134,6 +139,8 @@ lib.ipd_apd_set_plan.argtypes = [c_void_p, c_void_p]
 lib.ipd_cost_points_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_create_points.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_get_cost.argtypes = [c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_create_points_free.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_cost_info.argtypes = [c_void_p, c_void_p]
 lib.ipd_apd_get_w.argtypes = [c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_eval_trial.argtypes = [c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int32, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]
@@ -166,6 +173,7 @@ EXPORTS = [
     "ipd_amg_packed_operator",
     "ipd_apd_plan", "ipd_apd_plan_dev", "ipd_apd_set_plan",
     "ipd_cost_points_dev", "ipd_apd_create_points", "ipd_apd_get_cost",
+    "ipd_apd_create_points_free", "ipd_apd_cost_info",
     "ipd_apd_get_w", "ipd_apd_eval_trial", "ipd_apd_merit", "ipd_apd_end",
 ]
 

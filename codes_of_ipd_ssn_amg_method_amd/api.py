@@ -775,18 +775,29 @@ class APDWorkspace:
 
     @classmethod
     def from_points(klass, cls, xs, ys, r, l, p, q, metric="sqeuclidean", scale=False, gama=np.inf,
-                    mu=0.0, phi=None, ctx=None):
+                    mu=0.0, phi=None, ctx=None, matrix_free=False):
         """The workspace of problem class ``cls`` with ``c = point_cost(xs, ys, metric, scale)`` built on
         the device (``ipd_apd_create_points``): (m+n)*d coordinates go up, nothing mn-sized.  ``xs`` is
         (m, d), ``ys`` (n, d), one point per row (1-D for d = 1); class 2 with ``phi=None`` takes
-        ``phi`` as all ones."""
+        ``phi`` as all ones.  ``matrix_free=True`` (``ipd_apd_create_points_free``, d <= 3) never stores
+        ``c``: the passes recompute an entry from the coordinates, with the bits of the stored one."""
         self = klass.__new__(klass)
         d = self._data(cls, r, l, p, q, gama, mu, phi, ctx)
         spec, keep = _cost_spec(xs, ys, metric, scale)
         if (spec.m, spec.n) != (self.m, self.n):
             raise ValueError(f"from_points: xs, ys must hold {self.m} and {self.n} points")
-        check(lib.ipd_apd_create_points((ctx or get_ctx()).handle, byref(d), byref(spec), byref(self.handle)))
+        create = lib.ipd_apd_create_points_free if matrix_free else lib.ipd_apd_create_points
+        check(create((ctx or get_ctx()).handle, byref(d), byref(spec), byref(self.handle)))
         return self
+
+    def cost_info(self) -> dict:
+        """How the workspace holds the cost (``ipd_apd_cost_info``): ``form`` 0 stored / 1 matrix-free,
+        ``dim, metric, scale`` of the point-cloud specification (0 for a host matrix) and
+        ``device_bytes``, what it keeps on the device for the cost."""
+        info = L.ipd_cost_info()
+        check(lib.ipd_apd_cost_info(self.handle, byref(info)))
+        return dict(form=int(info.form), dim=int(info.dim), metric=int(info.metric), scale=int(info.scale),
+                    device_bytes=int(info.device_bytes))
 
     def cost(self, stats: bool = False):
         """``c`` as an (m, n) array, read back from the workspace (``ipd_apd_get_cost``);
@@ -1144,22 +1155,26 @@ def point_cost(xs, ys, metric="sqeuclidean", scale=False, stats=False, ctx=None)
 
 def APD_SsN_Class1_points(xs, ys, r, l, p, q, metric="sqeuclidean", scale=False, gama=np.inf, prob=2,
                           rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
-                          plan_tol=None, **opts) -> dict:
-    """``APD_SsN_Class1`` with ``c = point_cost(xs, ys, metric, scale)`` built on the device."""
+                          plan_tol=None, matrix_free=False, **opts) -> dict:
+    """``APD_SsN_Class1`` with ``c = point_cost(xs, ys, metric, scale)`` built on the device
+    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``)."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=30, theta=1 / 4, smoth=5, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     warm = (0.0, 100) if prob > 0 else (5e-2, np.inf)
-    ws = APDWorkspace.from_points(1, xs, ys, r, l, p, q, metric=metric, scale=scale, gama=gama)
+    ws = APDWorkspace.from_points(1, xs, ys, r, l, p, q, metric=metric, scale=scale, gama=gama,
+                                  matrix_free=matrix_free)
     return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol)
 
 
 def APD_SsN_Class2_points(xs, ys, r, l, p, q, mu, phi=None, metric="sqeuclidean", scale=False,
                           rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
-                          plan_tol=None, **opts) -> dict:
-    """``APD_SsN_Class2`` with the cost built on the device; ``phi=None`` is all ones."""
+                          plan_tol=None, matrix_free=False, **opts) -> dict:
+    """``APD_SsN_Class2`` with the cost built on the device; ``phi=None`` is all ones
+    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``)."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=40, theta=1 / 4, smoth=10, cycle="w",
                                 isnsp=1, inter=1, guess=None)
-    ws = APDWorkspace.from_points(2, xs, ys, r, l, p, q, metric=metric, scale=scale, mu=mu, phi=phi)
+    ws = APDWorkspace.from_points(2, xs, ys, r, l, p, q, metric=metric, scale=scale, mu=mu, phi=phi,
+                                  matrix_free=matrix_free)
     return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol)
 
 

@@ -22,31 +22,41 @@
 namespace {
 
 // --- APD_SsN_Class1.m:125 / Class2 :119  wk = -wc + bk*(uk+ak*vk)/ak^2 ; partials of H*uk
-struct OpBegin {
+template <class CS>   // CS: CostStored or CostFree<D> (ipd_apd_tiles.h)
+struct OpBeginT {
     static constexpr bool NEED_AX = true;
-    static constexpr int FC = 16;
+    // matrix-free: 8 columns of q and D coordinates are what the scalar registers hold
+    static constexpr int FC = CS::FREE ? 8 : 16;
     Prob P;
     const double* u;
     const double* v;
     double* w;
     double ak, bk, ak2;
+    [[no_unique_address]] CS cs;
     struct Raw {
         double c, u, v, phi;
     };
-    struct RowC {};
+    struct RowC {
+        typename CS::Row x;
+    };
     struct ColC {
         double q;
+        typename CS::Col y;
     };
-    __device__ void row_const(RowC&, int) const {}
-    __device__ void col_const(ColC& c, int j) const { c.q = P.q[j]; }
+    __device__ void row_const(RowC& rc, int i) const { cs.row(rc.x, i); }
+    __device__ void col_const(ColC& c, int j) const {
+        c.q = P.q[j];
+        cs.col(c.y, j);
+    }
     __device__ void fetch(Raw& r, size_t idx) const {
-        r.c = P.c[idx];
+        r.c = CS::FREE ? 0.0 : P.c[idx];
         r.u = u[idx];
         r.v = v[idx];
         r.phi = P.cls2 ? P.phi[idx] : 0.0;
     }
-    __device__ double compute(const Raw& r, const RowC&, const ColC&, size_t idx, double* sc) const {
-        w[idx] = -r.c + bk * (r.u + ak * r.v) / ak2;
+    __device__ double compute(const Raw& r, const RowC& rc, const ColC& cc, size_t idx, double* sc) const {
+        const double c = cs.value(r.c, rc.x, cc.y);
+        w[idx] = -c + bk * (r.u + ak * r.v) / ak2;
         sc[3] += r.phi * r.u;
         return r.u;
     }
@@ -163,10 +173,11 @@ struct OpMerit {
 };
 
 // --- :239-242,253-254  uk1 = prox(zk), vk1, and the KKT residuals of (uk1, lk1)
-template <bool FROM_W>
-struct OpEnd {
+template <bool FROM_W, class CS>
+struct OpEndT {
     static constexpr bool NEED_AX = true;
-    static constexpr int FC = 8;
+    // matrix-free: 4 columns of y1, q and D coordinates (8 spilled up to 73 scalar registers)
+    static constexpr int FC = CS::FREE ? 4 : 8;
     Prob P;
     const double* w;      // FROM_W
     const double* uold;   // FROM_W: current iterate ; else: the iterate to measure
@@ -174,27 +185,32 @@ struct OpEnd {
     double* v;            // FROM_W
     Lam lam;
     double itk, ak;
+    [[no_unique_address]] CS cs;
     struct Raw {
         double w, u, c, phi, g;
     };
     struct RowC {
         double pi, y2;
+        typename CS::Row x;
     };
     struct ColC {
         double y1, q;
+        typename CS::Col y;
     };
     __device__ void row_const(RowC& rc, int i) const {
         rc.pi = P.p[i];
         rc.y2 = lam.at(P.n + i);
+        cs.row(rc.x, i);
     }
     __device__ void col_const(ColC& c, int j) const {
         c.y1 = lam.at(j);
         c.q = P.q[j];
+        cs.col(c.y, j);
     }
     __device__ void fetch(Raw& r, size_t idx) const {
         r.w = FROM_W ? w[idx] : 0.0;
         r.u = uold[idx];
-        r.c = P.c[idx];
+        r.c = CS::FREE ? 0.0 : P.c[idx];
         r.phi = P.cls2 ? P.phi[idx] : 0.0;
         r.g = P.gama ? P.gama[idx] : P.gs;
     }
@@ -209,9 +225,10 @@ struct OpEnd {
             unew[idx] = u1;
             v[idx] = u1 + (u1 - r.u) / ak;
         }
-        const double d = u1 - prox_of(P, u1 - r.c - aty, r.g);       // :242 / Class2 :227
+        const double c = cs.value(r.c, rc.x, cc.y);
+        const double d = u1 - prox_of(P, u1 - c - aty, r.g);       // :242 / Class2 :227
         sc[0] += d * d;
-        sc[1] += r.c * u1;
+        sc[1] += c * u1;
         sc[3] += r.phi * u1;
         return u1;
     }
@@ -525,15 +542,18 @@ void apd_begin(ipd_apd* h, int k) {
     h->ak = st.ak;
     h->bk1 = st.bk1;
     h->tk = st.tk;
-    OpBegin op;
-    op.P = h->P;
-    op.u = h->u;
-    op.v = h->v;
-    op.w = h->w;
-    op.ak = h->ak;
-    op.bk = h->bk;
-    op.ak2 = h->ak * h->ak;
-    launch_tiles(h, op);
+    with_cost_source(h, [&](auto cs) {
+        OpBeginT<decltype(cs)> op;
+        op.P = h->P;
+        op.u = h->u;
+        op.v = h->v;
+        op.w = h->w;
+        op.ak = h->ak;
+        op.bk = h->bk;
+        op.ak2 = h->ak * h->ak;
+        op.cs = cs;
+        launch_tiles(h, op);
+    });
     BeginFin f;
     f.pt = parts_of(h);
     f.P = h->P;
@@ -618,29 +638,33 @@ void apd_merit(ipd_apd* h, const double* lam_base, const double* zeta, const dou
 void apd_end(ipd_apd* h, bool from_w, const double* src_u, const double* lam, double out_kkt[4], double* fx) {
     ProfScope ps(h->ctx, PROF_BEGIN_END);
     const Lam L{lam, nullptr, 0.0};
-    if (from_w) {
-        OpEnd<true> op;
-        op.P = h->P;
-        op.w = h->w;
-        op.uold = h->u;
-        op.unew = h->u2;
-        op.v = h->v;
-        op.lam = L;
-        op.itk = 1.0 / h->tk;
-        op.ak = h->ak;
-        launch_tiles(h, op);
-    } else {
-        OpEnd<false> op;
-        op.P = h->P;
-        op.w = nullptr;
-        op.uold = src_u;
-        op.unew = nullptr;
-        op.v = nullptr;
-        op.lam = L;
-        op.itk = 0.0;
-        op.ak = 1.0;
-        launch_tiles(h, op);
-    }
+    with_cost_source(h, [&](auto cs) {
+        if (from_w) {
+            OpEndT<true, decltype(cs)> op;
+            op.P = h->P;
+            op.w = h->w;
+            op.uold = h->u;
+            op.unew = h->u2;
+            op.v = h->v;
+            op.lam = L;
+            op.itk = 1.0 / h->tk;
+            op.ak = h->ak;
+            op.cs = cs;
+            launch_tiles(h, op);
+        } else {
+            OpEndT<false, decltype(cs)> op;
+            op.P = h->P;
+            op.w = nullptr;
+            op.uold = src_u;
+            op.unew = nullptr;
+            op.v = nullptr;
+            op.lam = L;
+            op.itk = 0.0;
+            op.ak = 1.0;
+            op.cs = cs;
+            launch_tiles(h, op);
+        }
+    });
     EndFin f;
     f.pt = parts_of(h);
     f.P = h->P;

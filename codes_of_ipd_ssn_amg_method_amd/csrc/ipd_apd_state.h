@@ -51,6 +51,11 @@ struct ipd_apd {
     int phi_npart = 0;
     ipd_cost_stats cost_stats{};   // min, max, sum of c: from the build out of points, or on demand (ipd_apd_get_cost)
     bool have_cost_stats = false;  // (c never changes after the create)
+    // matrix-free (ipd_apd_create_points_free): c stays nullptr, the coordinates live in the
+    // arena and cost_src describes them to the passes that read c(i,j)
+    bool cost_free = false;
+    CostSrc cost_src{};
+    int cost_dim = 0, cost_metric = 0, cost_scale = 0;   // of the specification; 0 for a workspace from a host c
     // script variables
     int k = 0;
     double bk = 1.0;
@@ -99,6 +104,20 @@ void launch_tiles(ipd_apd* h, const Op& op) {
     IPD_KERNEL_CHECK();
 }
 
+// f(cs) with the cost source of the workspace, CostStored{} or CostFree<D>{...}: every host function that launches
+// an op reading c picks the op's instantiation through this
+template <class F>
+void with_cost_source(const ipd_apd* h, F&& f) {
+    if (!h->cost_free) return f(CostStored{});
+    switch (h->cost_src.dim) {
+        case 1: return f(CostFree<1>{h->cost_src});
+        case 2: return f(CostFree<2>{h->cost_src});
+        case 3: return f(CostFree<3>{h->cost_src});
+        default: throw IpdError(IPD_E_LIMIT, COST_FREE_TEXT[COST_FREE_DIM]);
+    }
+}
+static_assert(COST_FREE_DIM_MAX == 3, "with_cost_source instantiates D = 1, 2, 3");
+
 }  // namespace
 
 // ---- ipd_driver.hip ------------------------------------------------------------------------
@@ -107,7 +126,12 @@ void launch_tiles(ipd_apd* h, const Op& op) {
 using ApdCostFill = std::function<void(double* c_dev, double* phi_ones_dev, ipd_cost_stats* st)>;
 // The one body of ipd_apd_create and ipd_apd_create_points.  Allocates and uploads everything but c: fill == nullptr
 // uploads d->c (and needs d->phi for class 2), otherwise fill makes c (and the phi the caller left out).
-void apd_create_common(ipd_ctx* ctx, const ipd_apd_data* d, const ApdCostFill* fill, ipd_apd** out);
+// Matrix-free, the third way: nothing mn-sized is allocated for c.  Called last with the workspace under
+// construction; it puts the coordinates into h->arena and sets h->cost_free, cost_src and cost_stats (and fills
+// phi_ones_dev as ApdCostFill does).
+using ApdCostFree = std::function<void(ipd_apd* h, double* phi_ones_dev)>;
+void apd_create_common(ipd_ctx* ctx, const ipd_apd_data* d, const ApdCostFill* fill, ipd_apd** out,
+                       const ApdCostFree* free_fill = nullptr);
 // the script variables after a new state went in: what ipd_apd_set_state does besides the uploads
 // (k, the KKT reference, the records and the AMG counters start over; bk, lk, histories stay)
 void apd_restart_script(ipd_apd* h);

@@ -10,6 +10,7 @@
 #pragma once
 
 #include "ipd_apd_geo.h"
+#include "ipd_cost_plan.h"
 #include "ipd_cycle_dev.h"
 
 // TR, TC, Geo and make_geo: ipd_apd_geo.h
@@ -32,6 +33,50 @@ __device__ __forceinline__ double prox_of(const Prob& P, double x, double g) {
     const double t = x > 0.0 ? x : 0.0;
     return P.cls2 ? t : (t < g ? t : g);
 }
+
+// ---------------------------------------------------------------------------
+// where an op that reads c(i,j) takes it from: a compile-time choice of the op
+// ---------------------------------------------------------------------------
+// the stored matrix (P.c, or PlanCount::c): nothing per row or column, the value is what the op loaded
+struct CostStored {
+    static constexpr bool FREE = false;
+    struct Row {};
+    struct Col {};
+    __device__ __forceinline__ void row(Row&, int) const {}
+    __device__ __forceinline__ void col(Col&, int) const {}
+    __device__ __forceinline__ void col_of_lane(Col&, const Col&, int) const {}
+    __device__ __forceinline__ double value(double stored, const Row&, const Col&) const { return stored; }
+};
+// none stored: the row's D coordinates are registers of the lane, the column's are wave-uniform, and the entry
+// is folded by cost_src_value, the code k_cost_build stores an entry with.  The coordinates are never written
+// while a workspace lives, so the column loads go through the constant address space: a uniform address there
+// is a scalar load even in a kernel that stores elsewhere.
+template <int D>
+struct CostFree {
+    static constexpr bool FREE = true;
+    CostSrc s;
+    struct Row {
+        double x[D];
+    };
+    struct Col {
+        double y[D];
+    };
+    __device__ __forceinline__ void row(Row& r, int i) const { cost_src_row<D>(s, i, r.x); }
+    __device__ __forceinline__ void col(Col& c, int j) const {
+        typedef const double __attribute__((address_space(4))) * ConstPtr;
+        ConstPtr const ys = (ConstPtr)s.ys;
+#pragma unroll
+        for (int k = 0; k < D; ++k) c.y[k] = ys[(size_t)k * s.n + j];
+    }
+    // the coordinates lane `src_lane` fetched with col(), in every lane
+    __device__ __forceinline__ void col_of_lane(Col& c, const Col& mine, int src_lane) const {
+#pragma unroll
+        for (int k = 0; k < D; ++k) c.y[k] = __shfl(mine.y[k], src_lane);
+    }
+    __device__ __forceinline__ double value(double, const Row& r, const Col& c) const {
+        return cost_src_value<D>(s, r.x, c.y);
+    }
+};
 
 // multiplier, optionally a line-search trial point lam + step*zeta (:189,200)
 struct Lam {

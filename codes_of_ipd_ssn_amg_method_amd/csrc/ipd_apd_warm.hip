@@ -12,7 +12,8 @@ namespace {
 // warm start: warmup_class1.m:57-77 / warmup_class2.m:57-85, two passes per iteration
 // ---------------------------------------------------------------------------
 // pass A: dd = etafk*wuk - ak^2*(wc + cAlk + sgk*cAw); partials of H*dd
-struct OpWarmA {
+template <class CS>   // CS: CostStored or CostFree<D> (ipd_apd_tiles.h)
+struct OpWarmAT {
     static constexpr bool NEED_AX = true;
     static constexpr int FC = 4;
     Prob P;
@@ -25,24 +26,29 @@ struct OpWarmA {
     const double* b;
     double* dd;
     WarmScal s;
+    [[no_unique_address]] CS cs;
     struct Raw {
         double x, v, w, pi, l2, c, phi;
     };
     struct RowC {
         double pi, h2, b2;
+        typename CS::Row x;
     };
     struct ColC {
         double bj, hj, q;
+        typename CS::Col y;
     };
     __device__ void row_const(RowC& rc, int i) const {
         rc.pi = P.p[i];
         rc.h2 = hl1[P.n + i];
         rc.b2 = b[P.n + i];
+        cs.row(rc.x, i);
     }
     __device__ void col_const(ColC& c, int j) const {
         c.bj = b[j];
         c.hj = hl1[j];
         c.q = P.q[j];
+        cs.col(c.y, j);
     }
     __device__ void fetch(Raw& r, size_t idx) const {
         r.x = x[idx];
@@ -50,7 +56,7 @@ struct OpWarmA {
         r.w = wk[idx];
         r.pi = pik[idx];
         r.l2 = l2[idx];
-        r.c = P.c[idx];
+        r.c = CS::FREE ? 0.0 : P.c[idx];
         r.phi = P.cls2 ? P.phi[idx] : 0.0;
     }
     __device__ double compute(const Raw& r, const RowC& rc, const ColC& cc, size_t idx,
@@ -68,7 +74,7 @@ struct OpWarmA {
             cAlk = aty + hl2;                                                          // Class1 :66
         }
         const double cAw = -atb - r.w;
-        const double d = s.etafk * wux - s.ak2 * (r.c + cAlk + s.sgk * cAw);          // :67
+        const double d = s.etafk * wux - s.ak2 * (cs.value(r.c, rc.x, cc.y) + cAlk + s.sgk * cAw);          // :67
         dd[idx] = d;
         sc[3] += r.phi * d;
         return d;
@@ -268,18 +274,21 @@ void apd_warmup(ipd_apd* h, double res, long long maxit) {
         hipLaunchKernelGGL(k_warm_hl1, dim3(1), dim3(BT), 0, ctx->stream, L, (const double*)lk1,
                            (const double*)Hx, (const double*)h->b, s.ibk, s.akbk, hl1);
         IPD_KERNEL_CHECK();
-        OpWarmA a;
-        a.P = h->P;
-        a.x = x;
-        a.v = v;
-        a.wk = wk;
-        a.pik = pik;
-        a.l2 = l2;
-        a.hl1 = hl1;
-        a.b = h->b;
-        a.dd = dd;
-        a.s = s;
-        launch_tiles(h, a);
+        with_cost_source(h, [&](auto cs) {
+            OpWarmAT<decltype(cs)> a;
+            a.P = h->P;
+            a.x = x;
+            a.v = v;
+            a.wk = wk;
+            a.pik = pik;
+            a.l2 = l2;
+            a.hl1 = hl1;
+            a.b = h->b;
+            a.dd = dd;
+            a.s = s;
+            a.cs = cs;
+            launch_tiles(h, a);
+        });
         WarmFinA fa;
         fa.pt = parts_of(h);
         fa.P = h->P;

@@ -16,6 +16,10 @@
 //           8*mn bytes, no read-back.
 //   finish  one workgroup adds the partials in workgroup order and a fixed tree (as k_plan_fin): no float
 //           atomics, two calls give the same bits.
+//   free    ipd_apd_create_points_free keeps the coordinates in the workspace and stores no
+//           c: the build kernel runs without a store, for the largest entry (scale) and for the statistics of what
+//           a stored workspace would hold, and ipd_apd_get_cost builds the matrix into scratch memory on demand.
+//           The passes that read c(i,j) recompute it (CostFree<D>, ipd_apd_tiles.h).
 //
 // An entry is folded by cost_fold / cost_finish of ipd_cost_plan.h, the code its CPU test runs.
 #pragma clang fp contract(off)
@@ -299,18 +303,17 @@ void check_spec(const ipd_cost_spec* s) {
     IPD_REQUIRE(ck == COST_OK, ck == COST_SHAPE ? IPD_E_LIMIT : IPD_E_ARG, COST_CHECK_TEXT[ck]);
 }
 
-// A checked specification -> c_dev (mn) and the statistics of what is stored.  The caller holds a CallScope;
-// the stream has been waited for when this returns (the scratch arrays are the next call's).
-void cost_from_points(ipd_ctx* ctx, const ipd_cost_spec* s, double* c_dev, ipd_cost_stats* st) {
+// The coordinates on the device -> c_dev (mn) and the statistics of what is stored; c_dev == nullptr stores
+// nothing and gives the statistics of what would be stored.  `aligned16` is the alignment of the array that is, or
+// would be, stored to: it decides the rows per lane, and with them the order in which the sum is added.  *src (or
+// nullptr) receives the source the matrix-free passes recompute an entry from.  The stream has been waited for
+// when this returns.
+void cost_build_dev(ipd_ctx* ctx, const ipd_cost_spec* s, const double* xs_dev, const double* ys_dev, double* c_dev,
+                    bool aligned16, ipd_cost_stats* st, CostSrc* src) {
     Arena& S = *ctx->scratch;
     const int m = (int)s->m, n = (int)s->n, d = s->dim;
-    double* xs_dev = S.alloc<double>((size_t)m * d);
-    double* ys_dev = S.alloc<double>((size_t)n * d);
-    ctx->upload(xs_dev, s->xs, (size_t)m * d);
-    ctx->upload(ys_dev, s->ys, (size_t)n * d);
     CostArgs a{};
-    a.g = cost_geo(m, n, cost_rows_per_lane(m, d, (reinterpret_cast<uintptr_t>(c_dev) & 15) == 0,
-                                            switch_value("IPD_COST_STORE")));
+    a.g = cost_geo(m, n, cost_rows_per_lane(m, d, aligned16, switch_value("IPD_COST_STORE")));
     a.d = d;
     a.part = S.alloc<double>((size_t)a.g.nib * a.g.njg * CSC);
     ipd_cost_stats* dst = reinterpret_cast<ipd_cost_stats*>(S.alloc<double>(sizeof(ipd_cost_stats) / sizeof(double)));
@@ -323,6 +326,39 @@ void cost_from_points(ipd_ctx* ctx, const ipd_cost_spec* s, double* c_dev, ipd_c
     }
     launch_build(ctx, s->metric, a, xs_dev, ys_dev, c_dev);
     finish_stats(ctx, a, dst, st);
+    if (src) {
+        src->xs = xs_dev;
+        src->ys = ys_dev;
+        src->m = m;
+        src->n = n;
+        src->dim = d;
+        src->metric = s->metric;
+        src->divide = a.divide;
+        src->denom = a.denom;
+    }
+}
+
+// A checked specification -> c_dev (mn) and the statistics of what is stored.  The caller holds a CallScope;
+// the stream has been waited for when this returns (the scratch arrays are the next call's).
+void cost_from_points(ipd_ctx* ctx, const ipd_cost_spec* s, double* c_dev, ipd_cost_stats* st) {
+    Arena& S = *ctx->scratch;
+    const int m = (int)s->m, n = (int)s->n, d = s->dim;
+    double* xs_dev = S.alloc<double>((size_t)m * d);
+    double* ys_dev = S.alloc<double>((size_t)n * d);
+    ctx->upload(xs_dev, s->xs, (size_t)m * d);
+    ctx->upload(ys_dev, s->ys, (size_t)n * d);
+    cost_build_dev(ctx, s, xs_dev, ys_dev, c_dev, (reinterpret_cast<uintptr_t>(c_dev) & 15) == 0, st, nullptr);
+}
+
+void fill_ones(ipd_ctx* ctx, size_t mn, double* phi_ones_dev) {
+    hipLaunchKernelGGL(k_cost_ones, dim3(elems_grid((long long)mn)), dim3(256), 0, ctx->stream, mn, phi_ones_dev);
+    IPD_KERNEL_CHECK();
+}
+
+void note_spec(ipd_apd* h, const ipd_cost_spec* s) {
+    h->cost_dim = s->dim;
+    h->cost_metric = s->metric;
+    h->cost_scale = s->scale;
 }
 
 }  // namespace
@@ -348,14 +384,53 @@ extern "C" int ipd_apd_create_points(ipd_ctx* ctx, const ipd_apd_data* d, const 
         IPD_REQUIRE(s->m == d->m && s->n == d->n, IPD_E_ARG, "ipd_apd_create_points: m, n of the spec and of the data differ");
         const ApdCostFill fill = [&](double* c_dev, double* phi_ones_dev, ipd_cost_stats* st) {
             CallScope scope(ctx);
-            if (phi_ones_dev) {
-                const size_t mn = (size_t)s->m * (size_t)s->n;
-                hipLaunchKernelGGL(k_cost_ones, dim3(elems_grid((long long)mn)), dim3(256), 0, ctx->stream, mn, phi_ones_dev);
-                IPD_KERNEL_CHECK();
-            }
+            if (phi_ones_dev) fill_ones(ctx, (size_t)s->m * (size_t)s->n, phi_ones_dev);
             cost_from_points(ctx, s, c_dev, st);
         };
-        apd_create_common(ctx, d, &fill, out);
+        ipd_apd* h = nullptr;
+        apd_create_common(ctx, d, &fill, &h);
+        note_spec(h, s);
+        *out = h;
+    });
+}
+
+extern "C" int ipd_apd_create_points_free(ipd_ctx* ctx, const ipd_apd_data* d, const ipd_cost_spec* s,
+                                          ipd_apd** out) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(ctx && d && s && out, IPD_E_ARG, "ipd_apd_create_points_free: NULL argument");
+        IPD_REQUIRE(!d->c, IPD_E_ARG, "ipd_apd_create_points_free: c must be NULL (the cost comes from the points)");
+        check_spec(s);
+        IPD_REQUIRE(cost_free_check(s->dim) == COST_FREE_OK, IPD_E_LIMIT, COST_FREE_TEXT[COST_FREE_DIM]);
+        IPD_REQUIRE(s->m == d->m && s->n == d->n, IPD_E_ARG,
+                    "ipd_apd_create_points_free: m, n of the spec and of the data differ");
+        const ApdCostFree free_fill = [&](ipd_apd* h, double* phi_ones_dev) {
+            CallScope scope(ctx);
+            const size_t m = (size_t)s->m, n = (size_t)s->n, dim = (size_t)s->dim;
+            if (phi_ones_dev) fill_ones(ctx, m * n, phi_ones_dev);
+            // the coordinates are the workspace's own: its passes read them for as long as it lives
+            double* xs_dev = h->arena->alloc<double>(m * dim);
+            double* ys_dev = h->arena->alloc<double>(n * dim);
+            ctx->upload(xs_dev, s->xs, m * dim);
+            ctx->upload(ys_dev, s->ys, n * dim);
+            // the statistics of what a stored workspace would hold, in its geometry: the workspace's c comes out
+            // of the arena, 16-byte aligned
+            cost_build_dev(ctx, s, xs_dev, ys_dev, nullptr, true, &h->cost_stats, &h->cost_src);
+            h->cost_free = true;
+            note_spec(h, s);
+        };
+        apd_create_common(ctx, d, nullptr, out, &free_fill);
+    });
+}
+
+extern "C" int ipd_apd_cost_info(ipd_apd* h, ipd_cost_info* info) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && info, IPD_E_ARG, "ipd_apd_cost_info: NULL argument");
+        info->form = h->cost_free ? 1 : 0;
+        info->dim = h->cost_dim;
+        info->metric = h->cost_metric;
+        info->scale = h->cost_scale;
+        info->device_bytes = h->cost_free ? (int64_t)(8 * ((size_t)h->m + (size_t)h->n) * (size_t)h->cost_dim)
+                                          : (int64_t)(8 * h->mn);
     });
 }
 
@@ -364,7 +439,22 @@ extern "C" int ipd_apd_get_cost(ipd_apd* h, double* c, ipd_cost_stats* st) {
         IPD_REQUIRE(h, IPD_E_ARG, "ipd_apd_get_cost: NULL handle");
         ipd_ctx* ctx = h->ctx;
         CallScope scope(ctx);
-        if (c) ctx->fetch(h->c, c, h->mn);
+        if (c && h->cost_free) {
+            // matrix-free: the matrix exists for this call only, in the scratch arena (given back with the scope)
+            double* c_dev = ctx->scratch->alloc<double>(h->mn);
+            const CostSrc& src = h->cost_src;
+            CostArgs a{};
+            a.g = cost_geo(h->m, h->n, cost_rows_per_lane(h->m, src.dim, (reinterpret_cast<uintptr_t>(c_dev) & 15) == 0,
+                                                          switch_value("IPD_COST_STORE")));
+            a.d = src.dim;
+            a.denom = src.denom;
+            a.divide = src.divide;
+            a.part = ctx->scratch->alloc<double>((size_t)a.g.nib * a.g.njg * CSC);
+            launch_build(ctx, src.metric, a, src.xs, src.ys, c_dev);
+            ctx->fetch(c_dev, c, h->mn);
+        } else if (c) {
+            ctx->fetch(h->c, c, h->mn);
+        }
         if (!st) return;
         if (!h->have_cost_stats) {
             Arena& S = *ctx->scratch;

@@ -86,6 +86,86 @@ static inline double cost_entry(int metric, int d, const double* xi, const doubl
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Matrix-free cost: a workspace that keeps the (m+n)*d coordinates and no c.  The passes
+// that read c(i,j) recompute it from a CostSrc: the row's coordinates sit in registers, the column's are
+// wave-uniform, and cost_src_value folds them exactly as k_cost_build folds what it stores -- cost_fold in
+// ascending k, cost_finish, then the one IEEE division of scale = 1 -- so a recomputed entry has the stored
+// entry's bits.  The metric is a wave-uniform switch around cost_fold<METRIC>; D is a template parameter, no
+// register array is indexed by a run-time k.
+// ---------------------------------------------------------------------------------------------------------------
+#if defined(__clang__)
+#define COST_UNROLL _Pragma("unroll")   // D <= 3 iterations: every index below is a constant after unrolling
+#else
+#define COST_UNROLL
+#endif
+
+struct CostSrc {
+    const double* xs;   // m*dim, xs[i + k*m]
+    const double* ys;   // n*dim, ys[j + k*n]
+    int m, n;
+    int dim, metric;
+    int divide;         // != 0: every entry is divided by denom
+    double denom;
+};
+
+enum CostFreeCheck { COST_FREE_OK, COST_FREE_DIM };
+static constexpr const char* COST_FREE_TEXT[] = {
+    "",
+    "matrix-free cost: dim must be in [1, 3] (the row coordinates are registers); larger dim needs a stored cost",
+};
+static constexpr int COST_FREE_DIM_MAX = 3;
+static inline CostFreeCheck cost_free_check(int dim) {
+    return dim >= 1 && dim <= COST_FREE_DIM_MAX ? COST_FREE_OK : COST_FREE_DIM;
+}
+
+template <int METRIC, int D>
+IPD_HD_INLINE double cost_src_fold_of(const double (&x)[D], const double (&y)[D]) {
+    double acc = 0.0;
+    COST_UNROLL
+    for (int k = 0; k < D; ++k) acc = cost_fold<METRIC>(acc, x[k], y[k]);
+    return cost_finish<METRIC>(acc);
+}
+// x, y: the D coordinates of row i and column j
+template <int D>
+IPD_HD_INLINE double cost_src_value(const CostSrc& s, const double (&x)[D], const double (&y)[D]) {
+    double v;
+    switch (s.metric) {
+        case COST_SQEUCLIDEAN: v = cost_src_fold_of<COST_SQEUCLIDEAN, D>(x, y); break;
+        case COST_EUCLIDEAN: v = cost_src_fold_of<COST_EUCLIDEAN, D>(x, y); break;
+        case COST_CITYBLOCK: v = cost_src_fold_of<COST_CITYBLOCK, D>(x, y); break;
+        default: v = cost_src_fold_of<COST_CHEBYSHEV, D>(x, y); break;
+    }
+    if (s.divide) v = v / s.denom;   // as k_cost_build: one IEEE division, after the metric's last operation
+    return v;
+}
+template <int D>
+IPD_HD_INLINE void cost_src_row(const CostSrc& s, int i, double (&x)[D]) {
+    COST_UNROLL
+    for (int k = 0; k < D; ++k) x[k] = s.xs[(size_t)k * s.m + i];
+}
+template <int D>
+IPD_HD_INLINE void cost_src_col(const CostSrc& s, int j, double (&y)[D]) {
+    COST_UNROLL
+    for (int k = 0; k < D; ++k) y[k] = s.ys[(size_t)k * s.n + j];
+}
+template <int D>
+IPD_HD_INLINE double cost_src_entry_of(const CostSrc& s, int i, int j) {
+    double x[D], y[D];
+    cost_src_row<D>(s, i, x);
+    cost_src_col<D>(s, j, y);
+    return cost_src_value<D>(s, x, y);
+}
+// entry (i, j) of a source that passed cost_free_check
+IPD_HD_INLINE double cost_src_entry(const CostSrc& s, int i, int j) {
+    switch (s.dim) {
+        case 1: return cost_src_entry_of<1>(s, i, j);
+        case 2: return cost_src_entry_of<2>(s, i, j);
+        default: return cost_src_entry_of<3>(s, i, j);
+    }
+}
+static_assert(COST_FREE_DIM_MAX == 3, "cost_src_entry instantiates D = 1, 2, 3");
+
+// ---------------------------------------------------------------------------------------------------------------
 // Launch geometry: the walk of the plan kernels (ipd_plan.hip).  c(i,j) = c[i + j*m]; lanes along i; a wave owns
 // 64*rpl consecutive rows (lane l: rows rpl*l .. rpl*l + rpl - 1 of them, one 8-byte or one 16-byte store per
 // column) and walks COST_TC*reps columns alone; a workgroup is 4 waves, the grid nib x njg.
@@ -93,6 +173,7 @@ static inline double cost_entry(int metric, int d, const double* xi, const doubl
 static constexpr int COST_TC = 16;      // columns a wave has in flight
 static constexpr int COST_WAVES = 4;    // waves of a workgroup
 static constexpr int COST_DT_MAX = 3;   // dimensions up to which the row coordinates are template registers
+static_assert(COST_FREE_DIM_MAX == COST_DT_MAX, "matrix-free keeps the row coordinates where k_cost_build<D> does");
 
 struct CostGeo {
     int m, n, rpl;          // rpl: rows per lane, 1 or 2

@@ -311,15 +311,17 @@ extern "C" void ipd_apd_opts_init(int32_t cls, ipd_apd_opts* o) {
     o->pcg_maxit = 10000;
 }
 
-// The one body of ipd_apd_create and ipd_apd_create_points (ipd_cost.hip): fill == nullptr takes c (and phi) from
-// the host arrays of *d, otherwise fill makes them on the device.
-void apd_create_common(ipd_ctx* ctx, const ipd_apd_data* d, const ApdCostFill* fill, ipd_apd** out) {
+// The one body of ipd_apd_create, ipd_apd_create_points and ipd_apd_create_points_free (ipd_cost.hip): without
+// fill and free_fill c (and phi) come from the host arrays of *d, fill makes them on the device, and free_fill
+// keeps the coordinates in place of c.
+void apd_create_common(ipd_ctx* ctx, const ipd_apd_data* d, const ApdCostFill* fill, ipd_apd** out,
+                       const ApdCostFree* free_fill) {
     IPD_REQUIRE(ctx && d && out, IPD_E_ARG, "NULL argument");
     IPD_REQUIRE(d->cls == 1 || d->cls == 2, IPD_E_ARG, "cls must be 1 or 2");
     IPD_REQUIRE(d->m > 0 && d->n > 0 && d->m <= IPD_APD_SIDE_MAX && d->n <= IPD_APD_SIDE_MAX, IPD_E_LIMIT,
                 "m, n must be in [1, 16384]");
-    IPD_REQUIRE((fill || d->c) && d->r && d->l && d->p && d->q, IPD_E_ARG, "NULL problem vector");
-    IPD_REQUIRE(d->cls == 1 || d->phi || fill, IPD_E_ARG, "class 2 needs phi");
+    IPD_REQUIRE((fill || free_fill || d->c) && d->r && d->l && d->p && d->q, IPD_E_ARG, "NULL problem vector");
+    IPD_REQUIRE(d->cls == 1 || d->phi || fill || free_fill, IPD_E_ARG, "class 2 needs phi");
     ctx->set_device();
     std::unique_ptr<ipd_apd> h(new ipd_apd);
     h->ctx = ctx;
@@ -339,11 +341,11 @@ void apd_create_common(ipd_ctx* ctx, const ipd_apd_data* d, const ApdCostFill* f
     h->geo = make_geo(m, n, forced_reps);
     const size_t mn = h->mn, U = h->U;
     const int L = h->L;
-    h->c = A.alloc<double>(mn);
+    if (!free_fill) h->c = A.alloc<double>(mn);   // matrix-free: c stays nullptr
     h->p = A.alloc<double>((size_t)m);
     h->q = A.alloc<double>((size_t)n);
     h->b = A.alloc<double>((size_t)L);
-    if (!fill) ctx->upload(h->c, d->c, mn);
+    if (!fill && !free_fill) ctx->upload(h->c, d->c, mn);
     ctx->upload(h->p, d->p, (size_t)m);
     ctx->upload(h->q, d->q, (size_t)n);
     ctx->upload(h->b, d->r, (size_t)n);            // b = [r;l(;mu)]  (:33 / Class2 :29)
@@ -404,6 +406,9 @@ void apd_create_common(ipd_ctx* ctx, const ipd_apd_data* d, const ApdCostFill* f
     P.gs = d->cls == 2 ? std::numeric_limits<double>::infinity() : d->gama_scalar;
     if (fill) {
         (*fill)(h->c, d->cls == 2 && !d->phi ? h->phi : nullptr, &h->cost_stats);
+        h->have_cost_stats = true;
+    } else if (free_fill) {
+        (*free_fill)(h.get(), d->cls == 2 && !d->phi ? h->phi : nullptr);
         h->have_cost_stats = true;
     }
     if (d->cls == 2) {

@@ -75,10 +75,11 @@ __device__ __forceinline__ double wave_max(double v) {
 // ---------------------------------------------------------------------------
 // count pass
 // ---------------------------------------------------------------------------
-struct PlanCount {
+template <class CS>   // CS: CostStored or CostFree<D> (ipd_apd_tiles.h)
+struct PlanCountT {
     PlanGeo g;
     const double* x;
-    const double* c;
+    const double* c;   // CostStored
     const double* p;
     const double* q;
     double tol;
@@ -86,10 +87,11 @@ struct PlanCount {
     double* spart;   // [workgroup][PSC]
     double* lpart;   // AX: [jg][m]      partial sums of X*q
     double* rpart;   // AX: [segment slot][n]  partial sums of X'*p (slots of absent segments hold zeros)
+    [[no_unique_address]] CS cs;
 };
 
-template <bool AX>
-__global__ __launch_bounds__(256) void k_plan_count(const PlanCount a) {
+template <bool AX, class CS>
+__global__ __launch_bounds__(256) void k_plan_count(const PlanCountT<CS> a) {
     __shared__ double red[4 * PSC];
     const PlanGeo& g = a.g;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
@@ -99,6 +101,8 @@ __global__ __launch_bounds__(256) void k_plan_count(const PlanCount a) {
     const int ic = in_i ? i : g.m - 1;
     const int seg = ib * 4 + wv;
     const double pi = (AX && in_i) ? a.p[i] : 0.0;
+    typename CS::Row crow;
+    a.cs.row(crow, ic);
     double skept = 0.0, sdrop = 0.0, mdrop = 0.0, fkept = 0.0, lacc = 0.0;
     for (int rep = 0; rep < g.reps; ++rep) {
         const int j0 = (jg * g.reps + rep) * TC;
@@ -109,10 +113,13 @@ __global__ __launch_bounds__(256) void k_plan_count(const PlanCount a) {
             const int j = min(j0 + jj, g.n - 1);   // clamped: the loads need no branch
             const size_t idx = (size_t)j * g.m + ic;
             xr[jj] = a.x[idx];
-            cr[jj] = a.c[idx];
+            cr[jj] = CS::FREE ? 0.0 : a.c[idx];
         }
         // lane jj fetches q of column j0 + jj (16 uniform loads held 32 scalar registers too many)
         const double ql = (AX && lane < TC) ? a.q[min(j0 + lane, g.n - 1)] : 0.0;
+        // matrix-free: and the coordinates of column j0 + (lane mod 16), for the same reason
+        typename CS::Col clane;
+        a.cs.col(clane, min(j0 + (lane & (TC - 1)), g.n - 1));
         int mycnt = 0;
         double xv[TC];
 #pragma unroll
@@ -124,10 +131,12 @@ __global__ __launch_bounds__(256) void k_plan_count(const PlanCount a) {
             const unsigned long long bal = __ballot(keep);
             if (lane == jj) mycnt = __popcll(bal);
             const double qj = AX ? __shfl(ql, jj) : 0.0;
+            typename CS::Col ccol;
+            a.cs.col_of_lane(ccol, clane, jj);
             double xk = 0.0;
             if (keep) {
                 skept += x;
-                fkept += cr[jj] * x;
+                fkept += a.cs.value(cr[jj], crow, ccol) * x;
                 if (AX) lacc += x * qj;
                 xk = x;
             } else if (valid) {
@@ -379,23 +388,30 @@ void plan_count_phase(ipd_apd* h, double tol, int64_t* jc_dev, double* ax_dev, P
     int* jc32 = S.alloc<int>((size_t)g.n + 1);
     double* spart = S.alloc<double>((size_t)nblk * PSC);
     PlanScal* dscal = reinterpret_cast<PlanScal*>(S.alloc<double>(sizeof(PlanScal) / sizeof(double)));
-    PlanCount a;
-    a.g = g;
-    a.x = h->u;
-    a.c = h->c;
-    a.p = h->p;
-    a.q = h->q;
-    a.tol = tol;
-    a.cnt = cnt;
-    a.spart = spart;
-    a.lpart = a.rpart = nullptr;
+    double* lpart = nullptr;
+    double* rpart = nullptr;
     if (ax_dev) {
-        a.lpart = S.alloc<double>((size_t)g.njg * g.m);
-        a.rpart = S.alloc<double>((size_t)g.nib * 4 * g.n);
-        hipLaunchKernelGGL(k_plan_count<true>, dim3(g.nib, g.njg), dim3(256), 0, ctx->stream, a);
-    } else {
-        hipLaunchKernelGGL(k_plan_count<false>, dim3(g.nib, g.njg), dim3(256), 0, ctx->stream, a);
+        lpart = S.alloc<double>((size_t)g.njg * g.m);
+        rpart = S.alloc<double>((size_t)g.nib * 4 * g.n);
     }
+    with_cost_source(h, [&](auto cs) {
+        PlanCountT<decltype(cs)> a;
+        a.g = g;
+        a.x = h->u;
+        a.c = h->c;
+        a.p = h->p;
+        a.q = h->q;
+        a.tol = tol;
+        a.cnt = cnt;
+        a.spart = spart;
+        a.lpart = lpart;
+        a.rpart = rpart;
+        a.cs = cs;
+        if (ax_dev)
+            hipLaunchKernelGGL((k_plan_count<true, decltype(cs)>), dim3(g.nib, g.njg), dim3(256), 0, ctx->stream, a);
+        else
+            hipLaunchKernelGGL((k_plan_count<false, decltype(cs)>), dim3(g.nib, g.njg), dim3(256), 0, ctx->stream, a);
+    });
     IPD_KERNEL_CHECK();
     hipLaunchKernelGGL(k_plan_colscan, dim3(cdiv(g.n, 4)), dim3(256), 0, ctx->stream, g.n, g.nseg, cnt, colcnt);
     IPD_KERNEL_CHECK();
@@ -404,8 +420,8 @@ void plan_count_phase(ipd_apd* h, double tol, int64_t* jc_dev, double* ax_dev, P
     f.g = g;
     f.nblk = nblk;
     f.spart = spart;
-    f.lpart = a.lpart;
-    f.rpart = a.rpart;
+    f.lpart = lpart;
+    f.rpart = rpart;
     f.jc32 = jc32;
     f.jc = jc_dev;
     f.ax = ax_dev;

@@ -555,6 +555,22 @@ int ipd_apd_create_points(ipd_ctx*, const ipd_apd_data* d, const ipd_cost_spec* 
  * from a host c computes them at the first call.                                                   */
 int ipd_apd_get_cost(ipd_apd* h, double* c, ipd_cost_stats* st);
 
+/* Matrix-free cost: ipd_apd_create_points without the mn doubles of c.  The workspace
+ * keeps the (m+n)*d coordinates, and every pass that reads c(i,j) recomputes it with the operations
+ * that would have stored it, so each result has the bits of the stored workspace's.  Everything as
+ * ipd_apd_create_points, and IPD_E_LIMIT for dim > 3 (the row's coordinates are registers; nothing is
+ * stored instead).  ipd_apd_get_cost on such a workspace builds the matrix into scratch memory for
+ * the call when c is given; its statistics are those of the stored workspace.                      */
+int ipd_apd_create_points_free(ipd_ctx*, const ipd_apd_data* d, const ipd_cost_spec* s, ipd_apd** out);
+typedef struct ipd_cost_info {
+    int32_t form;          /* 0 stored, 1 matrix-free                                             */
+    int32_t dim;           /* of the specification; 0 for a workspace from a host matrix          */
+    int32_t metric;        /* likewise                                                            */
+    int32_t scale;         /* likewise                                                            */
+    int64_t device_bytes;  /* kept for the cost: 8*mn stored, 8*(m+n)*dim matrix-free             */
+} ipd_cost_info;
+int ipd_apd_cost_info(ipd_apd* h, ipd_cost_info* info);
+
 /* Matrix-free level-1 operator.  If level 1 of `h` is exactly Hybrid_AMG's
  * rescaled operator Ae = bk1*Q0^2 + (Q0*T*Q0 + Q0*H0*Q0)/tk for these p, q, tk (checked entry by
  * entry against A_1's CSR values), the level-1 Gauss-Seidel sweeps read one BIT per entry (the

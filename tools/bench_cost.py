@@ -15,6 +15,16 @@ synchronise, the variants alternating `--reps` times.  Per size:
       coordinates, reduces the statistics and reads them back).  COPY_TBPS is the guide's measured rate of a
       float4 copy on MI355X -- a read plus a write, named here for orientation; it is not a write ceiling.
 The condition of DESIGN.md section 4g: in every repetition (b) is faster than from_matrix alone.
+
+  python tools/bench_cost.py --passes [--sizes ...] [--reps 2] [--out FILE]
+DESIGN.md section 4i: a stored and a matrix-free workspace from the same points, in one process, the two forms
+alternating `--reps` times after a warm-up of both.  Per form and repetition: the create, `begin`, `end(from_w=True)`
+(200 calls each, the mean), one warm-start iteration (warmup(0, 105) minus warmup(0, 5), over 100) and
+`plan(tol, stats=True)` of the iterate the warm start leaves (20 calls; that iterate is dense, so tol is its 99th
+percentile of |x|: one entry in a hundred is kept and crosses to the host, in both forms alike).  Host clock around
+calls that end in a device synchronise, so a call carries its launch and read-back overhead in both forms alike.
+Per pass the line gives min(stored) / min(free) and the spread between the stored form's own repetitions, the
+margin a difference has to clear.
 """
 import argparse
 import ctypes
@@ -112,11 +122,57 @@ def bench_size(N, reps, emit):
     buf.free()
 
 
+def bench_passes(N, reps, emit):
+    rs = np.random.RandomState(1)
+    xs, ys = rs.standard_normal((N, 2)), rs.standard_normal((N, 2))
+    r, l = rs.random_sample(N), rs.random_sample(N)
+    l = l * r.sum() / l.sum()
+    one = np.ones(N)
+    K0, K1, CALLS, PLAN_CALLS = 5, 105, 200, 20
+    for scale in (False, True):
+        def one_form(free):
+            t = {}
+            t["create"], ws = clock(lambda: ipd.APDWorkspace.from_points(1, xs, ys, r, l, one, one, metric="sqeuclidean",
+                                                                         scale=scale, matrix_free=free))
+            t_k0 = clock(lambda: ws.warmup(0.0, K0))[0]
+            t_k1 = clock(lambda: ws.warmup(0.0, K1))[0]
+            t["warm_iteration"] = (t_k1 - t_k0) / (K1 - K0)
+            u, _, lam, _ = ws.state()
+            tol = float(np.partition(np.abs(u), int(0.99 * u.size))[int(0.99 * u.size)])
+            del u
+            t["plan"], (X, st, ax) = clock(lambda: ws.plan(tol, stats=True), PLAN_CALLS)
+            t["begin"] = clock(lambda: ws.begin(1), CALLS)[0]
+            t["end_from_w"] = clock(lambda: ws.end(lam, from_w=True), CALLS)[0]
+            info = ws.cost_info()
+            ws.close()
+            return t, info, (int(st["nnz"]), st["fval_kept"])
+        forms = [("stored", False), ("free", True)]
+        for _, free in forms:                # both forms once before the clock counts
+            one_form(free)
+        times = {name: [] for name, _ in forms}
+        infos, plans = {}, {}
+        for _ in range(reps):
+            for name, free in forms:
+                t, infos[name], plans[name] = one_form(free)
+                times[name].append(t)
+        passes = {}
+        for key in ("create", "begin", "end_from_w", "warm_iteration", "plan"):
+            st_, fr_ = [t[key] for t in times["stored"]], [t[key] for t in times["free"]]
+            passes[key] = dict(stored=[round(v, 7) for v in st_], free=[round(v, 7) for v in fr_],
+                               stored_over_free=min(st_) / min(fr_),
+                               stored_spread=(max(st_) - min(st_)) / min(st_))
+        emit(dict(bench="cost_free_passes", N=N, d=2, metric="sqeuclidean", scale=scale, reps=reps,
+                  calls=dict(begin=CALLS, end_from_w=CALLS, plan=PLAN_CALLS, warm_iterations=K1 - K0),
+                  seconds=passes, device_bytes={k: v["device_bytes"] for k, v in infos.items()},
+                  plan_nnz=plans["stored"][0], same_plan_statistics=bool(plans["stored"] == plans["free"])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1024,4096,8192")
     ap.add_argument("--reps", type=int, default=2, help="alternating repetitions of the variants")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
+    ap.add_argument("--passes", action="store_true", help="stored against matrix-free workspaces, pass by pass")
     a = ap.parse_args()
 
     def emit(rec):
@@ -127,7 +183,7 @@ def main():
                 f.write(line + "\n")
 
     for N in [int(s) for s in a.sizes.split(",") if s]:
-        bench_size(N, a.reps, emit)
+        (bench_passes if a.passes else bench_size)(N, a.reps, emit)
 
 
 if __name__ == "__main__":

@@ -2,8 +2,11 @@
 """Compares the gfx950 kernels of two builds (no GPU needed): for every kernel symbol the sequence of instruction
 encodings of a plain llvm-objdump -d, and the register / scratch / LDS figures of tools/kernel_regs.py.  Addresses
 and file offsets are not compared, so a kernel may sit in another object, or at another place in it.
-  python tools/kernel_isa_diff.py --a FILE [FILE ...] --b FILE [FILE ...] [--out REPORT]
-FILE: object files or libipdamg.so.  Exit status 1 when a kernel is missing on one side or differs."""
+  python tools/kernel_isa_diff.py --a FILE [FILE ...] --b FILE [FILE ...] [--out REPORT] [--rename-b OLD=NEW ...]
+FILE: object files or libipdamg.so.  Exit status 1 when a kernel is missing on one side or differs.
+--rename-b: a kernel of b whose demangled name contains OLD is paired with the kernel of a that has NEW there (a type
+that became a template instantiation changes the mangled name and nothing else); kernels of b that stay unpaired
+after the renames are listed as ONLY IN b and counted apart with --allow-new."""
 import argparse
 import os
 import re
@@ -73,21 +76,42 @@ def main():
     ap.add_argument("--a", nargs="+", required=True)
     ap.add_argument("--b", nargs="+", required=True)
     ap.add_argument("--out")
+    ap.add_argument("--rename-b", nargs="*", default=[], metavar="OLD=NEW")
+    ap.add_argument("--allow-new", action="store_true", help="kernels only in b are listed but are no failure")
     args = ap.parse_args()
     ka, kb = kernel_symbols(args.a), kernel_symbols(args.b)
     ca, cb = kernel_code(args.a, ka), kernel_code(args.b, kb)
     ra, rb = figures(args.a), figures(args.b)
     names = demangle(sorted(ka | kb))
-    lines, bad = [], 0
+    # kernels are paired by demangled name, b's after the renames; everything below is keyed by a's name
+    renames = [r.split("=", 1) for r in args.rename_b]
+
+    def renamed(dem):
+        for old, new in renames:
+            dem = dem.replace(old, new)
+        return dem
+
+    short = lambda dem: dem.replace("(anonymous namespace)", "{anonymous}").split("(")[0]
+    key_b = {renamed(names[s]): s for s in kb}
+    key_a = {names[s]: s for s in ka}
+    rb = {short(renamed(names[s])): rb.get(short(names[s])) for s in kb}
+    ca = {names[s]: c for s, c in ca.items()}
+    cb = {renamed(names[s]): c for s, c in cb.items()}
+    ka, kb = set(key_a), set(key_b)
+    names = {k: k for k in ka | kb}
+    lines, bad, new = [], 0, 0
     for sym in sorted(ka | kb, key=lambda s: names[s]):
-        dem = names[sym].replace("(anonymous namespace)", "{anonymous}").split("(")[0]
+        dem = short(names[sym])
         if sym in ka and sym in kb and (sym not in ca or sym not in cb):
             lines.append("%-72s NO CODE FOUND IN %s" % (dem[-72:], "a" if sym not in ca else "b"))
             bad += 1
             continue
         if sym not in ka or sym not in kb:
             lines.append("%-72s ONLY IN %s" % (dem[-72:], "a" if sym in ka else "b"))
-            bad += 1
+            if sym in kb and args.allow_new:
+                new += 1
+            else:
+                bad += 1
             continue
         na, nb = [len(b) for b in ca[sym]], [len(b) for b in cb[sym]]
         if ca[sym] == cb[sym] and min(na) > 0 and ra.get(dem) == rb.get(dem):
@@ -99,7 +123,9 @@ def main():
             lines.append("    a: %s" % "; ".join(ra.get(dem, [])))
             lines.append("    b: %s" % "; ".join(rb.get(dem, [])))
     head = ["a: " + " ".join(args.a), "b: " + " ".join(args.b),
-            "%d kernels in a, %d in b, %d in both; %d missing or different" % (len(ka), len(kb), len(ka & kb), bad), ""]
+            "renames of b: " + (" ".join(args.rename_b) or "none"),
+            "%d kernels in a, %d in b, %d in both; %d missing or different; %d only in b and allowed" %
+            (len(ka), len(kb), len(ka & kb), bad, new), ""]
     text = "\n".join(head + lines) + "\n"
     if args.out:
         open(args.out, "w").write(text)
