@@ -136,6 +136,8 @@ lib.ipd_amg_pcg_multi_dev.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_vo
 lib.ipd_apd_plan.argtypes = [c_void_p, c_double, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_plan_dev.argtypes = [c_void_p, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_set_plan.argtypes = [c_void_p, c_void_p]
+lib.ipd_apd_plan_apply.argtypes = [c_void_p, c_double, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_plan_apply_dev.argtypes = lib.ipd_apd_plan_apply.argtypes
 lib.ipd_cost_points_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_create_points.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_get_cost.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -172,6 +174,7 @@ EXPORTS = [
     "ipd_aug_pcg", "ipd_pcg4pot", "ipd_spd_solve", "ipd_amg_resident_levels", "ipd_amg_resident_kernel", "ipd_amg_level_forms", "ipd_amg_poly_operator",
     "ipd_amg_packed_operator",
     "ipd_apd_plan", "ipd_apd_plan_dev", "ipd_apd_set_plan",
+    "ipd_apd_plan_apply", "ipd_apd_plan_apply_dev",
     "ipd_cost_points_dev", "ipd_apd_create_points", "ipd_apd_get_cost",
     "ipd_apd_create_points_free", "ipd_apd_cost_info",
     "ipd_apd_get_w", "ipd_apd_eval_trial", "ipd_apd_merit", "ipd_apd_end",

@@ -911,6 +911,75 @@ class APDWorkspace:
         A = L.CscIn(X)
         check(lib.ipd_apd_set_plan(self.handle, A.ref()))
 
+    # -- the plan applied on the device ----------------------------------------
+    def _apply_dims(self, side):
+        if side not in (0, 1):
+            raise ValueError("side must be 0 (X @ B) or 1 (X.T @ B)")
+        return (self.n, self.m) if side == 0 else (self.m, self.n)
+
+    def apply_plan(self, B, side: int = 0, tol: float = 0.0, normalize: bool = False, mass: bool = False):
+        """``Y = X @ B`` (``side=0``, ``B`` (n, k) or 1-D) or ``Y = X.T @ B`` (``side=1``, ``B`` (m, k))
+        with ``X = plan(tol)``, computed where the iterate lives (``ipd_apd_plan_apply``): one streaming
+        read of ``x`` per four columns of ``B``, k <= 16, and only ``B``, ``Y`` and the mass cross to the
+        host.  ``Y`` has shape (m or n, k).  ``mass=True`` -> ``(Y, w)`` with ``w = X @ 1`` (``X.T @ 1``),
+        the plain mass of the kept entries.  ``normalize=True`` divides row r of ``Y`` by ``w[r]``; a row
+        without kept mass is ``0/0 = nan``.  A dropped entry contributes ``+0.0`` whatever ``B`` holds there.
+        On a plan that is already sparse on the host (a converged run, about m+n entries), and when
+        ``plan()`` is needed anyway, ``plan(tol) @ B`` is the better route: both take about the time of one
+        read of ``x`` and the product itself is trivial (DESIGN.md section 4j has the measured rows)."""
+        rin, rout = self._apply_dims(side)
+        B_ = np.asarray(B, dtype=np.float64)
+        if B_.ndim == 1:
+            B_ = B_.reshape(-1, 1)
+        if B_.ndim != 2 or B_.shape[0] != rin:
+            raise ValueError(f"B must have {rin} rows")
+        k = B_.shape[1]
+        Bf = np.asfortranarray(B_)
+        Y = np.empty((rout, k), order="F")
+        w = np.empty(rout) if mass else None
+        check(lib.ipd_apd_plan_apply(self.handle, c_double(float(tol)), c_int32(side), c_int32(k),
+                                     c_int32(1 if normalize else 0), Bf.ctypes.data, Y.ctypes.data,
+                                     w.ctypes.data if mass else None))
+        return (Y, w) if mass else Y
+
+    def apply_plan_dev(self, B, Y, w=None, side: int = 0, tol: float = 0.0, normalize: bool = False) -> None:
+        """The same on caller-owned device arrays (``ipd_apd_plan_apply_dev``), column-major float64:
+        ``B`` (n or m) x k, ``Y`` (m or n) x k, ``w`` m or n entries or None -- torch tensors on the
+        workspace's GPU (contiguous, so a (rows, k) matrix is passed as its transpose's storage),
+        ``DeviceBuffer`` objects, or ``(pointer, entries)`` pairs.  k is taken from the entries of ``B``."""
+        rin, rout = self._apply_dims(side)
+
+        def ptr_count(a, name):
+            if isinstance(a, tuple):
+                return c_void_p(int(a[0])), int(a[1])
+            if isinstance(a, L.DeviceBuffer):
+                return a.ptr, a.nbytes // 8
+            if hasattr(a, "data_ptr"):
+                if a.element_size() != 8 or not a.is_contiguous():
+                    raise ValueError("apply_plan_dev: tensors must be contiguous float64")
+                return c_void_p(a.data_ptr()), a.numel()
+            raise ValueError(f"apply_plan_dev: {name} must be a tensor, a DeviceBuffer or a (pointer, entries) pair")
+        B_p, B_cnt = ptr_count(B, "B")
+        Y_p, Y_cnt = ptr_count(Y, "Y")
+        k, rest = divmod(B_cnt, rin)
+        if rest or k < 1:
+            raise ValueError(f"apply_plan_dev: B must hold k columns of {rin} entries")
+        if Y_cnt < rout * k:
+            raise ValueError(f"apply_plan_dev: Y must hold {k} columns of {rout} entries")
+        w_p = None
+        if w is not None:
+            w_p, w_cnt = ptr_count(w, "w")
+            if w_cnt < rout:
+                raise ValueError(f"apply_plan_dev: w must hold {rout} entries")
+        check(lib.ipd_apd_plan_apply_dev(self.handle, c_double(float(tol)), c_int32(side), c_int32(k),
+                                         c_int32(1 if normalize else 0), B_p, Y_p, w_p))
+
+    def barycentric_map(self, points, side: int = 0, tol: float = 0.0):
+        """The barycentric projection of the plan, ``apply_plan(points, side, tol, normalize=True)``:
+        ``side=0`` with ``points = ys`` (n, d) is where each source point is sent,
+        ``T(x_i) = sum_j x_ij y_j / sum_j x_ij``; ``side=1`` with ``points = xs`` (m, d) is the reverse."""
+        return self.apply_plan(points, side=side, tol=tol, normalize=True)
+
     # -- the loop -------------------------------------------------------------
     def options(self, **kw) -> L.ipd_apd_opts:
         o = L.ipd_apd_opts()

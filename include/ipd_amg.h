@@ -524,6 +524,26 @@ int ipd_apd_plan_dev(ipd_apd* h, double tol, int64_t cap, int64_t* jc_dev, int64
  * column.                                                                                        */
 int ipd_apd_set_plan(ipd_apd* h, const ipd_csc* X);
 
+/* The plan applied on the device: with X what ipd_apd_plan returns at this tol (a NaN is
+ * kept, tol = 0 keeps every nonzero; class 2: the x block of uk),
+ *   side = 0:  Y = X*B,   B n x k as B[j + c*n],  Y m x k as Y[i + c*m],  w = X*1  (m entries)
+ *   side = 1:  Y = X'*B,  B m x k as B[i + c*m],  Y n x k as Y[j + c*n],  w = X'*1 (n entries)
+ * -- the layouts of ipd_cost_spec::xs / ys, so a point cloud goes in as it is.  k is in [1, 16]; w may be
+ * NULL and is the plain mass of the kept entries (p and q are not applied: that is ax of ipd_apd_plan).
+ * A dropped entry contributes exactly +0.0 whatever B holds there: an inf or NaN in a row of B that meets
+ * only dropped entries does not reach Y (B is not checked for finiteness otherwise).  normalize = 1
+ * divides row r of Y by w[r], one IEEE division per entry (the barycentric projection when B is a point
+ * cloud); a row of zero kept mass is 0/0 = NaN.  Deterministic: two calls, and the two entries, give the
+ * same bits.  The workspace is only read -- state, script variables, histories and partial buffers are as
+ * before -- and neither c nor the coordinates are touched, so stored, point-cloud and matrix-free
+ * workspaces behave alike.  IPD_E_ARG for a NULL h, B or Y, side or normalize outside {0, 1}, tol negative
+ * or NaN; IPD_E_LIMIT for k outside [1, 16]; nothing is written then.  Both return when the result is
+ * complete.                                                                                         */
+int ipd_apd_plan_apply(ipd_apd* h, double tol, int32_t side, int32_t k, int32_t normalize,
+                       const double* B, double* Y, double* w);          /* host arrays   */
+int ipd_apd_plan_apply_dev(ipd_apd* h, double tol, int32_t side, int32_t k, int32_t normalize,
+                           const double* B_dev, double* Y_dev, double* w_dev);   /* device arrays */
+
 /* The cost matrix built on the device from two point clouds: a driver run is created
  * from (m+n)*d coordinates, nothing mn-sized crosses the host boundary.  With t_k = xs(i,k) - ys(j,k)
  * folded in ascending k into an accumulator that starts at +0.0, multiply and add separate:
