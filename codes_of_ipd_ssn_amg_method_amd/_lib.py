@@ -81,6 +81,11 @@ class ipd_plan_stats(Structure):
                 ("max_dropped", c_double), ("fval_kept", c_double)]
 
 
+class ipd_dual_stats(Structure):
+    _fields_ = [("dual", c_double), ("bterm", c_double), ("cap", c_double), ("dmin", c_double),
+                ("imin", c_int64), ("jmin", c_int64), ("nneg", c_int64), ("fval", c_double), ("gap", c_double)]
+
+
 class ipd_cost_spec(Structure):
     _fields_ = [("metric", c_int32), ("dim", c_int32), ("m", c_int64), ("n", c_int64),
                 ("xs", POINTER(c_double)), ("ys", POINTER(c_double)), ("scale", c_int32)]
@@ -138,6 +143,8 @@ lib.ipd_apd_plan_dev.argtypes = [c_void_p, c_double, c_int64, c_void_p, c_void_p
 lib.ipd_apd_set_plan.argtypes = [c_void_p, c_void_p]
 lib.ipd_apd_plan_apply.argtypes = [c_void_p, c_double, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_plan_apply_dev.argtypes = lib.ipd_apd_plan_apply.argtypes
+lib.ipd_apd_dual.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_dual_dev.argtypes = lib.ipd_apd_dual.argtypes
 lib.ipd_cost_points_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_create_points.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_get_cost.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -175,6 +182,7 @@ EXPORTS = [
     "ipd_amg_packed_operator",
     "ipd_apd_plan", "ipd_apd_plan_dev", "ipd_apd_set_plan",
     "ipd_apd_plan_apply", "ipd_apd_plan_apply_dev",
+    "ipd_apd_dual", "ipd_apd_dual_dev",
     "ipd_cost_points_dev", "ipd_apd_create_points", "ipd_apd_get_cost",
     "ipd_apd_create_points_free", "ipd_apd_cost_info",
     "ipd_apd_get_w", "ipd_apd_eval_trial", "ipd_apd_merit", "ipd_apd_end",

@@ -751,10 +751,13 @@ class APDWorkspace:
         d.r, d.l, d.p, d.q = dptr(r_), dptr(l_), dptr(p_), dptr(q_)
         d.mu = float(mu)
         d.gama_scalar = np.inf
+        self._finite_gama = False     # class 1 with a finite scalar or a vector gama: the dual keeps its cap term
         if self.cls == 1:
             if np.ndim(gama) == 0 or np.size(gama) == 1:
                 d.gama_scalar = float(np.asarray(gama).reshape(-1)[0])
+                self._finite_gama = bool(np.isfinite(d.gama_scalar))
             else:
+                self._finite_gama = True
                 g = f64(gama)
                 if g.size != m * n:
                     raise ValueError("gama must be a scalar or an m*n vector")
@@ -980,6 +983,98 @@ class APDWorkspace:
         ``T(x_i) = sum_j x_ij y_j / sum_j x_ij``; ``side=1`` with ``points = xs`` (m, d) is the reverse."""
         return self.apply_plan(points, side=side, tol=tol, normalize=True)
 
+    # -- the dual certificate --------------------------------------------------
+    @staticmethod
+    def _dual_stats(st: L.ipd_dual_stats) -> dict:
+        return dict(dual=st.dual, bterm=st.bterm, cap=st.cap, dmin=st.dmin, imin=int(st.imin), jmin=int(st.jmin),
+                    nneg=int(st.nneg), fval=st.fval, gap=st.gap)
+
+    def _dual_side(self, side):
+        if side not in (-1, 0, 1):
+            raise ValueError("side must be -1 (evaluate), 0 (hold alpha, new beta) or 1 (hold beta, new alpha)")
+        return (self.m, self.n)[side] if side >= 0 else 0
+
+    def dual(self, lam=None, side: int = -1, primal: bool = False, arg: bool = False) -> dict:
+        """The dual value of a multiplier, computed where the cost lives (``ipd_apd_dual``): ``lam``
+        (``[alpha (n); beta (m)(; tau)]``, None: the workspace's ``lk``) as it is (``side=-1``) or after the
+        c-transform of one side -- ``side=0`` holds ``alpha`` and takes ``beta_i = max_j (-C_ij - p_i alpha_j)/q_j``,
+        ``side=1`` holds ``beta`` (class 2: with ``tau*phi`` and the clamps at 0).  Returns ``dict(dual, bterm, cap,
+        dmin, imin, jmin, nneg, fval, gap)``: ``dual = bterm - cap`` with ``bterm = -<b,lam>`` and ``cap`` the
+        finite-``gama`` sum, the smallest reduced cost and its first place, the count of negative ones, and with
+        ``primal=True`` ``fval = <c,xk>`` and ``gap = fval - dual`` (nan otherwise).  After a transform the dict
+        also holds ``lam``, the repaired multiplier, and with ``arg=True`` ``arg``, the winning column of every
+        row (``side=0``) or row of every column (``side=1``): the Laguerre-cell assignment.  Nothing mn-sized
+        crosses to the host, and the workspace is only read."""
+        rows = self._dual_side(side)
+        lam_ = self._lam_sized(lam, "lam") if lam is not None else None
+        out = np.empty(self.L) if side >= 0 else None
+        am = np.empty(rows, np.int32) if side >= 0 and arg else None
+        st = L.ipd_dual_stats()
+        check(lib.ipd_apd_dual(self.handle, lam_.ctypes.data if lam_ is not None else None, c_int32(side),
+                               c_int32(1 if primal else 0), out.ctypes.data if out is not None else None,
+                               am.ctypes.data if am is not None else None, byref(st)))
+        res = self._dual_stats(st)
+        if out is not None:
+            res["lam"] = out
+        if am is not None:
+            res["arg"] = am
+        return res
+
+    def dual_dev(self, lam=None, side: int = -1, primal: bool = False, lam_out=None, arg=None) -> dict:
+        """The same on caller-owned device arrays (``ipd_apd_dual_dev``): ``lam`` and ``lam_out`` L float64,
+        ``arg`` m (``side=0``) or n (``side=1``) int32, each may be None -- torch tensors on the workspace's GPU,
+        ``DeviceBuffer`` objects, or ``(pointer, entries)`` pairs, as ``plan_dev`` takes them.  Returns the
+        statistics."""
+        rows = self._dual_side(side)
+
+        def ptr_of(a, itemsize, need, name):
+            if a is None:
+                return None
+            if isinstance(a, tuple):
+                p, cnt = c_void_p(int(a[0])), int(a[1])
+            elif isinstance(a, L.DeviceBuffer):
+                p, cnt = a.ptr, a.nbytes // itemsize
+            elif hasattr(a, "data_ptr"):
+                if a.element_size() != itemsize or not a.is_contiguous():
+                    raise ValueError("dual_dev: tensors must be contiguous float64 (arg: int32)")
+                p, cnt = c_void_p(a.data_ptr()), a.numel()
+            else:
+                raise ValueError(f"dual_dev: {name} must be a tensor, a DeviceBuffer or a (pointer, entries) pair")
+            if cnt < need:
+                raise ValueError(f"dual_dev: {name} must hold {need} entries")
+            return p
+        lam_p = ptr_of(lam, 8, self.L, "lam")
+        out_p = ptr_of(lam_out, 8, self.L, "lam_out")
+        arg_p = ptr_of(arg, 4, rows, "arg")
+        st = L.ipd_dual_stats()
+        check(lib.ipd_apd_dual_dev(self.handle, lam_p, c_int32(side), c_int32(1 if primal else 0), out_p, arg_p,
+                                   byref(st)))
+        return self._dual_stats(st)
+
+    def c_transform(self, lam=None, side: int = 0):
+        """The multiplier with one side replaced by its c-transform (``dual(lam, side)["lam"]``): ``side=0`` holds
+        ``alpha`` and returns the best feasible ``beta`` for it, ``side=1`` the reverse.  Alternating the two is a
+        loop of the caller's."""
+        if side not in (0, 1):
+            raise ValueError("c_transform: side must be 0 or 1")
+        return self.dual(lam, side=side)["lam"]
+
+    def certificate(self) -> dict:
+        """The better of the two repaired multipliers of the workspace's ``lk``: ``dual(side=0)`` and
+        ``dual(side=1)`` with ``primal=True`` and ``arg=True``, the one with the larger ``dual`` (a certified lower
+        bound when ``dmin >= 0``; ``gap`` is then a bound on ``<c,xk> - f*`` for a feasible ``xk``), marked with
+        its ``side``.  With finite ``gama`` (class 1) every multiplier is feasible and no transform applies: the
+        evaluation of ``lk`` itself, ``side = -1``."""
+        if self._finite_gama:
+            res = self.dual(side=-1, primal=True)
+            res["side"] = -1
+            return res
+        both = [self.dual(side=s, primal=True, arg=True) for s in (0, 1)]
+        side = 1 if both[1]["dual"] > both[0]["dual"] else 0
+        res = both[side]
+        res["side"] = side
+        return res
+
     # -- the loop -------------------------------------------------------------
     def options(self, **kw) -> L.ipd_apd_opts:
         o = L.ipd_apd_opts()
@@ -1136,7 +1231,7 @@ def warmup_class2(c, r, l, p, q, mu, phi, res=None, maxit=None):
 
 
 def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool = False,
-                plan_tol=None) -> dict:
+                plan_tol=None, certificate: bool = False) -> dict:
     try:
         if warm is not None:
             ws.warmup(*warm)
@@ -1147,33 +1242,39 @@ def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool 
         out["xk"] = u[:ws.m * ws.n]
         if plan_tol is not None:
             out["plan"], out["plan_stats"], out["plan_ax"] = ws.plan(plan_tol, stats=True)
+        if certificate:
+            out["certificate"] = ws.certificate()
         return out
     finally:
         ws.close()
 
 
 def APD_SsN_Class1(c, r, l, p, q, gama=np.inf, prob=2, rng: MatlabRand | None = None,
-                   amg_opts: dict | None = None, krylov: bool = False, plan_tol=None, **opts) -> dict:
+                   amg_opts: dict | None = None, krylov: bool = False, plan_tol=None, certificate: bool = False,
+                   **opts) -> dict:
     """The script ``Class1/APD_SsN_Class1.m`` with ``inner_solver = 4`` on the workspace it
     loads (``:27``); returns the variables it leaves behind.  Warm start as ``:53-59``.
     ``krylov``: see ``APDWorkspace.run``.  ``plan_tol``: when given, the result gains ``plan`` (the
     final ``xk`` as a sparse m x n matrix without the entries with ``abs(x) <= plan_tol``),
-    ``plan_stats`` and ``plan_ax`` (``APDWorkspace.plan``)."""
+    ``plan_stats`` and ``plan_ax`` (``APDWorkspace.plan``).  ``certificate=True``: the result gains
+    ``certificate``, the dual certificate of the final ``lk`` (``APDWorkspace.certificate``: the better c-transform
+    with its dual value, smallest reduced cost and duality gap; with finite ``gama`` the evaluation of ``lk``)."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=30, theta=1 / 4, smoth=5, cycle="w",
                                 isnsp=1, inter=1, guess=None)                          # :87-88
     warm = (0.0, 100) if prob > 0 else (5e-2, np.inf)                                  # :53-58
     ws = APDWorkspace(1, c, r, l, p, q, gama=gama)
-    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol)
+    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol, certificate)
 
 
 def APD_SsN_Class2(c, r, l, p, q, mu, phi, rng: MatlabRand | None = None,
-                   amg_opts: dict | None = None, krylov: bool = False, plan_tol=None, **opts) -> dict:
+                   amg_opts: dict | None = None, krylov: bool = False, plan_tol=None, certificate: bool = False,
+                   **opts) -> dict:
     """The script ``Class2/APD_SsN_Class2.m`` with ``inner_solver = 4`` (AMG4POT 'amg', or
-    'amg_pcg' with ``krylov``).  ``plan_tol``: as in ``APD_SsN_Class1``."""
+    'amg_pcg' with ``krylov``).  ``plan_tol``, ``certificate``: as in ``APD_SsN_Class1``."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=40, theta=1 / 4, smoth=10, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     ws = APDWorkspace(2, c, r, l, p, q, mu=mu, phi=phi)
-    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol)
+    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate)
 
 
 # ---------------------------------------------------------------------------
@@ -1224,27 +1325,28 @@ def point_cost(xs, ys, metric="sqeuclidean", scale=False, stats=False, ctx=None)
 
 def APD_SsN_Class1_points(xs, ys, r, l, p, q, metric="sqeuclidean", scale=False, gama=np.inf, prob=2,
                           rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
-                          plan_tol=None, matrix_free=False, **opts) -> dict:
+                          plan_tol=None, matrix_free=False, certificate: bool = False, **opts) -> dict:
     """``APD_SsN_Class1`` with ``c = point_cost(xs, ys, metric, scale)`` built on the device
-    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``)."""
+    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``: as there."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=30, theta=1 / 4, smoth=5, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     warm = (0.0, 100) if prob > 0 else (5e-2, np.inf)
     ws = APDWorkspace.from_points(1, xs, ys, r, l, p, q, metric=metric, scale=scale, gama=gama,
                                   matrix_free=matrix_free)
-    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol)
+    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol, certificate)
 
 
 def APD_SsN_Class2_points(xs, ys, r, l, p, q, mu, phi=None, metric="sqeuclidean", scale=False,
                           rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
-                          plan_tol=None, matrix_free=False, **opts) -> dict:
+                          plan_tol=None, matrix_free=False, certificate: bool = False, **opts) -> dict:
     """``APD_SsN_Class2`` with the cost built on the device; ``phi=None`` is all ones
-    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``)."""
+    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``: as in
+    ``APD_SsN_Class1``."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=40, theta=1 / 4, smoth=10, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     ws = APDWorkspace.from_points(2, xs, ys, r, l, p, q, metric=metric, scale=scale, mu=mu, phi=phi,
                                   matrix_free=matrix_free)
-    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol)
+    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate)
 
 
 def load_input(path: str) -> dict:

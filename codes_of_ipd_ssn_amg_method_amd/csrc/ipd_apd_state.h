@@ -5,7 +5,9 @@
 //   ipd_apd_passes.hip   the four pass families of an iteration (begin, eval, merit, end) and their epilogues
 //   ipd_apd_warm.hip     the A-ADMM warm start
 //   ipd_plan.hip         the transport plan as a sparse matrix, out of and into the workspace
+//   ipd_plan_apply.hip   the plan applied to a thin dense matrix
 //   ipd_cost.hip         the cost matrix from point clouds
+//   ipd_dual.hip         the c-transform of the multiplier, the dual value and the duality gap
 #pragma once
 
 #include <functional>
@@ -56,6 +58,9 @@ struct ipd_apd {
     bool cost_free = false;
     CostSrc cost_src{};
     int cost_dim = 0, cost_metric = 0, cost_scale = 0;   // of the specification; 0 for a workspace from a host c
+    // ipd_apd_dual: what the one check of a c-transform's divider found, [0] q (side 0), [1] p (side 1):
+    // 0 not looked at yet, 1 every entry positive and finite, -1 refused
+    int8_t dual_divider[2] = {0, 0};
     // script variables
     int k = 0;
     double bk = 1.0;
@@ -154,3 +159,8 @@ float apd_bench_eval(ipd_apd* h, bool merit3, int reps);
 // ---- ipd_apd_warm.hip ----------------------------------------------------------------------
 // A-ADMM warm start                       warmup_class1.m:22-96 / warmup_class2.m:19-100
 void apd_warmup(ipd_apd* h, double res, long long maxit);
+
+// ---- ipd_dual.hip --------------------------------------------------------------------------
+// (reached through the C ABI only, ipd_apd_dual and ipd_apd_dual_dev: it reads the workspace through the handle
+// above, remembers its divider check in ipd_apd::dual_divider and keeps every temporary in the context's scratch
+// arena)

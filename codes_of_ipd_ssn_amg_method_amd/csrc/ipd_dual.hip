@@ -1,0 +1,639 @@
+// The dual certificate where the multiplier lives (ipd_apd_dual, ipd_apd_dual_dev): the
+// c-transform of one side of lam = [alpha (n); beta (m)(; tau)] with its arg-max map, and the dual value, the smallest
+// reduced cost and the duality gap of the result.  Nothing mn-sized crosses the host boundary and nothing of the
+// workspace is written: partials and results live in the context's scratch arena.
+//
+//   transform  one streaming read of c (and phi), lanes along i (coalesced), 16 loads per lane and array in flight, a
+//              wave walks the DU_CPG chunks of its column group alone, no LDS, no barrier.  A candidate is
+//                side 0   t(i,j) = ((-c(i,j) [- tau*phi(i,j)]) - p_i*alpha_j) / q_j     beta^_i  = max_j t(i,j)
+//                side 1   t(i,j) = ((-c(i,j) [- tau*phi(i,j)]) - q_j*beta_i)  / p_i     alpha^_j = max_i t(i,j)
+//              every operation one IEEE operation in the order written; a NaN counts as -inf; the key of the
+//              maximum is (value descending, index ascending), which is associative: any tree gives the same bits.
+//     side 0   alpha_j and q_j are uniform over the wave (lane l fetches those of column j0 + (l & 15), __shfl hands
+//              them round); the running (max, arg max) stays in registers over the column group and leaves as one
+//              partial per (group, row).
+//     side 1   a lane holds p_i and beta_i; per chunk one colmax16 butterfly -- colsum16 of the tile walker on the
+//              (value, index) key -- gives the wave's 16 column maxima, one partial per (segment slot, column).
+//   finish     one thread per entry of lam_out: the new side combines its partials in index order (class 2: clamped
+//              at 0), the held side is copied (class 2: clamped at 0), tau passes through.
+//   evaluate   one pass forms d(i,j) = ((c + p_i*alpha_j) + q_j*beta_i) [+ tau*phi] and keeps, per workgroup, the
+//              smallest d with its first column-major place, the count of d < 0, sum gama*(-d) over d < 0 (finite
+//              gama only) and, with primal = 1, sum c*x -- the only case that reads u.
+//   last       one workgroup: the evaluation's partials in a fixed shape, class 2's alpha and beta blocks of d,
+//              -<b, lam> (thread t adds entries t, t + 256, ... in order, then a fixed tree), the dual value and gap.
+//
+// Geometry and every index: ipd_dual_geo.h.  Deterministic: maxima and minima are order-independent, every sum has a
+// fixed shape, no float atomics -- two calls give the same bits, and so do the host and the device entry.
+#pragma clang fp contract(off)
+
+#include <cmath>
+#include <limits>
+#include <vector>
+
+#include "ipd_apd_state.h"
+#include "ipd_dual_geo.h"
+
+namespace {
+
+// TR, TC: ipd_apd_geo.h; colsum_index: ipd_apd_tiles.h
+constexpr int DU_NOIDX = 0x7fffffff;                  // the index of a padding lane: behind every row
+constexpr long long DU_NOPLACE = 0x7fffffffffffffffLL;   // the place of "no entry"
+
+// (value descending, index ascending): does (bv, bi) come before (av, ai)?
+__device__ __forceinline__ bool du_before(double bv, int bi, double av, int ai) {
+    return bv > av || (bv == av && bi < ai);
+}
+__device__ __forceinline__ void du_merge(double& v, int& i, double ov, int oi) {
+    const bool take = du_before(ov, oi, v, i);
+    v = take ? ov : v;
+    i = take ? oi : i;
+}
+// (value ascending, place ascending)
+__device__ __forceinline__ void du_merge_min(double& v, long long& i, double ov, long long oi) {
+    const bool take = ov < v || (ov == v && oi < i);
+    v = take ? ov : v;
+    i = take ? oi : i;
+}
+__device__ __forceinline__ double du_clamp0(double v) { return v > 0.0 ? v : 0.0; }   // a NaN becomes 0
+
+// 16 candidates per lane (one per column of a chunk, all of row `row`) -> the 16 column maxima over the wave's 64
+// rows with the rows that reach them: colsum16's butterfly (ipd_apd_tiles.h) on the key.  On return lane l < 16
+// holds the maximum of column colsum_index(l).
+__device__ __forceinline__ void colmax16(const double (&xv)[TC], int row, int lane, double& out_v, int& out_i) {
+    double v8[8], v4[4], v2[2], v1;
+    int i8[8], i4[4], i2[2], i1;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const bool hi = lane & 1;
+        v8[k] = hi ? xv[k + 8] : xv[k];
+        i8[k] = row;
+        du_merge(v8[k], i8[k], __shfl_xor(hi ? xv[k] : xv[k + 8], 1), __shfl_xor(row, 1));
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const bool hi = lane & 2;
+        v4[k] = hi ? v8[k + 4] : v8[k];
+        i4[k] = hi ? i8[k + 4] : i8[k];
+        du_merge(v4[k], i4[k], __shfl_xor(hi ? v8[k] : v8[k + 4], 2), __shfl_xor(hi ? i8[k] : i8[k + 4], 2));
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const bool hi = lane & 4;
+        v2[k] = hi ? v4[k + 2] : v4[k];
+        i2[k] = hi ? i4[k + 2] : i4[k];
+        du_merge(v2[k], i2[k], __shfl_xor(hi ? v4[k] : v4[k + 2], 4), __shfl_xor(hi ? i4[k] : i4[k + 2], 4));
+    }
+    {
+        const bool hi = lane & 8;
+        v1 = hi ? v2[1] : v2[0];
+        i1 = hi ? i2[1] : i2[0];
+        du_merge(v1, i1, __shfl_xor(hi ? v2[0] : v2[1], 8), __shfl_xor(hi ? i2[0] : i2[1], 8));
+    }
+    du_merge(v1, i1, __shfl_xor(v1, 16), __shfl_xor(i1, 16));
+    du_merge(v1, i1, __shfl_xor(v1, 32), __shfl_xor(i1, 32));
+    out_v = v1;
+    out_i = i1;
+}
+
+// ---------------------------------------------------------------------------
+// transform
+// ---------------------------------------------------------------------------
+template <class CS>   // CS: CostStored or CostFree<D> (ipd_apd_tiles.h)
+struct DuWalk {
+    DuGeo g;
+    int cls2;
+    const double* c;     // CostStored
+    const double* phi;   // class 2
+    const double* p;
+    const double* q;
+    const double* lam;   // alpha at lam, beta at lam + n, class 2: tau at lam[n + m]
+    double* pv;          // du_part_index
+    int* pi;
+    [[no_unique_address]] CS cs;
+};
+
+// side 0: hold alpha, produce beta^
+template <class CS>
+__global__ __launch_bounds__(256) void k_du_rows(const DuWalk<CS> a) {
+    const DuGeo& g = a.g;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int ib = blockIdx.x, grp = blockIdx.y;
+    const int i = ib * TR + tid;
+    const bool in_i = i < g.m;
+    const int ic = in_i ? i : g.m - 1;
+    const double pi = a.p[ic];
+    const double tau = a.cls2 ? a.lam[g.n + g.m] : 0.0;
+    typename CS::Row crow;
+    a.cs.row(crow, ic);
+    double bv = -INFINITY;
+    int bj = du_chunk_col(grp, 0);   // below n; stays when every candidate of the group is -inf
+    for (int ch = 0; ch < DU_CPG; ++ch) {
+        const int j0 = du_chunk_col(grp, ch);
+        if (j0 >= g.n) break;  // uniform
+        double cr[TC], fr[TC];
+#pragma unroll
+        for (int jj = 0; jj < TC; ++jj) {
+            const int j = min(j0 + jj, g.n - 1);   // clamped: the loads need no branch
+            const size_t idx = (size_t)j * g.m + ic;
+            cr[jj] = CS::FREE ? 0.0 : a.c[idx];
+            fr[jj] = a.cls2 ? a.phi[idx] : 0.0;
+        }
+        // lane l fetches alpha, q (and the coordinates) of column j0 + (l & 15), as k_plan_count fetches q
+        const int jl = min(j0 + (lane & (TC - 1)), g.n - 1);
+        double al = a.lam[jl];
+        if (a.cls2) al = du_clamp0(al);
+        const double ql = a.q[jl];
+        typename CS::Col clane;
+        a.cs.col(clane, jl);
+#pragma unroll
+        for (int jj = 0; jj < TC; ++jj) {
+            const double aj = __shfl(al, jj), qj = __shfl(ql, jj);
+            typename CS::Col ccol;
+            a.cs.col_of_lane(ccol, clane, jj);
+            double t = -a.cs.value(cr[jj], crow, ccol);
+            if (a.cls2) {
+                const double tf = tau * fr[jj];
+                t = t - tf;
+            }
+            const double pa = pi * aj;
+            t = t - pa;
+            t = t / qj;
+            const double cand = (j0 + jj < g.n && t == t) ? t : -INFINITY;   // a NaN never wins
+            if (cand > bv) {   // columns ascend: the first of equal maxima stays
+                bv = cand;
+                bj = j0 + jj;
+            }
+        }
+    }
+    if (in_i) {
+        a.pv[du_part_index(g, grp, i)] = bv;
+        a.pi[du_part_index(g, grp, i)] = bj;
+    }
+}
+
+// side 1: hold beta, produce alpha^
+template <class CS>
+__global__ __launch_bounds__(256) void k_du_cols(const DuWalk<CS> a) {
+    const DuGeo& g = a.g;
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int ib = blockIdx.x, grp = blockIdx.y;
+    const int i = ib * TR + tid;
+    const bool in_i = i < g.m;
+    const int ic = in_i ? i : g.m - 1;
+    const int slot = ib * APD_WAVES + wv;   // of a segment without rows too: its maxima are (-inf, DU_NOIDX)
+    const double pi = a.p[ic];
+    double bi = a.lam[g.n + ic];
+    if (a.cls2) bi = du_clamp0(bi);
+    const double tau = a.cls2 ? a.lam[g.n + g.m] : 0.0;
+    typename CS::Row crow;
+    a.cs.row(crow, ic);
+    for (int ch = 0; ch < DU_CPG; ++ch) {
+        const int j0 = du_chunk_col(grp, ch);
+        if (j0 >= g.n) break;  // uniform
+        double cr[TC], fr[TC];
+#pragma unroll
+        for (int jj = 0; jj < TC; ++jj) {
+            const int j = min(j0 + jj, g.n - 1);
+            const size_t idx = (size_t)j * g.m + ic;
+            cr[jj] = CS::FREE ? 0.0 : a.c[idx];
+            fr[jj] = a.cls2 ? a.phi[idx] : 0.0;
+        }
+        const int jl = min(j0 + (lane & (TC - 1)), g.n - 1);
+        const double ql = a.q[jl];
+        typename CS::Col clane;
+        a.cs.col(clane, jl);
+        double xv[TC];
+#pragma unroll
+        for (int jj = 0; jj < TC; ++jj) {
+            const double qj = __shfl(ql, jj);
+            typename CS::Col ccol;
+            a.cs.col_of_lane(ccol, clane, jj);
+            double t = -a.cs.value(cr[jj], crow, ccol);
+            if (a.cls2) {
+                const double tf = tau * fr[jj];
+                t = t - tf;
+            }
+            const double qb = qj * bi;
+            t = t - qb;
+            t = t / pi;
+            xv[jj] = (in_i && j0 + jj < g.n && t == t) ? t : -INFINITY;
+        }
+        double mv;
+        int mi;
+        colmax16(xv, in_i ? i : DU_NOIDX, lane, mv, mi);
+        const int col = j0 + colsum_index(lane);
+        if (lane < 16 && col < g.n) {
+            a.pv[du_part_index(g, slot, col)] = mv;
+            a.pi[du_part_index(g, slot, col)] = mi;
+        }
+    }
+}
+
+struct DuFin {
+    DuGeo g;
+    int cls2;
+    const double* pv;
+    const int* pi;
+    const double* lam;
+    double* lam_out;   // L entries
+    int* arg;          // R entries or nullptr
+};
+
+constexpr int DU_FB = 16;   // partials a finishing thread has in flight
+
+template <bool ARG>
+__global__ __launch_bounds__(256) void k_du_fin(const DuFin a) {
+    const DuGeo& g = a.g;
+    const int M = g.n + g.m;
+    const int t = blockIdx.x * 256 + threadIdx.x;   // position in lam = [alpha (n); beta (m)(; tau)]
+    if (t >= M + a.cls2) return;
+    const bool made = g.side == 0 ? (t >= g.n && t < M) : t < g.n;
+    if (!made) {
+        double v = a.lam[t];
+        if (a.cls2 && t < M) v = du_clamp0(v);   // the held side; tau passes through
+        a.lam_out[t] = v;
+        return;
+    }
+    const int r = g.side == 0 ? t - g.n : t;
+    const int S = du_part_count(g);
+    double bv = a.pv[du_part_index(g, 0, r)];
+    int bi = a.pi[du_part_index(g, 0, r)];
+    int s = 1;
+    for (; s + DU_FB <= S; s += DU_FB) {   // loads go out DU_FB at a time, as sum_strided's: a plain loop pays a round trip each
+        double v[DU_FB];
+        int ix[DU_FB];
+#pragma unroll
+        for (int k = 0; k < DU_FB; ++k) {
+            v[k] = a.pv[du_part_index(g, s + k, r)];
+            ix[k] = a.pi[du_part_index(g, s + k, r)];
+        }
+#pragma unroll
+        for (int k = 0; k < DU_FB; ++k) du_merge(bv, bi, v[k], ix[k]);
+    }
+    for (; s < S; ++s) du_merge(bv, bi, a.pv[du_part_index(g, s, r)], a.pi[du_part_index(g, s, r)]);
+    if (a.cls2) bv = du_clamp0(bv);
+    a.lam_out[t] = bv;
+    if (ARG) a.arg[r] = bi;
+}
+
+// ---------------------------------------------------------------------------
+// evaluate
+// ---------------------------------------------------------------------------
+template <class CS>
+struct DuEval {
+    DuGeo g;
+    int cls2;
+    int cap_on;           // class 1 with finite gama: sum gama*(-d) over d < 0
+    const double* c;      // CostStored
+    const double* phi;    // class 2
+    const double* gama;   // class 1, nullptr -> gs
+    double gs;
+    const double* p;
+    const double* q;
+    const double* lam;
+    const double* x;      // PRIMAL
+    DuEvalPart* part;     // du_eval_index
+    [[no_unique_address]] CS cs;
+};
+
+template <bool PRIMAL, class CS>
+__global__ __launch_bounds__(256) void k_du_eval(const DuEval<CS> a) {
+    __shared__ DuEvalPart red[APD_WAVES];
+    const DuGeo& g = a.g;
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int ib = blockIdx.x, grp = blockIdx.y;
+    const int i = ib * TR + tid;
+    const bool in_i = i < g.m;
+    const int ic = in_i ? i : g.m - 1;
+    const double pi = a.p[ic];
+    const double bi = a.lam[g.n + ic];
+    const double tau = a.cls2 ? a.lam[g.n + g.m] : 0.0;
+    const bool gvec = a.cap_on && a.gama;
+    typename CS::Row crow;
+    a.cs.row(crow, ic);
+    double dmin = INFINITY, cap = 0.0, fv = 0.0;
+    long long didx = DU_NOPLACE;
+    int nneg = 0;
+    for (int ch = 0; ch < DU_CPG; ++ch) {
+        const int j0 = du_chunk_col(grp, ch);
+        if (j0 >= g.n) break;  // uniform
+        double cr[TC], fr[TC], gr[TC], xr[TC];
+#pragma unroll
+        for (int jj = 0; jj < TC; ++jj) {
+            const int j = min(j0 + jj, g.n - 1);
+            const size_t idx = (size_t)j * g.m + ic;
+            cr[jj] = CS::FREE ? 0.0 : a.c[idx];
+            xr[jj] = PRIMAL ? a.x[idx] : 0.0;
+            fr[jj] = a.cls2 ? a.phi[idx] : 0.0;
+            gr[jj] = gvec ? a.gama[idx] : a.gs;
+        }
+        const int jl = min(j0 + (lane & (TC - 1)), g.n - 1);
+        const double al = a.lam[jl];
+        const double ql = a.q[jl];
+        typename CS::Col clane;
+        a.cs.col(clane, jl);
+#pragma unroll
+        for (int jj = 0; jj < TC; ++jj) {
+            const double aj = __shfl(al, jj), qj = __shfl(ql, jj);
+            typename CS::Col ccol;
+            a.cs.col_of_lane(ccol, clane, jj);
+            const double cv = a.cs.value(cr[jj], crow, ccol);
+            const double pa = pi * aj;
+            double d = cv + pa;
+            const double qb = qj * bi;
+            d = d + qb;
+            if (a.cls2) {
+                const double tf = tau * fr[jj];
+                d = d + tf;
+            }
+            const bool valid = in_i && j0 + jj < g.n;
+            if (valid && d < dmin) {   // columns ascend: the first of equal minima stays; a NaN never wins
+                dmin = d;
+                didx = (long long)(j0 + jj) * g.m + i;
+            }
+            const bool neg = valid && d < 0.0;
+            nneg += neg ? 1 : 0;
+            if (a.cap_on) {
+                const double w = gr[jj] * (-d);
+                cap += neg ? w : 0.0;
+            }
+            if (PRIMAL) {
+                const double cx = cv * xr[jj];
+                fv += valid ? cx : 0.0;
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        du_merge_min(dmin, didx, __shfl_xor(dmin, s), __shfl_xor(didx, s));
+        nneg += __shfl_xor(nneg, s);
+    }
+    cap = wave_sum(cap);
+    fv = wave_sum(fv);
+    if (lane == 0) {
+        red[wv].dmin = dmin;
+        red[wv].idx = didx;
+        red[wv].nneg = nneg;
+        red[wv].cap = cap;
+        red[wv].fval = fv;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        DuEvalPart r = red[0];
+#pragma unroll
+        for (int w = 1; w < APD_WAVES; ++w) {
+            du_merge_min(r.dmin, r.idx, red[w].dmin, red[w].idx);
+            r.nneg += red[w].nneg;
+            r.cap += red[w].cap;
+            r.fval += red[w].fval;
+        }
+        a.part[du_eval_index(g, ib, grp)] = r;
+    }
+}
+
+struct DuLast {
+    DuGeo g;
+    int cls2, primal;
+    const DuEvalPart* part;
+    const double* b;     // [r; l(; mu)]
+    const double* lam;   // the multiplier that was evaluated
+    ipd_dual_stats* out;
+};
+
+__global__ __launch_bounds__(256) void k_du_last(const DuLast a) {
+    __shared__ DuEvalPart red[APD_WAVES];
+    __shared__ double redb[APD_WAVES];
+    const DuGeo& g = a.g;
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int M = g.n + g.m, L = M + a.cls2, nblk = du_eval_blocks(g);
+    const long long mn = (long long)g.m * g.n;
+    DuEvalPart r;
+    r.dmin = INFINITY;
+    r.idx = DU_NOPLACE;
+    r.nneg = 0;
+    r.cap = r.fval = 0.0;
+    for (int k = tid; k < nblk; k += 256) {
+        const DuEvalPart o = a.part[k];
+        du_merge_min(r.dmin, r.idx, o.dmin, o.idx);
+        r.nneg += o.nneg;
+        r.cap += o.cap;
+        r.fval += o.fval;
+    }
+    if (a.cls2)   // the blocks d_y = alpha, d_z = beta follow the x block
+        for (int k = tid; k < M; k += 256) {
+            const double v = a.lam[k];
+            du_merge_min(r.dmin, r.idx, v, mn + k);
+            r.nneg += v < 0.0 ? 1 : 0;
+        }
+    double bs = 0.0;
+    int k0 = tid;
+    for (; k0 + (DU_FB - 1) * 256 < L; k0 += DU_FB * 256) {   // the same order of additions, the loads in one burst
+        double t[DU_FB];
+#pragma unroll
+        for (int k = 0; k < DU_FB; ++k) t[k] = a.b[k0 + k * 256] * a.lam[k0 + k * 256];
+#pragma unroll
+        for (int k = 0; k < DU_FB; ++k) bs += t[k];
+    }
+    for (; k0 < L; k0 += 256) {
+        const double t = a.b[k0] * a.lam[k0];
+        bs += t;
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        du_merge_min(r.dmin, r.idx, __shfl_xor(r.dmin, s), __shfl_xor(r.idx, s));
+        r.nneg += __shfl_xor(r.nneg, s);
+    }
+    r.cap = wave_sum(r.cap);
+    r.fval = wave_sum(r.fval);
+    bs = wave_sum(bs);
+    if (lane == 0) {
+        red[wv] = r;
+        redb[wv] = bs;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        r = red[0];
+        bs = redb[0];
+#pragma unroll
+        for (int w = 1; w < APD_WAVES; ++w) {
+            du_merge_min(r.dmin, r.idx, red[w].dmin, red[w].idx);
+            r.nneg += red[w].nneg;
+            r.cap += red[w].cap;
+            r.fval += red[w].fval;
+            bs += redb[w];
+        }
+        ipd_dual_stats st;
+        st.bterm = -bs;
+        st.cap = r.cap;
+        st.dual = st.bterm - st.cap;
+        st.dmin = r.dmin;
+        const bool in_x = r.idx < mn;
+        st.imin = in_x ? r.idx % g.m : -1;
+        st.jmin = in_x ? r.idx / g.m : -1;
+        st.nneg = r.nneg;
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        st.fval = a.primal ? r.fval : nan;
+        st.gap = a.primal ? st.fval - st.dual : nan;
+        *a.out = st;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+bool cap_on(const ipd_apd* h) { return h->cls == 1 && (h->gama || std::isfinite(h->P.gs)); }
+
+// the divider of a transform, q (side 0) or p (side 1), must be positive and finite: read once per workspace (p and q
+// never change after the create) and remembered
+void check_divider(ipd_apd* h, int side) {
+    int8_t& known = h->dual_divider[side];
+    if (!known) {
+        const size_t cnt = side ? (size_t)h->m : (size_t)h->n;
+        std::vector<double> v(cnt);
+        h->ctx->fetch(side ? h->p : h->q, v.data(), cnt);
+        known = 1;
+        for (double x : v)
+            if (!(x > 0.0) || !std::isfinite(x)) known = -1;
+    }
+    IPD_REQUIRE(known > 0, IPD_E_ARG,
+                side ? "ipd_apd_dual: side 1 divides by p, which has an entry that is <= 0 or not finite"
+                     : "ipd_apd_dual: side 0 divides by q, which has an entry that is <= 0 or not finite");
+}
+
+void check_args(ipd_apd* h, int32_t side, int32_t primal, const ipd_dual_stats* st) {
+    IPD_REQUIRE(h && st, IPD_E_ARG, "ipd_apd_dual: NULL argument");
+    IPD_REQUIRE(side >= -1 && side <= 1, IPD_E_ARG, "ipd_apd_dual: side must be -1, 0 or 1");
+    IPD_REQUIRE(primal == 0 || primal == 1, IPD_E_ARG, "ipd_apd_dual: primal must be 0 or 1");
+    IPD_REQUIRE(side < 0 || !cap_on(h), IPD_E_UNSUPPORTED,
+                "ipd_apd_dual: with finite gama every multiplier is feasible; only side = -1 applies");
+}
+
+// all launches of a call on the context's stream; *st is read back (the stream is waited for).  lam_dev: L entries;
+// lam_out_dev: L entries or nullptr; arg_dev: du_out_rows entries or nullptr (both ignored for side < 0)
+void dual_dev(ipd_apd* h, const double* lam_dev, int side, int primal, double* lam_out_dev, int32_t* arg_dev,
+              ipd_dual_stats* st) {
+    ipd_ctx* ctx = h->ctx;
+    Arena& S = *ctx->scratch;
+    const DuGeo g = du_make_geo(h->m, h->n, side > 0 ? 1 : 0);
+    const dim3 grid(g.nib, g.ng);
+    const int cls2 = h->cls == 2 ? 1 : 0;
+    const double* lam_eval = lam_dev;
+    if (side >= 0) {
+        double* pv = S.alloc<double>(du_part_len(g));
+        int* pi = S.alloc<int>(du_part_len(g));
+        if (!lam_out_dev) lam_out_dev = S.alloc<double>((size_t)h->L);
+        with_cost_source(h, [&](auto cs) {
+            DuWalk<decltype(cs)> a;
+            a.g = g;
+            a.cls2 = cls2;
+            a.c = h->c;
+            a.phi = h->phi;
+            a.p = h->p;
+            a.q = h->q;
+            a.lam = lam_dev;
+            a.pv = pv;
+            a.pi = pi;
+            a.cs = cs;
+            if (side == 0)
+                hipLaunchKernelGGL((k_du_rows<decltype(cs)>), grid, dim3(256), 0, ctx->stream, a);
+            else
+                hipLaunchKernelGGL((k_du_cols<decltype(cs)>), grid, dim3(256), 0, ctx->stream, a);
+        });
+        IPD_KERNEL_CHECK();
+        DuFin f;
+        f.g = g;
+        f.cls2 = cls2;
+        f.pv = pv;
+        f.pi = pi;
+        f.lam = lam_dev;
+        f.lam_out = lam_out_dev;
+        f.arg = arg_dev;
+        const dim3 fgrid(cdiv(h->L, 256));
+        if (arg_dev)
+            hipLaunchKernelGGL(k_du_fin<true>, fgrid, dim3(256), 0, ctx->stream, f);
+        else
+            hipLaunchKernelGGL(k_du_fin<false>, fgrid, dim3(256), 0, ctx->stream, f);
+        IPD_KERNEL_CHECK();
+        lam_eval = lam_out_dev;
+    }
+    DuEvalPart* part = reinterpret_cast<DuEvalPart*>(
+        S.alloc<double>((size_t)du_eval_blocks(g) * (sizeof(DuEvalPart) / sizeof(double))));
+    with_cost_source(h, [&](auto cs) {
+        DuEval<decltype(cs)> a;
+        a.g = g;
+        a.cls2 = cls2;
+        a.cap_on = cap_on(h) ? 1 : 0;
+        a.c = h->c;
+        a.phi = h->phi;
+        a.gama = h->gama;
+        a.gs = h->P.gs;
+        a.p = h->p;
+        a.q = h->q;
+        a.lam = lam_eval;
+        a.x = h->u;   // class 2: the x block of uk comes first
+        a.part = part;
+        a.cs = cs;
+        if (primal)
+            hipLaunchKernelGGL((k_du_eval<true, decltype(cs)>), grid, dim3(256), 0, ctx->stream, a);
+        else
+            hipLaunchKernelGGL((k_du_eval<false, decltype(cs)>), grid, dim3(256), 0, ctx->stream, a);
+    });
+    IPD_KERNEL_CHECK();
+    DuLast l;
+    l.g = g;
+    l.cls2 = cls2;
+    l.primal = primal;
+    l.part = part;
+    l.b = h->b;
+    l.lam = lam_eval;
+    l.out = reinterpret_cast<ipd_dual_stats*>(S.alloc<double>(16));
+    hipLaunchKernelGGL(k_du_last, dim3(1), dim3(256), 0, ctx->stream, l);
+    IPD_KERNEL_CHECK();
+    ctx->fetch_bytes(l.out, st, sizeof(ipd_dual_stats));
+}
+static_assert(sizeof(ipd_dual_stats) <= 16 * sizeof(double) && sizeof(DuEvalPart) % sizeof(double) == 0,
+              "dual_dev sizes the result and the partials in doubles");
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------
+extern "C" int ipd_apd_dual_dev(ipd_apd* h, const double* lam_dev, int32_t side, int32_t primal, double* lam_out_dev,
+                                int32_t* arg_dev, ipd_dual_stats* st) {
+    return ipd_guard([&] {
+        check_args(h, side, primal, st);
+        CallScope scope(h->ctx);
+        if (side >= 0) check_divider(h, side);
+        ipd_dual_stats got;
+        dual_dev(h, lam_dev ? lam_dev : h->lam, side, primal, lam_out_dev, arg_dev, &got);
+        h->ctx->sync();   // the scratch arrays are the next call's
+        *st = got;
+    });
+}
+
+extern "C" int ipd_apd_dual(ipd_apd* h, const double* lam, int32_t side, int32_t primal, double* lam_out,
+                            int32_t* arg, ipd_dual_stats* st) {
+    return ipd_guard([&] {
+        check_args(h, side, primal, st);
+        ipd_ctx* ctx = h->ctx;
+        CallScope scope(ctx);
+        if (side >= 0) check_divider(h, side);
+        Arena& S = *ctx->scratch;
+        const size_t L = (size_t)h->L, R = side > 0 ? (size_t)h->n : (size_t)h->m;
+        const double* lam_dev = h->lam;
+        if (lam) {
+            double* up = S.alloc<double>(L);
+            ctx->upload(up, lam, L);
+            lam_dev = up;
+        }
+        double* out_dev = side >= 0 && lam_out ? S.alloc<double>(L) : nullptr;
+        int32_t* arg_dev = side >= 0 && arg ? S.alloc<int32_t>(R) : nullptr;
+        ipd_dual_stats got;
+        dual_dev(h, lam_dev, side, primal, out_dev, arg_dev, &got);
+        if (out_dev) ctx->fetch(out_dev, lam_out, L);
+        if (arg_dev) ctx->fetch(arg_dev, arg, R);
+        ctx->sync();
+        *st = got;
+    });
+}

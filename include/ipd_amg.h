@@ -544,6 +544,40 @@ int ipd_apd_plan_apply(ipd_apd* h, double tol, int32_t side, int32_t k, int32_t 
 int ipd_apd_plan_apply_dev(ipd_apd* h, double tol, int32_t side, int32_t k, int32_t normalize,
                            const double* B_dev, double* Y_dev, double* w_dev);   /* device arrays */
 
+/* The dual certificate on the device.  With C = reshape(c,m,n), lam = [alpha (n); beta (m)] and,
+ * class 2, tau behind them, b = [r; l(; mu)], the reduced cost (Aty.m) is
+ *   d(i,j) = ((C(i,j) + p_i*alpha_j) + q_j*beta_i) [+ tau*phi(i,j)],   class 2 also: d_y = alpha, d_z = beta,
+ * and the dual value g(lam) = -<b,lam> - sum_ij gama_ij*max(0, -d_ij); for gama = inf and for class 2 the last
+ * sum is dropped and lam is feasible when d >= 0 (class 2: over all three blocks).
+ *   side = -1  evaluates lam (L entries, NULL: the workspace's lk) as it is.
+ *   side =  0  holds alpha and replaces beta by its c-transform, beta^_i = max_j t(i,j) with
+ *              t(i,j) = ((-C(i,j) [- tau*phi(i,j)]) - p_i*alpha_j) / q_j, then evaluates the result;
+ *   side =  1  holds beta: alpha^_j = max_i ((-C(i,j) [- tau*phi(i,j)]) - q_j*beta_i) / p_i.
+ * Class 2 first clamps the held side to max(., 0) and clamps the new side likewise.  Every operation is one IEEE
+ * operation in the order written; a NaN candidate counts as -inf; of equal maxima the smallest index wins.  With
+ * r, l >= 0 the transform yields the best feasible multiplier for the held side.  lam_out (L entries or NULL)
+ * receives the repaired multiplier -- the held side (clamped for class 2), the new side, tau passed through --
+ * and arg (NULL, or m entries for side 0, n for side 1) the winning column (row); both are ignored for
+ * side = -1.  primal = 1 adds fval = <c, xk> of the workspace's iterate and the gap (the only case that reads u).
+ * Deterministic: two calls, and the two entries, give the same bits; stored, point-cloud and matrix-free
+ * workspaces give the same bits.  The workspace is only read -- state, script variables, histories and partial
+ * buffers are as before; scratch comes from the context's arena.  IPD_E_ARG for a NULL h or st, side outside
+ * {-1, 0, 1}, primal outside {0, 1}, and for a transform whose divider (q for side 0, p for side 1) has an
+ * entry that is <= 0 or not finite (checked once per workspace and remembered); IPD_E_UNSUPPORTED for
+ * side >= 0 on a class-1 workspace with finite gama (every lam is feasible there); nothing is written then.
+ * Both return when the result is complete.                                                              */
+typedef struct ipd_dual_stats {
+    double dual, bterm, cap;     /* g(lam_out); -<b,lam_out>; sum gama*max(0,-d), 0 when dropped             */
+    double dmin;                 /* smallest reduced cost of lam_out (class 2: over d, alpha, beta)         */
+    int64_t imin, jmin, nneg;    /* first place of dmin in column-major order (-1,-1 if in the y/z blocks);
+                                    count of d < 0 (class 2: over all three blocks)                         */
+    double fval, gap;            /* <c, xk> of the workspace iterate and fval - dual; NaN when primal = 0   */
+} ipd_dual_stats;
+int ipd_apd_dual(ipd_apd* h, const double* lam, int32_t side, int32_t primal,
+                 double* lam_out, int32_t* arg, ipd_dual_stats* st);          /* host arrays   */
+int ipd_apd_dual_dev(ipd_apd* h, const double* lam_dev, int32_t side, int32_t primal,
+                     double* lam_out_dev, int32_t* arg_dev, ipd_dual_stats* st);   /* device arrays; st on the host */
+
 /* The cost matrix built on the device from two point clouds: a driver run is created
  * from (m+n)*d coordinates, nothing mn-sized crosses the host boundary.  With t_k = xs(i,k) - ys(j,k)
  * folded in ascending k into an accumulator that starts at +0.0, multiply and add separate:
