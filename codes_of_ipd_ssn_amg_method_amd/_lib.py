@@ -155,6 +155,7 @@ lib.ipd_apd_eval_trial.argtypes = [c_void_p, c_void_p, c_void_p, c_double, c_voi
                                    c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_merit.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_end.argtypes = [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.ipd_amg_resident_variant.argtypes = [c_void_p, c_void_p, c_void_p]
 
 # every symbol the header declares (tests check that they all resolve)
 EXPORTS = [
@@ -178,7 +179,7 @@ EXPORTS = [
     "ipd_apd_set_state", "ipd_apd_get_state", "ipd_apd_run", "ipd_apd_history",
     "ipd_apd_records", "ipd_apd_reuse_stats", "ipd_apd_begin", "ipd_apd_eval", "ipd_apd_bench_eval", "ipd_prof_read", "ipd_amg_bench_subcycle",
     "ipd_amg_attach_mask_operator", "ipd_amg_attach_mask_transfers", "ipd_amg_attach_level2_poly", "ipd_twogrid_bigph", "ipd_twogrid", "ipd_hybrid_twogrid", "ipd_amg4pot_twogrid",
-    "ipd_aug_pcg", "ipd_pcg4pot", "ipd_spd_solve", "ipd_amg_resident_levels", "ipd_amg_resident_kernel", "ipd_amg_level_forms", "ipd_amg_poly_operator",
+    "ipd_aug_pcg", "ipd_pcg4pot", "ipd_spd_solve", "ipd_amg_resident_levels", "ipd_amg_resident_kernel", "ipd_amg_resident_variant", "ipd_amg_level_forms", "ipd_amg_poly_operator",
     "ipd_amg_packed_operator",
     "ipd_apd_plan", "ipd_apd_plan_dev", "ipd_apd_set_plan",
     "ipd_apd_plan_apply", "ipd_apd_plan_apply_dev",

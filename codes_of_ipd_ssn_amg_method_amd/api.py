@@ -270,6 +270,13 @@ class AMGHierarchy:
         self.ctx.sync()
         return bool(got.value)
 
+    def resident_variant(self):
+        """``ipd_amg_resident_variant``: (full, diag) of the last resident launch -- the full-shape form of the
+        composed kernel, and the form that holds the stamps and the test hook."""
+        full, diag = c_int32(0), c_int32(0)
+        check(lib.ipd_amg_resident_variant(self.handle, byref(full), byref(diag)))
+        return bool(full.value), bool(diag.value)
+
     def level_dims(self, k: int):
         rows, nnz = c_int64(), c_int64()
         check(lib.ipd_amg_level_dims(self.handle, c_int(k), byref(rows), byref(nnz)))

@@ -749,6 +749,7 @@ PlanSwitches read_plan_switches() {
     if (const char* e = switch_value("IPD_RESIDENT_RANKS")) s.resident_ranks = std::atoi(e);
     if (const char* e = switch_value("IPD_RES_PRESLEEP")) s.res_presleep = std::max(0, std::atoi(e));
     if (const char* e = switch_value("IPD_RES_DEBUG_SKIP_PUBLISH")) s.res_skip_publish = (unsigned)std::max(0, std::atoi(e));
+    s.res_no_full = switch_on("IPD_RES_NO_FULL");
     return s;
 }
 

@@ -41,6 +41,7 @@ struct PlanSwitches : LaunchSwitches {
     int resident_g = 0, resident_ranks = 0;      // IPD_RESIDENT_G, IPD_RESIDENT_RANKS (0: unset)
     int res_presleep = -1;                       // IPD_RES_PRESLEEP (-1: unset)
     unsigned res_skip_publish = 0;               // IPD_RES_DEBUG_SKIP_PUBLISH
+    bool res_no_full = false;                    // IPD_RES_NO_FULL: k_resident's general form where the full-shape one applies
 };
 
 enum ImageRole { IMG_SOLVE, IMG_SUB, IMG_SUB3, IMG_SUB4, IMG_NONE };

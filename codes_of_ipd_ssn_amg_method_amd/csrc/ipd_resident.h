@@ -300,10 +300,21 @@ enum res_class {
 // [4] clocks in the barrier before the publish, [5] in the store phase, [6] in the closing barrier, [9] in the
 // finishing lanes of the column-slice half sweeps (whose one barrier counts as [4], their receipt as [5]).
 // Column slices: dbg has 32 words, [16 + c] the clocks and [24 + c] the hand-offs of class c (res_class).
-template <int KE1, int KE2, int KE3 = 0, bool POLY2 = false>
+//
+// DIAG: the stamps and the skip-publish test hook are in the code (a launch asks for them through D.dbg /
+// D.dbg_skip_seq); false: the production form of the column-slice kernels, none of it compiled in.
+// FULL (POLY2 only, resident_takes_full): the metric's full shape -- nf = nc = N2 = 2 BT, G RES_WAVES = nf, mask-form
+// transfers with P = [W; I], isnsp, local first sweeps, nu >= 1, one-row local tail.  Sizes, row ranges and mode flags
+// are then constants: no bound, no clamp, no mode select and no CSR alternative is left in the cycle loop, and the
+// tail workgroup's code is not in the kernel.  Arithmetic and the order of every sum are the general form's.
+template <int KE1, int KE2, int KE3 = 0, bool POLY2 = false, bool DIAG = true, bool FULL = false>
 __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const double* __restrict__ bvec,
                                                     double* xg, double* out, int fixed_cycles) {
     static_assert(!POLY2 || (KE3 == 0 && KE1 == 16), "POLY2: three-level hierarchies in column slices (resident_takes_poly2)");
+    static_assert(!FULL || POLY2, "FULL: the composed instantiation only (resident_takes_full)");
+    static_assert(DIAG || KE1 == 16, "the production form exists for the column-slice kernels");
+    constexpr int FG = 2 * BT / RES_WAVES;   // FULL: workgroups, each with RES_WAVES rows of every block
+    if constexpr (FULL) __builtin_assume(__builtin_amdgcn_workitem_id_x() < (unsigned)BT);
     constexpr bool THREE = KE3 > 0;
     constexpr bool POLY3 = KE3 == 1;   // level 3 in polynomial form (ResDesc::p3rows)
     constexpr int K3 = (THREE && !POLY3) ? KE3 : 2;
@@ -311,9 +322,14 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     double* sm = reinterpret_cast<double*>(res_smem);
     const char* smb = res_smem;
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int b = blockIdx.x, G = gridDim.x - (D.remote ? 1 : 0);   // G: workgroups of levels 1-2
-    const int N1 = D.L1.N, N2 = D.L2.N, nf = D.L1.nf, nc = N1 - nf, Nt = D.Nt;
-    if (D.remote && b == G) {   // the tail workgroup
+    // (macros, not variables or lambdas: in the general forms they leave the very expressions that stood here, so
+    // the encodings of those kernels do not change)
+#define RES_REMOTE (FULL ? 0 : D.remote)
+#define RES_WIDENT (FULL ? 1 : D.wident)
+    const int b = blockIdx.x, G = FULL ? FG : gridDim.x - (RES_REMOTE ? 1 : 0);   // G: workgroups of levels 1-2
+    const int N1 = FULL ? 4 * BT : D.L1.N, N2 = FULL ? 2 * BT : D.L2.N, nf = FULL ? 2 * BT : D.L1.nf, nc = N1 - nf;
+    const int Nt = FULL ? 1 : D.Nt;
+    if (RES_REMOTE && b == G) {   // the tail workgroup
         __shared__ PhaseLds tail_lds;
         __shared__ double tail_red[16];
         __shared__ double tail_part[48 + SOLVE_ML + 1];
@@ -356,9 +372,14 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     double* red = sm + oRED;
 
     // ---- rows of this wave ------------------------------------------------------------------
-    const int loF = (int)(((long long)b * nf) / G), hiF = (int)(((long long)(b + 1) * nf) / G);
-    const int loC = nf + (int)(((long long)b * nc) / G), hiC = nf + (int)(((long long)(b + 1) * nc) / G);
-    const int lo2 = (int)(((long long)b * N2) / G), hi2 = (int)(((long long)(b + 1) * N2) / G);
+    const int loF = FULL ? b * RES_WAVES : (int)(((long long)b * nf) / G);
+    const int hiF = FULL ? loF + RES_WAVES : (int)(((long long)(b + 1) * nf) / G);
+    const int loC = FULL ? nf + b * RES_WAVES : nf + (int)(((long long)b * nc) / G);
+    const int hiC = FULL ? loC + RES_WAVES : nf + (int)(((long long)(b + 1) * nc) / G);
+    const int lo2 = FULL ? b * RES_WAVES : (int)(((long long)b * N2) / G);
+    const int hi2 = FULL ? lo2 + RES_WAVES : (int)(((long long)(b + 1) * N2) / G);
+    // row l of a block's own rows (every workgroup owns a row of every block: a lane beyond them takes the last)
+#define RES_OWN_ROW(lo, hi, l) (FULL ? (lo) + ((l) & (RES_WAVES - 1)) : ((lo) + (l) < (hi) ? (lo) + (l) : (hi) - 1))
     const int rowF = loF + w, rowC = loC + w, row2 = lo2 + w;
     const bool vF = rowF < hiF, vC = rowC < hiC, v2 = row2 < hi2;
     const int rF = vF ? rowF : 0, rC = vC ? rowC : 0, r2 = v2 ? row2 : 0;
@@ -488,8 +509,8 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         // remote tail: row b + G*w of the restriction to its root level, if there is one
         const int rin = b + G * w;
         const ResCsr& Pin = D.tail.root == 4 ? D.Pt4 : D.Pt3;
-        rowp[12 * w + 6] = (D.remote && rin < Nt) ? Pin.rp[rin] : 0;
-        rowp[12 * w + 7] = (D.remote && rin < Nt) ? Pin.rp[rin + 1] : 0;
+        rowp[12 * w + 6] = (RES_REMOTE && rin < Nt) ? Pin.rp[rin] : 0;
+        rowp[12 * w + 7] = (RES_REMOTE && rin < Nt) ? Pin.rp[rin + 1] : 0;
         // third resident level: its own row of P3' (restriction 2 -> 3), this wave's level-2 row of P3
         rowp[12 * w + 8] = v3 ? D.Pt3.rp[r3] : 0;
         rowp[12 * w + 9] = v3 ? D.Pt3.rp[r3 + 1] : 0;
@@ -506,7 +527,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
 #define dv2 sm[oOWN + 7 * RES_WAVES + w]
 #define dg3 sm[oOWN + 8 * RES_WAVES + w]
 #define dv3 sm[oOWN + 9 * RES_WAVES + w]
-    const bool nsp = D.isnsp != 0;
+    const bool nsp = FULL ? true : D.isnsp != 0;
     const double xx1 = nsp ? D.L1.xx[0] : 1.0, xx2 = nsp ? D.L2.xx[0] : 1.0;
     const double xx3 = (THREE && nsp) ? D.L3.xx[0] : 1.0;
     // the kernel-space scalars of the hand-offs are formed as sum * (1 / xx): a multiply where a division
@@ -530,13 +551,13 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     // unused upper half of the RR2 slot (restriction and prolongation use the same numbers), and
     // its operator is one number: the tail then costs two LDS passes instead of five dependent
     // trips to L2 per visit.
-    const bool tail1 = !THREE && Nt == 1 && N2 <= RES_NMAX / 2;
+    const bool tail1 = FULL ? true : !THREE && Nt == 1 && N2 <= RES_NMAX / 2;
     constexpr int oP3C = oRR2 + RES_NMAX / 2;
     // First sweep of a visit (zero start): e = D^-1 (r - (A 1) c) needs no matrix row, so every
     // workgroup forms ALL its entries itself from the r it has just received -- no hand-off.  The
     // inverse diagonals of the F rows of level 1 and of level 2 sit in the unused upper halves of
     // the R2 / E2 slots (same condition as tail1's column: at most RES_NMAX / 2 rows).
-    const bool lfirst = D.localfirst && D.nu >= 1 && N2 <= RES_NMAX / 2 && nf <= RES_NMAX / 2;
+    const bool lfirst = FULL ? true : D.localfirst && D.nu >= 1 && N2 <= RES_NMAX / 2 && nf <= RES_NMAX / 2;
     const bool lfirst2 = lfirst && !THREE;   // (DV2 shares the upper half of the E2 slot with E3)
     constexpr int oDV1 = oR2 + RES_NMAX / 2, oDV2 = oE2 + RES_NMAX / 2;
     if (lfirst) {
@@ -546,7 +567,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     }
     // mask-form transfers: this wave's F-row bits over the C nodes (low half) and its C-row bits over the
     // F rows (high half); bit q of a half <-> entry lane + 64 q, the layout of the register slices
-    const bool xm = !THREE && D.xm != 0 && nc == N2 && D.wident != 0;
+    const bool xm = FULL ? true : !THREE && D.xm != 0 && nc == N2 && D.wident != 0;
     unsigned xbits = 0;
     if (xm) {
         // (all 32 words requested in one burst: a loop of dependent loads cost ~1 us per word)
@@ -587,7 +608,9 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     const auto rs = __builtin_amdgcn_make_buffer_rsrc(D.gran0, 0, 2 * RES_GRAN_MAX * 16, 0x00020000);
     unsigned seq = 0;       // number of the last hand-off
     bool dead = false;      // a spin gave up somewhere: skip every further wait
-    const bool dbg = D.dbg != nullptr && b == 0 && tid == 0;
+    const bool dbg = DIAG && D.dbg != nullptr && b == 0 && tid == 0;
+    // the test hook (ResDesc::dbg_skip_seq): the last workgroup omits its publish of hand-off sq
+#define RES_SKIPPED(sq) (DIAG && (sq) == D.dbg_skip_seq && b == G - 1)
     if (dbg) {
         dbg_acc[0] = dbg_acc[3] = dbg_acc[4] = dbg_acc[5] = dbg_acc[6] = dbg_acc[7] = dbg_acc[8] = 0;
         dbg_acc[1] = __builtin_amdgcn_s_memtime();
@@ -649,7 +672,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             const int l8_ = lane & (RES_WAVES - 1);                                                \
             const bool second_ = lane >= RES_WAVES;                                                \
             if (lane < 2 * RES_WAVES && l8_ < (second_ ? (cB) : (cA)) &&                           \
-                !(seq == D.dbg_skip_seq && b == G - 1))                                            \
+                !RES_SKIPPED(seq))                                                                 \
                 res_publish(rs, seq, (second_ ? (gB) : (gA)) + l8_, (PUBV));                       \
         }                                                                                          \
         double p0 = 0.0, p1 = 0.0;                                                                 \
@@ -754,7 +777,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     auto cs_row_value = [&](int off, bool rhs_b) __attribute__((always_inline)) {
         const bool sec = lane >= RES_WAVES;
         const int r = lane & (RES_WAVES - 1);
-        const int row = sec ? (loC + r < hiC ? loC + r : hiC - 1) : (loF + r < hiF ? loF + r : hiF - 1);
+        const int row = sec ? RES_OWN_ROW(loC, hiC, r) : RES_OWN_ROW(loF, hiF, r);
         const double T = res_red8_tree(sm + oPART + RES_WAVES * lane);
         const double dg_ = sm[oOWN + (sec ? 3 : 0) * RES_WAVES + r];
         const double base = rhs_b ? sm[oOWN + (sec ? 5 : 2) * RES_WAVES + r] : sm[oR1 + row];
@@ -810,7 +833,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         const double cc = c1;
         if (w == 0 && lane < RES_WAVES) {
             // (every workgroup owns a row of every block)
-            const int row = frows ? (loF + lane < hiF ? loF + lane : hiF - 1) : (loC + lane < hiC ? loC + lane : hiC - 1);
+            const int row = frows ? RES_OWN_ROW(loF, hiF, lane) : RES_OWN_ROW(loC, hiC, lane);
             const int g0 = frows ? loF : loC - nf, cnt = frows ? hiF - loF : hiC - loC;
             // (the row's own scalars first: their reads go out with the parts', one LDS latency for all)
             const double dg_ = sm[oOWN + (frows ? 0 : 3) * RES_WAVES + lane];
@@ -821,7 +844,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             const double s = T + dg_ * eo;
             const double g_i = r_own - s - ax_own * cc;
             const double wv = eo + dv_ * g_i;
-            if (lane < cnt && !(sq == D.dbg_skip_seq && b == G - 1)) res_publish(rs, sq, g0 + lane, wv);
+            if (lane < cnt && !RES_SKIPPED(sq)) res_publish(rs, sq, g0 + lane, wv);
             // this half: wv (+ c in a second half); the other half: + c in a second half
             const double mine = first ? wv : wv + cc;
             if (frows) {
@@ -853,8 +876,8 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 res_cs_rows(AF, v0, v1, sm + oPART + RES_WAVES * RES_WAVES * csBuf, w, lane);
             else
                 res_cs_rows(AC, v0, v1, sm + oPART + RES_WAVES * RES_WAVES * csBuf, w, lane);
-            eFo = sm[oE1 + (loF + lane < hiF ? loF + lane : hiF - 1)];
-            eCo = sm[oE1 + (loC + lane < hiC ? loC + lane : hiC - 1)];
+            eFo = sm[oE1 + RES_OWN_ROW(loF, hiF, lane)];
+            eCo = sm[oE1 + RES_OWN_ROW(loC, hiC, lane)];
             __syncthreads();
             cs_finish(frows, first, false, seq);
         }
@@ -1133,7 +1156,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         if (nsp) cnext = res_red8(red) / xxd;
         };
     auto tail = [&]() __attribute__((always_inline)) {
-        if (D.remote) {
+        if (RES_REMOTE) {
             remote_tail(D.Pt3, oRR2, oE2, oR2, oAX2, xx2, N2, c2s);
             return;
         }
@@ -1314,7 +1337,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 if (lane == 0) sm[oPUB + w] = sm[oR3L + r3] - s;
                 RES_HANDOFF3({ sm[oRR3L + j] = v; }, 0, dum0);
             }
-            if (D.remote)
+            if (RES_REMOTE)
                 remote_tail(D.Pt4, oRR3L, oE3L, oR3L, oAX3L, xx3, N3, c3s);
             else
                 local_tail(D.Pt4, D.A4, D.P4, oRR3L, oE3L, oR3L, oAX3L, xx3, N3, c3s);
@@ -1376,7 +1399,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             __syncthreads();
             if (dbg) dbg_acc[3] += __builtin_amdgcn_s_memtime();
             const bool pub = w == 0 && lane < RES_WAVES && lane < hi2 - lo2;
-            if (pub && !(seq == D.dbg_skip_seq && b == G - 1)) res_publish(rs, seq, lo2 + lane, sm[oPUB + lane]);
+            if (pub && !RES_SKIPPED(seq)) res_publish(rs, seq, lo2 + lane, sm[oPUB + lane]);
             // (between the publish and the wait: the stacked restriction row s at the thread's two columns)
             const double s0 = tid < N2 ? sm[oP3C + tid] : 0.0, s1 = tid + BT < N2 ? sm[oP3C + tid + BT] : 0.0;
             double hv[2] = {0.0, 0.0};
@@ -1416,7 +1439,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 const double sr = res_red8_tree(red), sum1 = res_red8_tree(red + RES_WAVES);
                 const double d = res_pcg_1x1(sr + p2ws * sum1, h33, D.pcg_maxit);
                 const double val = T + wB * sum1 + mp * d;
-                if (pub && !(seq == D.dbg_skip_seq && b == G - 1)) res_publish(rs, seq, lo2 + lane, val);
+                if (pub && !RES_SKIPPED(seq)) res_publish(rs, seq, lo2 + lane, val);
             }
             if (dbg) dbg_acc[0] -= __builtin_amdgcn_s_memtime();
             for (int ps = 0; ps < D.presleep; ++ps) __builtin_amdgcn_s_sleep(1);
@@ -1482,7 +1505,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             // row r2 of P' is [W(:,r2)' , 1 at nf + r2]; rowC == nf + row2 (level 2 = the C nodes)
             const double s = xm ? sm[oBETA + r2] * masked_sum(xbits >> 16, oRR1, nf) + sm[oRR1 + rC]
                                 : res_csr_rowdot(D.Pt2, rowp[12 * w + 0], rowp[12 * w + 1], lane, sm, oRR1) +
-                                      (D.wident ? sm[oRR1 + rC] : 0.0);
+                                      (RES_WIDENT ? sm[oRR1 + rC] : 0.0);
             if (dbg) dbg_acc[6] += __builtin_amdgcn_s_memtime();
             if (lane == 0) sm[oPUB + w] = s;
             if constexpr (POLY2) {   // ... and the whole visit of level 2 behind the one barrier of its receipt
@@ -1525,7 +1548,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             }
             const double sF = xm ? sm[oRHO + rF] * masked_sum(xbits & 0xffffu, oU, N2)
                                  : res_csr_rowdot(D.P2, rowp[12 * w + 2], rowp[12 * w + 3], lane, sm, oE2);
-            const double sC = D.wident ? sm[oE2 + r2]
+            const double sC = RES_WIDENT ? sm[oE2 + r2]
                                        : res_csr_rowdot(D.P2, rowp[12 * w + 4], rowp[12 * w + 5], lane, sm, oE2);
             if (dbg) dbg_acc[6] += __builtin_amdgcn_s_memtime();
             if (lane == 0) {
@@ -1537,7 +1560,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 // The F block as it arrives (granules t and t + BT of the hand-off: nf <= 2 BT) feeds the C rows of
                 // the first post-smoothing half sweep, as a half sweep's receipt feeds the next one: behind the
                 // closing barrier the finishing lanes publish it, and the run starts without a barrier of its own.
-                const bool fedpost = nu >= 1 && nf <= 2 * BT;
+                const bool fedpost = FULL ? true : nu >= 1 && nf <= 2 * BT;
                 double fe[2] = {0.0, 0.0};
                 RES_HANDOFF_PVA(4, N1, loF, hiF - loF, loC, hiC - loC, sm[oPUB + lane],
                                 { pa_[u_] = sm[oR1 + j]; pb_[u_] = sm[oAX1 + j]; },
@@ -1555,8 +1578,8 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                                 {}, (nsp ? 1 : 0), xig, dum1);
                 c1 = nsp ? xig * rxx1 : 0.0;
                 if (fedpost) {
-                    eFo = sm[oE1 + (loF + lane < hiF ? loF + lane : hiF - 1)];
-                    eCo = sm[oE1 + (loC + lane < hiC ? loC + lane : hiC - 1)];
+                    eFo = sm[oE1 + RES_OWN_ROW(loF, hiF, lane)];
+                    eCo = sm[oE1 + RES_OWN_ROW(loC, hiC, lane)];
                     cs_finish(false, true, false, seq + 1);
                     csFed = 1;
                 }
@@ -1580,7 +1603,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     const int maxit = D.maxit;
     const bool writer = b == 0 && tid == 0;
     const ResSolve sol = res_stationary(top, cycle, add_correction, D.retol, maxit, D.anycycle, fixed_cycles, dead, writer, out);
-    if (D.remote && b == 0 && tid == 0)   // release the tail workgroup
+    if (RES_REMOTE && b == 0 && tid == 0)   // release the tail workgroup
         __hip_atomic_store(D.tail.tctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (b == 0)
         for (int j = tid; j < N1; j += BT) xg[j] = sm[oX + j];
@@ -1610,10 +1633,14 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         D.dbg[6] = dbg_acc[5];
         D.dbg[7] = dbg_acc[6];
         D.dbg[8] = dbg_acc[7];
-        if (CS1 && !D.remote) D.dbg[9] = dbg_acc[8];   // (a remote tail reports its busy time there)
+        if (CS1 && !RES_REMOTE) D.dbg[9] = dbg_acc[8];   // (a remote tail reports its busy time there)
         if constexpr (CS1)
             for (int k = 0; k < 2 * RES_NCLASS; ++k) D.dbg[16 + k] = (long long)cls_acc[k];
     }
+#undef RES_REMOTE
+#undef RES_WIDENT
+#undef RES_OWN_ROW
+#undef RES_SKIPPED
 #undef RES_HANDOFF3
 #undef RES_HANDOFF3R
 #undef RES_HANDOFF4

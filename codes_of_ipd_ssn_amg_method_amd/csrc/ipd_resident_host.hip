@@ -25,13 +25,14 @@ struct ResidentState {
     int timeouts = 0;            // launches whose bounded spins gave up (then: multi-launch path)
     long long last_handoffs = 0;   // hand-offs and cycles of the last launch (ipd_amg_resident_kernel)
     int last_cycles = 0;
+    bool last_full = false, last_diag = false;   // the variant the last launch took (ipd_amg_resident_variant)
     int capacity = -1;   // workgroups of the chosen instantiation the device holds at once (-1: not asked yet)
     int line_ke = 0, line_ke3 = 0;   // what the "[ipd] resident launch:" line shows as ke / ke3
     bool mask_form() const { return plan.kind == RESIDENT_BIG || plan.kind == RESIDENT_DEEP; }
 };
 
 // ---- the instantiations ---------------------------------------------------------------------
-// Three units instantiate the kernels; this one takes their addresses and compiles none of them.
+// Four units instantiate the kernels; this one takes their addresses and compiles none of them.
 // ipd_resident_kbig.hip
 extern template __global__ void k_resident_big<4, 2, true>(const ResBigDesc, const double* __restrict__, double*, double*, int);
 extern template __global__ void k_resident_big<8, 2, true>(const ResBigDesc, const double* __restrict__, double*, double*, int);
@@ -42,6 +43,11 @@ extern template __global__ void k_resident<16, 16, 0, true>(const ResDesc, const
 extern template __global__ void k_resident<4, 4, 0, false>(const ResDesc, const double* __restrict__, double*, double*, int);
 extern template __global__ void k_resident<8, 8, 0, false>(const ResDesc, const double* __restrict__, double*, double*, int);
 extern template __global__ void k_resident<16, 16, 0, false>(const ResDesc, const double* __restrict__, double*, double*, int);
+// ipd_resident_kprod.hip
+extern template __global__ void k_resident<16, 16, 0, true, false, true>(const ResDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident<16, 16, 0, true, true, true>(const ResDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident<16, 16, 0, true, false, false>(const ResDesc, const double* __restrict__, double*, double*, int);
+extern template __global__ void k_resident<16, 16, 0, false, false, false>(const ResDesc, const double* __restrict__, double*, double*, int);
 // ipd_resident_k3.hip
 extern template __global__ void k_resident<4, 4, 1, false>(const ResDesc, const double* __restrict__, double*, double*, int);
 extern template __global__ void k_resident<8, 8, 1, false>(const ResDesc, const double* __restrict__, double*, double*, int);
@@ -73,11 +79,41 @@ static const ResidentKernel RESIDENT_KERNELS[] = {
     {"k_resident<8,8,4>", ResidentKey::k(8, 4, false), IPD_KFN(k_resident<8, 8, 4, false>)},
     {"k_resident<8,8,8>", ResidentKey::k(8, 8, false), IPD_KFN(k_resident<8, 8, 8, false>)},
 };
+// The variants of those rows (ipd_resident_kprod.hip; k_resident's DIAG and FULL): the production forms of the
+// column-slice kernels, without stamps and test hook, which every launch without a diagnostic request takes, and the
+// full-shape forms of the composed instantiation.  A row of RESIDENT_KERNELS is the diagnostic general form of its
+// key (for the kernels without a production form: the only one), and a variant reports that row's name.
+struct ResidentVariant {
+    ResidentKey key;   // (with `full`)
+    bool diag;
+    const void* fn;
+};
+static ResidentKey full_key(ResidentKey k) {
+    k.full = true;
+    return k;
+}
+static const ResidentVariant RESIDENT_VARIANTS[] = {
+    {full_key(ResidentKey::k(16, 0, true)), false, IPD_KFN(k_resident<16, 16, 0, true, false, true>)},
+    {full_key(ResidentKey::k(16, 0, true)), true, IPD_KFN(k_resident<16, 16, 0, true, true, true>)},
+    {ResidentKey::k(16, 0, true), false, IPD_KFN(k_resident<16, 16, 0, true, false, false>)},
+    {ResidentKey::k(16, 0, false), false, IPD_KFN(k_resident<16, 16, 0, false, false, false>)},
+};
 #undef IPD_KFN
-static const ResidentKernel* resident_kernel(const ResidentKey& key) {
+// the row that names a key's instantiations (whatever the variant)
+static const ResidentKernel* resident_kernel(ResidentKey key) {
+    key.full = false;
     for (const ResidentKernel& k : RESIDENT_KERNELS)
         if (k.key == key) return &k;
     return nullptr;
+}
+// the kernel a launch of `key` takes, with or without diagnostics; *diag: what the kernel taken has
+static const void* resident_kernel_fn(const ResidentKey& key, bool* diag) {
+    for (const ResidentVariant& v : RESIDENT_VARIANTS)
+        if (v.key == key && v.diag == *diag) return v.fn;
+    if (key.full) return nullptr;   // (every full-shape key has both rows)
+    const ResidentKernel* k = resident_kernel(key);
+    *diag = true;
+    return k ? k->fn : nullptr;
 }
 
 // ---- the checks a plan's execution launches ---------------------------------------------------
@@ -222,6 +258,20 @@ static void commit_resident(ipd_amg* h, ResidentState& R, const ResidentPlan& p,
     R.skip_publish = sw.res_skip_publish;
     if (!R.out) R.out = h->arena->alloc<double>(4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2));
     R.ok = true;
+}
+
+// The full-shape form of the composed instantiation: decided again whenever an attach call has changed what the
+// predicate looks at (the composed level 2, the mask-form transfers)
+static void choose_full_shape(const ipd_amg* h, const CycleState* st, ResidentState& R, const PlanSwitches& sw) {
+    if (!R.ok || R.plan.kind != RESIDENT_K) return;
+    const std::vector<LevelShape> shapes = level_shapes(h, st);
+    const ResDesc& D = R.desc;
+    const ResidentFullFacts facts{D.xm != 0, D.wident, D.isnsp, D.localfirst != 0};
+    const bool full = resident_takes_full(R.plan, resident_inputs(h, st, shapes), facts, sw);
+    if (full != R.plan.key.full) {
+        R.plan.key.full = full;
+        R.capacity = -1;   // (another instantiation: asked again before its first launch)
+    }
 }
 
 // ---- k_resident: planned at amg_prepare_levels (ipd_cycle_state.h) -----------------------------
@@ -369,6 +419,8 @@ bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double* x, in
     D.dbg_skip_seq = R.skip_publish;
     ResBigDesc B = R.big;
     B.dbg_skip_seq = R.skip_publish;
+    // stamps asked for, or the skip-publish hook about to fire: the instantiation that has them
+    bool diag = dbg_dev != nullptr || R.skip_publish != 0;
     if (switch_on("IPD_DEBUG_LEVELS"))
         std::fprintf(stderr, "[ipd] resident launch: grid %d ke %d ke3 %d xm %d wident %d three %d remote %d\n", grid,
                      R.line_ke, R.line_ke3, D.xm, D.wident, D.three, D.remote);
@@ -386,12 +438,14 @@ bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double* x, in
     // checked against what the device can hold of this instantiation (registers, LDS: one workgroup
     // per CU) before the first launch; an oversized grid takes the multi-launch path for good -- and so
     // does a key the table has no row for.
-    const ResidentKernel* kern = resident_kernel(p.key);
+    // (the capacity asked once serves a key's diagnostic and production forms: the launch's LDS admits one workgroup
+    // per CU whatever the registers)
+    const void* kern = resident_kernel_fn(p.key, &diag);
     if (kern) {
-        IPD_OPTIN_LDS(ctx, kern->fn, RES_LDS_MAX);
+        IPD_OPTIN_LDS(ctx, kern, RES_LDS_MAX);
         if (R.capacity < 0) {
             int nb = 0;
-            IPD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern->fn, BT, p.lds));
+            IPD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, BT, p.lds));
             R.capacity = nb * st->num_cu;
         }
     }
@@ -399,8 +453,10 @@ bool run_resident(ipd_amg* h, CycleState* st, const double* b_dev, double* x, in
         R.ok = false;
         return false;
     }
+    R.last_full = p.key.full;
+    R.last_diag = diag;
     void* args[] = {p.key.big ? (void*)&B : (void*)&D, (void*)&b_dev, (void*)&x, (void*)&R.out, (void*)&fixed_cycles};
-    IPD_HIP(hipLaunchKernel(kern->fn, dim3(grid), dim3(BT), args, p.lds, ctx->stream));
+    IPD_HIP(hipLaunchKernel(kern, dim3(grid), dim3(BT), args, p.lds, ctx->stream));
     IPD_KERNEL_CHECK();
     if (ms) IPD_HIP(hipEventRecord(e1, ctx->stream));
     const size_t nout = 4 + 2 * ((size_t)std::max(h->opts.maxit, 0) + 2);
@@ -527,6 +583,7 @@ bool amg_attach_maskop(ipd_amg* h, const double* p_dev, const double* q_dev, int
             D.xm_cbits = mo.cbits;
             D.xm_beta = mo.beta;
             D.xm_rho = rho;
+            choose_full_shape(h, st, R, sw);
         }
     }
     {
@@ -605,6 +662,7 @@ static bool amg_attach_poly2(ipd_amg* h) {
     st->poly2_op = rows_op(pb);
     R.plan.key.poly2 = true;
     R.capacity = -1;   // (another instantiation: asked again before its first launch)
+    choose_full_shape(h, st, R, read_plan_switches());
     st->level_forms.resize((size_t)h->J + 1, 0);
     st->level_forms[2] |= 128;
     ctx->sync();   // the pack's scratch operands die with the call scope
@@ -669,6 +727,19 @@ extern "C" int ipd_amg_resident_kernel(const ipd_amg* h, char* name, int32_t cap
         if (cycles) *cycles = st ? st->res->last_cycles : 0;
         // level 1 <-> 2 transfers from the bit mask: always in the mask-form kernel, ResDesc::xm otherwise
         if (mask_transfers) *mask_transfers = (st && st->res->ok && (st->res->mask_form() || st->res->desc.xm)) ? 1 : 0;
+    });
+}
+
+// The variant of that kernel the hierarchy's last resident launch took: the full-shape form of the composed
+// instantiation (resident_takes_full), and the form with stamps and test hook (a launch of ipd_amg_bench_resident /
+// _classes, or one on which IPD_RES_DEBUG_SKIP_PUBLISH fired; kernels without a production form always have them).
+// Zeros before the first launch.
+extern "C" int ipd_amg_resident_variant(const ipd_amg* h, int32_t* full, int32_t* diag) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h, IPD_E_ARG, "NULL handle");
+        const CycleState* st = h->cyc.get();
+        if (full) *full = st && st->res->last_full ? 1 : 0;
+        if (diag) *diag = st && st->res->last_diag ? 1 : 0;
     });
 }
 

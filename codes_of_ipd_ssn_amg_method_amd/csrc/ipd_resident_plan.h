@@ -22,10 +22,12 @@ struct ResidentKey {
     bool poly2 = false;    // ... level 2 composed over a visit (ipd_amg_attach_level2_poly)
     int ke2 = 0, rpw = 0;  // k_resident_big: entries per lane of a level-2 row, rows of a block per wave
     bool deep = false;
+    bool full = false;     // k_resident, poly2: the full-shape form (resident_takes_full)
     static ResidentKey k(int ke, int ke3, bool poly2) { return ResidentKey{false, ke, ke3, poly2, 0, 0, false}; }
     static ResidentKey mask(int ke2, int rpw, bool deep) { return ResidentKey{true, 0, 0, false, ke2, rpw, deep}; }
     bool operator==(const ResidentKey& o) const {
-        return std::tie(big, ke, ke3, poly2, ke2, rpw, deep) == std::tie(o.big, o.ke, o.ke3, o.poly2, o.ke2, o.rpw, o.deep);
+        return std::tie(big, ke, ke3, poly2, ke2, rpw, deep, full) ==
+               std::tie(o.big, o.ke, o.ke3, o.poly2, o.ke2, o.rpw, o.deep, o.full);
     }
 };
 
@@ -214,6 +216,28 @@ inline bool resident_takes_poly2(const ResidentPlan& p, const ResidentInputs& in
     if (p.kind != RESIDENT_K || p.key.poly2 || p.remote || p.key.ke3 != 0 || p.key.ke != 16) return false;
     return in.J == 3 && p.Nin == 1 && !p.three && in.cycle == 'v' && in.smoth >= 1 && in.L[2].nr <= RES_NMAX / 2 &&
            in.L[1].nf <= RES_NMAX / 2 && in.L[2].nr <= 64 * 16;
+}
+
+// What the attach calls and the options have left in the descriptor of a k_resident plan
+struct ResidentFullFacts {
+    bool mask_transfers;   // level 1 <-> 2 transfers from the bit mask are attached (ResDesc::xm)
+    int wident;            // P = [W; I]: 1 yes (by construction or verified), 0 no, -1 not verified yet
+    int isnsp;
+    bool localfirst;       // zero-start first sweeps are formed locally (ResDesc::localfirst)
+};
+
+// The full-shape form of the composed instantiation (k_resident's FULL): the metric's shape, where every size, row
+// range and mode flag of the kernel is a constant -- F block, C block and level 2 of 2 BT rows each, RES_WAVES rows of
+// every block per workgroup, transfers from the mask with P = [W; I], isnsp, local first sweeps, at least one sweep,
+// a one-row local tail and the V cycle (the last two: resident_takes_poly2).  IPD_RES_NO_FULL=1 keeps the general form.
+inline bool resident_takes_full(const ResidentPlan& p, const ResidentInputs& in, const ResidentFullFacts& f,
+                                const PlanSwitches& sw) {
+    if (sw.res_no_full || p.kind != RESIDENT_K || !p.key.poly2 || p.key.ke != 16 || p.key.ke3 != 0 || p.remote || p.three)
+        return false;
+    if (in.J != 3 || p.Nin != 1 || in.cycle != 'v' || in.smoth < 1) return false;
+    const int nf = in.L[1].nf, nc = in.L[1].nr - nf, N2 = in.L[2].nr;
+    if (nf != 2 * BT || nc != 2 * BT || N2 != 2 * BT || p.G * RES_WAVES != nf) return false;
+    return f.mask_transfers && f.wident == 1 && f.isnsp == 1 && f.localfirst;
 }
 
 // ---- mask-form kernel (k_resident_big), planned once the bit mask of level 1 is there -------

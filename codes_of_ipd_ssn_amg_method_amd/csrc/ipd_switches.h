@@ -27,6 +27,7 @@ static constexpr SwitchInfo IPD_SWITCHES[] = {
     {"IPD_RESIDENT_RANKS", SW_VALUE, "<R>: rank groups with a granule buffer each (the sharded resident kernel in emulation, tests)"},
     {"IPD_RES_PRESLEEP", SW_VALUE, "<n>: k_resident's s_sleep(1) count between a publish and the first poll (measurement)"},
     {"IPD_RES_DEBUG_SKIP_PUBLISH", SW_VALUE, "<step>: one omitted publish exercises the give-up and recovery path (tests)"},
+    {"IPD_RES_NO_FULL", SW_FLAG, "k_resident's general form where the full-shape one applies: its bit-for-bit reference (tests) and A/B control"},
     {"IPD_NO_SUBCYCLE", SW_FLAG, "the single-workgroup sub-cycle off: the generic phases stay tested"},
     {"IPD_NO_SMALL", SW_FLAG, "the single-workgroup whole solve off: the generic phases stay tested"},
     {"IPD_NO_BLK", SW_FLAG, "the thread-per-row levels of the single-workgroup kernels off: their generic phases stay tested"},

@@ -687,6 +687,12 @@ int ipd_amg_resident_levels(const ipd_amg* h, int32_t* levels, int32_t* tail_roo
  * pointer but name may be NULL.                                                                    */
 int ipd_amg_resident_kernel(const ipd_amg* h, char* name, int32_t cap, int64_t* handoffs,
                             int32_t* cycles, int32_t* mask_transfers);
+/* The variant of that kernel the hierarchy's LAST resident launch took: *full != 0 the full-shape form of the
+ * composed instantiation (every size and mode of the metric's shape a constant of the kernel; IPD_RES_NO_FULL=1
+ * keeps the general form), *diag != 0 the form that holds the stamps and the skip-publish test hook (a launch of
+ * ipd_amg_bench_resident / _classes or one on which IPD_RES_DEBUG_SKIP_PUBLISH fires; the kernels that have no
+ * production form always).  Zeros before the first launch.  Either pointer may be NULL.            */
+int ipd_amg_resident_variant(const ipd_amg* h, int32_t* full, int32_t* diag);
 /* forms[k], k < count (level k = 1..J; forms[0] = 0): how level k runs where it is held in a single
  * workgroup's LDS image (bit mask over the images packed for this hierarchy; 64 / 128: level 3-4 / level 2 of a
  * resident kernel in polynomial form, held by the resident workgroups): 1 thread-per-row sweeps,
