@@ -88,7 +88,7 @@ static constexpr int RES_WAVES = BT / 64;     // row slots per block and workgro
 static constexpr int RES_NMAX = 4 * BT;        // rows per level (fixed LDS slots)
 static constexpr int RES_P4_SEG = 128;         // ... of ResDesc::p4rows: 128 + 128 + 64
 static constexpr int RES_TAIL_MAX = 64;        // rows of the redundantly solved tail level
-static constexpr size_t RES_LDS_BYTES = sizeof(double) * ((size_t)9 * RES_NMAX + RES_NMAX / 2 + 3 * RES_TAIL_MAX + 14 * RES_WAVES + 12 + 6 * RES_WAVES + 8);   // (... sums, publish slots, own scalars; fail word and stamps; rowp: 12 ints per wave; stamps by class)
+static constexpr size_t RES_LDS_BYTES = sizeof(double) * ((size_t)9 * RES_NMAX + RES_NMAX / 2 + 3 * RES_TAIL_MAX + 14 * RES_WAVES + 12 + 6 * RES_WAVES + 8 + RES_WAVES * RES_WAVES);   // (... sums, publish slots, own scalars; fail word and stamps; rowp: 12 ints per wave; stamps by class; the full shape's third buffer of row totals)
 static constexpr size_t RES_LDS_MAX = IMAGE_LDS_OPTIN;   // dynamic LDS a resident launch may ask for (its own or its tail image's)
 
 // mask-form resident kernel (ipd_resident_big.h)

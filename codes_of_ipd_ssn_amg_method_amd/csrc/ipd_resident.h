@@ -306,7 +306,9 @@ enum res_class {
 // FULL (POLY2 only, resident_takes_full): the metric's full shape -- nf = nc = N2 = 2 BT, G RES_WAVES = nf, mask-form
 // transfers with P = [W; I], isnsp, local first sweeps, nu >= 1, one-row local tail.  Sizes, row ranges and mode flags
 // are then constants: no bound, no clamp, no mode select and no CSR alternative is left in the cycle loop, and the
-// tail workgroup's code is not in the kernel.  Arithmetic and the order of every sum are the general form's.
+// tail workgroup's code is not in the kernel.  Arithmetic and the order of every sum are the general form's.  The hand-offs
+// between the runs of half sweeps are fed there as well: rr rides the pre run's last half sweep and top (with x += e) the post
+// run's (half1_cs), the prolongation sends its F block only, and the pre run starts from top's local first half.
 template <int KE1, int KE2, int KE3 = 0, bool POLY2 = false, bool DIAG = true, bool FULL = false>
 __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const double* __restrict__ bvec,
                                                     double* xg, double* out, int fixed_cycles) {
@@ -362,6 +364,12 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     // stamps by class, 32-bit words (a class's clocks of one launch stay far below 2^32, and sums of differences of
     // low words are exact modulo 2^32): clocks [0 .. 8), hand-offs [8 .. 16)
     unsigned* cls_acc = reinterpret_cast<unsigned*>(sm + oOWN + 10 * RES_WAVES + 12 + 6 * RES_WAVES);
+    // FULL: a third buffer of row totals behind everything else.  The last half sweep of a run forms the totals of
+    // BOTH blocks (they feed rr, or top's r = b - A x): the other block's between its publish and its wait, where the
+    // finishing lanes may still be reading the totals of that very publish from buffer csBuf -- so they go here --,
+    // and the received block's at its receipt, into buffer csBuf ^ 1 as in every fed half sweep.
+    constexpr int oPART3 = oOWN + 10 * RES_WAVES + 12 + 6 * RES_WAVES + 8;
+    static_assert(!FULL || sizeof(double) * (oPART3 + RES_WAVES * RES_WAVES) <= RES_LDS_BYTES, "the third buffer lies inside the launch's LDS");
     // third resident level (THREE): its vectors sit in the upper halves of level 2's slots (N2 <= 1024,
     // N3 <= 512); E3 is a gather target and must lie below 64 KB
     constexpr int oE3L = oE2 + RES_NMAX / 2, oR3L = oRR2 + RES_NMAX / 2, oRR3L = oRR2 + 3 * RES_NMAX / 4;
@@ -761,6 +769,10 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     int csFed = -1, csBuf = 0;
     double eFo = 0.0, eCo = 0.0;
     (void)csFed; (void)csBuf; (void)eFo; (void)eCo;
+    // FULL: the post run's last half sweep has added the correction to x, formed the totals of A x and published top's
+    // hand-off behind its one barrier (half1_cs); add_correction and top's own row work and publish are then skipped
+    bool topfed = false;
+    (void)topfed;
     // A times the LDS vector at `off` on both blocks' own rows, one call each: thread t brings entries t, t + BT of
     // the other block.  The caller's barrier follows; then finishing lane 8 sec + r holds row r's total of block sec.
     auto cs_both_rows = [&](int off) __attribute__((always_inline)) {
@@ -785,6 +797,54 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     };
 
     auto top = [&]() __attribute__((always_inline)) {
+        double nrm2 = 0.0, sumr = 0.0;
+        bool fed = false;
+        if constexpr (FULL) {
+            if (topfed) {   // published by the post run's last half sweep: the receipt and its closing barrier remain
+                fed = true;
+                topfed = false;
+                ++seq;
+                if (*fail) dead = true;   // (a give-up of that half sweep: its barrier has ordered the flag)
+                double hv[4];
+                if (dbg) dbg_acc[0] -= __builtin_amdgcn_s_memtime();
+                for (int ps = 0; ps < D.presleep; ++ps) __builtin_amdgcn_s_sleep(1);
+                if (res_sweep<4>(rs, seq, N1, dead, D.tmo, hv, D.pollsleep)) {
+                    *fail = 1;
+                    if (lane == 0) __hip_atomic_store(D.tmo, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                if (dbg) {
+                    const long long t_ = __builtin_amdgcn_s_memtime();
+                    dbg_acc[0] += t_;
+                    dbg_acc[4] -= t_;
+                }
+                double p0 = 0.0, p1 = 0.0;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int j = tid + u * BT;
+                    const double v = hv[u];
+                    sm[oR1 + j] = v;
+                    sm[oE1 + j] = 0.0;
+                    p0 += v * v;
+                    p1 += v;
+                }
+                p0 = wave_sum(p0);
+                p1 = wave_sum(p1);
+                if (lane == 0) {
+                    red[w] = p0;
+                    red[RES_WAVES + w] = p1;
+                }
+                if (dbg) {
+                    const long long t_ = __builtin_amdgcn_s_memtime();
+                    dbg_acc[4] += t_;
+                    dbg_acc[5] -= t_;
+                }
+                __syncthreads();
+                if (dbg) dbg_acc[5] += __builtin_amdgcn_s_memtime();
+                nrm2 = res_red8_tree(red);
+                sumr = res_red8_tree(red + RES_WAVES);
+            }
+        }
+        if (!fed) {
         if constexpr (CS1) {
             cls_begin(RES_CL_TOP);
             cs_both_rows(oX);
@@ -796,14 +856,38 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             sm[oPUB + RES_WAVES + w] = bC - (sC + dgC * sm[oX + rC]);
         }
         }
-        double nrm2 = 0.0, sumr = 0.0;
         if constexpr (CS1)
             RES_HANDOFF_PV(4, N1, loF, hiF - loF, loC, hiC - loC, cs_row_value(oX, true), {},
                            { sm[oR1 + j] = v; sm[oE1 + j] = 0.0; p0 += v * v; p1 += v; }, {}, 2, nrm2, sumr);
         else
         RES_HANDOFF(4, N1, loF, hiF - loF, loC, hiC - loC,
                     { sm[oR1 + j] = v; sm[oE1 + j] = 0.0; p0 += v * v; p1 += v; }, {}, 2, nrm2, sumr);
+        }
         c1 = nsp ? sumr * rxx1 : 0.0;
+        if constexpr (FULL) {
+            // The first half (F rows) of the first pre-smoothing sweep, and the start of the pre run with it: thread t
+            // forms entries t and t + BT itself, so they feed the C rows' totals from the registers they were formed
+            // in, ahead of the loop's barrier; cycle() publishes the run's first hand-off behind it (no barrier and no
+            // trip through E1 of its own).  The finishing lanes form their own rows' entries by the same expression.
+            double e0[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int j = tid + u * BT;
+                const double g_i = sm[oR1 + j] - sm[oAX1 + j] * c1;
+                e0[u] = sm[oDV1 + j] * g_i;
+                sm[oE1 + j] = e0[u];
+            }
+            csBuf ^= 1;
+            res_cs_rows(AC, e0[0], e0[1], sm + oPART + RES_WAVES * RES_WAVES * csBuf, w, lane);
+            {
+                const int row = loF + (lane & (RES_WAVES - 1));
+                const double g_i = sm[oR1 + row] - sm[oAX1 + row] * c1;
+                eFo = sm[oDV1 + row] * g_i;
+                eCo = 0.0;
+            }
+            csFed = 1;
+            __syncthreads();
+        } else
         if (lfirst) {   // first half (F rows) of the first pre-smoothing sweep: half1(true, true, true)
             for (int j = tid; j < nf; j += BT) {
                 const double g_i = sm[oR1 + j] - sm[oAX1 + j] * c1;
@@ -862,13 +946,117 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         const int blk0 = frows ? 0 : nf, nblk = frows ? nf : nc;
         const int oth0 = frows ? nf : 0, noth = frows ? nc : nf;
         const int me = frows ? 0 : 1;
+        if constexpr (FULL) {
+            if (!feed) {
+                // The last half sweep of a run (a second half, published behind the barrier of the half sweep before
+                // it) carries the hand-off that follows the run: rr = r - A e behind the pre run (C rows), top's
+                // r = b - A x behind the post run (F rows), whose vector is then x + e: add_correction's own add, made
+                // here by the thread that holds the entry.  Both blocks' totals of A times that vector are formed on
+                // the way: the other block's entries, shifted by c between the publish and the wait, are the columns
+                // of this block's rows (totals in buffer PART3); the received entries are the columns of the other
+                // block's rows (totals in buffer csBuf ^ 1, at the receipt).  Behind the one barrier the finishing
+                // lanes finish the rows and publish from registers: cs_both_rows' pass and the publish barrier of the
+                // hand-off are gone.  Nothing reads c1 before that hand-off sets it again (the prolongation's receipt
+                // or top's), so no part of the scalar is formed either.
+                cls_begin(RES_CL_HALF);
+                ++seq;
+                if (*fail) dead = true;
+                const double cc = c1;
+                double ov[2], xo[2] = {0.0, 0.0}, hv[2] = {0.0, 0.0}, mv[2];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {   // (each entry of E1 and of X is read and written by thread j % BT alone)
+                    const int jo = oth0 + tid + u * BT;
+                    const double en = sm[oE1 + jo] + cc;
+                    sm[oE1 + jo] = en;
+                    if (frows) {
+                        const double xn = sm[oX + jo] + en;
+                        sm[oX + jo] = xn;
+                        ov[u] = xn;
+                        xo[u] = sm[oX + blk0 + tid + u * BT];
+                    } else {
+                        ov[u] = en;
+                    }
+                }
+                if (frows)
+                    res_cs_rows(AF, ov[0], ov[1], sm + oPART3, w, lane);
+                else
+                    res_cs_rows(AC, ov[0], ov[1], sm + oPART3, w, lane);
+                if (dbg) dbg_acc[0] -= __builtin_amdgcn_s_memtime();
+                for (int ps = 0; ps < D.presleep; ++ps) __builtin_amdgcn_s_sleep(1);
+                if (res_sweep<2>(rs, seq, nblk, dead, D.tmo, hv, D.pollsleep)) {
+                    *fail = 1;
+                    if (lane == 0) __hip_atomic_store(D.tmo, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                if (dbg) {
+                    const long long t_ = __builtin_amdgcn_s_memtime();
+                    dbg_acc[0] += t_;
+                    dbg_acc[4] -= t_;
+                }
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int j = blk0 + tid + u * BT;
+                    const double en = hv[u] + cc;
+                    sm[oE1 + j] = en;
+                    if (frows) {
+                        const double xn = xo[u] + en;
+                        sm[oX + j] = xn;
+                        mv[u] = xn;
+                    } else {
+                        mv[u] = en;
+                    }
+                }
+                csBuf ^= 1;
+                if (frows)
+                    res_cs_rows(AC, mv[0], mv[1], sm + oPART + RES_WAVES * RES_WAVES * csBuf, w, lane);
+                else
+                    res_cs_rows(AF, mv[0], mv[1], sm + oPART + RES_WAVES * RES_WAVES * csBuf, w, lane);
+                if (dbg) {
+                    const long long t_ = __builtin_amdgcn_s_memtime();
+                    dbg_acc[4] += t_;
+                    dbg_acc[3] -= t_;
+                }
+                __syncthreads();
+                if (dbg) dbg_acc[3] += __builtin_amdgcn_s_memtime();
+                cls_end(RES_CL_HALF);
+                cls_begin(frows ? RES_CL_TOP : RES_CL_RR);
+                // finishing lanes: the F rows' totals lie where this block's or the other block's went
+                const double* totF = frows ? sm + oPART3 : sm + oPART + RES_WAVES * RES_WAVES * csBuf;
+                const double* totC = frows ? sm + oPART + RES_WAVES * RES_WAVES * csBuf : sm + oPART3;
+                if (frows) {   // top: b - (A x) of both blocks' rows, 2 RES_WAVES granules (cs_row_value(oX, true))
+                    if (w == 0 && lane < 2 * RES_WAVES) {
+                        const bool sec = lane >= RES_WAVES;
+                        const int r = lane & (RES_WAVES - 1);
+                        const int row = (sec ? loC : loF) + r;
+                        const double T = res_red8_tree((sec ? totC : totF) + RES_WAVES * r);
+                        const double dg_ = sm[oOWN + (sec ? 3 : 0) * RES_WAVES + r];
+                        const double base = sm[oOWN + (sec ? 5 : 2) * RES_WAVES + r];
+                        const double val = base - (T + dg_ * sm[oX + row]);
+                        if (!RES_SKIPPED(seq + 1)) res_publish(rs, seq + 1, row, val);
+                    }
+                    topfed = true;
+                } else {       // rr: the F block is published, the own C rows' entries stay in the workgroup
+                    if (w == 0 && lane < RES_WAVES) {
+                        const double TF = res_red8_tree(totF + RES_WAVES * lane);
+                        const double TC = res_red8_tree(totC + RES_WAVES * lane);
+                        const double dF_ = sm[oOWN + 0 * RES_WAVES + lane], dC_ = sm[oOWN + 3 * RES_WAVES + lane];
+                        const double rF_ = sm[oR1 + loF + lane], rC_ = sm[oR1 + loC + lane];
+                        const double val = rF_ - (TF + dF_ * eFo);
+                        if (!RES_SKIPPED(seq + 1)) res_publish(rs, seq + 1, loF + lane, val);
+                        sm[oRR1 + loC + lane] = rC_ - (TC + dC_ * eCo);
+                    }
+                }
+                csFed = -1;
+                eFo = eCo = 0.0;   // (dead outside a run of half sweeps)
+                return;
+            }
+        }
         cls_begin(start ? RES_CL_START : RES_CL_HALF);
         ++seq;
         if (*fail) dead = true;           // (a give-up of the previous hand-off: its barrier has ordered the flag)
         if (ezero && first) {             // zero start: the row's sum and its own entry are zero
             eFo = eCo = 0.0;
             cs_finish(frows, first, true, seq);
-        } else if (csFed != me) {         // the first of a run: the totals from E1 in LDS, the own entries too
+        } else if (!FULL && csFed != me) {   // the first of a run: the totals from E1 in LDS, the own entries too (FULL: every run is fed)
             const double v0 = tid < noth ? sm[oE1 + oth0 + tid] : 0.0;
             const double v1 = tid + BT < noth ? sm[oE1 + oth0 + tid + BT] : 0.0;
             csBuf ^= 1;
@@ -1009,7 +1197,7 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
         if constexpr (CS1) {
             const bool local = lfirst && ezero && !post;   // (the first half: done by top())
             if (!local) half1_cs(!post, true, ezero, true, start);
-            half1_cs(post, false, ezero, !last, local);   // (the run's next sweep starts with the other block)
+            half1_cs(post, false, ezero, !last, FULL ? false : local);   // (the run's next sweep starts with the other block; FULL: top() has fed the start)
         } else {
         if (!(lfirst && ezero && !post)) half1(!post, true, ezero);   // else: done by top()    // pre: F rows first (Rk{1}); post: C rows first (Rk{1}')
         half1(post, false, ezero);
@@ -1441,6 +1629,14 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                 const double val = T + wB * sum1 + mp * d;
                 if (pub && !RES_SKIPPED(seq)) res_publish(rs, seq, lo2 + lane, val);
             }
+            // FULL: beta .* e_2, the prolongation's masked-sum operand, is formed at e_2's receipt by the thread that
+            // receives the entry (oU is free: its last reader, the prolongation of the cycle before, lies hand-offs back)
+            double be[2] = {0.0, 0.0};
+            (void)be;
+            if constexpr (FULL) {
+                be[0] = sm[oBETA + tid];
+                be[1] = sm[oBETA + tid + BT];
+            }
             if (dbg) dbg_acc[0] -= __builtin_amdgcn_s_memtime();
             for (int ps = 0; ps < D.presleep; ++ps) __builtin_amdgcn_s_sleep(1);
             if (res_sweep<2>(rs, seq, N2, dead, D.tmo, hv, D.pollsleep)) {
@@ -1454,6 +1650,10 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             }
             if (tid < N2) sm[oE2 + tid] = hv[0];
             if (tid + BT < N2) sm[oE2 + tid + BT] = hv[1];
+            if constexpr (FULL) {
+                sm[oU + tid] = be[0] * hv[0];
+                sm[oU + tid + BT] = be[1] * hv[1];
+            }
             if (dbg) {
                 const long long t_ = __builtin_amdgcn_s_memtime();
                 dbg_acc[4] += t_;
@@ -1468,7 +1668,39 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
     // MG_Vcycle / MG_Wcycle from level 1 down; the correction ends in E1
     auto cycle = [&]() __attribute__((always_inline)) {
         const int nu = D.nu;
+        // FULL: top() has left the C rows' totals of its local first half in PART, behind its barrier: the pre run's
+        // first hand-off is published from them here, like a fed half sweep's
+        if constexpr (FULL) cs_finish(false, false, false, seq + 1);
         for (int s = 0; s < nu; ++s) sweep1(false, s == 0, s == nu - 1, s == 0);
+        if constexpr (FULL) {
+            // rr = r - A e: the pre run's last half sweep has published the F block and left the workgroup's own
+            // entries of the C block in RR1 (half1_cs).  The F block is all the restriction reads beside those: half
+            // the granules, no row work and no publish barrier here.  It arrives pre-scaled by rho as below.
+            ++seq;
+            if (*fail) dead = true;   // (a give-up of that half sweep: its barrier has ordered the flag)
+            const double rh0 = sm[oRHO + tid], rh1 = sm[oRHO + tid + BT];
+            double hv[2] = {0.0, 0.0};
+            if (dbg) dbg_acc[0] -= __builtin_amdgcn_s_memtime();
+            for (int ps = 0; ps < D.presleep; ++ps) __builtin_amdgcn_s_sleep(1);
+            if (res_sweep<2>(rs, seq, nf, dead, D.tmo, hv, D.pollsleep)) {
+                *fail = 1;
+                if (lane == 0) __hip_atomic_store(D.tmo, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (dbg) {
+                const long long t_ = __builtin_amdgcn_s_memtime();
+                dbg_acc[0] += t_;
+                dbg_acc[4] -= t_;
+            }
+            sm[oRR1 + tid] = hv[0] * rh0;
+            sm[oRR1 + tid + BT] = hv[1] * rh1;
+            if (dbg) {
+                const long long t_ = __builtin_amdgcn_s_memtime();
+                dbg_acc[4] += t_;
+                dbg_acc[5] -= t_;
+            }
+            __syncthreads();
+            if (dbg) dbg_acc[5] += __builtin_amdgcn_s_memtime();
+        } else
         {   // rr = r - A e on both blocks
             if constexpr (CS1) {
                 cls_begin(RES_CL_RR);
@@ -1542,6 +1774,68 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
             cls_begin(RES_CL_PROLONG);
             if (dbg) dbg_acc[6] -= __builtin_amdgcn_s_memtime();
             // F rows: W(rowF,:) against E2 (A's columns nf + i are level-2 indices i); C rows: identity
+            if constexpr (FULL) {
+                // beta .* e_2 lies in oU since e_2's receipt (poly2_fed).  With P = [W; I] a C row's new value is
+                // E1[nf + j] + E2[j]: thread j % BT, which holds both, adds them itself between the publish and the
+                // wait, so the C block is not sent -- half the granules -- and its terms of the scalar are ready before
+                // the wait.  They join the thread's sum behind the two F terms, the order of the four-granule form.
+                const double sF = sm[oRHO + rF] * masked_sum(xbits & 0xffffu, oU, N2);
+                if (dbg) dbg_acc[6] += __builtin_amdgcn_s_memtime();
+                if (lane == 0) sm[oPUB + w] = sm[oE1 + rF] + sF;
+                ++seq;
+                if (*fail) dead = true;
+                if (dbg) dbg_acc[3] -= __builtin_amdgcn_s_memtime();
+                __syncthreads();
+                if (dbg) dbg_acc[3] += __builtin_amdgcn_s_memtime();
+                if (w == 0 && lane < RES_WAVES && !RES_SKIPPED(seq)) res_publish(rs, seq, loF + lane, sm[oPUB + lane]);
+                double pa[2], pb[2], tc[2], hv[2] = {0.0, 0.0};
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int j = tid + u * BT;
+                    pa[u] = sm[oR1 + j];
+                    pb[u] = sm[oAX1 + j];
+                    const double ec = sm[oE1 + nf + j] + sm[oE2 + j];
+                    sm[oE1 + nf + j] = ec;
+                    tc[u] = sm[oR1 + nf + j] - sm[oAX1 + nf + j] * ec;
+                }
+                if (dbg) dbg_acc[0] -= __builtin_amdgcn_s_memtime();
+                for (int ps = 0; ps < D.presleep; ++ps) __builtin_amdgcn_s_sleep(1);
+                if (res_sweep<2>(rs, seq, nf, dead, D.tmo, hv, D.pollsleep)) {
+                    *fail = 1;
+                    if (lane == 0) __hip_atomic_store(D.tmo, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                if (dbg) {
+                    const long long t_ = __builtin_amdgcn_s_memtime();
+                    dbg_acc[0] += t_;
+                    dbg_acc[4] -= t_;
+                }
+                double p0 = 0.0;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    sm[oE1 + tid + u * BT] = hv[u];
+                    p0 += pa[u] - pb[u] * hv[u];
+                }
+                p0 += tc[0];
+                p0 += tc[1];
+                // the F block as it arrives feeds the C rows of the first post-smoothing half sweep (see below)
+                csBuf ^= 1;
+                res_cs_rows(AC, hv[0], hv[1], sm + oPART + RES_WAVES * RES_WAVES * csBuf, w, lane);
+                p0 = wave_sum(p0);
+                if (lane == 0) red[w] = p0;
+                if (dbg) {
+                    const long long t_ = __builtin_amdgcn_s_memtime();
+                    dbg_acc[4] += t_;
+                    dbg_acc[5] -= t_;
+                }
+                __syncthreads();
+                if (dbg) dbg_acc[5] += __builtin_amdgcn_s_memtime();
+                c1 = res_red8_tree(red) * rxx1;
+                eFo = sm[oE1 + loF + (lane & (RES_WAVES - 1))];
+                eCo = sm[oE1 + loC + (lane & (RES_WAVES - 1))];
+                cs_finish(false, true, false, seq + 1);
+                csFed = 1;
+                cls_end(RES_CL_PROLONG);
+            } else {
             if (xm) {   // beta .* e_2 once per workgroup, then one masked sum per F row
                 for (int j = tid; j < N2; j += BT) sm[oU + j] = sm[oBETA + j] * sm[oE2 + j];
                 __syncthreads();
@@ -1589,12 +1883,16 @@ __global__ __launch_bounds__(BT, 2) void k_resident(const ResDesc D, const doubl
                           { sm[oE1 + j] = v; p0 += pa_[u_] - pb_[u_] * v; }, {}, (nsp ? 1 : 0), xig, dum1);
             c1 = nsp ? xig * rxx1 : 0.0;
             }
+            }
         }
         // (column slices: the post run's first half sweep is fed by the prolongation, see above)
         for (int s = 0; s < nu; ++s) sweep1(true, false, s == nu - 1, s == 0 && csFed != 1);
     };
 
     auto add_correction = [&]() __attribute__((always_inline)) {   // x += e                                       Class_AMG.m:98,101
+        if constexpr (FULL) {
+            if (topfed) return;   // (added entry by entry in the post run's last half sweep: half1_cs)
+        }
         for (int j = tid; j < N1; j += BT) sm[oX + j] = sm[oX + j] + sm[oE1 + j];
         __syncthreads();
     };
