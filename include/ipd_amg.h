@@ -304,6 +304,9 @@ int ipd_amg4pot_pcg(ipd_ctx*, const ipd_prob* pd, const ipd_amg_opts* o, ipd_rng
                     double* zeta, int32_t* itamg, double* resamg, int64_t info[2]);
 
 /* ---- device-resident path (inputs already in HBM) ------------------------ */
+/* A device pointer needs only the alignment of its element type (8 bytes for double, 1 for a mask
+ * byte): a slice of a larger array is a valid argument.  Wider accesses are taken where the address
+ * allows them and give the same result.                                                        */
 /* raw device memory on the context's GPU */
 int ipd_dmalloc(ipd_ctx*, size_t bytes, void** dptr);
 int ipd_dfree(ipd_ctx*, void* dptr);
@@ -326,6 +329,7 @@ int ipd_aty_dev(ipd_ctx*, const double* y_dev, const double* p_dev, const double
                 int64_t m, int64_t n, double* z_dev);
 int ipd_asat_dev(ipd_ctx*, const uint8_t* s_dev, const double* p_dev, const double* q_dev,
                  int64_t m, int64_t n, ipd_dmat** H);
+/* The hierarchy keeps its own copy of A: the ipd_dmat may be destroyed as soon as the call returns. */
 int ipd_amg_setup_dev(ipd_ctx*, const ipd_dmat* A, const ipd_amg_opts* o, ipd_rng* rng,
                       ipd_amg** out);
 int ipd_amg_solve_dev(ipd_amg* h, const double* b_dev, const double* guess_dev,
