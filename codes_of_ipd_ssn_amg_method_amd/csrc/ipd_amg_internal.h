@@ -58,7 +58,7 @@ struct Level {
 
 struct CycleState;   // ipd_cycle_state.h
 struct KrylovState;  // ipd_krylov.hip
-struct BlockState;   // ipd_block.h
+struct BlockState;   // ipd_block_state.h
 struct BlockKrylovState;   // ipd_block_krylov.hip
 struct LevelDev;     // ipd_cycle_dev.h
 
@@ -84,8 +84,8 @@ struct ipd_amg {
     // AMG-preconditioned CG (ipd_krylov.hip): its level-1 sized vectors, scalars and tickets out of
     // `arena`, made on the first ipd_amg_pcg call
     std::shared_ptr<KrylovState> kry;
-    // block solve of several right-hand sides (ipd_block.hip): its N x W work blocks out of `arena`,
-    // made on the first ipd_amg_solve_multi call and made again for a wider W
+    // block solve of several right-hand sides (ipd_block.hip, block_state): its N x W work blocks out of
+    // `arena`, made on the first ipd_amg_solve_multi or ipd_amg_pcg_multi call and made again for a wider W
     std::shared_ptr<BlockState> blk;
     // AMG-PCG of several right-hand sides (ipd_block_krylov.hip): its N x W vectors, scalars and tickets
     // out of `arena`, made on the first ipd_amg_pcg_multi call and made again for a wider W
@@ -135,7 +135,7 @@ void amg_pcg_small_launch(ipd_amg* h, const PcgSmallVecs& v, double tol, int max
 // hierarchy is planned for it and as launches elsewhere (resk: host, maxit slots or NULL)
 void amg_pcg_planned_dev(ipd_amg* h, const double* e, const double* guess, double tol, long long maxit,
                          double* d_out, long long* it_out, double* res_out, double* resk);
-// What the block solve (ipd_block.hip) needs of a level's launch-path cycle: the CSR matrices with
+// What the block cycle (ipd_block.hip; BlockState: ipd_block_state.h) needs of a level's launch-path cycle: the CSR matrices with
 // their lanes per row and whole-level grids, the smoother data and the coarsest PCG's settings.
 struct BlockCsr {
     int nr = 0, nc = 0;

@@ -2,10 +2,11 @@
 // of E runs the loop of ipd_amg_pcg (ipd_krylov.hip; PCG.m:68-87, M = one cycle from a zero guess,
 // flexible beta) as if it were solved alone, every column of a block in lockstep.
 //
-// The vectors are the block path's (ipd_block.h): N x W row-major, W in {1, 2, 4, 8}, k_blk_in /
-// k_blk_out at the edges, and the preconditioner is BlockRun<W>::cycle on the CSR arrays of every
-// level.  One iteration is the block form of ipd_krylov.hip's four steps and one host read of the
-// W x SC_N scalar records:
+// The vectors are the block path's: N x W row-major, W in {1, 2, 4, 8}, block_in / block_out at the
+// edges, and the preconditioner is block_cycle on the CSR arrays of every level (ipd_block_state.h: this
+// unit instantiates and launches the k_bkry_* kernels only; the row-walk helpers are ipd_block_dev.h's).
+// One iteration is the block form of ipd_krylov.hip's four steps and one host read of the W x SC_N scalar
+// records:
 //   K1 k_bkry_dir_spmv  p_new(:,c) = w(:,c) + beta_c p_old(:,c) formed inside the level-1 CSR row
 //                       walk's gather (p_old is only read), p_new and w_old stored for the owned rows,
 //                       q = A_1 p_new for all W columns (each matrix entry read once), per-workgroup
@@ -13,15 +14,17 @@
 //                       START it forms r = E - A_1 D0 instead.
 //   K2 k_bkry_update    active columns: D += alpha_c p ; r -= alpha_c q.  The new r goes into the block
 //                       cycle's input v[1].r, zero for a frozen column (which then gets e = 0).
-//   cycle               BlockRun<W>::cycle(1, wc, false): w = v[1].e.
-//   K3 k_bkry_dots      r'w and r'w_old per column in one pass; the last workgroup forms delta_new,
-//                       beta, resk and the stop flag of every active column, and the "any active" word.
+//   cycle               block_cycle: w = v[1].e.
+//   K3 k_bkry_dots      r'w and r'w_old per column in one pass; the last workgroup takes the step of
+//                       ipd_pcg_step.h for every active column, and forms the "any active" word.
 // Frozen columns: a column whose stop flag is set keeps D, r and its record; K1 gathers zero for it.
 // Padding columns are zero and stop at the first test (delta_0 = 0).
 // Reductions: per-workgroup partials, one row of G per column, summed in fixed workgroup order by the
 // workgroup that arrives last (kry_last_arrival / kry_sum_parts): no float atomics, the same bits run
 // to run, and no column's sum sees another column's data.  Separate multiplies and adds.
-#include "ipd_block.h"
+#include "ipd_block_state.h"
+
+#include "ipd_block_dev.h"
 #include "ipd_krylov.h"
 
 struct BlockKrylovState {
@@ -148,12 +151,7 @@ __global__ __launch_bounds__(BT) void k_bkry_dir_spmv(BkryDirArgs a) {
 #pragma unroll 1
     for (int c = 0; c < W; ++c) {
         const double pq = kry_sum_parts(a.part + (size_t)c * G, G, 1);
-        if (threadIdx.x == 0 && (act >> c & 1u)) {
-            double* S = a.sc + c * SC_N;
-            const double dn = S[SC_DNEW];
-            S[SC_DOLD] = dn;                                                      // :77
-            S[SC_ALPHA] = dn / pq;                                                // :78
-        }
+        if (threadIdx.x == 0 && (act >> c & 1u)) pcg_step_alpha(a.sc + c * SC_N, pq);   // :77-78
     }
 }
 
@@ -225,24 +223,8 @@ __global__ __launch_bounds__(BT) void k_bkry_dots(BkryDotArgs a) {
     for (int c = 0; c < W; ++c) {
         const double dn = kry_sum_parts(a.part + (size_t)c * G, G, 1);
         const double s_wo = FIRST ? 0.0 : kry_sum_parts(a.part + (size_t)(W + c) * G, G, 1);
-        if (threadIdx.x == 0 && (act >> c & 1u)) {
-            double* S = a.sc + c * SC_N;
-            double d0, itv;
-            if (FIRST) {                                                          // PCG.m:70-72
-                d0 = dn;
-                itv = 0.0;
-                S[SC_D0] = d0;
-                S[SC_BETA] = 0.0;
-            } else {
-                d0 = S[SC_D0];
-                S[SC_BETA] = (dn - s_wo) / S[SC_DOLD];                            // flexible :82
-                itv = S[SC_IT] + 1.0;                                             // :84
-            }
-            S[SC_DNEW] = dn;                                                      // :81
-            S[SC_IT] = itv;
-            S[SC_RES] = sqrt(fabs(dn / d0));                                      // :85 / :88
-            const bool go = itv < a.maxit && dn > a.tol2 * d0;                    // :76
-            S[SC_STOP] = go ? 0.0 : 1.0;
+        if (threadIdx.x == 0 && (act >> c & 1u)) {                                // PCG.m:70-72, :81-85, :76
+            const bool go = pcg_step<FIRST>(a.sc + c * SC_N, dn, s_wo, a.maxit, a.tol2);
             any = any || go;
         }
     }
@@ -282,8 +264,8 @@ static BlockKrylovState* bkry_state(ipd_amg* h, int W, int N, int G1, int G3) {
 
 #define BKRY_K1(W, START, args)                                                                             \
     do {                                                                                                    \
-        if (staged)                                                                                         \
-            hipLaunchKernelGGL((k_bkry_dir_spmv<W, true, START>), dim3(G1), dim3(BT), dyn, ctx->stream, args); \
+        if (st.staged)                                                                                      \
+            hipLaunchKernelGGL((k_bkry_dir_spmv<W, true, START>), dim3(G1), dim3(BT), st.dyn, ctx->stream, args); \
         else                                                                                                \
             hipLaunchKernelGGL((k_bkry_dir_spmv<W, false, START>), dim3(G1), dim3(BT), 0, ctx->stream, args); \
         IPD_KERNEL_CHECK();                                                                                 \
@@ -294,32 +276,28 @@ template <int W>
 static void pcg_chunk(ipd_amg* h, const double* E, long long lde, int ncol, const double* guess, double tol,
                       long long maxit, double* D, int64_t* it, double* res, double* resk) {
     ipd_ctx* ctx = h->ctx;
-    BlockRun<W> run{h, ctx, block_state(h, W)};
-    BlockState* bs = run.bs;
+    BlockState* bs = block_state(h, W);
     const BlockLevel& bl = bs->lv[1];
     const int N = bl.N;
     const int G1 = bl.A.grid;
-    const int G3 = std::max(1, std::min(ctx->num_cu, cdiv(N, BT)));
+    const int G3 = krylov_g3(N, ctx->num_cu);
     BlockKrylovState* ks = bkry_state(h, W, N, G1, G3);
-    const bool staged = blk_staged((long long)N * W);
-    const size_t dyn = staged ? sizeof(double) * (size_t)N * W : 0;
+    const BlockStage st = block_stage(N, W);
     const bool wc = h->opts.cycle == 'w';
     double* r1 = bs->v[1].r;
-    const int grid_io = std::max(1, std::min(1024, cdiv((long long)N * W, 256)));
-    hipLaunchKernelGGL(k_blk_in, dim3(grid_io), dim3(256), 0, ctx->stream, N, W, ncol, E, lde, ks->e);
-    IPD_KERNEL_CHECK();
-    hipLaunchKernelGGL(k_blk_in, dim3(grid_io), dim3(256), 0, ctx->stream, N, W, ncol, guess, lde, ks->p[0]);
-    IPD_KERNEL_CHECK();
+    block_in(ctx, N, W, ncol, E, lde, ks->e);
+    block_in(ctx, N, W, ncol, guess, lde, ks->p[0]);
     // tickets start at zero on every call (the last arriver resets its own, this covers a launch
     // that never completed)
     IPD_HIP(hipMemsetAsync(ks->cnt, 0, 2 * sizeof(unsigned), ctx->stream));
 
-    BkryDirArgs ka{};
-    ka.rp = bl.A.rp;
-    ka.ci = bl.A.ci;
-    ka.va = bl.A.va;
-    ka.N = N;
-    ka.L = bl.A.L;
+    BkryDirArgs walk{};   // level 1's row walk, for both forms of K1
+    walk.rp = bl.A.rp;
+    walk.ci = bl.A.ci;
+    walk.va = bl.A.va;
+    walk.N = N;
+    walk.L = bl.A.L;
+    BkryDirArgs ka = walk;
     ka.w = ks->p[0];                                                              // PCG.m:68
     ka.e = ks->e;
     ka.r = ks->r;
@@ -335,7 +313,7 @@ static void pcg_chunk(ipd_amg* h, const double* E, long long lde, int ncol, cons
     kd.sc = ks->sc;
     kd.part = ks->part3;
     kd.cnt = ks->cnt + 1;
-    run.cycle(1, wc, false);                                                      // :69
+    block_cycle(h, bs, W, wc);                                                     // :69
     kd.w = bs->v[1].e;
     hipLaunchKernelGGL((k_bkry_dots<W, true>), dim3(G3), dim3(BT), 0, ctx->stream, kd);
     IPD_KERNEL_CHECK();
@@ -347,12 +325,7 @@ static void pcg_chunk(ipd_amg* h, const double* E, long long lde, int ncol, cons
         act[(size_t)c] = sc[(size_t)c * SC_N + SC_STOP] == 0.0;
     }
 
-    ka = BkryDirArgs{};
-    ka.rp = bl.A.rp;
-    ka.ci = bl.A.ci;
-    ka.va = bl.A.va;
-    ka.N = N;
-    ka.L = bl.A.L;
+    ka = walk;
     ka.w_old = ks->w_old;
     ka.q = ks->q;
     ka.sc = ks->sc;
@@ -370,7 +343,7 @@ static void pcg_chunk(ipd_amg* h, const double* E, long long lde, int ncol, cons
         hipLaunchKernelGGL(k_bkry_update<W>, dim3(G3), dim3(BT), 0, ctx->stream, N, (const double*)ks->sc,
                            (const double*)ks->p[cur], (const double*)ks->q, ks->d, ks->r, r1);
         IPD_KERNEL_CHECK();                                                       // :79
-        run.cycle(1, wc, false);                                                  // :80
+        block_cycle(h, bs, W, wc);                                                 // :80
         kd.w = bs->v[1].e;
         hipLaunchKernelGGL((k_bkry_dots<W, false>), dim3(G3), dim3(BT), 0, ctx->stream, kd);
         IPD_KERNEL_CHECK();                                                       // :81-82, :84-85
@@ -379,35 +352,26 @@ static void pcg_chunk(ipd_amg* h, const double* E, long long lde, int ncol, cons
             if (!act[(size_t)c]) continue;
             const double* S = sc.data() + (size_t)c * SC_N;
             it[c] = (int64_t)S[SC_IT];
-            if (resk) resk[(size_t)c * (size_t)maxit + (size_t)(it[c] - 1)] = S[SC_RES];
+            if (resk) resk[pcg_resk_slot(c, maxit, it[c])] = S[SC_RES];
             act[(size_t)c] = S[SC_STOP] == 0.0;
         }
     }
     if (res)
         for (int c = 0; c < ncol; ++c) res[c] = sc[(size_t)c * SC_N + SC_RES];   // :88
-    hipLaunchKernelGGL(k_blk_out, dim3(grid_io), dim3(256), 0, ctx->stream, N, W, ncol, (const double*)ks->d, D,
-                       lde);
-    IPD_KERNEL_CHECK();
+    block_out(ctx, N, W, ncol, ks->d, D, lde);
     ctx->sync();
 }
 
 // all columns, in chunks of at most BLK_WMAX (device E, guess, D; host outputs)
 static void amg_pcg_multi_dev(ipd_amg* h, const double* E, long long lde, long long nrhs, const double* guess,
                               double tol, long long maxit, double* D, int64_t* it, double* res, double* resk) {
-    for (long long j0 = 0; j0 < nrhs; j0 += BLK_WMAX) {
-        const int ncol = (int)std::min<long long>(BLK_WMAX, nrhs - j0);
-        const double* Ej = E + j0 * lde;
-        const double* gj = guess ? guess + j0 * lde : nullptr;
-        double* Dj = D + j0 * lde;
-        double* rs = res ? res + j0 : nullptr;
-        double* rk = resk ? resk + j0 * maxit : nullptr;
-        switch (block_width(ncol)) {
-            case 1: pcg_chunk<1>(h, Ej, lde, ncol, gj, tol, maxit, Dj, it + j0, rs, rk); break;
-            case 2: pcg_chunk<2>(h, Ej, lde, ncol, gj, tol, maxit, Dj, it + j0, rs, rk); break;
-            case 4: pcg_chunk<4>(h, Ej, lde, ncol, gj, tol, maxit, Dj, it + j0, rs, rk); break;
-            default: pcg_chunk<8>(h, Ej, lde, ncol, gj, tol, maxit, Dj, it + j0, rs, rk); break;
-        }
-    }
+    block_chunks(nrhs, [&](long long j0, int ncol, int W) {
+        with_block_width(W, [&](auto Wc) {
+            pcg_chunk<decltype(Wc)::value>(h, E + j0 * lde, lde, ncol, guess ? guess + j0 * lde : nullptr, tol, maxit,
+                                           D + j0 * lde, it + j0, res ? res + j0 : nullptr,
+                                           resk ? resk + pcg_resk_slot(j0, maxit, 1) : nullptr);   // column j0's
+        });
+    });
 }
 
 static void check_pcg_multi_args(ipd_amg* h, const double* E, long long lde, long long nrhs, const double* D,
@@ -440,20 +404,9 @@ extern "C" int ipd_amg_pcg_multi(ipd_amg* h, const double* E, int64_t lde, int64
         double tol;
         long long maxit;
         pcg_opts_of(o, &tol, &maxit);
-        ipd_ctx* ctx = h->ctx;
-        CallScope scope(ctx);
-        const size_t n = (size_t)lde * (size_t)nrhs;
-        double* dE = ctx->scratch->alloc<double>(n);
-        double* dD = ctx->scratch->alloc<double>(n);
-        double* dg = nullptr;
-        ctx->upload(dE, E, n);
-        if (guess) {
-            dg = ctx->scratch->alloc<double>(n);
-            ctx->upload(dg, guess, n);
-        }
-        // rows N..lde-1 of D are the caller's: carry them through
-        if ((long long)lde > (long long)h->L[1].A.nr) ctx->upload(dD, D, n);
-        amg_pcg_multi_dev(h, dE, lde, nrhs, dg, tol, maxit, dD, it, res, resk);
-        ctx->fetch(dD, D, n);
+        CallScope scope(h->ctx);
+        block_host_call(h, E, lde, nrhs, guess, D, [&](const double* dE, const double* dg, double* dD) {
+            amg_pcg_multi_dev(h, dE, lde, nrhs, dg, tol, maxit, dD, it, res, resk);
+        });
     });
 }

@@ -1,13 +1,13 @@
-// What the single-vector AMG-PCG (ipd_krylov.hip) and its block form (ipd_block_krylov.hip) share: the
-// scalar record of one right-hand side, the fixed-order last-arriver reduction and the pcg_options rule.
+// What the kernels of the single-vector AMG-PCG (ipd_krylov.hip) and of its block form (ipd_block_krylov.hip)
+// share: the fixed-order last-arriver reduction, and the scalar step (ipd_pcg_step.h) and host rules
+// (ipd_krylov_plan.h) that come with it.
 #pragma once
 
 #include "ipd_amg_internal.h"
 
 #include "ipd_cycle_dev.h"
-
-// scalar record of one right-hand side (doubles)
-enum { SC_DNEW, SC_DOLD, SC_ALPHA, SC_BETA, SC_D0, SC_IT, SC_RES, SC_STOP, SC_N };
+#include "ipd_krylov_plan.h"
+#include "ipd_pcg_step.h"
 
 // Wave 0 of every workgroup calls this after thread 0 stored the workgroup's partials; true (in wave
 // 0 only) in the workgroup that arrives last, which then sees every partial and has reset the ticket.
@@ -33,11 +33,6 @@ __device__ __forceinline__ double kry_sum_parts(const double* part, int n, int s
 }
 
 static inline void pcg_opts_of(const ipd_pcg_opts* o, double* tol, long long* maxit) {
-    *tol = 1e-11;   // PCG.m:24-27 defaults
-    *maxit = 10000;
-    if (!o) return;
-    IPD_REQUIRE(o->precd == -1, IPD_E_ARG, "AMG-PCG: pcg_options.precd must be unset (the hierarchy preconditions)");
-    if (o->retol >= 0) *tol = o->retol;
-    if (o->maxit >= 0) *maxit = o->maxit;
+    IPD_REQUIRE(pcg_opts_rule(o, tol, maxit), IPD_E_ARG,
+                "AMG-PCG: pcg_options.precd must be unset (the hierarchy preconditions)");
 }
-

@@ -130,11 +130,7 @@ __global__ __launch_bounds__(BT) void k_kry_dir_spmv(KryDirArgs a) {
     block_totals_to(acc, a.part + b, 0.0, nullptr, &lds);
     if (tid >= 64 || !kry_last_arrival(a.cnt)) return;
     const double pq = kry_sum_parts(a.part, G, 1);
-    if (tid == 0) {
-        const double dn = a.sc[SC_DNEW];
-        a.sc[SC_DOLD] = dn;                                                       // :77
-        a.sc[SC_ALPHA] = dn / pq;                                                 // :78
-    }
+    if (tid == 0) pcg_step_alpha(a.sc, pq);                                       // :77-78
 }
 
 // d += alpha p ; r -= alpha q (both copies of r)                                 PCG.m:79
@@ -177,23 +173,7 @@ __global__ __launch_bounds__(BT) void k_kry_dots(KryDotArgs a) {
     if (tid >= 64 || !kry_last_arrival(a.cnt)) return;
     const double dn = kry_sum_parts(a.part, G, 2);
     const double s_wo = FIRST ? 0.0 : kry_sum_parts(a.part + 1, G, 2);
-    if (tid == 0) {
-        double d0, itv;
-        if (FIRST) {                                                              // PCG.m:70-72
-            d0 = dn;
-            itv = 0.0;
-            a.sc[SC_D0] = d0;
-            a.sc[SC_BETA] = 0.0;
-        } else {
-            d0 = a.sc[SC_D0];
-            a.sc[SC_BETA] = (dn - s_wo) / a.sc[SC_DOLD];                          // flexible :82
-            itv = a.sc[SC_IT] + 1.0;                                              // :84
-        }
-        a.sc[SC_DNEW] = dn;                                                       // :81
-        a.sc[SC_IT] = itv;
-        a.sc[SC_RES] = sqrt(fabs(dn / d0));                                       // :85 / :88
-        a.sc[SC_STOP] = (itv < a.maxit && dn > a.tol2 * d0) ? 0.0 : 1.0;          // :76
-    }
+    if (tid == 0) pcg_step<FIRST>(a.sc, dn, s_wo, a.maxit, a.tol2);               // PCG.m:70-72, :81-85, :76
 }
 
 static KrylovState* krylov_state(ipd_amg* h, int N, int G1, int G3) {
@@ -220,22 +200,35 @@ static KrylovState* krylov_state(ipd_amg* h, int N, int G1, int G3) {
     return h->kry.get();
 }
 
+// What both routes start with: the cycle check, level 1's row walk, the hierarchy's one KrylovState
+struct KrylovCall {
+    LevelDev lv;
+    int staged = 0, G1 = 1, G3 = 1, N = 0;
+    KrylovState* ks = nullptr;
+};
+static KrylovCall krylov_call(ipd_amg* h, PcgRoute route) {
+    const int cyc = h->opts.cycle;
+    IPD_REQUIRE(cyc == 'v' || cyc == 'w', IPD_E_ARG,
+                "AMG-PCG: the hierarchy's cycle must be 'v' or 'w' (any other value applies no correction)");
+    KrylovCall c;
+    IPD_REQUIRE(amg_level1_walk(h, &c.lv, &c.staged, &c.G1), IPD_E_UNSUPPORTED,
+                "AMG-PCG: level 1 is sharded over ranks");
+    c.N = c.lv.N;
+    c.G3 = krylov_g3(c.N, h->ctx->num_cu);
+    c.ks = krylov_state(h, c.N, c.G1, c.G3);
+    c.ks->last_mode = route;
+    return c;
+}
+
 // [d,it,res,resk] = AMG_PCG(h,e,pcg_options) on device vectors; resk: host, maxit slots or NULL
 static void amg_pcg_dev(ipd_amg* h, const double* e, const double* guess, double tol, long long maxit,
                         double* d_out, long long* it_out, double* res_out, double* resk) {
     ipd_ctx* ctx = h->ctx;
-    const int cyc = h->opts.cycle;
-    IPD_REQUIRE(cyc == 'v' || cyc == 'w', IPD_E_ARG,
-                "AMG-PCG: the hierarchy's cycle must be 'v' or 'w' (any other value applies no correction)");
-    LevelDev lv;
-    int staged = 0, G1 = 1;
-    IPD_REQUIRE(amg_level1_walk(h, &lv, &staged, &G1), IPD_E_UNSUPPORTED,
-                "AMG-PCG: level 1 is sharded over ranks");
+    const KrylovCall kc = krylov_call(h, PCG_LAUNCHES);
+    const LevelDev& lv = kc.lv;
+    const int staged = kc.staged, G1 = kc.G1, G3 = kc.G3, N = kc.N;
+    KrylovState* ks = kc.ks;
     const bool pad = lv.S > 0;
-    const int N = lv.N;
-    const int G3 = std::max(1, std::min(ctx->num_cu, cdiv(N, BT)));
-    KrylovState* ks = krylov_state(h, N, G1, G3);
-    ks->last_mode = 0;
     const size_t dyn = staged ? sizeof(double) * (size_t)N : 0;
     double* r1 = h->L[1].r;
     // tickets start at zero on every call (the last arriver resets its own, this covers a launch
@@ -300,7 +293,7 @@ static void amg_pcg_dev(ipd_amg* h, const double* e, const double* guess, double
         IPD_KERNEL_CHECK();                                                       // :81-82, :84-85
         ctx->fetch(ks->sc, sc, SC_N);
         it = (long long)sc[SC_IT];
-        if (resk) resk[it - 1] = sc[SC_RES];
+        if (resk) resk[pcg_resk_slot(0, maxit, it)] = sc[SC_RES];
     }
     IPD_HIP(hipMemcpyAsync(d_out, ks->d, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, ctx->stream));
     if (it_out) *it_out = it;
@@ -313,22 +306,14 @@ static void amg_pcg_dev(ipd_amg* h, const double* e, const double* guess, double
 // PCG_SMALL_MAXIT) it IS amg_pcg_dev.
 void amg_pcg_planned_dev(ipd_amg* h, const double* e, const double* guess, double tol, long long maxit,
                          double* d_out, long long* it_out, double* res_out, double* resk) {
-    if (!amg_pcg_small_ok(h) || maxit > PCG_SMALL_MAXIT || maxit < 0) {
+    if (pcg_route(amg_pcg_small_ok(h), maxit) == PCG_LAUNCHES) {
         amg_pcg_dev(h, e, guess, tol, maxit, d_out, it_out, res_out, resk);
         return;
     }
     ipd_ctx* ctx = h->ctx;
-    const int cyc = h->opts.cycle;
-    IPD_REQUIRE(cyc == 'v' || cyc == 'w', IPD_E_ARG,
-                "AMG-PCG: the hierarchy's cycle must be 'v' or 'w' (any other value applies no correction)");
-    LevelDev lv;
-    int staged = 0, G1 = 1;
-    IPD_REQUIRE(amg_level1_walk(h, &lv, &staged, &G1), IPD_E_UNSUPPORTED,
-                "AMG-PCG: level 1 is sharded over ranks");
-    const int N = lv.N;
-    const int G3 = std::max(1, std::min(ctx->num_cu, cdiv(N, BT)));
-    KrylovState* ks = krylov_state(h, N, G1, G3);   // the launch path's vectors: one state per hierarchy
-    ks->last_mode = 1;
+    const KrylovCall kc = krylov_call(h, PCG_ONE_LAUNCH);   // the launch path's vectors: one state per hierarchy
+    const int N = kc.N;
+    KrylovState* ks = kc.ks;
     if (guess)
         IPD_HIP(hipMemcpyAsync(ks->d, guess, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, ctx->stream));
     else
@@ -359,23 +344,13 @@ extern "C" int ipd_amg_pcg_mode(const ipd_amg* h, int32_t* mode) {
     });
 }
 
-extern "C" int ipd_amg_pcg_planned_dev(ipd_amg* h, const double* e_dev, const double* guess_dev,
-                                       const ipd_pcg_opts* o, double* d_dev, int64_t* it, double* res,
-                                       double* resk) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h && e_dev && d_dev, IPD_E_ARG, "NULL argument");
-        double tol;
-        long long maxit;
-        pcg_opts_of(o, &tol, &maxit);
-        CallScope scope(h->ctx);
-        long long its = 0;
-        amg_pcg_planned_dev(h, e_dev, guess_dev, tol, maxit, d_dev, &its, res, resk);
-        if (it) *it = its;
-    });
-}
+typedef void (*PcgDevFn)(ipd_amg*, const double*, const double*, double, long long, double*, long long*, double*,
+                         double*);
 
-extern "C" int ipd_amg_pcg_planned(ipd_amg* h, const double* e, const double* guess, const ipd_pcg_opts* o,
-                                   double* d, int64_t* it, double* res, double* resk) {
+// a single-vector entry around `solve` (amg_pcg_dev or amg_pcg_planned_dev): device vectors as they are, host
+// vectors through the call's scratch
+static int pcg_entry(PcgDevFn solve, bool host, ipd_amg* h, const double* e, const double* guess,
+                     const ipd_pcg_opts* o, double* d, int64_t* it, double* res, double* resk) {
     return ipd_guard([&] {
         IPD_REQUIRE(h && e && d, IPD_E_ARG, "NULL argument");
         double tol;
@@ -384,57 +359,44 @@ extern "C" int ipd_amg_pcg_planned(ipd_amg* h, const double* e, const double* gu
         ipd_ctx* ctx = h->ctx;
         CallScope scope(ctx);
         const size_t N = (size_t)h->L[1].A.nr;
-        double* de = ctx->scratch->alloc<double>(N);
-        double* dd = ctx->scratch->alloc<double>(N);
-        double* dg = nullptr;
-        ctx->upload(de, e, N);
-        if (guess) {
-            dg = ctx->scratch->alloc<double>(N);
-            ctx->upload(dg, guess, N);
+        const double *de = e, *dg = guess;
+        double* dd = d;
+        if (host) {
+            double* up = ctx->scratch->alloc<double>(N);
+            dd = ctx->scratch->alloc<double>(N);
+            ctx->upload(up, e, N);
+            de = up;
+            if (guess) {
+                up = ctx->scratch->alloc<double>(N);
+                ctx->upload(up, guess, N);
+                dg = up;
+            }
         }
         long long its = 0;
-        amg_pcg_planned_dev(h, de, dg, tol, maxit, dd, &its, res, resk);
+        solve(h, de, dg, tol, maxit, dd, &its, res, resk);
         if (it) *it = its;
-        ctx->fetch(dd, d, N);
+        if (host) ctx->fetch(dd, d, N);
     });
+}
+
+extern "C" int ipd_amg_pcg_planned_dev(ipd_amg* h, const double* e_dev, const double* guess_dev,
+                                       const ipd_pcg_opts* o, double* d_dev, int64_t* it, double* res,
+                                       double* resk) {
+    return pcg_entry(amg_pcg_planned_dev, false, h, e_dev, guess_dev, o, d_dev, it, res, resk);
+}
+
+extern "C" int ipd_amg_pcg_planned(ipd_amg* h, const double* e, const double* guess, const ipd_pcg_opts* o,
+                                   double* d, int64_t* it, double* res, double* resk) {
+    return pcg_entry(amg_pcg_planned_dev, true, h, e, guess, o, d, it, res, resk);
 }
 
 extern "C" int ipd_amg_pcg_dev(ipd_amg* h, const double* e_dev, const double* guess_dev,
                                const ipd_pcg_opts* o, double* d_dev, int64_t* it, double* res,
                                double* resk) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h && e_dev && d_dev, IPD_E_ARG, "NULL argument");
-        double tol;
-        long long maxit;
-        pcg_opts_of(o, &tol, &maxit);
-        CallScope scope(h->ctx);
-        long long its = 0;
-        amg_pcg_dev(h, e_dev, guess_dev, tol, maxit, d_dev, &its, res, resk);
-        if (it) *it = its;
-    });
+    return pcg_entry(amg_pcg_dev, false, h, e_dev, guess_dev, o, d_dev, it, res, resk);
 }
 
 extern "C" int ipd_amg_pcg(ipd_amg* h, const double* e, const double* guess, const ipd_pcg_opts* o,
                            double* d, int64_t* it, double* res, double* resk) {
-    return ipd_guard([&] {
-        IPD_REQUIRE(h && e && d, IPD_E_ARG, "NULL argument");
-        double tol;
-        long long maxit;
-        pcg_opts_of(o, &tol, &maxit);
-        ipd_ctx* ctx = h->ctx;
-        CallScope scope(ctx);
-        const size_t N = (size_t)h->L[1].A.nr;
-        double* de = ctx->scratch->alloc<double>(N);
-        double* dd = ctx->scratch->alloc<double>(N);
-        double* dg = nullptr;
-        ctx->upload(de, e, N);
-        if (guess) {
-            dg = ctx->scratch->alloc<double>(N);
-            ctx->upload(dg, guess, N);
-        }
-        long long its = 0;
-        amg_pcg_dev(h, de, dg, tol, maxit, dd, &its, res, resk);
-        if (it) *it = its;
-        ctx->fetch(dd, d, N);
-    });
+    return pcg_entry(amg_pcg_dev, true, h, e, guess, o, d, it, res, resk);
 }

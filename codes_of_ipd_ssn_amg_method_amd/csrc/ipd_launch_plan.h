@@ -1,4 +1,4 @@
-// Planner of the multi-launch path (amg_cycle, launch_top, the block solve: ipd_cycle.hip, ipd_block.h): from
+// Planner of the multi-launch path (amg_cycle, launch_top, the block solve: ipd_cycle.hip, ipd_block.hip): from
 // the shapes of the levels and of their transfers, the device's CU count and three switches it decides, once per
 // hierarchy, how every level's phases run -- lanes per row and grids of the row walks, the padded copy, LDS
 // staging, which phases are queued into the fused single-workgroup program and which are launches of their own,

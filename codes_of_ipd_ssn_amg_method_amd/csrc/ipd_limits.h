@@ -69,6 +69,11 @@ static constexpr size_t SOL_HEAD = 12592;
 // then cannot outlast ~0.3 s; a call with a larger maxit runs as launches
 static constexpr int PCG_SMALL_MAXIT = 1000;
 
+// widest block of right-hand sides (ipd_block.hip, ipd_block_krylov.hip; chunking: ipd_krylov_plan.h).
+// W = 16 was dropped: its smoother and loop-top instantiations spill (VGPRs and SGPRs past the 256 / 106
+// a 512-thread workgroup gets; -Rpass-analysis=kernel-resource-usage), W <= 8 do not
+static constexpr int BLK_WMAX = 8;
+
 // dense thread-per-row levels (SolveLevel::blk_dense, ipd_cycle.hip): 24 values per lane: the register
 // budget of the tail (the resident kernels' worker paths set the kernels' allocation; the tail must stay
 // below it) -- the same storage serves the lane-map entries.

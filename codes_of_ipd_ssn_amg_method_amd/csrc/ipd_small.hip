@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "ipd_interp.h"   // and ipd_cycle_pcg.h
+#include "ipd_pcg_step.h"
 
 // out[0] = it, out[1] = rel_res, out[2] = res0; rel_resk at out[4 ..], rhok at out[4+maxit+2 ..]
 // fixed_cycles > 0: run exactly that many loop bodies without the stopping rules (bench hook)
@@ -103,7 +104,8 @@ __global__ __launch_bounds__(BT) void k_solve_small(const SolveDesc* __restrict_
 // whole AMG-PCG solve in ONE workgroup (ipd_amg_pcg_planned)
 // ---------------------------------------------------------------------------
 // The loop of ipd_krylov.hip (PCG.m:68-87, flexible beta) run by the workgroup that k_solve_small is, on
-// the same SolveDesc / LDS image, with M(r) = sol_cycle(c) from a zero guess: one launch and one
+// the same SolveDesc / LDS image, with M(r) = sol_cycle(c) from a zero guess, the scalar rules those of
+// ipd_pcg_step.h over values in registers: one launch and one
 // read-back per solve.  The PCG's own vectors (d, r, p, q, w_old) are the hierarchy's krylov_state
 // vectors in global memory (<= 8 KB each, L2-resident): the image's LDS budget is planned to the byte
 // for the stationary solve, and five more level-1 vectors would push level 1 of the larger mode-1
@@ -204,9 +206,9 @@ __global__ __launch_bounds__(BT) void k_pcg_small(const SolveDesc* __restrict__ 
     double delta = block_sum(acc, red);                                       // :70
     const double delta0 = delta;
     double beta = 0.0;
-    double res = sqrt(fabs(delta / delta0));
+    double res = pcg_res(delta, delta0);
     int it = 0;
-    while (it < a.maxit && delta > a.tol2 * delta0) {                         // :76
+    while (it < a.maxit && delta > a.tol2 * delta0) {   // :76, restates pcg_step's test (ipd_pcg_step.h) on an int count
         const double pq = block_sum(pcgs_dir_spmv(c, a, w, beta, it > 0), red);   // :77, :83
         const double alpha = delta / pq;                                      // :78
         for (int i = threadIdx.x; i < N; i += BT) {                           // :79
@@ -226,10 +228,10 @@ __global__ __launch_bounds__(BT) void k_pcg_small(const SolveDesc* __restrict__ 
         }
         const double dn = block_sum(rw, red);                                 // :81
         const double s_wo = block_sum(rwo, red);
-        beta = (dn - s_wo) / delta;                                           // flexible :82
+        beta = pcg_beta(dn, s_wo, delta);                                     // flexible :82
         delta = dn;
         ++it;                                                                 // :84
-        res = sqrt(fabs(dn / delta0));                                        // :85
+        res = pcg_res(dn, delta0);                                            // :85
         if (threadIdx.x == 0) a.out[4 + it - 1] = res;
     }
     if (threadIdx.x == 0) {

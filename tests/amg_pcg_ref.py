@@ -18,14 +18,17 @@ def cycle_operator(h, amg_options):
     raise ValueError("AMG-PCG needs cycle 'v' or 'w'")
 
 
-def amg_pcg(A, e, M, retol=1e-11, maxit=10000, guess=None):
-    """Returns d, it, res, resk (resk has `it` entries)."""
+def amg_pcg(A, e, M, retol=1e-11, maxit=10000, guess=None, trace=None):
+    """Returns d, it, res, resk (resk has `it` entries).  trace: a list that receives delta_0 and then, per
+    iteration, the inner products and scalars (pq, rw, rwo, alpha, beta) as Python floats."""
     e = np.asarray(e, float)
     d = np.zeros_like(e) if guess is None else np.array(guess, float)
     r = e - A @ d
     w = M(r)
     delta_new = float(r @ w)
     delta_0 = delta_new
+    if trace is not None:
+        trace.append(delta_0)
     p = w
     it = 0
     resk = []
@@ -33,13 +36,17 @@ def amg_pcg(A, e, M, retol=1e-11, maxit=10000, guess=None):
         while it < maxit and delta_new > retol ** 2 * delta_0:
             delta_old = delta_new
             q = A @ p
-            alpha = delta_old / float(q @ p)
+            pq = float(q @ p)
+            alpha = delta_old / pq
             d = d + alpha * p
             r = r - alpha * q
             w_old = w
             w = M(r)
             delta_new = float(r @ w)
-            beta = (delta_new - float(r @ w_old)) / delta_old
+            rwo = float(r @ w_old)
+            beta = (delta_new - rwo) / delta_old
+            if trace is not None:
+                trace.append(dict(pq=pq, rw=delta_new, rwo=rwo, alpha=alpha, beta=beta))
             p = w + beta * p
             it += 1
             resk.append(math.sqrt(abs(delta_new / delta_0)))

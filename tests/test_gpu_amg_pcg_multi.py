@@ -337,6 +337,27 @@ def test_edges_and_side_effects(ipd):
     assert np.array_equal(sm0[0], sm1[0]) and np.array_equal(sm0[1], sm1[1])
     assert all(np.array_equal(a, b) for a, b in zip(sm0[3], sm1[3]))
     assert np.array_equal(p0[0], p1[0]) and p0[1] == p1[1] and np.array_equal(p0[3], p1[3])
+    # the two calls share the hierarchy's work blocks, which are made for the widest block met so far: on a
+    # fresh hierarchy (same stream, so the same hierarchy) a call whose blocks were made for a narrower width
+    # by the other entry, and a call narrower than the blocks it finds, give the bits of the calls above
+    same_multi = lambda a, b: (np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and
+                               all(np.array_equal(u, v) for u, v in zip(a[3], b[3])))
+    E9, G9 = np.column_stack([E, 0.5 * E, -E]), np.column_stack([G, G, G])
+    h3 = ipd.AMGHierarchy(A, o, ipd.MatlabRand())
+    sm_w1 = h3.solve_multi(E[:, :1], G[:, :1])                     # blocks made for width 1
+    assert same_bits(h3.pcg_multi(E, po), out)                     # width 4 on blocks made for 1
+    assert same_multi(h3.solve_multi(E[:, :1], G[:, :1]), sm_w1)   # width 1 on blocks made for 4
+    pm_w2 = h3.pcg_multi(E[:, :2], dict(po, guess=G[:, :2]))       # width 2 on blocks (both kinds) made for 4
+    sm9 = h3.solve_multi(E9, G9)                                   # chunks of width 8 then 1: blocks grow to 8
+    pm9 = h3.pcg_multi(E9, dict(po, guess=G9))                     # the PCG's own vectors grow from 4 to 8
+    assert same_bits(h3.pcg_multi(E, po), out) and same_multi(h3.solve_multi(E, G), sm0)   # 4 on 8
+    h3.close()
+    h4 = ipd.AMGHierarchy(A, o, ipd.MatlabRand())
+    assert same_bits(h4.pcg_multi(E[:, :2], dict(po, guess=G[:, :2])), pm_w2)   # first call: made for width 2
+    assert same_multi(h4.solve_multi(E, G), sm0)                   # width 4 on blocks the PCG made for 2
+    assert same_bits(h4.pcg_multi(E9, dict(po, guess=G9)), pm9)    # 8 then 1 on blocks made for 4
+    assert same_multi(h4.solve_multi(E9, G9), sm9)                 # ... and on blocks the PCG made for 8
+    h4.close()
     # IPD_E_ARG cases
     Ef = np.asfortranarray(E)
     Df = np.empty((N, 3), order="F")

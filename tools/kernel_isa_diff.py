@@ -6,7 +6,10 @@ and file offsets are not compared, so a kernel may sit in another object, or at 
 FILE: object files or libipdamg.so.  Exit status 1 when a kernel is missing on one side or differs.
 --rename-b: a kernel of b whose demangled name contains OLD is paired with the kernel of a that has NEW there (a type
 that became a template instantiation changes the mangled name and nothing else); kernels of b that stay unpaired
-after the renames are listed as ONLY IN b and counted apart with --allow-new."""
+after the renames are listed as ONLY IN b and counted apart with --allow-new.
+--distinct: a template that several units instantiate has one body per unit; compare the DISTINCT bodies (and figures)
+of each kernel instead of the sorted lists, so that a second copy that went away is no difference, and report the
+copies per side (x2 -> x1) and how many kernels lost or gained copies."""
 import argparse
 import os
 import re
@@ -78,6 +81,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--rename-b", nargs="*", default=[], metavar="OLD=NEW")
     ap.add_argument("--allow-new", action="store_true", help="kernels only in b are listed but are no failure")
+    ap.add_argument("--distinct", action="store_true", help="compare each kernel's distinct bodies, report the copies")
     args = ap.parse_args()
     ka, kb = kernel_symbols(args.a), kernel_symbols(args.b)
     ca, cb = kernel_code(args.a, ka), kernel_code(args.b, kb)
@@ -99,7 +103,16 @@ def main():
     cb = {renamed(names[s]): c for s, c in cb.items()}
     ka, kb = set(key_a), set(key_b)
     names = {k: k for k in ka | kb}
-    lines, bad, new = [], 0, 0
+    lines, bad, new, recount = [], 0, 0, 0
+
+    def uniq(seq):   # sorted distinct entries (bodies are lists)
+        out = []
+        for x in sorted(seq or []):
+            if not out or out[-1] != x:
+                out.append(x)
+        return out
+
+    same = (lambda x, y: uniq(x) == uniq(y)) if args.distinct else (lambda x, y: x == y)
     for sym in sorted(ka | kb, key=lambda s: names[s]):
         dem = short(names[sym])
         if sym in ka and sym in kb and (sym not in ca or sym not in cb):
@@ -114,9 +127,13 @@ def main():
                 bad += 1
             continue
         na, nb = [len(b) for b in ca[sym]], [len(b) for b in cb[sym]]
-        if ca[sym] == cb[sym] and min(na) > 0 and ra.get(dem) == rb.get(dem):
-            lines.append("%-72s identical  %6d instructions  %s%s" % (dem[-72:], na[0], ra[dem][0],
-                                                                      "  (x%d)" % len(na) if len(na) > 1 else ""))
+        if same(ca[sym], cb[sym]) and min(na) > 0 and same(ra.get(dem), rb.get(dem)):
+            if len(na) != len(nb):   # (only with --distinct)
+                recount += 1
+                copies = "  (x%d -> x%d, %d distinct -> %d)" % (len(na), len(nb), len(uniq(ca[sym])), len(uniq(cb[sym])))
+            else:
+                copies = "  (x%d)" % len(na) if len(na) > 1 else ""
+            lines.append("%-72s identical  %6d instructions  %s%s" % (dem[-72:], na[0], ra[dem][0], copies))
         else:
             bad += 1
             lines.append("%-72s DIFFERS    %s -> %s instructions (%+d)" % (dem[-72:], na, nb, sum(nb) - sum(na)))
@@ -125,7 +142,11 @@ def main():
     head = ["a: " + " ".join(args.a), "b: " + " ".join(args.b),
             "renames of b: " + (" ".join(args.rename_b) or "none"),
             "%d kernels in a, %d in b, %d in both; %d missing or different; %d only in b and allowed" %
-            (len(ka), len(kb), len(ka & kb), bad, new), ""]
+            (len(ka), len(kb), len(ka & kb), bad, new)]
+    if args.distinct:
+        head.append("distinct bodies compared: %d bodies in a, %d in b; %d kernels with another number of copies" %
+                    (sum(len(c) for c in ca.values()), sum(len(c) for c in cb.values()), recount))
+    head.append("")
     text = "\n".join(head + lines) + "\n"
     if args.out:
         open(args.out, "w").write(text)
