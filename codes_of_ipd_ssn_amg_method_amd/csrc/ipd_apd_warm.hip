@@ -5,6 +5,7 @@
 #pragma clang fp contract(off)
 
 #include "ipd_apd_state.h"
+#include "ipd_kkt.h"
 
 namespace {
 

@@ -11,6 +11,7 @@
 #include <limits>
 
 #include "ipd_apd_state.h"
+#include "ipd_kkt.h"
 
 static_assert(MK == IPD_APD_MERIT_STEPS, "ipd_apd_merit takes MK steps");
 
@@ -356,7 +357,7 @@ void apd_create_common(ipd_ctx* ctx, const ipd_apd_data* d, const ApdCostFill* f
         if (d->phi) ctx->upload(h->phi, d->phi, mn);
         h->tmask = A.alloc<double>((size_t)h->M);
         h->phi_l = A.alloc<double>((size_t)h->M);
-        h->phi_part = A.alloc<double>(1024);
+        h->phi_part = A.alloc<double>(PHI_PARTS_MAX);
     } else if (d->gama) {
         h->gama = A.alloc<double>(mn);
         ctx->upload(h->gama, d->gama, mn);

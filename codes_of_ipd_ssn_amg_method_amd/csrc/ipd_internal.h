@@ -152,7 +152,7 @@ struct ipd_ctx {
     // entries of P, Pt*A and Ac of the last hierarchy's level k (amg_transfer's lazy counts: the kernel-choice
     // heuristics of the next hierarchy's products run on these estimates; 0 = none yet)
     int xfer_hint[XFER_HINT_LEVELS][4] = {};   // [3]: longest row of P'A
-    void* asat_agg = nullptr;      // k_asat_small's chained-scan words (ipd_kkt.hip)
+    void* asat_agg = nullptr;      // k_asat_small's chained-scan words (ipd_asat.hip)
     // Zero pool: temporaries that must start out as zeros (transpose bitmaps, dense operand blocks, flags) are
     // bumped out of one block that a single memset clears again at the start of the next hierarchy build --
     // one fill per setup where there were fourteen.  zalloc'd memory dies when the function that took it returns
@@ -607,20 +607,4 @@ void csr_expand_dense(ipd_ctx* ctx, const Csr& A, double* dense, int ld);  // de
 void dense_rowcount(ipd_ctx* ctx, int nr, int nc, int ld, const double* dense, int* rowcnt, const ScanTail& st);
 void dense_compact(ipd_ctx* ctx, int nr, int nc, int ld, const double* dense, const Csr& out);
 void csr_copy(ipd_ctx* ctx, Arena& dst, const Csr& A, Csr* out);
-void csr_drop_zeros(ipd_ctx* ctx, Arena& dst, const Csr& A, Csr* out);  // ipd_kkt.hip
-
-// ipd_kkt.hip
-void kkt_ax(ipd_ctx* ctx, const double* x, const double* p, const double* q, int m, int n,
-            double* y);
-void kkt_aty(ipd_ctx* ctx, const double* y, const double* p, const double* q, int m, int n,
-             double* z);
-void kkt_asat(ipd_ctx* ctx, Arena& dst, const uint8_t* s, const double* p, const double* q,
-              int m, int n, Csr* H);
-void kkt_inv_aat(ipd_ctx* ctx, const double* x, const double* p, const double* q, int m, int n,
-                 double sg1, double sg2, double* y);
-void kkt_inv_hht(ipd_ctx* ctx, const double* v, const double* p, const double* q, int m, int n,
-                 double sg, const double* phi, double* y);
-void kkt_inv_hht_pre(ipd_ctx* ctx, const double* v, const double* p, const double* q, int m, int n,
-                     double sg, const double* l, const double* part, int npart, double* y);
-int kkt_phi_consts(ipd_ctx* ctx, const double* phi, const double* p, const double* q, int m, int n,
-                   double* l, double* part);
+void csr_drop_zeros(ipd_ctx* ctx, Arena& dst, const Csr& A, Csr* out);

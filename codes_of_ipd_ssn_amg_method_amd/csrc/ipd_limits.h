@@ -54,6 +54,21 @@ static constexpr int XFER_HINT_LEVELS = 40;                  // levels ipd_ctx::
 static constexpr int IPD_APD_SIDE_MAX = 16384;
 static constexpr int IPD_COST_DIM_MAX = 16;
 
+// the KKT operators (ipd_kkt.hip, ipd_asat.hip; their host rules: ipd_kkt_plan.h)
+static constexpr int AX_TR = 256;         // Ax: tile rows
+static constexpr int AX_TC = 16;          // Ax: tile columns
+static constexpr int AX_LD = AX_TR + 16;  // Ax: padded column stride of the LDS tile (bank spread)
+static constexpr int ATY_TC = 16;         // Aty: columns per workgroup
+static constexpr int ASAT_TILE = 64;      // ASAt: edge of a mask tile (one 64-bit word per row or column of it)
+static constexpr int PHI_PARTS_MAX = 1024;   // invHHt: most partial sums of |phi|^2 (k_inv_hht_combine's one workgroup adds them)
+// ASAt's one-launch route (k_asat_small): mask words a thread holds for its row, workgroups the chained scan
+// can look back over (one lane per predecessor), the largest entry count of the previous call that takes it,
+// and the count it posts when a spin gave up
+static constexpr int ASAT_SMALL_WORDS = 16;
+static constexpr int ASAT_SMALL_WGS = 64;
+static constexpr int ASAT_SMALL_HINT_MAX = 65536;
+static constexpr int ASAT_GAVE_UP = 2147483647;
+
 // levels a single-workgroup image (SolveDesc) holds
 static constexpr int SOLVE_ML = 24;
 // An LDS image (ipd_level_plan.h): the planner admits levels while the predicted dynamic LDS stays within the

@@ -6,6 +6,7 @@
 #include <thread>
 
 #include "ipd_hybrid_state.h"
+#include "ipd_kkt.h"
 
 #include <algorithm>
 

@@ -106,6 +106,51 @@ void csr_copy(ipd_ctx* ctx, Arena& dst, const Csr& A, Csr* out) {
     *out = m;
 }
 
+// "drop exact zeros" (rare paths: ASAt's squares that underflow, ipd_asat.hip; the coarsening, ipd_coarsen.hip)
+__global__ __launch_bounds__(256) void k_count_nz(int nr, const int* __restrict__ rp,
+                                                  const double* __restrict__ va,
+                                                  int* __restrict__ cnt) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nr) return;
+    int c = 0;
+    for (int e = rp[r]; e < rp[r + 1]; ++e) c += (va[e] != 0.0);
+    cnt[r] = c;
+}
+__global__ __launch_bounds__(256) void k_copy_nz(int nr, const int* __restrict__ rp,
+                                                 const int* __restrict__ ci,
+                                                 const double* __restrict__ va,
+                                                 const int* __restrict__ orp, int* __restrict__ oci,
+                                                 double* __restrict__ ova) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nr) return;
+    int pos = orp[r];
+    for (int e = rp[r]; e < rp[r + 1]; ++e)
+        if (va[e] != 0.0) {
+            oci[pos] = ci[e];
+            ova[pos] = va[e];
+            ++pos;
+        }
+}
+
+void csr_drop_zeros(ipd_ctx* ctx, Arena& dst, const Csr& A, Csr* out) {
+    Arena& tmp = *ctx->scratch;
+    int* cnt = tmp.alloc<int>((size_t)A.nr + 1);
+    Csr o;
+    o.nr = A.nr;
+    o.nc = A.nc;
+    o.rp = dst.alloc<int>((size_t)A.nr + 1);
+    hipLaunchKernelGGL(k_count_nz, dim3(cdiv(std::max(A.nr, 1), 256)), dim3(256), 0, ctx->stream,
+                       A.nr, A.rp, A.va, cnt);
+    IPD_KERNEL_CHECK();
+    o.nnz = exclusive_scan_total(ctx, cnt, o.rp, A.nr);
+    o.ci = dst.alloc<int>((size_t)o.nnz);
+    o.va = dst.alloc<double>((size_t)o.nnz);
+    hipLaunchKernelGGL(k_copy_nz, dim3(cdiv(std::max(A.nr, 1), 256)), dim3(256), 0, ctx->stream,
+                       A.nr, A.rp, A.ci, A.va, o.rp, o.ci, o.va);
+    IPD_KERNEL_CHECK();
+    *out = o;
+}
+
 // ---------------------------------------------------------------------------
 // deterministic transpose through a per-column row bitmap
 // ---------------------------------------------------------------------------

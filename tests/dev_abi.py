@@ -126,7 +126,7 @@ def mask_bytes(m, n, density, flavour, seed=0):
 
 
 def bytes_to_bits_model(x):
-    """ipd_kkt.hip's bytes_to_bits on one 64-bit word, in Python integers."""
+    """ipd_asat.hip's bytes_to_bits on one 64-bit word, in Python integers."""
     x |= x >> 4
     x |= x >> 2
     x |= x >> 1

@@ -92,7 +92,7 @@ def test_bytes_to_bits_maps_every_nonzero_byte_to_one():
         for lane in range(8):
             assert D.bytes_to_bits_model(b << (8 * lane)) == ((1 << lane) if b else 0), (b, lane)
     assert D.bytes_to_bits_model(0x80FF021001000200) == 0b11111010
-    with open(os.path.join(D.CSRC, "ipd_kkt.hip")) as fh:
+    with open(os.path.join(D.CSRC, "ipd_asat.hip")) as fh:
         src = fh.read()
     assert "x &= 0x0101010101010101ull;" in src and "(x * 0x0102040810204080ull) >> 56" in src
 
@@ -119,7 +119,7 @@ def test_spmv_matrices_take_the_intended_branch_and_exceed_the_cap():
 
 
 def test_ax_shapes_straddle_the_tile_edges():
-    with open(os.path.join(D.CSRC, "ipd_kkt.hip")) as fh:
+    with open(os.path.join(D.CSRC, "ipd_limits.h")) as fh:
         src = fh.read()
     assert "AX_TR = 256;" in src and "AX_TC = 16;" in src and "ATY_TC = 16;" in src
     ms, ns = {m for m, n in D.AX_SHAPES}, {n for m, n in D.AX_SHAPES}
