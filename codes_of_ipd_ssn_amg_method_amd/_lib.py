@@ -86,6 +86,12 @@ class ipd_dual_stats(Structure):
                 ("imin", c_int64), ("jmin", c_int64), ("nneg", c_int64), ("fval", c_double), ("gap", c_double)]
 
 
+class ipd_round_stats(Structure):
+    _fields_ = [("fval", c_double), ("fs", c_double), ("cc", c_double), ("theta", c_double), ("t", c_double),
+                ("se", c_double), ("sf", c_double), ("ms", c_double), ("cp", c_double), ("viol_in", c_double),
+                ("dropped", c_double), ("ndropped", c_int64), ("ok", c_int32)]
+
+
 class ipd_cost_spec(Structure):
     _fields_ = [("metric", c_int32), ("dim", c_int32), ("m", c_int64), ("n", c_int64),
                 ("xs", POINTER(c_double)), ("ys", POINTER(c_double)), ("scale", c_int32)]
@@ -145,6 +151,9 @@ lib.ipd_apd_plan_apply.argtypes = [c_void_p, c_double, c_int32, c_int32, c_int32
 lib.ipd_apd_plan_apply_dev.argtypes = lib.ipd_apd_plan_apply.argtypes
 lib.ipd_apd_dual.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_dual_dev.argtypes = lib.ipd_apd_dual.argtypes
+lib.ipd_apd_round.argtypes = [c_void_p, c_double, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_round_dev.argtypes = [c_void_p, c_double, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]
 lib.ipd_cost_points_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_create_points.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_get_cost.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -184,6 +193,7 @@ EXPORTS = [
     "ipd_apd_plan", "ipd_apd_plan_dev", "ipd_apd_set_plan",
     "ipd_apd_plan_apply", "ipd_apd_plan_apply_dev",
     "ipd_apd_dual", "ipd_apd_dual_dev",
+    "ipd_apd_round", "ipd_apd_round_dev",
     "ipd_cost_points_dev", "ipd_apd_create_points", "ipd_apd_get_cost",
     "ipd_apd_create_points_free", "ipd_apd_cost_info",
     "ipd_apd_get_w", "ipd_apd_eval_trial", "ipd_apd_merit", "ipd_apd_end",

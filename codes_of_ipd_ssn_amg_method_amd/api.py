@@ -1082,6 +1082,83 @@ class APDWorkspace:
         res["side"] = side
         return res
 
+    # -- the primal certificate ------------------------------------------------
+    @staticmethod
+    def _round_stats(st: L.ipd_round_stats) -> dict:
+        return dict(fval=st.fval, fs=st.fs, cc=st.cc, theta=st.theta, t=st.t, se=st.se, sf=st.sf, ms=st.ms, cp=st.cp,
+                    viol_in=st.viol_in, dropped=st.dropped, ndropped=int(st.ndropped), ok=int(st.ok))
+
+    def _round_args(self, tol, side):
+        if side not in (0, 1):
+            raise ValueError("side must be 0 (rows scaled first) or 1 (columns scaled first)")
+        if not tol >= 0:
+            raise ValueError("tol must be >= 0")
+
+    def round_plan(self, tol: float = 0.0, side: int = 0, install: bool = False, vectors: bool = True) -> dict:
+        """The iterate rounded onto the feasible set, where it lives (``ipd_apd_round``): the entries with
+        ``abs(x) <= tol`` and the negative ones dropped, rows and columns scaled down to their marginals (``side=0``:
+        rows first), the missing mass put back as a rank-one term -- ``X^ = theta*(rho_i x+_ij kappa_j) + t*e_i f_j``
+        -- with its exact cost ``fval = <c, X^>``, a certified upper bound on ``f*`` when ``ok``.  Returns
+        ``dict(fval, fs, cc, theta, t, se, sf, ms, cp, viol_in, dropped, ndropped, ok)`` and with ``vectors`` the
+        factors ``rho`` (m), ``kappa`` (n), ``e`` (m), ``f`` (n).  ``install=True`` makes ``X^`` the state (class 2:
+        with its slacks; ``lk``, ``bk`` and the histories stay) and raises ``IpdError`` (``IPD_E_NUMERIC``) when
+        ``ok == 0``.  Nothing mn-sized crosses to the host."""
+        self._round_args(tol, side)
+        vec = [np.empty(k) for k in (self.m, self.n, self.m, self.n)] if vectors else [None] * 4
+        st = L.ipd_round_stats()
+        check(lib.ipd_apd_round(self.handle, c_double(tol), c_int32(side), c_int32(1 if install else 0),
+                                *[v.ctypes.data if v is not None else None for v in vec], byref(st)))
+        res = self._round_stats(st)
+        if vectors:
+            res.update(rho=vec[0], kappa=vec[1], e=vec[2], f=vec[3])
+        return res
+
+    def round_plan_dev(self, tol: float = 0.0, side: int = 0, install: bool = False, rho=None, kappa=None, e=None,
+                       f=None, x_out=None) -> dict:
+        """The same on caller-owned device arrays (``ipd_apd_round_dev``): ``rho``, ``e`` m float64, ``kappa``,
+        ``f`` n, ``x_out`` mn (receives ``X^`` in full, column-major), each may be None -- torch tensors on the
+        workspace's GPU, ``DeviceBuffer`` objects, or ``(pointer, entries)`` pairs, as ``dual_dev`` takes them.
+        Returns the statistics."""
+        self._round_args(tol, side)
+
+        def ptr_of(a, need, name):
+            if a is None:
+                return None
+            if isinstance(a, tuple):
+                p, cnt = c_void_p(int(a[0])), int(a[1])
+            elif isinstance(a, L.DeviceBuffer):
+                p, cnt = a.ptr, a.nbytes // 8
+            elif hasattr(a, "data_ptr"):
+                if a.element_size() != 8 or not a.is_contiguous():
+                    raise ValueError("round_plan_dev: tensors must be contiguous float64")
+                p, cnt = c_void_p(a.data_ptr()), a.numel()
+            else:
+                raise ValueError(f"round_plan_dev: {name} must be a tensor, a DeviceBuffer or a (pointer, entries) "
+                                 "pair")
+            if cnt < need:
+                raise ValueError(f"round_plan_dev: {name} must hold {need} entries")
+            return p
+        ptrs = [ptr_of(rho, self.m, "rho"), ptr_of(kappa, self.n, "kappa"), ptr_of(e, self.m, "e"),
+                ptr_of(f, self.n, "f"), ptr_of(x_out, self.m * self.n, "x_out")]
+        st = L.ipd_round_stats()
+        check(lib.ipd_apd_round_dev(self.handle, c_double(tol), c_int32(side), c_int32(1 if install else 0), *ptrs,
+                                    byref(st)))
+        return self._round_stats(st)
+
+    def bracket(self, tol: float = 0.0) -> dict:
+        """``lower <= f* <= upper`` with nothing mn-sized crossing to the host: ``lower`` is ``certificate()``,
+        ``upper`` the better of ``round_plan(tol, side=0)`` and ``round_plan(tol, side=1)`` (``ok`` first, then the
+        smaller ``fval``), marked with its ``side``, and ``gap = upper["fval"] - lower["dual"]``.  The workspace is
+        only read.  Not for finite ``gama``."""
+        if self._finite_gama:
+            raise ValueError("bracket: rounding does not keep x <= gama; finite gama is not supported")
+        lower = self.certificate()
+        both = [self.round_plan(tol, side=s) for s in (0, 1)]
+        side = min((0, 1), key=lambda s: (not both[s]["ok"], both[s]["fval"]))
+        upper = both[side]
+        upper["side"] = side
+        return dict(lower=lower, upper=upper, gap=upper["fval"] - lower["dual"])
+
     # -- the loop -------------------------------------------------------------
     def options(self, **kw) -> L.ipd_apd_opts:
         o = L.ipd_apd_opts()
@@ -1238,8 +1315,10 @@ def warmup_class2(c, r, l, p, q, mu, phi, res=None, maxit=None):
 
 
 def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool = False,
-                plan_tol=None, certificate: bool = False) -> dict:
+                plan_tol=None, certificate: bool = False, bracket: bool = False) -> dict:
     try:
+        if bracket and ws._finite_gama:     # before the run, not after it
+            raise ValueError("bracket: rounding does not keep x <= gama; finite gama is not supported")
         if warm is not None:
             ws.warmup(*warm)
         out = ws.run(amg_opts, rng, krylov=krylov, **opts)
@@ -1251,6 +1330,8 @@ def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool 
             out["plan"], out["plan_stats"], out["plan_ax"] = ws.plan(plan_tol, stats=True)
         if certificate:
             out["certificate"] = ws.certificate()
+        if bracket:
+            out["bracket"] = ws.bracket()
         return out
     finally:
         ws.close()
@@ -1258,30 +1339,33 @@ def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool 
 
 def APD_SsN_Class1(c, r, l, p, q, gama=np.inf, prob=2, rng: MatlabRand | None = None,
                    amg_opts: dict | None = None, krylov: bool = False, plan_tol=None, certificate: bool = False,
-                   **opts) -> dict:
+                   bracket: bool = False, **opts) -> dict:
     """The script ``Class1/APD_SsN_Class1.m`` with ``inner_solver = 4`` on the workspace it
     loads (``:27``); returns the variables it leaves behind.  Warm start as ``:53-59``.
     ``krylov``: see ``APDWorkspace.run``.  ``plan_tol``: when given, the result gains ``plan`` (the
     final ``xk`` as a sparse m x n matrix without the entries with ``abs(x) <= plan_tol``),
     ``plan_stats`` and ``plan_ax`` (``APDWorkspace.plan``).  ``certificate=True``: the result gains
     ``certificate``, the dual certificate of the final ``lk`` (``APDWorkspace.certificate``: the better c-transform
-    with its dual value, smallest reduced cost and duality gap; with finite ``gama`` the evaluation of ``lk``)."""
+    with its dual value, smallest reduced cost and duality gap; with finite ``gama`` the evaluation of ``lk``).
+    ``bracket=True``: the result gains ``bracket`` (``APDWorkspace.bracket``: that certificate as ``lower``, the final
+    ``xk`` rounded to a feasible plan with its exact cost as ``upper``, and their ``gap``; not with finite ``gama``)."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=30, theta=1 / 4, smoth=5, cycle="w",
                                 isnsp=1, inter=1, guess=None)                          # :87-88
     warm = (0.0, 100) if prob > 0 else (5e-2, np.inf)                                  # :53-58
     ws = APDWorkspace(1, c, r, l, p, q, gama=gama)
-    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol, certificate)
+    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol, certificate,
+                       bracket)
 
 
 def APD_SsN_Class2(c, r, l, p, q, mu, phi, rng: MatlabRand | None = None,
                    amg_opts: dict | None = None, krylov: bool = False, plan_tol=None, certificate: bool = False,
-                   **opts) -> dict:
+                   bracket: bool = False, **opts) -> dict:
     """The script ``Class2/APD_SsN_Class2.m`` with ``inner_solver = 4`` (AMG4POT 'amg', or
-    'amg_pcg' with ``krylov``).  ``plan_tol``, ``certificate``: as in ``APD_SsN_Class1``."""
+    'amg_pcg' with ``krylov``).  ``plan_tol``, ``certificate``, ``bracket``: as in ``APD_SsN_Class1``."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=40, theta=1 / 4, smoth=10, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     ws = APDWorkspace(2, c, r, l, p, q, mu=mu, phi=phi)
-    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate)
+    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate, bracket)
 
 
 # ---------------------------------------------------------------------------
@@ -1332,28 +1416,32 @@ def point_cost(xs, ys, metric="sqeuclidean", scale=False, stats=False, ctx=None)
 
 def APD_SsN_Class1_points(xs, ys, r, l, p, q, metric="sqeuclidean", scale=False, gama=np.inf, prob=2,
                           rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
-                          plan_tol=None, matrix_free=False, certificate: bool = False, **opts) -> dict:
+                          plan_tol=None, matrix_free=False, certificate: bool = False, bracket: bool = False,
+                          **opts) -> dict:
     """``APD_SsN_Class1`` with ``c = point_cost(xs, ys, metric, scale)`` built on the device
-    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``: as there."""
+    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``, ``bracket``: as
+    there."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=30, theta=1 / 4, smoth=5, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     warm = (0.0, 100) if prob > 0 else (5e-2, np.inf)
     ws = APDWorkspace.from_points(1, xs, ys, r, l, p, q, metric=metric, scale=scale, gama=gama,
                                   matrix_free=matrix_free)
-    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol, certificate)
+    return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol, certificate,
+                       bracket)
 
 
 def APD_SsN_Class2_points(xs, ys, r, l, p, q, mu, phi=None, metric="sqeuclidean", scale=False,
                           rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
-                          plan_tol=None, matrix_free=False, certificate: bool = False, **opts) -> dict:
+                          plan_tol=None, matrix_free=False, certificate: bool = False, bracket: bool = False,
+                          **opts) -> dict:
     """``APD_SsN_Class2`` with the cost built on the device; ``phi=None`` is all ones
-    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``: as in
-    ``APD_SsN_Class1``."""
+    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``, ``bracket``: as
+    in ``APD_SsN_Class1``."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=40, theta=1 / 4, smoth=10, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     ws = APDWorkspace.from_points(2, xs, ys, r, l, p, q, metric=metric, scale=scale, mu=mu, phi=phi,
                                   matrix_free=matrix_free)
-    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate)
+    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate, bracket)
 
 
 def load_input(path: str) -> dict:

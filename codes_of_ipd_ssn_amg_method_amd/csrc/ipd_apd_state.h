@@ -8,6 +8,7 @@
 //   ipd_plan_apply.hip   the plan applied to a thin dense matrix
 //   ipd_cost.hip         the cost matrix from point clouds
 //   ipd_dual.hip         the c-transform of the multiplier, the dual value and the duality gap
+//   ipd_round.hip        the iterate rounded to a feasible plan, its exact cost
 #pragma once
 
 #include <functional>
@@ -164,3 +165,8 @@ void apd_warmup(ipd_apd* h, double res, long long maxit);
 // (reached through the C ABI only, ipd_apd_dual and ipd_apd_dual_dev: it reads the workspace through the handle
 // above, remembers its divider check in ipd_apd::dual_divider and keeps every temporary in the context's scratch
 // arena)
+
+// ---- ipd_round.hip -------------------------------------------------------------------------
+// (reached through the C ABI only, ipd_apd_round and ipd_apd_round_dev: it reads the workspace through the handle
+// above, writes the x (class 2: and y, z) blocks of u and v with install = 1 and nothing else, and keeps every
+// temporary in the context's scratch arena)

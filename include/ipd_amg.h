@@ -582,6 +582,62 @@ int ipd_apd_dual(ipd_apd* h, const double* lam, int32_t side, int32_t primal,
 int ipd_apd_dual_dev(ipd_apd* h, const double* lam_dev, int32_t side, int32_t primal,
                      double* lam_out_dev, int32_t* arg_dev, ipd_dual_stats* st);   /* device arrays; st on the host */
 
+/* The primal certificate on the device: the iterate rounded onto the feasible set, and the exact cost
+ * of the result -- Altschuler, Weed and Rigollet's Algorithm 2 with the weights p, q and class 2's phi row.  With
+ * X = reshape(x,m,n) the x block of the workspace's u, C the cost, PHI class 2's phi, and the constraints of Ax.m
+ * (class 1: sum_i p_i X_ij = r_j, sum_j q_j X_ij = l_i; class 2: both with <=, and sum phi_ij X_ij = mu), every
+ * operation below one IEEE operation in the order written:
+ *    1  clamp        x+_ij = (!(|x_ij| <= tol) && x_ij > 0) ? x_ij : 0     (ipd_apd_plan's threshold, then the clamp
+ *                    at 0; a NaN becomes 0)
+ *    2  marginals    a0_i = sum_j q_j*x+_ij,   b0_j = sum_i p_i*x+_ij
+ *    3  side = 0     rho_i = a0_i > l_i ? l_i/a0_i : 1;   b1_j = sum_i p_i*(rho_i*x+_ij);
+ *                    kappa_j = b1_j > r_j ? r_j/b1_j : 1
+ *    4  side = 1     kappa_j = b0_j > r_j ? r_j/b0_j : 1;   a1_i = sum_j q_j*(x+_ij*kappa_j);
+ *                    rho_i = a1_i > l_i ? l_i/a1_i : 1
+ *    5  scaled plan  X2_ij = (rho_i*x+_ij)*kappa_j
+ *    6  its sums     a2_i = sum_j q_j*X2_ij,  b2_j = sum_i p_i*X2_ij,  fs = sum c_ij*X2_ij,
+ *                    class 2: ms = sum phi_ij*X2_ij
+ *    7  deficits     e_i = max(l_i - a2_i, 0),  f_j = max(r_j - b2_j, 0),  the clamp written d > 0 ? d : 0
+ *    8  their sums   Se = sum p_i*e_i,  Sf = sum q_j*f_j,  cc = sum c_ij*(e_i*f_j),  class 2: cp = sum phi_ij*(e_i*f_j)
+ *    9  class 1      theta = 1,  t = Se > 0 ? 1/Se : 0
+ *   10  class 2      ms >= mu:  theta = mu/ms, t = 0;   otherwise  theta = 1, t = (mu - ms)/cp
+ *   11  result       X^_ij = theta*X2_ij + t*(e_i*f_j),   fval = theta*fs + t*cc,
+ *                    class 2: y^_j = max(r_j - (theta*b2_j + t*(Se*f_j)), 0),  z^_i = max(l_i - (theta*a2_i + t*(e_i*Sf)), 0)
+ *   12  ok = 1 iff theta, t and fval are finite and, class 2, t*Se <= 1 and t*Sf <= 1.  ok = 0: no repair of this
+ *       shape exists -- a result, not an error.
+ * X^ stays factored: rho (m), kappa (n), e (m), f (n) -- each may be NULL -- with theta and t of the statistics
+ * rebuild it from x; x_out_dev (mn entries or NULL, not the workspace's own) receives it in full.  viol_in is
+ * sum p_i|a0_i - l_i| + sum q_j|b0_j - r_j| (class 2: the positive parts of a0_i - l_i and b0_j - r_j only), dropped
+ * the sum of |x| over the nonzero entries that step 1 set to 0 and ndropped their count (a NaN is counted and adds
+ * nothing to dropped); ms and cp are NaN for class 1.
+ * Summation shapes (fixed: two calls, the two entries, and stored, point-cloud and matrix-free workspaces give the
+ * same bits; no float atomics): with column groups of 64 columns and segments of 64 rows, a row sum (a0, a1, a2) adds
+ * the columns of a group in ascending order and then the groups in ascending order; a column sum (b0, b1, b2) adds
+ * the 64 rows of a segment in the butterfly of the tile walker's colsum16 and then the segments in ascending order; a
+ * scalar over mn entries (fs, ms, cc, cp, dropped, ndropped) adds a row's entries of a column group in ascending
+ * order, the 64 rows of a segment in a fixed tree, the four segments of a 256-row block in order, and the blocks
+ * (column-group major) as entries t, t + 256, ... per thread t, the 256 threads in the same tree; Se, Sf and the two
+ * halves of viol_in add entries t, t + 256, ... per thread and then that tree.
+ * install = 1 makes X^ the state: the x blocks of u and v are written, class 2 also their y and z blocks with y^ and
+ * z^; lk, bk, histories and records are untouched.  It is refused with IPD_E_NUMERIC, state unchanged and nothing
+ * written, when ok = 0.  With install = 0 the workspace is only read.  Scratch comes from the context's arena.
+ * IPD_E_ARG for a NULL h or st, side or install outside {0, 1}, tol negative or NaN; IPD_E_UNSUPPORTED for a class-1
+ * workspace with finite gama, scalar or vector (the rank-one term does not keep x <= gama); nothing is written then.
+ * Both return when the result is complete.                                                                      */
+typedef struct ipd_round_stats {
+    double fval, fs, cc;         /* <c, X^> = theta*fs + t*cc; <c, X2>; sum c_ij*(e_i*f_j)                   */
+    double theta, t, se, sf;     /* the scalars of steps 9, 10 and the deficit sums of step 8                */
+    double ms, cp;               /* class 2: <phi, X2>, sum phi_ij*(e_i*f_j); NaN for class 1                */
+    double viol_in, dropped;     /* weighted marginal violation of x+; sum |x| over entries step 1 zeroed    */
+    int64_t ndropped;            /* their count                                                              */
+    int32_t ok;
+} ipd_round_stats;
+int ipd_apd_round(ipd_apd* h, double tol, int32_t side, int32_t install,
+                  double* rho, double* kappa, double* e, double* f, ipd_round_stats* st);      /* host arrays */
+int ipd_apd_round_dev(ipd_apd* h, double tol, int32_t side, int32_t install,
+                      double* rho_dev, double* kappa_dev, double* e_dev, double* f_dev,
+                      double* x_out_dev, ipd_round_stats* st);   /* device arrays; st on the host */
+
 /* The cost matrix built on the device from two point clouds: a driver run is created
  * from (m+n)*d coordinates, nothing mn-sized crosses the host boundary.  With t_k = xs(i,k) - ys(j,k)
  * folded in ascending k into an accumulator that starts at +0.0, multiply and add separate:
