@@ -3,15 +3,14 @@
 // reduced cost and the duality gap of the result.  Nothing mn-sized crosses the host boundary and nothing of the
 // workspace is written: partials and results live in the context's scratch arena.
 //
-//   transform  one streaming read of c (and phi), lanes along i (coalesced), 16 loads per lane and array in flight, a
-//              wave walks the DU_CPG chunks of its column group alone, no LDS, no barrier.  A candidate is
+//   transform  one streaming read of c (and phi) on the column-group walk of DESIGN.md section 4j (ipd_walk_geo.h,
+//              ipd_walk_dev.h).  A candidate is
 //                side 0   t(i,j) = ((-c(i,j) [- tau*phi(i,j)]) - p_i*alpha_j) / q_j     beta^_i  = max_j t(i,j)
 //                side 1   t(i,j) = ((-c(i,j) [- tau*phi(i,j)]) - q_j*beta_i)  / p_i     alpha^_j = max_i t(i,j)
 //              every operation one IEEE operation in the order written; a NaN counts as -inf; the key of the
 //              maximum is (value descending, index ascending), which is associative: any tree gives the same bits.
-//     side 0   alpha_j and q_j are uniform over the wave (lane l fetches those of column j0 + (l & 15), __shfl hands
-//              them round); the running (max, arg max) stays in registers over the column group and leaves as one
-//              partial per (group, row).
+//     side 0   the running (max, arg max) stays in registers over the column group and leaves as one partial per
+//              (group, row).
 //     side 1   a lane holds p_i and beta_i; per chunk one colmax16 butterfly -- colsum16 of the tile walker on the
 //              (value, index) key -- gives the wave's 16 column maxima, one partial per (segment slot, column).
 //   finish     one thread per entry of lam_out: the new side combines its partials in index order (class 2: clamped
@@ -32,6 +31,7 @@
 
 #include "ipd_apd_state.h"
 #include "ipd_dual_geo.h"
+#include "ipd_walk_dev.h"
 
 namespace {
 
@@ -54,7 +54,6 @@ __device__ __forceinline__ void du_merge_min(double& v, long long& i, double ov,
     v = take ? ov : v;
     i = take ? oi : i;
 }
-__device__ __forceinline__ double du_clamp0(double v) { return v > 0.0 ? v : 0.0; }   // a NaN becomes 0
 
 // 16 candidates per lane (one per column of a chunk, all of row `row`) -> the 16 column maxima over the wave's 64
 // rows with the rows that reach them: colsum16's butterfly (ipd_apd_tiles.h) on the key.  On return lane l < 16
@@ -98,7 +97,7 @@ __device__ __forceinline__ void colmax16(const double (&xv)[TC], int row, int la
 // ---------------------------------------------------------------------------
 // transform
 // ---------------------------------------------------------------------------
-template <class CS>   // CS: CostStored or CostFree<D> (ipd_apd_tiles.h)
+// the cost source CS of a walking kernel (CostStored or CostFree<D>, ipd_apd_tiles.h) is an argument of its own
 struct DuWalk {
     DuGeo g;
     int cls2;
@@ -109,120 +108,107 @@ struct DuWalk {
     const double* lam;   // alpha at lam, beta at lam + n, class 2: tau at lam[n + m]
     double* pv;          // du_part_index
     int* pi;
-    [[no_unique_address]] CS cs;
 };
 
 // side 0: hold alpha, produce beta^
 template <class CS>
-__global__ __launch_bounds__(256) void k_du_rows(const DuWalk<CS> a) {
+__global__ __launch_bounds__(256) void k_du_rows(const DuWalk a, const CS cs) {
     const DuGeo& g = a.g;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int ib = blockIdx.x, grp = blockIdx.y;
-    const int i = ib * TR + tid;
-    const bool in_i = i < g.m;
-    const int ic = in_i ? i : g.m - 1;
-    const double pi = a.p[ic];
+    const WalkLane t = walk_lane(g.m);
+    const double pi = a.p[t.ic];
     const double tau = a.cls2 ? a.lam[g.n + g.m] : 0.0;
     typename CS::Row crow;
-    a.cs.row(crow, ic);
+    cs.row(crow, t.ic);
     double bv = -INFINITY;
-    int bj = du_chunk_col(grp, 0);   // below n; stays when every candidate of the group is -inf
-    for (int ch = 0; ch < DU_CPG; ++ch) {
-        const int j0 = du_chunk_col(grp, ch);
+    int bj = walk_chunk_col(t.grp, 0);   // below n; stays when every candidate of the group is -inf
+    for (int ch = 0; ch < WK_CPG; ++ch) {
+        const int j0 = walk_chunk_col(t.grp, ch);
         if (j0 >= g.n) break;  // uniform
         double cr[TC], fr[TC];
 #pragma unroll
         for (int jj = 0; jj < TC; ++jj) {
-            const int j = min(j0 + jj, g.n - 1);   // clamped: the loads need no branch
-            const size_t idx = (size_t)j * g.m + ic;
+            const size_t idx = walk_place(t, g, j0, jj);
             cr[jj] = CS::FREE ? 0.0 : a.c[idx];
             fr[jj] = a.cls2 ? a.phi[idx] : 0.0;
         }
-        // lane l fetches alpha, q (and the coordinates) of column j0 + (l & 15), as k_plan_count fetches q
-        const int jl = min(j0 + (lane & (TC - 1)), g.n - 1);
+        const int jl = walk_lane_col(t, g, j0);   // alpha, q (and the coordinates)
         double al = a.lam[jl];
-        if (a.cls2) al = du_clamp0(al);
+        if (a.cls2) al = walk_pos(al);
         const double ql = a.q[jl];
         typename CS::Col clane;
-        a.cs.col(clane, jl);
+        cs.col(clane, jl);
 #pragma unroll
         for (int jj = 0; jj < TC; ++jj) {
             const double aj = __shfl(al, jj), qj = __shfl(ql, jj);
             typename CS::Col ccol;
-            a.cs.col_of_lane(ccol, clane, jj);
-            double t = -a.cs.value(cr[jj], crow, ccol);
+            cs.col_of_lane(ccol, clane, jj);
+            double v = -cs.value(cr[jj], crow, ccol);
             if (a.cls2) {
                 const double tf = tau * fr[jj];
-                t = t - tf;
+                v = v - tf;
             }
             const double pa = pi * aj;
-            t = t - pa;
-            t = t / qj;
-            const double cand = (j0 + jj < g.n && t == t) ? t : -INFINITY;   // a NaN never wins
+            v = v - pa;
+            v = v / qj;
+            const double cand = (j0 + jj < g.n && v == v) ? v : -INFINITY;   // a NaN never wins
             if (cand > bv) {   // columns ascend: the first of equal maxima stays
                 bv = cand;
                 bj = j0 + jj;
             }
         }
     }
-    if (in_i) {
-        a.pv[du_part_index(g, grp, i)] = bv;
-        a.pi[du_part_index(g, grp, i)] = bj;
+    if (t.in_i) {
+        a.pv[du_part_index(g, t.grp, t.i)] = bv;
+        a.pi[du_part_index(g, t.grp, t.i)] = bj;
     }
 }
 
 // side 1: hold beta, produce alpha^
 template <class CS>
-__global__ __launch_bounds__(256) void k_du_cols(const DuWalk<CS> a) {
+__global__ __launch_bounds__(256) void k_du_cols(const DuWalk a, const CS cs) {
     const DuGeo& g = a.g;
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const int ib = blockIdx.x, grp = blockIdx.y;
-    const int i = ib * TR + tid;
-    const bool in_i = i < g.m;
-    const int ic = in_i ? i : g.m - 1;
-    const int slot = ib * APD_WAVES + wv;   // of a segment without rows too: its maxima are (-inf, DU_NOIDX)
-    const double pi = a.p[ic];
-    double bi = a.lam[g.n + ic];
-    if (a.cls2) bi = du_clamp0(bi);
+    const WalkLane t = walk_lane(g.m);
+    const int slot = t.slot();   // of a segment without rows too: its maxima are (-inf, DU_NOIDX)
+    const double pi = a.p[t.ic];
+    double bi = a.lam[g.n + t.ic];
+    if (a.cls2) bi = walk_pos(bi);
     const double tau = a.cls2 ? a.lam[g.n + g.m] : 0.0;
     typename CS::Row crow;
-    a.cs.row(crow, ic);
-    for (int ch = 0; ch < DU_CPG; ++ch) {
-        const int j0 = du_chunk_col(grp, ch);
+    cs.row(crow, t.ic);
+    for (int ch = 0; ch < WK_CPG; ++ch) {
+        const int j0 = walk_chunk_col(t.grp, ch);
         if (j0 >= g.n) break;  // uniform
         double cr[TC], fr[TC];
 #pragma unroll
         for (int jj = 0; jj < TC; ++jj) {
-            const int j = min(j0 + jj, g.n - 1);
-            const size_t idx = (size_t)j * g.m + ic;
+            const size_t idx = walk_place(t, g, j0, jj);
             cr[jj] = CS::FREE ? 0.0 : a.c[idx];
             fr[jj] = a.cls2 ? a.phi[idx] : 0.0;
         }
-        const int jl = min(j0 + (lane & (TC - 1)), g.n - 1);
+        const int jl = walk_lane_col(t, g, j0);
         const double ql = a.q[jl];
         typename CS::Col clane;
-        a.cs.col(clane, jl);
+        cs.col(clane, jl);
         double xv[TC];
 #pragma unroll
         for (int jj = 0; jj < TC; ++jj) {
             const double qj = __shfl(ql, jj);
             typename CS::Col ccol;
-            a.cs.col_of_lane(ccol, clane, jj);
-            double t = -a.cs.value(cr[jj], crow, ccol);
+            cs.col_of_lane(ccol, clane, jj);
+            double v = -cs.value(cr[jj], crow, ccol);
             if (a.cls2) {
                 const double tf = tau * fr[jj];
-                t = t - tf;
+                v = v - tf;
             }
             const double qb = qj * bi;
-            t = t - qb;
-            t = t / pi;
-            xv[jj] = (in_i && j0 + jj < g.n && t == t) ? t : -INFINITY;
+            v = v - qb;
+            v = v / pi;
+            xv[jj] = (t.in_i && j0 + jj < g.n && v == v) ? v : -INFINITY;
         }
         double mv;
-        int mi;
-        colmax16(xv, in_i ? i : DU_NOIDX, lane, mv, mi);
-        const int col = j0 + colsum_index(lane);
-        if (lane < 16 && col < g.n) {
+        int mi, col;
+        colmax16(xv, t.in_i ? t.i : DU_NOIDX, t.lane, mv, mi);
+        if (walk_col_owner(t, g, j0, col)) {
             a.pv[du_part_index(g, slot, col)] = mv;
             a.pi[du_part_index(g, slot, col)] = mi;
         }
@@ -247,14 +233,14 @@ __global__ __launch_bounds__(256) void k_du_fin(const DuFin a) {
     const int M = g.n + g.m;
     const int t = blockIdx.x * 256 + threadIdx.x;   // position in lam = [alpha (n); beta (m)(; tau)]
     if (t >= M + a.cls2) return;
-    const bool made = g.side == 0 ? (t >= g.n && t < M) : t < g.n;
+    const bool made = g.own.side == 0 ? (t >= g.n && t < M) : t < g.n;
     if (!made) {
         double v = a.lam[t];
-        if (a.cls2 && t < M) v = du_clamp0(v);   // the held side; tau passes through
+        if (a.cls2 && t < M) v = walk_pos(v);   // the held side; tau passes through
         a.lam_out[t] = v;
         return;
     }
-    const int r = g.side == 0 ? t - g.n : t;
+    const int r = g.own.side == 0 ? t - g.n : t;
     const int S = du_part_count(g);
     double bv = a.pv[du_part_index(g, 0, r)];
     int bi = a.pi[du_part_index(g, 0, r)];
@@ -271,7 +257,7 @@ __global__ __launch_bounds__(256) void k_du_fin(const DuFin a) {
         for (int k = 0; k < DU_FB; ++k) du_merge(bv, bi, v[k], ix[k]);
     }
     for (; s < S; ++s) du_merge(bv, bi, a.pv[du_part_index(g, s, r)], a.pi[du_part_index(g, s, r)]);
-    if (a.cls2) bv = du_clamp0(bv);
+    if (a.cls2) bv = walk_pos(bv);
     a.lam_out[t] = bv;
     if (ARG) a.arg[r] = bi;
 }
@@ -279,7 +265,6 @@ __global__ __launch_bounds__(256) void k_du_fin(const DuFin a) {
 // ---------------------------------------------------------------------------
 // evaluate
 // ---------------------------------------------------------------------------
-template <class CS>
 struct DuEval {
     DuGeo g;
     int cls2;
@@ -292,52 +277,46 @@ struct DuEval {
     const double* q;
     const double* lam;
     const double* x;      // PRIMAL
-    DuEvalPart* part;     // du_eval_index
-    [[no_unique_address]] CS cs;
+    DuEvalPart* part;     // walk_block_index
 };
 
 template <bool PRIMAL, class CS>
-__global__ __launch_bounds__(256) void k_du_eval(const DuEval<CS> a) {
+__global__ __launch_bounds__(256) void k_du_eval(const DuEval a, const CS cs) {
     __shared__ DuEvalPart red[APD_WAVES];
     const DuGeo& g = a.g;
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const int ib = blockIdx.x, grp = blockIdx.y;
-    const int i = ib * TR + tid;
-    const bool in_i = i < g.m;
-    const int ic = in_i ? i : g.m - 1;
-    const double pi = a.p[ic];
-    const double bi = a.lam[g.n + ic];
+    const WalkLane t = walk_lane(g.m);
+    const double pi = a.p[t.ic];
+    const double bi = a.lam[g.n + t.ic];
     const double tau = a.cls2 ? a.lam[g.n + g.m] : 0.0;
     const bool gvec = a.cap_on && a.gama;
     typename CS::Row crow;
-    a.cs.row(crow, ic);
+    cs.row(crow, t.ic);
     double dmin = INFINITY, cap = 0.0, fv = 0.0;
     long long didx = DU_NOPLACE;
     int nneg = 0;
-    for (int ch = 0; ch < DU_CPG; ++ch) {
-        const int j0 = du_chunk_col(grp, ch);
+    for (int ch = 0; ch < WK_CPG; ++ch) {
+        const int j0 = walk_chunk_col(t.grp, ch);
         if (j0 >= g.n) break;  // uniform
         double cr[TC], fr[TC], gr[TC], xr[TC];
 #pragma unroll
         for (int jj = 0; jj < TC; ++jj) {
-            const int j = min(j0 + jj, g.n - 1);
-            const size_t idx = (size_t)j * g.m + ic;
+            const size_t idx = walk_place(t, g, j0, jj);
             cr[jj] = CS::FREE ? 0.0 : a.c[idx];
             xr[jj] = PRIMAL ? a.x[idx] : 0.0;
             fr[jj] = a.cls2 ? a.phi[idx] : 0.0;
             gr[jj] = gvec ? a.gama[idx] : a.gs;
         }
-        const int jl = min(j0 + (lane & (TC - 1)), g.n - 1);
+        const int jl = walk_lane_col(t, g, j0);
         const double al = a.lam[jl];
         const double ql = a.q[jl];
         typename CS::Col clane;
-        a.cs.col(clane, jl);
+        cs.col(clane, jl);
 #pragma unroll
         for (int jj = 0; jj < TC; ++jj) {
             const double aj = __shfl(al, jj), qj = __shfl(ql, jj);
             typename CS::Col ccol;
-            a.cs.col_of_lane(ccol, clane, jj);
-            const double cv = a.cs.value(cr[jj], crow, ccol);
+            cs.col_of_lane(ccol, clane, jj);
+            const double cv = cs.value(cr[jj], crow, ccol);
             const double pa = pi * aj;
             double d = cv + pa;
             const double qb = qj * bi;
@@ -346,10 +325,10 @@ __global__ __launch_bounds__(256) void k_du_eval(const DuEval<CS> a) {
                 const double tf = tau * fr[jj];
                 d = d + tf;
             }
-            const bool valid = in_i && j0 + jj < g.n;
+            const bool valid = t.in_i && j0 + jj < g.n;
             if (valid && d < dmin) {   // columns ascend: the first of equal minima stays; a NaN never wins
                 dmin = d;
-                didx = (long long)(j0 + jj) * g.m + i;
+                didx = (long long)(j0 + jj) * g.m + t.i;
             }
             const bool neg = valid && d < 0.0;
             nneg += neg ? 1 : 0;
@@ -370,15 +349,15 @@ __global__ __launch_bounds__(256) void k_du_eval(const DuEval<CS> a) {
     }
     cap = wave_sum(cap);
     fv = wave_sum(fv);
-    if (lane == 0) {
-        red[wv].dmin = dmin;
-        red[wv].idx = didx;
-        red[wv].nneg = nneg;
-        red[wv].cap = cap;
-        red[wv].fval = fv;
+    if (t.lane == 0) {
+        red[t.wv].dmin = dmin;
+        red[t.wv].idx = didx;
+        red[t.wv].nneg = nneg;
+        red[t.wv].cap = cap;
+        red[t.wv].fval = fv;
     }
     __syncthreads();
-    if (tid == 0) {
+    if (t.tid == 0) {
         DuEvalPart r = red[0];
 #pragma unroll
         for (int w = 1; w < APD_WAVES; ++w) {
@@ -387,7 +366,7 @@ __global__ __launch_bounds__(256) void k_du_eval(const DuEval<CS> a) {
             r.cap += red[w].cap;
             r.fval += red[w].fval;
         }
-        a.part[du_eval_index(g, ib, grp)] = r;
+        a.part[walk_block_index(g, t.ib, t.grp)] = r;
     }
 }
 
@@ -405,7 +384,7 @@ __global__ __launch_bounds__(256) void k_du_last(const DuLast a) {
     __shared__ double redb[APD_WAVES];
     const DuGeo& g = a.g;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const int M = g.n + g.m, L = M + a.cls2, nblk = du_eval_blocks(g);
+    const int M = g.n + g.m, L = M + a.cls2, nblk = walk_blocks(g);
     const long long mn = (long long)g.m * g.n;
     DuEvalPart r;
     r.dmin = INFINITY;
@@ -522,22 +501,21 @@ void dual_dev(ipd_apd* h, const double* lam_dev, int side, int primal, double* l
         double* pv = S.alloc<double>(du_part_len(g));
         int* pi = S.alloc<int>(du_part_len(g));
         if (!lam_out_dev) lam_out_dev = S.alloc<double>((size_t)h->L);
+        DuWalk a;
+        a.g = g;
+        a.cls2 = cls2;
+        a.c = h->c;
+        a.phi = h->phi;
+        a.p = h->p;
+        a.q = h->q;
+        a.lam = lam_dev;
+        a.pv = pv;
+        a.pi = pi;
         with_cost_source(h, [&](auto cs) {
-            DuWalk<decltype(cs)> a;
-            a.g = g;
-            a.cls2 = cls2;
-            a.c = h->c;
-            a.phi = h->phi;
-            a.p = h->p;
-            a.q = h->q;
-            a.lam = lam_dev;
-            a.pv = pv;
-            a.pi = pi;
-            a.cs = cs;
             if (side == 0)
-                hipLaunchKernelGGL((k_du_rows<decltype(cs)>), grid, dim3(256), 0, ctx->stream, a);
+                hipLaunchKernelGGL((k_du_rows<decltype(cs)>), grid, dim3(256), 0, ctx->stream, a, cs);
             else
-                hipLaunchKernelGGL((k_du_cols<decltype(cs)>), grid, dim3(256), 0, ctx->stream, a);
+                hipLaunchKernelGGL((k_du_cols<decltype(cs)>), grid, dim3(256), 0, ctx->stream, a, cs);
         });
         IPD_KERNEL_CHECK();
         DuFin f;
@@ -557,26 +535,25 @@ void dual_dev(ipd_apd* h, const double* lam_dev, int side, int primal, double* l
         lam_eval = lam_out_dev;
     }
     DuEvalPart* part = reinterpret_cast<DuEvalPart*>(
-        S.alloc<double>((size_t)du_eval_blocks(g) * (sizeof(DuEvalPart) / sizeof(double))));
+        S.alloc<double>((size_t)walk_blocks(g) * (sizeof(DuEvalPart) / sizeof(double))));
+    DuEval e;
+    e.g = g;
+    e.cls2 = cls2;
+    e.cap_on = cap_on(h) ? 1 : 0;
+    e.c = h->c;
+    e.phi = h->phi;
+    e.gama = h->gama;
+    e.gs = h->P.gs;
+    e.p = h->p;
+    e.q = h->q;
+    e.lam = lam_eval;
+    e.x = h->u;   // class 2: the x block of uk comes first
+    e.part = part;
     with_cost_source(h, [&](auto cs) {
-        DuEval<decltype(cs)> a;
-        a.g = g;
-        a.cls2 = cls2;
-        a.cap_on = cap_on(h) ? 1 : 0;
-        a.c = h->c;
-        a.phi = h->phi;
-        a.gama = h->gama;
-        a.gs = h->P.gs;
-        a.p = h->p;
-        a.q = h->q;
-        a.lam = lam_eval;
-        a.x = h->u;   // class 2: the x block of uk comes first
-        a.part = part;
-        a.cs = cs;
         if (primal)
-            hipLaunchKernelGGL((k_du_eval<true, decltype(cs)>), grid, dim3(256), 0, ctx->stream, a);
+            hipLaunchKernelGGL((k_du_eval<true, decltype(cs)>), grid, dim3(256), 0, ctx->stream, e, cs);
         else
-            hipLaunchKernelGGL((k_du_eval<false, decltype(cs)>), grid, dim3(256), 0, ctx->stream, a);
+            hipLaunchKernelGGL((k_du_eval<false, decltype(cs)>), grid, dim3(256), 0, ctx->stream, e, cs);
     });
     IPD_KERNEL_CHECK();
     DuLast l;

@@ -29,6 +29,7 @@
 #include <cstdlib>
 
 #include "ipd_apd_state.h"
+#include "ipd_walk_dev.h"
 
 namespace {
 
@@ -94,42 +95,37 @@ template <bool AX, class CS>
 __global__ __launch_bounds__(256) void k_plan_count(const PlanCountT<CS> a) {
     __shared__ double red[4 * PSC];
     const PlanGeo& g = a.g;
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const int ib = blockIdx.x, jg = blockIdx.y;
-    const int i = ib * TR + tid;
-    const bool in_i = i < g.m;
-    const int ic = in_i ? i : g.m - 1;
-    const int seg = ib * 4 + wv;
-    const double pi = (AX && in_i) ? a.p[i] : 0.0;
+    const WalkLane t = walk_lane(g.m);   // on the driver's geometry: t.grp is its column group jg
+    const int seg = t.slot();
+    const double pi = (AX && t.in_i) ? a.p[t.i] : 0.0;
     typename CS::Row crow;
-    a.cs.row(crow, ic);
+    a.cs.row(crow, t.ic);
     double skept = 0.0, sdrop = 0.0, mdrop = 0.0, fkept = 0.0, lacc = 0.0;
     for (int rep = 0; rep < g.reps; ++rep) {
-        const int j0 = (jg * g.reps + rep) * TC;
+        const int j0 = (t.grp * g.reps + rep) * TC;
         if (j0 >= g.n) break;  // uniform
         double xr[TC], cr[TC];
 #pragma unroll
         for (int jj = 0; jj < TC; ++jj) {
-            const int j = min(j0 + jj, g.n - 1);   // clamped: the loads need no branch
-            const size_t idx = (size_t)j * g.m + ic;
+            const size_t idx = walk_place(t, g, j0, jj);
             xr[jj] = a.x[idx];
             cr[jj] = CS::FREE ? 0.0 : a.c[idx];
         }
         // lane jj fetches q of column j0 + jj (16 uniform loads held 32 scalar registers too many)
-        const double ql = (AX && lane < TC) ? a.q[min(j0 + lane, g.n - 1)] : 0.0;
+        const double ql = (AX && t.lane < TC) ? a.q[min(j0 + t.lane, g.n - 1)] : 0.0;
         // matrix-free: and the coordinates of column j0 + (lane mod 16), for the same reason
         typename CS::Col clane;
-        a.cs.col(clane, min(j0 + (lane & (TC - 1)), g.n - 1));
+        a.cs.col(clane, walk_lane_col(t, g, j0));
         int mycnt = 0;
         double xv[TC];
 #pragma unroll
         for (int jj = 0; jj < TC; ++jj) {
-            const bool valid = in_i && j0 + jj < g.n;
+            const bool valid = t.in_i && j0 + jj < g.n;
             const double x = xr[jj];
             const double ab = fabs(x);
-            const bool keep = valid && !(ab <= a.tol);   // a NaN is kept, as MATLAB's sparse() keeps it
+            const bool keep = valid && walk_keep(x, a.tol);
             const unsigned long long bal = __ballot(keep);
-            if (lane == jj) mycnt = __popcll(bal);
+            if (t.lane == jj) mycnt = __popcll(bal);
             const double qj = AX ? __shfl(ql, jj) : 0.0;
             typename CS::Col ccol;
             a.cs.col_of_lane(ccol, clane, jj);
@@ -146,34 +142,34 @@ __global__ __launch_bounds__(256) void k_plan_count(const PlanCountT<CS> a) {
             xv[jj] = xk * pi;
         }
         // lane jj holds the count of column j0 + jj: one store instruction for the 16 of them
-        if (lane < TC && seg < g.nseg && j0 + lane < g.n) a.cnt[(size_t)(j0 + lane) * g.nseg + seg] = mycnt;
+        if (t.lane < TC && seg < g.nseg && j0 + t.lane < g.n) a.cnt[(size_t)(j0 + t.lane) * g.nseg + seg] = mycnt;
         if (AX) {
-            const double cs = colsum16(xv, lane);
-            const int col = j0 + colsum_index(lane);
-            if (lane < 16 && col < g.n) a.rpart[(size_t)seg * g.n + col] = cs;
+            const double cs = colsum16(xv, t.lane);
+            int col;
+            if (walk_col_owner(t, g, j0, col)) a.rpart[(size_t)seg * g.n + col] = cs;
         }
     }
-    if (AX && in_i) a.lpart[(size_t)jg * g.m + i] = lacc;
+    if (AX && t.in_i) a.lpart[(size_t)t.grp * g.m + t.i] = lacc;
     const double w0 = wave_add(skept), w1 = wave_add(sdrop), w2 = wave_max(mdrop), w3 = wave_add(fkept);
-    if (lane == 0) {
-        red[wv * PSC + 0] = w0;
-        red[wv * PSC + 1] = w1;
-        red[wv * PSC + 2] = w2;
-        red[wv * PSC + 3] = w3;
+    if (t.lane == 0) {
+        red[t.wv * PSC + 0] = w0;
+        red[t.wv * PSC + 1] = w1;
+        red[t.wv * PSC + 2] = w2;
+        red[t.wv * PSC + 3] = w3;
     }
     __syncthreads();
-    if (tid < PSC) {
-        const int blk = jg * gridDim.x + ib;
-        const double r0 = red[tid], r1 = red[PSC + tid], r2 = red[2 * PSC + tid], r3 = red[3 * PSC + tid];
+    if (t.tid < PSC) {
+        const int blk = t.grp * gridDim.x + t.ib;
+        const double r0 = red[t.tid], r1 = red[PSC + t.tid], r2 = red[2 * PSC + t.tid], r3 = red[3 * PSC + t.tid];
         double r;
-        if (tid == 2) {
+        if (t.tid == 2) {
             r = r0 > r1 ? r0 : r1;
             r = r2 > r ? r2 : r;
             r = r3 > r ? r3 : r;
         } else {
             r = r0 + r1 + r2 + r3;
         }
-        a.spart[(size_t)blk * PSC + tid] = r;
+        a.spart[(size_t)blk * PSC + t.tid] = r;
     }
 }
 
@@ -334,7 +330,7 @@ __global__ __launch_bounds__(256) void k_plan_fill(const PlanFill a) {
         for (int jj = 0; jj < TC; ++jj) {
             const bool valid = in_i && j0 + jj < g.n;
             const double x = xr[jj];
-            const bool keep = valid && !(fabs(x) <= a.tol);
+            const bool keep = valid && walk_keep(x, a.tol);
             const unsigned long long bal = __ballot(keep);
             const int o = __shfl(off, jj);
             if (keep) {

@@ -4,15 +4,13 @@
 // entries and, on request, the rows of Y divided by it (the barycentric projection).  Nothing mn-sized crosses the
 // host boundary and nothing of the workspace is written: the partials live in the context's scratch arena.
 //
-//   walk    one streaming read of x per pass of PA_KC = 4 components, in k_plan_count's style: a wave owns 64
-//           consecutive rows and walks the PA_CPG chunks of its column group alone, lanes along i (coalesced), 16
-//           loads per lane in flight, no LDS tile, no barrier.  A dropped entry, a padding lane and a clamped column
-//           contribute +0.0 through a select, so an inf or NaN of B that meets only those never reaches Y.
-//     side 0  B(j, c0 .. c0+KC) is uniform over the wave: lane l loads B[j0 + (l & 15), c0 + (l >> 4)], one load per
-//             lane and chunk, and __shfl hands it round.  KC row accumulators and the mass stay in registers over
-//             the column group and leave as one partial per (group, component, row).
-//     side 1  a lane holds B(i, c0 .. c0+KC) in registers; per chunk and component one colsum16 butterfly of the
-//             tile walker gives the wave's 16 column sums, one partial per (segment slot, component, column).
+//   walk    one streaming read of x per pass of PA_KC = 4 components, on the column-group walk of DESIGN.md section 4j
+//           (ipd_walk_geo.h, ipd_walk_dev.h).  A dropped entry, a padding lane and a clamped column contribute +0.0
+//           through a select, so an inf or NaN of B that meets only those never reaches Y.
+//     side 0  lane l loads B[j0 + (l & 15), c0 + (l >> 4)], one load per lane and chunk.  KC row accumulators and the
+//             mass stay in registers over the column group and leave as one partial per (group, component, row).
+//     side 1  a lane holds B(i, c0 .. c0+KC) in registers; per chunk and component one colsum16 butterfly gives the
+//             wave's 16 column sums, one partial per (segment slot, component, column).
 //   finish  one thread per entry of the pass's columns of Y adds its partials in index order, divides by the mass
 //           when asked to (one IEEE division; a row of zero kept mass is 0/0 = NaN) and stores.  Pass 0 also sums the
 //           mass and leaves it in w (the caller's, or a scratch vector) for the passes after it.
@@ -25,10 +23,11 @@
 
 #include "ipd_apd_state.h"
 #include "ipd_plan_apply_geo.h"
+#include "ipd_walk_dev.h"
 
 namespace {
 
-// TR, TC: ipd_apd_geo.h; colsum16, colsum_index, sum_strided: ipd_apd_tiles.h
+// TR, TC: ipd_apd_geo.h; colsum16, sum_strided: ipd_apd_tiles.h
 static_assert(PA_KC * TC == 64, "side 0: the lanes of a wave fetch a chunk's TC x PA_KC block of B in one load each");
 
 struct PaWalk {
@@ -46,44 +45,36 @@ struct PaWalk {
 template <int KC, bool MASS>
 __global__ __launch_bounds__(256) void k_pa_rows(const PaWalk a) {
     const PaGeo& g = a.g;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int ib = blockIdx.x, grp = blockIdx.y;
-    const int i = ib * TR + tid;
-    const bool in_i = i < g.m;
-    const int ic = in_i ? i : g.m - 1;
+    const WalkLane t = walk_lane(g.m);
     double acc[KC], wacc = 0.0;
 #pragma unroll
     for (int c = 0; c < KC; ++c) acc[c] = 0.0;
-    for (int ch = 0; ch < PA_CPG; ++ch) {
-        const int j0 = pa_chunk_col(grp, ch);
+    for (int ch = 0; ch < WK_CPG; ++ch) {
+        const int j0 = walk_chunk_col(t.grp, ch);
         if (j0 >= g.n) break;  // uniform
         double xr[TC];
 #pragma unroll
-        for (int jj = 0; jj < TC; ++jj) {
-            const int j = min(j0 + jj, g.n - 1);   // clamped: the loads need no branch
-            xr[jj] = a.x[(size_t)j * g.m + ic];
-        }
-        // lane l fetches B(j0 + (l & 15), c0 + (l >> 4)) (64 uniform loads would hold the scalar registers k_plan_count
-        // could not spare for q either)
-        const int lc = lane >> 4;
-        const double bl = lc < KC ? a.B[(size_t)(a.c0 + lc) * g.n + min(j0 + (lane & (TC - 1)), g.n - 1)] : 0.0;
+        for (int jj = 0; jj < TC; ++jj) xr[jj] = a.x[walk_place(t, g, j0, jj)];
+        // lane l fetches B(j0 + (l & 15), c0 + (l >> 4))
+        const int lc = t.lane >> 4;
+        const double bl = lc < KC ? a.B[(size_t)(a.c0 + lc) * g.n + walk_lane_col(t, g, j0)] : 0.0;
 #pragma unroll
         for (int jj = 0; jj < TC; ++jj) {
             const double x = xr[jj];
-            const bool keep = in_i && j0 + jj < g.n && !(fabs(x) <= a.tol);   // a NaN is kept
+            const bool keep = t.in_i && j0 + jj < g.n && walk_keep(x, a.tol);
 #pragma unroll
             for (int c = 0; c < KC; ++c) {
                 const double b = __shfl(bl, c * TC + jj);
-                const double t = x * b;
-                acc[c] += keep ? t : 0.0;
+                const double xb = x * b;
+                acc[c] += keep ? xb : 0.0;
             }
             if (MASS) wacc += keep ? x : 0.0;
         }
     }
-    if (in_i) {
+    if (t.in_i) {
 #pragma unroll
-        for (int c = 0; c < KC; ++c) a.part[pa_part_index(g, grp, c, i)] = acc[c];
-        if (MASS) a.part[pa_part_index(g, grp, PA_KC, i)] = wacc;
+        for (int c = 0; c < KC; ++c) a.part[pa_part_index(g, t.grp, c, t.i)] = acc[c];
+        if (MASS) a.part[pa_part_index(g, t.grp, PA_KC, t.i)] = wacc;
     }
 }
 
@@ -93,45 +84,38 @@ __global__ __launch_bounds__(256) void k_pa_rows(const PaWalk a) {
 template <int KC, bool MASS>
 __global__ __launch_bounds__(256) void k_pa_cols(const PaWalk a) {
     const PaGeo& g = a.g;
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const int ib = blockIdx.x, grp = blockIdx.y;
-    const int i = ib * TR + tid;
-    const bool in_i = i < g.m;
-    const int ic = in_i ? i : g.m - 1;
-    const int slot = ib * APD_WAVES + wv;   // of a segment without rows too: its sums are zeros
+    const WalkLane t = walk_lane(g.m);
+    const int slot = t.slot();   // of a segment without rows too: its sums are zeros
     double bi[KC];
 #pragma unroll
-    for (int c = 0; c < KC; ++c) bi[c] = a.B[(size_t)(a.c0 + c) * g.m + ic];
-    for (int ch = 0; ch < PA_CPG; ++ch) {
-        const int j0 = pa_chunk_col(grp, ch);
+    for (int c = 0; c < KC; ++c) bi[c] = a.B[(size_t)(a.c0 + c) * g.m + t.ic];
+    for (int ch = 0; ch < WK_CPG; ++ch) {
+        const int j0 = walk_chunk_col(t.grp, ch);
         if (j0 >= g.n) break;  // uniform
         double xr[TC];
 #pragma unroll
-        for (int jj = 0; jj < TC; ++jj) {
-            const int j = min(j0 + jj, g.n - 1);
-            xr[jj] = a.x[(size_t)j * g.m + ic];
-        }
+        for (int jj = 0; jj < TC; ++jj) xr[jj] = a.x[walk_place(t, g, j0, jj)];
         bool keep[TC];
 #pragma unroll
-        for (int jj = 0; jj < TC; ++jj) keep[jj] = in_i && j0 + jj < g.n && !(fabs(xr[jj]) <= a.tol);
-        const int col = j0 + colsum_index(lane);
-        const bool owner = lane < 16 && col < g.n;
+        for (int jj = 0; jj < TC; ++jj) keep[jj] = t.in_i && j0 + jj < g.n && walk_keep(xr[jj], a.tol);
+        int col;
+        const bool owner = walk_col_owner(t, g, j0, col);
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
             double xv[TC];
 #pragma unroll
             for (int jj = 0; jj < TC; ++jj) {
-                const double t = xr[jj] * bi[c];
-                xv[jj] = keep[jj] ? t : 0.0;
+                const double xb = xr[jj] * bi[c];
+                xv[jj] = keep[jj] ? xb : 0.0;
             }
-            const double cs = colsum16(xv, lane);
+            const double cs = colsum16(xv, t.lane);
             if (owner) a.part[pa_part_index(g, slot, c, col)] = cs;
         }
         if (MASS) {
             double xv[TC];
 #pragma unroll
             for (int jj = 0; jj < TC; ++jj) xv[jj] = keep[jj] ? xr[jj] : 0.0;
-            const double cs = colsum16(xv, lane);
+            const double cs = colsum16(xv, t.lane);
             if (owner) a.part[pa_part_index(g, slot, PA_KC, col)] = cs;
         }
     }
@@ -177,7 +161,7 @@ __global__ __launch_bounds__(256) void k_pa_fin(const PaFin a) {
 template <int KC, bool MASS>
 void launch_walk(ipd_ctx* ctx, const PaWalk& a) {
     const dim3 grid(a.g.nib, a.g.ng);
-    if (a.g.side == 0)
+    if (a.g.own.side == 0)
         hipLaunchKernelGGL((k_pa_rows<KC, MASS>), grid, dim3(256), 0, ctx->stream, a);
     else
         hipLaunchKernelGGL((k_pa_cols<KC, MASS>), grid, dim3(256), 0, ctx->stream, a);

@@ -4,13 +4,12 @@
 // result.  The result stays factored (rho, kappa, e, f, theta, t), so nothing mn-sized crosses the host boundary;
 // partials and vectors live in the context's scratch arena, and the workspace is written only with install = 1.
 //
-//   walk   every mn-sized pass is one instantiation of k_rd_walk: lanes along i (coalesced), 16 loads per lane and
-//          array in flight, a wave walks the RD_CPG chunks of its column group alone, no LDS tile, no barrier in the
-//          loop.  Row sums stay in a register over the column group (columns ascending) and leave as one partial per
-//          (group, row); the 16 column sums of a chunk over the wave's 64 rows come out of colsum16's butterfly, one
-//          partial per (segment slot, column); a scalar sum is a lane's sum over its entries (columns ascending),
-//          wave_sum's tree, the workgroup's four waves in order, one partial per workgroup.  Per-column values (q,
-//          kappa, f, the coordinates) are fetched by lane l for column j0 + (l & 15) and handed round with __shfl.
+//   walk   every mn-sized pass is one instantiation of k_rd_walk on the column-group walk of DESIGN.md section 4j
+//          (ipd_walk_geo.h, ipd_walk_dev.h).  Row sums stay in a register over the column group (columns ascending) and
+//          leave as one partial per (group, row); the 16 column sums of a chunk come out of colsum16's butterfly, one
+//          partial per (segment slot, column); a scalar sum is a lane's sum over its entries (columns ascending), then
+//          walk_wave_sums' shape, one partial per workgroup.  The kernel writes the frame of ipd_walk_dev.h out: taken
+//          from there, passes D and W compile to other machine code.
 //            A   x                  a0, b0 partials; dropped, ndropped
 //            B   x                  side 0: b1 partials; side 1: a1 partials
 //            C   x, c (, phi)       a2, b2 partials; fs (, ms)
@@ -34,6 +33,7 @@
 
 #include "ipd_apd_state.h"
 #include "ipd_round_geo.h"
+#include "ipd_walk_dev.h"
 
 namespace {
 
@@ -50,12 +50,11 @@ static_assert(sizeof(ipd_round_stats) <= 16 * sizeof(double) && sizeof(RdDev) <=
 
 // step 1: plan()'s threshold, then the clamp at 0; a NaN becomes 0
 __device__ __forceinline__ double rd_clamp(double x, double tol) {
-    return (!(fabs(x) <= tol) && x > 0.0) ? x : 0.0;
+    return (walk_keep(x, tol) && x > 0.0) ? x : 0.0;
 }
-__device__ __forceinline__ double rd_pos(double d) { return d > 0.0 ? d : 0.0; }
 __device__ __forceinline__ double rd_scale(double s, double bound) { return s > bound ? bound / s : 1.0; }
 
-template <class CS>   // CS: CostStored or CostFree<D> (ipd_apd_tiles.h)
+// the cost source CS of a pass that reads c (CostStored or CostFree<D>, ipd_apd_tiles.h) is an argument of its own
 struct RdWalk {
     RdGeo g;
     int cls2;
@@ -69,17 +68,16 @@ struct RdWalk {
     const double* sc;    // [kappa (n); rho (m)]
     const double* ef;    // [f (n); e (m)]
     const RdDev* dev;    // W
-    double* rpart;       // rd_row_index
-    double* cpart;       // rd_col_index
+    double* rpart;       // walk_row_part_index
+    double* cpart;       // walk_col_part_index
     double* spart;       // rd_scal_index
     double* o0;          // W: destinations or nullptr
     double* o1;
     double* o2;
-    [[no_unique_address]] CS cs;
 };
 
 template <int PASS, class CS>
-__global__ __launch_bounds__(256) void k_rd_walk(const RdWalk<CS> a) {
+__global__ __launch_bounds__(256) void k_rd_walk(const RdWalk a, const CS cs) {
     constexpr bool USE_X = PASS != RD_D;
     constexpr bool USE_C = PASS == RD_C || PASS == RD_D;
     constexpr bool ROWS = PASS == RD_A || PASS == RD_B1 || PASS == RD_C;
@@ -90,7 +88,7 @@ __global__ __launch_bounds__(256) void k_rd_walk(const RdWalk<CS> a) {
     constexpr bool USE_EF = PASS == RD_D || PASS == RD_W;
     __shared__ double red[APD_WAVES * RD_NS];
     const RdGeo& g = a.g;
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;   // walk_lane
     const int ib = blockIdx.x, grp = blockIdx.y;
     const int i = ib * TR + tid;
     const bool in_i = i < g.m;
@@ -105,27 +103,26 @@ __global__ __launch_bounds__(256) void k_rd_walk(const RdWalk<CS> a) {
     const double rho = USE_RHO ? a.sc[g.n + ic] : 1.0;
     const double ei = USE_EF ? a.ef[g.n + ic] : 0.0;
     typename CS::Row crow;
-    if (USE_C) a.cs.row(crow, ic);
+    if (USE_C) cs.row(crow, ic);
     double racc = 0.0, s0 = 0.0, s1 = 0.0;
-    for (int ch = 0; ch < RD_CPG; ++ch) {
-        const int j0 = rd_chunk_col(grp, ch);
+    for (int ch = 0; ch < WK_CPG; ++ch) {
+        const int j0 = walk_chunk_col(grp, ch);
         if (j0 >= g.n) break;  // uniform
         double xr[TC], cr[TC], fr[TC];
 #pragma unroll
         for (int jj = 0; jj < TC; ++jj) {
-            const int j = min(j0 + jj, g.n - 1);   // clamped: the loads need no branch
+            const int j = min(j0 + jj, g.n - 1);   // walk_place
             const size_t idx = (size_t)j * g.m + ic;
             xr[jj] = USE_X ? a.x[idx] : 0.0;
             cr[jj] = (USE_C && !CS::FREE) ? a.c[idx] : 0.0;
             fr[jj] = (USE_C && a.cls2) ? a.phi[idx] : 0.0;
         }
-        // lane l fetches the values (and the coordinates) of column j0 + (l & 15), as k_du_rows does
-        const int jl = min(j0 + (lane & (TC - 1)), g.n - 1);
+        const int jl = min(j0 + (lane & (TC - 1)), g.n - 1);   // walk_lane_col
         const double ql = ROWS ? a.q[jl] : 0.0;
         const double kl = USE_KAP ? a.sc[jl] : 1.0;
         const double fl = USE_EF ? a.ef[jl] : 0.0;
         typename CS::Col clane;
-        if (USE_C) a.cs.col(clane, jl);
+        if (USE_C) cs.col(clane, jl);
         double xv[TC];
 #pragma unroll
         for (int jj = 0; jj < TC; ++jj) {
@@ -136,8 +133,8 @@ __global__ __launch_bounds__(256) void k_rd_walk(const RdWalk<CS> a) {
             double cv = 0.0;
             if (USE_C) {
                 typename CS::Col ccol;
-                a.cs.col_of_lane(ccol, clane, jj);
-                cv = a.cs.value(cr[jj], crow, ccol);
+                cs.col_of_lane(ccol, clane, jj);
+                cv = cs.value(cr[jj], crow, ccol);
             }
             const double xp = USE_X ? rd_clamp(xr[jj], a.tol) : 0.0;
             double term_r = 0.0, term_c = 0.0;
@@ -193,10 +190,10 @@ __global__ __launch_bounds__(256) void k_rd_walk(const RdWalk<CS> a) {
         if (COLS) {
             const double cs = colsum16(xv, lane);
             const int col = j0 + colsum_index(lane);
-            if (lane < 16 && col < g.n) a.cpart[rd_col_index(g, rd_slot(ib, wv), col)] = cs;
+            if (lane < 16 && col < g.n) a.cpart[walk_col_part_index(g, walk_slot(ib, wv), col)] = cs;
         }
     }
-    if (ROWS && in_i) a.rpart[rd_row_index(g, grp, i)] = racc;
+    if (ROWS && in_i) a.rpart[walk_row_part_index(g, grp, i)] = racc;
     if (SCAL) {
         s0 = wave_sum(s0);
         s1 = wave_sum(s1);
@@ -250,7 +247,7 @@ __global__ __launch_bounds__(256) void k_rd_fin(const RdFin a) {
     } else {
         a.ab2[t] = s;
         const double d = bt - s;
-        a.ef[t] = rd_pos(d);
+        a.ef[t] = walk_pos(d);
     }
 }
 
@@ -279,7 +276,7 @@ __global__ __launch_bounds__(256) void k_rd_last(const RdLast a) {
     __shared__ double red[APD_WAVES * RD_NSUM];
     const RdGeo& g = a.g;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const int nblk = rd_blocks(g);
+    const int nblk = walk_blocks(g);
     // 0 dropped, 1 ndropped, 2 fs, 3 ms, 4 cc, 5 cp, 6 Se, 7 the rows of viol_in, 8 Sf, 9 the columns of viol_in
     double s[RD_NSUM];
 #pragma unroll
@@ -299,7 +296,7 @@ __global__ __launch_bounds__(256) void k_rd_last(const RdLast a) {
         const double pe = pi * a.ef[g.n + i];
         s[6] += pe;
         const double d = a.ab0[g.n + i] - a.b[g.n + i];
-        const double v = a.cls2 ? rd_pos(d) : fabs(d);
+        const double v = a.cls2 ? walk_pos(d) : fabs(d);
         const double pv = pi * v;
         s[7] += pv;
     }
@@ -309,24 +306,14 @@ __global__ __launch_bounds__(256) void k_rd_last(const RdLast a) {
         const double qf = qj * a.ef[j];
         s[8] += qf;
         const double d = a.ab0[j] - a.b[j];
-        const double v = a.cls2 ? rd_pos(d) : fabs(d);
+        const double v = a.cls2 ? walk_pos(d) : fabs(d);
         const double qv = qj * v;
         s[9] += qv;
     }
-#pragma unroll
-    for (int k = 0; k < RD_NSUM; ++k) {
-        const double w = wave_sum(s[k]);
-        if (lane == 0) red[wv * RD_NSUM + k] = w;
-    }
-    __syncthreads();
+    walk_wave_sums(lane, wv, s, red);
     if (tid == 0) {
 #pragma unroll
-        for (int k = 0; k < RD_NSUM; ++k) {
-            double r = red[k];
-#pragma unroll
-            for (int w = 1; w < APD_WAVES; ++w) r += red[w * RD_NSUM + k];
-            s[k] = r;
-        }
+        for (int k = 0; k < RD_NSUM; ++k) s[k] = walk_waves_total<RD_NSUM>(red, k);
         const double nan = std::numeric_limits<double>::quiet_NaN();
         const double fs = s[2], ms = s[3], cc = s[4], cp = s[5], se = s[6], sf = s[8];
         double theta = 1.0, t;
@@ -394,7 +381,7 @@ __global__ __launch_bounds__(256) void k_rd_slack(const RdSlack a) {
     const double t2 = tt * w;
     const double v = t1 + t2;
     const double d = a.b[t] - v;
-    const double y = rd_pos(d);
+    const double y = walk_pos(d);
     a.u_yz[t] = y;
     a.v_yz[t] = y;
 }
@@ -416,9 +403,9 @@ struct RdVecs {
     const double* ef;   // [f (n); e (m)]
 };
 
-template <int PASS, class CS>
-void launch_walk(ipd_apd* h, const RdWalk<CS>& a) {
-    hipLaunchKernelGGL((k_rd_walk<PASS, CS>), dim3(a.g.nib, a.g.ng), dim3(256), 0, h->ctx->stream, a);
+template <int PASS, class CS = CostStored>
+void launch_walk(ipd_apd* h, const RdWalk& a, CS cs = CS()) {
+    hipLaunchKernelGGL((k_rd_walk<PASS, CS>), dim3(a.g.nib, a.g.ng), dim3(256), 0, h->ctx->stream, a, cs);
     IPD_KERNEL_CHECK();
 }
 
@@ -427,11 +414,11 @@ void launch_walk(ipd_apd* h, const RdWalk<CS>& a) {
 RdVecs round_dev(ipd_apd* h, double tol, int side, int install, double* x_out_dev, ipd_round_stats* st) {
     ipd_ctx* ctx = h->ctx;
     Arena& S = *ctx->scratch;
-    const RdGeo g = rd_make_geo(h->m, h->n);
+    const RdGeo g = walk_make_geo(h->m, h->n);
     const int cls2 = h->cls == 2 ? 1 : 0;
     const size_t M = (size_t)h->M;
-    double* rpart = S.alloc<double>(rd_row_len(g));
-    double* cpart = S.alloc<double>(rd_col_len(g));
+    double* rpart = S.alloc<double>(walk_row_part_len(g));
+    double* cpart = S.alloc<double>(walk_col_part_len(g));
     double* sA = S.alloc<double>(rd_scal_len(g));
     double* sC = S.alloc<double>(rd_scal_len(g));
     double* sD = S.alloc<double>(rd_scal_len(g));
@@ -442,7 +429,7 @@ RdVecs round_dev(ipd_apd* h, double tol, int side, int install, double* x_out_de
     ipd_round_stats* out = reinterpret_cast<ipd_round_stats*>(S.alloc<double>(16));
     RdDev* dev = reinterpret_cast<RdDev*>(S.alloc<double>(8));
 
-    RdWalk<CostStored> w;
+    RdWalk w;
     w.g = g;
     w.cls2 = cls2;
     w.need_ok = install;
@@ -472,31 +459,6 @@ RdVecs round_dev(ipd_apd* h, double tol, int side, int install, double* x_out_de
     f.ab2 = ab2;
     f.ef = ef;
     const dim3 fgrid(cdiv((long long)M, 256));
-    // with the cost source of the workspace: the walk `w` with spart = sp
-    auto with_cost = [&](double* sp, auto&& launch) {
-        with_cost_source(h, [&](auto cs) {
-            RdWalk<decltype(cs)> a;
-            a.g = w.g;
-            a.cls2 = w.cls2;
-            a.need_ok = w.need_ok;
-            a.tol = w.tol;
-            a.x = w.x;
-            a.c = w.c;
-            a.phi = w.phi;
-            a.p = w.p;
-            a.q = w.q;
-            a.sc = w.sc;
-            a.ef = w.ef;
-            a.dev = w.dev;
-            a.rpart = w.rpart;
-            a.cpart = w.cpart;
-            a.spart = sp;
-            a.o0 = a.o1 = a.o2 = nullptr;
-            a.cs = cs;
-            launch(a);
-        });
-    };
-
     launch_walk<RD_A>(h, w);
     hipLaunchKernelGGL(k_rd_fin<0>, fgrid, dim3(256), 0, ctx->stream, f);
     IPD_KERNEL_CHECK();
@@ -506,10 +468,12 @@ RdVecs round_dev(ipd_apd* h, double tol, int side, int install, double* x_out_de
         launch_walk<RD_B1>(h, w);
     hipLaunchKernelGGL(k_rd_fin<1>, fgrid, dim3(256), 0, ctx->stream, f);
     IPD_KERNEL_CHECK();
-    with_cost(sC, [&](auto& a) { launch_walk<RD_C>(h, a); });
+    w.spart = sC;
+    with_cost_source(h, [&](auto cs) { launch_walk<RD_C>(h, w, cs); });
     hipLaunchKernelGGL(k_rd_fin<2>, fgrid, dim3(256), 0, ctx->stream, f);
     IPD_KERNEL_CHECK();
-    with_cost(sD, [&](auto& a) { launch_walk<RD_D>(h, a); });
+    w.spart = sD;
+    with_cost_source(h, [&](auto cs) { launch_walk<RD_D>(h, w, cs); });
     RdLast l;
     l.g = g;
     l.cls2 = cls2;

@@ -2,29 +2,29 @@
 // (codes_of_ipd_ssn_amg_method_amd/csrc/ipd_plan_apply_geo.h) for tests/test_plan_apply_geo.py.  One query per
 // input line, `<what> <m> <n> <k> <side>`:
 //   geo     the grid, the passes and the buffer sizes
-//   cover   walks the columns as k_pa_rows / k_pa_cols do and the components as the launcher's pass loop does
+//   cover   walks the components as the launcher's pass loop does (the columns: tests/walk_geo_driver.cpp)
 //   reach   walks every index the walking kernels write and the finishing kernel reads of the partial buffer
 // Per query it prints one line:
 //   geo nib= ng= nslot= npass= R= S= stride= part= scratch_dev= scratch_host=
-//   cover min=<fewest (group, chunk, column-in-chunk) owners of a column j < n> max=<most> broke=<walks ended by
-//         j0 >= n> idle=<chunks not walked after such an end> cmin=<fewest passes owning a component> cmax=<most>
-//         kcmax=<most components of a pass> tail=<components of the last pass>
+//   cover cmin=<fewest passes owning a component> cmax=<most> kcmax=<most components of a pass> tail=<components of
+//         the last pass>
 //   reach wmax=<largest index written> rmax=<largest index read> unwritten=<indices read by the finishing kernel
 //         that no walking kernel writes in a pass of PA_KC components with the mass> dup=<indices written twice> len=
 //   <what> refused     for a side outside {0, 1} or k outside [1, PA_KMAX]
 // The first line of the output is
-//   limits TR= TC= APD_WAVES= PA_KMAX= PA_KC= PA_NC= PA_CPG=
+//   limits TR= TC= APD_WAVES= PA_KMAX= PA_KC= PA_NC= WK_CPG=
 #include <cstdio>
 #include <iostream>
 #include <sstream>
 #include <string>
 #include <vector>
 
+#include "geo_buf.h"
 #include "ipd_plan_apply_geo.h"
 
 int main() {
-    std::printf("limits TR=%d TC=%d APD_WAVES=%d PA_KMAX=%d PA_KC=%d PA_NC=%d PA_CPG=%d\n", TR, TC, APD_WAVES, PA_KMAX,
-                PA_KC, PA_NC, PA_CPG);
+    std::printf("limits TR=%d TC=%d APD_WAVES=%d PA_KMAX=%d PA_KC=%d PA_NC=%d WK_CPG=%d\n", TR, TC, APD_WAVES, PA_KMAX,
+                PA_KC, PA_NC, WK_CPG);
     std::string line;
     while (std::getline(std::cin, line)) {
         std::istringstream in(line);
@@ -41,25 +41,6 @@ int main() {
                         g.nib, g.ng, g.nslot, g.npass, pa_out_rows(g), pa_part_count(g), pa_part_stride(g),
                         pa_part_len(g), pa_scratch_bytes(g, true, false, false), pa_scratch_bytes(g, false, true, true));
         } else if (what == "cover") {
-            // the columns do not depend on the row block: one wave's walk per column group
-            std::vector<int> owners((size_t)n, 0);
-            long long broke = 0, idle = 0;
-            for (int grp = 0; grp < g.ng; ++grp)
-                for (int ch = 0; ch < PA_CPG; ++ch) {
-                    const int j0 = pa_chunk_col(grp, ch);
-                    if (j0 >= n) {   // the kernels: if (j0 >= g.n) break;
-                        ++broke;
-                        idle += PA_CPG - ch;
-                        break;
-                    }
-                    for (int cc = 0; cc < TC; ++cc)
-                        if (j0 + cc < n) ++owners[(size_t)(j0 + cc)];
-                }
-            int lo = 1 << 30, hi = 0;
-            for (int v : owners) {
-                lo = v < lo ? v : lo;
-                hi = v > hi ? v : hi;
-            }
             std::vector<int> comp((size_t)k, 0);
             int kcmax = 0, tail = 0;
             for (int p = 0; p < g.npass; ++p) {
@@ -77,52 +58,34 @@ int main() {
                 clo = v < clo ? v : clo;
                 chi = v > chi ? v : chi;
             }
-            std::printf("cover min=%d max=%d broke=%lld idle=%lld cmin=%d cmax=%d kcmax=%d tail=%d\n", lo, hi, broke, idle,
-                        clo, chi, kcmax, tail);
+            std::printf("cover cmin=%d cmax=%d kcmax=%d tail=%d\n", clo, chi, kcmax, tail);
         } else if (what == "reach") {
             // one pass of PA_KC components with the mass: the fullest the buffer gets
-            const size_t len = pa_part_len(g);
-            std::vector<unsigned char> written(len, 0);
-            size_t wmax = 0, rmax = 0, dup = 0, unwritten = 0;
-            bool outside = false;
-            auto write = [&](size_t idx) {
-                wmax = idx > wmax ? idx : wmax;
-                if (idx >= len) {
-                    outside = true;
-                    return;
-                }
-                dup += written[idx];
-                written[idx] = 1;
-            };
+            Buf part(pa_part_len(g));
             if (side == 0) {
                 // k_pa_rows: lane of row i < m of group grp stores its PA_NC accumulators
                 for (int grp = 0; grp < g.ng; ++grp)
                     for (int c = 0; c < PA_NC; ++c)
-                        for (int i = 0; i < m; ++i) write(pa_part_index(g, grp, c, i));
+                        for (int i = 0; i < m; ++i) part.write(pa_part_index(g, grp, c, i));
             } else {
                 // k_pa_cols: wave `slot` stores the sums of the columns below n of every chunk it walks
                 for (int slot = 0; slot < g.nslot; ++slot)
                     for (int grp = 0; grp < g.ng; ++grp)
-                        for (int ch = 0; ch < PA_CPG; ++ch) {
-                            const int j0 = pa_chunk_col(grp, ch);
+                        for (int ch = 0; ch < WK_CPG; ++ch) {
+                            const int j0 = walk_chunk_col(grp, ch);
                             if (j0 >= n) break;
                             for (int cc = 0; cc < TC; ++cc)
                                 if (j0 + cc < n)
-                                    for (int c = 0; c < PA_NC; ++c) write(pa_part_index(g, slot, c, j0 + cc));
+                                    for (int c = 0; c < PA_NC; ++c) part.write(pa_part_index(g, slot, c, j0 + cc));
                         }
             }
             // k_pa_fin: S partials from pa_part_index(g, 0, c, r) at stride pa_part_stride(g)
             const int R = pa_out_rows(g), S = pa_part_count(g);
             for (int c = 0; c < PA_NC; ++c)
                 for (int r = 0; r < R; ++r)
-                    for (int s = 0; s < S; ++s) {
-                        const size_t idx = pa_part_index(g, 0, c, r) + (size_t)s * pa_part_stride(g);
-                        rmax = idx > rmax ? idx : rmax;
-                        if (idx >= len) outside = true;
-                        else if (!written[idx]) ++unwritten;
-                    }
-            std::printf("reach wmax=%zu rmax=%zu unwritten=%zu dup=%zu len=%zu outside=%d\n", wmax, rmax, unwritten, dup,
-                        len, outside ? 1 : 0);
+                    for (int s = 0; s < S; ++s) part.read(pa_part_index(g, 0, c, r) + (size_t)s * pa_part_stride(g));
+            std::printf("reach wmax=%zu rmax=%zu unwritten=%zu dup=%zu len=%zu outside=%d\n", part.wmax, part.rmax,
+                        part.unwritten, part.dup, part.len(), part.outside ? 1 : 0);
         }
     }
     return 0;

@@ -1,91 +1,31 @@
 """The dual certificate's host-clean geometry header (csrc/ipd_dual_geo.h) on the CPU: a small C++ driver
 (tests/dual_geo_driver.cpp) is built with the system g++ against the header.  Over the shapes of tests/test_apd_geo.py
-and up to 16384 x 16384 it shows that each row and each column has exactly one owner, that every partial index the
-walking kernels write and the finishing kernels read lies inside the buffers (each read entry written exactly once),
-and that the scratch of a call stays at or below mn/2 bytes -- a sixteenth of one mn vector -- from m = n = 1024 on.
-The two shapes tests/test_gpu_dual.py adds to the plan tests' are pinned.  CPU only."""
-import atexit
-import functools
-import os
-import shutil
-import subprocess
-import tempfile
-
+and up to 16384 x 16384 it shows that every partial index the walking kernels write and the finishing kernels read
+lies inside the buffers (each read entry written exactly once), and that the scratch of a call stays at or below mn/2
+bytes -- a sixteenth of one mn vector -- from m = n = 1024 on.  The walk of the rows and columns itself is
+tests/test_walk_geo.py's.  The two shapes tests/test_gpu_dual.py adds to the plan tests' are pinned.  CPU only."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "codes_of_ipd_ssn_amg_method_amd", "csrc")
-HERE = os.path.dirname(os.path.abspath(__file__))
+from tests.geo_driver import LARGE, SHAPES, WALK, GeoDriver, cdiv, fields as _fields
 
-# tests/test_apd_geo.py's shapes, re-stated
-SHAPES = [(300, 147), (65, 40), (257, 500), (1, 1), (1, 17), (256, 16), (257, 15), (64, 128), (65, 129), (70, 8211),
-          (300, 4099), (1793, 17), (10900, 17), (512, 255), (512, 256), (512, 257), (3, 2049)]
-LARGE = [(4096, 4096), (8192, 4096), (16384, 16384), (1793, 16353), (1793, 16337), (16384, 1), (1, 16384)]
-
-
-@functools.lru_cache(maxsize=None)
-def driver_exe():
-    d = tempfile.mkdtemp(prefix="dual_geo")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    exe = os.path.join(d, "dual_geo_driver")
-    res = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + CSRC,
-                          os.path.join(HERE, "dual_geo_driver.cpp"), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    return exe
-
-
-def _fields(line):
-    return {k: int(v) for k, v in (tok.split("=") for tok in line.split()[1:] if "=" in tok)}
-
-
-def ask(queries):
-    res = subprocess.run([driver_exe()], input="\n".join(queries) + "\n", capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    out = res.stdout.strip().split("\n")
-    assert out[0].startswith("limits ") and len(out) == len(queries) + 1, out
-    return out[1:], _fields(out[0])
-
-
-@functools.lru_cache(maxsize=None)
-def limits():
-    return ask([])[1]
-
-
-def cdiv(a, b):
-    return -(-a // b)
+DRV = GeoDriver("dual_geo_driver")
+ask, limits = DRV.ask, DRV.limits
 
 
 def test_limits():
-    assert limits() == dict(TR=256, TC=16, APD_WAVES=4, DU_CPG=4, EVALPART=40)
+    assert limits() == dict(TR=256, TC=16, APD_WAVES=4, WK_CPG=4, EVALPART=40)
 
 
 def test_refused_arguments():
-    out = ask(["geo 5 5 2", "geo 5 5 -1", "cover 5 5 3", "geo 5 5 1"])[0]
-    assert out[:3] == ["geo refused", "geo refused", "cover refused"] and out[3].startswith("geo nib=")
-
-
-@pytest.mark.parametrize("side", [0, 1])
-def test_every_row_and_column_has_one_owner(side):
-    shapes = SHAPES + LARGE
-    out = ask(["cover %d %d %d" % (m, n, side) for m, n in shapes])[0]
-    geo = ask(["geo %d %d %d" % (m, n, side) for m, n in shapes])[0]
-    T, CPG = limits()["TC"], limits()["DU_CPG"]
-    for (m, n), line, gl in zip(shapes, out, geo):
-        f, g = _fields(line), _fields(gl)
-        assert (f["rmin"], f["rmax"]) == (1, 1), (m, n, line)
-        assert (f["min"], f["max"]) == (1, 1), (m, n, line)
-        assert f["first"] == 1, (m, n, line)
-        # the last group is the only one that can end early, and the groups before it are full
-        assert g["ng"] * CPG * T >= n > (g["ng"] - 1) * CPG * T
-        assert f["broke"] == (1 if cdiv(n, T) % CPG else 0)
-        assert f["idle"] == g["ng"] * CPG - cdiv(n, T)
+    out = ask(["geo 5 5 2", "geo 5 5 -1", "reach 5 5 3", "geo 5 5 1"])[0]
+    assert out[:3] == ["geo refused", "geo refused", "reach refused"] and out[3].startswith("geo nib=")
 
 
 def test_the_two_added_gpu_shapes():
     """65 x 150: three column groups of 4, 4 and 2 chunks, the last chunk with 6 columns; 300 x 16: a second row
     block whose first wave is partly filled (rows 256 .. 299) and whose other three have no rows."""
     g = _fields(ask(["geo 65 150 0"])[0][0])
-    f = _fields(ask(["cover 65 150 0"])[0][0])
+    f = _fields(WALK.ask(["cover 65 150"])[0][0])
     assert (g["nib"], g["ng"], g["nslot"], g["blocks"]) == (1, 3, 4, 3)
     assert (f["broke"], f["idle"]) == (1, 2) and 150 - 9 * 16 == 6
     g = _fields(ask(["geo 300 16 1"])[0][0])

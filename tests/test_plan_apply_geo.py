@@ -1,64 +1,21 @@
 """The plan products' host-clean geometry header (csrc/ipd_plan_apply_geo.h) on the CPU: a small C++ driver
 (tests/plan_apply_geo_driver.cpp) is built with the system g++ against the header.  Over the shapes of
-tests/test_apd_geo.py and k in {1, 3, 4, 5, 15, 16} it shows that each column has exactly one (group, chunk,
-column-in-chunk) owner, that each of the k components belongs to exactly one pass, that the partial buffer has the
-size the walking kernels' and the finishing kernel's index functions reach, and that the scratch of a call stays at or
-below 2*mn bytes from m = n = 1024 on.  The group count is not switchable: the natural rule gives three groups with
-a partly filled last one at 65 x 150 (pinned below), which tests/test_gpu_plan_apply.py runs.  CPU only."""
-import atexit
-import functools
-import os
-import shutil
-import subprocess
-import tempfile
-
+tests/test_apd_geo.py and k in {1, 3, 4, 5, 15, 16} it shows that each of the k components belongs to exactly one
+pass, that the partial buffer has the size the walking kernels' and the finishing kernel's index functions reach, and
+that the scratch of a call stays at or below 2*mn bytes from m = n = 1024 on.  The walk of the rows and columns itself
+is tests/test_walk_geo.py's.  The group count is not switchable: the natural rule gives three groups with a partly
+filled last one at 65 x 150 (pinned below), which tests/test_gpu_plan_apply.py runs.  CPU only."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "codes_of_ipd_ssn_amg_method_amd", "csrc")
-HERE = os.path.dirname(os.path.abspath(__file__))
+from tests.geo_driver import LARGE, SHAPES, WALK, GeoDriver, cdiv, fields as _fields
 
-# tests/test_apd_geo.py's shapes, re-stated
-SHAPES = [(300, 147), (65, 40), (257, 500), (1, 1), (1, 17), (256, 16), (257, 15), (64, 128), (65, 129), (70, 8211),
-          (300, 4099), (1793, 17), (10900, 17), (512, 255), (512, 256), (512, 257), (3, 2049)]
-LARGE = [(4096, 4096), (8192, 4096), (16384, 16384), (1793, 16353), (1793, 16337), (16384, 1), (1, 16384)]
+DRV = GeoDriver("plan_apply_geo_driver")
+ask, limits = DRV.ask, DRV.limits
 KS = [1, 3, 4, 5, 15, 16]
 
 
-@functools.lru_cache(maxsize=None)
-def driver_exe():
-    d = tempfile.mkdtemp(prefix="plan_apply_geo")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    exe = os.path.join(d, "plan_apply_geo_driver")
-    res = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + CSRC,
-                          os.path.join(HERE, "plan_apply_geo_driver.cpp"), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    return exe
-
-
-def _fields(line):
-    return {k: int(v) for k, v in (tok.split("=") for tok in line.split()[1:] if "=" in tok)}
-
-
-def ask(queries):
-    res = subprocess.run([driver_exe()], input="\n".join(queries) + "\n", capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    out = res.stdout.strip().split("\n")
-    assert out[0].startswith("limits ") and len(out) == len(queries) + 1, out
-    return out[1:], _fields(out[0])
-
-
-@functools.lru_cache(maxsize=None)
-def limits():
-    return ask([])[1]
-
-
-def cdiv(a, b):
-    return -(-a // b)
-
-
 def test_limits():
-    assert limits() == dict(TR=256, TC=16, APD_WAVES=4, PA_KMAX=16, PA_KC=4, PA_NC=5, PA_CPG=4)
+    assert limits() == dict(TR=256, TC=16, APD_WAVES=4, PA_KMAX=16, PA_KC=4, PA_NC=5, WK_CPG=4)
 
 
 def test_refused_arguments():
@@ -72,24 +29,25 @@ def test_every_column_and_component_has_one_owner(k, side):
     shapes = SHAPES + LARGE
     out = ask(["cover %d %d %d %d" % (m, n, k, side) for m, n in shapes])[0]
     geo = ask(["geo %d %d %d %d" % (m, n, k, side) for m, n in shapes])[0]
-    T, CPG, KC = limits()["TC"], limits()["PA_CPG"], limits()["PA_KC"]
-    for (m, n), line, gl in zip(shapes, out, geo):
-        f, g = _fields(line), _fields(gl)
-        assert (f["min"], f["max"]) == (1, 1), (m, n, line)
+    walk = WALK.ask(["cover %d %d" % s for s in shapes])[0]   # the columns: the walk of tests/test_walk_geo.py
+    T, CPG, KC = limits()["TC"], limits()["WK_CPG"], limits()["PA_KC"]
+    for (m, n), line, gl, wl in zip(shapes, out, geo, walk):
+        f, g, w = _fields(line), _fields(gl), _fields(wl)
+        assert (w["min"], w["max"]) == (1, 1), (m, n, wl)
         assert (f["cmin"], f["cmax"]) == (1, 1), (m, n, k, line)
         assert f["kcmax"] == min(k, KC) and f["tail"] == (k % KC or KC)
         assert g["npass"] == cdiv(k, KC)
         # the last group is the only one that can end early, and the groups before it are full
         assert g["ng"] * CPG * T >= n > (g["ng"] - 1) * CPG * T
-        assert f["broke"] == (1 if cdiv(n, T) % CPG else 0)
-        assert f["idle"] == g["ng"] * CPG - cdiv(n, T)
+        assert w["broke"] == (1 if cdiv(n, T) % CPG else 0)
+        assert w["idle"] == g["ng"] * CPG - cdiv(n, T)
 
 
 def test_three_groups_with_a_partly_filled_last_one():
     """The shape tests/test_gpu_plan_apply.py uses for it: 150 columns are 10 chunks, the last with 6 columns, in
     groups of 4, 4 and 2 chunks."""
     g = _fields(ask(["geo 65 150 5 0"])[0][0])
-    f = _fields(ask(["cover 65 150 5 0"])[0][0])
+    f = _fields(WALK.ask(["cover 65 150"])[0][0])
     assert (g["nib"], g["ng"], g["nslot"], g["npass"]) == (1, 3, 4, 2)
     assert (f["broke"], f["idle"]) == (1, 2)
 
