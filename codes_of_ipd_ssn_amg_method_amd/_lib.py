@@ -92,6 +92,22 @@ class ipd_round_stats(Structure):
                 ("dropped", c_double), ("ndropped", c_int64), ("ok", c_int32)]
 
 
+class ipd_bracket(Structure):
+    _fields_ = [("lower", ipd_dual_stats), ("upper", ipd_round_stats), ("lower_side", c_int32),
+                ("upper_side", c_int32), ("gap", c_double)]
+
+
+class ipd_gap_rule(Structure):
+    _fields_ = [("gap_tol", c_double), ("gap_rel", c_double), ("tol", c_double), ("first", c_int32),
+                ("every", c_int32), ("install", c_int32)]
+
+
+class ipd_gap_rec(Structure):
+    _fields_ = [("k", c_int32), ("lower_side", c_int32), ("upper_side", c_int32), ("upper_ok", c_int32),
+                ("stop", c_int32), ("final", c_int32), ("lower", c_double), ("lower_dmin", c_double),
+                ("best", c_double), ("upper", c_double), ("viol_in", c_double), ("gap", c_double)]
+
+
 class ipd_cost_spec(Structure):
     _fields_ = [("metric", c_int32), ("dim", c_int32), ("m", c_int64), ("n", c_int64),
                 ("xs", POINTER(c_double)), ("ys", POINTER(c_double)), ("scale", c_int32)]
@@ -154,6 +170,11 @@ lib.ipd_apd_dual_dev.argtypes = lib.ipd_apd_dual.argtypes
 lib.ipd_apd_round.argtypes = [c_void_p, c_double, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_round_dev.argtypes = [c_void_p, c_double, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p]
+lib.ipd_apd_bracket.argtypes = [c_void_p, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_bracket_dev.argtypes = lib.ipd_apd_bracket.argtypes
+lib.ipd_apd_set_gap_rule.argtypes = [c_void_p, c_void_p]
+lib.ipd_apd_gap_records.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
+lib.ipd_apd_gap_lam.argtypes = [c_void_p, c_void_p, c_void_p]
 lib.ipd_cost_points_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_create_points.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_get_cost.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -194,6 +215,8 @@ EXPORTS = [
     "ipd_apd_plan_apply", "ipd_apd_plan_apply_dev",
     "ipd_apd_dual", "ipd_apd_dual_dev",
     "ipd_apd_round", "ipd_apd_round_dev",
+    "ipd_apd_bracket", "ipd_apd_bracket_dev",
+    "ipd_apd_set_gap_rule", "ipd_apd_gap_records", "ipd_apd_gap_lam",
     "ipd_cost_points_dev", "ipd_apd_create_points", "ipd_apd_get_cost",
     "ipd_apd_create_points_free", "ipd_apd_cost_info",
     "ipd_apd_get_w", "ipd_apd_eval_trial", "ipd_apd_merit", "ipd_apd_end",

@@ -758,6 +758,7 @@ class APDWorkspace:
         d.r, d.l, d.p, d.q = dptr(r_), dptr(l_), dptr(p_), dptr(q_)
         d.mu = float(mu)
         d.gama_scalar = np.inf
+        self._gap_rule = False        # set_gap_rule: run() reports gap_stop and gap while a rule is set
         self._finite_gama = False     # class 1 with a finite scalar or a vector gama: the dual keeps its cap term
         if self.cls == 1:
             if np.ndim(gama) == 0 or np.size(gama) == 1:
@@ -1159,6 +1160,92 @@ class APDWorkspace:
         upper["side"] = side
         return dict(lower=lower, upper=upper, gap=upper["fval"] - lower["dual"])
 
+    # -- both certificates in one call, and the stopping rule on their gap -------
+    def _gap_result(self, br: L.ipd_bracket) -> dict:
+        lower, upper = self._dual_stats(br.lower), self._round_stats(br.upper)
+        lower["side"], upper["side"] = int(br.lower_side), int(br.upper_side)
+        return dict(lower=lower, upper=upper, gap=br.gap)
+
+    def gap_probe(self, tol: float = 0.0, install: bool = False, vectors: bool = False) -> dict:
+        """``bracket()`` as one device call (``ipd_apd_bracket``): both c-transforms of ``lk`` in one walk over the
+        cost, both repaired multipliers evaluated in one read of ``c`` and ``xk``, the rounding's first pass shared
+        by the two sides, one read-back.  Returns ``dict(lower, upper, gap)`` with the bits of ``dual(side,
+        primal=True)`` and ``round_plan(tol, side)`` for the sides picked as ``certificate()`` and ``bracket()`` pick
+        them (``lower["side"]``, ``upper["side"]``); ``lower["lam"]`` is the repaired multiplier and with
+        ``vectors`` ``upper`` holds ``rho``, ``kappa``, ``e``, ``f``.  ``install=True`` makes the rounded plan the
+        state as ``round_plan(tol, upper["side"], install=True)`` does and raises ``IpdError`` (``IPD_E_NUMERIC``)
+        when ``upper["ok"] == 0``.  Not for finite ``gama`` (``IPD_E_UNSUPPORTED``)."""
+        lam = np.empty(self.L)
+        vec = [np.empty(k) for k in (self.m, self.n, self.m, self.n)] if vectors else [None] * 4
+        br = L.ipd_bracket()
+        check(lib.ipd_apd_bracket(self.handle, c_double(tol), c_int32(1 if install else 0), lam.ctypes.data,
+                                  *[v.ctypes.data if v is not None else None for v in vec], byref(br)))
+        res = self._gap_result(br)
+        res["lower"]["lam"] = lam
+        if vectors:
+            res["upper"].update(rho=vec[0], kappa=vec[1], e=vec[2], f=vec[3])
+        return res
+
+    def gap_probe_dev(self, tol: float = 0.0, install: bool = False, lam_out=None, rho=None, kappa=None, e=None,
+                      f=None) -> dict:
+        """The same on caller-owned device arrays (``ipd_apd_bracket_dev``): ``lam_out`` L float64, ``rho``, ``e`` m,
+        ``kappa``, ``f`` n, each may be None -- torch tensors on the workspace's GPU, ``DeviceBuffer`` objects, or
+        ``(pointer, entries)`` pairs, as ``round_plan_dev`` takes them.  Returns the statistics."""
+        def ptr_of(a, need, name):
+            if a is None:
+                return None
+            if isinstance(a, tuple):
+                p, cnt = c_void_p(int(a[0])), int(a[1])
+            elif isinstance(a, L.DeviceBuffer):
+                p, cnt = a.ptr, a.nbytes // 8
+            elif hasattr(a, "data_ptr"):
+                if a.element_size() != 8 or not a.is_contiguous():
+                    raise ValueError("gap_probe_dev: tensors must be contiguous float64")
+                p, cnt = c_void_p(a.data_ptr()), a.numel()
+            else:
+                raise ValueError(f"gap_probe_dev: {name} must be a tensor, a DeviceBuffer or a (pointer, entries) pair")
+            if cnt < need:
+                raise ValueError(f"gap_probe_dev: {name} must hold {need} entries")
+            return p
+        ptrs = [ptr_of(lam_out, self.L, "lam_out"), ptr_of(rho, self.m, "rho"), ptr_of(kappa, self.n, "kappa"),
+                ptr_of(e, self.m, "e"), ptr_of(f, self.n, "f")]
+        br = L.ipd_bracket()
+        check(lib.ipd_apd_bracket_dev(self.handle, c_double(tol), c_int32(1 if install else 0), *ptrs, byref(br)))
+        return self._gap_result(br)
+
+    def set_gap_rule(self, gap_tol=0.0, gap_rel: float = 0.0, tol: float = 0.0, first: int = 1, every: int = 1,
+                     install: bool = False) -> None:
+        """A stopping rule of ``run`` on the certified gap (``ipd_apd_set_gap_rule``): after iteration ``first``,
+        ``first + every``, ... and after the one that converges, ``gap_probe(tol)`` runs on the state; the loop
+        stops when the better rounded plan is a repair and ``upper - best <= max(gap_tol, gap_rel*|upper|)``, ``best``
+        the largest lower bound of the probes so far.  Both thresholds 0: probe and record only.  ``install``: the
+        rounded plan becomes the state at the probe that stops.  ``set_gap_rule(None)`` switches the rule off.  A
+        stopped workspace runs on only after the rule is set again."""
+        if gap_tol is None:
+            check(lib.ipd_apd_set_gap_rule(self.handle, None))
+            self._gap_rule = False
+            return
+        r = L.ipd_gap_rule(gap_tol, gap_rel, tol, int(first), int(every), int(install))
+        check(lib.ipd_apd_set_gap_rule(self.handle, byref(r)))
+        self._gap_rule = True
+
+    def gap_records(self) -> list:
+        """One dict per probe of the rule: ``k, lower_side, upper_side, upper_ok, stop, final, lower, lower_dmin,
+        best, upper, viol_in, gap`` with ``gap = upper - best``."""
+        cnt = c_int64()
+        check(lib.ipd_apd_gap_records(self.handle, None, c_int64(0), byref(cnt)))
+        arr = (L.ipd_gap_rec * max(cnt.value, 1))()
+        check(lib.ipd_apd_gap_records(self.handle, arr, c_int64(cnt.value), byref(cnt)))
+        keys = [f[0] for f in L.ipd_gap_rec._fields_]
+        return [{k: getattr(arr[i], k) for k in keys} for i in range(cnt.value)]
+
+    def gap_lam(self):
+        """``(lam, best)``: the best lower bound of the probes so far and the multiplier that attains it;
+        ``(None, -inf)`` before the first probe."""
+        lam, best = np.empty(self.L), c_double()
+        check(lib.ipd_apd_gap_lam(self.handle, lam.ctypes.data, byref(best)))
+        return (lam if best.value > -np.inf else None), best.value
+
     # -- the loop -------------------------------------------------------------
     def options(self, **kw) -> L.ipd_apd_opts:
         o = L.ipd_apd_opts()
@@ -1178,9 +1265,14 @@ class APDWorkspace:
         check(lib.ipd_apd_set_krylov(self.handle, c_int32(1 if krylov else 0)))
         check(lib.ipd_apd_run(self.handle, byref(o), byref(ao), rng.handle,
                               c_int32(o.maxit if iters is None else int(iters)), byref(res)))
-        return dict(converged=bool(res.converged), k=res.k, fval=res.fval, kkt=list(res.kkt),
-                    rr=res.rr, SumAMG=res.sum_amg, TotalAMG=res.total_amg, FailAMG=res.fail_amg,
-                    MaxAMG=res.max_amg, restarts=res.restarts, nrec=res.nrec)
+        out = dict(converged=bool(res.converged), k=res.k, fval=res.fval, kkt=list(res.kkt),
+                   rr=res.rr, SumAMG=res.sum_amg, TotalAMG=res.total_amg, FailAMG=res.fail_amg,
+                   MaxAMG=res.max_amg, restarts=res.restarts, nrec=res.nrec)
+        if self._gap_rule:
+            recs = self.gap_records()
+            out["gap"] = recs[-1] if recs else None
+            out["gap_stop"] = bool(recs and recs[-1]["stop"])
+        return out
 
     def history(self) -> dict:
         names = ["fxk", "KKT_xk", "KKT_lk", "KKT_yk", "KKT_zk", "SsN_itnum"]
@@ -1315,13 +1407,17 @@ def warmup_class2(c, r, l, p, q, mu, phi, res=None, maxit=None):
 
 
 def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool = False,
-                plan_tol=None, certificate: bool = False, bracket: bool = False) -> dict:
+                plan_tol=None, certificate: bool = False, bracket: bool = False, gap: dict | None = None) -> dict:
     try:
         if bracket and ws._finite_gama:     # before the run, not after it
             raise ValueError("bracket: rounding does not keep x <= gama; finite gama is not supported")
         if warm is not None:
             ws.warmup(*warm)
+        if gap is not None:
+            ws.set_gap_rule(**gap)
         out = ws.run(amg_opts, rng, krylov=krylov, **opts)
+        if gap is not None:
+            out["gap_records"] = ws.gap_records()
         u, v, lam, bk = ws.state()
         out.update(ws.history())
         out.update(uk=u, vk=v, lk=lam, bk=bk, records=ws.records(), reuse_stats=ws.reuse_stats())
@@ -1337,9 +1433,18 @@ def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool 
         ws.close()
 
 
+def _gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install):
+    """the drivers' ``gap_*`` keywords as ``set_gap_rule``'s; None when none of them was given"""
+    if gap_tol is None and gap_rel is None and gap_every is None and gap_first is None and not gap_install:
+        return None
+    return dict(gap_tol=gap_tol or 0.0, gap_rel=gap_rel or 0.0, first=1 if gap_first is None else gap_first,
+                every=1 if gap_every is None else gap_every, install=bool(gap_install))
+
+
 def APD_SsN_Class1(c, r, l, p, q, gama=np.inf, prob=2, rng: MatlabRand | None = None,
                    amg_opts: dict | None = None, krylov: bool = False, plan_tol=None, certificate: bool = False,
-                   bracket: bool = False, **opts) -> dict:
+                   bracket: bool = False, gap_tol=None, gap_rel=None, gap_every=None, gap_first=None,
+                   gap_install=False, **opts) -> dict:
     """The script ``Class1/APD_SsN_Class1.m`` with ``inner_solver = 4`` on the workspace it
     loads (``:27``); returns the variables it leaves behind.  Warm start as ``:53-59``.
     ``krylov``: see ``APDWorkspace.run``.  ``plan_tol``: when given, the result gains ``plan`` (the
@@ -1348,24 +1453,30 @@ def APD_SsN_Class1(c, r, l, p, q, gama=np.inf, prob=2, rng: MatlabRand | None = 
     ``certificate``, the dual certificate of the final ``lk`` (``APDWorkspace.certificate``: the better c-transform
     with its dual value, smallest reduced cost and duality gap; with finite ``gama`` the evaluation of ``lk``).
     ``bracket=True``: the result gains ``bracket`` (``APDWorkspace.bracket``: that certificate as ``lower``, the final
-    ``xk`` rounded to a feasible plan with its exact cost as ``upper``, and their ``gap``; not with finite ``gama``)."""
+    ``xk`` rounded to a feasible plan with its exact cost as ``upper``, and their ``gap``; not with finite ``gama``).
+    ``gap_tol``, ``gap_rel``, ``gap_every``, ``gap_first``, ``gap_install``: any of them sets the stopping rule on the
+    certified gap (``APDWorkspace.set_gap_rule``; the rounding's ``tol`` is 0) before the run; the result gains
+    ``gap_records``, ``gap_stop`` and ``gap``."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=30, theta=1 / 4, smoth=5, cycle="w",
                                 isnsp=1, inter=1, guess=None)                          # :87-88
     warm = (0.0, 100) if prob > 0 else (5e-2, np.inf)                                  # :53-58
     ws = APDWorkspace(1, c, r, l, p, q, gama=gama)
     return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol, certificate,
-                       bracket)
+                       bracket, gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install))
 
 
 def APD_SsN_Class2(c, r, l, p, q, mu, phi, rng: MatlabRand | None = None,
                    amg_opts: dict | None = None, krylov: bool = False, plan_tol=None, certificate: bool = False,
-                   bracket: bool = False, **opts) -> dict:
+                   bracket: bool = False, gap_tol=None, gap_rel=None, gap_every=None, gap_first=None,
+                   gap_install=False, **opts) -> dict:
     """The script ``Class2/APD_SsN_Class2.m`` with ``inner_solver = 4`` (AMG4POT 'amg', or
-    'amg_pcg' with ``krylov``).  ``plan_tol``, ``certificate``, ``bracket``: as in ``APD_SsN_Class1``."""
+    'amg_pcg' with ``krylov``).  ``plan_tol``, ``certificate``, ``bracket`` and the ``gap_*`` keywords: as in
+    ``APD_SsN_Class1``."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=40, theta=1 / 4, smoth=10, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     ws = APDWorkspace(2, c, r, l, p, q, mu=mu, phi=phi)
-    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate, bracket)
+    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate, bracket,
+                       gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install))
 
 
 # ---------------------------------------------------------------------------
@@ -1417,31 +1528,34 @@ def point_cost(xs, ys, metric="sqeuclidean", scale=False, stats=False, ctx=None)
 def APD_SsN_Class1_points(xs, ys, r, l, p, q, metric="sqeuclidean", scale=False, gama=np.inf, prob=2,
                           rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
                           plan_tol=None, matrix_free=False, certificate: bool = False, bracket: bool = False,
+                          gap_tol=None, gap_rel=None, gap_every=None, gap_first=None, gap_install=False,
                           **opts) -> dict:
     """``APD_SsN_Class1`` with ``c = point_cost(xs, ys, metric, scale)`` built on the device
-    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``, ``bracket``: as
-    there."""
+    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``, ``bracket`` and the
+    ``gap_*`` keywords: as there."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=30, theta=1 / 4, smoth=5, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     warm = (0.0, 100) if prob > 0 else (5e-2, np.inf)
     ws = APDWorkspace.from_points(1, xs, ys, r, l, p, q, metric=metric, scale=scale, gama=gama,
                                   matrix_free=matrix_free)
     return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol, certificate,
-                       bracket)
+                       bracket, gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install))
 
 
 def APD_SsN_Class2_points(xs, ys, r, l, p, q, mu, phi=None, metric="sqeuclidean", scale=False,
                           rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
                           plan_tol=None, matrix_free=False, certificate: bool = False, bracket: bool = False,
+                          gap_tol=None, gap_rel=None, gap_every=None, gap_first=None, gap_install=False,
                           **opts) -> dict:
     """``APD_SsN_Class2`` with the cost built on the device; ``phi=None`` is all ones
-    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``, ``bracket``: as
-    in ``APD_SsN_Class1``."""
+    (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``, ``bracket`` and the
+    ``gap_*`` keywords: as in ``APD_SsN_Class1``."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=40, theta=1 / 4, smoth=10, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     ws = APDWorkspace.from_points(2, xs, ys, r, l, p, q, metric=metric, scale=scale, mu=mu, phi=phi,
                                   matrix_free=matrix_free)
-    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate, bracket)
+    return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate, bracket,
+                       gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install))
 
 
 def load_input(path: str) -> dict:

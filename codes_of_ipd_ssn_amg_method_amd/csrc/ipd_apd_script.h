@@ -1,8 +1,9 @@
 // The scalar script of the drivers: every decision of APD_SsN_Class{1,2}.m and warmup_class{1,2}.m that the host
 // takes between two passes, written once.  ipd_driver.hip (apd_iterate, the ABI), ipd_apd_passes.hip and
 // ipd_apd_warm.hip call these functions and hold no copy of them.  Host-clean: no HIP types, no getenv -- the CPU
-// test of this header (tests/apd_script_driver.cpp) runs what the library runs.  Every expression keeps the order of
-// operations of the scripts (the library is built with -ffp-contract=off, and so is the test).
+// tests of this header (tests/apd_script_driver.cpp; tests/gap_rule_driver.cpp for the stopping rule on the certified
+// gap, which ipd_bracket.hip and ipd_apd_run's probe take from here) run what the library runs.  Every expression keeps
+// the order of operations of the scripts (the library is built with -ffp-contract=off, and so are the tests).
 #pragma once
 
 #include <algorithm>
@@ -165,6 +166,41 @@ static inline double apd_max_rr(bool cls2, const double kk[4], const double kkt0
 static inline bool apd_restarts(double bk1, double rr, double resk) { return bk1 < 1e-8 && rr > resk; }   // :245
 
 static inline double apd_restart_bk_class2(double bk1) { return 10.0 * bk1; }                 // Class2 :255
+
+// ---------------------------------------------------------------------------
+// the stopping rule on the certified gap (ipd_apd_set_gap_rule)
+// ---------------------------------------------------------------------------
+// a probe follows iteration k: at first, first + every, ... and at the iteration that converged
+static inline bool apd_gap_due(int k, int first, int every, bool converged) {
+    return converged || (k >= first && (k - first) % every == 0);
+}
+
+// the better of the two repaired multipliers: the larger dual value, side 0 on a tie and against a NaN
+// (APDWorkspace.certificate's `1 if d1 > d0 else 0`)
+static inline int apd_gap_lower_side(double dual0, double dual1) { return dual1 > dual0 ? 1 : 0; }
+
+// the better of the two rounded plans: a repaired one first, then the smaller cost, side 0 on a tie and against a NaN
+// (APDWorkspace.bracket's `min((0, 1), key=lambda s: (not ok[s], fval[s]))`)
+static inline int apd_gap_upper_side(int ok0, double fval0, int ok1, double fval1) {
+    return (ok1 > ok0 || (ok1 == ok0 && fval1 < fval0)) ? 1 : 0;
+}
+
+// every probe's dual value bounds f* from below, whatever the iterate: the best one so far stays (a NaN never enters)
+static inline bool apd_gap_improves(double lower, double best) { return lower > best; }
+static inline double apd_gap_best(double lower, double best) { return apd_gap_improves(lower, best) ? lower : best; }
+
+static inline double apd_gap_value(double upper, double best) { return upper - best; }
+
+// thr = max(gap_tol, gap_rel*|upper|); 0: the rule records and never stops
+static inline double apd_gap_threshold(double gap_tol, double gap_rel, double upper) {
+    const double rel = gap_rel * std::fabs(upper);
+    return rel > gap_tol ? rel : gap_tol;   // a NaN upper leaves gap_tol
+}
+
+// a NaN gap never stops
+static inline bool apd_gap_stops(double thr, int upper_ok, double gap) {
+    return thr > 0.0 && upper_ok != 0 && gap <= thr;
+}
 
 // ---------------------------------------------------------------------------
 // routes

@@ -9,14 +9,17 @@
 //   ipd_cost.hip         the cost matrix from point clouds
 //   ipd_dual.hip         the c-transform of the multiplier, the dual value and the duality gap
 //   ipd_round.hip        the iterate rounded to a feasible plan, its exact cost
+//   ipd_bracket.hip      both certificates of a state in one call; the drivers' probe of the certified gap
 #pragma once
 
 #include <functional>
+#include <limits>
 
 #include "ipd_amg_internal.h"
 #include "ipd_hybrid_state.h"
 #include "ipd_apd_script.h"
 #include "ipd_apd_tiles.h"
+#include "ipd_dual_geo.h"
 
 // device-side scalar results (read back through pinned memory)
 struct ApdScal {
@@ -83,6 +86,14 @@ struct ipd_apd {
     size_t s_words = 0;
     unsigned long long *s_prev = nullptr, *t_prev = nullptr;
     int* step_changed = nullptr;
+    // the stopping rule on the certified gap (ipd_apd_set_gap_rule): the rule, whether a probe stopped the loop, the
+    // best lower bound of the probes so far with the multiplier that attains it (L entries of the arena, made by the
+    // first set) and one record per probe
+    bool gap_on = false, gap_stopped = false, gap_have_lam = false;
+    ipd_gap_rule gap_rule{};
+    double gap_best = -std::numeric_limits<double>::infinity();
+    double* gap_lam = nullptr;
+    std::vector<ipd_gap_rec> gap_recs;
     int nblk() const { return (int)apd_nblk(geo); }
 };
 
@@ -162,11 +173,55 @@ float apd_bench_eval(ipd_apd* h, bool merit3, int reps);
 void apd_warmup(ipd_apd* h, double res, long long maxit);
 
 // ---- ipd_dual.hip --------------------------------------------------------------------------
-// (reached through the C ABI only, ipd_apd_dual and ipd_apd_dual_dev: it reads the workspace through the handle
-// above, remembers its divider check in ipd_apd::dual_divider and keeps every temporary in the context's scratch
-// arena)
+// (the certificate itself is reached through the C ABI, ipd_apd_dual and ipd_apd_dual_dev: it reads the workspace
+// through the handle above, remembers its divider check in ipd_apd::dual_divider and keeps every temporary in the
+// context's scratch arena.  ipd_bracket.hip walks c itself and has these launch what ipd_dual.hip defines.)
+constexpr int APD_STATS_DOUBLES = 16;   // doubles a device copy of ipd_dual_stats or ipd_round_stats takes
+bool apd_dual_cap_on(const ipd_apd* h);                // class 1 with finite gama
+void apd_dual_check_divider(ipd_apd* h, int side);     // IPD_E_ARG unless q (side 0) resp. p (side 1) is > 0 and finite
+// k_du_fin: the partials (pv, pi) of a transform of `side` and the held entries of lam_dev -> lam_out_dev (L), arg_dev
+// (du_out_rows entries or nullptr)
+void apd_dual_finish(ipd_apd* h, int side, const double* pv, const int* pi, const double* lam_dev, double* lam_out_dev,
+                     int32_t* arg_dev);
+// k_du_eval: one evaluation of lam_eval into walk_blocks partials
+void apd_dual_eval(ipd_apd* h, const double* lam_eval, int primal, DuEvalPart* part);
+// k_du_last: an evaluation's partials -> *out_dev (device, APD_STATS_DOUBLES doubles)
+void apd_dual_last(ipd_apd* h, const DuEvalPart* part, const double* lam_eval, int primal, ipd_dual_stats* out_dev);
 
 // ---- ipd_round.hip -------------------------------------------------------------------------
-// (reached through the C ABI only, ipd_apd_round and ipd_apd_round_dev: it reads the workspace through the handle
-// above, writes the x (class 2: and y, z) blocks of u and v with install = 1 and nothing else, and keeps every
-// temporary in the context's scratch arena)
+// (ipd_apd_round and ipd_apd_round_dev run the four stages below for one side, ipd_bracket.hip runs pass A once for
+// both.  Every array lives in the context's scratch arena: the caller holds a CallScope.  The workspace is written by
+// apd_round_write with install = 1 only: the x (class 2: and y, z) blocks of u and v.)
+struct RoundShared {
+    double *rpart = nullptr, *cpart = nullptr;   // a pass's row and column partials; the rest of a side overwrites A's
+    double *sA = nullptr, *ab0 = nullptr;        // pass A's scalars; the first marginals [b0 (n); a0 (m)]
+};
+struct RoundSide {
+    int side = 0;
+    double *sc = nullptr, *ab2 = nullptr, *ef = nullptr;   // [kappa; rho], [b2; a2], [f; e]: n + m entries each
+    double *sC = nullptr, *sD = nullptr;                   // the scalars of C and D
+    ipd_round_stats* out = nullptr;                        // device, APD_STATS_DOUBLES doubles
+    void* dev = nullptr;                                   // what k_rd_last leaves for the writing kernels
+};
+// tol, install: IPD_E_ARG; finite gama: IPD_E_UNSUPPORTED
+void apd_round_check_args(const ipd_apd* h, double tol, int32_t install);
+RoundShared apd_round_pass_a(ipd_apd* h, double tol);
+// out_dev: where the statistics go, nullptr: into the scratch
+RoundSide apd_round_first_scale(ipd_apd* h, const RoundShared& sh, int side, ipd_round_stats* out_dev);
+void apd_round_rest(ipd_apd* h, const RoundShared& sh, const RoundSide& s, double tol);
+void apd_round_write(ipd_apd* h, const RoundShared& sh, const RoundSide& s, double tol, int install, double* x_out_dev);
+
+// ---- ipd_bracket.hip -----------------------------------------------------------------------
+// Both certificates of the state in one pass over what they share (ipd_apd_bracket).  The caller
+// holds a CallScope: lam and the sides' arrays live in the scratch arena.
+struct BracketRun {
+    ipd_bracket b;           // read back and picked on the host
+    double tol = 0.0;
+    const double* lam[2] = {nullptr, nullptr};   // the two repaired multipliers (L entries each)
+    RoundShared shared;
+    RoundSide side[2];
+};
+// everything up to the one read-back and the two picks; the workspace is only read
+BracketRun apd_bracket_measure(ipd_apd* h, double tol);
+// the rounded plan of r.b.upper_side becomes the state; r.b.upper.ok must be 1
+void apd_bracket_install(ipd_apd* h, const BracketRun& r);

@@ -275,6 +275,41 @@ void apd_iterate(ipd_apd* h, const ipd_apd_opts& o, const AmgOpts& amg, ipd_rng*
     if (rr <= o.kkt_tol) h->converged = true;                                      // :266
 }
 
+// one probe of the certified gap on the state iteration h->k left: the bracket, the best lower
+// bound so far with its multiplier, the record, and at a stop the install the rule asks for.  Every decision is
+// ipd_apd_script.h's.
+void gap_probe(ipd_apd* h) {
+    ipd_ctx* ctx = h->ctx;
+    const ipd_gap_rule& rule = h->gap_rule;
+    CallScope scope(ctx);
+    const BracketRun r = apd_bracket_measure(h, rule.tol);
+    ipd_gap_rec rec;
+    rec.k = h->k;
+    rec.lower_side = r.b.lower_side;
+    rec.upper_side = r.b.upper_side;
+    rec.upper_ok = r.b.upper.ok;
+    rec.final = h->converged ? 1 : 0;
+    rec.lower = r.b.lower.dual;
+    rec.lower_dmin = r.b.lower.dmin;
+    if (apd_gap_improves(rec.lower, h->gap_best)) {
+        copy_dev(h, h->gap_lam, r.lam[r.b.lower_side], (size_t)h->L);
+        h->gap_have_lam = true;
+    }
+    h->gap_best = apd_gap_best(rec.lower, h->gap_best);
+    rec.best = h->gap_best;
+    rec.upper = r.b.upper.fval;
+    rec.viol_in = r.b.upper.viol_in;
+    rec.gap = apd_gap_value(rec.upper, rec.best);
+    const double thr = apd_gap_threshold(rule.gap_tol, rule.gap_rel, rec.upper);
+    rec.stop = apd_gap_stops(thr, rec.upper_ok, rec.gap) ? 1 : 0;
+    if (rec.stop) {
+        h->gap_stopped = true;
+        if (rule.install) apd_bracket_install(h, r);
+    }
+    ctx->sync();   // the scratch arrays are the next call's
+    h->gap_recs.push_back(rec);
+}
+
 void fill_result(const ipd_apd* h, ipd_apd_result* r) {
     r->converged = h->converged ? 1 : 0;
     r->k = h->k;
@@ -473,6 +508,10 @@ void apd_restart_script(ipd_apd* h) {
     h->recs.clear();
     h->sum_amg = h->total_amg = h->fail_amg = h->max_amg = 0;
     h->restarts = 0;
+    h->gap_stopped = false;
+    h->gap_have_lam = false;
+    h->gap_best = -std::numeric_limits<double>::infinity();
+    h->gap_recs.clear();
 }
 
 extern "C" int ipd_apd_set_krylov(ipd_apd* h, int32_t on) {
@@ -512,10 +551,59 @@ extern "C" int ipd_apd_run(ipd_apd* h, const ipd_apd_opts* o, const ipd_amg_opts
         ao.krylov = h->krylov && oo.inner_solver == 4;
         h->ctx->set_device();
         ensure_kkt(h);
-        for (int it = 0; it < iters && h->k < oo.maxit && !h->converged; ++it)
+        for (int it = 0; it < iters && h->k < oo.maxit && !h->converged && !h->gap_stopped; ++it) {
             apd_iterate(h, oo, ao, rng);
+            if (h->gap_on && apd_gap_due(h->k, h->gap_rule.first, h->gap_rule.every, h->converged)) gap_probe(h);
+        }
         h->ctx->sync();
         if (res) fill_result(h, res);
+    });
+}
+
+extern "C" int ipd_apd_set_gap_rule(ipd_apd* h, const ipd_gap_rule* r) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h, IPD_E_ARG, "NULL handle");
+        if (!r) {
+            h->gap_on = false;
+            h->gap_stopped = false;
+            return;
+        }
+        IPD_REQUIRE(!apd_dual_cap_on(h), IPD_E_UNSUPPORTED,
+                    "ipd_apd_set_gap_rule: the bracket does not apply with finite gama");
+        IPD_REQUIRE(r->gap_tol >= 0.0 && r->gap_rel >= 0.0 && r->tol >= 0.0, IPD_E_ARG,   // a NaN fails the comparison
+                    "ipd_apd_set_gap_rule: gap_tol, gap_rel and tol must be >= 0");
+        IPD_REQUIRE(std::isfinite(r->gap_tol) && std::isfinite(r->gap_rel), IPD_E_ARG,
+                    "ipd_apd_set_gap_rule: gap_tol and gap_rel must be finite");
+        IPD_REQUIRE(r->first >= 1 && r->every >= 1, IPD_E_ARG, "ipd_apd_set_gap_rule: first and every must be >= 1");
+        IPD_REQUIRE(r->install == 0 || r->install == 1, IPD_E_ARG, "ipd_apd_set_gap_rule: install must be 0 or 1");
+        h->ctx->set_device();
+        apd_dual_check_divider(h, 0);
+        apd_dual_check_divider(h, 1);
+        if (!h->gap_lam) h->gap_lam = h->arena->alloc<double>((size_t)h->L);
+        h->gap_rule = *r;
+        h->gap_on = true;
+        h->gap_stopped = false;
+    });
+}
+
+extern "C" int ipd_apd_gap_records(const ipd_apd* h, ipd_gap_rec* out, int64_t cap, int64_t* count) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h && count, IPD_E_ARG, "NULL argument");
+        const int64_t nn = std::min<int64_t>(cap, (int64_t)h->gap_recs.size());
+        if (out)
+            for (int64_t i = 0; i < nn; ++i) out[i] = h->gap_recs[(size_t)i];
+        *count = (int64_t)h->gap_recs.size();
+    });
+}
+
+extern "C" int ipd_apd_gap_lam(ipd_apd* h, double* lam, double* best) {
+    return ipd_guard([&] {
+        IPD_REQUIRE(h, IPD_E_ARG, "NULL handle");
+        if (lam && h->gap_have_lam) {
+            h->ctx->set_device();
+            h->ctx->fetch(h->gap_lam, lam, (size_t)h->L);
+        }
+        if (best) *best = h->gap_best;
     });
 }
 

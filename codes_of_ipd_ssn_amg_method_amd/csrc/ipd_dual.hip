@@ -21,6 +21,10 @@
 //   last       one workgroup: the evaluation's partials in a fixed shape, class 2's alpha and beta blocks of d,
 //              -<b, lam> (thread t adds entries t, t + 256, ... in order, then a fixed tree), the dual value and gap.
 //
+// The host side is cut into the stages of ipd_apd_state.h (apd_dual_finish, apd_dual_eval, apd_dual_last):
+// ipd_bracket.hip walks c itself, for both sides at once, and has them launch what this unit defines.  The keys and
+// colmax16: ipd_dual_dev.h.
+//
 // Geometry and every index: ipd_dual_geo.h.  Deterministic: maxima and minima are order-independent, every sum has a
 // fixed shape, no float atomics -- two calls give the same bits, and so do the host and the device entry.
 #pragma clang fp contract(off)
@@ -30,69 +34,9 @@
 #include <vector>
 
 #include "ipd_apd_state.h"
-#include "ipd_dual_geo.h"
-#include "ipd_walk_dev.h"
+#include "ipd_dual_dev.h"
 
 namespace {
-
-// TR, TC: ipd_apd_geo.h; colsum_index: ipd_apd_tiles.h
-constexpr int DU_NOIDX = 0x7fffffff;                  // the index of a padding lane: behind every row
-constexpr long long DU_NOPLACE = 0x7fffffffffffffffLL;   // the place of "no entry"
-
-// (value descending, index ascending): does (bv, bi) come before (av, ai)?
-__device__ __forceinline__ bool du_before(double bv, int bi, double av, int ai) {
-    return bv > av || (bv == av && bi < ai);
-}
-__device__ __forceinline__ void du_merge(double& v, int& i, double ov, int oi) {
-    const bool take = du_before(ov, oi, v, i);
-    v = take ? ov : v;
-    i = take ? oi : i;
-}
-// (value ascending, place ascending)
-__device__ __forceinline__ void du_merge_min(double& v, long long& i, double ov, long long oi) {
-    const bool take = ov < v || (ov == v && oi < i);
-    v = take ? ov : v;
-    i = take ? oi : i;
-}
-
-// 16 candidates per lane (one per column of a chunk, all of row `row`) -> the 16 column maxima over the wave's 64
-// rows with the rows that reach them: colsum16's butterfly (ipd_apd_tiles.h) on the key.  On return lane l < 16
-// holds the maximum of column colsum_index(l).
-__device__ __forceinline__ void colmax16(const double (&xv)[TC], int row, int lane, double& out_v, int& out_i) {
-    double v8[8], v4[4], v2[2], v1;
-    int i8[8], i4[4], i2[2], i1;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const bool hi = lane & 1;
-        v8[k] = hi ? xv[k + 8] : xv[k];
-        i8[k] = row;
-        du_merge(v8[k], i8[k], __shfl_xor(hi ? xv[k] : xv[k + 8], 1), __shfl_xor(row, 1));
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const bool hi = lane & 2;
-        v4[k] = hi ? v8[k + 4] : v8[k];
-        i4[k] = hi ? i8[k + 4] : i8[k];
-        du_merge(v4[k], i4[k], __shfl_xor(hi ? v8[k] : v8[k + 4], 2), __shfl_xor(hi ? i8[k] : i8[k + 4], 2));
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const bool hi = lane & 4;
-        v2[k] = hi ? v4[k + 2] : v4[k];
-        i2[k] = hi ? i4[k + 2] : i4[k];
-        du_merge(v2[k], i2[k], __shfl_xor(hi ? v4[k] : v4[k + 2], 4), __shfl_xor(hi ? i4[k] : i4[k + 2], 4));
-    }
-    {
-        const bool hi = lane & 8;
-        v1 = hi ? v2[1] : v2[0];
-        i1 = hi ? i2[1] : i2[0];
-        du_merge(v1, i1, __shfl_xor(hi ? v2[0] : v2[1], 8), __shfl_xor(hi ? i2[0] : i2[1], 8));
-    }
-    du_merge(v1, i1, __shfl_xor(v1, 16), __shfl_xor(i1, 16));
-    du_merge(v1, i1, __shfl_xor(v1, 32), __shfl_xor(i1, 32));
-    out_v = v1;
-    out_i = i1;
-}
 
 // ---------------------------------------------------------------------------
 // transform
@@ -460,11 +404,13 @@ __global__ __launch_bounds__(256) void k_du_last(const DuLast a) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-bool cap_on(const ipd_apd* h) { return h->cls == 1 && (h->gama || std::isfinite(h->P.gs)); }
+}  // namespace
+
+bool apd_dual_cap_on(const ipd_apd* h) { return h->cls == 1 && (h->gama || std::isfinite(h->P.gs)); }
 
 // the divider of a transform, q (side 0) or p (side 1), must be positive and finite: read once per workspace (p and q
 // never change after the create) and remembered
-void check_divider(ipd_apd* h, int side) {
+void apd_dual_check_divider(ipd_apd* h, int side) {
     int8_t& known = h->dual_divider[side];
     if (!known) {
         const size_t cnt = side ? (size_t)h->m : (size_t)h->n;
@@ -479,11 +425,69 @@ void check_divider(ipd_apd* h, int side) {
                      : "ipd_apd_dual: side 0 divides by q, which has an entry that is <= 0 or not finite");
 }
 
+void apd_dual_finish(ipd_apd* h, int side, const double* pv, const int* pi, const double* lam_dev, double* lam_out_dev,
+                     int32_t* arg_dev) {
+    DuFin f;
+    f.g = du_make_geo(h->m, h->n, side);
+    f.cls2 = h->cls == 2 ? 1 : 0;
+    f.pv = pv;
+    f.pi = pi;
+    f.lam = lam_dev;
+    f.lam_out = lam_out_dev;
+    f.arg = arg_dev;
+    const dim3 fgrid(cdiv(h->L, 256));
+    if (arg_dev)
+        hipLaunchKernelGGL(k_du_fin<true>, fgrid, dim3(256), 0, h->ctx->stream, f);
+    else
+        hipLaunchKernelGGL(k_du_fin<false>, fgrid, dim3(256), 0, h->ctx->stream, f);
+    IPD_KERNEL_CHECK();
+}
+
+void apd_dual_last(ipd_apd* h, const DuEvalPart* part, const double* lam_eval, int primal, ipd_dual_stats* out_dev) {
+    DuLast l;
+    l.g = du_make_geo(h->m, h->n, 0);   // the shape and the grid: the side is not read
+    l.cls2 = h->cls == 2 ? 1 : 0;
+    l.primal = primal;
+    l.part = part;
+    l.b = h->b;
+    l.lam = lam_eval;
+    l.out = out_dev;
+    hipLaunchKernelGGL(k_du_last, dim3(1), dim3(256), 0, h->ctx->stream, l);
+    IPD_KERNEL_CHECK();
+}
+
+void apd_dual_eval(ipd_apd* h, const double* lam_eval, int primal, DuEvalPart* part) {
+    const DuGeo g = du_make_geo(h->m, h->n, 0);
+    DuEval e;
+    e.g = g;
+    e.cls2 = h->cls == 2 ? 1 : 0;
+    e.cap_on = apd_dual_cap_on(h) ? 1 : 0;
+    e.c = h->c;
+    e.phi = h->phi;
+    e.gama = h->gama;
+    e.gs = h->P.gs;
+    e.p = h->p;
+    e.q = h->q;
+    e.lam = lam_eval;
+    e.x = h->u;   // class 2: the x block of uk comes first
+    e.part = part;
+    const dim3 grid(g.nib, g.ng);
+    with_cost_source(h, [&](auto cs) {
+        if (primal)
+            hipLaunchKernelGGL((k_du_eval<true, decltype(cs)>), grid, dim3(256), 0, h->ctx->stream, e, cs);
+        else
+            hipLaunchKernelGGL((k_du_eval<false, decltype(cs)>), grid, dim3(256), 0, h->ctx->stream, e, cs);
+    });
+    IPD_KERNEL_CHECK();
+}
+
+namespace {
+
 void check_args(ipd_apd* h, int32_t side, int32_t primal, const ipd_dual_stats* st) {
     IPD_REQUIRE(h && st, IPD_E_ARG, "ipd_apd_dual: NULL argument");
     IPD_REQUIRE(side >= -1 && side <= 1, IPD_E_ARG, "ipd_apd_dual: side must be -1, 0 or 1");
     IPD_REQUIRE(primal == 0 || primal == 1, IPD_E_ARG, "ipd_apd_dual: primal must be 0 or 1");
-    IPD_REQUIRE(side < 0 || !cap_on(h), IPD_E_UNSUPPORTED,
+    IPD_REQUIRE(side < 0 || !apd_dual_cap_on(h), IPD_E_UNSUPPORTED,
                 "ipd_apd_dual: with finite gama every multiplier is feasible; only side = -1 applies");
 }
 
@@ -518,57 +522,17 @@ void dual_dev(ipd_apd* h, const double* lam_dev, int side, int primal, double* l
                 hipLaunchKernelGGL((k_du_cols<decltype(cs)>), grid, dim3(256), 0, ctx->stream, a, cs);
         });
         IPD_KERNEL_CHECK();
-        DuFin f;
-        f.g = g;
-        f.cls2 = cls2;
-        f.pv = pv;
-        f.pi = pi;
-        f.lam = lam_dev;
-        f.lam_out = lam_out_dev;
-        f.arg = arg_dev;
-        const dim3 fgrid(cdiv(h->L, 256));
-        if (arg_dev)
-            hipLaunchKernelGGL(k_du_fin<true>, fgrid, dim3(256), 0, ctx->stream, f);
-        else
-            hipLaunchKernelGGL(k_du_fin<false>, fgrid, dim3(256), 0, ctx->stream, f);
-        IPD_KERNEL_CHECK();
+        apd_dual_finish(h, side, pv, pi, lam_dev, lam_out_dev, arg_dev);
         lam_eval = lam_out_dev;
     }
     DuEvalPart* part = reinterpret_cast<DuEvalPart*>(
         S.alloc<double>((size_t)walk_blocks(g) * (sizeof(DuEvalPart) / sizeof(double))));
-    DuEval e;
-    e.g = g;
-    e.cls2 = cls2;
-    e.cap_on = cap_on(h) ? 1 : 0;
-    e.c = h->c;
-    e.phi = h->phi;
-    e.gama = h->gama;
-    e.gs = h->P.gs;
-    e.p = h->p;
-    e.q = h->q;
-    e.lam = lam_eval;
-    e.x = h->u;   // class 2: the x block of uk comes first
-    e.part = part;
-    with_cost_source(h, [&](auto cs) {
-        if (primal)
-            hipLaunchKernelGGL((k_du_eval<true, decltype(cs)>), grid, dim3(256), 0, ctx->stream, e, cs);
-        else
-            hipLaunchKernelGGL((k_du_eval<false, decltype(cs)>), grid, dim3(256), 0, ctx->stream, e, cs);
-    });
-    IPD_KERNEL_CHECK();
-    DuLast l;
-    l.g = g;
-    l.cls2 = cls2;
-    l.primal = primal;
-    l.part = part;
-    l.b = h->b;
-    l.lam = lam_eval;
-    l.out = reinterpret_cast<ipd_dual_stats*>(S.alloc<double>(16));
-    hipLaunchKernelGGL(k_du_last, dim3(1), dim3(256), 0, ctx->stream, l);
-    IPD_KERNEL_CHECK();
-    ctx->fetch_bytes(l.out, st, sizeof(ipd_dual_stats));
+    apd_dual_eval(h, lam_eval, primal, part);
+    ipd_dual_stats* out = reinterpret_cast<ipd_dual_stats*>(S.alloc<double>(APD_STATS_DOUBLES));
+    apd_dual_last(h, part, lam_eval, primal, out);
+    ctx->fetch_bytes(out, st, sizeof(ipd_dual_stats));
 }
-static_assert(sizeof(ipd_dual_stats) <= 16 * sizeof(double) && sizeof(DuEvalPart) % sizeof(double) == 0,
+static_assert(sizeof(ipd_dual_stats) <= APD_STATS_DOUBLES * sizeof(double) && sizeof(DuEvalPart) % sizeof(double) == 0,
               "dual_dev sizes the result and the partials in doubles");
 
 }  // namespace
@@ -581,7 +545,7 @@ extern "C" int ipd_apd_dual_dev(ipd_apd* h, const double* lam_dev, int32_t side,
     return ipd_guard([&] {
         check_args(h, side, primal, st);
         CallScope scope(h->ctx);
-        if (side >= 0) check_divider(h, side);
+        if (side >= 0) apd_dual_check_divider(h, side);
         ipd_dual_stats got;
         dual_dev(h, lam_dev ? lam_dev : h->lam, side, primal, lam_out_dev, arg_dev, &got);
         h->ctx->sync();   // the scratch arrays are the next call's
@@ -595,7 +559,7 @@ extern "C" int ipd_apd_dual(ipd_apd* h, const double* lam, int32_t side, int32_t
         check_args(h, side, primal, st);
         ipd_ctx* ctx = h->ctx;
         CallScope scope(ctx);
-        if (side >= 0) check_divider(h, side);
+        if (side >= 0) apd_dual_check_divider(h, side);
         Arena& S = *ctx->scratch;
         const size_t L = (size_t)h->L, R = side > 0 ? (size_t)h->n : (size_t)h->m;
         const double* lam_dev = h->lam;

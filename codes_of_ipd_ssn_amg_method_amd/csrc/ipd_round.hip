@@ -24,6 +24,9 @@
 // W and slack read ok from the device and write nothing when install was asked and ok = 0: the host learns of it
 // from the one read-back of the statistics.
 //
+// The host side is four stages (ipd_apd_state.h: apd_round_pass_a, apd_round_first_scale, apd_round_rest,
+// apd_round_write): a call here runs them for one side, ipd_bracket.hip runs pass A once for both sides.
+//
 // Geometry and every index: ipd_round_geo.h.  Deterministic: every sum has a fixed shape, no float atomics -- two
 // calls give the same bits, and so do the host and the device entry and the three cost sources.
 #pragma clang fp contract(off)
@@ -44,7 +47,7 @@ struct RdDev {
     double theta, t, se, sf;
     long long ok;
 };
-static_assert(sizeof(ipd_round_stats) <= 16 * sizeof(double) && sizeof(RdDev) <= 8 * sizeof(double) &&
+static_assert(sizeof(ipd_round_stats) <= APD_STATS_DOUBLES * sizeof(double) && sizeof(RdDev) <= 8 * sizeof(double) &&
                   RD_RESULT_DOUBLES == 24,
               "round_dev sizes the result in doubles");
 
@@ -389,124 +392,169 @@ __global__ __launch_bounds__(256) void k_rd_slack(const RdSlack a) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-void check_args(const ipd_apd* h, double tol, int32_t side, int32_t install, const ipd_round_stats* st) {
-    IPD_REQUIRE(h && st, IPD_E_ARG, "ipd_apd_round: NULL argument");
-    IPD_REQUIRE(side == 0 || side == 1, IPD_E_ARG, "ipd_apd_round: side must be 0 or 1");
-    IPD_REQUIRE(install == 0 || install == 1, IPD_E_ARG, "ipd_apd_round: install must be 0 or 1");
-    IPD_REQUIRE(tol >= 0.0, IPD_E_ARG, "ipd_apd_round: tol must be >= 0");   // a NaN fails the comparison
-    IPD_REQUIRE(!(h->cls == 1 && (h->gama || std::isfinite(h->P.gs))), IPD_E_UNSUPPORTED,
-                "ipd_apd_round: the rank-one correction does not keep x <= gama; finite gama is not supported");
-}
-
-struct RdVecs {
-    const double* sc;   // [kappa (n); rho (m)]
-    const double* ef;   // [f (n); e (m)]
-};
-
 template <int PASS, class CS = CostStored>
 void launch_walk(ipd_apd* h, const RdWalk& a, CS cs = CS()) {
     hipLaunchKernelGGL((k_rd_walk<PASS, CS>), dim3(a.g.nib, a.g.ng), dim3(256), 0, h->ctx->stream, a, cs);
     IPD_KERNEL_CHECK();
 }
 
-// all launches of a call on the context's stream; *st is read back (the stream is waited for).  IPD_E_NUMERIC when
-// install was asked and ok = 0: the device wrote nothing then.
-RdVecs round_dev(ipd_apd* h, double tol, int side, int install, double* x_out_dev, ipd_round_stats* st) {
-    ipd_ctx* ctx = h->ctx;
-    Arena& S = *ctx->scratch;
-    const RdGeo g = walk_make_geo(h->m, h->n);
-    const int cls2 = h->cls == 2 ? 1 : 0;
-    const size_t M = (size_t)h->M;
-    double* rpart = S.alloc<double>(walk_row_part_len(g));
-    double* cpart = S.alloc<double>(walk_col_part_len(g));
-    double* sA = S.alloc<double>(rd_scal_len(g));
-    double* sC = S.alloc<double>(rd_scal_len(g));
-    double* sD = S.alloc<double>(rd_scal_len(g));
-    double* ab0 = S.alloc<double>(M);
-    double* sc = S.alloc<double>(M);
-    double* ab2 = S.alloc<double>(M);
-    double* ef = S.alloc<double>(M);
-    ipd_round_stats* out = reinterpret_cast<ipd_round_stats*>(S.alloc<double>(16));
-    RdDev* dev = reinterpret_cast<RdDev*>(S.alloc<double>(8));
-
+RdWalk walk_args(ipd_apd* h, const RoundShared& sh, const RoundSide& s, double tol) {
     RdWalk w;
-    w.g = g;
-    w.cls2 = cls2;
-    w.need_ok = install;
+    w.g = walk_make_geo(h->m, h->n);
+    w.cls2 = h->cls == 2 ? 1 : 0;
+    w.need_ok = 0;
     w.tol = tol;
     w.x = h->u;   // class 2: the x block of uk comes first
     w.c = h->c;
     w.phi = h->phi;
     w.p = h->p;
     w.q = h->q;
-    w.sc = sc;
-    w.ef = ef;
-    w.dev = dev;
-    w.rpart = rpart;
-    w.cpart = cpart;
-    w.spart = sA;
-    w.o0 = x_out_dev;
-    w.o1 = install ? h->u : nullptr;
-    w.o2 = install ? h->v : nullptr;
+    w.sc = s.sc;
+    w.ef = s.ef;
+    w.dev = static_cast<const RdDev*>(s.dev);
+    w.rpart = sh.rpart;
+    w.cpart = sh.cpart;
+    w.spart = sh.sA;
+    w.o0 = w.o1 = w.o2 = nullptr;
+    return w;
+}
+
+RdFin fin_args(ipd_apd* h, const RoundShared& sh, const RoundSide& s) {
     RdFin f;
-    f.g = g;
-    f.side = side;
-    f.rpart = rpart;
-    f.cpart = cpart;
+    f.g = walk_make_geo(h->m, h->n);
+    f.side = s.side;
+    f.rpart = sh.rpart;
+    f.cpart = sh.cpart;
     f.b = h->b;
-    f.ab0 = ab0;
-    f.sc = sc;
-    f.ab2 = ab2;
-    f.ef = ef;
-    const dim3 fgrid(cdiv((long long)M, 256));
-    launch_walk<RD_A>(h, w);
-    hipLaunchKernelGGL(k_rd_fin<0>, fgrid, dim3(256), 0, ctx->stream, f);
+    f.ab0 = sh.ab0;
+    f.sc = s.sc;
+    f.ab2 = s.ab2;
+    f.ef = s.ef;
+    return f;
+}
+
+dim3 fin_grid(const ipd_apd* h) { return dim3(cdiv((long long)h->M, 256)); }
+
+}  // namespace
+
+// pass A: the first marginals' partials and the scalars of the clamp, shared by the two sides
+RoundShared apd_round_pass_a(ipd_apd* h, double tol) {
+    Arena& S = *h->ctx->scratch;
+    const RdGeo g = walk_make_geo(h->m, h->n);
+    RoundShared sh;
+    sh.rpart = S.alloc<double>(walk_row_part_len(g));
+    sh.cpart = S.alloc<double>(walk_col_part_len(g));
+    sh.sA = S.alloc<double>(rd_scal_len(g));
+    sh.ab0 = S.alloc<double>((size_t)h->M);
+    launch_walk<RD_A>(h, walk_args(h, sh, RoundSide{}, tol));
+    return sh;
+}
+
+// one side's arrays and its first scale vector out of pass A's partials, which the rest of a side overwrites
+RoundSide apd_round_first_scale(ipd_apd* h, const RoundShared& sh, int side, ipd_round_stats* out_dev) {
+    Arena& S = *h->ctx->scratch;
+    const RdGeo g = walk_make_geo(h->m, h->n);
+    const size_t M = (size_t)h->M;
+    RoundSide s;
+    s.side = side;
+    s.sC = S.alloc<double>(rd_scal_len(g));
+    s.sD = S.alloc<double>(rd_scal_len(g));
+    s.sc = S.alloc<double>(M);
+    s.ab2 = S.alloc<double>(M);
+    s.ef = S.alloc<double>(M);
+    s.out = out_dev ? out_dev : reinterpret_cast<ipd_round_stats*>(S.alloc<double>(APD_STATS_DOUBLES));
+    s.dev = S.alloc<double>(8);
+    hipLaunchKernelGGL(k_rd_fin<0>, fin_grid(h), dim3(256), 0, h->ctx->stream, fin_args(h, sh, s));
     IPD_KERNEL_CHECK();
-    if (side == 0)
+    return s;
+}
+
+// B, C, D with their finishing kernels and the last kernel: s.out and s.dev are complete on the stream afterwards
+void apd_round_rest(ipd_apd* h, const RoundShared& sh, const RoundSide& s, double tol) {
+    ipd_ctx* ctx = h->ctx;
+    RdWalk w = walk_args(h, sh, s, tol);
+    const RdFin f = fin_args(h, sh, s);
+    if (s.side == 0)
         launch_walk<RD_B0>(h, w);
     else
         launch_walk<RD_B1>(h, w);
-    hipLaunchKernelGGL(k_rd_fin<1>, fgrid, dim3(256), 0, ctx->stream, f);
+    hipLaunchKernelGGL(k_rd_fin<1>, fin_grid(h), dim3(256), 0, ctx->stream, f);
     IPD_KERNEL_CHECK();
-    w.spart = sC;
+    w.spart = s.sC;
     with_cost_source(h, [&](auto cs) { launch_walk<RD_C>(h, w, cs); });
-    hipLaunchKernelGGL(k_rd_fin<2>, fgrid, dim3(256), 0, ctx->stream, f);
+    hipLaunchKernelGGL(k_rd_fin<2>, fin_grid(h), dim3(256), 0, ctx->stream, f);
     IPD_KERNEL_CHECK();
-    w.spart = sD;
+    w.spart = s.sD;
     with_cost_source(h, [&](auto cs) { launch_walk<RD_D>(h, w, cs); });
     RdLast l;
-    l.g = g;
-    l.cls2 = cls2;
+    l.g = w.g;
+    l.cls2 = w.cls2;
     l.mu = h->mu;
-    l.sA = sA;
-    l.sC = sC;
-    l.sD = sD;
-    l.ab0 = ab0;
-    l.ef = ef;
+    l.sA = sh.sA;
+    l.sC = s.sC;
+    l.sD = s.sD;
+    l.ab0 = sh.ab0;
+    l.ef = s.ef;
     l.b = h->b;
     l.p = h->p;
     l.q = h->q;
-    l.out = out;
-    l.dev = dev;
+    l.out = s.out;
+    l.dev = static_cast<RdDev*>(s.dev);
     hipLaunchKernelGGL(k_rd_last, dim3(1), dim3(256), 0, ctx->stream, l);
     IPD_KERNEL_CHECK();
-    if (install || x_out_dev) launch_walk<RD_W>(h, w);
-    if (install && cls2) {
-        RdSlack s;
-        s.g = g;
-        s.dev = dev;
-        s.ab2 = ab2;
-        s.ef = ef;
-        s.b = h->b;
-        s.u_yz = h->u + h->mn;
-        s.v_yz = h->v + h->mn;
-        hipLaunchKernelGGL(k_rd_slack, fgrid, dim3(256), 0, ctx->stream, s);
+}
+
+// X^ of a finished side to x_out_dev (or nullptr) and, with install, into the state (class 2: with its slacks); the
+// kernels read ok from the device and write nothing when install was asked and ok = 0
+void apd_round_write(ipd_apd* h, const RoundShared& sh, const RoundSide& s, double tol, int install,
+                     double* x_out_dev) {
+    if (!install && !x_out_dev) return;
+    RdWalk w = walk_args(h, sh, s, tol);
+    w.need_ok = install;
+    w.o0 = x_out_dev;
+    w.o1 = install ? h->u : nullptr;
+    w.o2 = install ? h->v : nullptr;
+    launch_walk<RD_W>(h, w);
+    if (install && h->cls == 2) {
+        RdSlack k;
+        k.g = w.g;
+        k.dev = static_cast<const RdDev*>(s.dev);
+        k.ab2 = s.ab2;
+        k.ef = s.ef;
+        k.b = h->b;
+        k.u_yz = h->u + h->mn;
+        k.v_yz = h->v + h->mn;
+        hipLaunchKernelGGL(k_rd_slack, fin_grid(h), dim3(256), 0, h->ctx->stream, k);
         IPD_KERNEL_CHECK();
     }
-    ctx->fetch_bytes(out, st, sizeof(ipd_round_stats));
+}
+
+void apd_round_check_args(const ipd_apd* h, double tol, int32_t install) {
+    IPD_REQUIRE(install == 0 || install == 1, IPD_E_ARG, "ipd_apd_round: install must be 0 or 1");
+    IPD_REQUIRE(tol >= 0.0, IPD_E_ARG, "ipd_apd_round: tol must be >= 0");   // a NaN fails the comparison
+    IPD_REQUIRE(!(h->cls == 1 && (h->gama || std::isfinite(h->P.gs))), IPD_E_UNSUPPORTED,
+                "ipd_apd_round: the rank-one correction does not keep x <= gama; finite gama is not supported");
+}
+
+namespace {
+
+void check_args(const ipd_apd* h, double tol, int32_t side, int32_t install, const ipd_round_stats* st) {
+    IPD_REQUIRE(h && st, IPD_E_ARG, "ipd_apd_round: NULL argument");
+    IPD_REQUIRE(side == 0 || side == 1, IPD_E_ARG, "ipd_apd_round: side must be 0 or 1");
+    apd_round_check_args(h, tol, install);
+}
+
+// all launches of a call on the context's stream; *st is read back (the stream is waited for).  IPD_E_NUMERIC when
+// install was asked and ok = 0: the device wrote nothing then.
+RoundSide round_dev(ipd_apd* h, double tol, int side, int install, double* x_out_dev, ipd_round_stats* st) {
+    const RoundShared sh = apd_round_pass_a(h, tol);
+    const RoundSide s = apd_round_first_scale(h, sh, side, nullptr);
+    apd_round_rest(h, sh, s, tol);
+    apd_round_write(h, sh, s, tol, install, x_out_dev);
+    h->ctx->fetch_bytes(s.out, st, sizeof(ipd_round_stats));
     if (install && !st->ok)
         throw IpdError(IPD_E_NUMERIC, "ipd_apd_round: no repair of this shape exists (ok = 0); nothing was installed");
-    return RdVecs{sc, ef};
+    return s;
 }
 
 }  // namespace
@@ -521,7 +569,7 @@ extern "C" int ipd_apd_round_dev(ipd_apd* h, double tol, int32_t side, int32_t i
         check_args(h, tol, side, install, st);
         CallScope scope(h->ctx);
         ipd_round_stats got;
-        const RdVecs v = round_dev(h, tol, side, install, x_out_dev, &got);
+        const RoundSide v = round_dev(h, tol, side, install, x_out_dev, &got);
         const size_t n = (size_t)h->n, m = (size_t)h->m;
         if (rho_dev) copy_dev(h, rho_dev, v.sc + n, m);
         if (kappa_dev) copy_dev(h, kappa_dev, v.sc, n);
@@ -539,7 +587,7 @@ extern "C" int ipd_apd_round(ipd_apd* h, double tol, int32_t side, int32_t insta
         ipd_ctx* ctx = h->ctx;
         CallScope scope(ctx);
         ipd_round_stats got;
-        const RdVecs v = round_dev(h, tol, side, install, nullptr, &got);
+        const RoundSide v = round_dev(h, tol, side, install, nullptr, &got);
         const size_t n = (size_t)h->n, m = (size_t)h->m;
         if (rho) ctx->fetch(v.sc + n, rho, m);
         if (kappa) ctx->fetch(v.sc, kappa, n);

@@ -1,6 +1,7 @@
 // The frame of the kernels that walk an m x n array by column groups (ipd_walk_geo.h): k_pa_rows
-// and k_pa_cols (ipd_plan_apply.hip), k_du_rows, k_du_cols and k_du_eval (ipd_dual.hip) and, with the driver's own
-// geometry, k_plan_count and k_plan_fill (ipd_plan.hip); k_rd_last (ipd_round.hip) takes the workgroup sums.  Device
+// and k_pa_cols (ipd_plan_apply.hip), k_du_rows, k_du_cols and k_du_eval (ipd_dual.hip), k_du_both and k_du_eval2
+// (ipd_bracket.hip) and, with the driver's own geometry, k_plan_count and k_plan_fill (ipd_plan.hip); k_rd_last
+// (ipd_round.hip) takes the workgroup sums.  Device
 // only, everything inlined and decided at compile time.  The helpers are as small as they are on purpose: these
 // kernels are held to the machine code they were measured with, and that code moves with the shape of the source --
 // a helper that owns the loop over a chunk's 16 loads changes the address arithmetic, so walk_place gives the place
@@ -13,7 +14,7 @@
 // the caller.  No LDS tile, no barrier inside the chunk loop.  What is uniform over the wave per column (q, a
 // multiplier, the coordinates) is fetched by lane l for column walk_lane_col and handed round with __shfl: 16 uniform
 // loads per array would hold scalar registers the kernels cannot spare.  The 16 column results of a chunk over the
-// wave's 64 rows come out of colsum16's butterfly (ipd_apd_tiles.h) or colmax16's (ipd_dual.hip), which leaves the
+// wave's 64 rows come out of colsum16's butterfly (ipd_apd_tiles.h) or colmax16's (ipd_dual_dev.h), which leaves the
 // result of column j0 + colsum_index(l) in lane l < 16.
 #pragma once
 

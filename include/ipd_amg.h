@@ -638,6 +638,66 @@ int ipd_apd_round_dev(ipd_apd* h, double tol, int32_t side, int32_t install,
                       double* rho_dev, double* kappa_dev, double* e_dev, double* f_dev,
                       double* x_out_dev, ipd_round_stats* st);   /* device arrays; st on the host */
 
+/* Both certificates of the state in one call: lower <= f* <= upper.  The two c-transforms of the
+ * workspace's lk are formed in one walk over c (class 2: and phi), the two repaired multipliers are evaluated in one
+ * read of c and x, the rounding's first pass runs once for both sides, and the four statistics come back in one
+ * read-back; the host then picks
+ *    lower_side = dual1 > dual0 ? 1 : 0
+ *    upper_side = (ok1 > ok0 || (ok1 == ok0 && fval1 < fval0)) ? 1 : 0
+ * Every field of lower, and lam_out (L entries or NULL), has the bits of ipd_apd_dual(h, NULL, lower_side, 1, ..);
+ * every field of upper, and rho (m), kappa (n), e (m), f (n) -- each may be NULL -- those of
+ * ipd_apd_round(h, tol, upper_side, 0, ..): per-entry operations and summation shapes are the ones stated there, and
+ * the maxima and minima do not depend on an order.  gap = upper.fval - lower.dual, one subtraction.  install = 1 makes
+ * the rounded plan of upper_side the state, as ipd_apd_round(.., upper_side, 1, ..) does; with upper.ok = 0 it is
+ * refused with IPD_E_NUMERIC and nothing is written.  With install = 0 the workspace is only read.  Two calls, the two
+ * entries, and stored, point-cloud and matrix-free workspaces give the same bits.
+ * IPD_E_ARG for a NULL h or out, install outside {0, 1}, tol negative or NaN, p or q with an entry that is <= 0 or not
+ * finite; IPD_E_UNSUPPORTED for a class-1 workspace with finite gama; nothing is written then.                   */
+typedef struct ipd_bracket {
+    ipd_dual_stats lower;             /* of the chosen repaired multiplier                                      */
+    ipd_round_stats upper;            /* of the chosen rounded plan                                             */
+    int32_t lower_side, upper_side;
+    double gap;                       /* upper.fval - lower.dual                                                */
+} ipd_bracket;
+int ipd_apd_bracket(ipd_apd* h, double tol, int32_t install, double* lam_out,
+                    double* rho, double* kappa, double* e, double* f, ipd_bracket* out);          /* host arrays */
+int ipd_apd_bracket_dev(ipd_apd* h, double tol, int32_t install, double* lam_out_dev,
+                        double* rho_dev, double* kappa_dev, double* e_dev, double* f_dev,
+                        ipd_bracket* out);                               /* device arrays; out on the host */
+
+/* A stopping rule of ipd_apd_run on the certified gap.  With a rule set, the bracket above is taken
+ * of the state an iteration leaves -- a probe -- after iteration k when
+ *    converged || (k >= first && (k - first) % every == 0)
+ * so a run that converges always ends with a probe of its final state (final = 1).  Per probe, in this order:
+ *    best  = lower > best ? lower : best      (from -inf; every probe's dual value bounds f*, whatever the iterate;
+ *                                              the multiplier that attains best is kept on the device)
+ *    gap   = upper - best
+ *    thr   = max(gap_tol, gap_rel*|upper|)    (both 0: probe and record, never stop)
+ *    stop  = thr > 0 && upper_ok && gap <= thr    (a NaN never stops)
+ * At a stop the loop ends; ipd_apd_result.converged stays the KKT flag, and further ipd_apd_run calls return at once
+ * until the rule is set again, which clears the stop and keeps best and the records.  install = 1 makes the rounded
+ * plan the state at the probe that stops, and only there; histories, records, lk and bk stay as ipd_apd_round leaves
+ * them.  ipd_apd_set_state (a restart of the script) clears the stop, best and the records; the rule holds until it
+ * is changed, NULL switches it off (the default).  Without a rule a run is what it was.
+ * ipd_apd_set_gap_rule: IPD_E_UNSUPPORTED for a class-1 workspace with finite gama; IPD_E_ARG for p or q with an entry
+ * that is <= 0 or not finite, gap_tol, gap_rel or tol negative or NaN, first or every < 1, install outside {0, 1};
+ * the rule in force stays then.
+ * ipd_apd_gap_records: as ipd_apd_records.  ipd_apd_gap_lam: *best and, into lam (L entries, host, may be NULL), the
+ * multiplier that attains it; before the first probe *best = -inf and lam is not written.                        */
+typedef struct ipd_gap_rule {
+    double gap_tol, gap_rel;
+    double tol;                       /* the rounding's threshold                                               */
+    int32_t first, every;             /* both >= 1                                                              */
+    int32_t install;
+} ipd_gap_rule;
+typedef struct ipd_gap_rec {
+    int32_t k, lower_side, upper_side, upper_ok, stop, final;
+    double lower, lower_dmin, best, upper, viol_in, gap;    /* gap = upper - best */
+} ipd_gap_rec;
+int ipd_apd_set_gap_rule(ipd_apd* h, const ipd_gap_rule* r);
+int ipd_apd_gap_records(const ipd_apd* h, ipd_gap_rec* out, int64_t cap, int64_t* count);
+int ipd_apd_gap_lam(ipd_apd* h, double* lam, double* best);
+
 /* The cost matrix built on the device from two point clouds: a driver run is created
  * from (m+n)*d coordinates, nothing mn-sized crosses the host boundary.  With t_k = xs(i,k) - ys(j,k)
  * folded in ascending k into an accumulator that starts at +0.0, multiply and add separate:
