@@ -92,6 +92,11 @@ class ipd_round_stats(Structure):
                 ("dropped", c_double), ("ndropped", c_int64), ("ok", c_int32)]
 
 
+class ipd_correction_info(Structure):
+    _fields_ = [("mode", c_int32), ("form", c_int32), ("count", c_int64), ("cc", c_double * 2),
+                ("fval", c_double * 2)]
+
+
 class ipd_bracket(Structure):
     _fields_ = [("lower", ipd_dual_stats), ("upper", ipd_round_stats), ("lower_side", c_int32),
                 ("upper_side", c_int32), ("gap", c_double)]
@@ -172,6 +177,10 @@ lib.ipd_apd_round_dev.argtypes = [c_void_p, c_double, c_int32, c_int32, c_void_p
                                   c_void_p, c_void_p]
 lib.ipd_apd_bracket.argtypes = [c_void_p, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_bracket_dev.argtypes = lib.ipd_apd_bracket.argtypes
+lib.ipd_apd_set_correction.argtypes = [c_void_p, c_int32, c_void_p, c_void_p]
+lib.ipd_apd_correction_entries.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
+lib.ipd_apd_correction_entries_dev.argtypes = lib.ipd_apd_correction_entries.argtypes
+lib.ipd_apd_correction_info.argtypes = [c_void_p, c_void_p]
 lib.ipd_apd_set_gap_rule.argtypes = [c_void_p, c_void_p]
 lib.ipd_apd_gap_records.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
 lib.ipd_apd_gap_lam.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -216,6 +225,8 @@ EXPORTS = [
     "ipd_apd_dual", "ipd_apd_dual_dev",
     "ipd_apd_round", "ipd_apd_round_dev",
     "ipd_apd_bracket", "ipd_apd_bracket_dev",
+    "ipd_apd_set_correction", "ipd_apd_correction_entries", "ipd_apd_correction_entries_dev",
+    "ipd_apd_correction_info",
     "ipd_apd_set_gap_rule", "ipd_apd_gap_records", "ipd_apd_gap_lam",
     "ipd_cost_points_dev", "ipd_apd_create_points", "ipd_apd_get_cost",
     "ipd_apd_create_points_free", "ipd_apd_cost_info",

@@ -31,7 +31,7 @@ __all__ = [
     "warmup_class2", "APD_SsN_Class1", "APD_SsN_Class2", "twogrid_bigph", "twogrid", "Hybrid_twogrid",
     "aug_PCG", "PCG4POT", "load_input", "sparse_multiply", "spd_solve", "AMG_PCG",
     "Class_AMG_multi", "AMG_PCG_multi", "Hybrid_AMG_PCG",
-    "point_cost", "APD_SsN_Class1_points", "APD_SsN_Class2_points",
+    "point_cost", "projection_order", "APD_SsN_Class1_points", "APD_SsN_Class2_points",
 ]
 
 
@@ -1246,6 +1246,51 @@ class APDWorkspace:
         check(lib.ipd_apd_gap_lam(self.handle, lam.ctypes.data, byref(best)))
         return (lam if best.value > -np.inf else None), best.value
 
+    # -- the rounding's correction ----------------------------------------------
+    CORRECTION_MODES = {"rank_one": 0, "north_west": 1, "cheaper": 2}
+
+    def set_correction(self, mode="rank_one", row_order=None, col_order=None) -> None:
+        """What carries the rounding's deficits (``ipd_apd_set_correction``): ``"rank_one"``, the dense term
+        ``t*e_i*f_j`` (the default, in the bits of a workspace without the setting); ``"north_west"``, a
+        north-west-corner coupling along ``row_order`` and ``col_order`` (permutations of ``0..m-1`` and ``0..n-1``,
+        None: the identity) with at most ``m + n - 1`` entries and no walk over the cost; ``"cheaper"``, both, and the
+        device keeps the one with ``ok`` first, then the smaller ``fval``.  ``round_plan``, ``round_plan_dev``,
+        ``bracket``, ``gap_probe``, ``gap_probe_dev`` and the gap rule's probes obey it."""
+        if mode not in self.CORRECTION_MODES:
+            raise ValueError("set_correction: mode must be one of %s" % sorted(self.CORRECTION_MODES))
+        orders = []
+        for a, need, name in ((row_order, self.m, "row_order"), (col_order, self.n, "col_order")):
+            if a is not None:
+                a = np.ascontiguousarray(a)
+                if a.ndim != 1 or a.size != need or not np.issubdtype(a.dtype, np.integer):
+                    raise ValueError(f"set_correction: {name} must hold {need} integers")
+                # (what does not fit int32 stays outside 0..need-1: the library refuses it)
+                a = np.clip(a.astype(np.int64), -1, 2 ** 31 - 1).astype(np.int32)
+            orders.append(a)
+        check(lib.ipd_apd_set_correction(self.handle, c_int32(self.CORRECTION_MODES[mode]),
+                                         *[a.ctypes.data if a is not None else None for a in orders]))
+
+    def correction_info(self) -> dict:
+        """Of the last rounding or bracket call (``ipd_apd_correction_info``): ``mode`` of that call, ``form`` it used
+        (0 rank-one, 1 north-west), ``count`` of its list and, under ``"cheaper"``, ``cc`` and ``fval`` of both forms
+        (``[0]`` rank-one, ``[1]`` north-west; NaN otherwise)."""
+        out = L.ipd_correction_info()
+        check(lib.ipd_apd_correction_info(self.handle, byref(out)))
+        return dict(mode=int(out.mode), form=int(out.form), count=int(out.count), cc=tuple(out.cc),
+                    fval=tuple(out.fval))
+
+    def correction_entries(self):
+        """``(i, j, g)`` of the last rounding or bracket call's list (``ipd_apd_correction_entries``), in ascending
+        order along the two orders: ``X^ = theta*X2`` plus ``t*g`` at ``(i, j)``.  Empty when that call used the
+        rank-one term."""
+        cnt = c_int64()
+        check(lib.ipd_apd_correction_entries(self.handle, None, None, None, c_int64(0), byref(cnt)))
+        i, j, g = np.empty(cnt.value, np.int32), np.empty(cnt.value, np.int32), np.empty(cnt.value)
+        if cnt.value:
+            check(lib.ipd_apd_correction_entries(self.handle, i.ctypes.data, j.ctypes.data, g.ctypes.data,
+                                                 c_int64(cnt.value), byref(cnt)))
+        return i, j, g
+
     # -- the loop -------------------------------------------------------------
     def options(self, **kw) -> L.ipd_apd_opts:
         o = L.ipd_apd_opts()
@@ -1407,8 +1452,11 @@ def warmup_class2(c, r, l, p, q, mu, phi, res=None, maxit=None):
 
 
 def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool = False,
-                plan_tol=None, certificate: bool = False, bracket: bool = False, gap: dict | None = None) -> dict:
+                plan_tol=None, certificate: bool = False, bracket: bool = False, gap: dict | None = None,
+                correction: dict | None = None) -> dict:
     try:
+        if correction is not None:
+            ws.set_correction(**correction)
         if bracket and ws._finite_gama:     # before the run, not after it
             raise ValueError("bracket: rounding does not keep x <= gama; finite gama is not supported")
         if warm is not None:
@@ -1428,6 +1476,8 @@ def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool 
             out["certificate"] = ws.certificate()
         if bracket:
             out["bracket"] = ws.bracket()
+        if correction is not None and (bracket or gap is not None):
+            out["correction"] = ws.correction_info()   # of the last rounding: the bracket's, else the last probe's
         return out
     finally:
         ws.close()
@@ -1441,10 +1491,43 @@ def _gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install):
                 every=1 if gap_every is None else gap_every, install=bool(gap_install))
 
 
+def projection_order(xs, ys):
+    """``(row_order, col_order)`` for ``set_correction``: the stable argsorts of the two clouds (``xs`` m x d, ``ys``
+    n x d) projected on the first principal axis of their union.  numpy, on the host, run once."""
+    xs, ys = np.asarray(xs, dtype=np.float64), np.asarray(ys, dtype=np.float64)
+    xs = xs[:, None] if xs.ndim == 1 else xs
+    ys = ys[:, None] if ys.ndim == 1 else ys
+    if xs.ndim != 2 or ys.ndim != 2 or xs.shape[1] != ys.shape[1]:
+        raise ValueError("projection_order: xs must be (m, d) and ys (n, d), one point per row")
+    both = np.concatenate([xs, ys])
+    centred = both - both.mean(axis=0)
+    axis = np.linalg.svd(centred, full_matrices=False)[2][0]
+    lead = np.argmax(np.abs(axis))
+    if axis[lead] < 0:    # the sign of a singular vector is arbitrary: its largest component positive
+        axis = -axis
+    t = centred @ axis
+    return (np.argsort(t[:len(xs)], kind="stable").astype(np.int32),
+            np.argsort(t[len(xs):], kind="stable").astype(np.int32))
+
+
+def _correction_keywords(correction, correction_order, points=None):
+    """the drivers' ``correction`` and ``correction_order`` keywords as ``set_correction``'s; None when neither was
+    given.  ``points``: the two clouds of a ``_points`` driver, which allow ``correction_order="projection"``."""
+    if correction is None and correction_order is None:
+        return None
+    if isinstance(correction_order, str):
+        if correction_order != "projection" or points is None:
+            raise ValueError('correction_order must be None, (row_order, col_order) or, in the drivers that take '
+                             'point clouds, "projection"')
+        correction_order = projection_order(*points)
+    row, col = correction_order if correction_order is not None else (None, None)
+    return dict(mode=correction if correction is not None else "rank_one", row_order=row, col_order=col)
+
+
 def APD_SsN_Class1(c, r, l, p, q, gama=np.inf, prob=2, rng: MatlabRand | None = None,
                    amg_opts: dict | None = None, krylov: bool = False, plan_tol=None, certificate: bool = False,
                    bracket: bool = False, gap_tol=None, gap_rel=None, gap_every=None, gap_first=None,
-                   gap_install=False, **opts) -> dict:
+                   gap_install=False, correction=None, correction_order=None, **opts) -> dict:
     """The script ``Class1/APD_SsN_Class1.m`` with ``inner_solver = 4`` on the workspace it
     loads (``:27``); returns the variables it leaves behind.  Warm start as ``:53-59``.
     ``krylov``: see ``APDWorkspace.run``.  ``plan_tol``: when given, the result gains ``plan`` (the
@@ -1456,19 +1539,24 @@ def APD_SsN_Class1(c, r, l, p, q, gama=np.inf, prob=2, rng: MatlabRand | None = 
     ``xk`` rounded to a feasible plan with its exact cost as ``upper``, and their ``gap``; not with finite ``gama``).
     ``gap_tol``, ``gap_rel``, ``gap_every``, ``gap_first``, ``gap_install``: any of them sets the stopping rule on the
     certified gap (``APDWorkspace.set_gap_rule``; the rounding's ``tol`` is 0) before the run; the result gains
-    ``gap_records``, ``gap_stop`` and ``gap``."""
+    ``gap_records``, ``gap_stop`` and ``gap``.  ``correction`` (``"rank_one"``, ``"north_west"``, ``"cheaper"``) and
+    ``correction_order`` (``(row_order, col_order)``; in the drivers that take point clouds also ``"projection"``,
+    ``projection_order`` of the clouds): ``APDWorkspace.set_correction`` before the run, obeyed by ``bracket`` and the
+    gap rule; the result then gains ``correction`` (``APDWorkspace.correction_info``).  Without them every result
+    keeps its bits."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=30, theta=1 / 4, smoth=5, cycle="w",
                                 isnsp=1, inter=1, guess=None)                          # :87-88
     warm = (0.0, 100) if prob > 0 else (5e-2, np.inf)                                  # :53-58
     ws = APDWorkspace(1, c, r, l, p, q, gama=gama)
     return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol, certificate,
-                       bracket, gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install))
+                       bracket, gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install),
+                       correction=_correction_keywords(correction, correction_order))
 
 
 def APD_SsN_Class2(c, r, l, p, q, mu, phi, rng: MatlabRand | None = None,
                    amg_opts: dict | None = None, krylov: bool = False, plan_tol=None, certificate: bool = False,
                    bracket: bool = False, gap_tol=None, gap_rel=None, gap_every=None, gap_first=None,
-                   gap_install=False, **opts) -> dict:
+                   gap_install=False, correction=None, correction_order=None, **opts) -> dict:
     """The script ``Class2/APD_SsN_Class2.m`` with ``inner_solver = 4`` (AMG4POT 'amg', or
     'amg_pcg' with ``krylov``).  ``plan_tol``, ``certificate``, ``bracket`` and the ``gap_*`` keywords: as in
     ``APD_SsN_Class1``."""
@@ -1476,7 +1564,8 @@ def APD_SsN_Class2(c, r, l, p, q, mu, phi, rng: MatlabRand | None = None,
                                 isnsp=1, inter=1, guess=None)
     ws = APDWorkspace(2, c, r, l, p, q, mu=mu, phi=phi)
     return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate, bracket,
-                       gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install))
+                       gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install),
+                       correction=_correction_keywords(correction, correction_order))
 
 
 # ---------------------------------------------------------------------------
@@ -1529,7 +1618,7 @@ def APD_SsN_Class1_points(xs, ys, r, l, p, q, metric="sqeuclidean", scale=False,
                           rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
                           plan_tol=None, matrix_free=False, certificate: bool = False, bracket: bool = False,
                           gap_tol=None, gap_rel=None, gap_every=None, gap_first=None, gap_install=False,
-                          **opts) -> dict:
+                          correction=None, correction_order=None, **opts) -> dict:
     """``APD_SsN_Class1`` with ``c = point_cost(xs, ys, metric, scale)`` built on the device
     (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``, ``bracket`` and the
     ``gap_*`` keywords: as there."""
@@ -1539,14 +1628,15 @@ def APD_SsN_Class1_points(xs, ys, r, l, p, q, metric="sqeuclidean", scale=False,
     ws = APDWorkspace.from_points(1, xs, ys, r, l, p, q, metric=metric, scale=scale, gama=gama,
                                   matrix_free=matrix_free)
     return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol, certificate,
-                       bracket, gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install))
+                       bracket, gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install),
+                       correction=_correction_keywords(correction, correction_order, (xs, ys)))
 
 
 def APD_SsN_Class2_points(xs, ys, r, l, p, q, mu, phi=None, metric="sqeuclidean", scale=False,
                           rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
                           plan_tol=None, matrix_free=False, certificate: bool = False, bracket: bool = False,
                           gap_tol=None, gap_rel=None, gap_every=None, gap_first=None, gap_install=False,
-                          **opts) -> dict:
+                          correction=None, correction_order=None, **opts) -> dict:
     """``APD_SsN_Class2`` with the cost built on the device; ``phi=None`` is all ones
     (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``, ``bracket`` and the
     ``gap_*`` keywords: as in ``APD_SsN_Class1``."""
@@ -1555,7 +1645,8 @@ def APD_SsN_Class2_points(xs, ys, r, l, p, q, mu, phi=None, metric="sqeuclidean"
     ws = APDWorkspace.from_points(2, xs, ys, r, l, p, q, metric=metric, scale=scale, mu=mu, phi=phi,
                                   matrix_free=matrix_free)
     return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate, bracket,
-                       gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install))
+                       gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install),
+                       correction=_correction_keywords(correction, correction_order, (xs, ys)))
 
 
 def load_input(path: str) -> dict:

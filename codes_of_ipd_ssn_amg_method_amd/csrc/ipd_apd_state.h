@@ -9,6 +9,7 @@
 //   ipd_cost.hip         the cost matrix from point clouds
 //   ipd_dual.hip         the c-transform of the multiplier, the dual value and the duality gap
 //   ipd_round.hip        the iterate rounded to a feasible plan, its exact cost
+//   ipd_round_nw.hip     the rounding's sparse correction: north-west corner along a given order
 //   ipd_bracket.hip      both certificates of a state in one call; the drivers' probe of the certified gap
 #pragma once
 
@@ -94,6 +95,17 @@ struct ipd_apd {
     double gap_best = -std::numeric_limits<double>::infinity();
     double* gap_lam = nullptr;
     std::vector<ipd_gap_rec> gap_recs;
+    // the rounding's correction (ipd_apd_set_correction): the mode, the two orders on the device
+    // (m and n entries of the arena, made by the first set that gives one; identity while corr_has_* is false), a
+    // list of m + n entries per side (made by the first set of a mode other than 0) and what the last rounding or
+    // bracket call used -- corr_last_side says whose list that is
+    int corr_mode = 0;
+    bool corr_has_row = false, corr_has_col = false;
+    int32_t *corr_row = nullptr, *corr_col = nullptr;
+    int32_t *nw_i[2] = {nullptr, nullptr}, *nw_j[2] = {nullptr, nullptr};
+    double* nw_g[2] = {nullptr, nullptr};
+    ipd_correction_info corr_last{};
+    int corr_last_side = 0;
     int nblk() const { return (int)apd_nblk(geo); }
 };
 
@@ -196,20 +208,58 @@ struct RoundShared {
     double *rpart = nullptr, *cpart = nullptr;   // a pass's row and column partials; the rest of a side overwrites A's
     double *sA = nullptr, *ab0 = nullptr;        // pass A's scalars; the first marginals [b0 (n); a0 (m)]
 };
+// what the last kernel of a side leaves on the device for the writing kernels
+struct RdDev {
+    double theta, t, se, sf;
+    long long ok;
+};
+// what the last kernel of ipd_round_nw.hip leaves for the read-back beside the statistics
+struct NwInfoDev {
+    long long form, count;        // 0 rank-one, 1 north-west; entries of the list (0 with the rank-one term)
+    double cc[2], fval[2];        // mode 2: [0] the rank-one term's, [1] the north-west list's; NaN otherwise
+    double pad[2];
+};
+// a side's arrays of the north-west correction (ipd_round_nw.hip, ipd_round_nw_geo.h); unset under mode 0
+struct RoundNw {
+    double* pre = nullptr;                               // the prefixes [C_0 .. C_n; R_0 .. R_m]
+    int32_t *di = nullptr, *dj = nullptr;                // dense slots: (i, j), i = -1 for an empty slot
+    double *dg = nullptr, *dc = nullptr, *dp = nullptr;  // g, c*g, phi*g of a slot
+    double *lc = nullptr, *lp = nullptr;                 // c*g, phi*g in list order
+    int32_t *li = nullptr, *lj = nullptr;                // the list: the workspace's buffers of this side
+    double* lg = nullptr;
+    RdDev* devw = nullptr;                               // the writing pass's scalars: t = 0 when the list carries t
+    NwInfoDev* info = nullptr;
+};
 struct RoundSide {
     int side = 0;
     double *sc = nullptr, *ab2 = nullptr, *ef = nullptr;   // [kappa; rho], [b2; a2], [f; e]: n + m entries each
     double *sC = nullptr, *sD = nullptr;                   // the scalars of C and D
     ipd_round_stats* out = nullptr;                        // device, APD_STATS_DOUBLES doubles
-    void* dev = nullptr;                                   // what k_rd_last leaves for the writing kernels
+    void* dev = nullptr;                                   // what the last kernel leaves for the writing kernels
+    RoundNw nw;
 };
 // tol, install: IPD_E_ARG; finite gama: IPD_E_UNSUPPORTED
 void apd_round_check_args(const ipd_apd* h, double tol, int32_t install);
 RoundShared apd_round_pass_a(ipd_apd* h, double tol);
-// out_dev: where the statistics go, nullptr: into the scratch
-RoundSide apd_round_first_scale(ipd_apd* h, const RoundShared& sh, int side, ipd_round_stats* out_dev);
+// out_dev: where the statistics go, nullptr: into the scratch; info_dev likewise, under a mode other than 0
+RoundSide apd_round_first_scale(ipd_apd* h, const RoundShared& sh, int side, ipd_round_stats* out_dev,
+                                NwInfoDev* info_dev = nullptr);
 void apd_round_rest(ipd_apd* h, const RoundShared& sh, const RoundSide& s, double tol);
 void apd_round_write(ipd_apd* h, const RoundShared& sh, const RoundSide& s, double tol, int install, double* x_out_dev);
+
+// ---- ipd_round_nw.hip ----------------------------------------------------------------------
+// (the north-west-corner correction along the workspace's orders; reached from the stages above
+// when h->corr_mode != 0, never under mode 0)
+// a side's scratch and its list buffers; info_dev: where the read-back's second part goes, nullptr: into the scratch
+RoundNw apd_nw_side(ipd_apd* h, int side, NwInfoDev* info_dev);
+// after k_rd_fin<2> (mode 2: and after pass D): scans, merge and the last kernel; s.out, s.dev, s.nw.devw and
+// s.nw.info are complete on the stream afterwards
+void apd_nw_rest(ipd_apd* h, const RoundShared& sh, const RoundSide& s);
+// after pass W wrote theta*X2: t*g added at the list's entries of up to three destinations
+void apd_nw_scatter(ipd_apd* h, const RoundSide& s, int need_ok, double* o0, double* o1, double* o2);
+// what a finished call used becomes what ipd_apd_correction_entries and ipd_apd_correction_info return; info = nullptr:
+// the rank-one term of mode 0
+void apd_nw_record(ipd_apd* h, int side, const NwInfoDev* info);
 
 // ---- ipd_bracket.hip -----------------------------------------------------------------------
 // Both certificates of the state in one pass over what they share (ipd_apd_bracket).  The caller

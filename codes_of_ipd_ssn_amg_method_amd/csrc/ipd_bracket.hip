@@ -18,6 +18,7 @@
 #pragma clang fp contract(off)
 
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <limits>
 
@@ -228,6 +229,7 @@ __global__ __launch_bounds__(256) void k_du_eval2(const DuEval2 a, const CS cs) 
 struct BracketStats {
     double dual[2][APD_STATS_DOUBLES];
     double round[2][APD_STATS_DOUBLES];
+    NwInfoDev nw[2];   // read back under a correction mode other than 0 only
 };
 
 void check_args(const ipd_apd* h, double tol, int32_t install, const ipd_bracket* out) {
@@ -307,10 +309,10 @@ BracketRun apd_bracket_measure(ipd_apd* h, double tol) {
     // the upper side: pass A once, both first scale vectors out of its partials, then the rest of each side
     r.shared = apd_round_pass_a(h, tol);
     for (int s = 0; s < 2; ++s)
-        r.side[s] = apd_round_first_scale(h, r.shared, s, reinterpret_cast<ipd_round_stats*>(st->round[s]));
+        r.side[s] = apd_round_first_scale(h, r.shared, s, reinterpret_cast<ipd_round_stats*>(st->round[s]), &st->nw[s]);
     for (int s = 0; s < 2; ++s) apd_round_rest(h, r.shared, r.side[s], tol);
     BracketStats got;
-    ctx->fetch_bytes(st, &got, sizeof(BracketStats));
+    ctx->fetch_bytes(st, &got, h->corr_mode != 0 ? sizeof(BracketStats) : offsetof(BracketStats, nw));
     ipd_dual_stats du[2];
     ipd_round_stats rd[2];
     for (int s = 0; s < 2; ++s) {
@@ -322,6 +324,7 @@ BracketRun apd_bracket_measure(ipd_apd* h, double tol) {
     r.b.lower = du[r.b.lower_side];
     r.b.upper = rd[r.b.upper_side];
     r.b.gap = apd_gap_value(r.b.upper.fval, r.b.lower.dual);
+    apd_nw_record(h, r.b.upper_side, h->corr_mode != 0 ? &got.nw[r.b.upper_side] : nullptr);
     return r;
 }
 static_assert(sizeof(ipd_dual_stats) <= APD_STATS_DOUBLES * sizeof(double) &&

@@ -32,6 +32,7 @@
 #pragma clang fp contract(off)
 
 #include <cmath>
+#include <cstring>
 #include <limits>
 
 #include "ipd_apd_state.h"
@@ -42,11 +43,7 @@ namespace {
 
 enum { RD_A = 0, RD_B0 = 1, RD_B1 = 2, RD_C = 3, RD_D = 4, RD_W = 5 };
 
-// what the last kernel leaves on the device for W and slack
-struct RdDev {
-    double theta, t, se, sf;
-    long long ok;
-};
+// (RdDev, what the last kernel leaves on the device for W and slack: ipd_apd_state.h)
 static_assert(sizeof(ipd_round_stats) <= APD_STATS_DOUBLES * sizeof(double) && sizeof(RdDev) <= 8 * sizeof(double) &&
                   RD_RESULT_DOUBLES == 24,
               "round_dev sizes the result in doubles");
@@ -451,7 +448,8 @@ RoundShared apd_round_pass_a(ipd_apd* h, double tol) {
 }
 
 // one side's arrays and its first scale vector out of pass A's partials, which the rest of a side overwrites
-RoundSide apd_round_first_scale(ipd_apd* h, const RoundShared& sh, int side, ipd_round_stats* out_dev) {
+RoundSide apd_round_first_scale(ipd_apd* h, const RoundShared& sh, int side, ipd_round_stats* out_dev,
+                                NwInfoDev* info_dev) {
     Arena& S = *h->ctx->scratch;
     const RdGeo g = walk_make_geo(h->m, h->n);
     const size_t M = (size_t)h->M;
@@ -464,12 +462,14 @@ RoundSide apd_round_first_scale(ipd_apd* h, const RoundShared& sh, int side, ipd
     s.ef = S.alloc<double>(M);
     s.out = out_dev ? out_dev : reinterpret_cast<ipd_round_stats*>(S.alloc<double>(APD_STATS_DOUBLES));
     s.dev = S.alloc<double>(8);
+    if (h->corr_mode != 0) s.nw = apd_nw_side(h, side, info_dev);
     hipLaunchKernelGGL(k_rd_fin<0>, fin_grid(h), dim3(256), 0, h->ctx->stream, fin_args(h, sh, s));
     IPD_KERNEL_CHECK();
     return s;
 }
 
-// B, C, D with their finishing kernels and the last kernel: s.out and s.dev are complete on the stream afterwards
+// B, C, D with their finishing kernels and the last kernel: s.out and s.dev are complete on the stream afterwards.
+// Mode 1 of the correction runs no pass D, and modes 1 and 2 end in ipd_round_nw.hip's kernels.
 void apd_round_rest(ipd_apd* h, const RoundShared& sh, const RoundSide& s, double tol) {
     ipd_ctx* ctx = h->ctx;
     RdWalk w = walk_args(h, sh, s, tol);
@@ -485,7 +485,8 @@ void apd_round_rest(ipd_apd* h, const RoundShared& sh, const RoundSide& s, doubl
     hipLaunchKernelGGL(k_rd_fin<2>, fin_grid(h), dim3(256), 0, ctx->stream, f);
     IPD_KERNEL_CHECK();
     w.spart = s.sD;
-    with_cost_source(h, [&](auto cs) { launch_walk<RD_D>(h, w, cs); });
+    if (h->corr_mode != 1) with_cost_source(h, [&](auto cs) { launch_walk<RD_D>(h, w, cs); });
+    if (h->corr_mode != 0) return apd_nw_rest(h, sh, s);
     RdLast l;
     l.g = w.g;
     l.cls2 = w.cls2;
@@ -514,7 +515,9 @@ void apd_round_write(ipd_apd* h, const RoundShared& sh, const RoundSide& s, doub
     w.o0 = x_out_dev;
     w.o1 = install ? h->u : nullptr;
     w.o2 = install ? h->v : nullptr;
+    if (h->corr_mode != 0) w.dev = s.nw.devw;   // t = 0 there when the list carries the correction
     launch_walk<RD_W>(h, w);
+    if (h->corr_mode != 0) apd_nw_scatter(h, s, install, w.o0, w.o1, w.o2);
     if (install && h->cls == 2) {
         RdSlack k;
         k.g = w.g;
@@ -548,10 +551,27 @@ void check_args(const ipd_apd* h, double tol, int32_t side, int32_t install, con
 // install was asked and ok = 0: the device wrote nothing then.
 RoundSide round_dev(ipd_apd* h, double tol, int side, int install, double* x_out_dev, ipd_round_stats* st) {
     const RoundShared sh = apd_round_pass_a(h, tol);
-    const RoundSide s = apd_round_first_scale(h, sh, side, nullptr);
+    // under a correction mode other than 0 the statistics and what the correction adds lie together: one read-back
+    struct Both {
+        double stats[APD_STATS_DOUBLES];
+        NwInfoDev info;
+    };
+    Both* both = h->corr_mode == 0
+                     ? nullptr
+                     : reinterpret_cast<Both*>(h->ctx->scratch->alloc<double>(sizeof(Both) / sizeof(double)));
+    const RoundSide s = apd_round_first_scale(h, sh, side, both ? reinterpret_cast<ipd_round_stats*>(both->stats) : nullptr,
+                                              both ? &both->info : nullptr);
     apd_round_rest(h, sh, s, tol);
     apd_round_write(h, sh, s, tol, install, x_out_dev);
-    h->ctx->fetch_bytes(s.out, st, sizeof(ipd_round_stats));
+    if (both) {
+        Both got;
+        h->ctx->fetch_bytes(both, &got, sizeof(Both));
+        std::memcpy(st, got.stats, sizeof(ipd_round_stats));
+        apd_nw_record(h, side, &got.info);
+    } else {
+        h->ctx->fetch_bytes(s.out, st, sizeof(ipd_round_stats));
+        apd_nw_record(h, side, nullptr);
+    }
     if (install && !st->ok)
         throw IpdError(IPD_E_NUMERIC, "ipd_apd_round: no repair of this shape exists (ok = 0); nothing was installed");
     return s;

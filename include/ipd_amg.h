@@ -638,6 +638,57 @@ int ipd_apd_round_dev(ipd_apd* h, double tol, int32_t side, int32_t install,
                       double* rho_dev, double* kappa_dev, double* e_dev, double* f_dev,
                       double* x_out_dev, ipd_round_stats* st);   /* device arrays; st on the host */
 
+/* The rounding's correction: what carries the deficits e, f of step 7 into X^.  A workspace setting,
+ * obeyed by ipd_apd_round, ipd_apd_round_dev, ipd_apd_bracket, ipd_apd_bracket_dev and the gap rule's probes.
+ *    mode 0  the rank-one term t*(e_i*f_j) of steps 8 and 11 above: the default, and what a workspace without the
+ *            setting computes, in the same bits
+ *    mode 1  a north-west-corner coupling G of the deficits along a row order sigma and a column order tau
+ *    mode 2  both are evaluated and the device keeps the one with ok = 1 first, then the one with the smaller fval
+ *            (class 1: the smaller cc, t being the same); the rank-one term stays on a tie
+ * Steps 1-7, 9, 10 and 12, Se, Sf and step 11's y^, z^ are as above; G replaces e_i*f_j in cc, cp and X^.  Every
+ * operation is one IEEE operation in the order written:
+ *   N1  orders      sigma a permutation of 0..m-1, tau of 0..n-1 (host int32 arrays; NULL is the identity)
+ *   N2  masses      alpha_k = (p_i*e_i)*Sf, i = sigma_k, k = 1..m;   beta_s = (q_j*f_j)*Se, j = tau_s, s = 1..n
+ *                   (both sum to Se*Sf in exact arithmetic)
+ *   N3  prefixes    R_0 = C_0 = 0; R_k, C_s the inclusive prefix sums of alpha, beta in this shape: the vector is cut
+ *                   into chunks of 64 entries; within a chunk c the local prefixes L are formed by adding its entries
+ *                   in ascending order, starting from the chunk's first entry; the chunk offsets are O_0 = 0,
+ *                   O_c+1 = O_c + (last local prefix of chunk c), in ascending order; a prefix is O_c + L (chunk 0:
+ *                   L itself).  In numpy: L = cumsum(alpha.reshape(-1, 64), axis=1), O = [0, cumsum(L[:, -1])[:-1]],
+ *                   R = O[:, None] + L.  The shape depends on nothing but the vector; with non-negative masses the
+ *                   prefixes are non-decreasing, across chunk edges too, which N4 relies on.
+ *   N4  entries     for every (k, s) with w = min(R_k, C_s) - max(R_k-1, C_s-1) > 0 one entry i = sigma_k, j = tau_s,
+ *                   g = w/(p_i*q_j); at most m + n - 1 entries, each (i, j) at most once, listed in ascending (k, s).
+ *                   An interval of one vector that lies beyond the other vector's total -- the two totals differ by
+ *                   their rounding at most -- has no entry.
+ *   N5  marginals   sum_j q_j*G_ij = e_i*Sf and sum_i p_i*G_ij = f_j*Se up to the rounding of N3: the rank-one term's
+ *                   marginals, which is why t, ok, y^ and z^ keep their formulas
+ *   N6  sums        cc = sum c_ij*g, class 2: cp = sum phi_ij*g, over the list in list order in Se's shape (entries
+ *                   t, t + 256, ... per thread t, then the tree)
+ *   N7  result      X^_ij = theta*X2_ij, and X^_ij = theta*X2_ij + t*g at the list's entries
+ * ipd_round_stats keeps its layout: cc and cp hold the sums of the form that was used.  c_ij is taken from the
+ * workspace's cost source, so stored, point-cloud and matrix-free workspaces give the same bits; two calls and the
+ * two entries do too.  An installed plan has at most nnz(x+) + m + n - 1 entries.  Finite gama stays
+ * IPD_E_UNSUPPORTED in the rounding calls.
+ * ipd_apd_set_correction: the orders are checked on the host and kept on the device with a list of m + n entries per
+ * side.  IPD_E_ARG for a NULL h, a mode outside {0, 1, 2} or an order that is not a permutation; IPD_E_LIMIT for a
+ * mode other than 0 with m or n above 16384; the setting in force stays then.
+ * ipd_apd_correction_entries (host arrays) and ipd_apd_correction_entries_dev (device arrays): the list of the last
+ * rounding or bracket call (a bracket: of the chosen side) -- *count its length, 0 when that call used the rank-one
+ * term, and the first min(cap, *count) entries into i, j, g (each may be NULL).  IPD_E_ARG for a NULL h or count or
+ * cap < 0.  ipd_apd_correction_info: the mode of that call, the form it used (0 rank-one, 1 north-west), the count
+ * and, under mode 2, cc and fval of both forms ([0] rank-one, [1] north-west; NaN otherwise).                    */
+typedef struct ipd_correction_info {
+    int32_t mode, form;
+    int64_t count;
+    double cc[2], fval[2];
+} ipd_correction_info;
+int ipd_apd_set_correction(ipd_apd* h, int32_t mode, const int32_t* row_order, const int32_t* col_order);
+int ipd_apd_correction_entries(ipd_apd* h, int32_t* i, int32_t* j, double* g, int64_t cap, int64_t* count);
+int ipd_apd_correction_entries_dev(ipd_apd* h, int32_t* i_dev, int32_t* j_dev, double* g_dev, int64_t cap,
+                                   int64_t* count);
+int ipd_apd_correction_info(const ipd_apd* h, ipd_correction_info* out);
+
 /* Both certificates of the state in one call: lower <= f* <= upper.  The two c-transforms of the
  * workspace's lk are formed in one walk over c (class 2: and phi), the two repaired multipliers are evaluated in one
  * read of c and x, the rounding's first pass runs once for both sides, and the four statistics come back in one

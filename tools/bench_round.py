@@ -3,6 +3,7 @@
 
   python tools/bench_round.py [--sizes 1024,4096] [--reps 2] [--out FILE]
   python tools/bench_round.py --converged [--out FILE]
+  python tools/bench_round.py --correction [--sizes 1024,4096] [--reps 3] [--out FILE]
 
 Per size, class 1 (gama = inf, p = q = 1), cost stored and matrix-free (both from the same d = 2 point clouds), state
 after warmup(0, 100), side in {0, 1}, timed with a host clock around calls that end in a device synchronise, every
@@ -19,6 +20,12 @@ A, B and D 8*mn, C 16*mn, W 8*mn read and 8*mn written per destination (DESIGN.m
 
 --converged: the four cases of tests/test_gpu_dual.py::test_feasibility_and_weak_duality run to convergence with the
 drivers' defaults and `bracket=True`; prints the certified bracket next to f* from HiGHS.
+
+--correction: per size and cost source, ipd_apd_round_dev (the four factors out, no x_out) under
+the rank-one term (mode 0: 8 launches), the north-west list (mode 1: 9 launches, none of them pass D) and the cheaper of
+the two (mode 2: 10 launches), the modes alternating `--reps` times in one process with the protocol above; mode 0 is
+the parent's path, the spread of its repetitions the bar for mode 1.  Next to the times the correction's cost t*cc of
+the state after warmup(0, 100) under mode 0, mode 1 along the identity, mode 1 along projection_order, and mode 2.
 """
 import argparse
 import json
@@ -108,6 +115,50 @@ def bench_size(N, reps, emit):
         ws.close()
 
 
+def bench_correction(N, reps, emit):
+    rs = np.random.RandomState(1)
+    xs, ys = rs.random_sample((N, 2)), rs.random_sample((N, 2))
+    r, l = rs.random_sample(N), rs.random_sample(N)
+    l = l * r.sum() / l.sum()
+    one = np.ones(N)
+    proj = ipd.projection_order(xs, ys)
+    for cost in ("stored", "free"):
+        ws = ipd.APDWorkspace.from_points(1, xs, ys, r, l, one, one, scale=True, matrix_free=cost == "free")
+        ws.warmup(0.0, 100)
+        bufs = [L.DeviceBuffer(8 * N) for _ in range(4)]
+        for side in (0, 1):
+            def call():
+                return ws.round_plan_dev(0.0, side=side, rho=bufs[0], kappa=bufs[1], e=bufs[2], f=bufs[3])
+
+            settings = [("rank_one", "rank_one", (None, None)), ("north_west_identity", "north_west", (None, None)),
+                        ("north_west", "north_west", proj), ("cheaper", "cheaper", proj)]
+            tcc, info = {}, {}
+            for name, mode, order in settings:
+                ws.set_correction(mode, *order)
+                st = call()
+                assert st["ok"] == 1
+                tcc[name] = st["t"] * st["cc"]
+                info[name] = ws.correction_info()
+            times = {name: [] for name, _, _ in settings if name != "north_west_identity"}
+            for _ in range(reps):
+                for name, mode, order in settings:
+                    if name in times:
+                        ws.set_correction(mode, *order)
+                        times[name].append(timed(call, 50))
+            r1 = times["rank_one"]
+            emit(dict(bench="round_correction", N=N, cost=cost, side=side,
+                      seconds={key: [round(t, 7) for t in v] for key, v in times.items()},
+                      launches=dict(rank_one=8, north_west=9, cheaper=10), t_cc=tcc,
+                      count=info["north_west"]["count"], cheaper_form=info["cheaper"]["form"],
+                      rank_one_spread=max(r1) - min(r1),
+                      north_west_minus_rank_one=min(times["north_west"]) - min(r1),
+                      north_west_within_spread=bool(min(times["north_west"]) <= max(r1))))
+        ws.set_correction("rank_one")
+        for b in bufs:
+            b.free()
+        ws.close()
+
+
 def converged(emit):
     """tests/test_gpu_dual.py's four cases to convergence, with the bracket"""
     import scipy.sparse as sp
@@ -144,6 +195,7 @@ def main():
     ap.add_argument("--sizes", default="1024,4096")
     ap.add_argument("--reps", type=int, default=2, help="alternating repetitions of the variants")
     ap.add_argument("--converged", action="store_true", help="the bracket of four converged runs instead")
+    ap.add_argument("--correction", action="store_true", help="the three correction modes of section 4n instead")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     a = ap.parse_args()
 
@@ -158,7 +210,7 @@ def main():
         converged(emit)
         return
     for N in [int(s) for s in a.sizes.split(",") if s]:
-        bench_size(N, a.reps, emit)
+        (bench_correction if a.correction else bench_size)(N, a.reps, emit)
 
 
 if __name__ == "__main__":
