@@ -122,6 +122,10 @@ class ipd_cost_stats(Structure):
     _fields_ = [("min", c_double), ("max", c_double), ("sum", c_double)]
 
 
+class ipd_grad_stats(Structure):
+    _fields_ = [("kept", c_int64), ("kinks", c_int64), ("denom", c_double)]
+
+
 class ipd_cost_info(Structure):
     _fields_ = [("form", c_int32), ("dim", c_int32), ("metric", c_int32), ("scale", c_int32),
                 ("device_bytes", c_int64)]
@@ -189,6 +193,9 @@ lib.ipd_apd_create_points.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_get_cost.argtypes = [c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_create_points_free.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_cost_info.argtypes = [c_void_p, c_void_p]
+lib.ipd_apd_point_grad.argtypes = [c_void_p, c_void_p, c_double, c_int32, c_void_p, c_void_p, c_void_p]
+lib.ipd_apd_point_grad_dev.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_double, c_int32,
+                                       c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_get_w.argtypes = [c_void_p, c_void_p, c_void_p]
 lib.ipd_apd_eval_trial.argtypes = [c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int32, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]
@@ -230,6 +237,7 @@ EXPORTS = [
     "ipd_apd_set_gap_rule", "ipd_apd_gap_records", "ipd_apd_gap_lam",
     "ipd_cost_points_dev", "ipd_apd_create_points", "ipd_apd_get_cost",
     "ipd_apd_create_points_free", "ipd_apd_cost_info",
+    "ipd_apd_point_grad", "ipd_apd_point_grad_dev",
     "ipd_apd_get_w", "ipd_apd_eval_trial", "ipd_apd_merit", "ipd_apd_end",
 ]
 

@@ -991,6 +991,112 @@ class APDWorkspace:
         ``T(x_i) = sum_j x_ij y_j / sum_j x_ij``; ``side=1`` with ``points = xs`` (m, d) is the reverse."""
         return self.apply_plan(points, side=side, tol=tol, normalize=True)
 
+    # -- the gradient of the transport cost in the point positions ---------------
+    @staticmethod
+    def _grad_stats(st: L.ipd_grad_stats) -> dict:
+        return dict(kept=int(st.kept), kinks=int(st.kinks), denom=st.denom)
+
+    def point_gradient(self, side: int = 0, tol: float = 0.0, points=None, metric=None, scale=None,
+                       mass: bool = False, stats: bool = False):
+        """The derivative of ``<c(xs, ys), X>`` in the positions of the points at fixed ``X = plan(tol)``, computed where
+        the iterate lives (``ipd_apd_point_grad``): ``side=0`` -> (m, d), row i ``sum_j X_ij dc(xs_i, ys_j)/dxs_i``;
+        ``side=1`` -> (n, d), row j ``sum_i X_ij dc(xs_i, ys_j)/dys_j``.  By the envelope theorem that is the gradient of
+        the transport cost at an optimal (or rounded feasible, ``gap_probe(install=True)``) plan.  ``points=None`` takes
+        the clouds, metric and scale the workspace was made from (``from_points``; a workspace from a host matrix has
+        none); ``points=(xs, ys)`` with ``metric`` (default ``"sqeuclidean"``) and ``scale`` (default False) may be
+        given to any workspace.  Where the cost is not differentiable (coincident points for ``euclidean``, a zero
+        coordinate difference for ``cityblock``, a tied or zero maximum for ``chebyshev``) one subgradient is taken:
+        0 for the tied coordinates, the first maximum for ``chebyshev``.  ``scale=True`` divides by the largest
+        unscaled entry, which is held constant -- a stop-gradient; the divider comes back as ``denom`` so that the
+        missing term can be added.  ``mass=True`` adds ``w``, the mass of the kept entries per row (column);
+        ``stats=True`` adds ``dict(kept, kinks, denom)``: the kept entries, those at which the cost is not
+        differentiable, and the divider (1.0 without scale).  Returns ``G``, or a tuple ``(G[, w][, stats])``.  For
+        ``sqeuclidean`` without scale, ``2 * (w[:, None] * xs - apply_plan(ys, mass=True)[0])`` is the same gradient and
+        the faster route (DESIGN.md section 4o has the measured rows)."""
+        if side not in (0, 1):
+            raise ValueError("side must be 0 (xs) or 1 (ys)")
+        R = self.n if side else self.m
+        spec_ref, keep = None, None
+        if points is not None:
+            spec, keep = _cost_spec(points[0], points[1], metric or "sqeuclidean", bool(scale))
+            if (spec.m, spec.n) != (self.m, self.n):
+                raise ValueError(f"point_gradient: xs, ys must hold {self.m} and {self.n} points")
+            spec_ref, d = byref(spec), int(spec.dim)
+        else:
+            if metric is not None or scale is not None:
+                raise ValueError("point_gradient: metric and scale go with points=(xs, ys)")
+            d = self.cost_info()["dim"]
+            if d == 0:
+                raise ValueError("point_gradient: the workspace was made from a host matrix; give points=(xs, ys)")
+        G = np.empty((R, d), order="F")
+        w = np.empty(R) if mass else None
+        st = L.ipd_grad_stats()
+        check(lib.ipd_apd_point_grad(self.handle, spec_ref, c_double(float(tol)), c_int32(side), G.ctypes.data,
+                                     w.ctypes.data if mass else None, byref(st)))
+        out = (G,) + ((w,) if mass else ()) + ((self._grad_stats(st),) if stats else ())
+        return out if len(out) > 1 else G
+
+    def point_gradient_dev(self, G, w=None, side: int = 0, tol: float = 0.0, xs=None, ys=None, metric=None,
+                           scale=None) -> dict:
+        """The same on caller-owned device arrays (``ipd_apd_point_grad_dev``), float64: ``G`` (m or n) x d as
+        ``G[r + k*R]``, ``w`` m or n entries or None, and -- both or neither -- ``xs`` m x d as ``xs[i + k*m]`` and ``ys``
+        n x d: torch tensors on the workspace's GPU (contiguous), ``DeviceBuffer`` objects, or ``(pointer, entries)``
+        pairs.  d is taken from the entries of ``xs`` (the workspace's own without it).  Device coordinates are not
+        looked at: they must be finite.  Returns the statistics."""
+        if side not in (0, 1):
+            raise ValueError("side must be 0 (xs) or 1 (ys)")
+        R = self.n if side else self.m
+
+        def ptr_count(a, name):
+            if isinstance(a, tuple):
+                return c_void_p(int(a[0])), int(a[1])
+            if isinstance(a, L.DeviceBuffer):
+                return a.ptr, a.nbytes // 8
+            if hasattr(a, "data_ptr"):
+                if a.element_size() != 8 or not a.is_contiguous():
+                    raise ValueError("point_gradient_dev: tensors must be contiguous float64")
+                return c_void_p(a.data_ptr()), a.numel()
+            raise ValueError(f"point_gradient_dev: {name} must be a tensor, a DeviceBuffer or a (pointer, entries) pair")
+        if (xs is None) != (ys is None):
+            raise ValueError("point_gradient_dev: give both xs and ys, or neither")
+        xs_p = ys_p = None
+        code = 0
+        if xs is not None:
+            if metric is not None and metric not in COST_METRICS:
+                raise ValueError(f"metric must be one of {sorted(COST_METRICS)}")
+            code = COST_METRICS[metric or "sqeuclidean"]
+            xs_p, xs_cnt = ptr_count(xs, "xs")
+            ys_p, ys_cnt = ptr_count(ys, "ys")
+            d, rest = divmod(xs_cnt, self.m)
+            if rest or d < 1:
+                raise ValueError(f"point_gradient_dev: xs must hold d coordinates of {self.m} points")
+            if ys_cnt < self.n * d:
+                raise ValueError(f"point_gradient_dev: ys must hold {d} coordinates of {self.n} points")
+        else:
+            if metric is not None or scale is not None:
+                raise ValueError("point_gradient_dev: metric and scale go with xs and ys")
+            d = self.cost_info()["dim"]
+            if d == 0:
+                raise ValueError("point_gradient_dev: the workspace was made from a host matrix; give xs and ys")
+        G_p, G_cnt = ptr_count(G, "G")
+        if G_cnt < R * d:
+            raise ValueError(f"point_gradient_dev: G must hold {d} columns of {R} entries")
+        w_p = None
+        if w is not None:
+            w_p, w_cnt = ptr_count(w, "w")
+            if w_cnt < R:
+                raise ValueError(f"point_gradient_dev: w must hold {R} entries")
+        st = L.ipd_grad_stats()
+        check(lib.ipd_apd_point_grad_dev(self.handle, c_int32(code), c_int32(d), c_int32(1 if scale else 0), xs_p, ys_p,
+                                         c_double(float(tol)), c_int32(side), G_p, w_p, byref(st)))
+        return self._grad_stats(st)
+
+    def transport_gradients(self, tol: float = 0.0) -> dict:
+        """``dict(xs=point_gradient(0, tol), ys=point_gradient(1, tol), stats=...)`` in the workspace's own clouds."""
+        gx, st = self.point_gradient(0, tol, stats=True)
+        gy = self.point_gradient(1, tol)
+        return dict(xs=gx, ys=gy, stats=st)
+
     # -- the dual certificate --------------------------------------------------
     @staticmethod
     def _dual_stats(st: L.ipd_dual_stats) -> dict:
@@ -1453,7 +1559,7 @@ def warmup_class2(c, r, l, p, q, mu, phi, res=None, maxit=None):
 
 def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool = False,
                 plan_tol=None, certificate: bool = False, bracket: bool = False, gap: dict | None = None,
-                correction: dict | None = None) -> dict:
+                correction: dict | None = None, gradient=None) -> dict:
     try:
         if correction is not None:
             ws.set_correction(**correction)
@@ -1478,6 +1584,9 @@ def _run_script(ws: APDWorkspace, amg_opts: dict, rng, warm, opts, krylov: bool 
             out["bracket"] = ws.bracket()
         if correction is not None and (bracket or gap is not None):
             out["correction"] = ws.correction_info()   # of the last rounding: the bracket's, else the last probe's
+        if gradient is not None:    # after bracket / gap_install: an installed plan is the one differentiated
+            g = ws.transport_gradients(gradient)
+            out.update(grad_xs=g["xs"], grad_ys=g["ys"], grad_stats=g["stats"])
         return out
     finally:
         ws.close()
@@ -1618,10 +1727,13 @@ def APD_SsN_Class1_points(xs, ys, r, l, p, q, metric="sqeuclidean", scale=False,
                           rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
                           plan_tol=None, matrix_free=False, certificate: bool = False, bracket: bool = False,
                           gap_tol=None, gap_rel=None, gap_every=None, gap_first=None, gap_install=False,
-                          correction=None, correction_order=None, **opts) -> dict:
+                          correction=None, correction_order=None, gradient=None, **opts) -> dict:
     """``APD_SsN_Class1`` with ``c = point_cost(xs, ys, metric, scale)`` built on the device
     (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``, ``bracket`` and the
-    ``gap_*`` keywords: as there."""
+    ``gap_*`` keywords: as there.  ``gradient=tol``: the result gains ``grad_xs`` (m, d), ``grad_ys`` (n, d) and
+    ``grad_stats``, the derivative of the transport cost in the positions of the points at the final plan without its
+    entries ``abs(x) <= tol`` (``APDWorkspace.transport_gradients``; with ``gap_install`` the installed feasible plan).
+    Without the keyword every result keeps its bits."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=30, theta=1 / 4, smoth=5, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     warm = (0.0, 100) if prob > 0 else (5e-2, np.inf)
@@ -1629,24 +1741,24 @@ def APD_SsN_Class1_points(xs, ys, r, l, p, q, metric="sqeuclidean", scale=False,
                                   matrix_free=matrix_free)
     return _run_script(ws, amg_opts, rng, warm, dict(prob=int(prob), **opts), krylov, plan_tol, certificate,
                        bracket, gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install),
-                       correction=_correction_keywords(correction, correction_order, (xs, ys)))
+                       correction=_correction_keywords(correction, correction_order, (xs, ys)), gradient=gradient)
 
 
 def APD_SsN_Class2_points(xs, ys, r, l, p, q, mu, phi=None, metric="sqeuclidean", scale=False,
                           rng: MatlabRand | None = None, amg_opts: dict | None = None, krylov: bool = False,
                           plan_tol=None, matrix_free=False, certificate: bool = False, bracket: bool = False,
                           gap_tol=None, gap_rel=None, gap_every=None, gap_first=None, gap_install=False,
-                          correction=None, correction_order=None, **opts) -> dict:
+                          correction=None, correction_order=None, gradient=None, **opts) -> dict:
     """``APD_SsN_Class2`` with the cost built on the device; ``phi=None`` is all ones
     (``matrix_free=True``: never stored, see ``APDWorkspace.from_points``); ``certificate``, ``bracket`` and the
-    ``gap_*`` keywords: as in ``APD_SsN_Class1``."""
+    ``gap_*`` keywords: as in ``APD_SsN_Class1``; ``gradient``: as in ``APD_SsN_Class1_points``."""
     amg_opts = amg_opts or dict(retol=1e-11, bigph=1, maxit=40, theta=1 / 4, smoth=10, cycle="w",
                                 isnsp=1, inter=1, guess=None)
     ws = APDWorkspace.from_points(2, xs, ys, r, l, p, q, metric=metric, scale=scale, mu=mu, phi=phi,
                                   matrix_free=matrix_free)
     return _run_script(ws, amg_opts, rng, (0.0, 100), opts, krylov, plan_tol, certificate, bracket,
                        gap=_gap_keywords(gap_tol, gap_rel, gap_every, gap_first, gap_install),
-                       correction=_correction_keywords(correction, correction_order, (xs, ys)))
+                       correction=_correction_keywords(correction, correction_order, (xs, ys)), gradient=gradient)
 
 
 def load_input(path: str) -> dict:

@@ -7,6 +7,7 @@
 //   ipd_plan.hip         the transport plan as a sparse matrix, out of and into the workspace
 //   ipd_plan_apply.hip   the plan applied to a thin dense matrix
 //   ipd_cost.hip         the cost matrix from point clouds
+//   ipd_point_grad.hip   the gradient of the transport cost in the point positions
 //   ipd_dual.hip         the c-transform of the multiplier, the dual value and the duality gap
 //   ipd_round.hip        the iterate rounded to a feasible plan, its exact cost
 //   ipd_round_nw.hip     the rounding's sparse correction: north-west corner along a given order
@@ -59,7 +60,8 @@ struct ipd_apd {
     ipd_cost_stats cost_stats{};   // min, max, sum of c: from the build out of points, or on demand (ipd_apd_get_cost)
     bool have_cost_stats = false;  // (c never changes after the create)
     // matrix-free (ipd_apd_create_points_free): c stays nullptr, the coordinates live in the
-    // arena and cost_src describes them to the passes that read c(i,j)
+    // arena and cost_src describes them to the passes that read c(i,j).  A stored workspace made from points
+    // (ipd_apd_create_points) fills cost_src too, cost_free false: ipd_point_grad.hip differentiates in them
     bool cost_free = false;
     CostSrc cost_src{};
     int cost_dim = 0, cost_metric = 0, cost_scale = 0;   // of the specification; 0 for a workspace from a host c
@@ -183,6 +185,11 @@ float apd_bench_eval(ipd_apd* h, bool merit3, int reps);
 // ---- ipd_apd_warm.hip ----------------------------------------------------------------------
 // A-ADMM warm start                       warmup_class1.m:22-96 / warmup_class2.m:19-100
 void apd_warmup(ipd_apd* h, double res, long long maxit);
+
+// ---- ipd_cost.hip --------------------------------------------------------------------------
+// the largest entry of the unscaled cost of device coordinates (scale = 1 divides by it); IPD_E_ARG when it is 0 or not
+// finite.  The caller holds a CallScope; the stream has been waited for afterwards.
+double apd_cost_largest(ipd_ctx* ctx, int metric, int dim, int m, int n, const double* xs_dev, const double* ys_dev);
 
 // ---- ipd_dual.hip --------------------------------------------------------------------------
 // (the certificate itself is reached through the C ABI, ipd_apd_dual and ipd_apd_dual_dev: it reads the workspace

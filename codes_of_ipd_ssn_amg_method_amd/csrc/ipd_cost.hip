@@ -298,6 +298,16 @@ void finish_stats(ipd_ctx* ctx, const CostArgs& a, ipd_cost_stats* dst, ipd_cost
     ctx->fetch_bytes(dst, st, sizeof(ipd_cost_stats));
 }
 
+// scale = 1: the largest entry of the unscaled cost, from the build without a destination in the geometry of `a` (whose
+// partials and *dst it uses); *st receives that pass's statistics.  IPD_E_ARG when it is 0 or not finite.
+double cost_largest(ipd_ctx* ctx, int metric, const CostArgs& a, const double* xs_dev, const double* ys_dev,
+                    ipd_cost_stats* dst, ipd_cost_stats* st) {
+    launch_build(ctx, metric, a, xs_dev, ys_dev, nullptr);
+    finish_stats(ctx, a, dst, st);
+    IPD_REQUIRE(cost_scale_ok(st->max), IPD_E_ARG, "cost spec: scale = 1 and the largest entry is 0 or not finite");
+    return st->max;
+}
+
 void check_spec(const ipd_cost_spec* s) {
     const CostCheck ck = cost_spec_check(s->metric, s->dim, s->m, s->n, s->xs, s->ys, s->scale);
     IPD_REQUIRE(ck == COST_OK, ck == COST_SHAPE ? IPD_E_LIMIT : IPD_E_ARG, COST_CHECK_TEXT[ck]);
@@ -318,10 +328,7 @@ void cost_build_dev(ipd_ctx* ctx, const ipd_cost_spec* s, const double* xs_dev, 
     a.part = S.alloc<double>((size_t)a.g.nib * a.g.njg * CSC);
     ipd_cost_stats* dst = reinterpret_cast<ipd_cost_stats*>(S.alloc<double>(sizeof(ipd_cost_stats) / sizeof(double)));
     if (s->scale) {
-        launch_build(ctx, s->metric, a, xs_dev, ys_dev, nullptr);
-        finish_stats(ctx, a, dst, st);
-        IPD_REQUIRE(cost_scale_ok(st->max), IPD_E_ARG, "cost spec: scale = 1 and the largest entry is 0 or not finite");
-        a.denom = st->max;
+        a.denom = cost_largest(ctx, s->metric, a, xs_dev, ys_dev, dst, st);
         a.divide = 1;
     }
     launch_build(ctx, s->metric, a, xs_dev, ys_dev, c_dev);
@@ -340,14 +347,15 @@ void cost_build_dev(ipd_ctx* ctx, const ipd_cost_spec* s, const double* xs_dev, 
 
 // A checked specification -> c_dev (mn) and the statistics of what is stored.  The caller holds a CallScope;
 // the stream has been waited for when this returns (the scratch arrays are the next call's).
-void cost_from_points(ipd_ctx* ctx, const ipd_cost_spec* s, double* c_dev, ipd_cost_stats* st) {
+void cost_from_points(ipd_ctx* ctx, const ipd_cost_spec* s, double* c_dev, ipd_cost_stats* st,
+                      CostSrc* src = nullptr) {
     Arena& S = *ctx->scratch;
     const int m = (int)s->m, n = (int)s->n, d = s->dim;
     double* xs_dev = S.alloc<double>((size_t)m * d);
     double* ys_dev = S.alloc<double>((size_t)n * d);
     ctx->upload(xs_dev, s->xs, (size_t)m * d);
     ctx->upload(ys_dev, s->ys, (size_t)n * d);
-    cost_build_dev(ctx, s, xs_dev, ys_dev, c_dev, (reinterpret_cast<uintptr_t>(c_dev) & 15) == 0, st, nullptr);
+    cost_build_dev(ctx, s, xs_dev, ys_dev, c_dev, (reinterpret_cast<uintptr_t>(c_dev) & 15) == 0, st, src);
 }
 
 void fill_ones(ipd_ctx* ctx, size_t mn, double* phi_ones_dev) {
@@ -361,7 +369,39 @@ void note_spec(ipd_apd* h, const ipd_cost_spec* s) {
     h->cost_scale = s->scale;
 }
 
+// A stored workspace made from points keeps what the matrix-free one keeps, the (m+n)*dim coordinates in its arena and
+// the divider, for the calls that differentiate in the positions (ipd_point_grad.hip).  Its passes go on reading the
+// stored c: cost_free stays false and ipd_apd_cost_info answers what it answered.  `built`: what cost_build_dev left,
+// its coordinate pointers were the build's scratch.  The coordinates go up a second time, 8*(m+n)*dim bytes once per
+// create: the build runs inside apd_create_common's fill callback, which has no workspace to allocate from yet.
+void keep_points(ipd_ctx* ctx, ipd_apd* h, const ipd_cost_spec* s, const CostSrc& built) {
+    CallScope scope(ctx);
+    const size_t m = (size_t)s->m, n = (size_t)s->n, dim = (size_t)s->dim;
+    double* xs_dev = h->arena->alloc<double>(m * dim);
+    double* ys_dev = h->arena->alloc<double>(n * dim);
+    ctx->upload(xs_dev, s->xs, m * dim);
+    ctx->upload(ys_dev, s->ys, n * dim);   // (an upload has taken its bytes when it returns)
+    h->cost_src = built;
+    h->cost_src.xs = xs_dev;
+    h->cost_src.ys = ys_dev;
+}
+
 }  // namespace
+
+// The largest entry of the unscaled cost of device coordinates, the number by which k_cost_build divides under
+// scale = 1: the build without a destination (any dim: beyond COST_DT_MAX a statistics-only pass of the generic form).
+// A maximum does not depend on the order it is taken in, so the rows per lane do not matter.  IPD_E_ARG when it is 0 or
+// not finite.  The caller holds a CallScope; the stream has been waited for when this returns.
+double apd_cost_largest(ipd_ctx* ctx, int metric, int dim, int m, int n, const double* xs_dev, const double* ys_dev) {
+    Arena& S = *ctx->scratch;
+    CostArgs a{};
+    a.g = cost_geo(m, n, 1);
+    a.d = dim;
+    a.part = S.alloc<double>((size_t)a.g.nib * a.g.njg * CSC);
+    ipd_cost_stats* dst = reinterpret_cast<ipd_cost_stats*>(S.alloc<double>(sizeof(ipd_cost_stats) / sizeof(double)));
+    ipd_cost_stats st;
+    return cost_largest(ctx, metric, a, xs_dev, ys_dev, dst, &st);
+}
 
 // ---------------------------------------------------------------------------
 // C ABI
@@ -382,14 +422,21 @@ extern "C" int ipd_apd_create_points(ipd_ctx* ctx, const ipd_apd_data* d, const 
         IPD_REQUIRE(!d->c, IPD_E_ARG, "ipd_apd_create_points: c must be NULL (the cost comes from the points)");
         check_spec(s);
         IPD_REQUIRE(s->m == d->m && s->n == d->n, IPD_E_ARG, "ipd_apd_create_points: m, n of the spec and of the data differ");
+        CostSrc built{};
         const ApdCostFill fill = [&](double* c_dev, double* phi_ones_dev, ipd_cost_stats* st) {
             CallScope scope(ctx);
             if (phi_ones_dev) fill_ones(ctx, (size_t)s->m * (size_t)s->n, phi_ones_dev);
-            cost_from_points(ctx, s, c_dev, st);
+            cost_from_points(ctx, s, c_dev, st, &built);
         };
         ipd_apd* h = nullptr;
         apd_create_common(ctx, d, &fill, &h);
         note_spec(h, s);
+        try {
+            keep_points(ctx, h, s, built);
+        } catch (...) {
+            ipd_apd_destroy(h);
+            throw;
+        }
         *out = h;
     });
 }

@@ -796,6 +796,46 @@ typedef struct ipd_cost_info {
 } ipd_cost_info;
 int ipd_apd_cost_info(ipd_apd* h, ipd_cost_info* info);
 
+/* The gradient of the transport cost in the point positions, on the device.  With X what
+ * ipd_apd_plan returns at this tol (x(i,j) = u[i + j*m], kept when !(|x| <= tol), a NaN is kept; class 2:
+ * the x block of uk) and c the cost of two point clouds, the envelope theorem gives at an optimal -- or
+ * rounded feasible, ipd_apd_bracket with install = 1 -- plan
+ *   side = 0:  G(i,k) = sum_j X_ij * h_k(i,j),     G m x d as G[i + k*m],  w = X*1  (m entries)
+ *   side = 1:  G(j,k) = sum_i X_ij * (-h_k(i,j)),  G n x d as G[j + k*n],  w = X'*1 (n entries)
+ * -- the layouts of xs / ys -- with h_k = dc(xs_i, ys_j)/dxs(i,k), every step one IEEE operation, multiply
+ * and add separate, t_k = xs(i,k) - ys(j,k):
+ *   1  h_k = t_k + t_k
+ *   2  a = the entry of metric 2 (folded as the cost is, in ascending k); h_k = t_k / a when a > 0, else +0.0
+ *   3  h_k = +1.0, -1.0 or +0.0 by the sign of t_k
+ *   4  k* = the smallest k with |t_k| equal to the maximum; h_k* = the sign of t_k*, every other h_k = +0.0
+ * Where c is not differentiable (2: a == 0; 3: some t_k == 0; 4: the maximum attained by two coordinates, or
+ * 0) that is one subgradient; st->kinks counts the kept entries there, st->kept all kept entries.  scale = 1
+ * divides h_k by the largest unscaled entry (one division, applied last; st->denom, 1.0 without scale): the
+ * normalisation is held constant -- a stop-gradient -- and the divider is returned so that a caller can add the
+ * missing term.  A dropped entry contributes exactly +0.0.  The sums have a fixed shape that depends neither on
+ * d nor on how the components are split into passes, and use no atomics: two calls, and the two entries, give
+ * the same bits; side 0 adds a row's terms in ascending j within a group of 64 columns, then the groups in
+ * ascending order, each from +0.0.  c is never read: every form of workspace gives the same bits.
+ * s == NULL (xs_dev == ys_dev == NULL; metric, dim and scale are then ignored) takes the specification and the
+ * coordinates the workspace was made from (ipd_apd_create_points, ipd_apd_create_points_free); a workspace
+ * from a host c has none: IPD_E_ARG.  A given specification may be used with any workspace: s->m, s->n must
+ * be the workspace's, dim is 1 .. 16 on every form, everything ipd_cost_points_dev refuses is refused with its
+ * code (the device entry cannot look at device coordinates: they must be finite), and with scale = 1 the
+ * divider is computed on the device without storing a matrix (one more read-back; IPD_E_ARG when it is 0 or not
+ * finite).  IPD_E_ARG also for a NULL h or G, a side other than 0 or 1, tol negative or NaN, exactly one of
+ * xs_dev, ys_dev NULL.  After an error nothing of G, w, st is written.  w and st may be NULL.  The workspace
+ * is only read; scratch comes from the context's arena.  Both return when the result is complete.        */
+typedef struct ipd_grad_stats {
+    int64_t kept;     /* kept entries                                                   */
+    int64_t kinks;    /* kept entries at which c is not differentiable                  */
+    double denom;     /* the divider of scale = 1 (the largest unscaled entry), else 1.0 */
+} ipd_grad_stats;
+int ipd_apd_point_grad(ipd_apd* h, const ipd_cost_spec* s, double tol, int32_t side,
+                       double* G, double* w, ipd_grad_stats* st);             /* host arrays   */
+int ipd_apd_point_grad_dev(ipd_apd* h, int32_t metric, int32_t dim, int32_t scale,
+                           const double* xs_dev, const double* ys_dev, double tol, int32_t side,
+                           double* G_dev, double* w_dev, ipd_grad_stats* st); /* device arrays */
+
 /* Matrix-free level-1 operator.  If level 1 of `h` is exactly Hybrid_AMG's
  * rescaled operator Ae = bk1*Q0^2 + (Q0*T*Q0 + Q0*H0*Q0)/tk for these p, q, tk (checked entry by
  * entry against A_1's CSR values), the level-1 Gauss-Seidel sweeps read one BIT per entry (the
